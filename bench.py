@@ -12,9 +12,13 @@ construction).
 
     python bench.py --gpus N --steps K --warmup W
 
-prints ONE JSON line on rank 0.  With N = 1 and the default workload the line also carries
-"secondary": a few steps each of the other BASELINE.json configurations that fit one GPU
-(config3, config4, config2q, config5), every entry with its own roofline and cpu_baseline.
+prints ONE JSON line on rank 0.  ``--dump-outputs DIR`` also writes what the last timed step
+computed (for a partition: its flat export, the arrays a caller receives) as DIR/<name>.npy; the
+inputs depend on the arguments only, so two builds can be compared output for output.  The
+timed region is K steps of the workload and nothing else; with N = 1, the default workload and
+``--secondary`` the line also carries "secondary": a few steps each of the other BASELINE.json
+configurations that fit one GPU (config3, config4, config2q, config5) and the time-boxed
+config5_scale entry (600 s), every entry with its own roofline and cpu_baseline.
 
 For N > 1 it is launched by torch.distributed.run with one rank per GPU; every rank runs ONE
 launch of the persistent frontier kernel from the roots: the tree above a deal depth is grown
@@ -323,9 +327,11 @@ def parse_args(argv=None):
                     help='explicit: states evaluated per step')
     ap.add_argument('--secondary-cpu-seconds', type=float, default=6.,
                     help='CPU-baseline time of each entry of the "secondary" list')
+    ap.add_argument('--secondary', action='store_true',
+                    help='append "secondary": a few steps each of config3 / config4 / config2q / '
+                         'config5 and the config5_scale entry (~13 min in all, whatever --steps)')
     ap.add_argument('--no-secondary', action='store_true',
-                    help='headline only: skip the few steps of config3 / config4 / config2q / '
-                         'config5 that the default invocation appends as "secondary"')
+                    help='headline only (the default; overrides --secondary)')
     ap.add_argument('--regions', type=int, default=0,
                     help='config5: regions to close per rank before a step stops (default: none, the '
                          'cells are grown to completion)')
@@ -376,7 +382,59 @@ def parse_args(argv=None):
                          'shared-block kernels), 0 = level-synchronous sweeps')
     ap.add_argument('--decide-full', action='store_true',
                     help='solve the suboptimality-test LPs to full accuracy (no sign-only stop)')
-    return ap.parse_args(argv)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step computed to DIR/<name>.npy '
+                         '(float64, <= 64 MB in all; a seeded sample of larger outputs) so that two '
+                         'builds can be compared output for output')
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+DUMP_BYTES = 56 << 20       # sampled arrays of --dump-outputs; the rest is a few small arrays
+
+
+def _dump_sample(n, per_item_bytes, seed=0):
+    """Indices of the items --dump-outputs writes: all of them if they fit DUMP_BYTES, else a
+    sorted sample drawn with a fixed seed."""
+    k = max(1, DUMP_BYTES // max(per_item_bytes, 1))
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, k, replace=False))
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (integers and flags are exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, 'outputs of %d bytes exceed 64 MB' % total
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
+def dump_flat_tree(out_dir, flat, step_info):
+    """--dump-outputs of a partition: the flat export a caller receives (engine.FlatTree; node k of
+    the breadth-first numbering) -- every node, or a seeded sample of them -- plus the counts of
+    the whole tree and (step_info: one rank) of the timed step it stands for."""
+    K = flat.n_nodes
+    per_node = 8 * (flat.vertices[0].size + flat.vertex_costs[0].size +
+                    flat.vertex_inputs[0].size + 6)
+    idx = _dump_sample(K, per_node)
+    leaf = flat.left < 0
+    arrays = {
+        'tree_counts': [K, int(leaf.sum()), int((leaf & ((flat.flags & 1) > 0)).sum())],
+        'node_index': idx, 'vertices': flat.vertices[idx], 'left': flat.left[idx],
+        'right': flat.right[idx], 'delta_idx': flat.delta_idx[idx],
+        'vertex_costs': flat.vertex_costs[idx], 'vertex_inputs': flat.vertex_inputs[idx],
+        'flags': flat.flags[idx],
+        # the sign of t* is the node's decision; its value comes from whichever solve decided the
+        # node first in the persistent kernel and varies from run to run
+        'tstar_nonnegative': flat.tstar[idx] >= 0}
+    if step_info is not None:
+        arrays['step_counts'] = [step_info['n_nodes'], step_info['n_closed']]
+    dump_outputs(out_dir, arrays)
 
 
 
@@ -528,6 +586,19 @@ def measure(args, ctx):
             with_export()
         ms_with_export = 1e3 * (time.perf_counter() - t1) / reps
         ms_export = ms_with_export - 1e3 * elapsed / args.steps
+    # --dump-outputs: the tree of the timed steps, exported.  A node's fate depends on its own
+    # record only, so the partition grown again here from the same roots IS the last step's tree
+    # (N > 1: the tree the ranks grew together); outside every timed region
+    if args.dump_outputs and rank == 0:
+        flat = gp.partition(roots, action='ecc', max_nodes=args.max_nodes, export=True,
+                            with_volume=False, engine=args.engine, max_depth=args.max_depth)
+        if world == 1 and (flat.info['n_nodes'], flat.info['n_closed']) != \
+                (infos[-1]['n_nodes'], infos[-1]['n_closed']):
+            sys.stderr.write('bench.py: the exported tree (%d nodes, %d closed) is not the last '
+                             'step\'s (%d, %d)\n' % (flat.info['n_nodes'], flat.info['n_closed'],
+                                                      infos[-1]['n_nodes'], infos[-1]['n_closed']))
+        dump_flat_tree(args.dump_outputs, flat, infos[-1] if world == 1 else None)
+        del flat
     # N > 1: the regions of all ranks together must be the regions of ONE unsharded partition (a
     # node's fate depends on its own record only, so the tree does not depend on who grows which
     # part of it): rank 0 grows the whole tree once more, outside the timed region, and the line
@@ -1358,6 +1429,23 @@ def measure_config5(args, ctx):
                                                        cell_vertices)
         else:
             out['cpu_baseline'] = None
+    if args.dump_outputs and rank == 0:
+        # this rank's trees of the last step, root cells in a fixed order (the handles of
+        # --host-streams finish them in any order): every leaf, or a seeded sample of them
+        trees = sorted(runs[-1][1], key=lambda t: tuple(np.asarray(t.data.vertices).ravel()))
+        leaves = [(k, nd, loc) for k, t in enumerate(trees) for nd, loc in t.leaves()]
+        nv = np.asarray(trees[0].data.vertices).size if trees else 0
+        idx = _dump_sample(len(leaves), 8 * (nv + 4))
+        dump_outputs(args.dump_outputs, {
+            'root_vertices': [np.asarray(t.data.vertices) for t in trees],
+            'leaf_counts': [len(leaves), sum(bool(nd.data.is_epsilon_suboptimal)
+                                             for _, nd, _ in leaves)],
+            'leaf_index': idx,
+            'leaf_root': [leaves[i][0] for i in idx],
+            'leaf_depth': [len(leaves[i][2]) for i in idx],
+            'leaf_closed': [bool(leaves[i][1].data.is_epsilon_suboptimal) for i in idx],
+            'leaf_vertices': np.reshape([np.ravel(leaves[i][1].data.vertices) for i in idx],
+                                        (len(idx), nv))})
     for nat in natives:
         nat.close()
     orc.close()
@@ -1396,6 +1484,7 @@ def measure_explicit(args, ctx):
     out_cases = []
     n_q = args.queries
     rng = np.random.default_rng(args.seed)
+    outputs = {}
 
     def run_case(name, flat, half, note):
         ex = explicit.ExplicitMPC(flat, device=device_index)
@@ -1409,6 +1498,12 @@ def measure_explicit(args, ctx):
             secs.append(ks)
         ks = float(np.mean(secs))
         p, n_u = ex.p, ex.n_u
+        if args.dump_outputs:
+            # the last step's inputs and leaves (a seeded sample of the queries: two cases share
+            # the budget)
+            idx = _dump_sample(n_q, 2 * 8 * (n_u + 2))
+            outputs.update({name + '_query_index': idx, name + '_u': u[idx],
+                            name + '_leaf': leaf[idx]})
         rec_bytes = 8 * (((p + p * p + 7) // 8) * 8)
         # algorithmic bytes: one record per containment test, the child pair per level, the leaf's
         # record + vertex inputs, the query in and the input out
@@ -1474,6 +1569,8 @@ def measure_explicit(args, ctx):
                               'the %d Delaunay roots of the p = 8 box of configs[4] as leaves: root '
                               'location only (one wavefront per query, 64 roots per step)' % K))
     head = out_cases[0]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs)
     return {
         'metric': 'explicit-law evaluations/s (SURVEY 8 f2; NOT the headline metric of BASELINE.json)',
         'value': head['evaluations_per_s'], 'unit': 'evaluations/s', 'n_gpus': 1,
@@ -1528,6 +1625,7 @@ def secondary_line(args, ctx, workload, steps, warmup):
     a.driver = 'native'
     a.order, a.max_visits, a.round_cap = 'lcss-first', None, 4096
     a.status_dir = None
+    a.dump_outputs = None           # the outputs are the headline workload's
     a.engine, a.solver, a.decide_full = 1, 2, False
     a.no_mid_first = a.no_inherit_witness = False
     t0 = time.perf_counter()
@@ -1566,8 +1664,8 @@ def main():
     try:
         out = (measure_config5 if args.workload == 'config5' else
                measure_explicit if args.workload == 'explicit' else measure)(args, ctx)
-        if (rank == 0 and world == 1 and args.workload == 'config2' and not args.no_secondary
-                and not args.status_dir):
+        if (rank == 0 and world == 1 and args.workload == 'config2' and args.secondary and
+                not args.no_secondary and not args.status_dir):
             out['secondary'] = [secondary_line(args, ctx, *w) for w in SECONDARY]
         if rank == 0:
             print(json.dumps(out))

@@ -590,6 +590,10 @@ def _worker_roots_stealing(rank, world, port, out_dir):
     trees = [Tree(NodeData(vertices=np.array(R))) for R in roots]
 
     def split_batch(R):
+        if rank == 0:
+            # the busy rank is the slow one: it still holds pending cells each time rank 1 is
+            # done with a parcel and asks again, however fast or loaded the host is
+            time.sleep(0.1)
         out = [geometry.split_along_longest_edge(r) for r in R]
         return (np.array([o[0] for o in out]), np.array([o[1] for o in out]),
                 np.array([o[2] for o in out], dtype=np.int32))

@@ -29,7 +29,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
                                 'tools'))
 
 
-def test_nodes_of_a_native_tree_against_one_milp_per_oracle_call():
+def test_nodes_of_a_native_tree_against_one_milp_per_oracle_call(monkeypatch):
     import config5_independent_check as c5
     from explicit_hybrid_mpc_amd import bnb, bnb_frontier, examples, frontier
     from explicit_hybrid_mpc_amd import tools as ehm_tools
@@ -77,10 +77,14 @@ def test_nodes_of_a_native_tree_against_one_milp_per_oracle_call():
         jobs.append(job)
         meta.append((loc, kind, leaf))
     # the checks are independent CPU work (HiGHS; the device handle is closed): one process each,
-    # the lcss splits -- minutes of branch and bound each -- first
+    # the lcss splits -- minutes of branch and bound each -- first.  Fresh processes (spawn, as
+    # tools/config5_independent_check.py does): a fork of this one would inherit the HIP runtime's
+    # and the thread pools' threads mid-flight; one BLAS thread each, eight processes share the host
     import multiprocessing as mp
+    for var in ('OMP_NUM_THREADS', 'OPENBLAS_NUM_THREADS', 'MKL_NUM_THREADS'):
+        monkeypatch.setenv(var, '1')
     order = sorted(range(len(jobs)), key=lambda k: -jobs[k][1])
-    with mp.get_context('fork').Pool(min(len(jobs), os.cpu_count() or 1)) as pool:
+    with mp.get_context('spawn').Pool(min(len(jobs), os.cpu_count() or 1)) as pool:
         results = pool.map(c5._check_one, [jobs[k] for k in order], chunksize=1)
     for k, res in zip(order, results):
         loc, kind, leaf = meta[k]

@@ -136,17 +136,18 @@ def test_reference_format_pickle_roundtrip(tmp_path):
     assert tree.Tree.__module__ == 'explicit_hybrid_mpc_amd.tree'
 
 
-REFERENCE_LIB = '/root/reference/lib'
-
-
-@pytest.mark.skipif(not os.path.exists(os.path.join(REFERENCE_LIB, 'tree.py')),
-                    reason='the reference tree is only present in the build container')
 def test_reference_tree_module_loads_the_pickle(tmp_path):
-    """f1 with the REAL consumer: the unmodified /root/reference/lib/tree.py (imports cleanly,
-    SURVEY 8c) unpickles what ``tree_io.dump_reference`` wrote -- a deep Delaunay-like spine and a
-    grown cell -- into ITS classes, and its own methods (``is_leaf``, attribute absence of
-    lib/tree.py:34-39, 86-95) read the result.  A tree pickled by the reference's classes comes
-    back through ``tree_io.load_reference``."""
+    """f1 against the REAL consumer's classes, as recorded from the unmodified lib/tree.py by
+    tests/golden/make_reference_pickles.py: what ``tree_io.dump_reference`` writes -- a deep
+    Delaunay-like spine and a grown cell -- names exactly the consumer's module and classes, and
+    every object carries the attributes one of its constructors leaves (a leaf / a grown Tree, a
+    NodeData with optional members), so its own methods (``is_leaf``, attribute absence of
+    lib/tree.py:34-39, 86-95) read the result.  A tree pickled by the reference's classes
+    (tests/golden/reference_tree.pkl) comes back through ``tree_io.load_reference``."""
+    import json
+    import types
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+    layout = json.load(open(os.path.join(golden, 'reference_tree_layout.json')))
     root = tree.Tree(tree.NodeData(np.zeros((3, 2))))
     cursor = root
     for k in range(1500):
@@ -157,26 +158,49 @@ def test_reference_tree_module_loads_the_pickle(tmp_path):
     root.left.grow(tree.NodeData(np.eye(3, 2)), tree.NodeData(np.eye(3, 2) * 2.))
     root.left.left.data.is_epsilon_suboptimal = True
     path = str(tmp_path / 'tree.pkl')
-    back_path = str(tmp_path / 'from_reference.pkl')
     tree_io.dump_reference(root, path)
-    code = ("import sys, pickle; sys.dont_write_bytecode = True; sys.setrecursionlimit(100000);"
-            "sys.path.insert(0, %r); import tree;"
-            "assert tree.__file__.startswith(%r), tree.__file__;"
-            "t = pickle.load(open(%r, 'rb'));"
-            "assert type(t) is tree.Tree and type(t.data) is tree.NodeData;"
-            "assert not t.is_leaf() and t.left.left.is_leaf();"
-            "assert t.left.left.data.is_epsilon_suboptimal and not t.left.right.data.is_epsilon_suboptimal;"
-            "assert hasattr(t.left.data, 'commutation') and not hasattr(t.data, 'commutation');"
-            "n = 0; c = t\n"
-            "while not c.right.is_leaf(): c = c.right; n += 1\n"
-            "assert c.data is None and c.right.data.vertices[0, 0] == -1.\n"
-            "r = tree.Tree(tree.NodeData(vertices=t.left.data.vertices, commutation=t.left.data.commutation))\n"
-            "r.grow(tree.NodeData(vertices=t.left.left.data.vertices), tree.NodeData(vertices=t.left.right.data.vertices))\n"
-            "pickle.dump(r, open(%r, 'wb'))\n"
-            "print(n)") % (REFERENCE_LIB, REFERENCE_LIB, path, back_path)
-    out = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True)
-    assert out.stdout.split() == ['1499'], out.stderr
-    back = tree_io.load_reference(back_path)
+    # the consumer's module as the pickle sees it: its classes, no behaviour of their own
+    consumer = types.ModuleType(layout['module'])
+    for name in layout['classes']:
+        setattr(consumer, name, type(name, (), {'__module__': layout['module']}))
+    Tree, NodeData = (getattr(consumer, name) for name in layout['classes'])
+    saved = sys.modules.get(layout['module'])
+    sys.modules[layout['module']] = consumer
+    limit = sys.getrecursionlimit()
+    try:
+        sys.setrecursionlimit(100000)
+        t = pickle.load(open(path, 'rb'))
+    finally:
+        sys.setrecursionlimit(limit)
+        if saved is None:
+            del sys.modules[layout['module']]
+        else:
+            sys.modules[layout['module']] = saved
+    required = set(layout['node_data_required'])
+    optional = set(layout['node_data_optional'])
+
+    def is_leaf(node):
+        attrs = sorted(vars(node))
+        assert attrs in (layout['tree_leaf'], layout['tree_inner']), attrs
+        return attrs == layout['tree_leaf']
+    stack = [t]
+    while stack:
+        node = stack.pop()
+        assert type(node) is Tree
+        if node.data is not None:
+            assert type(node.data) is NodeData
+            assert required <= set(vars(node.data)) <= required | optional, sorted(vars(node.data))
+        if not is_leaf(node):
+            stack += [node.left, node.right]
+    assert not is_leaf(t) and is_leaf(t.left.left)
+    assert t.left.left.data.is_epsilon_suboptimal and not t.left.right.data.is_epsilon_suboptimal
+    assert hasattr(t.left.data, 'commutation') and not hasattr(t.data, 'commutation')
+    n, c = 0, t
+    while not is_leaf(c.right):
+        c = c.right
+        n += 1
+    assert n == 1499 and c.data is None and c.right.data.vertices[0, 0] == -1.
+    back = tree_io.load_reference(os.path.join(golden, 'reference_tree.pkl'))
     assert isinstance(back, tree.Tree) and isinstance(back.data, tree.NodeData)
     assert np.array_equal(back.data.commutation, np.ones(3)) and not back.is_leaf()
     assert np.array_equal(back.left.data.vertices, np.eye(3, 2))

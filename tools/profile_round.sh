@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 export PYTHONPATH=$R
 O=$R/gpurun_out/round
 mkdir -p $O
-python $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
+python $R/bench.py --secondary > $O/bench_default.json 2> $O/bench_default.err
 tail -1 $O/bench_default.err
 RND=${RND:-r6}
 BENCH_ARGS="" bash $R/tools/profile.sh ${RND}_bench
