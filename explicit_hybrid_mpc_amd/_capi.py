@@ -38,7 +38,7 @@ EXPORTED = [
     'ehm_feas_all_batch', 'ehm_lcss_batch', 'ehm_partition_movable',
     'ehm_problem_update_blocks', 'ehm_simplex_idx_batch', 'ehm_point_idx_batch',
     'ehm_abi_sizes', 'ehm_solver_phase_ticks', 'ehm_problem_layout',
-    'ehm_host_alloc', 'ehm_host_free',
+    'ehm_host_alloc', 'ehm_host_free', 'ehm_explicit_set_plant', 'ehm_explicit_rollout',
 ]
 
 
@@ -246,6 +246,9 @@ def load(build_if_missing=True):
                                         ctypes.POINTER(vp)]
     lib.ehm_explicit_eval_batch.argtypes = [vp, i64, vp, vp, vp, vp, vp]
     lib.ehm_explicit_destroy.argtypes = [vp]
+    lib.ehm_explicit_set_plant.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp,
+                                           vp, i32, vp, vp]
+    lib.ehm_explicit_rollout.argtypes = [vp, i64, i32, vp, vp, vp, ctypes.c_double] + [vp] * 10
     lib.ehm_explicit_last_error.restype = ctypes.c_char_p
     lib.ehm_tree_info_get.argtypes = [vp, ctypes.POINTER(TreeInfo)]
     lib.ehm_tree_export.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -219,6 +219,299 @@ __global__ void k_explicit_eval(DevExplicit E, long long n, const double* __rest
     if (depth_out) depth_out[q] = visited;
 }
 
+// ---- fused closed-loop rollout (lib/simulator.py:124-188 for batches of trajectories) --------
+//
+// One thread per trajectory, the T steps inside the kernel: measure z = x + v (no error at t = 0,
+// lib/simulator.py:168), locate z with the walk of k_explicit_eval, stop if z is outside the leaf
+// (weight < -tol_exit), interpolate u as k_explicit_eval does, step the plant in the step-0 mode of
+// the leaf's commutation, accumulate stage cost / input 2-norm / worst constraint value.  Templated
+// on (p, n_u) so that state, weights and inputs live in VGPRs; the plant sits in LDS.
+#define EHM_R_MAX_NU 4
+#define EHM_R_MAX_MODES 4
+#define EHM_R_MAX_D 8
+#define EHM_R_MAX_ROWS 256       // constraint rows Gx, and mode-region rows of all modes together
+
+struct DevPlant {
+    const double* data;      // [total] doubles, the offsets below
+    int total, n_modes, n_d, n_g, cost_kind;          // cost_kind 0: inf-norm, 1: quadratic
+    int oA, oB, ow, oE, oH, oh, oG, og, oQ, oR;
+    int row0[EHM_R_MAX_MODES + 1];                    // region rows of mode m: row0[m] .. row0[m+1]
+};
+
+struct RollArgs {
+    long long n;
+    int T;
+    double tol_exit;
+    const double *x0, *d, *v;
+    const int32_t* node_mode;
+    const int32_t* nbr;      // root face adjacency (long spines) or nullptr
+    double *x_traj, *u_traj;
+    int32_t* leaf_traj;
+    double *x_final, *cost, *u_norm, *max_viol;
+    int32_t *steps, *status;
+};
+
+// the sums of `contains` / `weights` with p fixed at compile time.  Kept outside any fp-contract
+// pragma, as those two are: the compiler fuses the same products into the same FMAs, so the
+// containment verdicts and weights are bit-identical to k_explicit_eval's.
+template <int P>
+__device__ __forceinline__ bool contains_t(const DevExplicit& E, long long k, const double* x) {
+    const double* r = E.rec + (size_t)k * E.rec_stride;
+    const double eps = 2.220446049250313e-16;
+    double d[P];
+#pragma unroll
+    for (int c = 0; c < P; ++c) d[c] = x[c] - r[c];
+    double s = 0.0;
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+        double a = 0.0;
+#pragma unroll
+        for (int c = 0; c < P; ++c) a += r[P + q * P + c] * d[c];
+        if (!((a >= -eps) && (a <= 1.0 + eps))) return false;
+        s += a;
+    }
+    const double a0 = 1.0 - s;
+    return (a0 >= -eps) && (a0 <= 1.0 + eps);
+}
+
+template <int P>
+__device__ __forceinline__ void weights_t(const DevExplicit& E, long long k, const double* x,
+                                          double* alpha, double& alpha0) {
+    const double* r = E.rec + (size_t)k * E.rec_stride;
+    double d[P];
+#pragma unroll
+    for (int c = 0; c < P; ++c) d[c] = x[c] - r[c];
+    double s = 0.0;
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+        double a = 0.0;
+#pragma unroll
+        for (int c = 0; c < P; ++c) a += r[P + q * P + c] * d[c];
+        alpha[q] = a;
+        s += a;
+    }
+    alpha0 = 1.0 - s;
+}
+
+template <int P, int NU>
+__global__ __launch_bounds__(256) void k_explicit_rollout(DevExplicit E, DevPlant PL, RollArgs R) {
+#pragma clang fp contract(off)
+    extern __shared__ double sh[];
+    for (int i = threadIdx.x; i < PL.total; i += blockDim.x) sh[i] = PL.data[i];
+    __syncthreads();
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= R.n) return;
+    const long long n = R.n;
+    const double* sQ = sh + PL.oQ;
+    const double* sR = sh + PL.oR;
+    const double* sG = sh + PL.oG;
+    const double* sg = sh + PL.og;
+    const double* sE = sh + PL.oE;
+    double x[P], z[P], alpha[P], u[NU], xn[P], a0;
+#pragma unroll
+    for (int c = 0; c < P; ++c) x[c] = R.x0[q * P + c];
+    if (R.x_traj)
+#pragma unroll
+        for (int c = 0; c < P; ++c) R.x_traj[(size_t)q * P + c] = x[c];
+    double cost = 0.0, unorm = 0.0, maxv = -__builtin_inf();
+    int status = 0, t = 0;
+    int kr = (int)(q % E.n_roots);          // warm start of the root locator: the last step's root
+    for (; t < R.T; ++t) {
+        // measure
+        if (R.v && t > 0) {
+#pragma unroll
+            for (int c = 0; c < P; ++c) z[c] = x[c] + R.v[((size_t)t * n + q) * P + c];
+        } else {
+#pragma unroll
+            for (int c = 0; c < P; ++c) z[c] = x[c];
+        }
+        // locate: the spine (visibility walk from the last root where the spine is long, the
+        // serial walk wherever that walk gives up), then left iff inside the left child
+        long long k = E.n_roots - 1;
+        bool found = false;
+        if (R.nbr) {
+            int kw = kr;
+            for (int step = 0; step < EHM_X_STEPS; ++step) {
+                weights_t<P>(E, kw, z, alpha, a0);
+                double lo = a0;
+                int at = 0;
+#pragma unroll
+                for (int i = 0; i < P; ++i)
+                    if (alpha[i] < lo) {
+                        lo = alpha[i];
+                        at = i + 1;
+                    }
+                if (lo > EHM_X_STRICT) {
+                    found = true;
+                    break;
+                }
+                if (!(lo >= -EHM_X_STRICT)) {
+                    const int k2 = R.nbr[(size_t)kw * (P + 1) + at];
+                    if (k2 < 0) break;
+                    kw = k2;
+                } else {
+                    break;
+                }
+            }
+            if (found) k = kw;
+        }
+        if (!found)
+            for (int r = 0; r + 1 < E.n_roots; ++r)
+                if (contains_t<P>(E, r, z)) {
+                    k = r;
+                    break;
+                }
+        kr = (int)k;
+        for (;;) {
+            const int2 ch = E.child[k];
+            if (ch.x < 0) break;
+            k = contains_t<P>(E, ch.x, z) ? ch.x : ch.y;
+        }
+        // exit test: the walk ends in a leaf even for states outside the partitioned set
+        weights_t<P>(E, k, z, alpha, a0);
+        bool inside = a0 >= -R.tol_exit;
+#pragma unroll
+        for (int i = 0; i < P; ++i) inside = inside && (alpha[i] >= -R.tol_exit);
+        if (!inside) {
+            status = 1;
+            break;
+        }
+        // interpolate (the sums of k_explicit_eval)
+        const double* vi = E.vinput + (size_t)k * (P + 1) * NU;
+#pragma unroll
+        for (int c = 0; c < NU; ++c) {
+            double a = a0 * vi[c];
+#pragma unroll
+            for (int i = 0; i < P; ++i) a += vi[(i + 1) * NU + c] * alpha[i];
+            u[c] = a;
+        }
+        // the mode the leaf's commutation applies at step 0, and its region
+        const int m = R.node_mode[k];
+        if (m < 0 || m >= PL.n_modes) {
+            status = 3;
+            break;
+        }
+        bool in_region = true;
+        for (int r = PL.row0[m]; r < PL.row0[m + 1]; ++r) {
+            double s = 0.0;
+#pragma unroll
+            for (int c = 0; c < P; ++c) s += sh[PL.oH + r * P + c] * x[c];
+            in_region = in_region && (s <= sh[PL.oh + r] + R.tol_exit);
+        }
+        if (!in_region) {
+            status = 2;
+            break;
+        }
+        if (R.u_traj)
+#pragma unroll
+            for (int c = 0; c < NU; ++c) R.u_traj[((size_t)t * n + q) * NU + c] = u[c];
+        if (R.leaf_traj) R.leaf_traj[(size_t)t * n + q] = (int32_t)k;
+        // stage cost and input 2-norm
+        double su = 0.0;
+#pragma unroll
+        for (int c = 0; c < NU; ++c) su += u[c] * u[c];
+        unorm += sqrt(su);
+        if (PL.cost_kind == 0) {
+            double qx = 0.0, ru = 0.0;
+#pragma unroll
+            for (int i = 0; i < P; ++i) {
+                double s = 0.0;
+#pragma unroll
+                for (int c = 0; c < P; ++c) s += sQ[i * P + c] * x[c];
+                qx = fmax(qx, fabs(s));
+            }
+#pragma unroll
+            for (int i = 0; i < NU; ++i) {
+                double s = 0.0;
+#pragma unroll
+                for (int c = 0; c < NU; ++c) s += sR[i * NU + c] * u[c];
+                ru = fmax(ru, fabs(s));
+            }
+            cost += qx + ru;
+        } else {
+            double s = 0.0;
+#pragma unroll
+            for (int i = 0; i < P; ++i) {
+                double r = 0.0;
+#pragma unroll
+                for (int c = 0; c < P; ++c) r += sQ[i * P + c] * x[c];
+                s += x[i] * r;
+            }
+#pragma unroll
+            for (int i = 0; i < NU; ++i) {
+                double r = 0.0;
+#pragma unroll
+                for (int c = 0; c < NU; ++c) r += sR[i * NU + c] * u[c];
+                s += u[i] * r;
+            }
+            cost += s;
+        }
+        // plant step x+ = A_m x + B_m u + w_m + E d
+        const double* sA = sh + PL.oA + m * P * P;
+        const double* sB = sh + PL.oB + m * P * NU;
+        const double* sw = sh + PL.ow + m * P;
+        const double* dt = R.d ? R.d + ((size_t)t * n + q) * PL.n_d : nullptr;
+#pragma unroll
+        for (int i = 0; i < P; ++i) {
+            double s = 0.0;
+#pragma unroll
+            for (int c = 0; c < P; ++c) s += sA[i * P + c] * x[c];
+#pragma unroll
+            for (int c = 0; c < NU; ++c) s += sB[i * NU + c] * u[c];
+            s += sw[i];
+            if (dt)
+                for (int j = 0; j < PL.n_d; ++j) s += sE[i * PL.n_d + j] * dt[j];
+            xn[i] = s;
+        }
+        for (int j = 0; j < PL.n_g; ++j) {
+            double s = 0.0;
+#pragma unroll
+            for (int c = 0; c < P; ++c) s += sG[j * P + c] * xn[c];
+            maxv = fmax(maxv, s - sg[j]);
+        }
+#pragma unroll
+        for (int c = 0; c < P; ++c) x[c] = xn[c];
+        if (R.x_traj)
+#pragma unroll
+            for (int c = 0; c < P; ++c) R.x_traj[((size_t)(t + 1) * n + q) * P + c] = x[c];
+    }
+    // the records after a stop: NaN states / inputs, leaf -1
+    const double nan = __builtin_nan("");
+    for (int s = t; s < R.T; ++s) {
+        if (R.x_traj)
+#pragma unroll
+            for (int c = 0; c < P; ++c) R.x_traj[((size_t)(s + 1) * n + q) * P + c] = nan;
+        if (R.u_traj)
+#pragma unroll
+            for (int c = 0; c < NU; ++c) R.u_traj[((size_t)s * n + q) * NU + c] = nan;
+        if (R.leaf_traj) R.leaf_traj[(size_t)s * n + q] = -1;
+    }
+#pragma unroll
+    for (int c = 0; c < P; ++c) R.x_final[q * P + c] = x[c];
+    R.steps[q] = t;
+    R.status[q] = status;
+    R.cost[q] = cost;
+    R.u_norm[q] = unorm;
+    R.max_viol[q] = maxv;
+}
+
+typedef void (*rollout_fn)(DevExplicit, DevPlant, RollArgs);
+#define EHM_R_NU(P) &k_explicit_rollout<P, 1>, &k_explicit_rollout<P, 2>, \
+                    &k_explicit_rollout<P, 3>, &k_explicit_rollout<P, 4>
+const rollout_fn k_rollout_table[EHM_XP][EHM_R_MAX_NU] = {
+    {EHM_R_NU(1)}, {EHM_R_NU(2)}, {EHM_R_NU(3)}, {EHM_R_NU(4)},
+    {EHM_R_NU(5)}, {EHM_R_NU(6)}, {EHM_R_NU(7)}, {EHM_R_NU(8)}};
+#undef EHM_R_NU
+
+// EHM_EXPLICIT_LOCATE=0 in the environment: the reference's serial walk for every state
+bool locate_off() {
+    static const bool off = [] {
+        const char* e = getenv("EHM_EXPLICIT_LOCATE");
+        return e && atoi(e) == 0;
+    }();
+    return off;
+}
+
 thread_local std::string x_err;
 int xfail(int code, const char* fmt, ...) {
     char buf[512];
@@ -238,6 +531,8 @@ struct ehm_explicit {
     void *rec = nullptr, *child = nullptr, *vinput = nullptr;
     void *x = nullptr, *u = nullptr, *leaf = nullptr, *depth = nullptr, *root = nullptr;
     void* nbr = nullptr;        // [n_roots][p+1] root across the face opposite vertex i (-1: hull)
+    void *plant = nullptr, *node_mode = nullptr;     // ehm_explicit_set_plant
+    DevPlant pl{};
     size_t cap = 0;
     hipStream_t stream = nullptr;
 };
@@ -249,7 +544,8 @@ const char* ehm_explicit_last_error(void) { return x_err.c_str(); }
 int ehm_explicit_destroy(ehm_explicit* E) {
     if (!E) return EHM_OK;
     (void)hipSetDevice(E->device);
-    for (void* p : {E->rec, E->child, E->vinput, E->x, E->u, E->leaf, E->depth, E->root, E->nbr})
+    for (void* p : {E->rec, E->child, E->vinput, E->x, E->u, E->leaf, E->depth, E->root, E->nbr,
+                    E->plant, E->node_mode})
         if (p) (void)hipFree(p);
     if (E->stream) (void)hipStreamDestroy(E->stream);
     delete E;
@@ -385,13 +681,9 @@ int ehm_explicit_eval_batch(ehm_explicit* E, int64_t n, const double* x, double*
     Y_TRY(hipMemcpyAsync(E->x, x, (size_t)n * p * sizeof(double), hipMemcpyHostToDevice,
                          E->stream));
     (void)hipEventRecord(e0, E->stream);
-    // long spines: the visibility walk over the roots finds the root first (EHM_EXPLICIT_LOCATE=0:
-    // the reference's serial walk for every state)
-    static const int locate_off = [] {
-        const char* e = getenv("EHM_EXPLICIT_LOCATE");
-        return (e && atoi(e) == 0) ? 1 : 0;
-    }();
-    const bool locate = E->nbr && !locate_off;
+    // long spines: the visibility walk over the roots finds the root first (locate_off: the
+    // reference's serial walk for every state)
+    const bool locate = E->nbr && !locate_off();
     if (locate)
         hipLaunchKernelGGL(k_explicit_locate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                            E->stream, E->d, (long long)n, (const double*)E->x,
@@ -409,6 +701,191 @@ int ehm_explicit_eval_batch(ehm_explicit* E, int64_t n, const double* x, double*
                              E->stream));
     if (visited)
         Y_TRY(hipMemcpyAsync(visited, E->depth, (size_t)n * sizeof(int32_t),
+                             hipMemcpyDeviceToHost, E->stream));
+    Y_TRY(hipStreamSynchronize(E->stream));
+    if (kernel_seconds) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        *kernel_seconds = ms * 1e-3;
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    return EHM_OK;
+}
+
+int ehm_explicit_set_plant(ehm_explicit* E, int32_t n_modes, const double* A, const double* B,
+                           const double* w, int32_t n_d, const double* Emat,
+                           const int32_t* region_rows, const double* H, const double* h,
+                           int32_t n_g, const double* Gx, const double* gx,
+                           const int32_t* node_mode, int32_t cost_kind, const double* Q,
+                           const double* R) {
+    if (!E || !A || !B || !w || !node_mode || !Q || !R)
+        return xfail(EHM_E_INVALID, "set_plant: a required array is NULL");
+    if (n_modes < 1 || n_modes > EHM_R_MAX_MODES)
+        return xfail(EHM_E_INVALID, "set_plant: %d modes (1..%d)", (int)n_modes,
+                     EHM_R_MAX_MODES);
+    if (n_d < 0 || n_d > EHM_R_MAX_D || (n_d > 0 && !Emat))
+        return xfail(EHM_E_INVALID, "set_plant: n_d = %d (0..%d, E needed if > 0)", (int)n_d,
+                     EHM_R_MAX_D);
+    if (n_g < 0 || n_g > EHM_R_MAX_ROWS || (n_g > 0 && (!Gx || !gx)))
+        return xfail(EHM_E_INVALID, "set_plant: n_g = %d (0..%d)", (int)n_g, EHM_R_MAX_ROWS);
+    if (cost_kind != 0 && cost_kind != 1)
+        return xfail(EHM_E_INVALID, "set_plant: cost_kind %d (0 inf-norm, 1 quadratic)",
+                     (int)cost_kind);
+    const int p = E->d.p, n_u = E->d.n_u;
+    if (n_u > EHM_R_MAX_NU)
+        return xfail(EHM_E_INVALID, "set_plant: n_u = %d, the rollout takes at most %d inputs",
+                     n_u, EHM_R_MAX_NU);
+    DevPlant pl{};
+    pl.n_modes = n_modes;
+    pl.n_d = n_d;
+    pl.n_g = n_g;
+    pl.cost_kind = cost_kind;
+    int rows = 0;
+    for (int m = 0; m < n_modes; ++m) {
+        const int r = region_rows ? region_rows[m] : 0;
+        if (r < 0) return xfail(EHM_E_INVALID, "set_plant: mode %d has %d region rows", m, r);
+        pl.row0[m] = rows;
+        rows += r;
+    }
+    if (rows > EHM_R_MAX_ROWS || (rows > 0 && (!H || !h)))
+        return xfail(EHM_E_INVALID, "set_plant: %d mode-region rows (0..%d)", rows,
+                     EHM_R_MAX_ROWS);
+    for (int m = n_modes; m <= EHM_R_MAX_MODES; ++m) pl.row0[m] = rows;
+    std::vector<double> buf;
+    auto put = [&](const double* src, size_t cnt) {
+        const int off = (int)buf.size();
+        if (src) buf.insert(buf.end(), src, src + cnt);
+        else buf.insert(buf.end(), cnt, 0.0);
+        return off;
+    };
+    pl.oA = put(A, (size_t)n_modes * p * p);
+    pl.oB = put(B, (size_t)n_modes * p * n_u);
+    pl.ow = put(w, (size_t)n_modes * p);
+    pl.oE = put(Emat, (size_t)p * n_d);
+    pl.oH = put(H, (size_t)rows * p);
+    pl.oh = put(h, (size_t)rows);
+    pl.oG = put(Gx, (size_t)n_g * p);
+    pl.og = put(gx, (size_t)n_g);
+    pl.oQ = put(Q, (size_t)p * p);
+    pl.oR = put(R, (size_t)n_u * n_u);
+    pl.total = (int)buf.size();
+    for (int64_t k = 0; k < E->d.n_nodes; ++k)
+        if (node_mode[k] >= n_modes)
+            return xfail(EHM_E_INVALID, "set_plant: node %lld has mode %d of %d", (long long)k,
+                         (int)node_mode[k], (int)n_modes);
+    hipError_t e = hipSetDevice(E->device);
+    if (e != hipSuccess) return xfail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
+    void *d_plant = nullptr, *d_mode = nullptr;
+    const size_t mb = (size_t)E->d.n_nodes * sizeof(int32_t);
+    if (hipMalloc(&d_plant, buf.size() * sizeof(double)) != hipSuccess ||
+        hipMalloc(&d_mode, mb) != hipSuccess ||
+        hipMemcpy(d_plant, buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice) !=
+            hipSuccess ||
+        hipMemcpy(d_mode, node_mode, mb, hipMemcpyHostToDevice) != hipSuccess) {
+        if (d_plant) (void)hipFree(d_plant);
+        if (d_mode) (void)hipFree(d_mode);
+        return xfail(EHM_E_HIP, "set_plant: device allocation / copy failed");
+    }
+    if (E->plant) (void)hipFree(E->plant);
+    if (E->node_mode) (void)hipFree(E->node_mode);
+    E->plant = d_plant;
+    E->node_mode = d_mode;
+    pl.data = (const double*)d_plant;
+    E->pl = pl;
+    return EHM_OK;
+}
+
+int ehm_explicit_rollout(ehm_explicit* E, int64_t n, int32_t T, const double* x0,
+                         const double* d, const double* v, double tol_exit, double* x_traj,
+                         double* u_traj, int32_t* leaf_traj, double* x_final, int32_t* steps,
+                         int32_t* status, double* cost, double* u_norm_sum,
+                         double* max_violation, double* kernel_seconds) {
+    if (!E || !x0 || !x_final || !steps || !status || !cost || !u_norm_sum || !max_violation ||
+        n < 0 || T < 0 || !(tol_exit >= 0.0))
+        return xfail(EHM_E_INVALID, "rollout: bad argument");
+    if (!E->plant) return xfail(EHM_E_INVALID, "rollout: no plant (ehm_explicit_set_plant)");
+    if (d && E->pl.n_d == 0)
+        return xfail(EHM_E_INVALID, "rollout: a disturbance was given but the plant has no E");
+    const int p = E->d.p, n_u = E->d.n_u;
+    if (n == 0) return EHM_OK;
+    if (n > (int64_t)1 << 31) return xfail(EHM_E_INVALID, "rollout: %lld trajectories", (long long)n);
+    hipError_t e = hipSetDevice(E->device);
+    if (e != hipSuccess) return xfail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
+    const size_t N = (size_t)n, nT = (size_t)T;
+    // device buffers of this call, released on every return below
+    struct Bufs {
+        std::vector<void*> v;
+        ~Bufs() {
+            for (void* p : v) (void)hipFree(p);
+        }
+        void* get(size_t bytes) {
+            void* p = nullptr;
+            if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) return nullptr;
+            v.push_back(p);
+            return p;
+        }
+    } bufs;
+    RollArgs R{};
+    R.n = n;
+    R.T = T;
+    R.tol_exit = tol_exit;
+    double *dx0 = (double*)bufs.get(N * p * sizeof(double)), *dd = nullptr, *dv = nullptr;
+    R.x_final = (double*)bufs.get(N * p * sizeof(double));
+    R.cost = (double*)bufs.get(N * sizeof(double));
+    R.u_norm = (double*)bufs.get(N * sizeof(double));
+    R.max_viol = (double*)bufs.get(N * sizeof(double));
+    R.steps = (int32_t*)bufs.get(N * sizeof(int32_t));
+    R.status = (int32_t*)bufs.get(N * sizeof(int32_t));
+    if (d) dd = (double*)bufs.get(nT * N * E->pl.n_d * sizeof(double));
+    if (v) dv = (double*)bufs.get(nT * N * p * sizeof(double));
+    if (x_traj) R.x_traj = (double*)bufs.get((nT + 1) * N * p * sizeof(double));
+    if (u_traj) R.u_traj = (double*)bufs.get(nT * N * n_u * sizeof(double));
+    if (leaf_traj) R.leaf_traj = (int32_t*)bufs.get(nT * N * sizeof(int32_t));
+    if (!dx0 || !R.x_final || !R.cost || !R.u_norm || !R.max_viol || !R.steps || !R.status ||
+        (d && !dd) || (v && !dv) || (x_traj && !R.x_traj) || (u_traj && !R.u_traj) ||
+        (leaf_traj && !R.leaf_traj))
+        return xfail(EHM_E_HIP, "rollout: out of device memory for %lld x %d steps",
+                     (long long)n, (int)T);
+    R.x0 = dx0;
+    R.d = dd;
+    R.v = dv;
+    R.node_mode = (const int32_t*)E->node_mode;
+    R.nbr = (E->nbr && !locate_off()) ? (const int32_t*)E->nbr : nullptr;
+    Y_TRY(hipMemcpyAsync(dx0, x0, N * p * sizeof(double), hipMemcpyHostToDevice, E->stream));
+    if (d)
+        Y_TRY(hipMemcpyAsync(dd, d, nT * N * E->pl.n_d * sizeof(double), hipMemcpyHostToDevice,
+                             E->stream));
+    if (v)
+        Y_TRY(hipMemcpyAsync(dv, v, nT * N * p * sizeof(double), hipMemcpyHostToDevice,
+                             E->stream));
+    hipEvent_t e0, e1;
+    (void)hipEventCreate(&e0);
+    (void)hipEventCreate(&e1);
+    (void)hipEventRecord(e0, E->stream);
+    hipLaunchKernelGGL(k_rollout_table[p - 1][n_u - 1], dim3((unsigned)((n + 255) / 256)),
+                       dim3(256), (size_t)E->pl.total * sizeof(double), E->stream, E->d, E->pl,
+                       R);
+    (void)hipEventRecord(e1, E->stream);
+    Y_TRY(hipGetLastError());
+    Y_TRY(hipMemcpyAsync(x_final, R.x_final, N * p * sizeof(double), hipMemcpyDeviceToHost,
+                         E->stream));
+    Y_TRY(hipMemcpyAsync(steps, R.steps, N * sizeof(int32_t), hipMemcpyDeviceToHost, E->stream));
+    Y_TRY(hipMemcpyAsync(status, R.status, N * sizeof(int32_t), hipMemcpyDeviceToHost,
+                         E->stream));
+    Y_TRY(hipMemcpyAsync(cost, R.cost, N * sizeof(double), hipMemcpyDeviceToHost, E->stream));
+    Y_TRY(hipMemcpyAsync(u_norm_sum, R.u_norm, N * sizeof(double), hipMemcpyDeviceToHost,
+                         E->stream));
+    Y_TRY(hipMemcpyAsync(max_violation, R.max_viol, N * sizeof(double), hipMemcpyDeviceToHost,
+                         E->stream));
+    if (x_traj)
+        Y_TRY(hipMemcpyAsync(x_traj, R.x_traj, (nT + 1) * N * p * sizeof(double),
+                             hipMemcpyDeviceToHost, E->stream));
+    if (u_traj)
+        Y_TRY(hipMemcpyAsync(u_traj, R.u_traj, nT * N * n_u * sizeof(double),
+                             hipMemcpyDeviceToHost, E->stream));
+    if (leaf_traj)
+        Y_TRY(hipMemcpyAsync(leaf_traj, R.leaf_traj, nT * N * sizeof(int32_t),
                              hipMemcpyDeviceToHost, E->stream));
     Y_TRY(hipStreamSynchronize(E->stream));
     if (kernel_seconds) {

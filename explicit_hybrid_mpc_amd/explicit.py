@@ -28,12 +28,19 @@ def _check(rc):
         raise _capi.EhmError(rc, _capi.load().ehm_explicit_last_error().decode('utf-8', 'replace'))
 
 
-def flatten_tree(root):
+def node_commutation(nd):
+    """The commutation a nested-tree node stores (NodeData.commutation), or None."""
+    c = getattr(nd.data, 'commutation', None) if nd.data is not None else None
+    return None if c is None else np.asarray(c, dtype=np.float64)
+
+
+def flatten_tree(root, commutations=False):
     """
     Nested ``tree.Tree`` (reference layout) -> flat arrays with node 0 = root, children after
     their parents: (vertices, vertex_inputs, left, right, nodes).  Data-less spine nodes and
     nodes without inputs get placeholders; they are never tested (only left children and final
-    leaves are, lib/mpc_library.py:703-711) or never returned.
+    leaves are, lib/mpc_library.py:703-711) or never returned.  With ``commutations`` also the
+    list of every node's commutation vector (None where the node has none).
     """
     first, stack = None, [root]
     while stack:                        # any node with vertex inputs tells the shapes
@@ -69,7 +76,10 @@ def flatten_tree(root):
         vertices[k] = np.asarray(d.vertices, dtype=np.float64) if ok else unit
         if d is not None and hasattr(d, 'vertex_inputs'):
             vinput[k] = np.asarray(d.vertex_inputs, dtype=np.float64)
-    return vertices, vinput, np.array(left, dtype=np.int32), np.array(right, dtype=np.int32), nodes
+    out = (vertices, vinput, np.array(left, dtype=np.int32), np.array(right, dtype=np.int32), nodes)
+    if commutations:
+        return out + ([node_commutation(nd) for nd in nodes],)
+    return out
 
 
 class ImplicitMPC:
@@ -92,6 +102,19 @@ class ImplicitMPC:
         u, _, _, t = self.__oracle.P_theta(x)
         return u, t
 
+    def rollout(self, X0, T, d=None, v=None, record=True, tol_exit=1e-9, plant=None):
+        """
+        Closed loop from the states X0 [n, p] for T steps (simulate.py): per step one batched
+        P_theta over the live trajectories, the plant (default ``Plant.from_mpc``) stepped in
+        the step-0 mode of the returned commutation.  Returns a ``simulate.ClosedLoop``.
+        """
+        from . import simulate
+        if plant is None:
+            plant = simulate.Plant.from_mpc(self.__oracle.mpc)
+        self._rollout_plant = plant
+        return simulate.rollout_implicit(self.__oracle, plant, X0, T, d=d, v=v, record=record,
+                                         tol_exit=tol_exit)
+
     def evaluate(self, X):
         """Inputs for a batch of states (n, p) -> (n, n_u); NaN rows where infeasible."""
         J, u0, didx = self.__oracle.gpu.solve_pt(np.asarray(X, dtype=np.float64))
@@ -105,6 +128,8 @@ class ExplicitMPC:
 
     def __init__(self, tree, oracle=None, device=0):
         mpc = getattr(oracle, 'mpc', None)
+        self.mpc = mpc
+        self._rollout_plant = None
         self.plant = getattr(mpc, 'plant', None)
         self.T_s = getattr(mpc, 'T_s', None)
         if hasattr(mpc, 'specs'):
@@ -125,7 +150,8 @@ class ExplicitMPC:
             n_roots = int(t.info['n_roots'])
             self.nodes = None
         else:
-            vertices, vinput, left, right, self.nodes = flatten_tree(self.tree)
+            vertices, vinput, left, right, self.nodes, self._commutations = flatten_tree(
+                self.tree, commutations=True)
             n_roots = 1
         self.n_nodes, self.p, self.n_u = vertices.shape[0], vertices.shape[2], vinput.shape[2]
         self.eps = np.finfo(np.float64).eps
@@ -157,6 +183,87 @@ class ExplicitMPC:
         if return_info:
             return u, leaf, visited, secs.value
         return u
+
+    def node_modes(self, plant):
+        """int32 [n_nodes]: step-0 mode of every node's commutation (-1: none); all 0 for a
+        single-mode plant."""
+        if plant.n_modes == 1:
+            return np.zeros(self.n_nodes, dtype=np.int32)
+        if self.mpc is None or not hasattr(self.mpc, 'step0_mode'):
+            raise ValueError('the step-0 modes of a hybrid law need the oracle (its mpc)')
+        if isinstance(self.tree, FlatTree):
+            modes = np.array([self.mpc.step0_mode(dl) for dl in self.tree.deltas] + [-1],
+                             dtype=np.int32)
+            didx = np.asarray(self.tree.delta_idx)
+            return np.ascontiguousarray(np.where(didx >= 0, modes[didx], -1), dtype=np.int32)
+        return np.array([-1 if c is None else self.mpc.step0_mode(c)
+                         for c in self._commutations], dtype=np.int32)
+
+    def set_plant(self, plant):
+        """Hands the plant the rollout closes the loop around to the device (once per plant)."""
+        if plant.n_x != self.p or plant.n_u != self.n_u:
+            raise ValueError('plant (n_x %d, n_u %d) does not fit the law (p %d, n_u %d)' % (
+                plant.n_x, plant.n_u, self.p, self.n_u))
+        self._node_mode = self.node_modes(plant)
+        rows, H, h = plant.region_arrays()
+        keep = [f64(plant.A), f64(plant.B), f64(plant.w), f64(plant.E), rows, f64(H), f64(h),
+                f64(plant.Gx), f64(plant.gx), self._node_mode, f64(plant.Q), f64(plant.R)]
+        A, B, w, E, rows, H, h, Gx, gx, nm, Q, R = keep
+        _check(self._lib.ehm_explicit_set_plant(
+            self._handle, plant.n_modes, ptr(A), ptr(B), ptr(w), plant.n_d,
+            ptr(E) if plant.n_d else None, ptr(rows), ptr(H) if H.size else None,
+            ptr(h) if h.size else None, plant.gx.size, ptr(Gx) if Gx.size else None,
+            ptr(gx) if gx.size else None, ptr(nm), 0 if plant.cost == 'inf' else 1, ptr(Q),
+            ptr(R)))
+        self._rollout_plant = plant
+
+    def rollout(self, X0, T, d=None, v=None, record=True, tol_exit=1e-9, plant=None):
+        """
+        Closed loop from the states X0 [n, p] for T steps in ONE kernel launch
+        (ehm_explicit_rollout, one device thread per trajectory; conventions in simulate.py).
+        ``plant`` defaults to ``Plant.from_mpc`` of the oracle's law; d [T, n, n_d] and
+        v [T, n, p] are optional.  Returns a ``simulate.ClosedLoop`` (leaf, commutation and
+        mode recorded with ``record``).
+        """
+        from . import simulate
+        if plant is None:
+            plant = self._rollout_plant
+            if plant is None:
+                if self.mpc is None:
+                    raise ValueError('rollout needs a plant (or an oracle whose mpc gives one)')
+                plant = simulate.Plant.from_mpc(self.mpc)
+        if plant is not self._rollout_plant:
+            self.set_plant(plant)
+        X0 = f64(np.atleast_2d(X0))
+        n, p = X0.shape
+        T = int(T)
+        if p != self.p or T < 0:
+            raise ValueError('X0 must be [n, %d] and T >= 0' % self.p)
+        d = simulate._as_batch(d, (T, n, plant.n_d), 'd')
+        v = simulate._as_batch(v, (T, n, p), 'v')
+        x_final = np.empty((n, p))
+        steps = np.empty(n, dtype=np.int32)
+        status = np.empty(n, dtype=np.int32)
+        cost, unorm, maxv = np.empty(n), np.empty(n), np.empty(n)
+        xs = np.empty((T + 1, n, p)) if record else None
+        us = np.empty((T, n, self.n_u)) if record else None
+        leaf = np.empty((T, n), dtype=np.int32) if record else None
+        secs = ctypes.c_double(0.)
+        _check(self._lib.ehm_explicit_rollout(
+            self._handle, n, T, ptr(X0), None if d is None else ptr(d),
+            None if v is None else ptr(v), float(tol_exit), None if xs is None else ptr(xs),
+            None if us is None else ptr(us), None if leaf is None else ptr(leaf), ptr(x_final),
+            ptr(steps), ptr(status), ptr(cost), ptr(unorm), ptr(maxv), ctypes.addressof(secs)))
+        out = simulate.ClosedLoop(x_final=x_final, steps=steps, status=status, cost=cost,
+                                  u_norm_sum=unorm, max_violation=maxv, seconds=secs.value)
+        if record:
+            out.x, out.u, out.leaf = xs, us, leaf
+            live = leaf >= 0
+            out.mode = np.where(live, self._node_mode[np.maximum(leaf, 0)], -1).astype(np.int32)
+            if isinstance(self.tree, FlatTree):
+                didx = np.asarray(self.tree.delta_idx, dtype=np.int32)
+                out.commutation = np.where(live, didx[np.maximum(leaf, 0)], -1).astype(np.int32)
+        return out
 
     def get_containing_cell(self, x):
         """NodeData of the leaf that contains x (nested trees), or its node index (FlatTree)."""

@@ -191,6 +191,11 @@ class PWAMPC:
             d[self.delta_size * k + i] = 1.
         return d
 
+    def step0_mode(self, delta):
+        """The mode a commutation vector applies at step 0: inverse of ``sequence_to_delta`` on
+        the first step (the dynamics the plant follows under this commutation's first input)."""
+        return int(np.argmax(np.asarray(delta)[:self.delta_size]))
+
     # -- condensation ---------------------------------------------------------------
     def _prediction(self, seq):
         """x_k = Phi[k] theta + Gam[k] U + om[k],  U = [u_0;..;u_{N-1}]."""
@@ -536,6 +541,12 @@ class SatelliteZ:
             if s > 0:
                 d[self.delta_size * k + (s - 1)] = 1.
         return d
+
+    def step0_mode(self, delta):
+        """Step-0 value of the commutation: 0 input off, 1 + i input piece i (the plant's
+        dynamics are the same in all three)."""
+        head = np.asarray(delta)[:self.delta_size]
+        return 0 if not head.any() else 1 + int(np.argmax(head))
 
     def box_vertices(self):
         """Vertices of the partitioned set (lib/examples.py:77-79)."""

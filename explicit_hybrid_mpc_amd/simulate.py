@@ -1,0 +1,265 @@
+"""
+Closed-loop simulation of the explicit and the implicit law (lib/simulator.py,
+lib/post_process.py:242-266, 405-420), for whole batches of initial states.
+
+    plant = Plant.from_mpc(mpc)                       # x+ = A_m x + B_m u + w_m + E d
+    res = ExplicitMPC(flat, oracle).rollout(X0, T)    # one device thread per trajectory
+    res = ImplicitMPC(oracle).rollout(X0, T)          # one batched P_theta per step
+    fig = compare(explicit, implicit, X0, T)          # delta-v overconsumption, cost ratio
+    sim = Simulator(law, T_final).run(x0)             # the reference's SimulationOutput
+
+Conventions (both laws): at step t the law sees z_t = x_t + v_t (no error at t = 0, as in
+lib/simulator.py:168); the plant steps in the step-0 mode m of the commutation the law used;
+a trajectory STOPS -- no input applied, ``steps`` = t -- with status 1 if the explicit law's leaf
+does not hold z_t (a barycentric weight < -tol_exit: the state left the partitioned set; the
+reference would extrapolate), 2 if mode m's region does not hold x_t (theory says this cannot
+happen: a check), 3 if there is no law at z_t (implicit: P_theta infeasible; explicit: a leaf
+without a commutation).  Disturbances d [T][n][n_d] and measurement errors v [T][n][p] are passed
+in by the caller; the reference's state-dependent noise samplers are not reproduced.
+"""
+
+import time
+
+import numpy as np
+
+STATUS_OK, STATUS_EXIT, STATUS_MODE, STATUS_NO_LAW = 0, 1, 2, 3
+
+
+class Plant:
+    """
+    Plant of a law with the controller's period: x+ = A[m] x + B[m] u + w[m] + E d, mode m
+    admissible where H_m x <= h_m (``regions[m]``, None = everywhere); Gx x <= gx the state
+    constraints; stage cost ||Q x||_inf + ||R u||_inf (cost 'inf') or x'Qx + u'Ru ('quadratic').
+    """
+
+    def __init__(self, A, B, w, E, regions, Gx, gx, Q, R, cost, T_s=None):
+        self.A = np.ascontiguousarray(A, dtype=np.float64)
+        self.B = np.ascontiguousarray(B, dtype=np.float64)
+        self.w = np.ascontiguousarray(w, dtype=np.float64)
+        self.n_modes, self.n_x, self.n_u = self.B.shape
+        self.E = np.zeros((self.n_x, 0)) if E is None else np.ascontiguousarray(E, dtype=np.float64)
+        self.n_d = self.E.shape[1]
+        self.regions = list(regions)
+        self.Gx = np.ascontiguousarray(Gx, dtype=np.float64)
+        self.gx = np.ascontiguousarray(gx, dtype=np.float64)
+        self.Q = np.ascontiguousarray(Q, dtype=np.float64)
+        self.R = np.ascontiguousarray(R, dtype=np.float64)
+        if cost not in ('inf', 'quadratic'):
+            raise ValueError("cost must be 'inf' or 'quadratic'")
+        self.cost = cost
+        self.T_s = T_s
+
+    @classmethod
+    def from_mpc(cls, mpc):
+        """The plant of a ``PWAMPC`` (its modes, regions and cost) or of a ``SatelliteZ``
+        (``LinearPlant(T_s, A, B, E)`` of lib/mpc_library.py:258-269; one mode per step-0
+        commutation value -- off, piece 0, piece 1 -- all with the same dynamics; the quadratic
+        weights of its cost, R = 1/dv_max^2, Q = 1e-2 D_x^-2)."""
+        if hasattr(mpc, 'u_pieces'):
+            pars = mpc.pars
+            k = mpc.delta_size + 1
+            Dxi = np.diag([1. / pars['pos_err_max'], 1. / pars['vel_err_max']])
+            return cls([mpc.A] * k, [mpc.B] * k, [np.zeros(mpc.n_x)] * k, mpc.E, [None] * k,
+                       mpc.Gx, mpc.gx, 1e-2 * Dxi @ Dxi,
+                       np.array([[1. / pars['delta_v_max'] ** 2]]), 'quadratic', T_s=mpc.T_s)
+        return cls(mpc.A, mpc.B, mpc.w, None, mpc.regions, mpc.Gx, mpc.gx, mpc.Q, mpc.R,
+                   mpc.cost_type, T_s=getattr(mpc, 'T_s', None))
+
+    def region_arrays(self):
+        """(rows per mode, H stacked, h stacked) of the mode regions."""
+        rows, H, h = [], [np.zeros((0, self.n_x))], [np.zeros(0)]
+        for r in self.regions:
+            rows.append(0 if r is None else len(r[1]))
+            if r is not None:
+                H.append(np.asarray(r[0], dtype=np.float64).reshape(-1, self.n_x))
+                h.append(np.asarray(r[1], dtype=np.float64).ravel())
+        return np.array(rows, dtype=np.int32), np.vstack(H), np.concatenate(h)
+
+    def in_region(self, X, m, tol):
+        """bool [n]: mode m[i]'s region holds X[i] (within tol)."""
+        X = np.atleast_2d(X)
+        ok = np.ones(X.shape[0], dtype=bool)
+        for mode in np.unique(m):
+            r = self.regions[int(mode)]
+            if r is None:
+                continue
+            sel = m == mode
+            ok[sel] = np.all(X[sel] @ r[0].T <= r[1] + tol, axis=1)
+        return ok
+
+    def step(self, X, U, m, D=None):
+        """x+ for rows X [n, n_x], U [n, n_u], modes m [n], disturbances D [n, n_d] or None."""
+        out = np.einsum('nij,nj->ni', self.A[m], X) + np.einsum('nij,nj->ni', self.B[m], U) \
+            + self.w[m]
+        if D is not None:
+            out = out + D @ self.E.T
+        return out
+
+    def stage_cost(self, X, U):
+        if self.cost == 'inf':
+            return np.abs(X @ self.Q.T).max(axis=1) + np.abs(U @ self.R.T).max(axis=1)
+        return np.einsum('ni,ij,nj->n', X, self.Q, X) + np.einsum('ni,ij,nj->n', U, self.R, U)
+
+
+class ClosedLoop:
+    """
+    Result of a batched rollout (n trajectories, T steps).  Records, time-major, None unless
+    asked for: x [T+1, n, n_x], u [T, n, n_u] (NaN after a stop), leaf [T, n] (explicit law,
+    -1 after a stop), commutation [T, n] (index into the law's commutations, -1 after a stop),
+    mode [T, n] (applied mode, -1 after a stop).  Always: x_final [n, n_x], steps [n], status [n]
+    (STATUS_*), cost [n] (summed stage cost), u_norm_sum [n] (sum_t ||u_t||_2), max_violation [n]
+    (max_t max_j (Gx x_{t+1} - gx)_j, -inf without a step), seconds (device time of the explicit
+    rollout kernel / wall time of the implicit loop).
+    """
+
+    def __init__(self, **kw):
+        self.x = self.u = self.leaf = self.commutation = self.mode = None
+        self.seconds = 0.
+        self.__dict__.update(kw)
+
+    @property
+    def exited(self):
+        return self.status == STATUS_EXIT
+
+    @property
+    def mode_violations(self):
+        return self.status == STATUS_MODE
+
+
+def _as_batch(a, shape, name):
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.shape != shape:
+        raise ValueError('%s must have shape %s, not %s' % (name, shape, a.shape))
+    return a
+
+
+def rollout_implicit(oracle, plant, X0, T, d=None, v=None, record=True, tol_exit=1e-9):
+    """
+    The implicit law in closed loop: per step one batched ``solve_pt`` (the device's
+    mixed-integer oracle) over the live trajectories, the plant step on the host with the
+    conventions of the module docstring.  Returns a ClosedLoop (commutation, no leaf).
+    """
+    X0 = np.ascontiguousarray(np.atleast_2d(X0), dtype=np.float64)
+    n, p = X0.shape
+    d = _as_batch(d, (T, n, plant.n_d), 'd')
+    v = _as_batch(v, (T, n, p), 'v')
+    can = oracle.canonical
+    mode_of = np.array([oracle.mpc.step0_mode(dl) for dl in can.deltas], dtype=np.int64)
+    x = X0.copy()
+    steps = np.full(n, T, dtype=np.int32)
+    status = np.zeros(n, dtype=np.int32)
+    cost, unorm = np.zeros(n), np.zeros(n)
+    maxv = np.full(n, -np.inf)
+    if record:
+        xs = np.full((T + 1, n, p), np.nan)
+        xs[0] = x
+        us = np.full((T, n, plant.n_u), np.nan)
+        cs = np.full((T, n), -1, dtype=np.int32)
+        ms = np.full((T, n), -1, dtype=np.int32)
+    live = np.arange(n)
+    tic = time.time()
+    for t in range(T):
+        if live.size == 0:
+            break
+        z = x[live] + v[t, live] if (v is not None and t > 0) else x[live]
+        _, u0, didx = oracle.gpu.solve_pt(z)
+        bad = (didx < 0) | ~np.all(np.isfinite(u0), axis=1)
+        m = mode_of[np.maximum(didx, 0)]
+        off = ~bad & ~plant.in_region(x[live], m, tol_exit)
+        for sel, code in ((bad, STATUS_NO_LAW), (off, STATUS_MODE)):
+            status[live[sel]] = code
+            steps[live[sel]] = t
+        go = ~(bad | off)
+        live, u0, m, didx = live[go], u0[go], m[go], didx[go]
+        xl = x[live]
+        cost[live] += plant.stage_cost(xl, u0)
+        unorm[live] += np.sqrt(np.sum(u0 * u0, axis=1))
+        xn = plant.step(xl, u0, m, None if d is None else d[t, live])
+        if plant.gx.size:
+            maxv[live] = np.maximum(maxv[live], (xn @ plant.Gx.T - plant.gx).max(axis=1))
+        x[live] = xn
+        if record:
+            us[t, live] = u0
+            cs[t, live] = didx
+            ms[t, live] = m
+            xs[t + 1, live] = xn
+    out = ClosedLoop(x_final=x, steps=steps, status=status, cost=cost, u_norm_sum=unorm,
+                     max_violation=maxv, seconds=time.time() - tic)
+    if record:
+        out.x, out.u, out.commutation, out.mode = xs, us, cs, ms
+    return out
+
+
+def compare(explicit, implicit, X0, T, d=None, v=None, tol_exit=1e-9, record=False):
+    """
+    The explicit against the implicit law from the same initial states under the same d / v
+    (total_delta_v_usage, lib/post_process.py:242-266).  Per trajectory: ``overconsumption``
+    = (sum ||u||_ex - sum ||u||_im) / sum ||u||_im and ``cost_ratio`` = cost_ex / cost_im (NaN
+    where the implicit figure is 0).  Aggregates over the trajectories both laws ran for all T
+    steps (``both_ok``): ``overconsumption_total`` (the statistic of total_delta_v_usage over
+    the summed usage) and ``cost_ratio_total``.  Also the exit / stop counts and the two
+    ClosedLoop results (``explicit``, ``implicit``).
+    """
+    ex = explicit.rollout(X0, T, d=d, v=v, record=record, tol_exit=tol_exit)
+    im = implicit.rollout(X0, T, d=d, v=v, record=record, tol_exit=tol_exit)
+    both = (ex.status == STATUS_OK) & (im.status == STATUS_OK)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        over = np.where(im.u_norm_sum > 0, (ex.u_norm_sum - im.u_norm_sum) / im.u_norm_sum,
+                        np.nan)
+        ratio = np.where(im.cost > 0, ex.cost / im.cost, np.nan)
+    su_ex, su_im = float(ex.u_norm_sum[both].sum()), float(im.u_norm_sum[both].sum())
+    sc_ex, sc_im = float(ex.cost[both].sum()), float(im.cost[both].sum())
+    return dict(overconsumption=over, cost_ratio=ratio,
+                overconsumption_total=(su_ex - su_im) / su_im if su_im > 0 else float('nan'),
+                cost_ratio_total=sc_ex / sc_im if sc_im > 0 else float('nan'),
+                u_norm_explicit=su_ex, u_norm_implicit=su_im,
+                both_ok=int(both.sum()), n=int(both.size),
+                exits_explicit=int(ex.exited.sum()),
+                mode_violations_explicit=int(ex.mode_violations.sum()),
+                stopped_explicit=int((ex.status != STATUS_OK).sum()),
+                stopped_implicit=int((im.status != STATUS_OK).sum()),
+                explicit=ex, implicit=im)
+
+
+class SimulationOutput:
+    """The reference's simulation record (lib/simulator.py:31-71), already compiled to arrays:
+    t, t_call [K]; x [n_x, K], u [n_u, K], w [n_d, K], v [n_x, K], e [n_u, K] column-stacked,
+    column k = the state before step k and what acted on it."""
+
+    def __init__(self):
+        self.t, self.t_call, self.x, self.u, self.w, self.v, self.e = [], [], [], [], [], [], []
+
+
+class Simulator:
+    """
+    ``Simulator(mpc, T).run(x_0, label)`` of lib/simulator.py:73-188 for a law with a
+    ``rollout`` (``ExplicitMPC`` / ``ImplicitMPC``): T is the final time, the plant runs at the
+    controller's period T_s (1 if the law has none), so the run has int(T / T_s + 1) steps, as
+    the reference's time grid.  Nominal (no noise); a trajectory that stops ends the record.
+    """
+
+    def __init__(self, mpc, T):
+        self.law = mpc
+        self.T_f = T
+        self.h = getattr(mpc, 'T_s', None) or 1.
+        self.sim_history = SimulationOutput()
+
+    def run(self, x_0, label=None):
+        out = self.sim_history = SimulationOutput()
+        if label is not None:
+            out.label = label
+        times = np.linspace(0, self.T_f, int(self.T_f / self.h + 1))
+        res = self.law.rollout(np.asarray(x_0, dtype=np.float64)[None], len(times), record=True)
+        K = int(res.steps[0])
+        n_x, n_u = res.x.shape[2], res.u.shape[2]
+        n_d = getattr(getattr(self.law, '_rollout_plant', None), 'n_d', 0)
+        out.t = times[:K]
+        out.t_call = np.full(K, res.seconds / max(len(times), 1))
+        out.x = res.x[:K, 0].T.copy().reshape(n_x, K)
+        out.u = res.u[:K, 0].T.copy().reshape(n_u, K)
+        out.w = np.zeros((n_d, K))
+        out.v = np.zeros((n_x, K))
+        out.e = np.zeros((n_u, K))
+        return out

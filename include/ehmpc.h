@@ -473,6 +473,43 @@ int ehm_explicit_eval_batch(ehm_explicit* ex, int64_t n, const double* x, double
 int ehm_explicit_destroy(ehm_explicit* ex);
 const char* ehm_explicit_last_error(void);
 
+/* ---- closed-loop simulation under the explicit law (lib/simulator.py, lib/post_process.py) ---
+ *
+ * The plant the law is closed around (Simulator.__init__, lib/simulator.py:73-122, with the
+ * plant period equal to the controller's T_s):
+ *     x+ = A_m x + B_m u + w_m + E d      m = step-0 mode of the leaf's commutation,
+ * n_modes <= 4 modes, A [n_modes][p][p], B [n_modes][p][n_u], w [n_modes][p]; E [p][n_d] with
+ * n_d <= 8 (n_d = 0: no disturbance input, E may be NULL); mode m holds where
+ * H_m x <= h_m: region_rows [n_modes] rows each (NULL: no region), H [rows][p], h [rows] stacked
+ * by mode; Gx [n_g][p], gx [n_g] (n_g <= 256) the state constraints whose worst value the
+ * rollout reports; node_mode [n_nodes] the mode of every node (-1: no commutation, a
+ * trajectory that reaches such a leaf stops with status 3); stage cost cost_kind 0:
+ * ||Q x||_inf + ||R u||_inf, 1: x'Qx + u'Ru, Q [p][p], R [n_u][n_u].  The law's n_u must be
+ * <= 4.  Replaces an earlier plant. */
+int ehm_explicit_set_plant(ehm_explicit* ex, int32_t n_modes, const double* A, const double* B,
+                           const double* w, int32_t n_d, const double* E,
+                           const int32_t* region_rows, const double* H, const double* h,
+                           int32_t n_g, const double* Gx, const double* gx,
+                           const int32_t* node_mode, int32_t cost_kind, const double* Q,
+                           const double* R);
+/* n trajectories of T steps from x0 [n][p], one device thread each (Simulator.run,
+ * lib/simulator.py:124-188).  Step t: measure z = x + v[t] (v [T][n][p] or NULL; no error at
+ * t = 0, :168), locate z with the walk of ehm_explicit_eval_batch (same leaf, bit-equal u),
+ * stop if z is outside the leaf (a barycentric weight < -tol_exit: status 1, no input applied),
+ * stop if the mode's region does not hold x (status 2), else apply u and step the plant with
+ * d[t] (d [T][n][n_d] or NULL).  Time-major records, each may be NULL: x_traj [T+1][n][p],
+ * u_traj [T][n][n_u], leaf_traj [T][n]; after a stop NaN states / inputs and leaf -1.  Always:
+ * x_final [n][p], steps [n] (T if never stopped), status [n] (0 ok, 1 left the set, 2 mode
+ * region violated, 3 leaf without commutation), cost [n] (summed stage cost), u_norm_sum [n]
+ * (sum of ||u_t||_2, the delta-v usage of total_delta_v_usage, lib/post_process.py:242-266),
+ * max_violation [n] (max over steps and rows of Gx x_{t+1} - gx; -inf if no step was taken).
+ * kernel_seconds (may be NULL) = device time of the rollout kernel. */
+int ehm_explicit_rollout(ehm_explicit* ex, int64_t n, int32_t T, const double* x0,
+                         const double* d, const double* v, double tol_exit, double* x_traj,
+                         double* u_traj, int32_t* leaf_traj, double* x_final, int32_t* steps,
+                         int32_t* status, double* cost, double* u_norm_sum,
+                         double* max_violation, double* kernel_seconds);
+
 /* Cumulative counters of a problem handle (SURVEY.md section 5 "tracing"). */
 typedef struct ehm_counters {
     int64_t lp_solves;

@@ -1,0 +1,155 @@
+#!/usr/bin/env python
+"""
+Closed-loop simulation throughput and the cwh_z delta-v overconsumption table (needs a GPU).
+
+    python tools/rollout_bench.py [--n 1000000] [--T 100] [--jobs 1,2,3,4,5] [--n-compare 10000]
+
+Trajectory-steps/s, one JSON line per tree and path:
+  (a) fused    ExplicitMPC.rollout: one launch of ehm_explicit_rollout (device time of the kernel,
+               and wall time including the host copies); steps counted are the ones applied;
+  (b) host     T calls of ExplicitMPC.evaluate plus a numpy plant step, what a caller writes
+               without the rollout (wall time; every trajectory runs all T steps, no exit test);
+  (c) cpu      the CPU restatement (oracle.explicit_cpu.ExplicitFlatCPU + the numpy plant step),
+               one process, a few trajectories, for scale.
+Trees: the headline partition (linear_mpc(0), abs_frac 0.02, eps_r 1e-2, as bench.py) and cwh_z
+job 1.  Then simulate.compare on cwh_z jobs 1..5 (lib/post_process.py:484-526 / make_jobs.sh) from
+uniform initial states in the box, nominal and with a box-bounded process disturbance; the
+paper's overconsumption (lib/post_process.py:414-415, single noisy trajectories) is printed beside
+it for context only.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+import types
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from explicit_hybrid_mpc_amd import engine, examples, explicit, simulate   # noqa: E402
+from explicit_hybrid_mpc_amd import tools as ehm_tools                   # noqa: E402
+from oracle import geometry                                              # noqa: E402
+from oracle.explicit_cpu import ExplicitFlatCPU                          # noqa: E402
+
+CWH_FRACS = [0.5, 0.25, 0.1, 0.03, 0.01]
+PAPER_IMPLICIT = [4.02, 3.78, 3.74, 3.72, 3.88]       # lib/post_process.py:414-415 [mm/s]
+PAPER_EXPLICIT = [40.24, 37.29, 4.79, 2.2, 3.94]
+
+
+def headline_tree():
+    mpc = examples.linear_mpc(seed=0)
+    gp = engine.GpuProblem(mpc.compile(), 1., 1.)
+    V = examples.box_vertices(examples.theta_box(mpc))
+    roots, _ = ehm_tools.delaunay_roots(V)
+    gp.set_eps(float(np.max(gp.solve_pt(0.02 * V)[0])), 1e-2)
+    flat = gp.partition(roots, action='ecc', max_nodes=1 << 23)
+    gp.close()
+    return mpc, flat
+
+
+def cwh_tree(job):
+    known = json.load(open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                        'tests', 'golden', 'known_answers.json')))['runs']
+    full_set, _, oracle = examples.example('cwh_z', abs_frac=CWH_FRACS[job - 1],
+                                           rel_err=float(known[job - 1]['rel_err']))
+    roots, _ = geometry.delaunay_simplices(full_set)
+    flat = oracle.gpu.partition(np.array(roots), action='ecc', max_nodes=1 << 24)
+    return oracle, flat
+
+
+def rates(name, mpc, flat, n, T, rng):
+    ex = explicit.ExplicitMPC(flat, types.SimpleNamespace(mpc=mpc))
+    pl = simulate.Plant.from_mpc(mpc)
+    half = examples.theta_box(mpc)
+    X0 = rng.uniform(-1, 1, (n, half.size)) * half
+    ex.rollout(X0[:1024], T, record=False)                 # warm-up (set-up of the plant, code)
+    t0 = time.perf_counter()
+    res = ex.rollout(X0, T, record=False)
+    wall = time.perf_counter() - t0
+    applied = int(res.steps.sum())
+    print(json.dumps(dict(tree=name, path='(a) fused rollout', nodes=int(flat.n_nodes),
+                          trajectories=n, T=T, applied_steps=applied,
+                          stopped=int((res.status != 0).sum()),
+                          kernel_s=res.seconds, wall_s=wall,
+                          steps_per_s_kernel=applied / res.seconds,
+                          steps_per_s_wall=applied / wall)), flush=True)
+    m = ex._node_mode
+    ex.evaluate(X0[:1024])
+    t0 = time.perf_counter()
+    x = X0.copy()
+    for t in range(T):
+        u, leaf, _, _ = ex.evaluate(x, return_info=True)
+        x = pl.step(x, u, m[leaf])
+    wall = time.perf_counter() - t0
+    print(json.dumps(dict(tree=name, path='(b) host loop of evaluate + numpy plant',
+                          trajectories=n, T=T, wall_s=wall, steps_per_s_wall=n * T / wall)),
+          flush=True)
+    cpu = ExplicitFlatCPU(flat.vertices, flat.vertex_inputs, flat.left, flat.right,
+                          flat.info['n_roots'])
+    nc, Tc = 20, min(T, 10)
+    t0 = time.perf_counter()
+    for i in range(nc):
+        x = X0[i].copy()
+        for t in range(Tc):
+            u, k = cpu(x)
+            x = pl.step(x[None], u[None], m[[k]])[0]
+    wall = time.perf_counter() - t0
+    print(json.dumps(dict(tree=name, path='(c) CPU restatement, one process',
+                          trajectories=nc, T=Tc, wall_s=wall, steps_per_s_wall=nc * Tc / wall)),
+          flush=True)
+    ex.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--n', type=int, default=1000000)
+    ap.add_argument('--T', type=int, default=100)
+    ap.add_argument('--jobs', default='1,2,3,4,5')
+    ap.add_argument('--n-compare', type=int, default=10000)
+    ap.add_argument('--skip-rates', action='store_true')
+    args = ap.parse_args()
+    rng = np.random.default_rng(0)
+    if not args.skip_rates:
+        mpc, flat = headline_tree()
+        rates('headline (configs[2])', mpc, flat, args.n, args.T, rng)
+        del flat
+        oracle, flat = cwh_tree(1)
+        rates('cwh_z job 1', oracle.mpc, flat, args.n, args.T, rng)
+        oracle.close()
+    table = []
+    for job in [int(j) for j in args.jobs.split(',') if j]:
+        oracle, flat = cwh_tree(job)
+        mpc = oracle.mpc
+        ex = explicit.ExplicitMPC(flat, oracle)
+        im = explicit.ImplicitMPC(oracle)
+        X0 = rng.uniform(-1, 1, (args.n_compare, 2)) * examples.theta_box(mpc)
+        d = rng.uniform(-1, 1, (args.T, args.n_compare, 1)) * mpc.pars['w_max']
+        for label, dist in (('nominal', None), ('d in +-w_max', d)):
+            t0 = time.perf_counter()
+            fig = simulate.compare(ex, im, X0, args.T, d=dist)
+            row = dict(job=job, leaves=int(np.sum(flat.left < 0)), case=label,
+                       trajectories=args.n_compare, T=args.T, both_ok=fig['both_ok'],
+                       overconsumption_pct=100 * fig['overconsumption_total'],
+                       overconsumption_median_pct=100 * float(np.nanmedian(fig['overconsumption'])),
+                       cost_ratio=fig['cost_ratio_total'], exits_explicit=fig['exits_explicit'],
+                       stopped_implicit=fig['stopped_implicit'],
+                       max_violation_explicit=float(fig['explicit'].max_violation.max()),
+                       paper_overconsumption_pct=100 * (PAPER_EXPLICIT[job - 1] - PAPER_IMPLICIT[job - 1])
+                       / PAPER_IMPLICIT[job - 1],
+                       wall_s=time.perf_counter() - t0)
+            table.append(row)
+            print(json.dumps(row), flush=True)
+        ex.close()
+        oracle.close()
+    if table:
+        print('\njob  leaves  case            over. %   median %   cost ratio  exits  paper %')
+        for r in table:
+            print('%3d  %6d  %-14s  %7.2f   %8.2f   %10.4f  %5d  %7.1f' % (
+                r['job'], r['leaves'], r['case'], r['overconsumption_pct'],
+                r['overconsumption_median_pct'], r['cost_ratio'], r['exits_explicit'],
+                r['paper_overconsumption_pct']))
+
+
+if __name__ == '__main__':
+    main()
