@@ -39,6 +39,7 @@ EXPORTED = [
     'ehm_problem_update_blocks', 'ehm_simplex_idx_batch', 'ehm_point_idx_batch',
     'ehm_abi_sizes', 'ehm_solver_phase_ticks', 'ehm_problem_layout',
     'ehm_host_alloc', 'ehm_host_free', 'ehm_explicit_set_plant', 'ehm_explicit_rollout',
+    'ehm_explicit_set_noise', 'ehm_explicit_rollout_noisy', 'ehm_philox_batch',
 ]
 
 
@@ -249,6 +250,10 @@ def load(build_if_missing=True):
     lib.ehm_explicit_set_plant.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp,
                                            vp, i32, vp, vp]
     lib.ehm_explicit_rollout.argtypes = [vp, i64, i32, vp, vp, vp, ctypes.c_double] + [vp] * 10
+    lib.ehm_explicit_set_noise.argtypes = [vp, i32, vp, vp, i32, i32]
+    lib.ehm_explicit_rollout_noisy.argtypes = [vp, i64, i32, vp, ctypes.c_uint64, ctypes.c_uint64,
+                                               ctypes.c_double] + [vp] * 13
+    lib.ehm_philox_batch.argtypes = [i64, vp, vp, vp]
     lib.ehm_explicit_last_error.restype = ctypes.c_char_p
     lib.ehm_tree_info_get.argtypes = [vp, ctypes.POINTER(TreeInfo)]
     lib.ehm_tree_export.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/ehmpc.h"
+#include "ehm_philox.h"
 
 #define EHM_XP 8   // max parameter dimension (EHM_MAX_P)
 #define EHM_X_LOCATE_MIN 128     // spines at least this long get the root locator
@@ -249,7 +250,122 @@ struct RollArgs {
     int32_t* leaf_traj;
     double *x_final, *cost, *u_norm, *max_viol;
     int32_t *steps, *status;
+    double *v_traj, *e_traj, *w_traj;       // records of the noisy rollout
 };
+
+// ---- the uncertainty model of the noisy rollout (noise.py, ehm_explicit_set_noise) -----------
+//
+// Terms in model order; desc per term: kind (0 process, 1 state, 2 input), shape (0 box, 1 ball),
+// dim, ball norm code, radius dependency (0 const, 1 state, 2 input), its norm code, rows of F,
+// offset of the term's doubles (box: c, h, M [out][dim]; ball: sigma, F [rows][p or n_u],
+// L [out][dim]); norm codes 0 inf, 1, 2.  The doubles sit in LDS after the plant's.
+#define EHM_N_MAX_TERMS 16
+#define EHM_N_DESC 8
+#define EHM_N_MAX_BOX 8
+#define EHM_N_MAX_BALL 3
+#define EHM_N_MAX_F_ROWS 8
+#define EHM_N_ATTEMPTS 64
+#define EHM_N_MAX_LDS 8192       // doubles of plant and model together in the noisy kernel's LDS
+
+struct DevNoise {
+    const double* data;
+    int total, n_terms;
+    unsigned long long seed, traj0;
+    int desc[EHM_N_MAX_TERMS][EHM_N_DESC];
+};
+
+// The draw of one kind, summed over its terms in model order from 0.0 (OUT slots, n_out used),
+// counter (id, t, j, attempt) under the key (seed, 0).  No FMA: bit-equal to noise.py.
+template <int P, int NU, int OUT>
+__device__ __forceinline__ void noise_kind(const DevNoise& N, const double* sn, int kind,
+                                           int n_out, uint64_t id, uint64_t t, const double* x,
+                                           const double* u, double* acc) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int i = 0; i < OUT; ++i) acc[i] = 0.0;
+    for (int j = 0; j < N.n_terms; ++j) {
+        const int* ds = N.desc[j];
+        if (ds[0] != kind) continue;
+        const int dim = ds[2];
+        const double* td = sn + ds[7];
+        const double* map;
+        double q[EHM_N_MAX_BOX];
+        if (ds[1] == 0) {
+            uint64_t w[EHM_N_MAX_BOX];
+#pragma unroll
+            for (int b = 0; b < EHM_N_MAX_BOX / 4; ++b) {
+                uint64_t c[4] = {id, t, (uint64_t)j, (uint64_t)b};
+                if (4 * b < dim) ehm_philox4x64_10(c, N.seed, 0);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) w[4 * b + k] = c[k];
+            }
+#pragma unroll
+            for (int k = 0; k < EHM_N_MAX_BOX; ++k)
+                q[k] = (k < dim) ? td[k] + td[dim + k] * ehm_uniform_pm1(w[k]) : 0.0;
+            map = td + 2 * dim;
+        } else {
+            double r = td[0];
+            int off = 1;
+            if (ds[4] != 0) {
+                const int rows = ds[6], code = ds[5];
+                double nrm = 0.0;
+                for (int i = 0; i < rows; ++i) {
+                    double y = 0.0;
+                    if (ds[4] == 1) {
+#pragma unroll
+                        for (int c = 0; c < P; ++c) y += td[1 + i * P + c] * x[c];
+                    } else {
+#pragma unroll
+                        for (int c = 0; c < NU; ++c) y += td[1 + i * NU + c] * u[c];
+                    }
+                    if (code == 0) nrm = fmax(nrm, fabs(y));
+                    else if (code == 1) nrm += fabs(y);
+                    else nrm += y * y;
+                }
+                if (code == 2) nrm = sqrt(nrm);
+                r = r * nrm;
+                off += rows * (ds[4] == 1 ? P : NU);
+            }
+            double s[EHM_N_MAX_BALL];
+            if (ds[3] != 2) {
+                uint64_t c[4] = {id, t, (uint64_t)j, 0};
+                ehm_philox4x64_10(c, N.seed, 0);
+#pragma unroll
+                for (int k = 0; k < EHM_N_MAX_BALL; ++k) s[k] = ehm_uniform_pm1(c[k]);
+            } else {
+                // uniform in the 2-ball: rejection from the cube, zero after the last attempt
+                bool ok = false;
+                for (int a = 0; a < EHM_N_ATTEMPTS && !ok; ++a) {
+                    uint64_t c[4] = {id, t, (uint64_t)j, (uint64_t)a};
+                    ehm_philox4x64_10(c, N.seed, 0);
+                    double ss = 0.0;
+#pragma unroll
+                    for (int k = 0; k < EHM_N_MAX_BALL; ++k) {
+                        s[k] = ehm_uniform_pm1(c[k]);
+                        if (k < dim) ss += s[k] * s[k];
+                    }
+                    ok = ss <= 1.0;
+                }
+                if (!ok)
+#pragma unroll
+                    for (int k = 0; k < EHM_N_MAX_BALL; ++k) s[k] = 0.0;
+            }
+#pragma unroll
+            for (int k = 0; k < EHM_N_MAX_BOX; ++k)
+                q[k] = (k < EHM_N_MAX_BALL && k < dim) ? r * s[k < EHM_N_MAX_BALL ? k : 0] : 0.0;
+            map = td + off;
+        }
+#pragma unroll
+        for (int i = 0; i < OUT; ++i) {
+            if (i >= n_out) break;
+            double y = 0.0;
+#pragma unroll
+            for (int k = 0; k < EHM_N_MAX_BOX; ++k)
+                if (k < dim) y += map[i * dim + k] * q[k];
+            acc[i] += y;
+        }
+    }
+}
 
 // the sums of `contains` / `weights` with p fixed at compile time.  Kept outside any fp-contract
 // pragma, as those two are: the compiler fuses the same products into the same FMAs, so the
@@ -293,11 +409,17 @@ __device__ __forceinline__ void weights_t(const DevExplicit& E, long long k, con
     alpha0 = 1.0 - s;
 }
 
-template <int P, int NU>
-__global__ __launch_bounds__(256) void k_explicit_rollout(DevExplicit E, DevPlant PL, RollArgs R) {
+// NOISY: v, e and w are drawn from the model in NZ (noise_kind) instead of read from R.v / R.d:
+// v at the true state and the last commanded input, e and w at the true state and the commanded
+// input, e = 0 where u = 0; the plant steps with u + e, cost and ||u|| stay the commanded input's
+template <int P, int NU, bool NOISY>
+__global__ __launch_bounds__(256) void k_explicit_rollout(DevExplicit E, DevPlant PL, RollArgs R,
+                                                          DevNoise NZ) {
 #pragma clang fp contract(off)
     extern __shared__ double sh[];
     for (int i = threadIdx.x; i < PL.total; i += blockDim.x) sh[i] = PL.data[i];
+    if constexpr (NOISY)
+        for (int i = threadIdx.x; i < NZ.total; i += blockDim.x) sh[PL.total + i] = NZ.data[i];
     __syncthreads();
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= R.n) return;
@@ -308,6 +430,12 @@ __global__ __launch_bounds__(256) void k_explicit_rollout(DevExplicit E, DevPlan
     const double* sg = sh + PL.og;
     const double* sE = sh + PL.oE;
     double x[P], z[P], alpha[P], u[NU], xn[P], a0;
+    double up[NU], vn[P], en[NU], wn[EHM_R_MAX_D];       // noisy path only
+    const double* sn = sh + PL.total;
+    const uint64_t id = NZ.traj0 + (uint64_t)q;
+    if constexpr (NOISY)
+#pragma unroll
+        for (int c = 0; c < NU; ++c) up[c] = 0.0;
 #pragma unroll
     for (int c = 0; c < P; ++c) x[c] = R.x0[q * P + c];
     if (R.x_traj)
@@ -318,7 +446,14 @@ __global__ __launch_bounds__(256) void k_explicit_rollout(DevExplicit E, DevPlan
     int kr = (int)(q % E.n_roots);          // warm start of the root locator: the last step's root
     for (; t < R.T; ++t) {
         // measure
-        if (R.v && t > 0) {
+        if constexpr (NOISY) {
+            noise_kind<P, NU, P>(NZ, sn, 1, P, id, (uint64_t)t, x, up, vn);
+            if (R.v_traj)
+#pragma unroll
+                for (int c = 0; c < P; ++c) R.v_traj[((size_t)t * n + q) * P + c] = vn[c];
+#pragma unroll
+            for (int c = 0; c < P; ++c) z[c] = t > 0 ? x[c] + vn[c] : x[c];
+        } else if (R.v && t > 0) {
 #pragma unroll
             for (int c = 0; c < P; ++c) z[c] = x[c] + R.v[((size_t)t * n + q) * P + c];
         } else {
@@ -446,6 +581,29 @@ __global__ __launch_bounds__(256) void k_explicit_rollout(DevExplicit E, DevPlan
             }
             cost += s;
         }
+        // input error and process noise at (x, u)
+        double ua[NU];
+#pragma unroll
+        for (int c = 0; c < NU; ++c) ua[c] = u[c];
+        if constexpr (NOISY) {
+            noise_kind<P, NU, NU>(NZ, sn, 2, NU, id, (uint64_t)t, x, u, en);
+            if (su == 0.0)
+#pragma unroll
+                for (int c = 0; c < NU; ++c) en[c] = 0.0;
+            noise_kind<P, NU, EHM_R_MAX_D>(NZ, sn, 0, PL.n_d, id, (uint64_t)t, x, u, wn);
+#pragma unroll
+            for (int c = 0; c < NU; ++c) {
+                ua[c] = u[c] + en[c];
+                up[c] = u[c];
+            }
+            if (R.e_traj)
+#pragma unroll
+                for (int c = 0; c < NU; ++c) R.e_traj[((size_t)t * n + q) * NU + c] = en[c];
+            if (R.w_traj)
+#pragma unroll
+                for (int j = 0; j < EHM_R_MAX_D; ++j)
+                    if (j < PL.n_d) R.w_traj[((size_t)t * n + q) * PL.n_d + j] = wn[j];
+        }
         // plant step x+ = A_m x + B_m u + w_m + E d
         const double* sA = sh + PL.oA + m * P * P;
         const double* sB = sh + PL.oB + m * P * NU;
@@ -457,10 +615,15 @@ __global__ __launch_bounds__(256) void k_explicit_rollout(DevExplicit E, DevPlan
 #pragma unroll
             for (int c = 0; c < P; ++c) s += sA[i * P + c] * x[c];
 #pragma unroll
-            for (int c = 0; c < NU; ++c) s += sB[i * NU + c] * u[c];
+            for (int c = 0; c < NU; ++c) s += sB[i * NU + c] * ua[c];
             s += sw[i];
-            if (dt)
+            if constexpr (NOISY) {
+#pragma unroll
+                for (int j = 0; j < EHM_R_MAX_D; ++j)
+                    if (j < PL.n_d) s += sE[i * PL.n_d + j] * wn[j];
+            } else if (dt) {
                 for (int j = 0; j < PL.n_d; ++j) s += sE[i * PL.n_d + j] * dt[j];
+            }
             xn[i] = s;
         }
         for (int j = 0; j < PL.n_g; ++j) {
@@ -485,6 +648,17 @@ __global__ __launch_bounds__(256) void k_explicit_rollout(DevExplicit E, DevPlan
 #pragma unroll
             for (int c = 0; c < NU; ++c) R.u_traj[((size_t)s * n + q) * NU + c] = nan;
         if (R.leaf_traj) R.leaf_traj[(size_t)s * n + q] = -1;
+        if constexpr (NOISY) {
+            // v of the step a trajectory stopped at was drawn and is kept
+            if (R.v_traj && s > t)
+#pragma unroll
+                for (int c = 0; c < P; ++c) R.v_traj[((size_t)s * n + q) * P + c] = nan;
+            if (R.e_traj)
+#pragma unroll
+                for (int c = 0; c < NU; ++c) R.e_traj[((size_t)s * n + q) * NU + c] = nan;
+            if (R.w_traj)
+                for (int j = 0; j < PL.n_d; ++j) R.w_traj[((size_t)s * n + q) * PL.n_d + j] = nan;
+        }
     }
 #pragma unroll
     for (int c = 0; c < P; ++c) R.x_final[q * P + c] = x[c];
@@ -495,13 +669,26 @@ __global__ __launch_bounds__(256) void k_explicit_rollout(DevExplicit E, DevPlan
     R.max_viol[q] = maxv;
 }
 
-typedef void (*rollout_fn)(DevExplicit, DevPlant, RollArgs);
-#define EHM_R_NU(P) &k_explicit_rollout<P, 1>, &k_explicit_rollout<P, 2>, \
-                    &k_explicit_rollout<P, 3>, &k_explicit_rollout<P, 4>
-const rollout_fn k_rollout_table[EHM_XP][EHM_R_MAX_NU] = {
-    {EHM_R_NU(1)}, {EHM_R_NU(2)}, {EHM_R_NU(3)}, {EHM_R_NU(4)},
-    {EHM_R_NU(5)}, {EHM_R_NU(6)}, {EHM_R_NU(7)}, {EHM_R_NU(8)}};
+typedef void (*rollout_fn)(DevExplicit, DevPlant, RollArgs, DevNoise);
+#define EHM_R_NU(P, Z) &k_explicit_rollout<P, 1, Z>, &k_explicit_rollout<P, 2, Z>, \
+                       &k_explicit_rollout<P, 3, Z>, &k_explicit_rollout<P, 4, Z>
+#define EHM_R_ALL(Z) {EHM_R_NU(1, Z)}, {EHM_R_NU(2, Z)}, {EHM_R_NU(3, Z)}, {EHM_R_NU(4, Z)}, \
+                     {EHM_R_NU(5, Z)}, {EHM_R_NU(6, Z)}, {EHM_R_NU(7, Z)}, {EHM_R_NU(8, Z)}
+const rollout_fn k_rollout_table[EHM_XP][EHM_R_MAX_NU] = {EHM_R_ALL(false)};
+const rollout_fn k_rollout_noisy_table[EHM_XP][EHM_R_MAX_NU] = {EHM_R_ALL(true)};
+#undef EHM_R_ALL
 #undef EHM_R_NU
+
+// raw Philox4x64-10 blocks (the oracle test of the generator)
+__global__ void k_philox_batch(long long n, const uint64_t* __restrict__ ctr, uint64_t k0,
+                               uint64_t k1, uint64_t* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint64_t c[4] = {ctr[4 * i], ctr[4 * i + 1], ctr[4 * i + 2], ctr[4 * i + 3]};
+    ehm_philox4x64_10(c, k0, k1);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out[4 * i + k] = c[k];
+}
 
 // EHM_EXPLICIT_LOCATE=0 in the environment: the reference's serial walk for every state
 bool locate_off() {
@@ -533,6 +720,9 @@ struct ehm_explicit {
     void* nbr = nullptr;        // [n_roots][p+1] root across the face opposite vertex i (-1: hull)
     void *plant = nullptr, *node_mode = nullptr;     // ehm_explicit_set_plant
     DevPlant pl{};
+    void* noise = nullptr;                           // ehm_explicit_set_noise
+    DevNoise nz{};
+    int noise_n_d = 0;
     size_t cap = 0;
     hipStream_t stream = nullptr;
 };
@@ -545,7 +735,7 @@ int ehm_explicit_destroy(ehm_explicit* E) {
     if (!E) return EHM_OK;
     (void)hipSetDevice(E->device);
     for (void* p : {E->rec, E->child, E->vinput, E->x, E->u, E->leaf, E->depth, E->root, E->nbr,
-                    E->plant, E->node_mode})
+                    E->plant, E->node_mode, E->noise})
         if (p) (void)hipFree(p);
     if (E->stream) (void)hipStreamDestroy(E->stream);
     delete E;
@@ -796,17 +986,32 @@ int ehm_explicit_set_plant(ehm_explicit* E, int32_t n_modes, const double* A, co
     return EHM_OK;
 }
 
-int ehm_explicit_rollout(ehm_explicit* E, int64_t n, int32_t T, const double* x0,
-                         const double* d, const double* v, double tol_exit, double* x_traj,
-                         double* u_traj, int32_t* leaf_traj, double* x_final, int32_t* steps,
-                         int32_t* status, double* cost, double* u_norm_sum,
-                         double* max_violation, double* kernel_seconds) {
+}  // extern "C"
+
+namespace {
+
+// the noisy rollout's extra arguments
+struct NoisyCall {
+    uint64_t seed, traj0;
+    double *v_traj, *e_traj, *w_traj;
+};
+
+// ehm_explicit_rollout (nz == nullptr) and ehm_explicit_rollout_noisy
+int rollout_run(ehm_explicit* E, int64_t n, int32_t T, const double* x0, const double* d,
+                const double* v, double tol_exit, double* x_traj, double* u_traj,
+                int32_t* leaf_traj, double* x_final, int32_t* steps, int32_t* status,
+                double* cost, double* u_norm_sum, double* max_violation, double* kernel_seconds,
+                const NoisyCall* nz) {
     if (!E || !x0 || !x_final || !steps || !status || !cost || !u_norm_sum || !max_violation ||
         n < 0 || T < 0 || !(tol_exit >= 0.0))
         return xfail(EHM_E_INVALID, "rollout: bad argument");
     if (!E->plant) return xfail(EHM_E_INVALID, "rollout: no plant (ehm_explicit_set_plant)");
     if (d && E->pl.n_d == 0)
         return xfail(EHM_E_INVALID, "rollout: a disturbance was given but the plant has no E");
+    // a plant set after the model may have grown past what set_noise checked
+    if (nz && E->pl.total + E->nz.total > EHM_N_MAX_LDS)
+        return xfail(EHM_E_INVALID, "rollout_noisy: plant and model take %d doubles of LDS (%d)",
+                     E->pl.total + E->nz.total, EHM_N_MAX_LDS);
     const int p = E->d.p, n_u = E->d.n_u;
     if (n == 0) return EHM_OK;
     if (n > (int64_t)1 << 31) return xfail(EHM_E_INVALID, "rollout: %lld trajectories", (long long)n);
@@ -842,9 +1047,13 @@ int ehm_explicit_rollout(ehm_explicit* E, int64_t n, int32_t T, const double* x0
     if (x_traj) R.x_traj = (double*)bufs.get((nT + 1) * N * p * sizeof(double));
     if (u_traj) R.u_traj = (double*)bufs.get(nT * N * n_u * sizeof(double));
     if (leaf_traj) R.leaf_traj = (int32_t*)bufs.get(nT * N * sizeof(int32_t));
+    if (nz && nz->v_traj) R.v_traj = (double*)bufs.get(nT * N * p * sizeof(double));
+    if (nz && nz->e_traj) R.e_traj = (double*)bufs.get(nT * N * n_u * sizeof(double));
+    if (nz && nz->w_traj) R.w_traj = (double*)bufs.get(nT * N * E->pl.n_d * sizeof(double));
     if (!dx0 || !R.x_final || !R.cost || !R.u_norm || !R.max_viol || !R.steps || !R.status ||
         (d && !dd) || (v && !dv) || (x_traj && !R.x_traj) || (u_traj && !R.u_traj) ||
-        (leaf_traj && !R.leaf_traj))
+        (leaf_traj && !R.leaf_traj) || (nz && nz->v_traj && !R.v_traj) ||
+        (nz && nz->e_traj && !R.e_traj) || (nz && nz->w_traj && !R.w_traj))
         return xfail(EHM_E_HIP, "rollout: out of device memory for %lld x %d steps",
                      (long long)n, (int)T);
     R.x0 = dx0;
@@ -863,9 +1072,17 @@ int ehm_explicit_rollout(ehm_explicit* E, int64_t n, int32_t T, const double* x0
     (void)hipEventCreate(&e0);
     (void)hipEventCreate(&e1);
     (void)hipEventRecord(e0, E->stream);
-    hipLaunchKernelGGL(k_rollout_table[p - 1][n_u - 1], dim3((unsigned)((n + 255) / 256)),
-                       dim3(256), (size_t)E->pl.total * sizeof(double), E->stream, E->d, E->pl,
-                       R);
+    DevNoise NZ{};
+    size_t lds = (size_t)E->pl.total * sizeof(double);
+    if (nz) {
+        NZ = E->nz;
+        NZ.seed = nz->seed;
+        NZ.traj0 = nz->traj0;
+        lds += (size_t)NZ.total * sizeof(double);
+    }
+    hipLaunchKernelGGL((nz ? k_rollout_noisy_table : k_rollout_table)[p - 1][n_u - 1],
+                       dim3((unsigned)((n + 255) / 256)), dim3(256), lds, E->stream, E->d, E->pl,
+                       R, NZ);
     (void)hipEventRecord(e1, E->stream);
     Y_TRY(hipGetLastError());
     Y_TRY(hipMemcpyAsync(x_final, R.x_final, N * p * sizeof(double), hipMemcpyDeviceToHost,
@@ -887,6 +1104,15 @@ int ehm_explicit_rollout(ehm_explicit* E, int64_t n, int32_t T, const double* x0
     if (leaf_traj)
         Y_TRY(hipMemcpyAsync(leaf_traj, R.leaf_traj, nT * N * sizeof(int32_t),
                              hipMemcpyDeviceToHost, E->stream));
+    if (R.v_traj)
+        Y_TRY(hipMemcpyAsync(nz->v_traj, R.v_traj, nT * N * p * sizeof(double),
+                             hipMemcpyDeviceToHost, E->stream));
+    if (R.e_traj)
+        Y_TRY(hipMemcpyAsync(nz->e_traj, R.e_traj, nT * N * n_u * sizeof(double),
+                             hipMemcpyDeviceToHost, E->stream));
+    if (R.w_traj)
+        Y_TRY(hipMemcpyAsync(nz->w_traj, R.w_traj, nT * N * E->pl.n_d * sizeof(double),
+                             hipMemcpyDeviceToHost, E->stream));
     Y_TRY(hipStreamSynchronize(E->stream));
     if (kernel_seconds) {
         float ms = 0.f;
@@ -895,6 +1121,110 @@ int ehm_explicit_rollout(ehm_explicit* E, int64_t n, int32_t T, const double* x0
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
+    return EHM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ehm_explicit_rollout(ehm_explicit* E, int64_t n, int32_t T, const double* x0,
+                         const double* d, const double* v, double tol_exit, double* x_traj,
+                         double* u_traj, int32_t* leaf_traj, double* x_final, int32_t* steps,
+                         int32_t* status, double* cost, double* u_norm_sum,
+                         double* max_violation, double* kernel_seconds) {
+    return rollout_run(E, n, T, x0, d, v, tol_exit, x_traj, u_traj, leaf_traj, x_final, steps,
+                       status, cost, u_norm_sum, max_violation, kernel_seconds, nullptr);
+}
+
+int ehm_explicit_set_noise(ehm_explicit* E, int32_t n_terms, const int32_t* desc,
+                           const double* data, int32_t n_data, int32_t n_d) {
+    if (!E || n_terms < 0 || n_terms > EHM_N_MAX_TERMS || (n_terms > 0 && !desc) || n_data < 0 ||
+        (n_data > 0 && !data) || n_d < 0 || n_d > EHM_R_MAX_D)
+        return xfail(EHM_E_INVALID, "set_noise: bad argument (at most %d terms, n_d <= %d)",
+                     EHM_N_MAX_TERMS, EHM_R_MAX_D);
+    const int p = E->d.p, n_u = E->d.n_u;
+    DevNoise nz{};
+    nz.n_terms = n_terms;
+    nz.total = n_data;
+    for (int j = 0; j < n_terms; ++j) {
+        const int32_t* ds = desc + (size_t)j * EHM_N_DESC;
+        const int kind = ds[0], shape = ds[1], dim = ds[2], norm = ds[3], dep = ds[4],
+                  pdep = ds[5], rows = ds[6], off = ds[7];
+        const int out = kind == 0 ? n_d : kind == 1 ? p : n_u;
+        long long need = -1;
+        if (kind < 0 || kind > 2 || off < 0) {
+        } else if (shape == 0 && dim >= 1 && dim <= EHM_N_MAX_BOX) {
+            need = 2LL * dim + (long long)out * dim;
+        } else if (shape == 1 && dim >= 1 && dim <= EHM_N_MAX_BALL && norm >= 0 && norm <= 2 &&
+                   (norm != 1 || dim == 1) && dep >= 0 && dep <= 2 && pdep >= 0 && pdep <= 2 &&
+                   rows >= 0 && rows <= EHM_N_MAX_F_ROWS && (dep != 0 || rows == 0)) {
+            need = 1LL + (long long)rows * (dep == 1 ? p : n_u) + (long long)out * dim;
+        }
+        if (need < 0 || off + need > n_data)
+            return xfail(EHM_E_INVALID, "set_noise: term %d has a bad descriptor", j);
+        for (int k = 0; k < EHM_N_DESC; ++k) nz.desc[j][k] = ds[k];
+    }
+    if (E->pl.total + n_data > EHM_N_MAX_LDS)
+        return xfail(EHM_E_INVALID, "set_noise: plant and model take %d doubles of LDS (%d)",
+                     E->pl.total + n_data, EHM_N_MAX_LDS);
+    hipError_t e = hipSetDevice(E->device);
+    if (e != hipSuccess) return xfail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
+    void* d_noise = nullptr;
+    if (hipMalloc(&d_noise, (size_t)(n_data ? n_data : 1) * sizeof(double)) != hipSuccess ||
+        (n_data > 0 && hipMemcpy(d_noise, data, (size_t)n_data * sizeof(double),
+                                 hipMemcpyHostToDevice) != hipSuccess)) {
+        if (d_noise) (void)hipFree(d_noise);
+        return xfail(EHM_E_HIP, "set_noise: device allocation / copy failed");
+    }
+    if (E->noise) (void)hipFree(E->noise);
+    E->noise = d_noise;
+    nz.data = (const double*)d_noise;
+    E->nz = nz;
+    E->noise_n_d = n_d;
+    return EHM_OK;
+}
+
+int ehm_explicit_rollout_noisy(ehm_explicit* E, int64_t n, int32_t T, const double* x0,
+                               uint64_t seed, uint64_t traj0, double tol_exit, double* x_traj,
+                               double* u_traj, int32_t* leaf_traj, double* v_traj,
+                               double* e_traj, double* w_traj, double* x_final, int32_t* steps,
+                               int32_t* status, double* cost, double* u_norm_sum,
+                               double* max_violation, double* kernel_seconds) {
+    if (!E) return xfail(EHM_E_INVALID, "rollout_noisy: no handle");
+    if (!E->noise) return xfail(EHM_E_INVALID, "rollout_noisy: no model (ehm_explicit_set_noise)");
+    if (E->plant && E->noise_n_d != E->pl.n_d)
+        return xfail(EHM_E_INVALID, "rollout_noisy: the model has n_d = %d, the plant %d",
+                     E->noise_n_d, E->pl.n_d);
+    const NoisyCall nz{seed, traj0, v_traj, e_traj, w_traj};
+    return rollout_run(E, n, T, x0, nullptr, nullptr, tol_exit, x_traj, u_traj, leaf_traj,
+                       x_final, steps, status, cost, u_norm_sum, max_violation, kernel_seconds,
+                       &nz);
+}
+
+int ehm_philox_batch(int64_t n, const uint64_t* counters, const uint64_t* key, uint64_t* out) {
+    if (n < 0 || (n > 0 && (!counters || !key || !out)))
+        return xfail(EHM_E_INVALID, "philox_batch: bad argument");
+    if (n == 0) return EHM_OK;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return xfail(EHM_E_NO_DEVICE, "philox_batch: %s", hipGetErrorString(e));
+    uint64_t *dc = nullptr, *dout = nullptr;
+    const size_t bytes = (size_t)n * 4 * sizeof(uint64_t);
+    struct Free {
+        uint64_t **a, **b;
+        ~Free() {
+            if (*a) (void)hipFree(*a);
+            if (*b) (void)hipFree(*b);
+        }
+    } fr{&dc, &dout};
+    Y_TRY(hipMalloc(&dc, bytes));
+    Y_TRY(hipMalloc(&dout, bytes));
+    Y_TRY(hipMemcpy(dc, counters, bytes, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_philox_batch, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0,
+                       (long long)n, (const uint64_t*)dc, key[0], key[1], dout);
+    Y_TRY(hipGetLastError());
+    Y_TRY(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
     return EHM_OK;
 }
 

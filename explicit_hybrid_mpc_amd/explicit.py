@@ -96,24 +96,28 @@ class ImplicitMPC:
         if hasattr(mpc, 'specs'):
             self.specs = mpc.specs
         self.__oracle = oracle
+        self.mpc = mpc
 
     def __call__(self, x):
         """(u, t): epsilon-suboptimal (here: optimal) input and evaluation time."""
         u, _, _, t = self.__oracle.P_theta(x)
         return u, t
 
-    def rollout(self, X0, T, d=None, v=None, record=True, tol_exit=1e-9, plant=None):
+    def rollout(self, X0, T, d=None, v=None, record=True, tol_exit=1e-9, plant=None, noise=None,
+                seed=0, traj0=0):
         """
         Closed loop from the states X0 [n, p] for T steps (simulate.py): per step one batched
         P_theta over the live trajectories, the plant (default ``Plant.from_mpc``) stepped in
-        the step-0 mode of the returned commutation.  Returns a ``simulate.ClosedLoop``.
+        the step-0 mode of the returned commutation.  ``noise`` (a ``noise.NoiseModel``) draws
+        v, e and d on the host with the counters of the device rollout (trajectory q has id
+        traj0 + q).  Returns a ``simulate.ClosedLoop``.
         """
         from . import simulate
         if plant is None:
             plant = simulate.Plant.from_mpc(self.__oracle.mpc)
         self._rollout_plant = plant
         return simulate.rollout_implicit(self.__oracle, plant, X0, T, d=d, v=v, record=record,
-                                         tol_exit=tol_exit)
+                                         tol_exit=tol_exit, noise=noise, seed=seed, traj0=traj0)
 
     def evaluate(self, X):
         """Inputs for a batch of states (n, p) -> (n, n_u); NaN rows where infeasible."""
@@ -217,15 +221,38 @@ class ExplicitMPC:
             ptr(R)))
         self._rollout_plant = plant
 
-    def rollout(self, X0, T, d=None, v=None, record=True, tol_exit=1e-9, plant=None):
+    def set_noise(self, model, plant):
+        """Hands the uncertainty model (``noise.NoiseModel``) to the device; a no-op when the
+        device already holds the same packed model for the same n_d."""
+        if (model.n_x, model.n_u, model.n_d) != (self.p, self.n_u, plant.n_d):
+            raise ValueError('noise model (n_x %d, n_u %d, n_d %d) does not fit the law and plant '
+                             '(%d, %d, %d)' % (model.n_x, model.n_u, model.n_d, self.p, self.n_u,
+                                               plant.n_d))
+        desc, data = model.pack()
+        held = getattr(self, '_noise_packed', None)
+        if held is not None and held[2] == plant.n_d and np.array_equal(held[0], desc) \
+                and np.array_equal(held[1], data):
+            return
+        self._noise_packed = None
+        _check(self._lib.ehm_explicit_set_noise(self._handle, desc.shape[0], ptr(desc),
+                                                ptr(data) if data.size else None, data.size,
+                                                plant.n_d))
+        self._noise_packed = (desc, data, plant.n_d)
+
+    def rollout(self, X0, T, d=None, v=None, record=True, tol_exit=1e-9, plant=None, noise=None,
+                seed=0, traj0=0):
         """
         Closed loop from the states X0 [n, p] for T steps in ONE kernel launch
         (ehm_explicit_rollout, one device thread per trajectory; conventions in simulate.py).
         ``plant`` defaults to ``Plant.from_mpc`` of the oracle's law; d [T, n, n_d] and
-        v [T, n, p] are optional.  Returns a ``simulate.ClosedLoop`` (leaf, commutation and
-        mode recorded with ``record``).
+        v [T, n, p] are optional.  With ``noise`` (a ``noise.NoiseModel``, not together with d
+        or v) the kernel draws v, e and d itself (ehm_explicit_rollout_noisy, Philox key seed,
+        trajectory q has id traj0 + q).  Returns a ``simulate.ClosedLoop`` (leaf, commutation,
+        mode -- and v, e, w under noise -- recorded with ``record``).
         """
         from . import simulate
+        if noise is not None and (d is not None or v is not None):
+            raise ValueError('noise draws d and v itself: give noise or d / v, not both')
         if plant is None:
             plant = self._rollout_plant
             if plant is None:
@@ -241,6 +268,8 @@ class ExplicitMPC:
             raise ValueError('X0 must be [n, %d] and T >= 0' % self.p)
         d = simulate._as_batch(d, (T, n, plant.n_d), 'd')
         v = simulate._as_batch(v, (T, n, p), 'v')
+        if noise is not None:
+            self.set_noise(noise, plant)
         x_final = np.empty((n, p))
         steps = np.empty(n, dtype=np.int32)
         status = np.empty(n, dtype=np.int32)
@@ -249,13 +278,26 @@ class ExplicitMPC:
         us = np.empty((T, n, self.n_u)) if record else None
         leaf = np.empty((T, n), dtype=np.int32) if record else None
         secs = ctypes.c_double(0.)
-        _check(self._lib.ehm_explicit_rollout(
-            self._handle, n, T, ptr(X0), None if d is None else ptr(d),
-            None if v is None else ptr(v), float(tol_exit), None if xs is None else ptr(xs),
-            None if us is None else ptr(us), None if leaf is None else ptr(leaf), ptr(x_final),
-            ptr(steps), ptr(status), ptr(cost), ptr(unorm), ptr(maxv), ctypes.addressof(secs)))
+        if noise is None:
+            _check(self._lib.ehm_explicit_rollout(
+                self._handle, n, T, ptr(X0), None if d is None else ptr(d),
+                None if v is None else ptr(v), float(tol_exit), None if xs is None else ptr(xs),
+                None if us is None else ptr(us), None if leaf is None else ptr(leaf),
+                ptr(x_final), ptr(steps), ptr(status), ptr(cost), ptr(unorm), ptr(maxv),
+                ctypes.addressof(secs)))
+        else:
+            vs = np.empty((T, n, p)) if record else None
+            es = np.empty((T, n, self.n_u)) if record else None
+            ws = np.empty((T, n, plant.n_d)) if record else None
+            opt = [None if a is None else ptr(a) for a in (xs, us, leaf, vs, es, ws)]
+            _check(self._lib.ehm_explicit_rollout_noisy(
+                self._handle, n, T, ptr(X0), int(seed), int(traj0), float(tol_exit), *opt,
+                ptr(x_final), ptr(steps), ptr(status), ptr(cost), ptr(unorm), ptr(maxv),
+                ctypes.addressof(secs)))
         out = simulate.ClosedLoop(x_final=x_final, steps=steps, status=status, cost=cost,
                                   u_norm_sum=unorm, max_violation=maxv, seconds=secs.value)
+        if noise is not None and record:
+            out.v, out.e, out.w = vs, es, ws
         if record:
             out.x, out.u, out.leaf = xs, us, leaf
             live = leaf >= 0

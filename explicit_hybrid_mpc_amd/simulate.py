@@ -15,7 +15,12 @@ does not hold z_t (a barycentric weight < -tol_exit: the state left the partitio
 reference would extrapolate), 2 if mode m's region does not hold x_t (theory says this cannot
 happen: a check), 3 if there is no law at z_t (implicit: P_theta infeasible; explicit: a leaf
 without a commutation).  Disturbances d [T][n][n_d] and measurement errors v [T][n][p] are passed
-in by the caller; the reference's state-dependent noise samplers are not reproduced.
+in by the caller, or drawn from an uncertainty model (``noise=``, a ``noise.NoiseModel``; the
+reference's samplers, lib/simulator.py:160-180): at step t, v_t at the true state x_t and the last
+commanded input, then the law's u_t, then the input error e_t (0 where u_t = 0) and d_t at x_t and
+u_t; the plant steps with u_t + e_t, while cost, sum ||u|| and the recorded u stay the commanded
+input's.  Both laws draw with the same counters (trajectory id traj0 + q), so the explicit and the
+implicit rollout of one seed see common random numbers.
 """
 
 import time
@@ -106,7 +111,8 @@ class ClosedLoop:
     Result of a batched rollout (n trajectories, T steps).  Records, time-major, None unless
     asked for: x [T+1, n, n_x], u [T, n, n_u] (NaN after a stop), leaf [T, n] (explicit law,
     -1 after a stop), commutation [T, n] (index into the law's commutations, -1 after a stop),
-    mode [T, n] (applied mode, -1 after a stop).  Always: x_final [n, n_x], steps [n], status [n]
+    mode [T, n] (applied mode, -1 after a stop); under a noise model also v [T, n, n_x] (NaN
+    after the step a trajectory stopped at), e [T, n, n_u] and w [T, n, n_d] (NaN from it on).  Always: x_final [n, n_x], steps [n], status [n]
     (STATUS_*), cost [n] (summed stage cost), u_norm_sum [n] (sum_t ||u_t||_2), max_violation [n]
     (max_t max_j (Gx x_{t+1} - gx)_j, -inf without a step), seconds (device time of the explicit
     rollout kernel / wall time of the implicit loop).
@@ -114,6 +120,7 @@ class ClosedLoop:
 
     def __init__(self, **kw):
         self.x = self.u = self.leaf = self.commutation = self.mode = None
+        self.v = self.e = self.w = None
         self.seconds = 0.
         self.__dict__.update(kw)
 
@@ -135,16 +142,24 @@ def _as_batch(a, shape, name):
     return a
 
 
-def rollout_implicit(oracle, plant, X0, T, d=None, v=None, record=True, tol_exit=1e-9):
+def rollout_implicit(oracle, plant, X0, T, d=None, v=None, record=True, tol_exit=1e-9, noise=None,
+                     seed=0, traj0=0):
     """
     The implicit law in closed loop: per step one batched ``solve_pt`` (the device's
     mixed-integer oracle) over the live trajectories, the plant step on the host with the
-    conventions of the module docstring.  Returns a ClosedLoop (commutation, no leaf).
+    conventions of the module docstring (``noise``: v, e, d from the host sampler of the
+    model).  Returns a ClosedLoop (commutation, no leaf).
     """
     X0 = np.ascontiguousarray(np.atleast_2d(X0), dtype=np.float64)
     n, p = X0.shape
+    if noise is not None and (d is not None or v is not None):
+        raise ValueError('noise draws d and v itself: give noise or d / v, not both')
     d = _as_batch(d, (T, n, plant.n_d), 'd')
     v = _as_batch(v, (T, n, p), 'v')
+    if noise is not None and (noise.n_x, noise.n_u, noise.n_d) != (p, plant.n_u, plant.n_d):
+        raise ValueError('the noise model does not fit the plant')
+    ids = np.uint64(int(traj0)) + np.arange(n, dtype=np.uint64)
+    u_prev = np.zeros((n, plant.n_u))
     can = oracle.canonical
     mode_of = np.array([oracle.mpc.step0_mode(dl) for dl in can.deltas], dtype=np.int64)
     x = X0.copy()
@@ -158,12 +173,22 @@ def rollout_implicit(oracle, plant, X0, T, d=None, v=None, record=True, tol_exit
         us = np.full((T, n, plant.n_u), np.nan)
         cs = np.full((T, n), -1, dtype=np.int32)
         ms = np.full((T, n), -1, dtype=np.int32)
+        if noise is not None:
+            vs = np.full((T, n, p), np.nan)
+            es = np.full((T, n, plant.n_u), np.nan)
+            ws = np.full((T, n, plant.n_d), np.nan)
     live = np.arange(n)
     tic = time.time()
     for t in range(T):
         if live.size == 0:
             break
-        z = x[live] + v[t, live] if (v is not None and t > 0) else x[live]
+        if noise is not None:
+            vt = noise.sample('state', seed, ids[live], t, x[live], u_prev[live])
+            if record:
+                vs[t, live] = vt
+            z = x[live] + vt if t > 0 else x[live]
+        else:
+            z = x[live] + v[t, live] if (v is not None and t > 0) else x[live]
         _, u0, didx = oracle.gpu.solve_pt(z)
         bad = (didx < 0) | ~np.all(np.isfinite(u0), axis=1)
         m = mode_of[np.maximum(didx, 0)]
@@ -176,7 +201,19 @@ def rollout_implicit(oracle, plant, X0, T, d=None, v=None, record=True, tol_exit
         xl = x[live]
         cost[live] += plant.stage_cost(xl, u0)
         unorm[live] += np.sqrt(np.sum(u0 * u0, axis=1))
-        xn = plant.step(xl, u0, m, None if d is None else d[t, live])
+        if noise is not None:
+            su = np.zeros(live.size)
+            for c in range(plant.n_u):
+                su = su + u0[:, c] * u0[:, c]
+            et = noise.sample('input', seed, ids[live], t, xl, u0)
+            et[su == 0.] = 0.
+            wt = noise.sample('process', seed, ids[live], t, xl, u0)
+            u_prev[live] = u0
+            if record:
+                es[t, live], ws[t, live] = et, wt
+            xn = plant.step(xl, u0 + et, m, wt if plant.n_d else None)
+        else:
+            xn = plant.step(xl, u0, m, None if d is None else d[t, live])
         if plant.gx.size:
             maxv[live] = np.maximum(maxv[live], (xn @ plant.Gx.T - plant.gx).max(axis=1))
         x[live] = xn
@@ -189,21 +226,28 @@ def rollout_implicit(oracle, plant, X0, T, d=None, v=None, record=True, tol_exit
                      max_violation=maxv, seconds=time.time() - tic)
     if record:
         out.x, out.u, out.commutation, out.mode = xs, us, cs, ms
+        if noise is not None:
+            out.v, out.e, out.w = vs, es, ws
     return out
 
 
-def compare(explicit, implicit, X0, T, d=None, v=None, tol_exit=1e-9, record=False):
+def compare(explicit, implicit, X0, T, d=None, v=None, tol_exit=1e-9, record=False, noise=None,
+            seed=0):
     """
-    The explicit against the implicit law from the same initial states under the same d / v
-    (total_delta_v_usage, lib/post_process.py:242-266).  Per trajectory: ``overconsumption``
+    The explicit against the implicit law from the same initial states under the same d / v, or
+    under the same draws of a noise model (common random numbers: one seed, the same trajectory
+    ids) (total_delta_v_usage, lib/post_process.py:242-266).  Per trajectory: ``overconsumption``
     = (sum ||u||_ex - sum ||u||_im) / sum ||u||_im and ``cost_ratio`` = cost_ex / cost_im (NaN
     where the implicit figure is 0).  Aggregates over the trajectories both laws ran for all T
     steps (``both_ok``): ``overconsumption_total`` (the statistic of total_delta_v_usage over
     the summed usage) and ``cost_ratio_total``.  Also the exit / stop counts and the two
     ClosedLoop results (``explicit``, ``implicit``).
     """
-    ex = explicit.rollout(X0, T, d=d, v=v, record=record, tol_exit=tol_exit)
-    im = implicit.rollout(X0, T, d=d, v=v, record=record, tol_exit=tol_exit)
+    kw = dict(d=d, v=v, record=record, tol_exit=tol_exit)
+    if noise is not None:
+        kw.update(noise=noise, seed=seed)
+    ex = explicit.rollout(X0, T, **kw)
+    im = implicit.rollout(X0, T, **kw)
     both = (ex.status == STATUS_OK) & (im.status == STATUS_OK)
     with np.errstate(divide='ignore', invalid='ignore'):
         over = np.where(im.u_norm_sum > 0, (ex.u_norm_sum - im.u_norm_sum) / im.u_norm_sum,
@@ -237,12 +281,22 @@ class Simulator:
     ``Simulator(mpc, T).run(x_0, label)`` of lib/simulator.py:73-188 for a law with a
     ``rollout`` (``ExplicitMPC`` / ``ImplicitMPC``): T is the final time, the plant runs at the
     controller's period T_s (1 if the law has none), so the run has int(T / T_s + 1) steps, as
-    the reference's time grid.  Nominal (no noise); a trajectory that stops ends the record.
+    the reference's time grid.  ``noise``: a ``noise.NoiseModel``, 'reference' for the one the law
+    was tightened against (``NoiseModel.from_mpc``), or None (nominal); w, v and e of the record
+    are its draws.  A trajectory that stops ends the record.
     """
 
-    def __init__(self, mpc, T):
+    def __init__(self, mpc, T, noise=None, seed=0):
         self.law = mpc
         self.T_f = T
+        if isinstance(noise, str):
+            if noise != 'reference':
+                raise ValueError("noise must be a NoiseModel, 'reference' or None")
+            from .noise import NoiseModel
+            noise = NoiseModel.from_mpc(mpc.mpc)
+            if noise is None:
+                raise ValueError('the law has no uncertainty model of its own')
+        self.noise, self.seed = noise, seed
         self.h = getattr(mpc, 'T_s', None) or 1.
         self.sim_history = SimulationOutput()
 
@@ -251,7 +305,9 @@ class Simulator:
         if label is not None:
             out.label = label
         times = np.linspace(0, self.T_f, int(self.T_f / self.h + 1))
-        res = self.law.rollout(np.asarray(x_0, dtype=np.float64)[None], len(times), record=True)
+        kw = {} if self.noise is None else dict(noise=self.noise, seed=self.seed)
+        res = self.law.rollout(np.asarray(x_0, dtype=np.float64)[None], len(times), record=True,
+                               **kw)
         K = int(res.steps[0])
         n_x, n_u = res.x.shape[2], res.u.shape[2]
         n_d = getattr(getattr(self.law, '_rollout_plant', None), 'n_d', 0)
@@ -259,7 +315,12 @@ class Simulator:
         out.t_call = np.full(K, res.seconds / max(len(times), 1))
         out.x = res.x[:K, 0].T.copy().reshape(n_x, K)
         out.u = res.u[:K, 0].T.copy().reshape(n_u, K)
-        out.w = np.zeros((n_d, K))
-        out.v = np.zeros((n_x, K))
-        out.e = np.zeros((n_u, K))
+        if self.noise is None:
+            out.w = np.zeros((n_d, K))
+            out.v = np.zeros((n_x, K))
+            out.e = np.zeros((n_u, K))
+        else:
+            out.w = res.w[:K, 0].T.copy().reshape(n_d, K)
+            out.v = res.v[:K, 0].T.copy().reshape(n_x, K)
+            out.e = res.e[:K, 0].T.copy().reshape(n_u, K)
         return out

@@ -510,6 +510,35 @@ int ehm_explicit_rollout(ehm_explicit* ex, int64_t n, int32_t T, const double* x
                          int32_t* status, double* cost, double* u_norm_sum,
                          double* max_violation, double* kernel_seconds);
 
+/* ---- the closed loop under the reference's noise model (lib/uncertainty_sets.py, noise.py) ----
+ *
+ * The model as flat arrays (NoiseModel.pack): n_terms <= 16 terms in model order, desc
+ * [n_terms][8] int32 per term: kind (0 process -> d, 1 state -> v, 2 input -> e), shape (0 box,
+ * 1 ball), dim (box <= 8, ball <= 3), ball norm (0 inf, 1 (dim 1 only), 2), radius dependency
+ * (0 constant, 1 ||F x||, 2 ||F u||), its norm (0 inf, 1, 2), rows of F (<= 8), offset into data;
+ * data [n_data] the terms' doubles: box c [dim], h [dim], M [out][dim] (draw M (c + h s));
+ * ball sigma, F [rows][p or n_u], L [out][dim] (draw L q, q uniform in the ball of radius sigma,
+ * sigma ||F x|| or sigma ||F u||).  out = n_d (must equal the plant's), p or n_u.  Replaces an
+ * earlier model. */
+int ehm_explicit_set_noise(ehm_explicit* ex, int32_t n_terms, const int32_t* desc,
+                           const double* data, int32_t n_data, int32_t n_d);
+/* ehm_explicit_rollout with v, e and d drawn from the model (lib/simulator.py:160-180): at step t
+ * v at the true state and the last commanded input (0 at t = 0), applied from t = 1; e and the
+ * plant's d at the true state and the commanded input u, e = 0 where ||u||_2 = 0; the plant
+ * steps with B (u + e) and E d; cost, u_norm_sum and u_traj stay the commanded input's.
+ * Random numbers: Philox4x64-10, key (seed, 0), counter (traj0 + q, t, term, attempt) for
+ * trajectory q.  Extra records (may be NULL): v_traj [T][n][p] (NaN after the step a trajectory
+ * stopped at), e_traj [T][n][n_u], w_traj [T][n][n_d] (NaN from that step on). */
+int ehm_explicit_rollout_noisy(ehm_explicit* ex, int64_t n, int32_t T, const double* x0,
+                               uint64_t seed, uint64_t traj0, double tol_exit, double* x_traj,
+                               double* u_traj, int32_t* leaf_traj, double* v_traj,
+                               double* e_traj, double* w_traj, double* x_final, int32_t* steps,
+                               int32_t* status, double* cost, double* u_norm_sum,
+                               double* max_violation, double* kernel_seconds);
+/* Raw Philox4x64-10 blocks on the current device: out[i] = philox(counters[i], key), counters
+ * and out [n][4], key [2] (numpy: np.random.Philox(counter=c - 1, key=key).random_raw(4)). */
+int ehm_philox_batch(int64_t n, const uint64_t* counters, const uint64_t* key, uint64_t* out);
+
 /* Cumulative counters of a problem handle (SURVEY.md section 5 "tracing"). */
 typedef struct ehm_counters {
     int64_t lp_solves;

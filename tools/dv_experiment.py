@@ -1,0 +1,135 @@
+#!/usr/bin/env python
+"""
+The reference's closed-loop experiment under its noise model (needs a GPU):
+
+    python tools/dv_experiment.py [--n 10000] [--n-implicit 256] [--jobs 1,2,3,4,5] [--seed 0]
+
+lib/post_process.py:553-568: both laws of cwh_z from x0 = 0 for 20 orbits at T_s = 100 s (1 115
+steps, Simulator's time grid), here with NoiseModel.from_mpc (the six terms of
+lib/mpc_library.py:236-255) drawn inside the rollout.  Explicit law: --n noisy trajectories;
+implicit law: the first --n-implicit of them, with common random numbers (same seed, same
+trajectory ids).  Per job the delta-v of total_delta_v_usage (sum_t ||u_t||_2, in mm/s): mean,
+median, 5 % and 95 % for both laws, the overconsumption on the common trajectories, and the
+paper's single-run numbers (lib/post_process.py:414-417) beside them.
+
+Then the throughput of the noisy against the nominal rollout, measured in the same call (1e6
+trajectories x 100 steps from uniform states, applied trajectory-steps per second of kernel time)
+on the cwh_z job-1 tree (the reference model) and on the headline tree (a hand-built
+state / input model).
+"""
+import argparse
+import json
+import os
+import sys
+import time
+import types
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from explicit_hybrid_mpc_amd import examples, explicit                  # noqa: E402
+from explicit_hybrid_mpc_amd.noise import NoiseModel, state_input_model  # noqa: E402
+from rollout_bench import PAPER_EXPLICIT, PAPER_IMPLICIT, cwh_tree, headline_tree  # noqa: E402
+
+
+def reference_steps(mpc):
+    T_f = 20 * 2 * np.pi / mpc.pars['wo']
+    return len(np.linspace(0, T_f, int(T_f / mpc.T_s + 1)))
+
+
+def stats(dv):
+    return dict(mean=float(dv.mean()), median=float(np.median(dv)),
+                p5=float(np.percentile(dv, 5)), p95=float(np.percentile(dv, 95)))
+
+
+def experiment(job, n, n_im, seed):
+    oracle, flat = cwh_tree(job)
+    mpc = oracle.mpc
+    T = reference_steps(mpc)
+    model = NoiseModel.from_mpc(mpc)
+    ex = explicit.ExplicitMPC(flat, oracle)
+    im = explicit.ImplicitMPC(oracle)
+    t0 = time.perf_counter()
+    a = ex.rollout(np.zeros((n, 2)), T, noise=model, seed=seed, record=False)
+    t_ex = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    b = im.rollout(np.zeros((n_im, 2)), T, noise=model, seed=seed, record=False)
+    t_im = time.perf_counter() - t0
+    dv_ex, dv_im = 1e3 * a.u_norm_sum, 1e3 * b.u_norm_sum
+    ok = (a.status[:n_im] == 0) & (b.status == 0)
+    row = dict(job=job, leaves=int(np.sum(flat.left < 0)), T=T, seed=seed,
+               explicit=dict(trajectories=n, stopped=int((a.status != 0).sum()),
+                             max_violation=float(a.max_violation.max()),
+                             kernel_s=a.seconds, wall_s=t_ex, dv_mm_s=stats(dv_ex)),
+               implicit=dict(trajectories=n_im, stopped=int((b.status != 0).sum()),
+                             max_violation=float(b.max_violation.max()), wall_s=t_im,
+                             dv_mm_s=stats(dv_im)),
+               common=int(ok.sum()),
+               overconsumption_pct=100. * (dv_ex[:n_im][ok].sum() - dv_im[ok].sum())
+               / dv_im[ok].sum(),
+               overconsumption_median_pct=100. * float(np.median(
+                   (dv_ex[:n_im][ok] - dv_im[ok]) / dv_im[ok])),
+               paper_implicit=PAPER_IMPLICIT[job - 1], paper_explicit=PAPER_EXPLICIT[job - 1],
+               paper_overconsumption_pct=100. * (PAPER_EXPLICIT[job - 1] - PAPER_IMPLICIT[job - 1])
+               / PAPER_IMPLICIT[job - 1])
+    print(json.dumps(row), flush=True)
+    ex.close()
+    oracle.close()
+    return row
+
+
+def throughput(name, mpc, flat, model, n, T, rng):
+    ex = explicit.ExplicitMPC(flat, types.SimpleNamespace(mpc=mpc))
+    half = examples.theta_box(mpc)
+    X0 = rng.uniform(-1, 1, (n, half.size)) * half
+    ex.rollout(X0[:1024], T, record=False)
+    ex.rollout(X0[:1024], T, record=False, noise=model)
+    row = dict(tree=name, nodes=int(flat.n_nodes), trajectories=n, T=T, terms=len(model.terms))
+    for label, kw in (('nominal', {}), ('noisy', dict(noise=model, seed=1))):
+        res = ex.rollout(X0, T, record=False, **kw)
+        applied = int(res.steps.sum())
+        row[label] = dict(applied_steps=applied, stopped=int((res.status != 0).sum()),
+                          kernel_s=res.seconds, steps_per_s=applied / res.seconds)
+    row['noisy_over_nominal'] = row['noisy']['steps_per_s'] / row['nominal']['steps_per_s']
+    print(json.dumps(row), flush=True)
+    ex.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--n', type=int, default=10000)
+    ap.add_argument('--n-implicit', type=int, default=256)
+    ap.add_argument('--jobs', default='1,2,3,4,5')
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--rate-n', type=int, default=1000000)
+    ap.add_argument('--rate-T', type=int, default=100)
+    ap.add_argument('--skip-rates', action='store_true')
+    args = ap.parse_args()
+    rows = [experiment(int(j), args.n, args.n_implicit, args.seed)
+            for j in args.jobs.split(',') if j]
+    if rows:
+        print('\ndelta-v [mm/s] over 20 orbits from x0 = 0 (explicit: %d trajectories, implicit: '
+              'the first %d, common random numbers)' % (args.n, args.n_implicit))
+        print('job  leaves   implicit mean  med   5%%    95%%  |  explicit mean  med   5%%    95%%'
+              '  | over. %%  | paper imp  exp   over. %%')
+        for r in rows:
+            i, e = r['implicit']['dv_mm_s'], r['explicit']['dv_mm_s']
+            print('%3d  %6d   %6.2f %6.2f %6.2f %6.2f | %6.2f %6.2f %6.2f %6.2f | %7.1f | %5.2f %6.2f %7.1f'
+                  % (r['job'], r['leaves'], i['mean'], i['median'], i['p5'], i['p95'],
+                     e['mean'], e['median'], e['p5'], e['p95'], r['overconsumption_pct'],
+                     r['paper_implicit'], r['paper_explicit'], r['paper_overconsumption_pct']))
+    if not args.skip_rates:
+        rng = np.random.default_rng(0)
+        oracle, flat = cwh_tree(1)
+        throughput('cwh_z job 1', oracle.mpc, flat, NoiseModel.from_mpc(oracle.mpc), args.rate_n,
+                   args.rate_T, rng)
+        oracle.close()
+        mpc, flat = headline_tree()
+        half = examples.theta_box(mpc)
+        throughput('headline (configs[2])', mpc, flat, state_input_model(half, mpc.B[0].shape[1]),
+                   args.rate_n, args.rate_T, rng)
+
+
+if __name__ == '__main__':
+    main()
