@@ -40,6 +40,7 @@ EXPORTED = [
     'ehm_abi_sizes', 'ehm_solver_phase_ticks', 'ehm_problem_layout',
     'ehm_host_alloc', 'ehm_host_free', 'ehm_explicit_set_plant', 'ehm_explicit_rollout',
     'ehm_explicit_set_noise', 'ehm_explicit_rollout_noisy', 'ehm_philox_batch',
+    'ehm_explicit_set_plant_guarded',
 ]
 
 
@@ -250,6 +251,8 @@ def load(build_if_missing=True):
     lib.ehm_explicit_set_plant.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp,
                                            vp, i32, vp, vp]
     lib.ehm_explicit_rollout.argtypes = [vp, i64, i32, vp, vp, vp, ctypes.c_double] + [vp] * 10
+    lib.ehm_explicit_set_plant_guarded.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp,
+                                                   vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp]
     lib.ehm_explicit_set_noise.argtypes = [vp, i32, vp, vp, i32, i32]
     lib.ehm_explicit_rollout_noisy.argtypes = [vp, i64, i32, vp, ctypes.c_uint64, ctypes.c_uint64,
                                                ctypes.c_double] + [vp] * 13

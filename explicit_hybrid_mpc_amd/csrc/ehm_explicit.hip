@@ -253,6 +253,25 @@ struct RollArgs {
     double *v_traj, *e_traj, *w_traj;       // records of the noisy rollout
 };
 
+// ---- guarded multi-rate plants (simulate.GuardedPlant, ehm_explicit_set_plant_guarded) -----------
+//
+// The plant picks its own mode before every plant step: the first guard whose rows all hold, else
+// the default mode; row r holds iff ((sum_c a_c x_c) + sum_c b_c u_c) + c_r  <=  t_r  (< if strict).
+// S plant steps per controller step, u held.  The modes sit in the DevPlant arrays (oA, oB, ow),
+// the rows after them in the same LDS block: a [rows][p] at oGa, b [rows][n_u] at oGb, c at oGc,
+// t at oGt.
+#define EHM_G_MAX_MODES 8
+#define EHM_G_MAX_ROWS 16
+#define EHM_G_MAX_SUB 64
+
+struct DevGuard {
+    int substeps, n_guards, default_mode;
+    int oGa, oGb, oGc, oGt;
+    int mode[EHM_G_MAX_ROWS];                 // guard g selects mode[g]
+    int row0[EHM_G_MAX_ROWS + 1];             // its rows row0[g] .. row0[g+1]
+    int strict[EHM_G_MAX_ROWS];               // per row
+};
+
 // ---- the uncertainty model of the noisy rollout (noise.py, ehm_explicit_set_noise) -----------
 //
 // Terms in model order; desc per term: kind (0 process, 1 state, 2 input), shape (0 box, 1 ball),
@@ -411,11 +430,14 @@ __device__ __forceinline__ void weights_t(const DevExplicit& E, long long k, con
 
 // NOISY: v, e and w are drawn from the model in NZ (noise_kind) instead of read from R.v / R.d:
 // v at the true state and the last commanded input, e and w at the true state and the commanded
-// input, e = 0 where u = 0; the plant steps with u + e, cost and ||u|| stay the commanded input's
-template <int P, int NU, bool NOISY>
+// input, e = 0 where u = 0; the plant steps with u + e, cost and ||u|| stay the commanded input's.
+// GUARDED: the plant of GD (never together with NOISY) -- no mode-region check (status 2), and the
+// commanded u is held over GD.substeps plant steps whose modes the guards choose.
+template <int P, int NU, bool NOISY, bool GUARDED>
 __global__ __launch_bounds__(256) void k_explicit_rollout(DevExplicit E, DevPlant PL, RollArgs R,
-                                                          DevNoise NZ) {
+                                                          DevNoise NZ, DevGuard GD) {
 #pragma clang fp contract(off)
+    static_assert(!(NOISY && GUARDED), "noisy guarded plants are not instantiated");
     extern __shared__ double sh[];
     for (int i = threadIdx.x; i < PL.total; i += blockDim.x) sh[i] = PL.data[i];
     if constexpr (NOISY)
@@ -522,20 +544,22 @@ __global__ __launch_bounds__(256) void k_explicit_rollout(DevExplicit E, DevPlan
         }
         // the mode the leaf's commutation applies at step 0, and its region
         const int m = R.node_mode[k];
-        if (m < 0 || m >= PL.n_modes) {
+        if (m < 0 || (!GUARDED && m >= PL.n_modes)) {
             status = 3;
             break;
         }
-        bool in_region = true;
-        for (int r = PL.row0[m]; r < PL.row0[m + 1]; ++r) {
-            double s = 0.0;
+        if constexpr (!GUARDED) {
+            bool in_region = true;
+            for (int r = PL.row0[m]; r < PL.row0[m + 1]; ++r) {
+                double s = 0.0;
 #pragma unroll
-            for (int c = 0; c < P; ++c) s += sh[PL.oH + r * P + c] * x[c];
-            in_region = in_region && (s <= sh[PL.oh + r] + R.tol_exit);
-        }
-        if (!in_region) {
-            status = 2;
-            break;
+                for (int c = 0; c < P; ++c) s += sh[PL.oH + r * P + c] * x[c];
+                in_region = in_region && (s <= sh[PL.oh + r] + R.tol_exit);
+            }
+            if (!in_region) {
+                status = 2;
+                break;
+            }
         }
         if (R.u_traj)
 #pragma unroll
@@ -604,27 +628,65 @@ __global__ __launch_bounds__(256) void k_explicit_rollout(DevExplicit E, DevPlan
                 for (int j = 0; j < EHM_R_MAX_D; ++j)
                     if (j < PL.n_d) R.w_traj[((size_t)t * n + q) * PL.n_d + j] = wn[j];
         }
-        // plant step x+ = A_m x + B_m u + w_m + E d
-        const double* sA = sh + PL.oA + m * P * P;
-        const double* sB = sh + PL.oB + m * P * NU;
-        const double* sw = sh + PL.ow + m * P;
-        const double* dt = R.d ? R.d + ((size_t)t * n + q) * PL.n_d : nullptr;
+        if constexpr (GUARDED) {
+            // S plant steps with u held, each in the mode the guards choose at (x, u)
+            for (int sub = 0; sub < GD.substeps; ++sub) {
+                int gm = GD.default_mode;
+                for (int g = 0; g < GD.n_guards; ++g) {
+                    bool ok = true;
+                    for (int r = GD.row0[g]; r < GD.row0[g + 1]; ++r) {
+                        double s = 0.0;
 #pragma unroll
-        for (int i = 0; i < P; ++i) {
-            double s = 0.0;
+                        for (int c = 0; c < P; ++c) s += sh[GD.oGa + r * P + c] * x[c];
 #pragma unroll
-            for (int c = 0; c < P; ++c) s += sA[i * P + c] * x[c];
+                        for (int c = 0; c < NU; ++c) s += sh[GD.oGb + r * NU + c] * u[c];
+                        s += sh[GD.oGc + r];
+                        const double t = sh[GD.oGt + r];
+                        ok = ok && (GD.strict[r] ? (s < t) : (s <= t));
+                    }
+                    if (ok) {
+                        gm = GD.mode[g];
+                        break;
+                    }
+                }
+                const double* gA = sh + PL.oA + gm * P * P;
+                const double* gB = sh + PL.oB + gm * P * NU;
+                const double* gw = sh + PL.ow + gm * P;
 #pragma unroll
-            for (int c = 0; c < NU; ++c) s += sB[i * NU + c] * ua[c];
-            s += sw[i];
-            if constexpr (NOISY) {
+                for (int i = 0; i < P; ++i) {
+                    double s = 0.0;
 #pragma unroll
-                for (int j = 0; j < EHM_R_MAX_D; ++j)
-                    if (j < PL.n_d) s += sE[i * PL.n_d + j] * wn[j];
-            } else if (dt) {
-                for (int j = 0; j < PL.n_d; ++j) s += sE[i * PL.n_d + j] * dt[j];
+                    for (int c = 0; c < P; ++c) s += gA[i * P + c] * x[c];
+#pragma unroll
+                    for (int c = 0; c < NU; ++c) s += gB[i * NU + c] * u[c];
+                    xn[i] = s + gw[i];
+                }
+#pragma unroll
+                for (int c = 0; c < P; ++c) x[c] = xn[c];
             }
-            xn[i] = s;
+        } else {
+            // plant step x+ = A_m x + B_m u + w_m + E d
+            const double* sA = sh + PL.oA + m * P * P;
+            const double* sB = sh + PL.oB + m * P * NU;
+            const double* sw = sh + PL.ow + m * P;
+            const double* dt = R.d ? R.d + ((size_t)t * n + q) * PL.n_d : nullptr;
+#pragma unroll
+            for (int i = 0; i < P; ++i) {
+                double s = 0.0;
+#pragma unroll
+                for (int c = 0; c < P; ++c) s += sA[i * P + c] * x[c];
+#pragma unroll
+                for (int c = 0; c < NU; ++c) s += sB[i * NU + c] * ua[c];
+                s += sw[i];
+                if constexpr (NOISY) {
+#pragma unroll
+                    for (int j = 0; j < EHM_R_MAX_D; ++j)
+                        if (j < PL.n_d) s += sE[i * PL.n_d + j] * wn[j];
+                } else if (dt) {
+                    for (int j = 0; j < PL.n_d; ++j) s += sE[i * PL.n_d + j] * dt[j];
+                }
+                xn[i] = s;
+            }
         }
         for (int j = 0; j < PL.n_g; ++j) {
             double s = 0.0;
@@ -669,13 +731,15 @@ __global__ __launch_bounds__(256) void k_explicit_rollout(DevExplicit E, DevPlan
     R.max_viol[q] = maxv;
 }
 
-typedef void (*rollout_fn)(DevExplicit, DevPlant, RollArgs, DevNoise);
-#define EHM_R_NU(P, Z) &k_explicit_rollout<P, 1, Z>, &k_explicit_rollout<P, 2, Z>, \
-                       &k_explicit_rollout<P, 3, Z>, &k_explicit_rollout<P, 4, Z>
-#define EHM_R_ALL(Z) {EHM_R_NU(1, Z)}, {EHM_R_NU(2, Z)}, {EHM_R_NU(3, Z)}, {EHM_R_NU(4, Z)}, \
-                     {EHM_R_NU(5, Z)}, {EHM_R_NU(6, Z)}, {EHM_R_NU(7, Z)}, {EHM_R_NU(8, Z)}
-const rollout_fn k_rollout_table[EHM_XP][EHM_R_MAX_NU] = {EHM_R_ALL(false)};
-const rollout_fn k_rollout_noisy_table[EHM_XP][EHM_R_MAX_NU] = {EHM_R_ALL(true)};
+typedef void (*rollout_fn)(DevExplicit, DevPlant, RollArgs, DevNoise, DevGuard);
+#define EHM_R_NU(P, Z, G) &k_explicit_rollout<P, 1, Z, G>, &k_explicit_rollout<P, 2, Z, G>, \
+                          &k_explicit_rollout<P, 3, Z, G>, &k_explicit_rollout<P, 4, Z, G>
+#define EHM_R_ALL(Z, G) {EHM_R_NU(1, Z, G)}, {EHM_R_NU(2, Z, G)}, {EHM_R_NU(3, Z, G)},       \
+                        {EHM_R_NU(4, Z, G)}, {EHM_R_NU(5, Z, G)}, {EHM_R_NU(6, Z, G)},       \
+                        {EHM_R_NU(7, Z, G)}, {EHM_R_NU(8, Z, G)}
+const rollout_fn k_rollout_table[EHM_XP][EHM_R_MAX_NU] = {EHM_R_ALL(false, false)};
+const rollout_fn k_rollout_noisy_table[EHM_XP][EHM_R_MAX_NU] = {EHM_R_ALL(true, false)};
+const rollout_fn k_rollout_guarded_table[EHM_XP][EHM_R_MAX_NU] = {EHM_R_ALL(false, true)};
 #undef EHM_R_ALL
 #undef EHM_R_NU
 
@@ -723,6 +787,8 @@ struct ehm_explicit {
     void* noise = nullptr;                           // ehm_explicit_set_noise
     DevNoise nz{};
     int noise_n_d = 0;
+    bool guarded = false;                            // ehm_explicit_set_plant_guarded
+    DevGuard gd{};
     size_t cap = 0;
     hipStream_t stream = nullptr;
 };
@@ -983,6 +1049,116 @@ int ehm_explicit_set_plant(ehm_explicit* E, int32_t n_modes, const double* A, co
     E->node_mode = d_mode;
     pl.data = (const double*)d_plant;
     E->pl = pl;
+    E->guarded = false;
+    return EHM_OK;
+}
+
+int ehm_explicit_set_plant_guarded(ehm_explicit* E, int32_t n_modes, const double* A,
+                                   const double* B, const double* w, int32_t substeps,
+                                   int32_t n_guards, const int32_t* guard_mode,
+                                   const int32_t* guard_row0, const double* ga, const double* gb,
+                                   const double* gc, const double* gt, const int32_t* strict,
+                                   int32_t default_mode, int32_t n_g, const double* Gx,
+                                   const double* gx, const int32_t* node_mode, int32_t cost_kind,
+                                   const double* Q, const double* R) {
+    if (!E || !A || !B || !w || !node_mode || !Q || !R || (n_guards > 0 && !guard_mode) ||
+        !guard_row0)
+        return xfail(EHM_E_INVALID, "set_plant_guarded: a required array is NULL");
+    if (n_modes < 1 || n_modes > EHM_G_MAX_MODES)
+        return xfail(EHM_E_INVALID, "set_plant_guarded: %d modes (1..%d)", (int)n_modes,
+                     EHM_G_MAX_MODES);
+    if (substeps < 1 || substeps > EHM_G_MAX_SUB)
+        return xfail(EHM_E_INVALID, "set_plant_guarded: %d substeps (1..%d)", (int)substeps,
+                     EHM_G_MAX_SUB);
+    if (n_guards < 0 || n_guards > EHM_G_MAX_ROWS)
+        return xfail(EHM_E_INVALID, "set_plant_guarded: %d guards (0..%d)", (int)n_guards,
+                     EHM_G_MAX_ROWS);
+    if (default_mode < 0 || default_mode >= n_modes)
+        return xfail(EHM_E_INVALID, "set_plant_guarded: default mode %d of %d", (int)default_mode,
+                     (int)n_modes);
+    if (n_g < 0 || n_g > EHM_R_MAX_ROWS || (n_g > 0 && (!Gx || !gx)))
+        return xfail(EHM_E_INVALID, "set_plant_guarded: n_g = %d (0..%d)", (int)n_g,
+                     EHM_R_MAX_ROWS);
+    if (cost_kind != 0 && cost_kind != 1)
+        return xfail(EHM_E_INVALID, "set_plant_guarded: cost_kind %d (0 inf-norm, 1 quadratic)",
+                     (int)cost_kind);
+    const int p = E->d.p, n_u = E->d.n_u;
+    if (n_u > EHM_R_MAX_NU)
+        return xfail(EHM_E_INVALID,
+                     "set_plant_guarded: n_u = %d, the rollout takes at most %d inputs", n_u,
+                     EHM_R_MAX_NU);
+    DevGuard gd{};
+    gd.substeps = substeps;
+    gd.n_guards = n_guards;
+    gd.default_mode = default_mode;
+    if (guard_row0[0] != 0)
+        return xfail(EHM_E_INVALID, "set_plant_guarded: the rows of guard 0 start at %d",
+                     (int)guard_row0[0]);
+    for (int g = 0; g <= n_guards; ++g) {
+        if (g < n_guards) {
+            if (guard_mode[g] < 0 || guard_mode[g] >= n_modes)
+                return xfail(EHM_E_INVALID, "set_plant_guarded: guard %d selects mode %d of %d", g,
+                             (int)guard_mode[g], (int)n_modes);
+            if (guard_row0[g + 1] <= guard_row0[g])
+                return xfail(EHM_E_INVALID, "set_plant_guarded: guard %d has no rows", g);
+            gd.mode[g] = guard_mode[g];
+        }
+        gd.row0[g] = guard_row0[g];
+    }
+    const int rows = guard_row0[n_guards];
+    if (rows > EHM_G_MAX_ROWS || (rows > 0 && (!ga || !gb || !gc || !gt || !strict)))
+        return xfail(EHM_E_INVALID, "set_plant_guarded: %d guard rows (0..%d)", rows,
+                     EHM_G_MAX_ROWS);
+    for (int r = 0; r < rows; ++r) gd.strict[r] = strict[r] != 0;
+    DevPlant pl{};
+    pl.n_modes = n_modes;
+    pl.n_g = n_g;
+    pl.cost_kind = cost_kind;
+    std::vector<double> buf;
+    auto put = [&](const double* src, size_t cnt) {
+        const int off = (int)buf.size();
+        if (src) buf.insert(buf.end(), src, src + cnt);
+        else buf.insert(buf.end(), cnt, 0.0);
+        return off;
+    };
+    pl.oA = put(A, (size_t)n_modes * p * p);
+    pl.oB = put(B, (size_t)n_modes * p * n_u);
+    pl.ow = put(w, (size_t)n_modes * p);
+    pl.oE = pl.oH = pl.oh = (int)buf.size();
+    pl.oG = put(Gx, (size_t)n_g * p);
+    pl.og = put(gx, (size_t)n_g);
+    pl.oQ = put(Q, (size_t)p * p);
+    pl.oR = put(R, (size_t)n_u * n_u);
+    gd.oGa = put(ga, (size_t)rows * p);
+    gd.oGb = put(gb, (size_t)rows * n_u);
+    gd.oGc = put(gc, (size_t)rows);
+    gd.oGt = put(gt, (size_t)rows);
+    pl.total = (int)buf.size();
+    for (int64_t k = 0; k < E->d.n_nodes; ++k)
+        if (node_mode[k] < -1)
+            return xfail(EHM_E_INVALID, "set_plant_guarded: node %lld has mode %d", (long long)k,
+                         (int)node_mode[k]);
+    hipError_t e = hipSetDevice(E->device);
+    if (e != hipSuccess) return xfail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
+    void *d_plant = nullptr, *d_mode = nullptr;
+    const size_t mb = (size_t)E->d.n_nodes * sizeof(int32_t);
+    if (hipMalloc(&d_plant, buf.size() * sizeof(double)) != hipSuccess ||
+        hipMalloc(&d_mode, mb) != hipSuccess ||
+        hipMemcpy(d_plant, buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice) !=
+            hipSuccess ||
+        hipMemcpy(d_mode, node_mode, mb, hipMemcpyHostToDevice) != hipSuccess) {
+        if (d_plant) (void)hipFree(d_plant);
+        if (d_mode) (void)hipFree(d_mode);
+        return xfail(EHM_E_HIP, "set_plant_guarded: device allocation / copy failed");
+    }
+    if (E->plant) (void)hipFree(E->plant);
+    if (E->node_mode) (void)hipFree(E->node_mode);
+    E->plant = d_plant;
+    E->node_mode = d_mode;
+    pl.data = (const double*)d_plant;
+    E->pl = pl;
+    E->gd = gd;
+    E->guarded = true;
     return EHM_OK;
 }
 
@@ -1009,6 +1185,9 @@ int rollout_run(ehm_explicit* E, int64_t n, int32_t T, const double* x0, const d
     if (d && E->pl.n_d == 0)
         return xfail(EHM_E_INVALID, "rollout: a disturbance was given but the plant has no E");
     // a plant set after the model may have grown past what set_noise checked
+    if (nz && E->guarded)
+        return xfail(EHM_E_INVALID, "rollout_noisy: the plant is guarded (noisy guarded plants "
+                                    "are not supported)");
     if (nz && E->pl.total + E->nz.total > EHM_N_MAX_LDS)
         return xfail(EHM_E_INVALID, "rollout_noisy: plant and model take %d doubles of LDS (%d)",
                      E->pl.total + E->nz.total, EHM_N_MAX_LDS);
@@ -1080,9 +1259,10 @@ int rollout_run(ehm_explicit* E, int64_t n, int32_t T, const double* x0, const d
         NZ.traj0 = nz->traj0;
         lds += (size_t)NZ.total * sizeof(double);
     }
-    hipLaunchKernelGGL((nz ? k_rollout_noisy_table : k_rollout_table)[p - 1][n_u - 1],
-                       dim3((unsigned)((n + 255) / 256)), dim3(256), lds, E->stream, E->d, E->pl,
-                       R, NZ);
+    const rollout_fn fn = (nz ? k_rollout_noisy_table
+                              : E->guarded ? k_rollout_guarded_table : k_rollout_table)[p - 1][n_u - 1];
+    hipLaunchKernelGGL(fn, dim3((unsigned)((n + 255) / 256)), dim3(256), lds, E->stream, E->d,
+                       E->pl, R, NZ, E->gd);
     (void)hipEventRecord(e1, E->stream);
     Y_TRY(hipGetLastError());
     Y_TRY(hipMemcpyAsync(x_final, R.x_final, N * p * sizeof(double), hipMemcpyDeviceToHost,

@@ -5,9 +5,9 @@ SURVEY.md section 8d) and the oracle factory.
 Role in the reference: ``lib/examples.py`` -- ``example()`` returns
 ``(full_set, partition_tree, oracle)`` (lib/examples.py:165-180) and ``create_oracle``
 fixes eps_a as the largest optimal cost at the ``abs_frac``-scaled vertices of the set
-to partition (lib/examples.py:18-47).  The reference's satellite / pendulum models need
-MOSEK, cdd and data files that are not shipped, so the instances here are the seeded
-random-polytope MPC problems BASELINE.json names.
+to partition (lib/examples.py:18-47).  Besides the reference's cwh_z and pendulum laws
+(``satellite_z``, ``pendulum``), the instances here are the seeded random-polytope MPC problems
+BASELINE.json names.
 
 Every builder is deterministic in ``seed`` (``numpy.random.default_rng``) and returns a
 ``PWAMPC`` plus the box ``Theta`` to partition.  The box half-widths are recorded
@@ -243,8 +243,41 @@ def satellite_z(N=4):
     return mpc
 
 
+def pendulum(N=4):
+    """
+    The reference's inverted pendulum on a cart with friction (lib/mpc_library.py:407-626,
+    ``InvertedPendulumOnCart``, reference commutation layout); the partitioned set is the box
+    D_x, pre-partitioned in three sections (``pendulum_sections``).
+    """
+    from .mpc_library import InvertedPendulumOnCart
+    mpc = InvertedPendulumOnCart(N)
+    THETA_SCALE.setdefault(mpc.name, 1.0)
+    return mpc
+
+
+def pendulum_sections(mpc):
+    """Vertices of the three boxes v >= v_eps, v <= -v_eps, |v| <= v_eps that lib/examples.py:
+    120-163 triangulates separately (the ECC feasibility split needs it: a simplex with vertices
+    on both sides of v = +-v_eps has no commutation feasible at all its vertices)."""
+    signs = box_vertices(np.ones(mpc.n_x))
+    return [np.where(signs > 0, hi[None, :], lo[None, :]) for lo, hi in mpc.sections()]
+
+
+def pendulum_roots(mpc):
+    """(roots (n, p+1, p), section index per root): the Delaunay simplices of the three
+    sections in the order of ``example('pendulum')``'s tree."""
+    from . import tools
+    roots, owner = [], []
+    for i, V in enumerate(pendulum_sections(mpc)):
+        r, _ = tools.delaunay_roots(V)
+        roots.append(r)
+        owner += [i] * r.shape[0]
+    return np.concatenate(roots), np.array(owner)
+
+
 EXAMPLES = {
     'cwh_z': lambda: satellite_z(4),          # make_jobs.sh:60-61 (EXAMPLE=cwh_z, MPC_N=4)
+    'pendulum': lambda: pendulum(4),          # lib/examples.py:113-163
     'double_integrator': lambda: double_integrator(3),
     'linear': lambda: linear_mpc(0),
     'pwa': lambda: pwa_mpc(0),
@@ -258,6 +291,14 @@ def example(name, abs_frac=0.5, abs_err=None, rel_err=2.0, device=0):
     """
     from . import tools
     mpc = EXAMPLES[name]()
+    if name == 'pendulum':
+        # the box split in three sections, triangulated apart and joined (lib/examples.py:146-163)
+        full_set = mpc.box_vertices()
+        parts = [tools.delaunay(V)[0] for V in pendulum_sections(mpc)]
+        tools.join_triangulation(parts[1], parts[2])
+        tools.join_triangulation(parts[0], parts[1])
+        oracle = create_oracle(mpc, full_set, abs_frac, abs_err, rel_err, device=device)
+        return full_set, parts[0], oracle
     full_set = box_vertices(theta_box(mpc))
     partition, _, _ = tools.delaunay(full_set)
     oracle = create_oracle(mpc, full_set, abs_frac, abs_err, rel_err, device=device)

@@ -191,7 +191,7 @@ class ExplicitMPC:
     def node_modes(self, plant):
         """int32 [n_nodes]: step-0 mode of every node's commutation (-1: none); all 0 for a
         single-mode plant."""
-        if plant.n_modes == 1:
+        if plant.n_modes == 1 and not hasattr(plant, 'guards'):
             return np.zeros(self.n_nodes, dtype=np.int32)
         if self.mpc is None or not hasattr(self.mpc, 'step0_mode'):
             raise ValueError('the step-0 modes of a hybrid law need the oracle (its mpc)')
@@ -209,6 +209,8 @@ class ExplicitMPC:
             raise ValueError('plant (n_x %d, n_u %d) does not fit the law (p %d, n_u %d)' % (
                 plant.n_x, plant.n_u, self.p, self.n_u))
         self._node_mode = self.node_modes(plant)
+        if hasattr(plant, 'guards'):
+            return self._set_plant_guarded(plant)
         rows, H, h = plant.region_arrays()
         keep = [f64(plant.A), f64(plant.B), f64(plant.w), f64(plant.E), rows, f64(H), f64(h),
                 f64(plant.Gx), f64(plant.gx), self._node_mode, f64(plant.Q), f64(plant.R)]
@@ -219,6 +221,20 @@ class ExplicitMPC:
             ptr(h) if h.size else None, plant.gx.size, ptr(Gx) if Gx.size else None,
             ptr(gx) if gx.size else None, ptr(nm), 0 if plant.cost == 'inf' else 1, ptr(Q),
             ptr(R)))
+        self._rollout_plant = plant
+
+    def _set_plant_guarded(self, plant):
+        """A ``simulate.GuardedPlant`` to the device (ehm_explicit_set_plant_guarded)."""
+        gm, row0, ga, gb, gc, gt, st = plant.guard_arrays()
+        keep = [f64(plant.A), f64(plant.B), f64(plant.w), f64(plant.Gx), f64(plant.gx),
+                f64(plant.Q), f64(plant.R), f64(ga), f64(gb), f64(gc), f64(gt)]
+        A, B, w, Gx, gx, Q, R, ga, gb, gc, gt = keep
+        opt = lambda a: ptr(a) if a.size else None
+        _check(self._lib.ehm_explicit_set_plant_guarded(
+            self._handle, plant.n_modes, ptr(A), ptr(B), ptr(w), plant.substeps, len(gm), opt(gm),
+            ptr(row0), opt(ga), opt(gb), opt(gc), opt(gt), opt(st), plant.default_mode,
+            plant.gx.size, opt(Gx), opt(gx), ptr(self._node_mode),
+            0 if plant.cost == 'inf' else 1, ptr(Q), ptr(R)))
         self._rollout_plant = plant
 
     def set_noise(self, model, plant):
@@ -247,8 +263,11 @@ class ExplicitMPC:
         ``plant`` defaults to ``Plant.from_mpc`` of the oracle's law; d [T, n, n_d] and
         v [T, n, p] are optional.  With ``noise`` (a ``noise.NoiseModel``, not together with d
         or v) the kernel draws v, e and d itself (ehm_explicit_rollout_noisy, Philox key seed,
-        trajectory q has id traj0 + q).  Returns a ``simulate.ClosedLoop`` (leaf, commutation,
-        mode -- and v, e, w under noise -- recorded with ``record``).
+        trajectory q has id traj0 + q).  A ``simulate.GuardedPlant`` (the default for a law that
+        has one, e.g. the pendulum) is held at u for its substeps per step and picks its own modes
+        (its instantiation of the kernel); it takes neither noise nor d.  Returns a
+        ``simulate.ClosedLoop`` (leaf, commutation, mode -- None for a guarded plant -- and v, e, w
+        under noise, recorded with ``record``).
         """
         from . import simulate
         if noise is not None and (d is not None or v is not None):
@@ -259,6 +278,9 @@ class ExplicitMPC:
                 if self.mpc is None:
                     raise ValueError('rollout needs a plant (or an oracle whose mpc gives one)')
                 plant = simulate.Plant.from_mpc(self.mpc)
+        guarded = hasattr(plant, 'guards')
+        if guarded and noise is not None:
+            raise ValueError('noise is not supported with a guarded plant')
         if plant is not self._rollout_plant:
             self.set_plant(plant)
         X0 = f64(np.atleast_2d(X0))
@@ -301,7 +323,9 @@ class ExplicitMPC:
         if record:
             out.x, out.u, out.leaf = xs, us, leaf
             live = leaf >= 0
-            out.mode = np.where(live, self._node_mode[np.maximum(leaf, 0)], -1).astype(np.int32)
+            if not guarded:
+                out.mode = np.where(live, self._node_mode[np.maximum(leaf, 0)],
+                                    -1).astype(np.int32)
             if isinstance(self.tree, FlatTree):
                 didx = np.asarray(self.tree.delta_idx, dtype=np.int32)
                 out.commutation = np.where(live, didx[np.maximum(leaf, 0)], -1).astype(np.int32)

@@ -31,6 +31,8 @@ def _law_struct(mpc):
     """(ehm_pwa_law, the arrays it points into)."""
     if getattr(mpc, 'cost_type', 'inf') != 'inf':
         raise ValueError('the native driver states infinity-norm laws')
+    if any(r is not None and len(r) == 3 for r in mpc.regions):
+        raise ValueError('the native driver states mode regions in x only')
     f = lambda a: np.ascontiguousarray(a, dtype=np.float64)
     keep = dict(A=f(np.stack(mpc.A)), B=f(np.stack(mpc.B)), w=f(np.stack(mpc.w)),
                 Gx=f(mpc.Gx), gx=f(mpc.gx), Gu=f(mpc.Gu), gu=f(mpc.gu), Q=f(mpc.Q), R=f(mpc.R))

@@ -107,6 +107,7 @@ class PWAMPC:
 
         x_{k+1} = A_i x_k + B_i u_k + w_i     if mode i is active at step k,
         Hx_i x_k <= hx_i                      (mode region, may be empty),
+        Hx_i x_k + Hu_i u_k <= hx_i           (input-dependent mode region, a 3-tuple),
         Gx x_k <= gx , k = 1..N ;  Gu u_k <= gu , k = 0..N-1 ;  x_0 = theta ,
         V = sum_{k=1..N} ||Q x_k||_inf + sum_{k=0..N-1} ||R u_k||_inf          (cost='inf')
         V = sum_{k=0..N-1} u_k'R u_k + sum_{k=1..N-1} x_k'Q x_k + x_N'P x_N     (cost='quadratic',
@@ -122,10 +123,12 @@ class PWAMPC:
         self.A = [np.asarray(a, dtype=np.float64) for a in A]
         self.B = [np.asarray(b, dtype=np.float64) for b in B]
         self.w = [np.asarray(v, dtype=np.float64) for v in w]
-        # regions[i] = (Hx_i, hx_i) or None
+        # regions[i] = (Hx_i, hx_i), (Hx_i, Hu_i, hx_i) or None
         self.regions = [None if r is None else
-                        (np.asarray(r[0], dtype=np.float64),
-                         np.asarray(r[1], dtype=np.float64)) for r in regions]
+                        tuple(np.asarray(a, dtype=np.float64) for a in r) for r in regions]
+        for r in self.regions:
+            if r is not None and len(r) not in (2, 3):
+                raise ValueError('a mode region is (Hx, hx) or (Hx, Hu, hx)')
         self.Gx = np.asarray(Gx, dtype=np.float64)
         self.gx = np.asarray(gx, dtype=np.float64)
         self.Gu = np.asarray(Gu, dtype=np.float64)
@@ -261,12 +264,15 @@ class PWAMPC:
                 Gz = pad(M_u)
                 Gz[:, nU + N + k] = -1.
                 add(Gz, np.zeros(self.R.shape[0]), np.zeros((self.R.shape[0], n_x)))
-        # mode regions, k = 0..N-1 :  Hx_i x_k <= hx_i
+        # mode regions, k = 0..N-1 :  Hx_i x_k (+ Hu_i u_k) <= hx_i
         for k in range(N):
             r = self.regions[seq[k]]
             if r is not None:
-                Hx, hx = r
-                add(pad(Hx @ Gam[k]), hx - Hx @ om[k], -Hx @ Phi[k])
+                Hx, hx = r[0], r[-1]
+                M_u = Hx @ Gam[k]
+                if len(r) == 3:
+                    M_u[:, k * n_u:(k + 1) * n_u] += r[1]
+                add(pad(M_u), hx - Hx @ om[k], -Hx @ Phi[k])
         G = np.vstack(rows_G)
         w = np.concatenate(rows_w)
         S = np.vstack(rows_S)
@@ -329,10 +335,12 @@ class PWAMPC:
         for kk in range(k):                              # mode regions of x_kk, kk < k
             reg = self.regions[prefix[kk]]
             if reg is not None:
-                Hx, hx = reg
+                Hx, hx = reg[0], reg[-1]
                 Phi, Gam, om = states[kk]
                 nr = Hx.shape[0]
                 G[row_r:row_r + nr, :nU] = Hx @ Gam
+                if len(reg) == 3:
+                    G[row_r:row_r + nr, kk * n_u:(kk + 1) * n_u] += reg[1]
                 w[row_r:row_r + nr] = hx - Hx @ om
                 S[row_r:row_r + nr] = -Hx @ Phi
                 row_r += nr
@@ -638,3 +646,231 @@ class SatelliteZ:
                                       np.zeros(3 * self.N), np.stack(ds), self.n_u, self.N,
                                       self.delta_size, quad=quad)
         return self._canonical
+
+
+# ---------------------------------------------------------------------------------------
+# inverted pendulum on a cart with static / kinetic friction (lib/mpc_library.py:407-626,
+# lib/pendulum_linearize.py)
+# ---------------------------------------------------------------------------------------
+def pendulum_parameters():
+    """Physical and timing parameters (lib/pendulum_linearize.py:19-41, same names and values)."""
+    return {'mu_s': 0.16,        # static friction coefficient
+            'mu_d': 0.03,        # kinetic friction coefficient
+            'g': 9.81,           # [m/s^2]
+            'l': 3.,             # [m] rod length
+            'm': 0.3,            # [kg] tip mass
+            'M': 1.,             # [kg] cart mass
+            'v_eps': 1e-3,       # [m/s] below this speed the cart may stick
+            'a_eps': 1e-3,       # [m/s^2] below this acceleration static friction holds
+            'T_s': 1 / 10.,      # [s] controller period
+            'T_s_plant': 1 / 100.}   # [s] plant period of the simulation
+
+
+# friction case -> (sign of the friction direction, which coefficient); case 4: stuck
+PENDULUM_CASES = ((1., 'mu_d'), (-1., 'mu_d'), (1., 'mu_s'), (-1., 'mu_s'), None)
+
+
+def pendulum_accelerations(case, theta, dtheta, F, pars, sin, cos):
+    """
+    (cart acceleration, angular acceleration) of friction case ``case`` (0 sliding right, 1
+    sliding left, 2 breaking away right, 3 breaking away left, 4 held), for any arithmetic with
+    ``sin`` / ``cos`` (sympy or numpy).  A cart sliding or breaking away in direction s feels a
+    friction force -s mu N through the normal force N of the pendulum-loaded cart; held, it does not
+    accelerate.  The rod swings as g/l sin(theta) - xdd/l cos(theta).
+    """
+    g, l, m, M = pars['g'], pars['l'], pars['m'], pars['M']
+    if PENDULUM_CASES[case] is None:
+        xdd = 0 * F
+    else:
+        s, key = PENDULUM_CASES[case]
+        mu = s * pars[key]
+        num = (F - m * g / 2 * sin(2 * theta) + m * l * dtheta ** 2 * (sin(theta) + mu * cos(theta))
+               - mu * (M + m * cos(theta) ** 2) * g)
+        xdd = num / (M + m * (sin(theta) ** 2 + mu / 2 * sin(2 * theta)))
+    return xdd, g / l * sin(theta) - xdd / l * cos(theta)
+
+
+def pendulum_linearization(pars=None):
+    """
+    Continuous-time linearisation of the five friction cases at x = 0, F = 0, state
+    (position, angle, velocity, angular rate): xdot = A_c x + B_c F + w_c with w_c = f(0)
+    (lib/pendulum_linearize.py:43-104).  Returns lists A_c [4x4], B_c [4], w_c [4], float64.
+    """
+    import sympy as sp
+    pars = pendulum_parameters() if pars is None else pars
+    pos, th, v, dth, F = sp.symbols('pos theta v dtheta F')
+    state = sp.Matrix([pos, th, v, dth])
+    at0 = {pos: 0, th: 0, v: 0, dth: 0, F: 0}
+    A_c, B_c, w_c = [], [], []
+    for case in range(len(PENDULUM_CASES)):
+        xdd, thdd = pendulum_accelerations(case, th, dth, F, pars, sp.sin, sp.cos)
+        f = sp.Matrix([v, dth, xdd, thdd])
+        A_c.append(np.array(f.jacobian(state).subs(at0), dtype=np.float64))
+        B_c.append(np.array(f.jacobian(sp.Matrix([F])).subs(at0), dtype=np.float64).ravel())
+        w_c.append(np.array(f.subs(at0), dtype=np.float64).ravel())
+    return A_c, B_c, w_c
+
+
+def discretize_affine(A_c, B_c, w_c, h):
+    """(A, B, w) of xdot = A_c x + B_c u + w_c held over h (lib/mpc_library.py:556-586)."""
+    import scipy.linalg as sla
+    n = A_c.shape[0]
+    B_c = np.asarray(B_c, dtype=np.float64).reshape(n, -1)
+    A = sla.expm(A_c * h)
+    nb = B_c.shape[1]
+    B = sla.expm(np.block([[A_c, B_c], [np.zeros((nb, n + nb))]]) * h)[:n, n:]
+    W = sla.expm(np.block([[A_c, np.eye(n)], [np.zeros((n, 2 * n))]]) * h)[:n, n:]
+    return A, B, W @ np.asarray(w_c, dtype=np.float64)
+
+
+def pendulum_sequences(N, reference_indexing=True):
+    """
+    Admissible mode sequences (step 0 most significant) and their 0/1 commutation vectors.  The
+    reference reads the binaries of step k as z[k][i] = delta[k*N + i] (lib/mpc_library.py:524),
+    so for N < 5 consecutive steps share entries: a sequence is admissible iff the vector with
+    delta[k*N + m_k] = 1 (all else 0) has exactly e_{m_k} in every window z[k].  With
+    ``reference_indexing=False`` the layout is delta[5k + i], every sequence admissible.
+    """
+    n_modes = len(PENDULUM_CASES)
+    seqs, deltas = [], []
+    for seq in itertools.product(range(n_modes), repeat=N):
+        d = np.zeros(n_modes * N)
+        stride = N if reference_indexing else n_modes
+        for k, i in enumerate(seq):
+            d[stride * k + i] = 1.
+        if all(np.array_equal(d[stride * k:stride * k + n_modes], np.eye(n_modes)[i])
+               for k, i in enumerate(seq)):
+            seqs.append(seq)
+            deltas.append(d)
+    return seqs, deltas
+
+
+class InvertedPendulumOnCart(PWAMPC):
+    """
+    The reference's ``InvertedPendulumOnCart`` law (lib/mpc_library.py:407-626): five friction
+    cases linearised at the origin and discretised at T_s, quadratic cost with the terminal
+    weight of the frictionless LQR design, and the big-M constraints of ``make_constraints``
+    (:521-554) with the binaries fixed to a mode sequence.  For mode j active at step k the
+    rows are, in (x_k, u_k):
+
+        |(A_j - A_i) x_k + (B_j - B_i) u_k + w_j - w_i| <= bigM   every inactive mode i,
+        the four velocity rows and the four acceleration rows of the friction conditions,
+        |u_k| <= F_max,
+
+    carried as an input-dependent mode region (Hx, Hu, h) per mode plus the input rows Gu.
+    ``reference_indexing`` selects the commutation layout (``pendulum_sequences``).
+    """
+
+    def __init__(self, N=4, reference_indexing=True, name=None):
+        import scipy.linalg as sla
+        pars = pendulum_parameters()
+        self.pars = pars
+        self.reference_indexing = bool(reference_indexing)
+        n_modes = len(PENDULUM_CASES)
+        seqs, deltas = pendulum_sequences(N, reference_indexing)
+        if len(seqs) > 256:
+            raise ValueError(
+                'InvertedPendulumOnCart(N=%d, reference_indexing=%s) has %d admissible commutations; '
+                'the hybrid engine enumerates at most 256 (N <= 4 with the reference layout, '
+                'N <= 3 with the delta[5k+i] layout), and the branch-and-bound engine states only '
+                'infinity-norm costs' % (N, reference_indexing, len(seqs)))
+        g, l, m, M = pars['g'], pars['l'], pars['m'], pars['M']
+        self.v_eps, self.a_eps = pars['v_eps'], pars['a_eps']
+        self.T_s, self.T_s_plant = pars['T_s'], pars['T_s_plant']
+        self.A_c, self.B_c, self.w_c = pendulum_linearization(pars)
+        disc = [discretize_affine(self.A_c[i], self.B_c[i], self.w_c[i], self.T_s)
+                for i in range(n_modes)]
+        A, B, w = [d[0] for d in disc], [d[1] for d in disc], [d[2] for d in disc]
+        # scalings, set and limits (:441-469)
+        p_max, v_max, rate_max = 1., 1., np.deg2rad(50)
+        ang_max = np.deg2rad(10)
+        self.a_max, self.F_max = 30., 20.
+        self.bigM = np.array([p_max, ang_max, v_max, rate_max])
+        self.p_err, self.v_err = 1., 1.
+        self.ang_err, self.rate_err = np.deg2rad(5), np.deg2rad(20)
+        self.D_x = np.diag([self.p_err, self.ang_err, self.v_err, self.rate_err])
+        self.D_u = np.diag([self.F_max])
+        Dxi, Dui = np.linalg.inv(self.D_x), np.linalg.inv(self.D_u)
+        Q = Dxi.T @ np.diag([0.1, 1., 1., 10.]) @ Dxi
+        R = Dui.T @ np.eye(1) @ Dui
+        # terminal weight: DARE of the frictionless model (:443-471)
+        A_lqr = np.array([[0, 0, 1, 0], [0, 0, 0, 1], [0, -m * g / M, 0, 0],
+                          [0, g / l * (1 + m / M), 0, 0]], dtype=np.float64)
+        B_lqr = np.array([0, 0, 1 / M, -1 / (M * l)])
+        A_d, B_d, _ = discretize_affine(A_lqr, B_lqr, np.zeros(4), self.T_s)
+        P = sla.solve_discrete_are(A_d, B_d, Q, R)
+        self.P_dare = P
+        regions = [self._mode_region(j, A, B, w) for j in range(n_modes)]
+        Gu = np.array([[1.], [-1.]])
+        gu = np.array([self.F_max, self.F_max])
+        super().__init__(A, B, w, regions, np.zeros((0, 4)), np.zeros(0), Gu, gu, Q, R, N,
+                         name=name or 'pendulum_N%d%s' % (N, '' if reference_indexing else '_k5'),
+                         cost='quadratic', P=0.5 * (P + P.T))
+        self._sequences = list(seqs)
+        self._deltas = {s: d for s, d in zip(seqs, deltas)}
+
+    def _mode_region(self, j, A, B, w):
+        """(Hx, Hu, h) of the rows that hold at a step whose active mode is j."""
+        Hx, Hu, h = [], [], []
+
+        def row(hx, hu, rhs):
+            Hx.append(np.asarray(hx, dtype=np.float64))
+            Hu.append(np.atleast_1d(np.asarray(hu, dtype=np.float64)))
+            h.append(float(rhs))
+        # inactive modes' dynamics, relaxed by bigM, with x_{k+1} = A_j x + B_j u + w_j
+        for i in range(len(PENDULUM_CASES)):
+            if i == j:
+                continue
+            dA, dB, dw = A[j] - A[i], B[j][:, 0] - B[i][:, 0], w[j] - w[i]
+            for r in range(4):
+                row(dA[r], dB[r], self.bigM[r] - dw[r])
+                row(-dA[r], -dB[r], self.bigM[r] + dw[r])
+        z = np.eye(len(PENDULUM_CASES))[j]
+        e2 = np.eye(4)[2]
+        bM, ve, ae, am = self.bigM[2], self.v_eps, self.a_eps, self.a_max
+        s = z[2] + z[3] + z[4]
+        row(-e2, 0., -(ve * z[0] - bM * (1 - z[0])))          # v >= v_eps z0 - bigM (1 - z0)
+        row(e2, 0., -ve * z[1] + bM * (1 - z[1]))             # v <= -v_eps z1 + bigM (1 - z1)
+        row(e2, 0., ve * s + bM * (1 - s))                    # v <= v_eps s + bigM (1 - s)
+        row(-e2, 0., ve * s + bM * (1 - s))                   # v >= -v_eps s - bigM (1 - s)
+        acc = [(self.A_c[i][2], self.B_c[i][2], self.w_c[i][2]) for i in range(5)]
+        a, b, c = acc[2]                                      # accel_3 >= a_eps z2 - a_max (1 - z2)
+        row(-a, -b, -(ae * z[2] - am * (1 - z[2])) + c)
+        a, b, c = acc[3]                                      # accel_4 <= -a_eps z3 + a_max (1 - z3)
+        row(a, b, -ae * z[3] + am * (1 - z[3]) - c)
+        a, b, c = acc[4]                                      # |accel_5| <= a_eps z4 + a_max (1 - z4)
+        row(-a, -b, ae * z[4] + am * (1 - z[4]) + c)
+        row(a, b, ae * z[4] + am * (1 - z[4]) - c)
+        return np.array(Hx), np.array(Hu), np.array(h)
+
+    def sequence_to_delta(self, seq):
+        """Mode sequence -> the reference's 5N-long 0/1 vector (unused entries 0)."""
+        d = self._deltas.get(tuple(int(i) for i in seq))
+        if d is None:
+            raise ValueError('%s is not an admissible mode sequence' % (tuple(seq),))
+        return d.copy()
+
+    def step0_mode(self, delta):
+        """The mode of step 0: z[0] = delta[0:5] in either layout."""
+        return int(np.argmax(np.asarray(delta)[:self.delta_size]))
+
+    def box_vertices(self):
+        """Vertices of the box D_x that is partitioned (lib/examples.py:120-124)."""
+        return np.array(list(itertools.product(*[(-h, h) for h in np.diag(self.D_x)])))
+
+    def sections(self):
+        """The three boxes the set is split into (v >= v_eps, v <= -v_eps, |v| <= v_eps),
+        as (lower, upper) bounds (lib/examples.py:125-145)."""
+        lo, hi = -np.diag(self.D_x), np.diag(self.D_x).copy()
+        out = []
+        for vlo, vhi in ((self.v_eps, self.v_err), (-self.v_err, -self.v_eps),
+                         (-self.v_eps, self.v_eps)):
+            a, b = lo.copy(), hi.copy()
+            a[2], b[2] = vlo, vhi
+            out.append((a, b))
+        return out
+
+    def guarded_plant(self):
+        """The multi-rate friction plant of lib/mpc_library.py:588-626 (simulate.GuardedPlant)."""
+        from .simulate import GuardedPlant
+        return GuardedPlant.pendulum(self)

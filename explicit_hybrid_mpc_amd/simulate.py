@@ -21,6 +21,10 @@ commanded input, then the law's u_t, then the input error e_t (0 where u_t = 0) 
 u_t; the plant steps with u_t + e_t, while cost, sum ||u|| and the recorded u stay the commanded
 input's.  Both laws draw with the same counters (trajectory id traj0 + q), so the explicit and the
 implicit rollout of one seed see common random numbers.
+
+A ``GuardedPlant`` (the pendulum's, ``Plant.from_mpc`` of an ``InvertedPendulumOnCart``) runs S
+plant steps per controller step with u held and picks each step's mode itself from ordered guards
+on (x, u); there is no status 2, no d and no noise model, and ``mode`` is not recorded.
 """
 
 import time
@@ -60,6 +64,10 @@ class Plant:
         (``LinearPlant(T_s, A, B, E)`` of lib/mpc_library.py:258-269; one mode per step-0
         commutation value -- off, piece 0, piece 1 -- all with the same dynamics; the quadratic
         weights of its cost, R = 1/dv_max^2, Q = 1e-2 D_x^-2)."""
+        if hasattr(mpc, 'guarded_plant'):
+            return mpc.guarded_plant()
+        if any(r is not None and len(r) == 3 for r in getattr(mpc, 'regions', ())):
+            raise ValueError('a law with input-dependent mode regions needs a plant of its own')
         if hasattr(mpc, 'u_pieces'):
             pars = mpc.pars
             k = mpc.delta_size + 1
@@ -104,6 +112,176 @@ class Plant:
         if self.cost == 'inf':
             return np.abs(X @ self.Q.T).max(axis=1) + np.abs(U @ self.R.T).max(axis=1)
         return np.einsum('ni,ij,nj->n', X, self.Q, X) + np.einsum('ni,ij,nj->n', U, self.R, U)
+
+
+def _dot_rows(M, X):
+    """[n, r] = X @ M.T summed in column order from 0.0, one rounding per product and per sum (no
+    FMA): the order of the device's sums."""
+    out = np.zeros((X.shape[0], M.shape[0]))
+    for c in range(M.shape[1]):
+        out = out + X[:, c:c + 1] * M[None, :, c]
+    return out
+
+
+class GuardedPlant:
+    """
+    A multi-rate piecewise-affine plant that picks its own mode (lib/simulator.py:124-188 with a
+    plant such as lib/mpc_library.py:588-626): modes x+ = A[m] x + B[m] u + w[m] at the plant
+    period, ``substeps`` S plant steps per controller period (an integer, as lib/simulator.py:91
+    assumes), u held over them.  Before each plant step the mode is the first guard whose rows all
+    hold, else ``default_mode``; a guard row is
+
+        r = ((sum_c a_c x_c) + sum_c b_c u_c) + c      compared  r <= t  (or  r < t, ``strict``),
+
+    i.e. a.x + b.u + c - t (<= | <) 0 with the sum rounded independently of the threshold t.
+    ``guards``: list of (mode, rows), rows a list of (a [n_x], b [n_u], c, t, strict).  Stage cost
+    x'Qx + u'Ru (or inf-norm) and the state rows Gx x <= gx are taken at controller steps.  The
+    numpy step below is the device's (ehm_explicit_set_plant_guarded) bit for bit: sums in a fixed
+    order from 0.0, no FMA.
+    """
+
+    def __init__(self, A, B, w, substeps, guards, default_mode, Q, R, cost='quadratic', Gx=None,
+                 gx=None, T_s=None, T_s_plant=None):
+        self.A = np.ascontiguousarray(A, dtype=np.float64)
+        self.B = np.ascontiguousarray(B, dtype=np.float64)
+        self.w = np.ascontiguousarray(w, dtype=np.float64)
+        self.n_modes, self.n_x, self.n_u = self.B.shape
+        if int(substeps) != substeps or substeps < 1:
+            raise ValueError('substeps must be a positive integer')
+        self.substeps = int(substeps)
+        self.default_mode = int(default_mode)
+        self.guards = []
+        for mode, rows in guards:
+            if not 0 <= int(mode) < self.n_modes or not rows:
+                raise ValueError('a guard needs a mode of the plant and at least one row')
+            self.guards.append((int(mode), [(np.asarray(a, dtype=np.float64).reshape(self.n_x),
+                                             np.asarray(b, dtype=np.float64).reshape(self.n_u),
+                                             float(c), float(t), bool(st))
+                                            for a, b, c, t, st in rows]))
+        if not 0 <= self.default_mode < self.n_modes:
+            raise ValueError('the default mode is not a mode of the plant')
+        self.E = np.zeros((self.n_x, 0))
+        self.n_d = 0
+        self.Gx = np.zeros((0, self.n_x)) if Gx is None else np.ascontiguousarray(Gx, np.float64)
+        self.gx = np.zeros(0) if gx is None else np.ascontiguousarray(gx, np.float64)
+        self.Q = np.ascontiguousarray(Q, dtype=np.float64)
+        self.R = np.ascontiguousarray(R, dtype=np.float64)
+        if cost not in ('inf', 'quadratic'):
+            raise ValueError("cost must be 'inf' or 'quadratic'")
+        self.cost = cost
+        self.T_s, self.T_s_plant = T_s, T_s_plant
+
+    @classmethod
+    def pendulum(cls, mpc):
+        """The friction plant of an ``InvertedPendulumOnCart``: its five cases discretised at
+        T_s_plant, guards [v >= v_eps -> 0, v <= -v_eps -> 1, accel_2 > a_eps -> 2,
+        accel_3 < -a_eps -> 3], default 4 -- the if-cascade of lib/mpc_library.py:601-623, accel_i
+        the continuous-time row A_c[i][2] x + B_c[i][2] u + w_c[i][2]."""
+        from .mpc_library import discretize_affine
+        S = mpc.T_s / mpc.T_s_plant
+        if abs(S - round(S)) > 1e-9:
+            raise ValueError('the controller period is not a multiple of the plant period')
+        disc = [discretize_affine(mpc.A_c[i], mpc.B_c[i], mpc.w_c[i], mpc.T_s_plant)
+                for i in range(len(mpc.A_c))]
+        e2 = np.eye(mpc.n_x)[2]
+        z = np.zeros(mpc.n_u)
+        acc = lambda i: (mpc.A_c[i][2], np.atleast_1d(mpc.B_c[i][2]), mpc.w_c[i][2])
+        a2, b2, c2 = acc(2)
+        a3, b3, c3 = acc(3)
+        guards = [(0, [(-e2, z, 0., -mpc.v_eps, False)]),        # v >= v_eps
+                  (1, [(e2, z, 0., -mpc.v_eps, False)]),         # v <= -v_eps
+                  (2, [(-a2, -b2, -c2, -mpc.a_eps, True)]),      # accel_2 > a_eps
+                  (3, [(a3, b3, c3, -mpc.a_eps, True)])]         # accel_3 < -a_eps
+        return cls([d[0] for d in disc], [d[1] for d in disc], [d[2] for d in disc], round(S),
+                   guards, 4, mpc.Q, mpc.R, cost=mpc.cost_type, T_s=mpc.T_s,
+                   T_s_plant=mpc.T_s_plant)
+
+    def guard_arrays(self):
+        """Packed guards: mode [g] int32, row0 [g+1] int32, a [r, n_x], b [r, n_u], c [r], t [r],
+        strict [r] int32."""
+        mode, row0, a, b, c, t, st = [], [0], [], [], [], [], []
+        for m, rows in self.guards:
+            mode.append(m)
+            for ra, rb, rc, rt, rs in rows:
+                a.append(ra)
+                b.append(rb)
+                c.append(rc)
+                t.append(rt)
+                st.append(int(rs))
+            row0.append(len(c))
+        i32 = lambda v: np.array(v, dtype=np.int32)
+        return (i32(mode), i32(row0), np.array(a, dtype=np.float64).reshape(-1, self.n_x),
+                np.array(b, dtype=np.float64).reshape(-1, self.n_u), np.array(c, dtype=np.float64),
+                np.array(t, dtype=np.float64), i32(st))
+
+    def select_mode(self, X, U):
+        """int [n]: the mode each (x, u) row steps in."""
+        X, U = np.atleast_2d(X), np.atleast_2d(U)
+        mode = np.full(X.shape[0], self.default_mode, dtype=np.int64)
+        open_ = np.ones(X.shape[0], dtype=bool)
+        for m, rows in self.guards:
+            ok = open_.copy()
+            for a, b, c, t, strict in rows:
+                r = _dot_rows(a[None], X)[:, 0]
+                for j in range(self.n_u):
+                    r = r + b[j] * U[:, j]
+                r = r + c
+                ok &= (r < t) if strict else (r <= t)
+            mode[ok] = m
+            open_ &= ~ok
+        return mode
+
+    def plant_step(self, X, U):
+        """One plant period: (x+ [n, n_x], mode [n])."""
+        X, U = np.atleast_2d(X), np.atleast_2d(U)
+        m = self.select_mode(X, U)
+        out = np.zeros_like(X)
+        for i in range(self.n_x):
+            s = np.zeros(X.shape[0])
+            for c in range(self.n_x):
+                s = s + self.A[m, i, c] * X[:, c]
+            for c in range(self.n_u):
+                s = s + self.B[m, i, c] * U[:, c]
+            out[:, i] = s + self.w[m, i]
+        return out, m
+
+    def step(self, X, U, m=None, D=None):
+        """x after one controller period (S plant steps with u held); ``m`` is ignored -- the
+        plant chooses its own modes."""
+        if D is not None:
+            raise ValueError('a guarded plant takes no disturbance')
+        for _ in range(self.substeps):
+            X, _ = self.plant_step(X, U)
+        return X
+
+    def stage_cost(self, X, U):
+        """The stage cost at a controller step, in the device's summation order."""
+        if self.cost == 'inf':
+            return np.abs(_dot_rows(self.Q, X)).max(axis=1) + np.abs(_dot_rows(self.R, U)).max(axis=1)
+        s = np.zeros(X.shape[0])
+        QX = _dot_rows(self.Q, X)
+        for i in range(self.n_x):
+            s = s + X[:, i] * QX[:, i]
+        RU = _dot_rows(self.R, U)
+        for i in range(self.n_u):
+            s = s + U[:, i] * RU[:, i]
+        return s
+
+    def in_region(self, X, m, tol):
+        return np.ones(np.atleast_2d(X).shape[0], dtype=bool)
+
+
+def reference_call_steps(T_f, h_plant, h_ctrl):
+    """The plant-step indices at which lib/simulator.py:150-165 calls the controller: plant times
+    linspace(0, T_f, int(T_f / h_plant + 1)), a call where t - t_last >= h_ctrl - eps."""
+    times = np.linspace(0, T_f, int(T_f / h_plant + 1))
+    eps = np.finfo(float).eps
+    calls, last = [], None
+    for j, t in enumerate(times):
+        if last is None or t - last >= h_ctrl - eps:
+            last = t
+            calls.append(j)
+    return np.array(calls, dtype=np.int64), times
 
 
 class ClosedLoop:
@@ -152,6 +330,9 @@ def rollout_implicit(oracle, plant, X0, T, d=None, v=None, record=True, tol_exit
     """
     X0 = np.ascontiguousarray(np.atleast_2d(X0), dtype=np.float64)
     n, p = X0.shape
+    guarded = isinstance(plant, GuardedPlant)
+    if guarded and noise is not None:
+        raise ValueError('noise is not supported with a guarded plant')
     if noise is not None and (d is not None or v is not None):
         raise ValueError('noise draws d and v itself: give noise or d / v, not both')
     d = _as_batch(d, (T, n, plant.n_d), 'd')
@@ -225,7 +406,7 @@ def rollout_implicit(oracle, plant, X0, T, d=None, v=None, record=True, tol_exit
     out = ClosedLoop(x_final=x, steps=steps, status=status, cost=cost, u_norm_sum=unorm,
                      max_violation=maxv, seconds=time.time() - tic)
     if record:
-        out.x, out.u, out.commutation, out.mode = xs, us, cs, ms
+        out.x, out.u, out.commutation, out.mode = xs, us, cs, (None if guarded else ms)
         if noise is not None:
             out.v, out.e, out.w = vs, es, ws
     return out
@@ -283,7 +464,11 @@ class Simulator:
     controller's period T_s (1 if the law has none), so the run has int(T / T_s + 1) steps, as
     the reference's time grid.  ``noise``: a ``noise.NoiseModel``, 'reference' for the one the law
     was tightened against (``NoiseModel.from_mpc``), or None (nominal); w, v and e of the record
-    are its draws.  A trajectory that stops ends the record.
+    are its draws.  A trajectory that stops ends the record.  A law whose plant is guarded (the
+    pendulum's) runs the plant at its own period T_s_plant, the grid int(T / T_s_plant + 1) plant
+    steps long, and the controller every ``substeps`` of them -- checked against the reference's
+    floating-point rule (``reference_call_steps``); the plant-rate record comes from the host
+    mirror of the plant, which is the device's bit for bit.
     """
 
     def __init__(self, mpc, T, noise=None, seed=0):
@@ -300,10 +485,46 @@ class Simulator:
         self.h = getattr(mpc, 'T_s', None) or 1.
         self.sim_history = SimulationOutput()
 
+    def _guarded_plant(self):
+        plant = getattr(self.law, '_rollout_plant', None)
+        if plant is None and getattr(self.law, 'mpc', None) is not None:
+            plant = Plant.from_mpc(self.law.mpc)
+        return plant if isinstance(plant, GuardedPlant) else None
+
+    def _run_guarded(self, plant, x_0, out):
+        if self.noise is not None:
+            raise ValueError('noise is not supported with a guarded plant')
+        calls, times = reference_call_steps(self.T_f, plant.T_s_plant, plant.T_s)
+        S = plant.substeps
+        if not np.array_equal(calls, np.arange(0, len(times), S)):
+            raise ValueError('for T = %r the reference calls the controller at plant steps %s, not '
+                             'every %d' % (self.T_f, calls[:8].tolist(), S))
+        res = self.law.rollout(np.asarray(x_0, dtype=np.float64)[None], len(calls), record=True,
+                               plant=plant)
+        xs, us, ts, tc = [], [], [], []
+        for c in range(int(res.steps[0])):
+            x, u = res.x[c, 0], res.u[c, 0]
+            for j in range(min(S, len(times) - c * S)):
+                xs.append(x)
+                us.append(u)
+                ts.append(times[c * S + j])
+                tc.append(res.seconds / max(len(calls), 1) if j == 0 else 0.)
+                x = plant.plant_step(x[None], u[None])[0][0]
+        K = len(xs)
+        n_x, n_u = plant.n_x, plant.n_u
+        out.t, out.t_call = np.array(ts), np.array(tc)
+        out.x = np.array(xs).T.reshape(n_x, K)
+        out.u = np.array(us).T.reshape(n_u, K)
+        out.w, out.v, out.e = np.zeros((0, K)), np.zeros((n_x, K)), np.zeros((n_u, K))
+        return out
+
     def run(self, x_0, label=None):
         out = self.sim_history = SimulationOutput()
         if label is not None:
             out.label = label
+        plant = self._guarded_plant()
+        if plant is not None:
+            return self._run_guarded(plant, x_0, out)
         times = np.linspace(0, self.T_f, int(self.T_f / self.h + 1))
         kw = {} if self.noise is None else dict(noise=self.noise, seed=self.seed)
         res = self.law.rollout(np.asarray(x_0, dtype=np.float64)[None], len(times), record=True,

@@ -492,6 +492,25 @@ int ehm_explicit_set_plant(ehm_explicit* ex, int32_t n_modes, const double* A, c
                            int32_t n_g, const double* Gx, const double* gx,
                            const int32_t* node_mode, int32_t cost_kind, const double* Q,
                            const double* R);
+/* A guarded multi-rate plant instead (simulate.GuardedPlant; lib/simulator.py:124-188 with a
+ * plant period T_s / substeps, lib/mpc_library.py:588-626): per controller step the law's u is
+ * held over substeps (1..64) plant steps x+ = A_m x + B_m u + w_m, n_modes <= 8, where before
+ * each plant step m is guard_mode[g] of the first guard g (n_guards of them) whose rows
+ * guard_row0[g] .. guard_row0[g+1]-1 all hold, else default_mode.  Row r holds iff
+ *     ((sum_c ga[r][c] x_c) + sum_c gb[r][c] u_c) + gc[r]  <=  gt[r]     (< if strict[r]),
+ * summed in that order without FMA (at most 16 rows; ga [rows][p], gb [rows][n_u]).  No
+ * mode-region check (status 2 does not occur) and no disturbance; node_mode only marks leaves
+ * without commutation (-1, status 3).  Stage cost, u_norm_sum and the Gx rows are taken at
+ * controller steps, the records of ehm_explicit_rollout too.  ehm_explicit_rollout_noisy
+ * refuses a guarded plant.  Replaces an earlier plant. */
+int ehm_explicit_set_plant_guarded(ehm_explicit* ex, int32_t n_modes, const double* A,
+                                   const double* B, const double* w, int32_t substeps,
+                                   int32_t n_guards, const int32_t* guard_mode,
+                                   const int32_t* guard_row0, const double* ga, const double* gb,
+                                   const double* gc, const double* gt, const int32_t* strict,
+                                   int32_t default_mode, int32_t n_g, const double* Gx,
+                                   const double* gx, const int32_t* node_mode, int32_t cost_kind,
+                                   const double* Q, const double* R);
 /* n trajectories of T steps from x0 [n][p], one device thread each (Simulator.run,
  * lib/simulator.py:124-188).  Step t: measure z = x + v[t] (v [T][n][p] or NULL; no error at
  * t = 0, :168), locate z with the walk of ehm_explicit_eval_batch (same leaf, bit-equal u),
