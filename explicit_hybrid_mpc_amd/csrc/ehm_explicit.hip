@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -226,7 +227,8 @@ __global__ void k_explicit_eval(DevExplicit E, long long n, const double* __rest
 // lib/simulator.py:168), locate z with the walk of k_explicit_eval, stop if z is outside the leaf
 // (weight < -tol_exit), interpolate u as k_explicit_eval does, step the plant in the step-0 mode of
 // the leaf's commutation, accumulate stage cost / input 2-norm / worst constraint value.  Templated
-// on (p, n_u) so that state, weights and inputs live in VGPRs; the plant sits in LDS.
+// on (p, n_u) so that state, weights and inputs live in VGPRs, and on the plant kind (PlantKind);
+// the plant sits in LDS.
 #define EHM_R_MAX_NU 4
 #define EHM_R_MAX_MODES 4
 #define EHM_R_MAX_D 8
@@ -428,16 +430,20 @@ __device__ __forceinline__ void weights_t(const DevExplicit& E, long long k, con
     alpha0 = 1.0 - s;
 }
 
-// NOISY: v, e and w are drawn from the model in NZ (noise_kind) instead of read from R.v / R.d:
-// v at the true state and the last commanded input, e and w at the true state and the commanded
-// input, e = 0 where u = 0; the plant steps with u + e, cost and ||u|| stay the commanded input's.
-// GUARDED: the plant of GD (never together with NOISY) -- no mode-region check (status 2), and the
-// commanded u is held over GD.substeps plant steps whose modes the guards choose.
-template <int P, int NU, bool NOISY, bool GUARDED>
+// The plant a rollout kernel closes the loop around.
+// PK_NOISY: the nominal plant, with v, e and w drawn from the model in NZ (noise_kind) instead of
+// read from R.v / R.d: v at the true state and the last commanded input, e and w at the true state
+// and the commanded input, e = 0 where u = 0; the plant steps with u + e, cost and ||u|| stay the
+// commanded input's.
+// PK_GUARDED: the plant of GD -- no mode-region check (status 2), and the commanded u is held over
+// GD.substeps plant steps whose modes the guards choose.
+enum PlantKind { PK_NOMINAL, PK_NOISY, PK_GUARDED, PK_KINDS };
+
+template <int P, int NU, PlantKind KIND>
 __global__ __launch_bounds__(256) void k_explicit_rollout(DevExplicit E, DevPlant PL, RollArgs R,
                                                           DevNoise NZ, DevGuard GD) {
 #pragma clang fp contract(off)
-    static_assert(!(NOISY && GUARDED), "noisy guarded plants are not instantiated");
+    constexpr bool NOISY = KIND == PK_NOISY, GUARDED = KIND == PK_GUARDED;
     extern __shared__ double sh[];
     for (int i = threadIdx.x; i < PL.total; i += blockDim.x) sh[i] = PL.data[i];
     if constexpr (NOISY)
@@ -732,14 +738,13 @@ __global__ __launch_bounds__(256) void k_explicit_rollout(DevExplicit E, DevPlan
 }
 
 typedef void (*rollout_fn)(DevExplicit, DevPlant, RollArgs, DevNoise, DevGuard);
-#define EHM_R_NU(P, Z, G) &k_explicit_rollout<P, 1, Z, G>, &k_explicit_rollout<P, 2, Z, G>, \
-                          &k_explicit_rollout<P, 3, Z, G>, &k_explicit_rollout<P, 4, Z, G>
-#define EHM_R_ALL(Z, G) {EHM_R_NU(1, Z, G)}, {EHM_R_NU(2, Z, G)}, {EHM_R_NU(3, Z, G)},       \
-                        {EHM_R_NU(4, Z, G)}, {EHM_R_NU(5, Z, G)}, {EHM_R_NU(6, Z, G)},       \
-                        {EHM_R_NU(7, Z, G)}, {EHM_R_NU(8, Z, G)}
-const rollout_fn k_rollout_table[EHM_XP][EHM_R_MAX_NU] = {EHM_R_ALL(false, false)};
-const rollout_fn k_rollout_noisy_table[EHM_XP][EHM_R_MAX_NU] = {EHM_R_ALL(true, false)};
-const rollout_fn k_rollout_guarded_table[EHM_XP][EHM_R_MAX_NU] = {EHM_R_ALL(false, true)};
+#define EHM_R_NU(P, K) &k_explicit_rollout<P, 1, K>, &k_explicit_rollout<P, 2, K>, \
+                       &k_explicit_rollout<P, 3, K>, &k_explicit_rollout<P, 4, K>
+#define EHM_R_ALL(K) {{EHM_R_NU(1, K)}, {EHM_R_NU(2, K)}, {EHM_R_NU(3, K)}, {EHM_R_NU(4, K)}, \
+                      {EHM_R_NU(5, K)}, {EHM_R_NU(6, K)}, {EHM_R_NU(7, K)}, {EHM_R_NU(8, K)}}
+// [kind][p - 1][n_u - 1]
+const rollout_fn k_rollout_table[PK_KINDS][EHM_XP][EHM_R_MAX_NU] = {
+    EHM_R_ALL(PK_NOMINAL), EHM_R_ALL(PK_NOISY), EHM_R_ALL(PK_GUARDED)};
 #undef EHM_R_ALL
 #undef EHM_R_NU
 
@@ -774,21 +779,92 @@ int xfail(int code, const char* fmt, ...) {
     return code;
 }
 
+#define Y_TRY(expr)                                                                        \
+    do {                                                                                   \
+        hipError_t e_ = (expr);                                                            \
+        if (e_ != hipSuccess)                                                              \
+            return xfail(EHM_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
+    } while (0)
+
+// One device allocation, freed when its owner goes; moved, never copied.
+struct DevBuf {
+    void* p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        std::swap(p, o.p);
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    explicit operator bool() const { return p != nullptr; }
+    template <class T> T* as() const { return (T*)p; }
+    void reset() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    // a new buffer of `bytes` (at least 1) in place of the held one
+    hipError_t alloc(size_t bytes) {
+        reset();
+        const hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
+        if (e != hipSuccess) p = nullptr;
+        return e;
+    }
+    // the same, holding a copy of `bytes` of host memory
+    hipError_t upload(const void* src, size_t bytes) {
+        const hipError_t e = alloc(bytes);
+        return (e != hipSuccess || !bytes) ? e : hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
+    }
+};
+
+// The two events that time a launch, destroyed on every return.
+struct EventPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventPair() {
+        (void)hipEventCreate(&e0);
+        (void)hipEventCreate(&e1);
+    }
+    EventPair(const EventPair&) = delete;
+    EventPair& operator=(const EventPair&) = delete;
+    ~EventPair() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+    void seconds(double* out) const {
+        if (!out) return;
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        *out = ms * 1e-3;
+    }
+};
+
+// The doubles of a plant, one array after the other; put gives the array's offset (NULL: zeros).
+struct Pack {
+    std::vector<double> buf;
+    int put(const double* src, size_t cnt) {
+        const int off = (int)buf.size();
+        if (src) buf.insert(buf.end(), src, src + cnt);
+        else buf.insert(buf.end(), cnt, 0.0);
+        return off;
+    }
+};
+
 }  // namespace
 
 struct ehm_explicit {
     int device = 0;
     DevExplicit d{};
-    void *rec = nullptr, *child = nullptr, *vinput = nullptr;
-    void *x = nullptr, *u = nullptr, *leaf = nullptr, *depth = nullptr, *root = nullptr;
-    void* nbr = nullptr;        // [n_roots][p+1] root across the face opposite vertex i (-1: hull)
-    void *plant = nullptr, *node_mode = nullptr;     // ehm_explicit_set_plant
+    DevBuf rec, child, vinput;
+    DevBuf x, u, leaf, depth, root;     // ehm_explicit_eval_batch, cap queries
+    DevBuf nbr;         // [n_roots][p+1] root across the face opposite vertex i (-1: hull)
+    DevBuf plant, node_mode;                         // ehm_explicit_set_plant(_guarded)
     DevPlant pl{};
-    void* noise = nullptr;                           // ehm_explicit_set_noise
+    PlantKind kind = PK_NOMINAL;                     // PK_GUARDED: ehm_explicit_set_plant_guarded
+    DevGuard gd{};
+    DevBuf noise;                                    // ehm_explicit_set_noise
     DevNoise nz{};
     int noise_n_d = 0;
-    bool guarded = false;                            // ehm_explicit_set_plant_guarded
-    DevGuard gd{};
     size_t cap = 0;
     hipStream_t stream = nullptr;
 };
@@ -800,22 +876,10 @@ const char* ehm_explicit_last_error(void) { return x_err.c_str(); }
 int ehm_explicit_destroy(ehm_explicit* E) {
     if (!E) return EHM_OK;
     (void)hipSetDevice(E->device);
-    for (void* p : {E->rec, E->child, E->vinput, E->x, E->u, E->leaf, E->depth, E->root, E->nbr,
-                    E->plant, E->node_mode, E->noise})
-        if (p) (void)hipFree(p);
     if (E->stream) (void)hipStreamDestroy(E->stream);
-    delete E;
+    delete E;       // the buffers free themselves
     return EHM_OK;
 }
-
-#define X_TRY(expr)                                                                       \
-    do {                                                                                  \
-        hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess) {                                                           \
-            ehm_explicit_destroy(E);                                                      \
-            return xfail(EHM_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));       \
-        }                                                                                 \
-    } while (0)
 
 int ehm_explicit_create(int device, int64_t n_nodes, int32_t n_roots, int32_t p, int32_t n_u,
                         const int32_t* left, const int32_t* right, const double* vertices,
@@ -827,37 +891,30 @@ int ehm_explicit_create(int device, int64_t n_nodes, int32_t n_roots, int32_t p,
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
         return xfail(EHM_E_NO_DEVICE, "no HIP device %d (libehmpc has no CPU fallback)", device);
-    ehm_explicit* E = new ehm_explicit();
+    // destroyed on every error return below
+    std::unique_ptr<ehm_explicit, int (*)(ehm_explicit*)> E(new ehm_explicit(),
+                                                            ehm_explicit_destroy);
     E->device = device;
-    X_TRY(hipSetDevice(device));
-    X_TRY(hipStreamCreate(&E->stream));
+    Y_TRY(hipSetDevice(device));
+    Y_TRY(hipStreamCreate(&E->stream));
     const int stride = ((p + p * p + 7) / 8) * 8;
     const size_t nV = (size_t)n_nodes * (p + 1) * p, nU = (size_t)n_nodes * (p + 1) * n_u;
-    void* d_vert = nullptr;
-    int32_t* d_sing = nullptr;
-    X_TRY(hipMalloc(&E->rec, (size_t)n_nodes * stride * sizeof(double)));
-    X_TRY(hipMalloc(&E->child, (size_t)n_nodes * sizeof(int2)));
-    X_TRY(hipMalloc(&E->vinput, nU * sizeof(double)));
-    X_TRY(hipMalloc(&d_vert, nV * sizeof(double)));
-    X_TRY(hipMalloc((void**)&d_sing, sizeof(int32_t)));
     std::vector<int2> ch((size_t)n_nodes);
     for (int64_t k = 0; k < n_nodes; ++k) ch[(size_t)k] = make_int2(left[k], right[k]);
-    X_TRY(hipMemcpy(E->child, ch.data(), ch.size() * sizeof(int2), hipMemcpyHostToDevice));
-    X_TRY(hipMemcpy(E->vinput, vinput, nU * sizeof(double), hipMemcpyHostToDevice));
-    X_TRY(hipMemcpy(d_vert, vertices, nV * sizeof(double), hipMemcpyHostToDevice));
-    X_TRY(hipMemset(d_sing, 0, sizeof(int32_t)));
+    DevBuf d_vert, d_sing;
+    Y_TRY(E->rec.alloc((size_t)n_nodes * stride * sizeof(double)));
+    Y_TRY(E->child.upload(ch.data(), ch.size() * sizeof(int2)));
+    Y_TRY(E->vinput.upload(vinput, nU * sizeof(double)));
+    Y_TRY(d_vert.upload(vertices, nV * sizeof(double)));
+    Y_TRY(d_sing.alloc(sizeof(int32_t)));
+    Y_TRY(hipMemset(d_sing.p, 0, sizeof(int32_t)));
     hipLaunchKernelGGL(k_explicit_setup, dim3((unsigned)((n_nodes + 127) / 128)), dim3(128), 0,
-                       E->stream, (long long)n_nodes, (int)p, stride, (const double*)d_vert,
-                       (double*)E->rec, d_sing);
+                       E->stream, (long long)n_nodes, (int)p, stride, d_vert.as<const double>(),
+                       E->rec.as<double>(), d_sing.as<int32_t>());
     int32_t sing = 0;
-    X_TRY(hipMemcpyAsync(&sing, d_sing, sizeof sing, hipMemcpyDeviceToHost, E->stream));
-    X_TRY(hipStreamSynchronize(E->stream));
-    (void)hipFree(d_vert);
-    (void)hipFree(d_sing);
-    if (sing) {
-        ehm_explicit_destroy(E);
-        return xfail(EHM_E_NUMERIC, "%d degenerate simplices in the partition", (int)sing);
-    }
+    Y_TRY(hipMemcpyAsync(&sing, d_sing.p, sizeof sing, hipMemcpyDeviceToHost, E->stream));
+    Y_TRY(hipStreamSynchronize(E->stream));
+    if (sing) return xfail(EHM_E_NUMERIC, "%d degenerate simplices in the partition", (int)sing);
     if (n_roots >= EHM_X_LOCATE_MIN && n_roots < (1 << 20)) {
         // face adjacency of the roots: vertices by value, faces by their sorted vertex ids
         std::unordered_map<std::string, int32_t> vid;
@@ -889,18 +946,17 @@ int ehm_explicit_create(int device, int64_t n_nodes, int32_t n_roots, int32_t p,
                     nbr[(size_t)o] = (int32_t)r;
                 }
             }
-        X_TRY(hipMalloc(&E->nbr, nbr.size() * sizeof(int32_t)));
-        X_TRY(hipMemcpy(E->nbr, nbr.data(), nbr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+        Y_TRY(E->nbr.upload(nbr.data(), nbr.size() * sizeof(int32_t)));
     }
-    E->d.rec = (const double*)E->rec;
-    E->d.child = (const int2*)E->child;
-    E->d.vinput = (const double*)E->vinput;
+    E->d.rec = E->rec.as<const double>();
+    E->d.child = E->child.as<const int2>();
+    E->d.vinput = E->vinput.as<const double>();
     E->d.rec_stride = stride;
     E->d.p = p;
     E->d.n_u = n_u;
     E->d.n_roots = n_roots;
     E->d.n_nodes = n_nodes;
-    *out = E;
+    *out = E.release();
     return EHM_OK;
 }
 
@@ -912,259 +968,105 @@ int ehm_explicit_eval_batch(ehm_explicit* E, int64_t n, const double* x, double*
     if (e != hipSuccess) return xfail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
     const int p = E->d.p, n_u = E->d.n_u;
     if ((size_t)n > E->cap) {
-        for (void** q : {&E->x, &E->u, &E->leaf, &E->depth, &E->root}) {
-            if (*q) (void)hipFree(*q);
-            *q = nullptr;
-        }
+        for (DevBuf* b : {&E->x, &E->u, &E->leaf, &E->depth, &E->root}) b->reset();
         E->cap = 0;
-        if (hipMalloc(&E->x, (size_t)n * p * sizeof(double)) != hipSuccess ||
-            hipMalloc(&E->u, (size_t)n * n_u * sizeof(double)) != hipSuccess ||
-            hipMalloc(&E->leaf, (size_t)n * sizeof(int32_t)) != hipSuccess ||
-            hipMalloc(&E->depth, (size_t)n * sizeof(int32_t)) != hipSuccess ||
-            hipMalloc(&E->root, (size_t)n * sizeof(int32_t)) != hipSuccess)
+        if (E->x.alloc((size_t)n * p * sizeof(double)) != hipSuccess ||
+            E->u.alloc((size_t)n * n_u * sizeof(double)) != hipSuccess ||
+            E->leaf.alloc((size_t)n * sizeof(int32_t)) != hipSuccess ||
+            E->depth.alloc((size_t)n * sizeof(int32_t)) != hipSuccess ||
+            E->root.alloc((size_t)n * sizeof(int32_t)) != hipSuccess)
             return xfail(EHM_E_HIP, "out of device memory for %lld queries", (long long)n);
         E->cap = (size_t)n;
     }
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
-#define Y_TRY(expr)                                                                        \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return xfail(EHM_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
-    } while (0)
-    Y_TRY(hipMemcpyAsync(E->x, x, (size_t)n * p * sizeof(double), hipMemcpyHostToDevice,
+    EventPair ev;
+    Y_TRY(hipMemcpyAsync(E->x.p, x, (size_t)n * p * sizeof(double), hipMemcpyHostToDevice,
                          E->stream));
-    (void)hipEventRecord(e0, E->stream);
+    (void)hipEventRecord(ev.e0, E->stream);
     // long spines: the visibility walk over the roots finds the root first (locate_off: the
     // reference's serial walk for every state)
     const bool locate = E->nbr && !locate_off();
     if (locate)
         hipLaunchKernelGGL(k_explicit_locate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                           E->stream, E->d, (long long)n, (const double*)E->x,
-                           (const int32_t*)E->nbr, (int32_t*)E->root);
+                           E->stream, E->d, (long long)n, E->x.as<const double>(),
+                           E->nbr.as<const int32_t>(), E->root.as<int32_t>());
     hipLaunchKernelGGL(k_explicit_eval, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       E->stream, E->d, (long long)n, (const double*)E->x, (double*)E->u,
-                       (int32_t*)E->leaf, (int32_t*)E->depth,
-                       locate ? (const int32_t*)E->root : (const int32_t*)nullptr);
-    (void)hipEventRecord(e1, E->stream);
+                       E->stream, E->d, (long long)n, E->x.as<const double>(), E->u.as<double>(),
+                       E->leaf.as<int32_t>(), E->depth.as<int32_t>(),
+                       locate ? E->root.as<const int32_t>() : (const int32_t*)nullptr);
+    (void)hipEventRecord(ev.e1, E->stream);
     Y_TRY(hipGetLastError());
-    Y_TRY(hipMemcpyAsync(u, E->u, (size_t)n * n_u * sizeof(double), hipMemcpyDeviceToHost,
+    Y_TRY(hipMemcpyAsync(u, E->u.p, (size_t)n * n_u * sizeof(double), hipMemcpyDeviceToHost,
                          E->stream));
     if (leaf)
-        Y_TRY(hipMemcpyAsync(leaf, E->leaf, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost,
+        Y_TRY(hipMemcpyAsync(leaf, E->leaf.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost,
                              E->stream));
     if (visited)
-        Y_TRY(hipMemcpyAsync(visited, E->depth, (size_t)n * sizeof(int32_t),
+        Y_TRY(hipMemcpyAsync(visited, E->depth.p, (size_t)n * sizeof(int32_t),
                              hipMemcpyDeviceToHost, E->stream));
     Y_TRY(hipStreamSynchronize(E->stream));
-    if (kernel_seconds) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        *kernel_seconds = ms * 1e-3;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    return EHM_OK;
-}
-
-int ehm_explicit_set_plant(ehm_explicit* E, int32_t n_modes, const double* A, const double* B,
-                           const double* w, int32_t n_d, const double* Emat,
-                           const int32_t* region_rows, const double* H, const double* h,
-                           int32_t n_g, const double* Gx, const double* gx,
-                           const int32_t* node_mode, int32_t cost_kind, const double* Q,
-                           const double* R) {
-    if (!E || !A || !B || !w || !node_mode || !Q || !R)
-        return xfail(EHM_E_INVALID, "set_plant: a required array is NULL");
-    if (n_modes < 1 || n_modes > EHM_R_MAX_MODES)
-        return xfail(EHM_E_INVALID, "set_plant: %d modes (1..%d)", (int)n_modes,
-                     EHM_R_MAX_MODES);
-    if (n_d < 0 || n_d > EHM_R_MAX_D || (n_d > 0 && !Emat))
-        return xfail(EHM_E_INVALID, "set_plant: n_d = %d (0..%d, E needed if > 0)", (int)n_d,
-                     EHM_R_MAX_D);
-    if (n_g < 0 || n_g > EHM_R_MAX_ROWS || (n_g > 0 && (!Gx || !gx)))
-        return xfail(EHM_E_INVALID, "set_plant: n_g = %d (0..%d)", (int)n_g, EHM_R_MAX_ROWS);
-    if (cost_kind != 0 && cost_kind != 1)
-        return xfail(EHM_E_INVALID, "set_plant: cost_kind %d (0 inf-norm, 1 quadratic)",
-                     (int)cost_kind);
-    const int p = E->d.p, n_u = E->d.n_u;
-    if (n_u > EHM_R_MAX_NU)
-        return xfail(EHM_E_INVALID, "set_plant: n_u = %d, the rollout takes at most %d inputs",
-                     n_u, EHM_R_MAX_NU);
-    DevPlant pl{};
-    pl.n_modes = n_modes;
-    pl.n_d = n_d;
-    pl.n_g = n_g;
-    pl.cost_kind = cost_kind;
-    int rows = 0;
-    for (int m = 0; m < n_modes; ++m) {
-        const int r = region_rows ? region_rows[m] : 0;
-        if (r < 0) return xfail(EHM_E_INVALID, "set_plant: mode %d has %d region rows", m, r);
-        pl.row0[m] = rows;
-        rows += r;
-    }
-    if (rows > EHM_R_MAX_ROWS || (rows > 0 && (!H || !h)))
-        return xfail(EHM_E_INVALID, "set_plant: %d mode-region rows (0..%d)", rows,
-                     EHM_R_MAX_ROWS);
-    for (int m = n_modes; m <= EHM_R_MAX_MODES; ++m) pl.row0[m] = rows;
-    std::vector<double> buf;
-    auto put = [&](const double* src, size_t cnt) {
-        const int off = (int)buf.size();
-        if (src) buf.insert(buf.end(), src, src + cnt);
-        else buf.insert(buf.end(), cnt, 0.0);
-        return off;
-    };
-    pl.oA = put(A, (size_t)n_modes * p * p);
-    pl.oB = put(B, (size_t)n_modes * p * n_u);
-    pl.ow = put(w, (size_t)n_modes * p);
-    pl.oE = put(Emat, (size_t)p * n_d);
-    pl.oH = put(H, (size_t)rows * p);
-    pl.oh = put(h, (size_t)rows);
-    pl.oG = put(Gx, (size_t)n_g * p);
-    pl.og = put(gx, (size_t)n_g);
-    pl.oQ = put(Q, (size_t)p * p);
-    pl.oR = put(R, (size_t)n_u * n_u);
-    pl.total = (int)buf.size();
-    for (int64_t k = 0; k < E->d.n_nodes; ++k)
-        if (node_mode[k] >= n_modes)
-            return xfail(EHM_E_INVALID, "set_plant: node %lld has mode %d of %d", (long long)k,
-                         (int)node_mode[k], (int)n_modes);
-    hipError_t e = hipSetDevice(E->device);
-    if (e != hipSuccess) return xfail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
-    void *d_plant = nullptr, *d_mode = nullptr;
-    const size_t mb = (size_t)E->d.n_nodes * sizeof(int32_t);
-    if (hipMalloc(&d_plant, buf.size() * sizeof(double)) != hipSuccess ||
-        hipMalloc(&d_mode, mb) != hipSuccess ||
-        hipMemcpy(d_plant, buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice) !=
-            hipSuccess ||
-        hipMemcpy(d_mode, node_mode, mb, hipMemcpyHostToDevice) != hipSuccess) {
-        if (d_plant) (void)hipFree(d_plant);
-        if (d_mode) (void)hipFree(d_mode);
-        return xfail(EHM_E_HIP, "set_plant: device allocation / copy failed");
-    }
-    if (E->plant) (void)hipFree(E->plant);
-    if (E->node_mode) (void)hipFree(E->node_mode);
-    E->plant = d_plant;
-    E->node_mode = d_mode;
-    pl.data = (const double*)d_plant;
-    E->pl = pl;
-    E->guarded = false;
-    return EHM_OK;
-}
-
-int ehm_explicit_set_plant_guarded(ehm_explicit* E, int32_t n_modes, const double* A,
-                                   const double* B, const double* w, int32_t substeps,
-                                   int32_t n_guards, const int32_t* guard_mode,
-                                   const int32_t* guard_row0, const double* ga, const double* gb,
-                                   const double* gc, const double* gt, const int32_t* strict,
-                                   int32_t default_mode, int32_t n_g, const double* Gx,
-                                   const double* gx, const int32_t* node_mode, int32_t cost_kind,
-                                   const double* Q, const double* R) {
-    if (!E || !A || !B || !w || !node_mode || !Q || !R || (n_guards > 0 && !guard_mode) ||
-        !guard_row0)
-        return xfail(EHM_E_INVALID, "set_plant_guarded: a required array is NULL");
-    if (n_modes < 1 || n_modes > EHM_G_MAX_MODES)
-        return xfail(EHM_E_INVALID, "set_plant_guarded: %d modes (1..%d)", (int)n_modes,
-                     EHM_G_MAX_MODES);
-    if (substeps < 1 || substeps > EHM_G_MAX_SUB)
-        return xfail(EHM_E_INVALID, "set_plant_guarded: %d substeps (1..%d)", (int)substeps,
-                     EHM_G_MAX_SUB);
-    if (n_guards < 0 || n_guards > EHM_G_MAX_ROWS)
-        return xfail(EHM_E_INVALID, "set_plant_guarded: %d guards (0..%d)", (int)n_guards,
-                     EHM_G_MAX_ROWS);
-    if (default_mode < 0 || default_mode >= n_modes)
-        return xfail(EHM_E_INVALID, "set_plant_guarded: default mode %d of %d", (int)default_mode,
-                     (int)n_modes);
-    if (n_g < 0 || n_g > EHM_R_MAX_ROWS || (n_g > 0 && (!Gx || !gx)))
-        return xfail(EHM_E_INVALID, "set_plant_guarded: n_g = %d (0..%d)", (int)n_g,
-                     EHM_R_MAX_ROWS);
-    if (cost_kind != 0 && cost_kind != 1)
-        return xfail(EHM_E_INVALID, "set_plant_guarded: cost_kind %d (0 inf-norm, 1 quadratic)",
-                     (int)cost_kind);
-    const int p = E->d.p, n_u = E->d.n_u;
-    if (n_u > EHM_R_MAX_NU)
-        return xfail(EHM_E_INVALID,
-                     "set_plant_guarded: n_u = %d, the rollout takes at most %d inputs", n_u,
-                     EHM_R_MAX_NU);
-    DevGuard gd{};
-    gd.substeps = substeps;
-    gd.n_guards = n_guards;
-    gd.default_mode = default_mode;
-    if (guard_row0[0] != 0)
-        return xfail(EHM_E_INVALID, "set_plant_guarded: the rows of guard 0 start at %d",
-                     (int)guard_row0[0]);
-    for (int g = 0; g <= n_guards; ++g) {
-        if (g < n_guards) {
-            if (guard_mode[g] < 0 || guard_mode[g] >= n_modes)
-                return xfail(EHM_E_INVALID, "set_plant_guarded: guard %d selects mode %d of %d", g,
-                             (int)guard_mode[g], (int)n_modes);
-            if (guard_row0[g + 1] <= guard_row0[g])
-                return xfail(EHM_E_INVALID, "set_plant_guarded: guard %d has no rows", g);
-            gd.mode[g] = guard_mode[g];
-        }
-        gd.row0[g] = guard_row0[g];
-    }
-    const int rows = guard_row0[n_guards];
-    if (rows > EHM_G_MAX_ROWS || (rows > 0 && (!ga || !gb || !gc || !gt || !strict)))
-        return xfail(EHM_E_INVALID, "set_plant_guarded: %d guard rows (0..%d)", rows,
-                     EHM_G_MAX_ROWS);
-    for (int r = 0; r < rows; ++r) gd.strict[r] = strict[r] != 0;
-    DevPlant pl{};
-    pl.n_modes = n_modes;
-    pl.n_g = n_g;
-    pl.cost_kind = cost_kind;
-    std::vector<double> buf;
-    auto put = [&](const double* src, size_t cnt) {
-        const int off = (int)buf.size();
-        if (src) buf.insert(buf.end(), src, src + cnt);
-        else buf.insert(buf.end(), cnt, 0.0);
-        return off;
-    };
-    pl.oA = put(A, (size_t)n_modes * p * p);
-    pl.oB = put(B, (size_t)n_modes * p * n_u);
-    pl.ow = put(w, (size_t)n_modes * p);
-    pl.oE = pl.oH = pl.oh = (int)buf.size();
-    pl.oG = put(Gx, (size_t)n_g * p);
-    pl.og = put(gx, (size_t)n_g);
-    pl.oQ = put(Q, (size_t)p * p);
-    pl.oR = put(R, (size_t)n_u * n_u);
-    gd.oGa = put(ga, (size_t)rows * p);
-    gd.oGb = put(gb, (size_t)rows * n_u);
-    gd.oGc = put(gc, (size_t)rows);
-    gd.oGt = put(gt, (size_t)rows);
-    pl.total = (int)buf.size();
-    for (int64_t k = 0; k < E->d.n_nodes; ++k)
-        if (node_mode[k] < -1)
-            return xfail(EHM_E_INVALID, "set_plant_guarded: node %lld has mode %d", (long long)k,
-                         (int)node_mode[k]);
-    hipError_t e = hipSetDevice(E->device);
-    if (e != hipSuccess) return xfail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
-    void *d_plant = nullptr, *d_mode = nullptr;
-    const size_t mb = (size_t)E->d.n_nodes * sizeof(int32_t);
-    if (hipMalloc(&d_plant, buf.size() * sizeof(double)) != hipSuccess ||
-        hipMalloc(&d_mode, mb) != hipSuccess ||
-        hipMemcpy(d_plant, buf.data(), buf.size() * sizeof(double), hipMemcpyHostToDevice) !=
-            hipSuccess ||
-        hipMemcpy(d_mode, node_mode, mb, hipMemcpyHostToDevice) != hipSuccess) {
-        if (d_plant) (void)hipFree(d_plant);
-        if (d_mode) (void)hipFree(d_mode);
-        return xfail(EHM_E_HIP, "set_plant_guarded: device allocation / copy failed");
-    }
-    if (E->plant) (void)hipFree(E->plant);
-    if (E->node_mode) (void)hipFree(E->node_mode);
-    E->plant = d_plant;
-    E->node_mode = d_mode;
-    pl.data = (const double*)d_plant;
-    E->pl = pl;
-    E->gd = gd;
-    E->guarded = true;
+    ev.seconds(kernel_seconds);
     return EHM_OK;
 }
 
 }  // extern "C"
 
 namespace {
+
+// What the two plant setters share: the checks of the common arguments; A, B, w, Gx, gx, Q and R
+// packed, then the setter's own arrays (`own` checks and packs them); node_mode checked (< n_modes
+// for the nominal plant; >= -1 for a guarded one, whose guards choose the modes); the new device
+// buffers swapped in.  gd: the guards of a guarded plant (filled by `own`), nullptr for the nominal.
+template <class Own>
+int install_plant(ehm_explicit* E, const char* who, int32_t n_modes, int max_modes,
+                  const double* A, const double* B, const double* w, int32_t n_g, const double* Gx,
+                  const double* gx, const int32_t* node_mode, int32_t cost_kind, const double* Q,
+                  const double* R, const DevGuard* gd, Own own) {
+    if (!E || !A || !B || !w || !node_mode || !Q || !R)
+        return xfail(EHM_E_INVALID, "%s: a required array is NULL", who);
+    if (n_modes < 1 || n_modes > max_modes)
+        return xfail(EHM_E_INVALID, "%s: %d modes (1..%d)", who, (int)n_modes, max_modes);
+    if (n_g < 0 || n_g > EHM_R_MAX_ROWS || (n_g > 0 && (!Gx || !gx)))
+        return xfail(EHM_E_INVALID, "%s: n_g = %d (0..%d)", who, (int)n_g, EHM_R_MAX_ROWS);
+    if (cost_kind != 0 && cost_kind != 1)
+        return xfail(EHM_E_INVALID, "%s: cost_kind %d (0 inf-norm, 1 quadratic)", who,
+                     (int)cost_kind);
+    const int p = E->d.p, n_u = E->d.n_u;
+    if (n_u > EHM_R_MAX_NU)
+        return xfail(EHM_E_INVALID, "%s: n_u = %d, the rollout takes at most %d inputs", who, n_u,
+                     EHM_R_MAX_NU);
+    DevPlant pl{};
+    pl.n_modes = n_modes;
+    pl.n_g = n_g;
+    pl.cost_kind = cost_kind;
+    Pack pk;
+    pl.oA = pk.put(A, (size_t)n_modes * p * p);
+    pl.oB = pk.put(B, (size_t)n_modes * p * n_u);
+    pl.ow = pk.put(w, (size_t)n_modes * p);
+    pl.oG = pk.put(Gx, (size_t)n_g * p);
+    pl.og = pk.put(gx, (size_t)n_g);
+    pl.oQ = pk.put(Q, (size_t)p * p);
+    pl.oR = pk.put(R, (size_t)n_u * n_u);
+    const int rc = own(pk, pl, p, n_u);
+    if (rc != EHM_OK) return rc;
+    pl.total = (int)pk.buf.size();
+    for (int64_t k = 0; k < E->d.n_nodes; ++k)
+        if (gd ? node_mode[k] < -1 : node_mode[k] >= n_modes)
+            return xfail(EHM_E_INVALID, "%s: node %lld has mode %d of %d", who, (long long)k,
+                         (int)node_mode[k], (int)n_modes);
+    hipError_t e = hipSetDevice(E->device);
+    if (e != hipSuccess) return xfail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
+    DevBuf d_plant, d_mode;
+    if (d_plant.upload(pk.buf.data(), pk.buf.size() * sizeof(double)) != hipSuccess ||
+        d_mode.upload(node_mode, (size_t)E->d.n_nodes * sizeof(int32_t)) != hipSuccess)
+        return xfail(EHM_E_HIP, "%s: device allocation / copy failed", who);
+    E->plant = std::move(d_plant);
+    E->node_mode = std::move(d_mode);
+    pl.data = E->plant.as<const double>();
+    E->pl = pl;
+    E->kind = gd ? PK_GUARDED : PK_NOMINAL;
+    if (gd) E->gd = *gd;
+    return EHM_OK;
+}
 
 // the noisy rollout's extra arguments
 struct NoisyCall {
@@ -1185,72 +1087,65 @@ int rollout_run(ehm_explicit* E, int64_t n, int32_t T, const double* x0, const d
     if (d && E->pl.n_d == 0)
         return xfail(EHM_E_INVALID, "rollout: a disturbance was given but the plant has no E");
     // a plant set after the model may have grown past what set_noise checked
-    if (nz && E->guarded)
+    if (nz && E->kind == PK_GUARDED)
         return xfail(EHM_E_INVALID, "rollout_noisy: the plant is guarded (noisy guarded plants "
                                     "are not supported)");
     if (nz && E->pl.total + E->nz.total > EHM_N_MAX_LDS)
         return xfail(EHM_E_INVALID, "rollout_noisy: plant and model take %d doubles of LDS (%d)",
                      E->pl.total + E->nz.total, EHM_N_MAX_LDS);
-    const int p = E->d.p, n_u = E->d.n_u;
+    const int p = E->d.p, n_u = E->d.n_u, n_d = E->pl.n_d;
     if (n == 0) return EHM_OK;
     if (n > (int64_t)1 << 31) return xfail(EHM_E_INVALID, "rollout: %lld trajectories", (long long)n);
     hipError_t e = hipSetDevice(E->device);
     if (e != hipSuccess) return xfail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
-    const size_t N = (size_t)n, nT = (size_t)T;
-    // device buffers of this call, released on every return below
-    struct Bufs {
-        std::vector<void*> v;
-        ~Bufs() {
-            for (void* p : v) (void)hipFree(p);
-        }
-        void* get(size_t bytes) {
-            void* p = nullptr;
-            if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) return nullptr;
-            v.push_back(p);
-            return p;
-        }
-    } bufs;
+    const size_t N = (size_t)n, nT = (size_t)T, D = sizeof(double), I = sizeof(int32_t);
     RollArgs R{};
     R.n = n;
     R.T = T;
     R.tol_exit = tol_exit;
-    double *dx0 = (double*)bufs.get(N * p * sizeof(double)), *dd = nullptr, *dv = nullptr;
-    R.x_final = (double*)bufs.get(N * p * sizeof(double));
-    R.cost = (double*)bufs.get(N * sizeof(double));
-    R.u_norm = (double*)bufs.get(N * sizeof(double));
-    R.max_viol = (double*)bufs.get(N * sizeof(double));
-    R.steps = (int32_t*)bufs.get(N * sizeof(int32_t));
-    R.status = (int32_t*)bufs.get(N * sizeof(int32_t));
-    if (d) dd = (double*)bufs.get(nT * N * E->pl.n_d * sizeof(double));
-    if (v) dv = (double*)bufs.get(nT * N * p * sizeof(double));
-    if (x_traj) R.x_traj = (double*)bufs.get((nT + 1) * N * p * sizeof(double));
-    if (u_traj) R.u_traj = (double*)bufs.get(nT * N * n_u * sizeof(double));
-    if (leaf_traj) R.leaf_traj = (int32_t*)bufs.get(nT * N * sizeof(int32_t));
-    if (nz && nz->v_traj) R.v_traj = (double*)bufs.get(nT * N * p * sizeof(double));
-    if (nz && nz->e_traj) R.e_traj = (double*)bufs.get(nT * N * n_u * sizeof(double));
-    if (nz && nz->w_traj) R.w_traj = (double*)bufs.get(nT * N * E->pl.n_d * sizeof(double));
-    if (!dx0 || !R.x_final || !R.cost || !R.u_norm || !R.max_viol || !R.steps || !R.status ||
-        (d && !dd) || (v && !dv) || (x_traj && !R.x_traj) || (u_traj && !R.u_traj) ||
-        (leaf_traj && !R.leaf_traj) || (nz && nz->v_traj && !R.v_traj) ||
-        (nz && nz->e_traj && !R.e_traj) || (nz && nz->w_traj && !R.w_traj))
+    // the per-trajectory outputs: host array (nullptr: not asked for), the RollArgs pointer its
+    // device buffer goes to, bytes
+    struct Out {
+        void* host;
+        void* field;
+        size_t bytes;
+        DevBuf buf;
+    } out[] = {
+        {x_final, &R.x_final, N * p * D},
+        {steps, &R.steps, N * I},
+        {status, &R.status, N * I},
+        {cost, &R.cost, N * D},
+        {u_norm_sum, &R.u_norm, N * D},
+        {max_violation, &R.max_viol, N * D},
+        {x_traj, &R.x_traj, (nT + 1) * N * p * D},
+        {u_traj, &R.u_traj, nT * N * n_u * D},
+        {leaf_traj, &R.leaf_traj, nT * N * I},
+        {nz ? nz->v_traj : nullptr, &R.v_traj, nT * N * p * D},
+        {nz ? nz->e_traj : nullptr, &R.e_traj, nT * N * n_u * D},
+        {nz ? nz->w_traj : nullptr, &R.w_traj, nT * N * n_d * D},
+    };
+    DevBuf dx0, dd, dv;
+    bool ok = dx0.alloc(N * p * D) == hipSuccess &&
+              (!d || dd.alloc(nT * N * n_d * D) == hipSuccess) &&
+              (!v || dv.alloc(nT * N * p * D) == hipSuccess);
+    for (Out& o : out)
+        if (ok && o.host) {
+            ok = o.buf.alloc(o.bytes) == hipSuccess;
+            std::memcpy(o.field, &o.buf.p, sizeof o.buf.p);
+        }
+    if (!ok)
         return xfail(EHM_E_HIP, "rollout: out of device memory for %lld x %d steps",
                      (long long)n, (int)T);
-    R.x0 = dx0;
-    R.d = dd;
-    R.v = dv;
-    R.node_mode = (const int32_t*)E->node_mode;
-    R.nbr = (E->nbr && !locate_off()) ? (const int32_t*)E->nbr : nullptr;
-    Y_TRY(hipMemcpyAsync(dx0, x0, N * p * sizeof(double), hipMemcpyHostToDevice, E->stream));
-    if (d)
-        Y_TRY(hipMemcpyAsync(dd, d, nT * N * E->pl.n_d * sizeof(double), hipMemcpyHostToDevice,
-                             E->stream));
-    if (v)
-        Y_TRY(hipMemcpyAsync(dv, v, nT * N * p * sizeof(double), hipMemcpyHostToDevice,
-                             E->stream));
-    hipEvent_t e0, e1;
-    (void)hipEventCreate(&e0);
-    (void)hipEventCreate(&e1);
-    (void)hipEventRecord(e0, E->stream);
+    R.x0 = dx0.as<const double>();
+    R.d = dd.as<const double>();
+    R.v = dv.as<const double>();
+    R.node_mode = E->node_mode.as<const int32_t>();
+    R.nbr = (E->nbr && !locate_off()) ? E->nbr.as<const int32_t>() : nullptr;
+    Y_TRY(hipMemcpyAsync(dx0.p, x0, N * p * D, hipMemcpyHostToDevice, E->stream));
+    if (d) Y_TRY(hipMemcpyAsync(dd.p, d, nT * N * n_d * D, hipMemcpyHostToDevice, E->stream));
+    if (v) Y_TRY(hipMemcpyAsync(dv.p, v, nT * N * p * D, hipMemcpyHostToDevice, E->stream));
+    EventPair ev;
+    (void)hipEventRecord(ev.e0, E->stream);
     DevNoise NZ{};
     size_t lds = (size_t)E->pl.total * sizeof(double);
     if (nz) {
@@ -1259,54 +1154,108 @@ int rollout_run(ehm_explicit* E, int64_t n, int32_t T, const double* x0, const d
         NZ.traj0 = nz->traj0;
         lds += (size_t)NZ.total * sizeof(double);
     }
-    const rollout_fn fn = (nz ? k_rollout_noisy_table
-                              : E->guarded ? k_rollout_guarded_table : k_rollout_table)[p - 1][n_u - 1];
+    const rollout_fn fn = k_rollout_table[nz ? PK_NOISY : E->kind][p - 1][n_u - 1];
     hipLaunchKernelGGL(fn, dim3((unsigned)((n + 255) / 256)), dim3(256), lds, E->stream, E->d,
                        E->pl, R, NZ, E->gd);
-    (void)hipEventRecord(e1, E->stream);
+    (void)hipEventRecord(ev.e1, E->stream);
     Y_TRY(hipGetLastError());
-    Y_TRY(hipMemcpyAsync(x_final, R.x_final, N * p * sizeof(double), hipMemcpyDeviceToHost,
-                         E->stream));
-    Y_TRY(hipMemcpyAsync(steps, R.steps, N * sizeof(int32_t), hipMemcpyDeviceToHost, E->stream));
-    Y_TRY(hipMemcpyAsync(status, R.status, N * sizeof(int32_t), hipMemcpyDeviceToHost,
-                         E->stream));
-    Y_TRY(hipMemcpyAsync(cost, R.cost, N * sizeof(double), hipMemcpyDeviceToHost, E->stream));
-    Y_TRY(hipMemcpyAsync(u_norm_sum, R.u_norm, N * sizeof(double), hipMemcpyDeviceToHost,
-                         E->stream));
-    Y_TRY(hipMemcpyAsync(max_violation, R.max_viol, N * sizeof(double), hipMemcpyDeviceToHost,
-                         E->stream));
-    if (x_traj)
-        Y_TRY(hipMemcpyAsync(x_traj, R.x_traj, (nT + 1) * N * p * sizeof(double),
-                             hipMemcpyDeviceToHost, E->stream));
-    if (u_traj)
-        Y_TRY(hipMemcpyAsync(u_traj, R.u_traj, nT * N * n_u * sizeof(double),
-                             hipMemcpyDeviceToHost, E->stream));
-    if (leaf_traj)
-        Y_TRY(hipMemcpyAsync(leaf_traj, R.leaf_traj, nT * N * sizeof(int32_t),
-                             hipMemcpyDeviceToHost, E->stream));
-    if (R.v_traj)
-        Y_TRY(hipMemcpyAsync(nz->v_traj, R.v_traj, nT * N * p * sizeof(double),
-                             hipMemcpyDeviceToHost, E->stream));
-    if (R.e_traj)
-        Y_TRY(hipMemcpyAsync(nz->e_traj, R.e_traj, nT * N * n_u * sizeof(double),
-                             hipMemcpyDeviceToHost, E->stream));
-    if (R.w_traj)
-        Y_TRY(hipMemcpyAsync(nz->w_traj, R.w_traj, nT * N * E->pl.n_d * sizeof(double),
-                             hipMemcpyDeviceToHost, E->stream));
+    for (const Out& o : out)
+        if (o.host)
+            Y_TRY(hipMemcpyAsync(o.host, o.buf.p, o.bytes, hipMemcpyDeviceToHost, E->stream));
     Y_TRY(hipStreamSynchronize(E->stream));
-    if (kernel_seconds) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        *kernel_seconds = ms * 1e-3;
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
+    ev.seconds(kernel_seconds);
     return EHM_OK;
 }
 
 }  // namespace
 
 extern "C" {
+
+int ehm_explicit_set_plant(ehm_explicit* E, int32_t n_modes, const double* A, const double* B,
+                           const double* w, int32_t n_d, const double* Emat,
+                           const int32_t* region_rows, const double* H, const double* h,
+                           int32_t n_g, const double* Gx, const double* gx,
+                           const int32_t* node_mode, int32_t cost_kind, const double* Q,
+                           const double* R) {
+    return install_plant(
+        E, "set_plant", n_modes, EHM_R_MAX_MODES, A, B, w, n_g, Gx, gx, node_mode, cost_kind, Q,
+        R, nullptr, [&](Pack& pk, DevPlant& pl, int p, int) {
+            if (n_d < 0 || n_d > EHM_R_MAX_D || (n_d > 0 && !Emat))
+                return xfail(EHM_E_INVALID, "set_plant: n_d = %d (0..%d, E needed if > 0)",
+                             (int)n_d, EHM_R_MAX_D);
+            int rows = 0;
+            for (int m = 0; m < n_modes; ++m) {
+                const int r = region_rows ? region_rows[m] : 0;
+                if (r < 0)
+                    return xfail(EHM_E_INVALID, "set_plant: mode %d has %d region rows", m, r);
+                pl.row0[m] = rows;
+                rows += r;
+            }
+            if (rows > EHM_R_MAX_ROWS || (rows > 0 && (!H || !h)))
+                return xfail(EHM_E_INVALID, "set_plant: %d mode-region rows (0..%d)", rows,
+                             EHM_R_MAX_ROWS);
+            for (int m = n_modes; m <= EHM_R_MAX_MODES; ++m) pl.row0[m] = rows;
+            pl.n_d = n_d;
+            pl.oE = pk.put(Emat, (size_t)p * n_d);
+            pl.oH = pk.put(H, (size_t)rows * p);
+            pl.oh = pk.put(h, (size_t)rows);
+            return (int)EHM_OK;
+        });
+}
+
+int ehm_explicit_set_plant_guarded(ehm_explicit* E, int32_t n_modes, const double* A,
+                                   const double* B, const double* w, int32_t substeps,
+                                   int32_t n_guards, const int32_t* guard_mode,
+                                   const int32_t* guard_row0, const double* ga, const double* gb,
+                                   const double* gc, const double* gt, const int32_t* strict,
+                                   int32_t default_mode, int32_t n_g, const double* Gx,
+                                   const double* gx, const int32_t* node_mode, int32_t cost_kind,
+                                   const double* Q, const double* R) {
+    DevGuard gd{};
+    return install_plant(
+        E, "set_plant_guarded", n_modes, EHM_G_MAX_MODES, A, B, w, n_g, Gx, gx, node_mode,
+        cost_kind, Q, R, &gd, [&](Pack& pk, DevPlant&, int p, int n_u) {
+            if ((n_guards > 0 && !guard_mode) || !guard_row0)
+                return xfail(EHM_E_INVALID, "set_plant_guarded: a required array is NULL");
+            if (substeps < 1 || substeps > EHM_G_MAX_SUB)
+                return xfail(EHM_E_INVALID, "set_plant_guarded: %d substeps (1..%d)",
+                             (int)substeps, EHM_G_MAX_SUB);
+            if (n_guards < 0 || n_guards > EHM_G_MAX_ROWS)
+                return xfail(EHM_E_INVALID, "set_plant_guarded: %d guards (0..%d)", (int)n_guards,
+                             EHM_G_MAX_ROWS);
+            if (default_mode < 0 || default_mode >= n_modes)
+                return xfail(EHM_E_INVALID, "set_plant_guarded: default mode %d of %d",
+                             (int)default_mode, (int)n_modes);
+            if (guard_row0[0] != 0)
+                return xfail(EHM_E_INVALID, "set_plant_guarded: the rows of guard 0 start at %d",
+                             (int)guard_row0[0]);
+            gd.substeps = substeps;
+            gd.n_guards = n_guards;
+            gd.default_mode = default_mode;
+            for (int g = 0; g <= n_guards; ++g) {
+                if (g < n_guards) {
+                    if (guard_mode[g] < 0 || guard_mode[g] >= n_modes)
+                        return xfail(EHM_E_INVALID,
+                                     "set_plant_guarded: guard %d selects mode %d of %d", g,
+                                     (int)guard_mode[g], (int)n_modes);
+                    if (guard_row0[g + 1] <= guard_row0[g])
+                        return xfail(EHM_E_INVALID, "set_plant_guarded: guard %d has no rows", g);
+                    gd.mode[g] = guard_mode[g];
+                }
+                gd.row0[g] = guard_row0[g];
+            }
+            const int rows = guard_row0[n_guards];
+            if (rows > EHM_G_MAX_ROWS || (rows > 0 && (!ga || !gb || !gc || !gt || !strict)))
+                return xfail(EHM_E_INVALID, "set_plant_guarded: %d guard rows (0..%d)", rows,
+                             EHM_G_MAX_ROWS);
+            for (int r = 0; r < rows; ++r) gd.strict[r] = strict[r] != 0;
+            gd.oGa = pk.put(ga, (size_t)rows * p);
+            gd.oGb = pk.put(gb, (size_t)rows * n_u);
+            gd.oGc = pk.put(gc, (size_t)rows);
+            gd.oGt = pk.put(gt, (size_t)rows);
+            return (int)EHM_OK;
+        });
+}
 
 int ehm_explicit_rollout(ehm_explicit* E, int64_t n, int32_t T, const double* x0,
                          const double* d, const double* v, double tol_exit, double* x_traj,
@@ -1350,16 +1299,11 @@ int ehm_explicit_set_noise(ehm_explicit* E, int32_t n_terms, const int32_t* desc
                      E->pl.total + n_data, EHM_N_MAX_LDS);
     hipError_t e = hipSetDevice(E->device);
     if (e != hipSuccess) return xfail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
-    void* d_noise = nullptr;
-    if (hipMalloc(&d_noise, (size_t)(n_data ? n_data : 1) * sizeof(double)) != hipSuccess ||
-        (n_data > 0 && hipMemcpy(d_noise, data, (size_t)n_data * sizeof(double),
-                                 hipMemcpyHostToDevice) != hipSuccess)) {
-        if (d_noise) (void)hipFree(d_noise);
+    DevBuf d_noise;
+    if (d_noise.upload(data, (size_t)n_data * sizeof(double)) != hipSuccess)
         return xfail(EHM_E_HIP, "set_noise: device allocation / copy failed");
-    }
-    if (E->noise) (void)hipFree(E->noise);
-    E->noise = d_noise;
-    nz.data = (const double*)d_noise;
+    E->noise = std::move(d_noise);
+    nz.data = E->noise.as<const double>();
     E->nz = nz;
     E->noise_n_d = n_d;
     return EHM_OK;
@@ -1389,22 +1333,15 @@ int ehm_philox_batch(int64_t n, const uint64_t* counters, const uint64_t* key, u
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return xfail(EHM_E_NO_DEVICE, "philox_batch: %s", hipGetErrorString(e));
-    uint64_t *dc = nullptr, *dout = nullptr;
     const size_t bytes = (size_t)n * 4 * sizeof(uint64_t);
-    struct Free {
-        uint64_t **a, **b;
-        ~Free() {
-            if (*a) (void)hipFree(*a);
-            if (*b) (void)hipFree(*b);
-        }
-    } fr{&dc, &dout};
-    Y_TRY(hipMalloc(&dc, bytes));
-    Y_TRY(hipMalloc(&dout, bytes));
-    Y_TRY(hipMemcpy(dc, counters, bytes, hipMemcpyHostToDevice));
+    DevBuf dc, dout;
+    Y_TRY(dc.upload(counters, bytes));
+    Y_TRY(dout.alloc(bytes));
     hipLaunchKernelGGL(k_philox_batch, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0,
-                       (long long)n, (const uint64_t*)dc, key[0], key[1], dout);
+                       (long long)n, dc.as<const uint64_t>(), key[0], key[1],
+                       dout.as<uint64_t>());
     Y_TRY(hipGetLastError());
-    Y_TRY(hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost));
+    Y_TRY(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
     return EHM_OK;
 }
 

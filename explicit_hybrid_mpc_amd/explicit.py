@@ -130,10 +130,13 @@ class ImplicitMPC:
 class ExplicitMPC:
     """GPU counterpart of lib/mpc_library.py:662-792 (same constructor and call signature)."""
 
+    # class defaults: rollout checks its arguments before it touches anything else
+    mpc = None
+    _rollout_plant = None       # the plant the device holds (set_plant)
+
     def __init__(self, tree, oracle=None, device=0):
         mpc = getattr(oracle, 'mpc', None)
         self.mpc = mpc
-        self._rollout_plant = None
         self.plant = getattr(mpc, 'plant', None)
         self.T_s = getattr(mpc, 'T_s', None)
         if hasattr(mpc, 'specs'):
@@ -191,7 +194,7 @@ class ExplicitMPC:
     def node_modes(self, plant):
         """int32 [n_nodes]: step-0 mode of every node's commutation (-1: none); all 0 for a
         single-mode plant."""
-        if plant.n_modes == 1 and not hasattr(plant, 'guards'):
+        if plant.n_modes == 1 and not plant.guarded:
             return np.zeros(self.n_nodes, dtype=np.int32)
         if self.mpc is None or not hasattr(self.mpc, 'step0_mode'):
             raise ValueError('the step-0 modes of a hybrid law need the oracle (its mpc)')
@@ -209,32 +212,22 @@ class ExplicitMPC:
             raise ValueError('plant (n_x %d, n_u %d) does not fit the law (p %d, n_u %d)' % (
                 plant.n_x, plant.n_u, self.p, self.n_u))
         self._node_mode = self.node_modes(plant)
-        if hasattr(plant, 'guards'):
-            return self._set_plant_guarded(plant)
-        rows, H, h = plant.region_arrays()
-        keep = [f64(plant.A), f64(plant.B), f64(plant.w), f64(plant.E), rows, f64(H), f64(h),
-                f64(plant.Gx), f64(plant.gx), self._node_mode, f64(plant.Q), f64(plant.R)]
-        A, B, w, E, rows, H, h, Gx, gx, nm, Q, R = keep
-        _check(self._lib.ehm_explicit_set_plant(
-            self._handle, plant.n_modes, ptr(A), ptr(B), ptr(w), plant.n_d,
-            ptr(E) if plant.n_d else None, ptr(rows), ptr(H) if H.size else None,
-            ptr(h) if h.size else None, plant.gx.size, ptr(Gx) if Gx.size else None,
-            ptr(gx) if gx.size else None, ptr(nm), 0 if plant.cost == 'inf' else 1, ptr(Q),
-            ptr(R)))
-        self._rollout_plant = plant
-
-    def _set_plant_guarded(self, plant):
-        """A ``simulate.GuardedPlant`` to the device (ehm_explicit_set_plant_guarded)."""
-        gm, row0, ga, gb, gc, gt, st = plant.guard_arrays()
-        keep = [f64(plant.A), f64(plant.B), f64(plant.w), f64(plant.Gx), f64(plant.gx),
-                f64(plant.Q), f64(plant.R), f64(ga), f64(gb), f64(gc), f64(gt)]
-        A, B, w, Gx, gx, Q, R, ga, gb, gc, gt = keep
         opt = lambda a: ptr(a) if a.size else None
-        _check(self._lib.ehm_explicit_set_plant_guarded(
-            self._handle, plant.n_modes, ptr(A), ptr(B), ptr(w), plant.substeps, len(gm), opt(gm),
-            ptr(row0), opt(ga), opt(gb), opt(gc), opt(gt), opt(st), plant.default_mode,
-            plant.gx.size, opt(Gx), opt(gx), ptr(self._node_mode),
-            0 if plant.cost == 'inf' else 1, ptr(Q), ptr(R)))
+        A, B, w, Gx, gx, Q, R = (f64(a) for a in (plant.A, plant.B, plant.w, plant.Gx, plant.gx,
+                                                  plant.Q, plant.R))
+        if plant.guarded:
+            gm, row0, ga, gb, gc, gt, st = plant.guard_arrays()
+            ga, gb, gc, gt = f64(ga), f64(gb), f64(gc), f64(gt)
+            fn = self._lib.ehm_explicit_set_plant_guarded
+            own = (plant.substeps, len(gm), opt(gm), ptr(row0), opt(ga), opt(gb), opt(gc), opt(gt),
+                   opt(st), plant.default_mode)
+        else:
+            rows, H, h = plant.region_arrays()
+            E, H, h = f64(plant.E), f64(H), f64(h)
+            fn = self._lib.ehm_explicit_set_plant
+            own = (plant.n_d, opt(E), ptr(rows), opt(H), opt(h))
+        _check(fn(self._handle, plant.n_modes, ptr(A), ptr(B), ptr(w), *own, plant.gx.size, opt(Gx),
+                  opt(gx), ptr(self._node_mode), 0 if plant.cost == 'inf' else 1, ptr(Q), ptr(R)))
         self._rollout_plant = plant
 
     def set_noise(self, model, plant):
@@ -270,60 +263,44 @@ class ExplicitMPC:
         under noise, recorded with ``record``).
         """
         from . import simulate
-        if noise is not None and (d is not None or v is not None):
-            raise ValueError('noise draws d and v itself: give noise or d / v, not both')
-        if plant is None:
-            plant = self._rollout_plant
-            if plant is None:
-                if self.mpc is None:
-                    raise ValueError('rollout needs a plant (or an oracle whose mpc gives one)')
-                plant = simulate.Plant.from_mpc(self.mpc)
-        guarded = hasattr(plant, 'guards')
-        if guarded and noise is not None:
-            raise ValueError('noise is not supported with a guarded plant')
-        if plant is not self._rollout_plant:
-            self.set_plant(plant)
         X0 = f64(np.atleast_2d(X0))
         n, p = X0.shape
         T = int(T)
+        if plant is None:
+            plant = self._rollout_plant
+        if plant is None and self.mpc is not None:
+            plant = simulate.Plant.from_mpc(self.mpc)
+        d, v = simulate._check_rollout_args(plant, noise, d, v, n, p, T)
         if p != self.p or T < 0:
             raise ValueError('X0 must be [n, %d] and T >= 0' % self.p)
-        d = simulate._as_batch(d, (T, n, plant.n_d), 'd')
-        v = simulate._as_batch(v, (T, n, p), 'v')
+        if plant is not self._rollout_plant:
+            self.set_plant(plant)
         if noise is not None:
             self.set_noise(noise, plant)
+        rec = lambda shape, dtype=np.float64: np.empty(shape, dtype) if record else None
+        xs, us, leaf = rec((T + 1, n, p)), rec((T, n, self.n_u)), rec((T, n), np.int32)
         x_final = np.empty((n, p))
         steps = np.empty(n, dtype=np.int32)
         status = np.empty(n, dtype=np.int32)
         cost, unorm, maxv = np.empty(n), np.empty(n), np.empty(n)
-        xs = np.empty((T + 1, n, p)) if record else None
-        us = np.empty((T, n, self.n_u)) if record else None
-        leaf = np.empty((T, n), dtype=np.int32) if record else None
         secs = ctypes.c_double(0.)
         if noise is None:
-            _check(self._lib.ehm_explicit_rollout(
-                self._handle, n, T, ptr(X0), None if d is None else ptr(d),
-                None if v is None else ptr(v), float(tol_exit), None if xs is None else ptr(xs),
-                None if us is None else ptr(us), None if leaf is None else ptr(leaf),
-                ptr(x_final), ptr(steps), ptr(status), ptr(cost), ptr(unorm), ptr(maxv),
-                ctypes.addressof(secs)))
+            vs = es = ws = None
+            fn = self._lib.ehm_explicit_rollout
+            head = (ptr(d), ptr(v), float(tol_exit), ptr(xs), ptr(us), ptr(leaf))
         else:
-            vs = np.empty((T, n, p)) if record else None
-            es = np.empty((T, n, self.n_u)) if record else None
-            ws = np.empty((T, n, plant.n_d)) if record else None
-            opt = [None if a is None else ptr(a) for a in (xs, us, leaf, vs, es, ws)]
-            _check(self._lib.ehm_explicit_rollout_noisy(
-                self._handle, n, T, ptr(X0), int(seed), int(traj0), float(tol_exit), *opt,
-                ptr(x_final), ptr(steps), ptr(status), ptr(cost), ptr(unorm), ptr(maxv),
-                ctypes.addressof(secs)))
+            vs, es, ws = rec((T, n, p)), rec((T, n, self.n_u)), rec((T, n, plant.n_d))
+            fn = self._lib.ehm_explicit_rollout_noisy
+            head = (int(seed), int(traj0), float(tol_exit), ptr(xs), ptr(us), ptr(leaf), ptr(vs),
+                    ptr(es), ptr(ws))
+        _check(fn(self._handle, n, T, ptr(X0), *head, ptr(x_final), ptr(steps), ptr(status),
+                  ptr(cost), ptr(unorm), ptr(maxv), ctypes.addressof(secs)))
         out = simulate.ClosedLoop(x_final=x_final, steps=steps, status=status, cost=cost,
-                                  u_norm_sum=unorm, max_violation=maxv, seconds=secs.value)
-        if noise is not None and record:
-            out.v, out.e, out.w = vs, es, ws
+                                  u_norm_sum=unorm, max_violation=maxv, seconds=secs.value,
+                                  x=xs, u=us, leaf=leaf, v=vs, e=es, w=ws)
         if record:
-            out.x, out.u, out.leaf = xs, us, leaf
             live = leaf >= 0
-            if not guarded:
+            if not plant.guarded:
                 out.mode = np.where(live, self._node_mode[np.maximum(leaf, 0)],
                                     -1).astype(np.int32)
             if isinstance(self.tree, FlatTree):

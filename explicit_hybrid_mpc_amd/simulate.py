@@ -34,29 +34,40 @@ import numpy as np
 STATUS_OK, STATUS_EXIT, STATUS_MODE, STATUS_NO_LAW = 0, 1, 2, 3
 
 
-class Plant:
-    """
-    Plant of a law with the controller's period: x+ = A[m] x + B[m] u + w[m] + E d, mode m
-    admissible where H_m x <= h_m (``regions[m]``, None = everywhere); Gx x <= gx the state
-    constraints; stage cost ||Q x||_inf + ||R u||_inf (cost 'inf') or x'Qx + u'Ru ('quadratic').
-    """
+class _PlantBase:
+    """What both kinds of plant hold: modes A [m, n_x, n_x], B [m, n_x, n_u], w [m, n_x], the
+    disturbance map E [n_x, n_d], the state rows Gx x <= gx (taken at controller steps) and the
+    stage cost ||Q x||_inf + ||R u||_inf (cost 'inf') or x'Qx + u'Ru ('quadratic').  ``guarded``
+    tells the kinds apart."""
 
-    def __init__(self, A, B, w, E, regions, Gx, gx, Q, R, cost, T_s=None):
+    guarded = False
+
+    def __init__(self, A, B, w, E, Gx, gx, Q, R, cost, T_s):
         self.A = np.ascontiguousarray(A, dtype=np.float64)
         self.B = np.ascontiguousarray(B, dtype=np.float64)
         self.w = np.ascontiguousarray(w, dtype=np.float64)
         self.n_modes, self.n_x, self.n_u = self.B.shape
         self.E = np.zeros((self.n_x, 0)) if E is None else np.ascontiguousarray(E, dtype=np.float64)
         self.n_d = self.E.shape[1]
-        self.regions = list(regions)
-        self.Gx = np.ascontiguousarray(Gx, dtype=np.float64)
-        self.gx = np.ascontiguousarray(gx, dtype=np.float64)
+        self.Gx = np.zeros((0, self.n_x)) if Gx is None else np.ascontiguousarray(Gx, np.float64)
+        self.gx = np.zeros(0) if gx is None else np.ascontiguousarray(gx, np.float64)
         self.Q = np.ascontiguousarray(Q, dtype=np.float64)
         self.R = np.ascontiguousarray(R, dtype=np.float64)
         if cost not in ('inf', 'quadratic'):
             raise ValueError("cost must be 'inf' or 'quadratic'")
         self.cost = cost
         self.T_s = T_s
+
+
+class Plant(_PlantBase):
+    """
+    Plant of a law with the controller's period: x+ = A[m] x + B[m] u + w[m] + E d, mode m
+    admissible where H_m x <= h_m (``regions[m]``, None = everywhere).
+    """
+
+    def __init__(self, A, B, w, E, regions, Gx, gx, Q, R, cost, T_s=None):
+        super().__init__(A, B, w, E, Gx, gx, Q, R, cost, T_s)
+        self.regions = list(regions)
 
     @classmethod
     def from_mpc(cls, mpc):
@@ -123,7 +134,7 @@ def _dot_rows(M, X):
     return out
 
 
-class GuardedPlant:
+class GuardedPlant(_PlantBase):
     """
     A multi-rate piecewise-affine plant that picks its own mode (lib/simulator.py:124-188 with a
     plant such as lib/mpc_library.py:588-626): modes x+ = A[m] x + B[m] u + w[m] at the plant
@@ -140,12 +151,11 @@ class GuardedPlant:
     order from 0.0, no FMA.
     """
 
+    guarded = True
+
     def __init__(self, A, B, w, substeps, guards, default_mode, Q, R, cost='quadratic', Gx=None,
                  gx=None, T_s=None, T_s_plant=None):
-        self.A = np.ascontiguousarray(A, dtype=np.float64)
-        self.B = np.ascontiguousarray(B, dtype=np.float64)
-        self.w = np.ascontiguousarray(w, dtype=np.float64)
-        self.n_modes, self.n_x, self.n_u = self.B.shape
+        super().__init__(A, B, w, None, Gx, gx, Q, R, cost, T_s)
         if int(substeps) != substeps or substeps < 1:
             raise ValueError('substeps must be a positive integer')
         self.substeps = int(substeps)
@@ -160,16 +170,7 @@ class GuardedPlant:
                                             for a, b, c, t, st in rows]))
         if not 0 <= self.default_mode < self.n_modes:
             raise ValueError('the default mode is not a mode of the plant')
-        self.E = np.zeros((self.n_x, 0))
-        self.n_d = 0
-        self.Gx = np.zeros((0, self.n_x)) if Gx is None else np.ascontiguousarray(Gx, np.float64)
-        self.gx = np.zeros(0) if gx is None else np.ascontiguousarray(gx, np.float64)
-        self.Q = np.ascontiguousarray(Q, dtype=np.float64)
-        self.R = np.ascontiguousarray(R, dtype=np.float64)
-        if cost not in ('inf', 'quadratic'):
-            raise ValueError("cost must be 'inf' or 'quadratic'")
-        self.cost = cost
-        self.T_s, self.T_s_plant = T_s, T_s_plant
+        self.T_s_plant = T_s_plant
 
     @classmethod
     def pendulum(cls, mpc):
@@ -311,13 +312,23 @@ class ClosedLoop:
         return self.status == STATUS_MODE
 
 
-def _as_batch(a, shape, name):
-    if a is None:
-        return None
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    if a.shape != shape:
-        raise ValueError('%s must have shape %s, not %s' % (name, shape, a.shape))
-    return a
+def _check_rollout_args(plant, noise, d, v, n, p, T):
+    """The refusals every rollout shares, before any use of the device.  Returns d [T, n, n_d] and
+    v [T, n, p] as contiguous float64 arrays (or None)."""
+    if noise is not None and (d is not None or v is not None):
+        raise ValueError('noise draws d and v itself: give noise or d / v, not both')
+    if plant is None:
+        raise ValueError('rollout needs a plant (or an oracle whose mpc gives one)')
+    if plant.guarded and noise is not None:
+        raise ValueError('noise is not supported with a guarded plant')
+    out = []
+    for a, shape, name in ((d, (T, n, plant.n_d), 'd'), (v, (T, n, p), 'v')):
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape != shape:
+                raise ValueError('%s must have shape %s, not %s' % (name, shape, a.shape))
+        out.append(a)
+    return out
 
 
 def rollout_implicit(oracle, plant, X0, T, d=None, v=None, record=True, tol_exit=1e-9, noise=None,
@@ -330,13 +341,7 @@ def rollout_implicit(oracle, plant, X0, T, d=None, v=None, record=True, tol_exit
     """
     X0 = np.ascontiguousarray(np.atleast_2d(X0), dtype=np.float64)
     n, p = X0.shape
-    guarded = isinstance(plant, GuardedPlant)
-    if guarded and noise is not None:
-        raise ValueError('noise is not supported with a guarded plant')
-    if noise is not None and (d is not None or v is not None):
-        raise ValueError('noise draws d and v itself: give noise or d / v, not both')
-    d = _as_batch(d, (T, n, plant.n_d), 'd')
-    v = _as_batch(v, (T, n, p), 'v')
+    d, v = _check_rollout_args(plant, noise, d, v, n, p, T)
     if noise is not None and (noise.n_x, noise.n_u, noise.n_d) != (p, plant.n_u, plant.n_d):
         raise ValueError('the noise model does not fit the plant')
     ids = np.uint64(int(traj0)) + np.arange(n, dtype=np.uint64)
@@ -406,7 +411,7 @@ def rollout_implicit(oracle, plant, X0, T, d=None, v=None, record=True, tol_exit
     out = ClosedLoop(x_final=x, steps=steps, status=status, cost=cost, u_norm_sum=unorm,
                      max_violation=maxv, seconds=time.time() - tic)
     if record:
-        out.x, out.u, out.commutation, out.mode = xs, us, cs, (None if guarded else ms)
+        out.x, out.u, out.commutation, out.mode = xs, us, cs, (None if plant.guarded else ms)
         if noise is not None:
             out.v, out.e, out.w = vs, es, ws
     return out
@@ -489,12 +494,11 @@ class Simulator:
         plant = getattr(self.law, '_rollout_plant', None)
         if plant is None and getattr(self.law, 'mpc', None) is not None:
             plant = Plant.from_mpc(self.law.mpc)
-        return plant if isinstance(plant, GuardedPlant) else None
+        return plant if plant is not None and plant.guarded else None
 
     def _run_guarded(self, plant, x_0, out):
-        if self.noise is not None:
-            raise ValueError('noise is not supported with a guarded plant')
         calls, times = reference_call_steps(self.T_f, plant.T_s_plant, plant.T_s)
+        _check_rollout_args(plant, self.noise, None, None, 1, plant.n_x, len(calls))
         S = plant.substeps
         if not np.array_equal(calls, np.arange(0, len(times), S)):
             raise ValueError('for T = %r the reference calls the controller at plant steps %s, not '
