@@ -21,6 +21,8 @@ EHM_E_HIP = -3
 EHM_E_CAPACITY = -4
 EHM_E_INFEASIBLE = -5
 EHM_E_NUMERIC = -6
+# ehm_tree_persist_kernel families, by their EHM_PERSIST_* value (include/ehmpc.h)
+PERSIST_FAMILIES = ('none', 'k2', 'kp', 'kpm', 'k4')
 EHM_MAX_P = 8           # include/ehmpc.h
 
 # every symbol include/ehmpc.h declares
@@ -37,7 +39,7 @@ EXPORTED = [
     'ehm_explicit_last_error', 'ehm_partition_progress', 'ehm_partition_counts', 'ehm_partition_advance', 'ehm_problem_set_quadratic',
     'ehm_feas_all_batch', 'ehm_lcss_batch', 'ehm_partition_movable',
     'ehm_problem_update_blocks', 'ehm_simplex_idx_batch', 'ehm_point_idx_batch',
-    'ehm_abi_sizes', 'ehm_solver_phase_ticks', 'ehm_problem_layout',
+    'ehm_abi_sizes', 'ehm_solver_phase_ticks', 'ehm_problem_layout', 'ehm_tree_persist_kernel',
     'ehm_host_alloc', 'ehm_host_free', 'ehm_explicit_set_plant', 'ehm_explicit_rollout',
     'ehm_explicit_set_noise', 'ehm_explicit_rollout_noisy', 'ehm_philox_batch',
     'ehm_explicit_set_plant_guarded',
@@ -266,6 +268,7 @@ def load(build_if_missing=True):
     lib.ehm_stats.argtypes = [vp, ctypes.POINTER(Counters)]
     lib.ehm_solver_phase_ticks.argtypes = [vp, vp]
     lib.ehm_problem_layout.argtypes = [vp, vp]
+    lib.ehm_tree_persist_kernel.argtypes = [vp, vp]
     for name in EXPORTED:
         fn = getattr(lib, name)
         if name not in ('ehm_last_error', 'ehm_version', 'ehm_stream',

@@ -550,6 +550,7 @@ struct ehm_tree {
     DevBuf rec, left, didx, depth, flags, tstar, grad, code, wit, mt_state, mt_data;
     ehm_tree_info info{};
     int skip_volume = 0;
+    int32_t persist_kernel[4] = {0, 0, 0, 0};   // the last persistent launch (ehm_tree_persist_kernel)
     // persistent engine: node ids follow the allocation order; the export relabels them to the
     // breadth-first order of the level-synchronous engine (perm[new id] = device id)
     bool unordered = false;
@@ -662,8 +663,10 @@ struct K2Cfg {
 };
 
 // kind_a / kind_b: the LP kinds the launch may assemble (workspace sized for the larger)
+// no_fits: leave out the families with a K2Api::fits check (ehm_k4.hip) -- its persistent kernel
+// ignores PersistDeal, so dealt, budgeted and witness-checking launches take the next instance
 static int k2_config(ehm_problem* P, int kind_a, int kind_b, long long n_items, K2Cfg& cfg,
-                     bool persist = false) {
+                     bool persist = false, bool no_fits = false) {
     int n_lp, ne, n_lp2, ne2;
     kind_dims(P->dp, kind_a, n_lp, ne);
     kind_dims(P->dp, kind_b, n_lp2, ne2);
@@ -671,7 +674,8 @@ static int k2_config(ehm_problem* P, int kind_a, int kind_b, long long n_items, 
     n_lp = std::max(n_lp, n_lp2);
     ne = std::max(ne, ne2);
     // (the instances are sized by the FACTORISED columns: ehm_ipm2.h eliminates [nd0, n))
-    const K2Api* api = k2_pick(n_lp - (P->dp.n - P->dp.nd0), slots, P->quadratic, &P->dp);
+    const K2Api* api = k2_pick(n_lp - (P->dp.n - P->dp.nd0), slots, P->quadratic,
+                               no_fits ? nullptr : &P->dp);
     if (!api)
         return fail(EHM_E_INVALID, "no kernel instance for an LP with %d columns, %d row slots",
                     n_lp, slots);
@@ -2272,6 +2276,12 @@ int ehm_problem_layout(ehm_problem* P, int32_t out[4]) {
     return EHM_OK;
 }
 
+int ehm_tree_persist_kernel(const ehm_tree* T, int32_t out[4]) {
+    if (!T || !out) return fail(EHM_E_INVALID, "null argument");
+    for (int k = 0; k < 4; ++k) out[k] = T->persist_kernel[k];
+    return EHM_OK;
+}
+
 int ehm_solver_phase_ticks(ehm_problem* P, int64_t out[24]) {
     if (!P || !out) return fail(EHM_E_INVALID, "null argument");
     HIP_TRY(hipSetDevice(P->device), EHM_E_HIP);
@@ -2632,11 +2642,18 @@ static int persistent_run(ehm_tree* T, long long max_pops = 0) {
     ehm_problem* P = T->prob;
     auto& R = T->run;
     K2Cfg cfg;
-    int rc = k2_config(P, LP_SLACK, LP_POINT, 1LL << 40, cfg, true);   // the full persistent grid
+    // one launch from the roots, dealt over the ranks at a tree depth (PersistDeal)
+    const bool dealt = R.deal_depth > 0 && R.shard_world > 1 && R.sweeps == 0;
+    // ehm_k4.hip's persistent kernel grows everything its queue holds to completion: it ignores
+    // PersistDeal (the deal, the pop budget, the witness cross-check), so such launches take the
+    // single-width kernel of the same size instead
+    const bool no_k4 = dealt || max_pops > 0 || P->check_witness;
+    int rc = k2_config(P, LP_SLACK, LP_POINT, 1LL << 40, cfg, true, no_k4);   // the full grid
     if (rc) return rc;
     if (!cfg.api->persist) return fail(EHM_E_INVALID, "no persistent kernel for this LP size");
     // two solver widths where a pair is compiled: the midpoint LPs have p + 1 columns less
     const KpApi* kp = nullptr;
+    bool kp_mid = false;
     if (!P->quadratic && !getenv("EHM_NO_KP")) {
         int n_d, ne_d, n_e, ne_e;
         kind_dims(P->dp, LP_SLACK, n_d, ne_d);
@@ -2653,8 +2670,10 @@ static int persistent_run(ehm_tree* T, long long max_pops = 0) {
             if (P->mid_first && !P->decide_full)
                 for (kp_getter g : g_kpm_getters) {
                     const KpApi* a = g();
-                    if (a->np_decide == ad->np && a->np_expand == ae->np && a->slots == slots)
+                    if (a->np_decide == ad->np && a->np_expand == ae->np && a->slots == slots) {
                         kp = a;
+                        kp_mid = true;
+                    }
                 }
         }
         if (kp) {
@@ -2709,8 +2728,7 @@ static int persistent_run(ehm_tree* T, long long max_pops = 0) {
     PersistDeal deal{0, 0, 0, 1, 0, 0};
     deal.check = P->check_witness ? 1 : 0;
     T->dt.code = nullptr;
-    if (R.deal_depth > 0 && R.shard_world > 1 && R.sweeps == 0) {
-        // one launch from the roots, dealt over the ranks at a tree depth (PersistDeal)
+    if (dealt) {
         deal = PersistDeal{0, R.deal_depth, R.shard_rank, R.shard_world,
                            getenv("EHM_DEAL_LOW_BITS") ? 0 : 1, 0, P->check_witness ? 1 : 0};
         if ((rc = T->code.ensure((size_t)T->cap * 4))) return rc;
@@ -2741,6 +2759,17 @@ static int persistent_run(ehm_tree* T, long long max_pops = 0) {
     (void)hipEventCreate(&e0);
     (void)hipEventCreate(&e1);
     (void)hipEventRecord(e0, P->stream);
+    if (kp) {
+        T->persist_kernel[0] = kp_mid ? EHM_PERSIST_KPM : EHM_PERSIST_KP;
+        T->persist_kernel[1] = kp->np_decide;
+        T->persist_kernel[2] = kp->np_expand;
+        T->persist_kernel[3] = kp->slots;
+    } else {
+        T->persist_kernel[0] = cfg.api == ehm_k4_api() ? EHM_PERSIST_K4 : EHM_PERSIST_K2;
+        T->persist_kernel[1] = cfg.api->np;
+        T->persist_kernel[2] = cfg.api->np;
+        T->persist_kernel[3] = cfg.api->slots;
+    }
     (kp ? kp->persist : cfg.api->persist)(cfg.L, P->dp, T->dt, slots, (int)n_slots,
                                           P->pq_ctl.as<PersistCtl>(), (int)T->limit, P->d_cnt,
                                           P->decide_full ? 0 : 1, R.max_depth, deal);
@@ -2837,7 +2866,9 @@ int ehm_partition_step(ehm_tree* T, int32_t max_sweeps, int64_t* frontier_size) 
             return (e && atoi(e) == 0) ? 1 : 0;
         }();
         K2Cfg pc;
-        wide_persist = !off && k2_config(P, LP_SLACK, LP_POINT, 1LL << 40, pc, true) == EHM_OK &&
+        wide_persist = !off &&
+                       k2_config(P, LP_SLACK, LP_POINT, 1LL << 40, pc, true, P->check_witness) ==
+                           EHM_OK &&
                        pc.api->persist != nullptr;
     }
     const bool want_persist = R.engine == 1 && P->solver_gen == 2 && max_sweeps <= 0 &&

@@ -65,6 +65,13 @@ def _info_dict(info):
     return out
 
 
+def _persist_kernel(lib, tree):
+    """ehm_tree_persist_kernel as (family, decide width, expand width, row slots)."""
+    out = (ctypes.c_int32 * 4)()
+    check(lib.ehm_tree_persist_kernel(tree, ctypes.addressof(out)))
+    return (_capi.PERSIST_FAMILIES[out[0]], int(out[1]), int(out[2]), int(out[3]))
+
+
 class FlatTree:
     """
     Flat export of a grown partition (struct of arrays, node k):
@@ -408,6 +415,7 @@ class GpuProblem:
             info = _capi.TreeInfo()
             check(self._lib.ehm_tree_info_get(tree, ctypes.byref(info)))
             info_d = _info_dict(info)
+            info_d['persist_kernel'] = _persist_kernel(self._lib, tree)
             if not export:
                 return info_d
             K = info.n_nodes
@@ -599,6 +607,7 @@ class PartitionRun:
             info = _capi.TreeInfo()
             check(self._lib.ehm_tree_info_get(self._tree, ctypes.byref(info)))
             info_d = _info_dict(info)
+            info_d['persist_kernel'] = _persist_kernel(self._lib, self._tree)
             if not export:
                 return info_d
             K = info.n_nodes

@@ -599,6 +599,20 @@ int ehm_solver_phase_ticks(ehm_problem* prob, int64_t out[24]);
  * the executed flops with it); no reference counterpart. */
 int ehm_problem_layout(ehm_problem* prob, int32_t out[4]);
 
+/* The persistent frontier kernel the last persistent launch of this tree ran: out = { family,
+ * decide width, expand width, row slots } (widths in factorised columns; the single-width
+ * families report theirs twice).  family: EHM_PERSIST_NONE (the run only swept), _K2 (the
+ * single-width kernel of ehm_k2.hip), _KP / _KPM (the two-width pair, suboptimality test or
+ * midpoint solve first), _K4 (the LDS-resident wide family, ehm_k4.hip: single-rank runs to
+ * completion only -- dealt, budgeted and witness-checking launches take the single-width kernel
+ * of the same size instead).  Reporting only; no reference counterpart. */
+#define EHM_PERSIST_NONE 0
+#define EHM_PERSIST_K2   1
+#define EHM_PERSIST_KP   2
+#define EHM_PERSIST_KPM  3
+#define EHM_PERSIST_K4   4
+int ehm_tree_persist_kernel(const ehm_tree* tree, int32_t out[4]);
+
 /* Device self test of the wave-level primitives (DPP reductions, reciprocal) of every
  * compiled kernel instance: out[5*k .. 5*k+4] for instance k, expected
  * {1072, 99, 25, 1/3, -1}.  Test hook, not part of the reference's surface. */

@@ -538,3 +538,16 @@ def test_lexicographic_stage_problems_and_the_oracles_rule():
                       bounds=(None, None), method='highs')
         assert res.status == 0 and res.fun <= J + 2e-7 * (1. + abs(J))
     assert wider >= 2           # the optimal face of the double integrator is wide at some
+
+
+def test_persistent_width_rows_carry_their_calibrated_scales():
+    """Every row of the persistent-kernel table (tests/test_gpu_persistent_widths.py) records
+    0.9 x its largest all-vertices-feasible box, recomputed here with the CPU oracle; the
+    instance names carry n_random, so only rows of one problem share a THETA_SCALE entry."""
+    names = set()
+    for row in helpers.PERSISTENT_WIDTH_ROWS:
+        assert helpers.persistent_width_scale(row) == row[9], row
+        mpc = helpers.persistent_width_instance(row)
+        assert examples.THETA_SCALE[mpc.name] == row[9]
+        names.add(mpc.name)
+    assert len(names) == len({row[4:8] for row in helpers.PERSISTENT_WIDTH_ROWS})
