@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/ehmpc.h"
+#include "ehm_host.h"
 #include "ehm_philox.h"
 
 #define EHM_XP 8   // max parameter dimension (EHM_MAX_P)
@@ -786,59 +787,6 @@ int xfail(int code, const char* fmt, ...) {
             return xfail(EHM_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
     } while (0)
 
-// One device allocation, freed when its owner goes; moved, never copied.
-struct DevBuf {
-    void* p = nullptr;
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
-    DevBuf& operator=(DevBuf&& o) noexcept {
-        std::swap(p, o.p);
-        return *this;
-    }
-    ~DevBuf() { reset(); }
-    explicit operator bool() const { return p != nullptr; }
-    template <class T> T* as() const { return (T*)p; }
-    void reset() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    // a new buffer of `bytes` (at least 1) in place of the held one
-    hipError_t alloc(size_t bytes) {
-        reset();
-        const hipError_t e = hipMalloc(&p, bytes ? bytes : 1);
-        if (e != hipSuccess) p = nullptr;
-        return e;
-    }
-    // the same, holding a copy of `bytes` of host memory
-    hipError_t upload(const void* src, size_t bytes) {
-        const hipError_t e = alloc(bytes);
-        return (e != hipSuccess || !bytes) ? e : hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
-    }
-};
-
-// The two events that time a launch, destroyed on every return.
-struct EventPair {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    EventPair() {
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
-    }
-    EventPair(const EventPair&) = delete;
-    EventPair& operator=(const EventPair&) = delete;
-    ~EventPair() {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-    }
-    void seconds(double* out) const {
-        if (!out) return;
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        *out = ms * 1e-3;
-    }
-};
-
 // The doubles of a plant, one array after the other; put gives the array's offset (NULL: zeros).
 struct Pack {
     std::vector<double> buf;
@@ -866,7 +814,7 @@ struct ehm_explicit {
     DevNoise nz{};
     int noise_n_d = 0;
     size_t cap = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;
 };
 
 extern "C" {
@@ -876,8 +824,7 @@ const char* ehm_explicit_last_error(void) { return x_err.c_str(); }
 int ehm_explicit_destroy(ehm_explicit* E) {
     if (!E) return EHM_OK;
     (void)hipSetDevice(E->device);
-    if (E->stream) (void)hipStreamDestroy(E->stream);
-    delete E;       // the buffers free themselves
+    delete E;       // the stream and the buffers free themselves
     return EHM_OK;
 }
 
@@ -896,7 +843,7 @@ int ehm_explicit_create(int device, int64_t n_nodes, int32_t n_roots, int32_t p,
                                                             ehm_explicit_destroy);
     E->device = device;
     Y_TRY(hipSetDevice(device));
-    Y_TRY(hipStreamCreate(&E->stream));
+    Y_TRY(E->stream.create());
     const int stride = ((p + p * p + 7) / 8) * 8;
     const size_t nV = (size_t)n_nodes * (p + 1) * p, nU = (size_t)n_nodes * (p + 1) * n_u;
     std::vector<int2> ch((size_t)n_nodes);
@@ -907,12 +854,12 @@ int ehm_explicit_create(int device, int64_t n_nodes, int32_t n_roots, int32_t p,
     Y_TRY(E->vinput.upload(vinput, nU * sizeof(double)));
     Y_TRY(d_vert.upload(vertices, nV * sizeof(double)));
     Y_TRY(d_sing.alloc(sizeof(int32_t)));
-    Y_TRY(hipMemset(d_sing.p, 0, sizeof(int32_t)));
+    Y_TRY(hipMemset(d_sing.ptr, 0, sizeof(int32_t)));
     hipLaunchKernelGGL(k_explicit_setup, dim3((unsigned)((n_nodes + 127) / 128)), dim3(128), 0,
                        E->stream, (long long)n_nodes, (int)p, stride, d_vert.as<const double>(),
                        E->rec.as<double>(), d_sing.as<int32_t>());
     int32_t sing = 0;
-    Y_TRY(hipMemcpyAsync(&sing, d_sing.p, sizeof sing, hipMemcpyDeviceToHost, E->stream));
+    Y_TRY(hipMemcpyAsync(&sing, d_sing.ptr, sizeof sing, hipMemcpyDeviceToHost, E->stream));
     Y_TRY(hipStreamSynchronize(E->stream));
     if (sing) return xfail(EHM_E_NUMERIC, "%d degenerate simplices in the partition", (int)sing);
     if (n_roots >= EHM_X_LOCATE_MIN && n_roots < (1 << 20)) {
@@ -979,7 +926,7 @@ int ehm_explicit_eval_batch(ehm_explicit* E, int64_t n, const double* x, double*
         E->cap = (size_t)n;
     }
     EventPair ev;
-    Y_TRY(hipMemcpyAsync(E->x.p, x, (size_t)n * p * sizeof(double), hipMemcpyHostToDevice,
+    Y_TRY(hipMemcpyAsync(E->x.ptr, x, (size_t)n * p * sizeof(double), hipMemcpyHostToDevice,
                          E->stream));
     (void)hipEventRecord(ev.e0, E->stream);
     // long spines: the visibility walk over the roots finds the root first (locate_off: the
@@ -995,13 +942,13 @@ int ehm_explicit_eval_batch(ehm_explicit* E, int64_t n, const double* x, double*
                        locate ? E->root.as<const int32_t>() : (const int32_t*)nullptr);
     (void)hipEventRecord(ev.e1, E->stream);
     Y_TRY(hipGetLastError());
-    Y_TRY(hipMemcpyAsync(u, E->u.p, (size_t)n * n_u * sizeof(double), hipMemcpyDeviceToHost,
+    Y_TRY(hipMemcpyAsync(u, E->u.ptr, (size_t)n * n_u * sizeof(double), hipMemcpyDeviceToHost,
                          E->stream));
     if (leaf)
-        Y_TRY(hipMemcpyAsync(leaf, E->leaf.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost,
+        Y_TRY(hipMemcpyAsync(leaf, E->leaf.ptr, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost,
                              E->stream));
     if (visited)
-        Y_TRY(hipMemcpyAsync(visited, E->depth.p, (size_t)n * sizeof(int32_t),
+        Y_TRY(hipMemcpyAsync(visited, E->depth.ptr, (size_t)n * sizeof(int32_t),
                              hipMemcpyDeviceToHost, E->stream));
     Y_TRY(hipStreamSynchronize(E->stream));
     ev.seconds(kernel_seconds);
@@ -1131,7 +1078,7 @@ int rollout_run(ehm_explicit* E, int64_t n, int32_t T, const double* x0, const d
     for (Out& o : out)
         if (ok && o.host) {
             ok = o.buf.alloc(o.bytes) == hipSuccess;
-            std::memcpy(o.field, &o.buf.p, sizeof o.buf.p);
+            std::memcpy(o.field, &o.buf.ptr, sizeof o.buf.ptr);
         }
     if (!ok)
         return xfail(EHM_E_HIP, "rollout: out of device memory for %lld x %d steps",
@@ -1141,9 +1088,9 @@ int rollout_run(ehm_explicit* E, int64_t n, int32_t T, const double* x0, const d
     R.v = dv.as<const double>();
     R.node_mode = E->node_mode.as<const int32_t>();
     R.nbr = (E->nbr && !locate_off()) ? E->nbr.as<const int32_t>() : nullptr;
-    Y_TRY(hipMemcpyAsync(dx0.p, x0, N * p * D, hipMemcpyHostToDevice, E->stream));
-    if (d) Y_TRY(hipMemcpyAsync(dd.p, d, nT * N * n_d * D, hipMemcpyHostToDevice, E->stream));
-    if (v) Y_TRY(hipMemcpyAsync(dv.p, v, nT * N * p * D, hipMemcpyHostToDevice, E->stream));
+    Y_TRY(hipMemcpyAsync(dx0.ptr, x0, N * p * D, hipMemcpyHostToDevice, E->stream));
+    if (d) Y_TRY(hipMemcpyAsync(dd.ptr, d, nT * N * n_d * D, hipMemcpyHostToDevice, E->stream));
+    if (v) Y_TRY(hipMemcpyAsync(dv.ptr, v, nT * N * p * D, hipMemcpyHostToDevice, E->stream));
     EventPair ev;
     (void)hipEventRecord(ev.e0, E->stream);
     DevNoise NZ{};
@@ -1161,7 +1108,7 @@ int rollout_run(ehm_explicit* E, int64_t n, int32_t T, const double* x0, const d
     Y_TRY(hipGetLastError());
     for (const Out& o : out)
         if (o.host)
-            Y_TRY(hipMemcpyAsync(o.host, o.buf.p, o.bytes, hipMemcpyDeviceToHost, E->stream));
+            Y_TRY(hipMemcpyAsync(o.host, o.buf.ptr, o.bytes, hipMemcpyDeviceToHost, E->stream));
     Y_TRY(hipStreamSynchronize(E->stream));
     ev.seconds(kernel_seconds);
     return EHM_OK;
@@ -1341,7 +1288,7 @@ int ehm_philox_batch(int64_t n, const uint64_t* counters, const uint64_t* key, u
                        (long long)n, dc.as<const uint64_t>(), key[0], key[1],
                        dout.as<uint64_t>());
     Y_TRY(hipGetLastError());
-    Y_TRY(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
+    Y_TRY(hipMemcpy(out, dout.ptr, bytes, hipMemcpyDeviceToHost));
     return EHM_OK;
 }
 

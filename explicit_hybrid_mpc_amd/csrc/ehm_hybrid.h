@@ -794,16 +794,6 @@ struct HyState {
     HyCtr h{};
     int fail_delta = -1;                 // test hook: vertex solves of this commutation "fail"
     PersistDeal deal{0, 0, 0, 1, 1};     // sharded runs: deal depth / rank / world
-    void release() {
-        DevBuf* all[] = {&vf, &cand, &black, &neg, &tneg, &fr_ecc[0], &fr_ecc[1], &fr_lcss[0], &fr_lcss[1],
-                         &known1, &ask, &slk, &vall, &redo, &koff, &src, &dst, &dcomm, &dsel2, &cnt,
-                         &tau, &tval,
-                         &st, &alpha, &act, &best, &ths, &vJ, &vu, &vst, &Jth, &Jth_st, &Jmin,
-                         &Jmin_st, &dselV, &eoffV, &dselT, &eoffT, &dselM, &eoffM, &sp_k, &sp_c0,
-                         &sp_ij, &sp_d, &mids, &Jm, &um, &mst, &midforced, &midask, &midbits,
-                         &moff, &ctr, &snaps, &pt_state, &pt_data};
-        for (DevBuf* b : all) b->release();
-    }
 };
 
 #define HY_MAX_SNAPS 8192
@@ -819,9 +809,8 @@ static int hy_alloc(ehm_tree* T) {
     const int nw = H.nw;
     H.ch = std::max<long long>(1024, std::min<long long>(1LL << 17, (1LL << 22) / nd));
     if (const char* e = getenv("EHM_HY_CHUNK")) H.ch = std::max(64, atoi(e));
-    const size_t ch = (size_t)H.ch, cap = (size_t)T->cap;
-    int rc;
-#define HY_ENSURE(buf, bytes) if ((rc = H.buf.ensure(bytes))) return rc
+    const size_t ch = (size_t)H.ch, cap = (size_t)T->pool.cap;
+#define HY_ENSURE(buf, bytes) HIP_TRY(H.buf.ensure(bytes), EHM_E_HIP)
     HY_ENSURE(vf, cap * nv * nw * 8);
     HY_ENSURE(cand, cap * nw * 8);
     HY_ENSURE(black, cap * nw * 8);
@@ -878,10 +867,7 @@ struct HyList {      // the work list sitting in H.src / H.dst / seg
 // event pair + counter snapshot around a batched launch: kernel seconds and iterations by LP kind
 static void hy_stamp(ehm_tree* T) {
     if (!T->prob->hy_timing) return;
-    hipEvent_t e;
-    (void)hipEventCreate(&e);
-    (void)hipEventRecord(e, T->prob->stream);
-    T->run.evs.push_back(e);
+    T->run.evs.push_back(Event::recorded(T->prob->stream));
 }
 static void hy_after_batch(ehm_tree* T, int lp_kind, int family) {
     HyState& H = *T->hy;
@@ -889,7 +875,7 @@ static void hy_after_batch(ehm_tree* T, int lp_kind, int family) {
     hy_stamp(T);
     T->run.ev_kind.push_back(family);
     if (H.snap_kind.size() < HY_MAX_SNAPS) {
-        (void)hipMemcpyAsync(H.snaps.as<DevCounters>() + H.snap_kind.size(), T->prob->d_cnt,
+        (void)hipMemcpyAsync(H.snaps.as<DevCounters>() + H.snap_kind.size(), T->prob->counters(),
                              sizeof(DevCounters), hipMemcpyDeviceToDevice, T->prob->stream);
         H.snap_kind.push_back(lp_kind);
     }
@@ -959,7 +945,7 @@ static int hy_run_simplex(ehm_tree* T, int mode, double* obj, double* alpha, int
     K2Gather G{L.src, L.dst, L.n_dev, rec_off_vcost(P->dp.p), nullptr, sign_mode};
     hy_stamp(T);
     cfg.api->simplex(cfg.L, P->dp, 0, T->dt.rec, nullptr, L.seg, mode, obj, alpha, status, nullptr,
-                     P->d_cnt, G);
+                     P->counters(), G);
     hy_after_batch(T, kind, 0);
     P->launches++;
     return EHM_OK;
@@ -982,7 +968,7 @@ static int hy_run_point(ehm_tree* T, const double* base, int feas, double* J, do
     K2Gather G{L.src, L.dst, L.n_dev, 0, nullptr, (feas && !P->decide_full) ? 1 : 0};
     G.pt = T->hy->pt;
     hy_stamp(T);
-    cfg.api->point(cfg.L, P->dp, 0, base, L.seg, feas, J, u0, status, nullptr, P->d_cnt, G);
+    cfg.api->point(cfg.L, P->dp, 0, base, L.seg, feas, J, u0, status, nullptr, P->counters(), G);
     hy_after_batch(T, feas ? LP_FEAS : LP_POINT, 1);
     P->launches++;
     return EHM_OK;
@@ -999,7 +985,7 @@ static void hy_run_simplex_v1(ehm_tree* T, int mode, double* obj, double* alpha,
     K2Gather G{L.src, L.dst, L.n_dev, rec_off_vcost(P->dp.p), nullptr, 0};
     hipLaunchKernelGGL(k_simplex_batch, dim3(P->num_cu * 8), dim3(64), P->lds_simplex, P->stream,
                        P->dp, 0LL, T->dt.rec, (const double*)nullptr, T->hy->dcomm.as<int32_t>(),
-                       mode, obj, alpha, status, (int32_t*)nullptr, P->d_cnt, G);
+                       mode, obj, alpha, status, (int32_t*)nullptr, P->counters(), G);
     if (P->solver_gen == 2)
         hipLaunchKernelGGL(hy_add_items, dim3(1), dim3(64), 0, P->stream, T->hy->ctr.as<HyCtr>());
     P->launches += 2;
@@ -1011,7 +997,7 @@ static void hy_run_point_v1(ehm_tree* T, const double* base, int feas, double* J
     K2Gather G{L.src, L.dst, L.n_dev, 0, nullptr, 0};
     hipLaunchKernelGGL(k_point_batch, dim3(P->num_cu * 8), dim3(64), P->lds_point, P->stream,
                        P->dp, 0LL, base, T->hy->dcomm.as<int32_t>(), feas, J, u0, status,
-                       (int32_t*)nullptr, P->d_cnt, G);
+                       (int32_t*)nullptr, P->counters(), G);
     if (P->solver_gen == 2)
         hipLaunchKernelGGL(hy_add_items, dim3(1), dim3(64), 0, P->stream, T->hy->ctr.as<HyCtr>());
     P->launches += 2;
@@ -1218,9 +1204,8 @@ static int hy_sweep(ehm_tree* T) {
     HyState& H = *T->hy;
     auto& R = T->run;
     const int cur = H.cur, nxt = 1 - cur;
-    int rc;
-    if ((rc = H.fr_ecc[nxt].ensure((size_t)(3 * H.n_ecc + 64) * 4))) return rc;
-    if ((rc = H.fr_lcss[nxt].ensure((size_t)(2 * H.n_lcss + H.n_ecc + 64) * 4))) return rc;
+    HIP_TRY(H.fr_ecc[nxt].ensure((size_t)(3 * H.n_ecc + 64) * 4), EHM_E_HIP);
+    HIP_TRY(H.fr_lcss[nxt].ensure((size_t)(2 * H.n_lcss + H.n_ecc + 64) * 4), EHM_E_HIP);
     int32_t* next_ecc = H.fr_ecc[nxt].as<int32_t>();
     int32_t* next_lcss = H.fr_lcss[nxt].as<int32_t>();
     for (long long f0 = 0; f0 < H.n_ecc; f0 += H.ch) {
@@ -1267,7 +1252,7 @@ static int hy_begin(ehm_tree* T, int64_t n_roots, const ehm_node_init* init) {
     auto& R = T->run;
     if (P->solver_gen != 2 && !P->v1_ok)
         return fail(EHM_E_INVALID, "this problem does not fit the generation-1 kernels");
-    T->hy = new HyState();
+    T->hy = std::make_unique<HyState>();
     HyState& H = *T->hy;
     H.on = true;
     int rc = hy_alloc(T);
@@ -1299,7 +1284,7 @@ static int hy_begin(ehm_tree* T, int64_t n_roots, const ehm_node_init* init) {
         if (sharded && R.deal_depth <= 0)
             return fail(EHM_E_INVALID, "sharded multi-commutation runs need ehm_run_opts.deal_depth");
         if (sharded) H.deal = PersistDeal{0, R.deal_depth, R.shard_rank, R.shard_world, 1};
-        if ((rc = T->code.ensure((size_t)T->cap * 4))) return rc;
+        HIP_TRY(T->code.ensure((size_t)T->pool.cap * 4), EHM_E_HIP);
         T->dt.code = T->code.as<uint32_t>();
         std::vector<uint32_t> codes((size_t)n_roots);
         for (int64_t k = 0; k < n_roots; ++k) codes[(size_t)k] = (uint32_t)k;
@@ -1337,12 +1322,12 @@ static int hy_begin(ehm_tree* T, int64_t n_roots, const ehm_node_init* init) {
         R.pre_nodes = n_roots;
         T->unordered = true;
         T->keep_ids = true;
-        int rc2;
-        if ((rc2 = H.fr_lcss[0].ensure(4096)) || (rc2 = H.fr_ecc[0].ensure(4096))) return rc2;
+        HIP_TRY(H.fr_lcss[0].ensure(4096), EHM_E_HIP);
+        HIP_TRY(H.fr_ecc[0].ensure(4096), EHM_E_HIP);
         return EHM_OK;
     }
     DevBuf& f0 = (R.action == 1) ? H.fr_lcss[0] : H.fr_ecc[0];
-    if ((rc = f0.ensure((size_t)n_roots * 4))) return rc;
+    HIP_TRY(f0.ensure((size_t)n_roots * 4), EHM_E_HIP);
     std::vector<int32_t> ids((size_t)n_roots);
     for (int64_t k = 0; k < n_roots; ++k) ids[(size_t)k] = (int32_t)k;
     HIP_TRY(hipMemcpyAsync(f0.ptr, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, P->stream),
@@ -1450,9 +1435,8 @@ static int hy_take(ehm_tree* T, int64_t count, int32_t* node_ids, double* record
                     (long long)count, H.n_lcss);
     if (count == 0) return EHM_OK;
     const int W = hy_record_doubles(P->dp.p, P->dp.n_u, H.nw);
-    int rc;
-    if ((rc = P->out0.ensure((size_t)count * W * sizeof(double)))) return rc;
-    if ((rc = P->out2.ensure((size_t)count * 2 * sizeof(int32_t)))) return rc;
+    HIP_TRY(P->out0.ensure((size_t)count * W * sizeof(double)), EHM_E_HIP);
+    HIP_TRY(P->out2.ensure((size_t)count * 2 * sizeof(int32_t)), EHM_E_HIP);
     const int32_t* cur = H.fr_lcss[H.cur].as<int32_t>() + (H.n_lcss - count);
     hipLaunchKernelGGL(hy_take_nodes, dim3((unsigned)count), dim3(64), 0, P->stream, T->dt, cur,
                        (int)count, H.nw, H.vf.as<hy_u64>(), H.cand.as<hy_u64>(),
@@ -1483,19 +1467,17 @@ static int hy_give(ehm_tree* T, int64_t count, const double* records, const int3
         return fail(EHM_E_CAPACITY, "node pool exhausted at %lld nodes (max_nodes=%lld)",
                     R.n_nodes, T->limit);
     const int W = hy_record_doubles(P->dp.p, P->dp.n_u, H.nw);
-    int rc;
-    if ((rc = P->in0.ensure((size_t)count * W * sizeof(double)))) return rc;
-    if ((rc = P->in1.ensure((size_t)count * 2 * sizeof(int32_t)))) return rc;
+    HIP_TRY(P->in0.ensure((size_t)count * W * sizeof(double)), EHM_E_HIP);
+    HIP_TRY(P->in1.ensure((size_t)count * 2 * sizeof(int32_t)), EHM_E_HIP);
     DevBuf& fb = H.fr_lcss[H.cur];
     if ((long long)fb.cap < (H.n_lcss + count) * 4) {
         DevBuf bigger;
-        if ((rc = bigger.ensure((size_t)(H.n_lcss + count) * 4 * 2))) return rc;
+        HIP_TRY(bigger.ensure((size_t)(H.n_lcss + count) * 4 * 2), EHM_E_HIP);
         if (H.n_lcss > 0)
             HIP_TRY(hipMemcpyAsync(bigger.ptr, fb.ptr, (size_t)H.n_lcss * 4,
                                    hipMemcpyDeviceToDevice, P->stream), EHM_E_HIP);
         HIP_TRY(hipStreamSynchronize(P->stream), EHM_E_HIP);
         std::swap(bigger, fb);
-        bigger.release();
     }
     HIP_TRY(hipMemcpyAsync(P->in0.ptr, records, (size_t)count * W * sizeof(double),
                            hipMemcpyDefault, P->stream), EHM_E_HIP);

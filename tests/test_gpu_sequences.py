@@ -62,6 +62,53 @@ def test_slot_entry_points_and_table_updates():
     gp.close()
 
 
+def same(a, b):
+    return all(np.array_equal(x, y, equal_nan=np.asarray(x).dtype.kind == 'f')
+               for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize('kind', ['pwa_small', 'lin', 'chain_small'])
+def test_updated_blocks_equal_created_blocks(kind):
+    """A handle created with blocks X and updated to blocks Y answers bit for bit as a handle
+    created with Y: every image ehm_problem_update_blocks writes is the one creation writes.
+    pwa_small: several commutations, slots reversed; lin: eliminated columns (DevProblem::Wc4);
+    chain_small: the row-major image of the wide kernels (DevProblem::Wr3)."""
+    import copy
+    from explicit_hybrid_mpc_amd import engine
+    mpc = helpers.make_instance(kind, 0)
+    x = mpc.compile()
+    y = copy.copy(x)
+    if kind == 'pwa_small':
+        y.G, y.w, y.S = (np.ascontiguousarray(a[::-1]) for a in (x.G, x.w, x.S))
+    else:
+        y.w = x.w + 1e-3 * (1. + np.abs(x.w))      # looser: the roots stay feasible
+    eps_a = helpers.eps_a_rule(mpc, 0.25)
+    a = engine.GpuProblem(x, eps_a, 0.2)
+    b = engine.GpuProblem(y, eps_a, 0.2)
+    try:
+        a.update_blocks(0, y.G, y.w, y.S)
+        rng = np.random.default_rng(1)
+        R = np.array(helpers.random_simplices(mpc, rng, 16))
+        slot = np.arange(16, dtype=np.int32) % x.n_delta
+        theta = R.mean(axis=1)
+        assert same(a.solve_ptd(theta, x.deltas[slot]), b.solve_ptd(theta, x.deltas[slot]))
+        for mode in (0, 2):
+            assert same(a.simplex_idx(R, slot, mode), b.simplex_idx(R, slot, mode))
+        roots, _ = helpers.roots_of(mpc)
+        roots = np.array(roots)[::2] if kind == 'chain_small' else np.array(roots)
+        # the level-synchronous sweeps: the persistent kernel's shared midpoint optima depend on
+        # which simplex solves a midpoint first, so its trees agree only to rounding
+        ta, tb = a.partition(roots, engine=0), b.partition(roots, engine=0)
+        assert ta.n_nodes > len(roots)
+        assert same([ta.vertices, ta.left, ta.right, ta.delta_idx, ta.vertex_costs,
+                     ta.vertex_inputs, ta.flags, ta.tstar],
+                    [tb.vertices, tb.left, tb.right, tb.delta_idx, tb.vertex_costs,
+                     tb.vertex_inputs, tb.flags, tb.tstar])
+    finally:
+        a.close()
+        b.close()
+
+
 def test_prefix_relaxations_on_the_device_match_the_uncondensed_lps():
     """The condensed prefix blocks (PWAMPC.condense_prefix) solve to the optima of the
     uncondensed relaxations (oracle/prefix_bb.PrefixModel, HiGHS)."""
