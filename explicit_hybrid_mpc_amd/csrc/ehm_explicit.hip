@@ -864,12 +864,15 @@ int ehm_explicit_create(int device, int64_t n_nodes, int32_t n_roots, int32_t p,
     if (sing) return xfail(EHM_E_NUMERIC, "%d degenerate simplices in the partition", (int)sing);
     if (n_roots >= EHM_X_LOCATE_MIN && n_roots < (1 << 20)) {
         // face adjacency of the roots: vertices by value, faces by their sorted vertex ids
+        // (the key holds -0.0 as 0.0: one vertex however a root writes its zero coordinates)
         std::unordered_map<std::string, int32_t> vid;
         std::vector<int32_t> ids((size_t)n_roots * (p + 1));
+        double vk[EHM_XP];
         for (int64_t r = 0; r < n_roots; ++r)
             for (int i = 0; i <= p; ++i) {
-                std::string key((const char*)(vertices + ((size_t)r * (p + 1) + i) * p),
-                                sizeof(double) * p);
+                const double* v = vertices + ((size_t)r * (p + 1) + i) * p;
+                for (int c = 0; c < p; ++c) vk[c] = (v[c] == 0.0) ? 0.0 : v[c];
+                std::string key((const char*)vk, sizeof(double) * p);
                 auto it = vid.find(key);
                 if (it == vid.end()) it = vid.emplace(std::move(key), (int32_t)vid.size()).first;
                 ids[(size_t)r * (p + 1) + i] = it->second;
