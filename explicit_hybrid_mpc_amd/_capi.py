@@ -43,6 +43,9 @@ EXPORTED = [
     'ehm_host_alloc', 'ehm_host_free', 'ehm_explicit_set_plant', 'ehm_explicit_rollout',
     'ehm_explicit_set_noise', 'ehm_explicit_rollout_noisy', 'ehm_philox_batch',
     'ehm_explicit_set_plant_guarded',
+    'ehm_implicit_create', 'ehm_implicit_destroy', 'ehm_implicit_last_error',
+    'ehm_implicit_set_plant', 'ehm_implicit_set_plant_guarded', 'ehm_implicit_set_noise',
+    'ehm_implicit_rollout',
 ]
 
 
@@ -260,6 +263,14 @@ def load(build_if_missing=True):
                                                ctypes.c_double] + [vp] * 13
     lib.ehm_philox_batch.argtypes = [i64, vp, vp, vp]
     lib.ehm_explicit_last_error.restype = ctypes.c_char_p
+    lib.ehm_implicit_last_error.restype = ctypes.c_char_p
+    lib.ehm_implicit_create.argtypes = [vp, ctypes.POINTER(vp)]
+    lib.ehm_implicit_destroy.argtypes = [vp]
+    lib.ehm_implicit_set_plant.argtypes = lib.ehm_explicit_set_plant.argtypes
+    lib.ehm_implicit_set_plant_guarded.argtypes = lib.ehm_explicit_set_plant_guarded.argtypes
+    lib.ehm_implicit_set_noise.argtypes = lib.ehm_explicit_set_noise.argtypes
+    lib.ehm_implicit_rollout.argtypes = [vp, i64, i32, vp, vp, vp, i32, ctypes.c_uint64,
+                                         ctypes.c_uint64, ctypes.c_double] + [vp] * 16
     lib.ehm_tree_info_get.argtypes = [vp, ctypes.POINTER(TreeInfo)]
     lib.ehm_tree_export.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.ehm_host_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(vp)]
@@ -272,7 +283,7 @@ def load(build_if_missing=True):
     for name in EXPORTED:
         fn = getattr(lib, name)
         if name not in ('ehm_last_error', 'ehm_version', 'ehm_stream',
-                        'ehm_explicit_last_error'):
+                        'ehm_explicit_last_error', 'ehm_implicit_last_error'):
             fn.restype = i32
     lib.ehm_search_last_error.restype = ctypes.c_char_p
     lib.ehm_search_create.argtypes = [i32, i32, i32, ctypes.POINTER(vp)]

@@ -3,7 +3,8 @@ Builds ``explicit_hybrid_mpc_amd/lib/libehmpc.so`` (HIP kernels + C-ABI, include
 for gfx950 with hipcc.  hipcc cross-compiles without a GPU, so this also runs in the
 CPU-only build container.
 
-Objects: ``ehm_capi.hip`` (C-ABI, host orchestration, generation-1 kernels), one
+Objects: ``ehm_capi.hip`` (C-ABI, host orchestration, generation-1 kernels),
+``ehm_explicit.hip`` and ``ehm_implicit.hip`` (the closed loops around the two laws), one
 instance of ``ehm_k2.hip`` per (column capacity NP, row slots) pair -- the solver keeps a
 row of the normal matrix and the LP's row vectors in registers, so both are compile-time
 sizes -- and the wide kernels ``ehm_k3.hip`` per row capacity.  The objects are compiled
@@ -127,6 +128,8 @@ def _objects():
     """(object path, source path, extra flags)"""
     objs = [(os.path.join(OBJ_DIR, 'ehm_capi.o'), os.path.join(SRC_DIR, 'ehm_capi.hip'), []),
             (os.path.join(OBJ_DIR, 'ehm_explicit.o'), os.path.join(SRC_DIR, 'ehm_explicit.hip'),
+             []),
+            (os.path.join(OBJ_DIR, 'ehm_implicit.o'), os.path.join(SRC_DIR, 'ehm_implicit.hip'),
              [])]
     for np_ in K2_NPS:
         for sl in K2_SLOTS:
@@ -181,7 +184,7 @@ def is_stale():
         return True                 # generated (tools/gen_kp.py), not in the repository
     srcs = [os.path.join(SRC_DIR, f)
             for f in ('ehm_capi.hip', 'ehm_k2.hip', 'ehm_k3.hip', 'ehm_k4.hip', 'ehm_kp.hip',
-                      'ehm_explicit.hip')]
+                      'ehm_explicit.hip', 'ehm_implicit.hip')]
     return max([_dep_mtime()] + [os.path.getmtime(s)
                                  for s in srcs + SEARCH_DEPS + FRONTIER_DEPS]) > t
 

@@ -19,6 +19,7 @@
 #define EHM_MAX_P_DEV 8
 #include "ehm_kernels.h"
 #include "ehm_k2.h"
+#include "ehm_implicit.h"
 
 using namespace ehm;
 
@@ -1341,13 +1342,9 @@ int ehm_solve_ptd_batch(ehm_problem* P, int64_t n_inst, const double* theta,
     return point_batch(P, n_inst, theta, didx.data(), 0, J, u0, status, iters);
 }
 
-// feasibility margin: the phase-one optimum is compared against a tolerance that is far
-// above the solver accuracy (1e-10 relative) and far below any constraint scale
-#define EHM_FEAS_TOL 1e-8
+// EHM_FEAS_TOL (feasibility margin of the phase-one optimum) and EHM_TIE_TOL (ties between
+// commutations): ehm_implicit.h, shared with the device loop around the implicit law
 #define EHM_SLIVER_TOL 1e-7
-// optimal values of different commutations closer than this (relative to 1+|value|) are
-// ties, broken by enumeration order (DESIGN.md "canonical commutation rule")
-#define EHM_TIE_TOL 1e-6
 
 int ehm_feas_ptd_batch(ehm_problem* P, int64_t n_inst, const double* theta,
                        const uint8_t* delta, uint8_t* feasible, double* tau) {
@@ -1607,6 +1604,35 @@ int ehm_solve_pt_batch(ehm_problem* P, int64_t n_inst, const double* theta, doub
             if (u0) std::memcpy(u0 + k * n_u, &u2[(size_t)f * n_u], n_u * sizeof(double));
         }
     }
+    return EHM_OK;
+}
+
+// ---- the closed loop around the implicit law (ehm_implicit.hip; interface: ehm_implicit.h) -----
+int ehm_imp_describe(ehm_problem* P, ImpProblem* out) {
+    if (!P || !out) return fail(EHM_E_INVALID, "null argument");
+    if (P->solver_gen != 2)
+        return fail(EHM_E_INVALID, "the device loop of the implicit law runs on the generation-2 "
+                                   "kernels (ehm_problem_set_solver)");
+    *out = ImpProblem{P->device, P->dp.p, P->dp.n_u, P->dp.n_delta, P->stream};
+    return EHM_OK;
+}
+
+int ehm_imp_point(ehm_problem* P, int feas, long long max_items, const double* base,
+                  const int32_t* seg, double* J, double* u0, int32_t* status,
+                  const long long* src, const int32_t* dst, const int32_t* n_dev) {
+    if (!P || !base || !seg || !J || !src || max_items < 1)
+        return fail(EHM_E_INVALID, "bad argument");
+    K2Cfg cfg;
+    int rc = k2_config(P, feas ? LP_FEAS : LP_POINT, feas ? LP_FEAS : LP_POINT, max_items, cfg);
+    if (rc) return rc;
+    K2Gather G{};
+    G.src = src;
+    G.dst = dst;
+    G.n_dev = n_dev;
+    cfg.api->point(cfg.L, P->dp, max_items, base, seg, feas, J, u0, status, nullptr,
+                   P->counters(), G);
+    P->launches++;
+    HIP_TRY(hipGetLastError(), EHM_E_HIP);
     return EHM_OK;
 }
 

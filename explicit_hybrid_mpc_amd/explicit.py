@@ -104,20 +104,23 @@ class ImplicitMPC:
         return u, t
 
     def rollout(self, X0, T, d=None, v=None, record=True, tol_exit=1e-9, plant=None, noise=None,
-                seed=0, traj0=0):
+                seed=0, traj0=0, on_device=False):
         """
         Closed loop from the states X0 [n, p] for T steps (simulate.py): per step one batched
         P_theta over the live trajectories, the plant (default ``Plant.from_mpc``) stepped in
         the step-0 mode of the returned commutation.  ``noise`` (a ``noise.NoiseModel``) draws
         v, e and d on the host with the counters of the device rollout (trajectory q has id
-        traj0 + q).  Returns a ``simulate.ClosedLoop``.
+        traj0 + q).  ``on_device=True``: the whole loop runs on the device
+        (``simulate.rollout_implicit``; the result also has ``stalled`` and ``n_stalled_pairs``).
+        Returns a ``simulate.ClosedLoop``.
         """
         from . import simulate
         if plant is None:
             plant = simulate.Plant.from_mpc(self.__oracle.mpc)
         self._rollout_plant = plant
         return simulate.rollout_implicit(self.__oracle, plant, X0, T, d=d, v=v, record=record,
-                                         tol_exit=tol_exit, noise=noise, seed=seed, traj0=traj0)
+                                         tol_exit=tol_exit, noise=noise, seed=seed, traj0=traj0,
+                                         on_device=on_device)
 
     def evaluate(self, X):
         """Inputs for a batch of states (n, p) -> (n, n_u); NaN rows where infeasible."""

@@ -37,6 +37,10 @@ class Oracle:
         self.gpu = GpuProblem(self.canonical, eps_a, eps_r, device=device)
 
     def close(self):
+        # the device loop of the implicit law borrows the solver handle: it goes first
+        dev = self.__dict__.pop('_implicit_device', None)
+        if dev is not None:
+            dev.close()
         self.gpu.close()
 
     def _delta_of(self, idx):

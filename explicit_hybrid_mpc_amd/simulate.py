@@ -294,7 +294,8 @@ class ClosedLoop:
     after the step a trajectory stopped at), e [T, n, n_u] and w [T, n, n_d] (NaN from it on).  Always: x_final [n, n_x], steps [n], status [n]
     (STATUS_*), cost [n] (summed stage cost), u_norm_sum [n] (sum_t ||u_t||_2), max_violation [n]
     (max_t max_j (Gx x_{t+1} - gx)_j, -inf without a step), seconds (device time of the explicit
-    rollout kernel / wall time of the implicit loop).
+    rollout kernel / wall time of the implicit loop / device time of the implicit device loop,
+    which also sets stalled [n] and n_stalled_pairs).
     """
 
     def __init__(self, **kw):
@@ -332,18 +333,31 @@ def _check_rollout_args(plant, noise, d, v, n, p, T):
 
 
 def rollout_implicit(oracle, plant, X0, T, d=None, v=None, record=True, tol_exit=1e-9, noise=None,
-                     seed=0, traj0=0):
+                     seed=0, traj0=0, on_device=False):
     """
     The implicit law in closed loop: per step one batched ``solve_pt`` (the device's
     mixed-integer oracle) over the live trajectories, the plant step on the host with the
     conventions of the module docstring (``noise``: v, e, d from the host sampler of the
     model).  Returns a ClosedLoop (commutation, no leaf).
+
+    ``on_device=True`` runs the whole loop on the device instead (implicit_device.py,
+    ``ehm_implicit_rollout``): the same conventions and ClosedLoop fields, plus ``stalled`` [n] and
+    ``n_stalled_pairs`` -- a solve that stalls, in phase one or in the point solve, is not
+    repeated on the generation-1 kernels there (phase one keeps its tau, a point solve is left out
+    of the minimum), so flagged trajectories may differ from this loop's; ``seconds`` is then the
+    device time between the first and the last launch.  It needs an oracle with enumerated
+    commutations (not ``bnb.PrefixOracle``), n_u <= 4 and p <= 8.
     """
     X0 = np.ascontiguousarray(np.atleast_2d(X0), dtype=np.float64)
     n, p = X0.shape
     d, v = _check_rollout_args(plant, noise, d, v, n, p, T)
     if noise is not None and (noise.n_x, noise.n_u, noise.n_d) != (p, plant.n_u, plant.n_d):
         raise ValueError('the noise model does not fit the plant')
+    if on_device:
+        from . import implicit_device
+        implicit_device.check_args(oracle, plant)
+        return implicit_device.rollout(oracle, plant, X0, T, d=d, v=v, record=record,
+                                       tol_exit=tol_exit, noise=noise, seed=seed, traj0=traj0)
     ids = np.uint64(int(traj0)) + np.arange(n, dtype=np.uint64)
     u_prev = np.zeros((n, plant.n_u))
     can = oracle.canonical
@@ -418,7 +432,7 @@ def rollout_implicit(oracle, plant, X0, T, d=None, v=None, record=True, tol_exit
 
 
 def compare(explicit, implicit, X0, T, d=None, v=None, tol_exit=1e-9, record=False, noise=None,
-            seed=0):
+            seed=0, implicit_on_device=False):
     """
     The explicit against the implicit law from the same initial states under the same d / v, or
     under the same draws of a noise model (common random numbers: one seed, the same trajectory
@@ -427,12 +441,15 @@ def compare(explicit, implicit, X0, T, d=None, v=None, tol_exit=1e-9, record=Fal
     where the implicit figure is 0).  Aggregates over the trajectories both laws ran for all T
     steps (``both_ok``): ``overconsumption_total`` (the statistic of total_delta_v_usage over
     the summed usage) and ``cost_ratio_total``.  Also the exit / stop counts and the two
-    ClosedLoop results (``explicit``, ``implicit``).
+    ClosedLoop results (``explicit``, ``implicit``).  ``implicit_on_device``: the implicit law's
+    rollout runs on the device (``rollout_implicit(..., on_device=True)``).
     """
     kw = dict(d=d, v=v, record=record, tol_exit=tol_exit)
     if noise is not None:
         kw.update(noise=noise, seed=seed)
     ex = explicit.rollout(X0, T, **kw)
+    if implicit_on_device:
+        kw['on_device'] = True
     im = implicit.rollout(X0, T, **kw)
     both = (ex.status == STATUS_OK) & (im.status == STATUS_OK)
     with np.errstate(divide='ignore', invalid='ignore'):

@@ -558,6 +558,68 @@ int ehm_explicit_rollout_noisy(ehm_explicit* ex, int64_t n, int32_t T, const dou
  * and out [n][4], key [2] (numpy: np.random.Philox(counter=c - 1, key=key).random_raw(4)). */
 int ehm_philox_batch(int64_t n, const uint64_t* counters, const uint64_t* key, uint64_t* out);
 
+/* ---- the closed loop around the IMPLICIT law on the device (csrc/ehm_implicit.hip) ------------
+ *
+ * simulate.rollout_implicit without its host loop: per step one mixed-integer P_theta for every
+ * running trajectory (phase one for the n * n_delta (trajectory, commutation) pairs, the point
+ * solve for the feasible ones, the minimum with the tie rule of ehm_solve_pt_batch), the plant step
+ * and the noise draws, all on the stream of the solver handle with no copy and no synchronisation
+ * between steps.  The handle borrows `prob` (generation-2 solver, p <= 8, n_u <= 4): destroy it
+ * before the problem, and do not use the problem from another thread while a rollout runs.  Errors:
+ * ehm_implicit_last_error. */
+typedef struct ehm_implicit ehm_implicit;
+int ehm_implicit_create(ehm_problem* prob, ehm_implicit** out);
+int ehm_implicit_destroy(ehm_implicit* im);
+const char* ehm_implicit_last_error(void);
+/* The plant, as ehm_explicit_set_plant / ehm_explicit_set_plant_guarded take it (the same flat
+ * arrays), with mode_of [n_delta] = the step-0 mode of every commutation of the problem in place of
+ * node_mode (each in [0, n_modes); a guarded plant only records it). */
+int ehm_implicit_set_plant(ehm_implicit* im, int32_t n_modes, const double* A, const double* B,
+                           const double* w, int32_t n_d, const double* E,
+                           const int32_t* region_rows, const double* H, const double* h,
+                           int32_t n_g, const double* Gx, const double* gx,
+                           const int32_t* mode_of, int32_t cost_kind, const double* Q,
+                           const double* R);
+int ehm_implicit_set_plant_guarded(ehm_implicit* im, int32_t n_modes, const double* A,
+                                   const double* B, const double* w, int32_t substeps,
+                                   int32_t n_guards, const int32_t* guard_mode,
+                                   const int32_t* guard_row0, const double* ga, const double* gb,
+                                   const double* gc, const double* gt, const int32_t* strict,
+                                   int32_t default_mode, int32_t n_g, const double* Gx,
+                                   const double* gx, const int32_t* mode_of, int32_t cost_kind,
+                                   const double* Q, const double* R);
+/* The uncertainty model, as ehm_explicit_set_noise takes it (NoiseModel.pack). */
+int ehm_implicit_set_noise(ehm_implicit* im, int32_t n_terms, const int32_t* desc,
+                           const double* data, int32_t n_data, int32_t n_d);
+/* n trajectories of T steps from x0 [n][p].  noisy = 0: the caller's d [T][n][n_d] and v [T][n][p]
+ * (each may be NULL; v applies from t = 1); noisy = 1: d and v NULL, v, e and d drawn with the
+ * counters of ehm_explicit_rollout_noisy (key (seed, 0), trajectory q has id traj0 + q; not with a
+ * guarded plant).  Step t: z = x + v; P_theta at z; no feasible commutation, or none whose point
+ * solve converged: status 3; the region of the commutation's step-0 mode does not hold the TRUE
+ * state (within tol_exit): status 2; else stage cost and ||u||_2 of the commanded u, the plant step
+ * with u + e (a guarded plant: its substeps with u held, no status 2), the worst Gx x+ - gx.
+ * Arithmetic of the step: sums in a fixed order from 0.0, no FMA -- x+ = ((A x) + (B u)) + w, then
+ * + (E d), each product summed over its columns; a guarded plant steps as in
+ * ehm_explicit_set_plant_guarded.  Outputs and time-major records (may be NULL) as
+ * ehm_explicit_rollout_noisy, with commutation_traj [T][n] (index of the commutation, -1 after a
+ * stop) in place of leaf_traj, and mode_traj [T][n] (its step-0 mode).
+ * Stalled solves (the host path repeats them on the generation-1 kernels, this loop cannot): a
+ * phase-one solve that ends with a non-zero status keeps the tau it reached, so its verdict may
+ * differ from the host's; a feasible pair whose point solve ends with one is left out of the
+ * minimum.  Both are counted, and stalled [n] flags the trajectories this happened to -- they may
+ * differ from simulate.rollout_implicit's.
+ * counts [5]: stalled pairs (both solves), phase-one LPs, point LPs, launches of the fixed
+ * sequence (1 + 7 T), stalled pairs of phase one alone.  device_seconds (may be
+ * NULL): device time from the first to the last launch. */
+int ehm_implicit_rollout(ehm_implicit* im, int64_t n, int32_t T, const double* x0,
+                         const double* d, const double* v, int32_t noisy, uint64_t seed,
+                         uint64_t traj0, double tol_exit, double* x_traj, double* u_traj,
+                         int32_t* commutation_traj, int32_t* mode_traj, double* v_traj,
+                         double* e_traj, double* w_traj, double* x_final, int32_t* steps,
+                         int32_t* status, double* cost, double* u_norm_sum,
+                         double* max_violation, int32_t* stalled, int64_t* counts,
+                         double* device_seconds);
+
 /* Cumulative counters of a problem handle (SURVEY.md section 5 "tracing"). */
 typedef struct ehm_counters {
     int64_t lp_solves;

@@ -3,6 +3,7 @@
 The reference's closed-loop experiment under its noise model (needs a GPU):
 
     python tools/dv_experiment.py [--n 10000] [--n-implicit 256] [--jobs 1,2,3,4,5] [--seed 0]
+                                  [--implicit-on-device [--implicit-trajectories N]]
 
 lib/post_process.py:553-568: both laws of cwh_z from x0 = 0 for 20 orbits at T_s = 100 s (1 115
 steps, Simulator's time grid), here with NoiseModel.from_mpc (the six terms of
@@ -10,7 +11,9 @@ lib/mpc_library.py:236-255) drawn inside the rollout.  Explicit law: --n noisy t
 implicit law: the first --n-implicit of them, with common random numbers (same seed, same
 trajectory ids).  Per job the delta-v of total_delta_v_usage (sum_t ||u_t||_2, in mm/s): mean,
 median, 5 % and 95 % for both laws, the overconsumption on the common trajectories, and the
-paper's single-run numbers (lib/post_process.py:414-417) beside them.
+paper's single-run numbers (lib/post_process.py:414-417) beside them.  --implicit-on-device runs the
+implicit law's loop on the device (rollout(..., on_device=True)), which makes --implicit-trajectories
+as large as --n affordable (it overrides --n-implicit); the row then also reports the stalled pairs.
 
 Then the throughput of the noisy against the nominal rollout, measured in the same call (1e6
 trajectories x 100 steps from uniform states, applied trajectory-steps per second of kernel time)
@@ -43,7 +46,7 @@ def stats(dv):
                 p5=float(np.percentile(dv, 5)), p95=float(np.percentile(dv, 95)))
 
 
-def experiment(job, n, n_im, seed):
+def experiment(job, n, n_im, seed, on_device=False):
     oracle, flat = cwh_tree(job)
     mpc = oracle.mpc
     T = reference_steps(mpc)
@@ -54,7 +57,8 @@ def experiment(job, n, n_im, seed):
     a = ex.rollout(np.zeros((n, 2)), T, noise=model, seed=seed, record=False)
     t_ex = time.perf_counter() - t0
     t0 = time.perf_counter()
-    b = im.rollout(np.zeros((n_im, 2)), T, noise=model, seed=seed, record=False)
+    b = im.rollout(np.zeros((n_im, 2)), T, noise=model, seed=seed, record=False,
+                   **(dict(on_device=True) if on_device else {}))
     t_im = time.perf_counter() - t0
     dv_ex, dv_im = 1e3 * a.u_norm_sum, 1e3 * b.u_norm_sum
     ok = (a.status[:n_im] == 0) & (b.status == 0)
@@ -64,6 +68,9 @@ def experiment(job, n, n_im, seed):
                              kernel_s=a.seconds, wall_s=t_ex, dv_mm_s=stats(dv_ex)),
                implicit=dict(trajectories=n_im, stopped=int((b.status != 0).sum()),
                              max_violation=float(b.max_violation.max()), wall_s=t_im,
+                             on_device=bool(on_device),
+                             stalled_pairs=getattr(b, 'n_stalled_pairs', None),
+                             stalled_trajectories=(int(b.stalled.sum()) if on_device else None),
                              dv_mm_s=stats(dv_im)),
                common=int(ok.sum()),
                overconsumption_pct=100. * (dv_ex[:n_im][ok].sum() - dv_im[ok].sum())
@@ -100,13 +107,19 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--n', type=int, default=10000)
     ap.add_argument('--n-implicit', type=int, default=256)
+    ap.add_argument('--implicit-on-device', action='store_true')
+    ap.add_argument('--implicit-trajectories', type=int, default=None)
     ap.add_argument('--jobs', default='1,2,3,4,5')
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--rate-n', type=int, default=1000000)
     ap.add_argument('--rate-T', type=int, default=100)
     ap.add_argument('--skip-rates', action='store_true')
     args = ap.parse_args()
-    rows = [experiment(int(j), args.n, args.n_implicit, args.seed)
+    if args.implicit_trajectories is not None:
+        if not args.implicit_on_device:
+            ap.error('--implicit-trajectories goes with --implicit-on-device')
+        args.n_implicit = min(args.implicit_trajectories, args.n)
+    rows = [experiment(int(j), args.n, args.n_implicit, args.seed, args.implicit_on_device)
             for j in args.jobs.split(',') if j]
     if rows:
         print('\ndelta-v [mm/s] over 20 orbits from x0 = 0 (explicit: %d trajectories, implicit: '
