@@ -7,8 +7,17 @@ Objects: ``ehm_capi.hip`` (C-ABI, host orchestration, generation-1 kernels),
 ``ehm_explicit.hip`` and ``ehm_implicit.hip`` (the closed loops around the two laws), one
 instance of ``ehm_k2.hip`` per (column capacity NP, row slots) pair -- the solver keeps a
 row of the normal matrix and the LP's row vectors in registers, so both are compile-time
-sizes -- and the wide kernels ``ehm_k3.hip`` per row capacity.  The objects are compiled
-in parallel and cached under ``lib/obj``.
+sizes --, one instance of ``ehm_kp.hip`` per (decide NP, expand NP, row slots) triple and flow
+-- the persistent frontier kernel of ``ehm_persist.h`` (which ``ehm_k2.hip`` compiles at one
+width) with each of its two LPs at the width that fits it --, the wide kernels ``ehm_k3.hip``
+per row capacity and the LDS-resident wide family ``ehm_k4.hip``.  The objects are compiled in
+parallel and cached under ``lib/obj``.
+
+The instance lists of ``ehm_capi.hip`` are the master copies -- ``EHM_K2_ALL``, ``EHM_K2Q_ALL``,
+``EHM_KP_ALL``, ``EHM_KPM_ALL`` and the ``ehm_k3_api_*`` getters: what it declares there it looks
+up at run time -- and the tuples below mirror them.  An instance named there and not built here
+fails the link; tests/test_host_logic.py checks that the built library holds exactly the getters
+of the tuples here.
 """
 
 import os
@@ -29,22 +38,19 @@ def _headers():
 
 
 HEADERS = _headers()
-# must match EHM_K2_ALL in ehm_capi.hip
 K2_NPS = (8, 12, 16, 20, 24, 28, 32)
 K2_SLOTS = (1, 2, 3, 4)
-# instances with the quadratic block (-DEHM2_QUAD=1); must match EHM_K2Q_ALL in ehm_capi.hip
+# instances with the quadratic block (-DEHM2_QUAD=1)
 K2Q_NPS = (8, 16, 24, 32)
-# persistent frontier kernel at two solver widths (ehm_kp.hip): (decide NP, expand NP, slots);
-# must match EHM_KP_ALL in ehm_capi.hip
+# persistent frontier kernel at two solver widths (ehm_kp.hip): (decide NP, expand NP, slots)
 # (widths = FACTORISED columns: ehm_ipm2.h eliminates the epigraph columns of the z-block)
 KP_INSTANCES = tuple((d, e, sl) for (d, e) in ((12, 8), (16, 8), (16, 12), (20, 12), (20, 16),
                                                 (24, 16), (24, 20), (28, 20), (28, 24), (32, 24),
                                                 (32, 28)) for sl in (2, 3)) + \
     ((16, 12, 4), (28, 20, 4), (32, 24, 4))
-# the same with the midpoint solve first (the default flow; EHM_KPM_ALL in ehm_capi.hip)
+# the same with the midpoint solve first (the default flow)
 KPM_INSTANCES = KP_INSTANCES
-# wide kernels (ehm_k3.hip): row slots per thread, rows <= 256 * slots; must match the
-# ehm_k3_api_* getters in ehm_capi.hip
+# wide kernels (ehm_k3.hip): row slots per thread, rows <= 256 * slots
 K3_RS = (2, 4)
 # the single-width persistent kernel of ehm_k2.hip (quadratic handles, unlisted width pairs) runs
 # the midpoint-first flow, like the ehm_kpm objects
@@ -160,17 +166,6 @@ def _objects():
     return objs
 
 
-def _regenerate_kp():
-    """ehm_kp.hip is derived from k2_persist in ehm_k2.hip (tools/gen_kp.py): keep it in step."""
-    k2 = os.path.join(SRC_DIR, 'ehm_k2.hip')
-    kp = os.path.join(SRC_DIR, 'ehm_kp.hip')
-    gen = os.path.normpath(os.path.join(HERE, '..', 'tools', 'gen_kp.py'))
-    if os.path.exists(gen) and (not os.path.exists(kp) or
-                                os.path.getmtime(kp) < max(os.path.getmtime(k2),
-                                                           os.path.getmtime(gen))):
-        subprocess.check_call([os.environ.get('PYTHON', 'python'), gen])
-
-
 def _stale(obj, src, dep_t):
     return (not os.path.exists(obj) or
             os.path.getmtime(obj) < max(dep_t, os.path.getmtime(src)))
@@ -180,8 +175,6 @@ def is_stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    if not os.path.exists(os.path.join(SRC_DIR, 'ehm_kp.hip')):
-        return True                 # generated (tools/gen_kp.py), not in the repository
     srcs = [os.path.join(SRC_DIR, f)
             for f in ('ehm_capi.hip', 'ehm_k2.hip', 'ehm_k3.hip', 'ehm_k4.hip', 'ehm_kp.hip',
                       'ehm_explicit.hip', 'ehm_implicit.hip')]
@@ -194,7 +187,6 @@ def build(force=False, verbose=False, jobs=None):
     if not force and not is_stale():
         return LIB
     os.makedirs(OBJ_DIR, exist_ok=True)
-    _regenerate_kp()
     hipcc = _hipcc()
     todo = [(o, s, f) for (o, s, f) in _objects() if force or _stale(o, s, _dep_mtime(s))]
 

@@ -153,7 +153,7 @@ struct K2Api {
     void (*vertex)(const K2Launch&, DevProblem, DevTree, const int32_t* nodes, int n_nodes,
                    DevCounters*);
     void (*selftest)(hipStream_t, double* out);
-    // persistent frontier kernel (ehm_k2.hip: k2_persist); null where not compiled (wide)
+    // persistent frontier kernel (ehm_persist.h as k2_persist); null where not compiled (wide)
     void (*persist)(const K2Launch&, DevProblem, DevTree, int32_t* slots, int n_slots,
                     PersistCtl* ctl, int node_cap, DevCounters*, int sign_only, int max_depth,
                     PersistDeal);
@@ -162,7 +162,7 @@ struct K2Api {
     int (*fits)(const DevProblem& P, int lds_budget_bytes);
 };
 
-// The persistent frontier kernel compiled at two solver widths (ehm_kp.hip).
+// The persistent frontier kernel (ehm_persist.h) compiled at two solver widths (ehm_kp.hip).
 struct KpApi {
     int np_decide, np_expand, slots, max_threads;
     hipError_t (*set_lds)(int bytes);

@@ -398,775 +398,11 @@ __global__ __launch_bounds__(EHM_K2_THREADS) void k2_lcss_expand(
 }
 
 
-// ---- persistent frontier kernel ------------------------------------------------------------
-// One launch grows the whole partition: every wavefront pops node ids from a global queue,
-// runs the suboptimality test (lib/worker.py:368-375) and, if the node stays open, at once the
-// split + midpoint solve + child construction (lib/worker.py:403-414, 354-365), allocates the
-// two child records from the node pool and pushes them.  No sweep barriers: subtrees progress
-// independently, the narrow top and bottom levels of the tree overlap with the bulk, and the
-// workgroup's copy of the constant LP block stays in LDS for the whole run.
-//   * queue slot k is written once (-1 = not yet): a consumer that drew a slot ahead of the
-//     tail waits for it (s_sleep) or leaves when `pending` (nodes pushed, not yet completed)
-//     reaches 0.  Producers never wait for consumers, and a waiting wavefront holds nothing
-//     another one needs, so the kernel cannot deadlock whatever the residency of the grid;
-//   * MI355X has one L2 per XCD: child records and structure words are written through to the
-//     device coherence point (agent-scope atomic stores), the wavefront waits for them to
-//     complete, then stores the queue slots; the consumer reads the slot with an agent-scope
-//     atomic load and invalidates its L1 / non-local L2 lines (acquire fence) before reading
-//     the record.  No L2 write-back anywhere;
-//   * node ids follow the allocation order and differ from run to run; the TREE does not
-//     (a node's fate depends on its own record only).  ehm_tree_export relabels to the
-//     breadth-first order of the level-synchronous engine.
-#define EHM_PERSIST_WATCHDOG_TICKS (60LL * 100000000LL)    // 60 s of the 100 MHz wall clock
-#ifndef EHM_PERSIST_MIDFIRST
-#define EHM_PERSIST_MIDFIRST 0
-#endif
-__global__ __launch_bounds__(EHM_K2_THREADS) void k2_persist(
-    DevProblem P, DevTree T, int32_t* slots, int n_slots, PersistCtl* ctl, int node_cap,
-    DevCounters* cnt, int wave_doubles, int sign_only, int max_depth, PersistDeal deal) {
-    K2_PROLOGUE();
-    const int p = P.p, n_u = P.n_u;
-    const int nrec = rec_doubles(p, n_u);
-    load_shared(P, 0, sm, tid, blockDim.x);
-    __syncthreads();
-    const long long t_start = wall_clock64();
-    // statistics are kept per wavefront (in LDS: registers are what this kernel is short of) and
-    // added to the global counters ONCE, when it leaves -- the level-synchronous kernels pay ~8
-    // device atomics per node for them
-    unsigned long long* wst = reinterpret_cast<unsigned long long*>(nb.aug);
-    double* wmargin = nb.aug + 16;
-    enum { W_SOLVES = 0, W_ITERS, W_STALLED, W_ERRORS, W_SLACK, W_SLACK_ITERS, W_CLOSED, W_SPLITS,
-           W_DEPTH, W_TRUNC, W_CERT, W_WIT, W_ROUTED, W_RCLOSED, W_RSPLITS, W_RSOLVES,
-           W_INH = 17, W_MT = 18, W_MTPARK = 19,           // slot 16 is *wmargin
-           W_TQ = 20, W_TMT = 21, W_TMID = 22, W_TSLK = 23, W_NMT = 24,     // DevCounters::prof
-           W_WITT = 25, W_TPRE = 26, W_TPOST = 27, W_REQ = 28 };
-    if (lane0 < 29 && lane0 != 16) wst[lane0] = 0ULL;
-    if (lane0 == 0) *wmargin = 1e300;
-    wsync();
-    int keep = -1;          // the child this wavefront goes on with (see "work first" below)
-    // hot: everything the kept child's visit reads first is still in LDS -- its record in nb.rec,
-    // its vertex gradients at nb.lp + K2_HOT_GRAD, its witness in the stash -- and its depth /
-    // commutation in registers: the visit starts without a single global round trip (the sibling's
-    // consumer pays those; round 3 re-read all of it, four dependent loads per kept child)
-    bool hot = false;
-    int hot_dep = 0, hot_d = 0;
-    const bool keep_child = deal.keep != 0;
-    for (;;) {
-        int id = -1;
-        const bool is_hot = hot && keep >= 0;
-        hot = false;
-        if (keep >= 0) {
-            id = keep;
-            keep = -1;
-        } else if (lane0 == 0) {
-            const int idx = atomicAdd(&ctl->head, 1);
-            if (idx < ((deal.pop_limit > 0 && deal.pop_limit < n_slots) ? deal.pop_limit
-                                                                        : n_slots)) {
-                long long t_q = 0;
-                for (;;) {
-                    id = __hip_atomic_load(&slots[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    if (id >= 0) break;
-                    if (!t_q) t_q = wall_clock64();
-                    if (__hip_atomic_load(&ctl->pending, __ATOMIC_RELAXED,
-                                          __HIP_MEMORY_SCOPE_AGENT) <= 0 ||
-                        __hip_atomic_load(&ctl->abort, __ATOMIC_RELAXED,
-                                          __HIP_MEMORY_SCOPE_AGENT) != 0)
-                        break;
-                    if (wall_clock64() - t_start > EHM_PERSIST_WATCHDOG_TICKS) {
-                        atomicMax(&ctl->abort, 3);
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(64);
-                }
-                if (t_q) wst[W_TQ] += (unsigned long long)(wall_clock64() - t_q);
-            }
-        }
-        id = __builtin_amdgcn_readfirstlane(id);
-        if (id < 0) break;
-        // a node that was put back once (its midpoint was being solved elsewhere) carries a mark
-        const bool came_back = (id & EHM_REQUEUED) != 0;
-        id &= ~EHM_REQUEUED;
-        const long long t_pre = wall_clock64();
-        const int lane = pin(lane0);
-        double* node = nb.rec;
-        double* hgrad = nb.lp + K2_HOT_GRAD;        // vertex gradients of the node, (p+1) p doubles
-        const int ng = (p + 1) * p;
-        int dep = hot_dep;
-        if (!is_hot) {
-            // acquire (L1 / non-local L2 invalidate): the record behind the slot is visible
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            const double* rec = T.rec + (size_t)id * T.rec_stride;
-            // record, gradients, witness and depth are independent loads: one wait for all of them
-            const double g_in = (T.grad && lane < ng) ? T.grad[(size_t)id * ng + lane] : 0.0;
-#if EHM_PERSIST_MIDFIRST
-            const double w_in = (T.wit && sign_only && lane < p + 2)
-                ? T.wit[(size_t)id * (p + 2) + lane] : 0.0;
-#endif
-            dep = T.depth[id];
-            for (int k = lane; k < nrec; k += 64) node[k] = rec[k];
-            if (T.grad) {
-                if (lane < ng) hgrad[lane] = g_in;
-                for (int k = lane + 64; k < ng; k += 64) hgrad[k] = T.grad[(size_t)id * ng + k];
-            }
-#if EHM_PERSIST_MIDFIRST
-            if (T.wit && sign_only && lane < p + 2)
-                nb.rec[(size_t)wave_doubles - k2_stash_doubles(p, n_u) + n_u + p + lane] = w_in;
-#endif
-        }
-        wsync();
-        // ---- suboptimality test --------------------------------------------------------------
-        // the inherited witness first (a dozen instructions): a node it proves open (t* > 0) cannot
-        // be closed by the tangent-plane bound (t* < 0), whose 45 pairs of planes are then skipped
-        bool inh_open = false;
-        double inh_tw = 0.0;
-#if EHM_PERSIST_MIDFIRST
-        if (T.wit && sign_only) {
-            const double* wit_ = nb.rec + (size_t)wave_doubles - k2_stash_doubles(p, n_u) + n_u + p;
-            const double* Vc = node + rec_off_vcost(p);
-            double vbw = 0.0;
-            for (int q = 0; q <= p; ++q) vbw = fma(wit_[1 + q], Vc[q], vbw);
-            const double cw = wit_[0];
-            const double tw = fmin(vbw - cw - P.eps_a, vbw - (1.0 + P.eps_r) * cw);
-            inh_open = tw > EHM_ROUTE_TOL * (1.0 + fabs(vbw));
-            inh_tw = tw;
-        }
-#endif
-        if (T.grad && sign_only && inh_open && deal.check) {
-            // option "check_witness": the witness says open -- the bound must not say closed
-            const double thr = -EHM_ROUTE_TOL * (1.0 + fabs(node[rec_off_vcost(p)]));
-            const double bnd = cut_bound(node, hgrad, p, P.eps_a, P.eps_r, lane, nb.lp, thr);
-            if (bnd < thr && lane == 0) wst[W_ERRORS] += 1;
-            wsync();
-        }
-        if (T.grad && sign_only && !inh_open) {
-            // tangent-plane bound of t* (ehm_dev.h, cut_bound): negative => closed, no LP
-            const double thr = -EHM_ROUTE_TOL * (1.0 + fabs(node[rec_off_vcost(p)]));
-            const double bnd = cut_bound(node, hgrad, p, P.eps_a, P.eps_r, lane, nb.lp, thr);
-            if (bnd < thr) {
-                if (lane == 0) {
-                    const int dep0 = dep;
-                    wst[W_CERT] += 1;
-                    wst[W_CLOSED] += 1;
-                    if (dep0 < deal.depth) wst[W_RCLOSED] += 1;
-                    *wmargin = fmin(*wmargin, -bnd);
-                    if ((unsigned long long)dep0 > wst[W_DEPTH]) wst[W_DEPTH] = (unsigned long long)dep0;
-                    T.tstar[id] = bnd;
-                    // (a kept child's flags are the ones it was created with a moment ago: 2)
-                    if (is_hot) T.flags[id] = 3;
-                    else T.flags[id] |= 1;
-                    atomicSub(&ctl->pending, 1);
-                }
-                wsync();
-                continue;
-            }
-        }
-#if EHM_PERSIST_MIDFIRST
-        // Midpoint first (-DEHM_PERSIST_MIDFIRST=1, how every instance is built since round 2;
-        // validated on the device: identical tree): after the tangent-plane bound has taken out 97 %
-        // of the closed leaves, almost every node that reaches an LP is open and needs its midpoint
-        // solve anyway.  Doing that solve FIRST gives a witness: at theta = mid the interpolated
-        // cost is (V_bi + V_bj)/2 and the optimal cost is the solve's optimum, so
-        //     t_mid = min( Vbar - J_mid - eps_a , Vbar - (1 + eps_r) J_mid ) <= t* ,
-        // and t_mid > 0 proves the node open without its suboptimality-test LP (42 % of the open
-        // nodes of the bench tree, tools/midpoint_certificate.py).  Otherwise the LP decides as
-        // before; a node it closes has paid for a midpoint solve it did not need (3 % of them).
-        const bool can_split = !(max_depth > 0 && dep >= max_depth);
-        double* mid = nb.th;
-        // the last k2_stash_doubles of the wave's LDS: midpoint input, midpoint gradient,
-        // the witness handed on to the children (DevTree::wit)
-        const int st_g = n_u, st_w = n_u + p;       // layout: k2_stash_doubles (ehm_k2.h)
-        double* stash = nb.rec + (size_t)wave_doubles - k2_stash_doubles(p, n_u);
-        double* wit = stash + st_w;
-        bool have_wit = false;
-        int mt_res = MT_NONE;       // table of midpoint optima (ehm_midtable.h)
-        int bi = 0, bj = 1;
-        int its = 0;
-        double Jm = 0.0;
-        int mid_status = 1, mid_iters = 0;
-        bool mid_conv = false;
-        bool open = false;
-        double tst = 0.0, margin = 0.0;
-        bool decided = false;
-        if (T.wit && sign_only) {
-            // inherited witness: the point that proved an ancestor open, if it lies in this node
-            // (loaded with the record, or left in the stash by the parent's visit; evaluated above)
-            if (inh_open) {
-                open = true;
-                decided = true;
-                have_wit = true;
-                tst = inh_tw;
-                margin = inh_tw;
-                if (lane == 0) wst[W_INH] += 1;
-            }
-        }
-        if (can_split) {
-            longest_edge_wave(node, p, lane, bi, bj);
-            if (lane < p) {
-#pragma clang fp contract(off)
-                mid[lane] = (node[bi * p + lane] + node[bj * p + lane]) / 2.0;
-            }
-            wsync();
-            if (T.mt.state) {
-                // the simplices around an edge all ask for this midpoint: solve it once
-                unsigned int mt_i = 0u;
-                int mt_slot = 0;
-                const unsigned long long mt_tg = mt_tag(mid, p, T.mt.mask, &mt_i);
-                if (lane == 0) {
-                    wst[W_TPRE] += (unsigned long long)(wall_clock64() - t_pre);
-                    long long waited = 0;
-                    // A node whose fate is known (inherited witness) needs nothing but this
-                    // optimum: if another wavefront is solving it right now, the node goes back
-                    // into the queue -- once -- and this wavefront takes another one instead of
-                    // sleeping through the solve.  (Not in budgeted launches: their left-over
-                    // must stay the contiguous slice behind the pop limit.)
-                    const bool may_requeue = decided && !came_back && deal.pop_limit <= 0 &&
-                                             id < EHM_REQUEUED;
-                    mt_res = mt_claim(T.mt, mt_tg, mt_i, t_start, EHM_PERSIST_WATCHDOG_TICKS,
-                                      &mt_slot, &waited, may_requeue);
-                    if (mt_res == MT_BUSY) {
-                        const int t = atomicAdd(&ctl->tail, 1);
-                        if (t < n_slots) {
-                            __hip_atomic_store(&slots[t], id | EHM_REQUEUED, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_AGENT);
-                            wst[W_REQ] += 1;
-                        } else {            // no room behind the tail: wait after all
-                            mt_res = mt_claim(T.mt, mt_tg, mt_i, t_start,
-                                              EHM_PERSIST_WATCHDOG_TICKS, &mt_slot, &waited);
-                        }
-                    }
-                    if (waited) {
-                        wst[W_TMT] += (unsigned long long)waited;
-                        wst[W_NMT] += 1;
-                    }
-                }
-                mt_res = __builtin_amdgcn_readfirstlane(mt_res);
-                mt_slot = __builtin_amdgcn_readfirstlane(mt_slot);
-                if (mt_res == MT_BUSY) {    // put back: still pending, somebody else's visit
-                    wsync();
-                    continue;
-                }
-                if (mt_res == MT_HIT) {
-                    bool same = false;
-                    const double ev = mt_read(T.mt, mt_slot, lane, mid, p, &same);
-                    if (!same) {
-                        mt_res = MT_NONE;               // another midpoint with this tag
-                    } else {
-                        // entry layout: ehm_midtable.h
-                        const int word = (int)__shfl(ev, 9);
-                        Jm = __shfl(ev, 8);
-                        mid_status = word & 0xff;
-                        mid_conv = ((word >> 8) & 1) != 0;
-                        mid_iters = 0;                  // no iterations were spent here
-                        if (lane >= 10 && lane < 10 + n_u) stash[lane - 10] = ev;
-                        if (T.grad && lane >= 18 && lane < 18 + p) stash[st_g + lane - 18] = ev;
-                        if (lane == 0) wst[W_MT] += 1;
-                    }
-                }
-                // what the code after the solve needs, parked in LDS: registers are what this
-                // kernel is short of while it solves
-                if (lane == 0) wst[W_MTPARK] = (unsigned long long)mt_res |
-                                               ((unsigned long long)mt_slot << 2);
-            }
-            if (mt_res != MT_HIT)
-            {
-            const long long t_mid = wall_clock64();
-            Wave Wm;
-            IpmResult rm;
-            for (int attempt = 0; attempt < EHM2_ATTEMPTS; ++attempt) {
-                double b[SLOTS];
-                const int ln = pin(lane);
-                assemble_point(S, Wm, nb.lp, mid, false, b, ln, P, 0);
-                rm = ipm_solve(S, Wm, b, ln, false, step_fraction(attempt), T.grad ? nb.F : nullptr);
-                its += rm.iters;
-                if (rm.status == 0) break;
-            }
-#if EHM2_QUAD
-            if (T.grad) quad_grad_add(Wm, P, 0, mid, nb.F, lane);
-#endif
-            Jm = rm.obj;
-            mid_status = rm.status;
-            mid_conv = (rm.status == 0) && (rm.merit <= 1.0);    // not merely "accepted"
-            mid_iters = its;
-            if (lane < n_u) stash[lane] = Wm.xb[lane];
-            if (lane == 0) wst[W_TMID] += (unsigned long long)(wall_clock64() - t_mid);
-            }
-            if (mt_res != MT_HIT && T.grad && lane < p) stash[st_g + lane] = nb.F[lane];
-            wsync();
-            if (T.mt.state) {
-                const unsigned long long park = wst[W_MTPARK];
-                mt_res = (int)(park & 3ull);
-                if (mt_res == MT_OWN) {
-                    unsigned int mt_i = 0u;
-                    const unsigned long long mt_tg = mt_tag(mid, p, T.mt.mask, &mt_i);
-                    mt_publish(T.mt, (int)(park >> 2), mt_tg, lane, mid, p, Jm, mid_status,
-                               mid_conv ? 1 : 0, mid_iters, stash, n_u,
-                               T.grad ? stash + st_g : nullptr);
-                }
-            }
-            if (sign_only && mid_conv && !decided) {
-                const double* Vc = node + rec_off_vcost(p);
-                const double vb = 0.5 * (Vc[bi] + Vc[bj]);
-                const double tw = fmin(vb - Jm - P.eps_a, vb - (1.0 + P.eps_r) * Jm);
-                if (tw > EHM_ROUTE_TOL * (1.0 + fabs(vb))) {
-                    open = true;
-                    decided = true;
-                    tst = tw;
-                    margin = tw;
-                    if (lane == 0) wst[W_WIT] += 1;
-                }
-            }
-        }
-#if !EHM2_QUAD
-        if (!decided && T.mt.state && sign_only) {
-            // The OTHER edges' midpoints.  A neighbour that has bisected one of this simplex's
-            // edges left the optimal cost at that edge's midpoint in the table; like the node's
-            // own midpoint it is a candidate witness -- V*(mid') known, interpolated cost
-            // (V_a + V_b)/2 -- and, unlike it, a point that stays in the interior of an edge of the
-            // children, so they inherit it.  Lane e looks edge e up (read-only, nobody waits).
-            const double* Vc = node + rec_off_vcost(p);
-            double tw_l = -1e300, J_l = 0.0;
-            int ea = 0, eb = 1, slot_l = -1;
-            const int n_edges = (p + 1) * p / 2;
-            // lane e's midpoint: 8 doubles of the wavefront's LP workspace (free between solves)
-            double* em = nb.lp + 8 * (lane < n_edges ? lane : 0);
-            if (lane < n_edges) {
-                int rem = lane;
-                while (rem >= p - ea) { rem -= (p - ea); ++ea; }
-                eb = ea + 1 + rem;
-                if (!(ea == bi && eb == bj)) {
-                    {
-#pragma clang fp contract(off)
-                        for (int k = 0; k < p; ++k) em[k] = (node[ea * p + k] + node[eb * p + k]) / 2.0;
-                    }
-                    unsigned int e_i = 0u;
-                    const unsigned long long e_tg = mt_tag(em, p, T.mt.mask, &e_i);
-                    slot_l = mt_find(T.mt, e_tg, e_i);
-                }
-            }
-            if (__builtin_amdgcn_ballot_w64(slot_l >= 0) != 0ull) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                if (slot_l >= 0) {
-                    const double* e = T.mt.data + (size_t)slot_l * MT_DOUBLES;
-                    bool same = true;
-                    for (int k = 0; k < p; ++k)
-                        same = same && __double_as_longlong(e[k]) == __double_as_longlong(em[k]);
-                    const int word = (int)e[9];
-                    if (same && (word & 0xff) == 0 && ((word >> 8) & 1)) {   // converged optimum
-                        J_l = e[8];
-                        const double vb = 0.5 * (Vc[ea] + Vc[eb]);
-                        const double tw = fmin(vb - J_l - P.eps_a, vb - (1.0 + P.eps_r) * J_l);
-                        if (tw > EHM_ROUTE_TOL * (1.0 + fabs(vb))) tw_l = tw;
-                    }
-                }
-                const unsigned long long won = __builtin_amdgcn_ballot_w64(tw_l > -1e299);
-                if (won != 0ull) {
-                    // first edge (enumeration order) whose midpoint proves the node open
-                    const int src = __builtin_ctzll(won);
-                    const double tw = __shfl(tw_l, src);
-                    const double Jw = __shfl(J_l, src);
-                    const int wa = __shfl(ea, src), wb = __shfl(eb, src);
-                    open = true;
-                    decided = true;
-                    tst = tw;
-                    margin = tw;
-                    if (T.wit) {
-                        if (lane == 0) wit[0] = Jw;
-                        if (lane <= p) wit[1 + lane] = (lane == wa || lane == wb) ? 0.5 : 0.0;
-                        have_wit = true;
-                    }
-                    if (lane == 0) wst[W_WITT] += 1;
-                    wsync();
-                }
-            }
-        }
-#endif
-        if (!decided) {
-            const long long t_slk = wall_clock64();
-            Wave W;
-            IpmResult r;
-            its = 0;
-            for (int attempt = 0; attempt < EHM2_ATTEMPTS; ++attempt) {
-                double b[SLOTS];
-                const int ln = pin(lane);
-                assemble_simplex(S, W, nb, node, node + rec_off_vcost(p), SX_SLACK, P.eps_a, P.eps_r,
-                                 b, ln, P, 0);
-                r = ipm_solve(S, W, b, ln, sign_only != 0, step_fraction(attempt));
-                its += r.iters;
-                if (r.status == 0) break;
-            }
-            tst = -r.obj;
-            open = (tst >= 0.0);
-            margin = r.margin;
-            const int slack_status = r.status;
-#if !EHM2_QUAD
-            if (T.wit && sign_only && open && slack_status == 0) {
-                // this node's own witness: the accepted iterate's parameter (barycentric) and the
-                // cost of its z, raised by the safety amount (EHM_WIT_REL, ehm_dev.h)
-                const int nz = S.n;
-                double cz = 0.0, sb = 0.0;
-                for (int q = 0; q < nz; ++q) cz = fma(S.cv[q], W.xb[zcol(W, S, q)], cz);
-                for (int q = 0; q < p; ++q) sb += W.xb[W.psi0 + q];
-                wsync();
-                if (lane == 0) {
-                    wit[0] = fma(EHM_WIT_REL, margin, cz);
-                    wit[1] = 1.0 - sb;
-                }
-                if (lane < p) wit[2 + lane] = W.xb[W.psi0 + lane];
-                have_wit = true;
-                wsync();
-            }
-#endif
-            if (lane == 0) {
-                wst[W_TSLK] += (unsigned long long)(wall_clock64() - t_slk);
-                wst[W_SOLVES] += 1;
-                if (dep < deal.depth) wst[W_RSOLVES] += 1;
-                wst[W_ITERS] += (unsigned long long)its;
-                wst[W_SLACK] += 1;
-                wst[W_SLACK_ITERS] += (unsigned long long)its;
-                if (slack_status != 0) {
-                    wst[W_STALLED] += 1;
-                    wst[W_ERRORS] += 1;
-                    T.flags[id] |= 8;
-                }
-            }
-        }
-        if (lane == 0) {
-            if (can_split) {        // the midpoint solve was done, whatever became of the node
-                if (mt_res != MT_HIT) {     // ... by this wavefront (else: taken from the table)
-                    wst[W_SOLVES] += 1;
-                    if (dep < deal.depth) wst[W_RSOLVES] += 1;
-                    wst[W_ITERS] += (unsigned long long)mid_iters;
-                }
-                if (mid_status != 0 && open) {
-                    wst[W_STALLED] += 1;
-                    wst[W_ERRORS] += 1;
-                    T.flags[id] |= 16;
-                }
-            }
-            *wmargin = fmin(*wmargin, margin);
-            if (margin < EHM_ROUTE_TOL * (1.0 + fabs(node[rec_off_vcost(p)]))) wst[W_ROUTED] += 1;
-            if ((unsigned long long)dep > wst[W_DEPTH]) wst[W_DEPTH] = (unsigned long long)dep;
-            T.tstar[id] = tst;
-            if (!open) {
-                T.flags[id] |= 1;
-                wst[W_CLOSED] += 1;
-                if (dep < deal.depth) wst[W_RCLOSED] += 1;
-            }
-        }
-        if (!open) {
-            if (lane == 0) atomicSub(&ctl->pending, 1);
-            wsync();
-            continue;
-        }
-        if (!can_split) {
-            if (lane == 0) {
-                wst[W_TRUNC] = 1;
-                atomicSub(&ctl->pending, 1);
-            }
-            wsync();
-            continue;
-        }
-        // ---- children (the midpoint solve is in Jm / stash) --------------------------------------
-        const long long t_post = wall_clock64();
-        // the wavefront goes on with child 1 itself (work first, below) unless the children are
-        // dealt over ranks at this depth: then its record, gradients and witness also stay in LDS
-        const bool fast = keep_child && !(deal.world > 1 && dep + 1 == deal.depth);
-        // the node's own gradients again (the solves have used the workspace they were staged in):
-        // the load is under way while the allocation below makes its round trip
-        const double gv0 = (T.grad && lane < ng) ? T.grad[(size_t)id * ng + lane] : 0.0;
-        const int d = is_hot ? hot_d : T.didx[id];
-        int c0 = 0;
-        if (lane == 0) c0 = atomicAdd(&ctl->n_nodes, 2);
-        c0 = __builtin_amdgcn_readfirstlane(c0);
-        if (c0 + 2 > node_cap) {
-            if (lane == 0) {
-                atomicMax(&ctl->abort, 1);
-                atomicSub(&ctl->pending, 1);
-            }
-            break;
-        }
-        struct { double obj; } r = {Jm};      // the child-record loop below reads r.obj
-        if (T.grad) {       // children's vertex gradients, written through like the records
-            const double* gp_ = T.grad + (size_t)id * ng;
-            double* g0 = T.grad + (size_t)c0 * ng;
-            for (int k = lane; k < ng; k += 64) {
-                const double gv = (k < 64) ? gv0 : gp_[k];
-                const double a0 = (k >= bi * p && k < bi * p + p) ? stash[st_g + k - bi * p] : gv;
-                const double a1 = (k >= bj * p && k < bj * p + p) ? stash[st_g + k - bj * p] : gv;
-                __hip_atomic_store(g0 + k, a0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(g0 + ng + k, a1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (fast) hgrad[k] = a1;
-            }
-        }
-        if (T.wit && lane < p + 2) {
-            // the witness goes to the child that contains it: child 0 (vertex bi -> midpoint) iff
-            // alpha_bj >= alpha_bi; theta_w = 2 a_i mid + (a_j - a_i) v_j + ... there.  The OTHER
-            // child gets the point where the segment from theta_w to the parent's vertex on its
-            // side meets the shared face, with the cost bound (1 - mu) c_w + mu V_vertex (a convex
-            // combination of two feasible decision vectors is feasible, the cost is linear)
-            double* w0 = T.wit + (size_t)c0 * (p + 2);
-            double v0 = 0.0, v1 = 0.0;
-            if (have_wit) {
-                witness_for_children(wit, node + rec_off_vcost(p), bi, bj, lane, v0, v1);
-            }
-            __hip_atomic_store(w0 + lane, v0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(w0 + (p + 2) + lane, v1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            wsync();                        // every lane has read the parent's witness
-            if (fast) wit[lane] = v1;       // child 1's, for its visit by this wavefront
-        }
-        if (lane == 0) {
-            wst[W_SPLITS] += 1;
-            if (dep < deal.depth) wst[W_RSPLITS] += 1;
-        }
-        const double* xmid = stash;
-#else
-        Wave W;
-        IpmResult r;
-        int its = 0;
-        for (int attempt = 0; attempt < EHM2_ATTEMPTS; ++attempt) {
-            double b[SLOTS];
-            const int ln = pin(lane);
-            assemble_simplex(S, W, nb, node, node + rec_off_vcost(p), SX_SLACK, P.eps_a, P.eps_r,
-                             b, ln, P, 0);
-            r = ipm_solve(S, W, b, ln, sign_only != 0, step_fraction(attempt));
-            its += r.iters;
-            if (r.status == 0) break;
-        }
-        r.iters = its;
-        const double tst = -r.obj;
-        const bool open = (tst >= 0.0);
-        if (lane == 0) {
-            wst[W_SOLVES] += 1;
-            if (dep < deal.depth) wst[W_RSOLVES] += 1;
-            wst[W_ITERS] += (unsigned long long)r.iters;
-            wst[W_SLACK] += 1;
-            wst[W_SLACK_ITERS] += (unsigned long long)r.iters;
-            if (r.status != 0) {
-                wst[W_STALLED] += 1;
-                wst[W_ERRORS] += 1;
-                T.flags[id] |= 8;
-            }
-            *wmargin = fmin(*wmargin, r.margin);
-            if (r.margin < EHM_ROUTE_TOL * (1.0 + fabs(node[rec_off_vcost(p)]))) wst[W_ROUTED] += 1;
-            if ((unsigned long long)dep > wst[W_DEPTH]) wst[W_DEPTH] = (unsigned long long)dep;
-            T.tstar[id] = tst;
-            if (!open) {
-                T.flags[id] |= 1;
-                wst[W_CLOSED] += 1;
-                if (dep < deal.depth) wst[W_RCLOSED] += 1;
-            }
-        }
-        if (!open) {
-            if (lane == 0) atomicSub(&ctl->pending, 1);
-            wsync();
-            continue;
-        }
-        if (max_depth > 0 && dep >= max_depth) {
-            if (lane == 0) {
-                wst[W_TRUNC] = 1;
-                atomicSub(&ctl->pending, 1);
-            }
-            wsync();
-            continue;
-        }
-        // ---- split, midpoint solve, children -------------------------------------------------
-        int c0 = 0;
-        if (lane == 0) c0 = atomicAdd(&ctl->n_nodes, 2);
-        c0 = __builtin_amdgcn_readfirstlane(c0);
-        if (c0 + 2 > node_cap) {
-            if (lane == 0) {
-                atomicMax(&ctl->abort, 1);
-                atomicSub(&ctl->pending, 1);
-            }
-            break;
-        }
-        double* mid = nb.th;
-        int bi, bj;
-        longest_edge_wave(node, p, lane, bi, bj);
-        if (lane < p) {
-#pragma clang fp contract(off)
-            mid[lane] = (node[bi * p + lane] + node[bj * p + lane]) / 2.0;
-        }
-        wsync();
-        const int d = T.didx[id];
-        its = 0;
-        for (int attempt = 0; attempt < EHM2_ATTEMPTS; ++attempt) {
-            double b[SLOTS];
-            const int ln = pin(lane);
-            assemble_point(S, W, nb.lp, mid, false, b, ln, P, 0);
-            r = ipm_solve(S, W, b, ln, false, step_fraction(attempt), T.grad ? nb.F : nullptr);
-            its += r.iters;
-            if (r.status == 0) break;
-        }
-        r.iters = its;
-#if EHM2_QUAD
-        if (T.grad) quad_grad_add(W, P, 0, mid, nb.F, lane);
-#endif
-        if (T.grad) {       // children's vertex gradients, written through like the records
-            const int ng = (p + 1) * p;
-            const double* gp_ = T.grad + (size_t)id * ng;
-            double* g0 = T.grad + (size_t)c0 * ng;
-            for (int k = lane; k < ng; k += 64) {
-                const double gv = gp_[k];
-                const double a0 = (k >= bi * p && k < bi * p + p) ? nb.F[k - bi * p] : gv;
-                const double a1 = (k >= bj * p && k < bj * p + p) ? nb.F[k - bj * p] : gv;
-                __hip_atomic_store(g0 + k, a0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(g0 + ng + k, a1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        if (lane == 0) {
-            wst[W_SOLVES] += 1;
-            wst[W_ITERS] += (unsigned long long)r.iters;
-            wst[W_SPLITS] += 1;
-            if (dep < deal.depth) {
-                wst[W_RSOLVES] += 1;
-                wst[W_RSPLITS] += 1;
-            }
-            if (r.status != 0) {
-                wst[W_STALLED] += 1;
-                wst[W_ERRORS] += 1;
-                T.flags[id] |= 16;
-            }
-        }
-        const long long t_post = wall_clock64();
-        const double* xmid = W.xb;
-#endif
-        double* rec0 = T.rec + (size_t)c0 * T.rec_stride;
-        double* rec1 = rec0 + T.rec_stride;
-        const int ov = rec_off_vcost(p), ou = rec_off_vinput(p);
-        for (int k = lane; k < nrec; k += 64) {
-            double v0 = node[k], v1 = node[k];
-            if (k < ov) {
-                if (k >= bi * p && k < bi * p + p) v0 = mid[k - bi * p];
-                if (k >= bj * p && k < bj * p + p) v1 = mid[k - bj * p];
-            } else if (k < ou) {
-                if (k - ov == bi) v0 = r.obj;
-                if (k - ov == bj) v1 = r.obj;
-            } else {
-                const int q = k - ou;
-                if (q >= bi * n_u && q < bi * n_u + n_u) v0 = xmid[q - bi * n_u];
-                if (q >= bj * n_u && q < bj * n_u + n_u) v1 = xmid[q - bj * n_u];
-            }
-            // everything a child's consumer reads or later overwrites is written THROUGH to the
-            // device coherence point (agent-scope atomic stores): visible to the other XCDs
-            // without writing this XCD's whole L2 back (a device-scope release fence would --
-            // measured: 47 GB of write-backs per partition, mostly register spills), and no
-            // dirty copy stays behind that could later clobber the consumer's own writes
-            __hip_atomic_store(rec0 + k, v0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(rec1 + k, v1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#if EHM_PERSIST_MIDFIRST
-            if (fast) node[k] = v1;         // child 1's record, in place (entry k depends on entry k)
-#endif
-        }
-        // sharded launch: the children created at the deal depth go to rank (path code % world)
-        int own0 = 1, own1 = 1;
-        if (lane == 0) {
-            T.left[id] = c0;
-#define EHM_WT(ptr, val) __hip_atomic_store((ptr), (val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-            if (T.code) {
-                const uint32_t pc = T.code[id];
-                const uint32_t code0 = 2u * pc, code1 = 2u * pc + 1u;
-                EHM_WT(&T.code[c0], code0);
-                EHM_WT(&T.code[c0 + 1], code1);
-                if (deal.world > 1 && dep + 1 == deal.depth) {
-                    const uint32_t h0 = deal.mix ? ((code0 * 2654435761u) >> 12) : code0;
-                    const uint32_t h1 = deal.mix ? ((code1 * 2654435761u) >> 12) : code1;
-                    own0 = (int)(h0 % (uint32_t)deal.world) == deal.rank;
-                    own1 = (int)(h1 % (uint32_t)deal.world) == deal.rank;
-                }
-            }
-            EHM_WT(&T.left[c0], -1);
-            EHM_WT(&T.left[c0 + 1], -1);
-            EHM_WT(&T.didx[c0], d);
-            EHM_WT(&T.didx[c0 + 1], d);
-            EHM_WT(&T.depth[c0], dep + 1);
-            EHM_WT(&T.depth[c0 + 1], dep + 1);
-            EHM_WT(&T.flags[c0], (uint8_t)(own0 ? 2 : 6));
-            EHM_WT(&T.flags[c0 + 1], (uint8_t)(own1 ? 2 : 6));
-            EHM_WT(&T.tstar[c0], 0.0);
-            EHM_WT(&T.tstar[c0 + 1], 0.0);
-#undef EHM_WT
-        }
-        // the write-through stores above have completed (s_waitcnt) before the slots go out
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_s_waitcnt(0);
-        int kept = -1;
-        if (lane == 0) {
-            // Work first: the wavefront goes on with ONE of the children itself (its record is
-            // hot, no queue round trip, and the deep chains that end a partition are followed at
-            // once instead of waiting behind the whole frontier at every level); the other child
-            // feeds the queue.  Budgeted launches (pop_limit) queue BOTH children by default
-            // (PersistDeal::keep = 0: persistent_run sets it unless option "budget_keep" is on):
-            // keeping one there was built and measured in round 5 -- the kept chains run depth
-            // first, what the launch leaves behind the pop limit is then made of deep small cells
-            // and the rebalancing rounds move 4x the nodes (38.2 against 33.4 ms for two ranks) --
-            // and stays off; with budget_keep = 1 a kept child never enters the queue, so what the
-            // launch leaves is still the contiguous slice behind the pop limit.
-            const int nown = own0 + own1;
-            int push0 = own0, push1 = own1;
-            if (keep_child) {
-                if (own1) { kept = c0 + 1; push1 = 0; }
-                else if (own0) { kept = c0; push0 = 0; }
-            }
-            const int npush = push0 + push1;
-            const int t = npush ? atomicAdd(&ctl->tail, npush) : 0;
-            if (t + npush <= n_slots) {
-                int at = t;
-                if (push0)
-                    __hip_atomic_store(&slots[at++], c0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (push1)
-                    __hip_atomic_store(&slots[at], c0 + 1, __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-                // -1 (this node) + its children, the queued one and the kept one alike
-                if (nown != 1) atomicAdd(&ctl->pending, nown - 1);
-            } else {
-                kept = -1;
-                atomicMax(&ctl->abort, 1);
-                atomicSub(&ctl->pending, 1);
-            }
-            wst[W_TPOST] += (unsigned long long)(wall_clock64() - t_post);
-        }
-        keep = __builtin_amdgcn_readfirstlane(kept);
-#if EHM_PERSIST_MIDFIRST
-        hot = fast && keep >= 0;
-        hot_dep = dep + 1;
-        hot_d = d;
-#endif
-        wsync();
-    }
-    wsync();
-    if (lane0 == 0) {
-        atomicAdd(&cnt->lp_solves, wst[W_SOLVES]);
-        atomicAdd(&cnt->ipm_iters, wst[W_ITERS]);
-        if (wst[W_STALLED]) atomicAdd(&cnt->stalled, wst[W_STALLED]);
-        if (wst[W_ERRORS]) atomicAdd(&cnt->errors, wst[W_ERRORS]);
-        atomicAdd(&cnt->slack_solves, wst[W_SLACK]);
-        atomicAdd(&cnt->slack_iters, wst[W_SLACK_ITERS]);
-        atomicMin(&cnt->min_margin_bits, (unsigned long long)__double_as_longlong(*wmargin));
-        if (wst[W_CERT]) atomicAdd(&cnt->cert_closed, wst[W_CERT]);
-        if (wst[W_WIT]) atomicAdd(&cnt->wit_open, wst[W_WIT]);
-        if (wst[W_INH]) atomicAdd(&cnt->wit_inherited, wst[W_INH]);
-        if (wst[W_MT]) atomicAdd(&cnt->mid_shared, wst[W_MT]);
-        if (wst[W_WITT]) atomicAdd(&cnt->wit_table, wst[W_WITT]);
-        atomicAdd(&cnt->prof[0], (unsigned long long)(wall_clock64() - t_start));
-        if (wst[W_TQ]) atomicAdd(&cnt->prof[1], wst[W_TQ]);
-        if (wst[W_TMT]) atomicAdd(&cnt->prof[2], wst[W_TMT]);
-        if (wst[W_TMID]) atomicAdd(&cnt->prof[3], wst[W_TMID]);
-        if (wst[W_TSLK]) atomicAdd(&cnt->prof[4], wst[W_TSLK]);
-        if (wst[W_NMT]) atomicAdd(&cnt->prof[5], wst[W_NMT]);
-        if (wst[W_TPRE]) atomicAdd(&cnt->prof[6], wst[W_TPRE]);
-        if (wst[W_TPOST]) atomicAdd(&cnt->prof[7], wst[W_TPOST]);
-        if (wst[W_REQ]) atomicAdd(&cnt->prof[8], wst[W_REQ]);
-        if (wst[W_ROUTED]) atomicAdd(&cnt->routed, wst[W_ROUTED]);
-        atomicAdd(&ctl->closed, wst[W_CLOSED]);
-        atomicAdd(&ctl->splits, wst[W_SPLITS]);
-        if (wst[W_RCLOSED]) atomicAdd(&ctl->repl_closed, wst[W_RCLOSED]);
-        if (wst[W_RSPLITS]) atomicAdd(&ctl->repl_splits, wst[W_RSPLITS]);
-        if (wst[W_RSOLVES]) atomicAdd(&ctl->repl_solves, wst[W_RSOLVES]);
-        atomicMax(&ctl->max_depth_seen, (int)wst[W_DEPTH]);
-        if (wst[W_TRUNC]) atomicMax(&ctl->truncated, 1);
-    }
-}
+// ---- persistent frontier kernel (ehm_persist.h), both solves at this instance's width -------
+namespace kd = EHM2_NS;
+namespace ke = EHM2_NS;
+#define kx_persist k2_persist
+#include "ehm_persist.h"
 
 // ---- vertex solves that seed a node's costs / inputs (lib/oracle.py:416-443) ---------------
 __global__ __launch_bounds__(EHM_K2_THREADS) void k2_vertex_solve(

@@ -2,7 +2,8 @@
 // the quadratic block of the cost, P_theta_delta / simplex problems (what used to be the top of
 // ehm_k2.hip).  NO include guard on purpose: like ehm_ipm2.h it is compiled once per column
 // capacity EHM_NP into its own namespace, and ehm_kp.hip includes it twice -- the persistent
-// frontier kernel solves its suboptimality-test LPs and its midpoint LPs at different widths.
+// frontier kernel (ehm_persist.h) names the instance of its suboptimality-test LPs and the one of
+// its midpoint LPs by two namespace aliases, which there are different widths.
 #include <hip/hip_runtime.h>
 
 #include "ehm_k2.h"

@@ -178,7 +178,7 @@ int ehm_problem_set_option(ehm_problem* prob, const char* name, double value);
  *   EHM_SOLVER=1|2, EHM_DECIDE_FULL=1   at ehm_problem_create, as the options above;
  *   EHM_ENGINE=0|1     overrides ehm_run_opts.engine (1 = persistent frontier kernel);
  *   EHM_NO_KP=1        persistent kernel at one solver width even where a two-width instance
- *                      (ehm_kp.hip) is compiled;
+ *                      (ehm_kp.hip, same kernel source) is compiled;
  *   EHM_NO_CUTS=1      no vertex gradients: every leaf is closed by its suboptimality-test LP
  *                      (the tangent-plane bound is also off under decide_full = 1);
  *   EHM_KEEP_GOING=1   a run whose oracle solves failed returns its tree instead of

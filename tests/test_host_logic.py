@@ -51,6 +51,24 @@ def test_library_exports_every_declared_symbol():
     assert exported - hooks == every, sorted((exported - hooks) ^ every)
 
 
+def test_library_holds_the_kernel_instances_build_lists():
+    """build.py's instance tuples mirror the lists of ehm_capi.hip, which declares the objects'
+    getters (hidden symbols, so one it names and build.py does not build fails the link).  The
+    library must hold exactly the getters of build.py's tuples."""
+    from explicit_hybrid_mpc_amd import build
+    _capi.load()
+    out = subprocess.run(['nm', '--defined-only', _capi.library_path()],
+                         capture_output=True, text=True).stdout
+    found = set(re.findall(r'\b[tT] (ehm_k(?:2|2q|3|p|pm)_api_[0-9_]+)$', out, re.M))
+    want = {'ehm_k2_api_%d_%d' % (n, s) for n in build.K2_NPS for s in build.K2_SLOTS}
+    want |= {'ehm_k2q_api_%d_%d' % (n, s) for n in build.K2Q_NPS for s in build.K2_SLOTS}
+    want |= {'ehm_kp_api_%d_%d_%d' % t for t in build.KP_INSTANCES}
+    want |= {'ehm_kpm_api_%d_%d_%d' % t for t in build.KPM_INSTANCES}
+    want |= {'ehm_k3_api_%d' % r for r in build.K3_RS}
+    assert len(want) == 28 + 16 + 25 + 25 + 2
+    assert found == want, sorted(found ^ want)
+
+
 def test_no_cpu_fallback_without_a_gpu():
     """On a box without a GPU the product path must fail loudly, not compute on the CPU."""
     import torch
