@@ -46,6 +46,9 @@ EXPORTED = [
     'ehm_implicit_create', 'ehm_implicit_destroy', 'ehm_implicit_last_error',
     'ehm_implicit_set_plant', 'ehm_implicit_set_plant_guarded', 'ehm_implicit_set_noise',
     'ehm_implicit_rollout',
+    'ehm_compiled_create', 'ehm_compiled_eval_batch', 'ehm_compiled_info', 'ehm_compiled_export',
+    'ehm_compiled_validate', 'ehm_compiled_import', 'ehm_compiled_destroy',
+    'ehm_compiled_last_error',
 ]
 
 
@@ -271,6 +274,14 @@ def load(build_if_missing=True):
     lib.ehm_implicit_set_noise.argtypes = lib.ehm_explicit_set_noise.argtypes
     lib.ehm_implicit_rollout.argtypes = [vp, i64, i32, vp, vp, vp, i32, ctypes.c_uint64,
                                          ctypes.c_uint64, ctypes.c_double] + [vp] * 16
+    lib.ehm_compiled_last_error.restype = ctypes.c_char_p
+    lib.ehm_compiled_create.argtypes = [vp, vp, ctypes.POINTER(vp), vp]
+    lib.ehm_compiled_eval_batch.argtypes = [vp, i64, vp, vp, vp, vp, vp]
+    lib.ehm_compiled_info.argtypes = [vp, vp]
+    lib.ehm_compiled_export.argtypes = [vp] * 8
+    lib.ehm_compiled_validate.argtypes = [vp] * 8
+    lib.ehm_compiled_import.argtypes = [i32] + [vp] * 8 + [ctypes.POINTER(vp)]
+    lib.ehm_compiled_destroy.argtypes = [vp]
     lib.ehm_tree_info_get.argtypes = [vp, ctypes.POINTER(TreeInfo)]
     lib.ehm_tree_export.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.ehm_host_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(vp)]
@@ -283,7 +294,8 @@ def load(build_if_missing=True):
     for name in EXPORTED:
         fn = getattr(lib, name)
         if name not in ('ehm_last_error', 'ehm_version', 'ehm_stream',
-                        'ehm_explicit_last_error', 'ehm_implicit_last_error'):
+                        'ehm_explicit_last_error', 'ehm_implicit_last_error',
+                        'ehm_compiled_last_error'):
             fn.restype = i32
     lib.ehm_search_last_error.restype = ctypes.c_char_p
     lib.ehm_search_create.argtypes = [i32, i32, i32, ctypes.POINTER(vp)]

@@ -1,0 +1,719 @@
+// The explicit law compiled into a hyperplane tree with affine leaf gains.
+//
+// Every split of a partition tree is a bisection: the two children share a face, so for a state
+// inside the parent "is it in the left child" is the sign of ONE affine function (p + 1 doubles
+// instead of the child's p + p^2 record), and the interpolation of the vertex inputs over a leaf
+// is an affine map u = u_0 + K (x - v_0).  ehm_compiled_create classifies the nodes of an
+// ehm_explicit handle on the device and writes
+//   node     [n_int][NS]   [a (p) | b | (left, right) int32 pair], 64 B (p <= 6) or 128 B; a child
+//                          index >= 0 is an internal node, < 0 is ~leaf.  PLANE node: left iff
+//                          ((0 + a_0 x_0) + .. + a_(p-1) x_(p-1)) + b >= -eps.  TEST node (children
+//                          that are no bisection, the data-less spine of a nested tree): a = +0.0
+//                          everywhere (no plane has a zero normal), b = its row of test_rec; left iff
+//                          the left child's simplex holds x, the reference's rule verbatim.
+//   leaf_rec [n_leaf][LS]  [v_0 (p) | u_0 (n_u) | K (n_u x p)], leaf_node [n_leaf] source node id
+//   test_rec / root_rec    [v_0 | inv(E)] of a test node's left child / of every root
+//   root_entry [n_roots]   a root's index (internal or ~leaf); nbr: the face adjacency of the roots
+// Internal nodes and leaves keep the source order, children come after their parents: a walk's
+// index grows strictly, so no array -- compiled here or imported from a file -- can hold a cycle.
+// One level of the walk is one dependent load (the source evaluator: child pair, then the child's
+// record).  The handle owns copies of all it needs: it outlives its source.
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/ehmpc.h"
+#include "ehm_explicit_view.h"
+#include "ehm_host.h"
+
+#define EHM_CP 8                 // max parameter dimension (EHM_MAX_P)
+#define EHM_C_LOCATE_MIN 128     // as EHM_X_LOCATE_MIN: spines at least this long get the locator
+#define EHM_C_STRICT 1e-9        // as EHM_X_STRICT
+#define EHM_C_STEPS 96           // as EHM_X_STEPS
+#define EHM_C_VERSION 1          // format of the arrays (ehm_compiled_export / _import)
+#define EHM_C_HEADER 12          // int64 entries of the header
+#define EHM_C_EPS 2.220446049250313e-16
+
+namespace {
+
+// doubles per internal record, per leaf record, per [v0 | inv(E)] record
+__host__ __device__ inline int node_stride_of(int p) { return p <= 6 ? 8 : 16; }
+inline int leaf_stride_of(int p, int n_u) { return ((p + n_u + n_u * p + 1) / 2) * 2; }
+inline int side_stride_of(int p) { return ((p + p * p + 1) / 2) * 2; }
+
+struct DevCompiled {
+    const double* node;
+    const double* leaf_rec;
+    const int32_t* leaf_node;
+    const double* test_rec;
+    const double* root_rec;
+    const int32_t* root_entry;
+    int leaf_stride, side_stride, p, n_u, n_roots;
+};
+
+// ---- compile kernels: one thread per source node -------------------------------------------------
+
+// cls[k]: -1 leaf; 0 test node; 1 + j plane node whose split face is the face of the left child
+// opposite its vertex j.  Vertices are compared by value (-0.0 == 0.0).
+__global__ void k_compiled_classify(long long n_nodes, int p, const int2* __restrict__ child,
+                                    const double* __restrict__ vertices,
+                                    int32_t* __restrict__ cls) {
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_nodes) return;
+    const int2 ch = child[k];
+    if (ch.x < 0) {
+        cls[k] = -1;
+        return;
+    }
+    const size_t vs = (size_t)(p + 1) * p;
+    const double* V = vertices + (size_t)k * vs;
+    const double* L = vertices + (size_t)ch.x * vs;
+    const double* R = vertices + (size_t)ch.y * vs;
+    int i = -1, j = -1, nl = 0, nr = 0;
+    for (int v = 0; v <= p; ++v) {
+        bool dl = false, dr = false;
+        for (int c = 0; c < p; ++c) {
+            dl = dl || !(L[v * p + c] == V[v * p + c]);
+            dr = dr || !(R[v * p + c] == V[v * p + c]);
+        }
+        if (dl) {
+            ++nl;
+            i = v;
+        }
+        if (dr) {
+            ++nr;
+            j = v;
+        }
+    }
+    bool plane = nl == 1 && nr == 1 && i != j;
+    if (plane)
+        for (int c = 0; c < p; ++c) plane = plane && (L[i * p + c] == R[j * p + c]);
+    cls[k] = plane ? 1 + j : 0;
+}
+
+struct CompileArgs {
+    long long n_nodes;
+    int p, n_u, rec_stride, node_stride, leaf_stride, side_stride;
+    const int2* child;
+    const double* rec;          // the source's [v0 | inv(E)] records
+    const double* vinput;
+    const int32_t* cls;
+    const int32_t* newid;       // internal index, or ~leaf index
+    const int32_t* test_idx;    // row of test_rec (test nodes)
+    double *node, *leaf_rec, *test_rec;
+    int32_t* leaf_node;
+};
+
+__global__ void k_compiled_write(CompileArgs A) {
+#pragma clang fp contract(off)
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= A.n_nodes) return;
+    const int p = A.p, n_u = A.n_u;
+    const int id = A.newid[k];
+    if (id < 0) {
+        // leaf: u = u_0 + K (x - v_0), K = (U_1..p - u_0)^T inv(E)
+        const int l = ~id;
+        const double* r = A.rec + (size_t)k * A.rec_stride;
+        const double* U = A.vinput + (size_t)k * (p + 1) * n_u;
+        double* out = A.leaf_rec + (size_t)l * A.leaf_stride;
+        for (int c = 0; c < p; ++c) out[c] = r[c];
+        for (int c = 0; c < n_u; ++c) out[p + c] = U[c];
+        for (int c = 0; c < n_u; ++c)
+            for (int q = 0; q < p; ++q) {
+                double s = 0.0;
+                for (int i = 0; i < p; ++i) s += (U[(i + 1) * n_u + c] - U[c]) * r[p + i * p + q];
+                out[p + n_u + c * p + q] = s;
+            }
+        for (int c = p + n_u + n_u * p; c < A.leaf_stride; ++c) out[c] = 0.0;
+        A.leaf_node[l] = (int32_t)k;
+        return;
+    }
+    const int2 ch = A.child[k];
+    double* out = A.node + (size_t)id * A.node_stride;
+    const double* r = A.rec + (size_t)ch.x * A.rec_stride;        // the left child's record
+    const int cls = A.cls[k];
+    for (int c = 0; c < A.node_stride; ++c) out[c] = 0.0;
+    if (cls == 0) {
+        const int t = A.test_idx[k];
+        out[p] = (double)t;
+        double* tr = A.test_rec + (size_t)t * A.side_stride;
+        for (int c = 0; c < p + p * p; ++c) tr[c] = r[c];
+        for (int c = p + p * p; c < A.side_stride; ++c) tr[c] = 0.0;
+    } else {
+        // the weight of x for vertex j of the left child, as a . x + b
+        const int j = cls - 1;
+        double b = (j == 0) ? 1.0 : 0.0;
+        for (int c = 0; c < p; ++c) {
+            double a = 0.0;
+            if (j == 0)
+                for (int q = 0; q < p; ++q) a -= r[p + q * p + c];
+            else
+                a = r[p + (j - 1) * p + c];
+            out[c] = a;
+            b -= a * r[c];
+        }
+        out[p] = b;
+    }
+    int2* cp = reinterpret_cast<int2*>(out + p + 1);
+    *cp = make_int2(A.newid[ch.x], A.newid[ch.y]);
+}
+
+// rows 0..n_roots-1 of the source's records, repacked at the side stride
+__global__ void k_compiled_roots(int n_roots, int p, int rec_stride, int side_stride,
+                                 const double* __restrict__ rec, double* __restrict__ root_rec) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_roots) return;
+    for (int c = 0; c < side_stride; ++c)
+        root_rec[(size_t)k * side_stride + c] = c < p + p * p ? rec[(size_t)k * rec_stride + c] : 0.0;
+}
+
+// ---- evaluation ----------------------------------------------------------------------------------
+
+// The sums of `contains` / `weights` of ehm_explicit.hip (their products fused into the sums, as the
+// compiler fuses them there), written out: a = fma(Minv[q][c], x_c - v0_c, a) from 0.0.
+template <int P>
+__device__ __forceinline__ bool c_contains(const double* __restrict__ r, const double* x) {
+    double d[P];
+#pragma unroll
+    for (int c = 0; c < P; ++c) d[c] = x[c] - r[c];
+    double s = 0.0;
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+        double a = 0.0;
+#pragma unroll
+        for (int c = 0; c < P; ++c) a = fma(r[P + q * P + c], d[c], a);
+        if (!((a >= -EHM_C_EPS) && (a <= 1.0 + EHM_C_EPS))) return false;
+        s += a;
+    }
+    const double a0 = 1.0 - s;
+    return (a0 >= -EHM_C_EPS) && (a0 <= 1.0 + EHM_C_EPS);
+}
+
+// k_explicit_locate on the compiled law's own root records: a visibility walk over the face
+// adjacency, root[q] = found | steps << 20, or -1 (the serial walk decides).
+template <int P>
+__global__ __launch_bounds__(256) void k_compiled_locate(DevCompiled C, long long n,
+                                                         const double* __restrict__ X,
+                                                         const int32_t* __restrict__ nbr,
+                                                         int32_t* __restrict__ root) {
+#pragma clang fp contract(off)
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    double x[P];
+#pragma unroll
+    for (int c = 0; c < P; ++c) x[c] = X[q * P + c];
+    int k = (int)(q % C.n_roots);
+    int found = -1, steps = 0;
+    for (int step = 0; step < EHM_C_STEPS; ++step) {
+        ++steps;
+        const double* r = C.root_rec + (size_t)k * C.side_stride;
+        double d[P];
+#pragma unroll
+        for (int c = 0; c < P; ++c) d[c] = x[c] - r[c];
+        double alpha[P], s = 0.0;
+#pragma unroll
+        for (int i = 0; i < P; ++i) {
+            double a = 0.0;
+#pragma unroll
+            for (int c = 0; c < P; ++c) a = fma(r[P + i * P + c], d[c], a);
+            alpha[i] = a;
+            s += a;
+        }
+        double lo = 1.0 - s;
+        int at = 0;
+#pragma unroll
+        for (int i = 0; i < P; ++i)
+            if (alpha[i] < lo) {
+                lo = alpha[i];
+                at = i + 1;
+            }
+        if (lo > EHM_C_STRICT) {
+            found = k;
+            break;
+        }
+        if (lo >= -EHM_C_STRICT) break;
+        const int k2 = nbr[(size_t)k * (P + 1) + at];
+        if (k2 < 0) break;
+        k = k2;
+    }
+    root[q] = (found < 0) ? -1 : (found | (steps << 20));
+}
+
+template <int P>
+__global__ __launch_bounds__(256) void k_compiled_eval(DevCompiled C, long long n,
+                                                       const double* __restrict__ X,
+                                                       double* __restrict__ U,
+                                                       int32_t* __restrict__ leaf,
+                                                       int32_t* __restrict__ depth_out,
+                                                       const int32_t* __restrict__ root) {
+#pragma clang fp contract(off)
+    constexpr int NS = P <= 6 ? 8 : 16;         // node_stride_of(P)
+    constexpr int NL = (P + 3) / 2;             // 16-byte loads that cover [a | b | children]
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    double x[P];
+#pragma unroll
+    for (int c = 0; c < P; ++c) x[c] = X[q * P + c];
+    // roots: first root that contains x, the last one without a test
+    int kr = C.n_roots - 1, visited = 0;
+    if (root && root[q] >= 0) {
+        kr = root[q] & 0xfffff;
+        visited = root[q] >> 20;
+    } else {
+        for (int r = 0; r + 1 < C.n_roots; ++r) {
+            ++visited;
+            if (c_contains<P>(C.root_rec + (size_t)r * C.side_stride, x)) {
+                kr = r;
+                break;
+            }
+        }
+    }
+    int k = C.root_entry[kr];
+    // the walk: one record per level, plane and children together
+    while (k >= 0) {
+        const double2* nd = reinterpret_cast<const double2*>(C.node + (size_t)k * NS);
+        double r[2 * NL];
+#pragma unroll
+        for (int i = 0; i < NL; ++i) {
+            const double2 t = nd[i];
+            r[2 * i] = t.x;
+            r[2 * i + 1] = t.y;
+        }
+        ++visited;
+        const long long ch = __double_as_longlong(r[P + 1]);
+        long long bits = 0;
+        double s = 0.0;
+#pragma unroll
+        for (int c = 0; c < P; ++c) {
+            bits |= __double_as_longlong(r[c]);
+            s = s + r[c] * x[c];
+        }
+        s = s + r[P];
+        bool go_left = s >= -EHM_C_EPS;
+        if (bits == 0)      // test node: the reference's containment test of the left child
+            go_left = c_contains<P>(C.test_rec + (size_t)(int)r[P] * C.side_stride, x);
+        k = go_left ? (int)(ch & 0xffffffffll) : (int)(ch >> 32);
+    }
+    const int l = ~k;
+    const double* lr = C.leaf_rec + (size_t)l * C.leaf_stride;
+    const double2* lv = reinterpret_cast<const double2*>(lr);
+    double d[P];
+#pragma unroll
+    for (int c = 0; c + 1 < P; c += 2) {
+        const double2 t = lv[c / 2];
+        d[c] = x[c] - t.x;
+        d[c + 1] = x[c + 1] - t.y;
+    }
+    if (P % 2) d[P - 1] = x[P - 1] - lr[P - 1];
+    const int n_u = C.n_u;
+    const double* Kc = lr + P + n_u;
+    for (int c = 0; c < n_u; ++c) {
+        double t = 0.0;
+#pragma unroll
+        for (int i = 0; i < P; ++i) t = t + Kc[c * P + i] * d[i];
+        U[q * n_u + c] = lr[P + c] + t;
+    }
+    if (leaf) leaf[q] = C.leaf_node[l];
+    if (depth_out) depth_out[q] = visited;
+}
+
+typedef void (*locate_fn)(DevCompiled, long long, const double*, const int32_t*, int32_t*);
+typedef void (*eval_fn)(DevCompiled, long long, const double*, double*, int32_t*, int32_t*,
+                        const int32_t*);
+const locate_fn k_locate_table[EHM_CP] = {
+    &k_compiled_locate<1>, &k_compiled_locate<2>, &k_compiled_locate<3>, &k_compiled_locate<4>,
+    &k_compiled_locate<5>, &k_compiled_locate<6>, &k_compiled_locate<7>, &k_compiled_locate<8>};
+const eval_fn k_eval_table[EHM_CP] = {
+    &k_compiled_eval<1>, &k_compiled_eval<2>, &k_compiled_eval<3>, &k_compiled_eval<4>,
+    &k_compiled_eval<5>, &k_compiled_eval<6>, &k_compiled_eval<7>, &k_compiled_eval<8>};
+
+bool locate_off() {
+    static const bool off = [] {
+        const char* e = getenv("EHM_EXPLICIT_LOCATE");
+        return e && atoi(e) == 0;
+    }();
+    return off;
+}
+
+thread_local std::string c_err;
+int cfail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    c_err = buf;
+    return code;
+}
+
+#define C_TRY(expr)                                                                        \
+    do {                                                                                   \
+        hipError_t e_ = (expr);                                                            \
+        if (e_ != hipSuccess)                                                              \
+            return cfail(EHM_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
+    } while (0)
+
+// header of the arrays: [version, p, n_u, n_roots, n_int, n_leaf, n_test, node_stride,
+// leaf_stride, side_stride, has_nbr, n_source_nodes]
+enum { H_VERSION, H_P, H_NU, H_ROOTS, H_INT, H_LEAF, H_TEST, H_NS, H_LS, H_SS, H_NBR, H_SRC };
+
+bool all_finite(const double* a, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(a[i])) return false;
+    return true;
+}
+
+bool entry_ok(int64_t c, int64_t n_int, int64_t n_leaf) {
+    return c >= 0 ? c < n_int : ~c < n_leaf;
+}
+
+// A file is untrusted input: every index the kernels follow is checked here.
+int validate(const int64_t* h, const double* node, const double* leaf_rec,
+             const int32_t* leaf_node, const double* test_rec, const double* root_rec,
+             const int32_t* root_entry, const int32_t* nbr) {
+    if (!h) return cfail(EHM_E_INVALID, "compiled law: no header");
+    if (h[H_VERSION] != EHM_C_VERSION)
+        return cfail(EHM_E_INVALID, "compiled law: format version %lld (this library reads %d)",
+                     (long long)h[H_VERSION], EHM_C_VERSION);
+    const int64_t p = h[H_P], n_u = h[H_NU], n_roots = h[H_ROOTS], n_int = h[H_INT],
+                  n_leaf = h[H_LEAF], n_test = h[H_TEST];
+    if (p < 1 || p > EHM_CP || n_u < 1 || n_u > (1 << 20))
+        return cfail(EHM_E_INVALID, "compiled law: p = %lld (1..%d), n_u = %lld", (long long)p,
+                     EHM_CP, (long long)n_u);
+    const int64_t lim = (int64_t)1 << 31;
+    if (n_roots < 1 || n_int < 0 || n_leaf < 1 || n_test < 0 || n_test > n_int ||
+        n_int >= lim || n_leaf >= lim || n_roots > n_int + n_leaf || h[H_SRC] < n_leaf ||
+        h[H_SRC] >= lim)
+        return cfail(EHM_E_INVALID, "compiled law: bad counts");
+    const int ns = node_stride_of((int)p), ls = leaf_stride_of((int)p, (int)n_u),
+              ss = side_stride_of((int)p);
+    if (h[H_NS] != ns || h[H_LS] != ls || h[H_SS] != ss)
+        return cfail(EHM_E_INVALID, "compiled law: record strides %lld / %lld / %lld, not "
+                     "%d / %d / %d", (long long)h[H_NS], (long long)h[H_LS], (long long)h[H_SS],
+                     ns, ls, ss);
+    if (h[H_NBR] != 0 && h[H_NBR] != 1)
+        return cfail(EHM_E_INVALID, "compiled law: bad adjacency flag");
+    if (h[H_NBR] && (n_roots < EHM_C_LOCATE_MIN || n_roots >= (1 << 20)))
+        return cfail(EHM_E_INVALID, "compiled law: an adjacency table with %lld roots",
+                     (long long)n_roots);
+    if ((n_int && !node) || !leaf_rec || !leaf_node || (n_test && !test_rec) || !root_rec ||
+        !root_entry || (h[H_NBR] && !nbr))
+        return cfail(EHM_E_INVALID, "compiled law: an array is missing");
+    for (int64_t k = 0; k < n_int; ++k) {
+        const double* r = node + (size_t)k * ns;
+        if (!all_finite(r, (size_t)p + 1))
+            return cfail(EHM_E_INVALID, "compiled law: node %lld is not finite", (long long)k);
+        int32_t ch[2];
+        std::memcpy(ch, r + p + 1, sizeof ch);
+        for (int s = 0; s < 2; ++s)
+            if (!entry_ok(ch[s], n_int, n_leaf) || (ch[s] >= 0 && ch[s] <= k))
+                return cfail(EHM_E_INVALID, "compiled law: node %lld has child %d (children "
+                             "come after their parents)", (long long)k, (int)ch[s]);
+        bool zero = true, bits = true;
+        for (int c = 0; c < p; ++c) {
+            zero = zero && r[c] == 0.0;
+            bits = bits && !std::signbit(r[c]);
+        }
+        if (zero && !(bits && r[p] >= 0.0 && r[p] < (double)n_test && r[p] == std::floor(r[p])))
+            return cfail(EHM_E_INVALID, "compiled law: node %lld has a zero normal and names no "
+                         "test record", (long long)k);
+    }
+    if (!all_finite(leaf_rec, (size_t)n_leaf * ls) || (n_test && !all_finite(test_rec, (size_t)n_test * ss)) ||
+        !all_finite(root_rec, (size_t)n_roots * ss))
+        return cfail(EHM_E_INVALID, "compiled law: a record is not finite");
+    for (int64_t l = 0; l < n_leaf; ++l)
+        if (leaf_node[l] < 0 || leaf_node[l] >= h[H_SRC])
+            return cfail(EHM_E_INVALID, "compiled law: leaf %lld names node %d of %lld",
+                         (long long)l, (int)leaf_node[l], (long long)h[H_SRC]);
+    for (int64_t r = 0; r < n_roots; ++r)
+        if (!entry_ok(root_entry[r], n_int, n_leaf))
+            return cfail(EHM_E_INVALID, "compiled law: root %lld enters at %d", (long long)r,
+                         (int)root_entry[r]);
+    if (h[H_NBR])
+        for (int64_t i = 0; i < n_roots * (p + 1); ++i)
+            if (nbr[i] < -1 || nbr[i] >= n_roots)
+                return cfail(EHM_E_INVALID, "compiled law: adjacency entry %lld is %d",
+                             (long long)i, (int)nbr[i]);
+    return EHM_OK;
+}
+
+}  // namespace
+
+struct ehm_compiled {
+    int device = 0;
+    DevCompiled d{};
+    int64_t h[EHM_C_HEADER] = {};
+    int64_t source_bytes = 0;
+    DevBuf node, leaf_rec, leaf_node, test_rec, root_rec, root_entry, nbr;
+    DevBuf x, u, leaf, depth, root;         // ehm_compiled_eval_batch, cap queries
+    size_t cap = 0;
+    Stream stream;
+
+    size_t node_bytes() const { return (size_t)h[H_INT] * h[H_NS] * sizeof(double); }
+    size_t leaf_bytes() const { return (size_t)h[H_LEAF] * h[H_LS] * sizeof(double); }
+    size_t leaf_node_bytes() const { return (size_t)h[H_LEAF] * sizeof(int32_t); }
+    size_t test_bytes() const { return (size_t)h[H_TEST] * h[H_SS] * sizeof(double); }
+    size_t root_bytes() const { return (size_t)h[H_ROOTS] * h[H_SS] * sizeof(double); }
+    size_t entry_bytes() const { return (size_t)h[H_ROOTS] * sizeof(int32_t); }
+    size_t nbr_bytes() const {
+        return h[H_NBR] ? (size_t)h[H_ROOTS] * (h[H_P] + 1) * sizeof(int32_t) : 0;
+    }
+    size_t bytes() const {
+        return node_bytes() + leaf_bytes() + leaf_node_bytes() + test_bytes() + root_bytes() +
+               entry_bytes() + nbr_bytes();
+    }
+    void bind() {
+        d.node = node.as<const double>();
+        d.leaf_rec = leaf_rec.as<const double>();
+        d.leaf_node = leaf_node.as<const int32_t>();
+        d.test_rec = test_rec.as<const double>();
+        d.root_rec = root_rec.as<const double>();
+        d.root_entry = root_entry.as<const int32_t>();
+        d.leaf_stride = (int)h[H_LS];
+        d.side_stride = (int)h[H_SS];
+        d.p = (int)h[H_P];
+        d.n_u = (int)h[H_NU];
+        d.n_roots = (int)h[H_ROOTS];
+    }
+};
+
+extern "C" {
+
+const char* ehm_compiled_last_error(void) { return c_err.c_str(); }
+
+int ehm_compiled_destroy(ehm_compiled* C) {
+    if (!C) return EHM_OK;
+    (void)hipSetDevice(C->device);
+    delete C;
+    return EHM_OK;
+}
+
+int ehm_compiled_create(ehm_explicit* src, const double* vertices, ehm_compiled** out,
+                        double* compile_seconds) {
+    if (!src || !vertices || !out) return cfail(EHM_E_INVALID, "compile: bad argument");
+    *out = nullptr;
+    ehm_explicit_view v{};
+    ehm_explicit_get_view(src, &v);
+    const int p = v.p, n_u = v.n_u;
+    const int64_t n = v.n_nodes;
+    if (n >= ((int64_t)1 << 31)) return cfail(EHM_E_INVALID, "compile: %lld nodes", (long long)n);
+    std::unique_ptr<ehm_compiled, int (*)(ehm_compiled*)> C(new ehm_compiled(),
+                                                            ehm_compiled_destroy);
+    C->device = v.device;
+    C_TRY(hipSetDevice(v.device));
+    C_TRY(C->stream.create());
+    const auto t0 = std::chrono::steady_clock::now();
+    // the numbering (host: a prefix count over the child pairs): internal nodes and leaves in
+    // source order
+    std::vector<int2> ch((size_t)n);
+    C_TRY(hipMemcpy(ch.data(), v.child, ch.size() * sizeof(int2), hipMemcpyDeviceToHost));
+    std::vector<int32_t> newid((size_t)n);
+    int64_t n_int = 0, n_leaf = 0;
+    for (int64_t k = 0; k < n; ++k) {
+        const int2 c = ch[(size_t)k];
+        if (c.x < 0) {
+            newid[(size_t)k] = ~(int32_t)n_leaf++;
+            continue;
+        }
+        if (c.x <= k || c.y <= k || c.x >= n || c.y >= n)
+            return cfail(EHM_E_INVALID, "compile: node %lld has children %d, %d (a compiled law "
+                         "needs children after their parents)", (long long)k, c.x, c.y);
+        newid[(size_t)k] = (int32_t)n_int++;
+    }
+    const int ns = node_stride_of(p), ls = leaf_stride_of(p, n_u), ss = side_stride_of(p);
+    DevBuf d_vert, d_cls, d_newid, d_tidx;
+    C_TRY(d_vert.upload(vertices, (size_t)n * (p + 1) * p * sizeof(double)));
+    C_TRY(d_cls.alloc((size_t)n * sizeof(int32_t)));
+    C_TRY(d_newid.upload(newid.data(), newid.size() * sizeof(int32_t)));
+    const dim3 grid((unsigned)((n + 127) / 128)), block(128);
+    hipLaunchKernelGGL(k_compiled_classify, grid, block, 0, C->stream, (long long)n, p, v.child,
+                       d_vert.as<const double>(), d_cls.as<int32_t>());
+    C_TRY(hipGetLastError());
+    std::vector<int32_t> cls((size_t)n), tidx((size_t)n, -1);
+    C_TRY(hipMemcpyAsync(cls.data(), d_cls.ptr, cls.size() * sizeof(int32_t),
+                         hipMemcpyDeviceToHost, C->stream));
+    C_TRY(hipStreamSynchronize(C->stream));
+    d_vert.reset();             // the vertices were needed for the classification only
+    int64_t n_test = 0;
+    for (int64_t k = 0; k < n; ++k)
+        if (cls[(size_t)k] == 0) tidx[(size_t)k] = (int32_t)n_test++;
+    C_TRY(d_tidx.upload(tidx.data(), tidx.size() * sizeof(int32_t)));
+    int64_t* h = C->h;
+    h[H_VERSION] = EHM_C_VERSION;
+    h[H_P] = p;
+    h[H_NU] = n_u;
+    h[H_ROOTS] = v.n_roots;
+    h[H_INT] = n_int;
+    h[H_LEAF] = n_leaf;
+    h[H_TEST] = n_test;
+    h[H_NS] = ns;
+    h[H_LS] = ls;
+    h[H_SS] = ss;
+    h[H_NBR] = v.nbr ? 1 : 0;
+    h[H_SRC] = n;
+    C_TRY(C->node.alloc(C->node_bytes()));
+    C_TRY(C->leaf_rec.alloc(C->leaf_bytes()));
+    C_TRY(C->leaf_node.alloc(C->leaf_node_bytes()));
+    C_TRY(C->test_rec.alloc(C->test_bytes()));
+    C_TRY(C->root_rec.alloc(C->root_bytes()));
+    C_TRY(C->root_entry.upload(newid.data(), C->entry_bytes()));
+    if (v.nbr) {
+        C_TRY(C->nbr.alloc(C->nbr_bytes()));
+        C_TRY(hipMemcpyAsync(C->nbr.ptr, v.nbr, C->nbr_bytes(), hipMemcpyDeviceToDevice,
+                             C->stream));
+    }
+    CompileArgs A{};
+    A.n_nodes = n;
+    A.p = p;
+    A.n_u = n_u;
+    A.rec_stride = v.rec_stride;
+    A.node_stride = ns;
+    A.leaf_stride = ls;
+    A.side_stride = ss;
+    A.child = v.child;
+    A.rec = v.rec;
+    A.vinput = v.vinput;
+    A.cls = d_cls.as<const int32_t>();
+    A.newid = d_newid.as<const int32_t>();
+    A.test_idx = d_tidx.as<const int32_t>();
+    A.node = C->node.as<double>();
+    A.leaf_rec = C->leaf_rec.as<double>();
+    A.test_rec = C->test_rec.as<double>();
+    A.leaf_node = C->leaf_node.as<int32_t>();
+    hipLaunchKernelGGL(k_compiled_write, grid, block, 0, C->stream, A);
+    hipLaunchKernelGGL(k_compiled_roots, dim3((unsigned)((v.n_roots + 127) / 128)), block, 0,
+                       C->stream, v.n_roots, p, v.rec_stride, ss, v.rec,
+                       C->root_rec.as<double>());
+    C_TRY(hipGetLastError());
+    C_TRY(hipStreamSynchronize(C->stream));
+    if (compile_seconds)
+        *compile_seconds =
+            std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    C->source_bytes = n * ((int64_t)v.rec_stride * 8 + 8 + (int64_t)(p + 1) * n_u * 8) +
+                      (int64_t)C->nbr_bytes();
+    C->bind();
+    *out = C.release();
+    return EHM_OK;
+}
+
+int ehm_compiled_validate(const int64_t* header, const double* node, const double* leaf_rec,
+                          const int32_t* leaf_node, const double* test_rec,
+                          const double* root_rec, const int32_t* root_entry,
+                          const int32_t* nbr) {
+    return validate(header, node, leaf_rec, leaf_node, test_rec, root_rec, root_entry, nbr);
+}
+
+int ehm_compiled_import(int device, const int64_t* header, const double* node,
+                        const double* leaf_rec, const int32_t* leaf_node, const double* test_rec,
+                        const double* root_rec, const int32_t* root_entry, const int32_t* nbr,
+                        ehm_compiled** out) {
+    if (!out) return cfail(EHM_E_INVALID, "import: bad argument");
+    *out = nullptr;
+    const int rc = validate(header, node, leaf_rec, leaf_node, test_rec, root_rec, root_entry, nbr);
+    if (rc != EHM_OK) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+        return cfail(EHM_E_NO_DEVICE, "no HIP device %d (libehmpc has no CPU fallback)", device);
+    std::unique_ptr<ehm_compiled, int (*)(ehm_compiled*)> C(new ehm_compiled(),
+                                                            ehm_compiled_destroy);
+    C->device = device;
+    std::memcpy(C->h, header, sizeof C->h);
+    C_TRY(hipSetDevice(device));
+    C_TRY(C->stream.create());
+    C_TRY(C->node.upload(node, C->node_bytes()));
+    C_TRY(C->leaf_rec.upload(leaf_rec, C->leaf_bytes()));
+    C_TRY(C->leaf_node.upload(leaf_node, C->leaf_node_bytes()));
+    C_TRY(C->test_rec.upload(test_rec, C->test_bytes()));
+    C_TRY(C->root_rec.upload(root_rec, C->root_bytes()));
+    C_TRY(C->root_entry.upload(root_entry, C->entry_bytes()));
+    if (header[H_NBR]) C_TRY(C->nbr.upload(nbr, C->nbr_bytes()));
+    C->bind();
+    *out = C.release();
+    return EHM_OK;
+}
+
+int ehm_compiled_info(const ehm_compiled* C, int64_t* info) {
+    if (!C || !info) return cfail(EHM_E_INVALID, "info: bad argument");
+    for (int i = 0; i < EHM_C_HEADER; ++i) info[i] = C->h[i];
+    info[EHM_C_HEADER] = (int64_t)C->bytes();
+    info[EHM_C_HEADER + 1] = C->source_bytes;
+    return EHM_OK;
+}
+
+int ehm_compiled_export(ehm_compiled* C, double* node, double* leaf_rec, int32_t* leaf_node,
+                        double* test_rec, double* root_rec, int32_t* root_entry, int32_t* nbr) {
+    if (!C) return cfail(EHM_E_INVALID, "export: bad argument");
+    C_TRY(hipSetDevice(C->device));
+    struct {
+        void* host;
+        const DevBuf* buf;
+        size_t bytes;
+    } parts[] = {{node, &C->node, C->node_bytes()},
+                 {leaf_rec, &C->leaf_rec, C->leaf_bytes()},
+                 {leaf_node, &C->leaf_node, C->leaf_node_bytes()},
+                 {test_rec, &C->test_rec, C->test_bytes()},
+                 {root_rec, &C->root_rec, C->root_bytes()},
+                 {root_entry, &C->root_entry, C->entry_bytes()},
+                 {nbr, &C->nbr, C->nbr_bytes()}};
+    for (const auto& part : parts)
+        if (part.host && part.bytes)
+            C_TRY(hipMemcpy(part.host, part.buf->ptr, part.bytes, hipMemcpyDeviceToHost));
+    return EHM_OK;
+}
+
+int ehm_compiled_eval_batch(ehm_compiled* C, int64_t n, const double* x, double* u,
+                            int32_t* leaf, int32_t* depth, double* kernel_seconds) {
+    if (!C || n < 0 || (n > 0 && (!x || !u))) return cfail(EHM_E_INVALID, "eval: bad argument");
+    if (kernel_seconds) *kernel_seconds = 0.0;
+    if (n == 0) return EHM_OK;
+    C_TRY(hipSetDevice(C->device));
+    const int p = C->d.p, n_u = C->d.n_u;
+    if ((size_t)n > C->cap) {
+        for (DevBuf* b : {&C->x, &C->u, &C->leaf, &C->depth, &C->root}) b->reset();
+        C->cap = 0;
+        if (C->x.alloc((size_t)n * p * sizeof(double)) != hipSuccess ||
+            C->u.alloc((size_t)n * n_u * sizeof(double)) != hipSuccess ||
+            C->leaf.alloc((size_t)n * sizeof(int32_t)) != hipSuccess ||
+            C->depth.alloc((size_t)n * sizeof(int32_t)) != hipSuccess ||
+            C->root.alloc((size_t)n * sizeof(int32_t)) != hipSuccess)
+            return cfail(EHM_E_HIP, "out of device memory for %lld queries", (long long)n);
+        C->cap = (size_t)n;
+    }
+    EventPair ev;
+    C_TRY(hipMemcpyAsync(C->x.ptr, x, (size_t)n * p * sizeof(double), hipMemcpyHostToDevice,
+                         C->stream));
+    (void)hipEventRecord(ev.e0, C->stream);
+    const bool locate = C->nbr && !locate_off();
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (locate)
+        hipLaunchKernelGGL(k_locate_table[p - 1], grid, block, 0, C->stream, C->d, (long long)n,
+                           C->x.as<const double>(), C->nbr.as<const int32_t>(),
+                           C->root.as<int32_t>());
+    hipLaunchKernelGGL(k_eval_table[p - 1], grid, block, 0, C->stream, C->d, (long long)n,
+                       C->x.as<const double>(), C->u.as<double>(), C->leaf.as<int32_t>(),
+                       C->depth.as<int32_t>(),
+                       locate ? C->root.as<const int32_t>() : (const int32_t*)nullptr);
+    (void)hipEventRecord(ev.e1, C->stream);
+    C_TRY(hipGetLastError());
+    C_TRY(hipMemcpyAsync(u, C->u.ptr, (size_t)n * n_u * sizeof(double), hipMemcpyDeviceToHost,
+                         C->stream));
+    if (leaf)
+        C_TRY(hipMemcpyAsync(leaf, C->leaf.ptr, (size_t)n * sizeof(int32_t),
+                             hipMemcpyDeviceToHost, C->stream));
+    if (depth)
+        C_TRY(hipMemcpyAsync(depth, C->depth.ptr, (size_t)n * sizeof(int32_t),
+                             hipMemcpyDeviceToHost, C->stream));
+    C_TRY(hipStreamSynchronize(C->stream));
+    ev.seconds(kernel_seconds);
+    return EHM_OK;
+}
+
+}  // extern "C"

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/ehmpc.h"
+#include "ehm_explicit_view.h"
 #include "ehm_host.h"
 #include "ehm_philox.h"
 #include "ehm_rollout_dev.h"
@@ -663,6 +664,13 @@ struct ehm_explicit {
     size_t cap = 0;
     Stream stream;
 };
+
+// what ehm_compiled_create reads of a handle (ehm_explicit_view.h)
+void ehm_explicit_get_view(const ehm_explicit* E, ehm_explicit_view* out) {
+    *out = ehm_explicit_view{E->device, E->d.rec, E->d.child, E->d.vinput,
+                             E->nbr.as<const int32_t>(), E->d.rec_stride, E->d.p, E->d.n_u,
+                             E->d.n_roots, E->d.n_nodes};
+}
 
 extern "C" {
 

@@ -169,6 +169,14 @@ class ExplicitMPC:
                                              ptr(left), ptr(right), ptr(vertices), ptr(vinput),
                                              ctypes.byref(self._handle)))
 
+    def compile(self):
+        """The law as a ``compiled.CompiledLaw``: one hyperplane per internal node, one affine map
+        per leaf, compiled on the device.  It holds its own arrays and outlives this object."""
+        from .compiled import CompiledLaw
+        vertices = self.tree.vertices if isinstance(self.tree, FlatTree) else \
+            flatten_tree(self.tree)[0]
+        return CompiledLaw.compile(self, vertices)
+
     def close(self):
         if getattr(self, '_handle', None):
             self._lib.ehm_explicit_destroy(self._handle)

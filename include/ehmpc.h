@@ -473,6 +473,54 @@ int ehm_explicit_eval_batch(ehm_explicit* ex, int64_t n, const double* x, double
 int ehm_explicit_destroy(ehm_explicit* ex);
 const char* ehm_explicit_last_error(void);
 
+/* ---- the explicit law compiled into a hyperplane tree with affine leaf gains ------------------
+ *
+ * Every split of the partition is a bisection, so inside a parent "left child" is the sign of one
+ * affine function (the split face), and the interpolation over a leaf is u = u_0 + K (x - v_0).
+ * A compiled law holds, in arrays it owns (it outlives the handle it was compiled from):
+ *   node       [n_int][node_stride]   [a (p) | b | (left, right) int32 pair]; a child >= 0 is an
+ *                                     internal node, < 0 is ~leaf; children come after parents.
+ *                                     Plane node: left iff ((0 + a_0 x_0) + ..) + b >= -eps.
+ *                                     Test node (children that are no bisection): a = +0.0, b = its
+ *                                     row of test_rec; left iff the left child's simplex holds x.
+ *   leaf_rec   [n_leaf][leaf_stride]  [v_0 (p) | u_0 (n_u) | K (n_u x p, row-major)]
+ *   leaf_node  [n_leaf]               node id of the leaf in the source tree
+ *   test_rec   [n_test][side_stride]  [v_0 | inv(E)] of a test node's left child
+ *   root_rec   [n_roots][side_stride] [v_0 | inv(E)] of the roots;  root_entry [n_roots]: a root's
+ *                                     index (internal, or ~leaf);  nbr [n_roots][p+1] (header
+ *                                     entry has_nbr): the roots' face adjacency
+ * (strides in doubles) and the header, int64 [12]: version, p, n_u, n_roots, n_int, n_leaf, n_test,
+ * node_stride, leaf_stride, side_stride, has_nbr, nodes of the source tree.
+ *
+ * create compiles the law of `src` on its device; vertices [n_nodes][p+1][p] are the ones `src`
+ * was created from (it keeps only their inverses); compile_seconds may be NULL. */
+typedef struct ehm_compiled ehm_compiled;
+int ehm_compiled_create(ehm_explicit* src, const double* vertices, ehm_compiled** out,
+                        double* compile_seconds);
+/* As ehm_explicit_eval_batch: leaf [n] = source node id of the leaf, depth [n] = decisions made
+ * (root tests or locator steps, then one per level); both and kernel_seconds may be NULL. */
+int ehm_compiled_eval_batch(ehm_compiled* law, int64_t n, const double* x, double* u,
+                            int32_t* leaf, int32_t* depth, double* kernel_seconds);
+/* info [14]: the header, then the device bytes of the arrays and of the source evaluator's arrays
+ * for the same tree (0 for an imported law). */
+int ehm_compiled_info(const ehm_compiled* law, int64_t* info);
+/* The arrays to host memory (sizes from the header; an array may be NULL to skip it). */
+int ehm_compiled_export(ehm_compiled* law, double* node, double* leaf_rec, int32_t* leaf_node,
+                        double* test_rec, double* root_rec, int32_t* root_entry, int32_t* nbr);
+/* Checks arrays of the sizes the header states (host only, no device needed): version, p <= 8,
+ * strides, every child / leaf / root / adjacency index in range, children after their parents
+ * (so no cycle), finite records.  EHM_E_INVALID otherwise: a file is untrusted input. */
+int ehm_compiled_validate(const int64_t* header, const double* node, const double* leaf_rec,
+                          const int32_t* leaf_node, const double* test_rec,
+                          const double* root_rec, const int32_t* root_entry, const int32_t* nbr);
+/* A new law from exported arrays, validated as above before anything reaches the device. */
+int ehm_compiled_import(int device, const int64_t* header, const double* node,
+                        const double* leaf_rec, const int32_t* leaf_node, const double* test_rec,
+                        const double* root_rec, const int32_t* root_entry, const int32_t* nbr,
+                        ehm_compiled** out);
+int ehm_compiled_destroy(ehm_compiled* law);
+const char* ehm_compiled_last_error(void);
+
 /* ---- closed-loop simulation under the explicit law (lib/simulator.py, lib/post_process.py) ---
  *
  * The plant the law is closed around (Simulator.__init__, lib/simulator.py:73-122, with the

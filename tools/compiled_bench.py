@@ -1,0 +1,130 @@
+#!/usr/bin/env python
+"""
+ExplicitMPC.evaluate against CompiledLaw.evaluate on one GPU: the same 2^21
+uniform states through the headline tree (the partition of configs[1], 1.6 M nodes) and through the
+p = 8 spine case of ``bench.py --workload explicit``, in kernel time (the ``secs`` both calls
+return) after a warm-up, median and spread of three repeats -- one repeat is the summed kernel time
+of ``--calls`` back-to-back calls, the two laws interleaved call by call, so that a sample spans
+tens of milliseconds and not one 2 ms launch --, plus the compile time and the device bytes of both forms next to the reference's own estimate of a storage-optimised law
+(lib/post_process.py:99-142, get_opt_memreq).
+
+    python tools/compiled_bench.py [--queries N] [--repeats R] [--out FILE]
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench                                                            # noqa: E402
+from explicit_hybrid_mpc_amd import engine, examples, explicit          # noqa: E402
+from explicit_hybrid_mpc_amd import tools as ehm_tools                  # noqa: E402
+
+
+def reference_opt_memreq(flat, p, n_u, word=8):
+    """Bytes of the reference's 'optimized storage ... in which the mixing matrix is stored
+    directly' (get_opt_memreq, lib/post_process.py:118-128) for this tree: per leaf a containment
+    record p (p + 1) and the inputs n_u (p + 1), per internal node whose left child is no leaf that
+    child's containment record."""
+    left = np.asarray(flat.left)
+    internal = np.nonzero(left >= 0)[0]
+    n_leaf = int((left < 0).sum())
+    n_rec = int((left[left[internal]] >= 0).sum())
+    return word * (n_leaf * (p * (p + 1) + n_u * (p + 1)) + n_rec * p * (p + 1))
+
+
+def run_case(name, flat, half, n_q, repeats, calls, rng, out):
+    ex = explicit.ExplicitMPC(flat)
+    t0 = time.perf_counter()
+    cl = ex.compile()
+    wall = time.perf_counter() - t0
+    st = cl.stats
+    X = rng.uniform(-1, 1, (n_q, half.size)) * half
+    times = {'evaluate': [], 'compiled': []}
+    for _ in range(3):                                      # warm-up: buffers, clocks, caches
+        for law in (ex, cl):
+            law.evaluate(X)
+    depth = {}
+    for _ in range(repeats):
+        total = {'evaluate': 0., 'compiled': 0.}
+        for _ in range(calls):                              # interleaved: drift hits both alike
+            for law, key in ((ex, 'evaluate'), (cl, 'compiled')):
+                u, leaf, vis, secs = law.evaluate(X, return_info=True)
+                total[key] += secs
+                depth[key] = float(vis.mean())
+                if key == 'evaluate':
+                    u_e, leaf_e = u, leaf
+        for key in total:
+            times[key].append(total[key] / calls)
+    same = float((leaf == leaf_e).mean())
+    du = float(np.abs(u - u_e)[leaf == leaf_e].max()) if same > 0 else float('nan')
+    out('case %s: %d nodes, %d roots, p = %d, n_u = %d, %d states; %d repeats, each the mean kernel '
+        'time of %d calls' % (name, flat.n_nodes, flat.info['n_roots'], ex.p, ex.n_u, n_q, repeats,
+                              calls))
+    for key in ('evaluate', 'compiled'):
+        t = np.array(times[key])
+        out('  %-9s kernel ms: median %.3f  min %.3f  max %.3f  (%.3g states/s, %.1f decisions '
+            'per state)' % (key, 1e3 * np.median(t), 1e3 * t.min(), 1e3 * t.max(),
+                            n_q / np.median(t), depth[key]))
+    te, tc = np.median(times['evaluate']), np.median(times['compiled'])
+    spread = max(np.ptp(times['evaluate']), np.ptp(times['compiled']))
+    out('  speed-up of the medians: %.2fx  (difference %.3f ms, largest spread %.3f ms)' % (
+        te / tc, 1e3 * (te - tc), 1e3 * spread))
+    out('  same leaf for %.4f %% of the states; max |u - u_evaluate| there %.3g' % (100 * same, du))
+    out('  compile: %.1f ms in the library, %.1f ms with the host copies' % (
+        1e3 * cl.compile_seconds, 1e3 * wall))
+    out('  nodes: %d plane, %d test, %d leaves; device bytes: compiled %d, evaluator %d (%.2fx); '
+        'the reference\'s get_opt_memreq formula on this tree: %d' % (
+            st['n_plane'], st['n_test'], st['n_leaf'], st['bytes'], st['source_bytes'],
+            st['source_bytes'] / st['bytes'],
+            reference_opt_memreq(flat, ex.p, ex.n_u)))
+    ex.close()
+    cl.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--queries', type=int, default=1 << 21)
+    ap.add_argument('--repeats', type=int, default=3)
+    ap.add_argument('--calls', type=int, default=20)
+    ap.add_argument('--seed', type=int, default=0)
+    ap.add_argument('--out', default=None)
+    args = ap.parse_args()
+    lines = []
+
+    def out(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    rng = np.random.default_rng(args.seed)
+    mpc = bench.make_mpc('config2', args.seed)
+    gp = engine.GpuProblem(mpc.compile(), 1., 1.)
+    half = examples.theta_box(mpc)
+    V = examples.box_vertices(half)
+    J_abs, _, _ = gp.solve_pt(0.02 * V)
+    gp.set_eps(float(np.max(J_abs)), 1e-2)
+    roots, _ = ehm_tools.delaunay_roots(V)
+    flat = gp.partition(roots, action='ecc', export=True, with_volume=False)
+    gp.close()
+    run_case('headline_tree', flat, half, args.queries, args.repeats, args.calls, rng, out)
+    mpc8 = examples.pwa4_mpc(N=bench.CONFIG5['N'], seed=args.seed)
+    half8 = examples.theta_box(mpc8)
+    roots8 = np.asarray(ehm_tools.delaunay_roots(examples.box_vertices(half8))[0], dtype=np.float64)
+    K, p8 = roots8.shape[0], roots8.shape[2]
+    n_u8 = int(mpc8.n_u)
+    leafs = -np.ones(K, dtype=np.int32)
+    flat8 = engine.FlatTree(roots8, leafs, leafs.copy(), np.zeros(K, dtype=np.int32),
+                            np.zeros((K, p8 + 1)), np.zeros((K, p8 + 1, n_u8)),
+                            np.zeros(K, dtype=np.uint8), np.zeros(K), {'n_roots': K}, None)
+    run_case('p8_spine', flat8, half8, args.queries, args.repeats, args.calls, rng, out)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, 'w') as f:
+            f.write('\n'.join(lines) + '\n')
+
+
+if __name__ == '__main__':
+    main()
