@@ -119,7 +119,8 @@ class TreeInfo(ctypes.Structure):
                 ('kind_solves', ctypes.c_int64 * 5), ('kind_iters', ctypes.c_int64 * 5),
                 ('near_threshold', ctypes.c_int64), ('witness_inherited', ctypes.c_int64),
                 ('midpoints_shared', ctypes.c_int64),
-                ('persist_ticks', ctypes.c_int64 * 10), ('witness_table', ctypes.c_int64)]
+                ('persist_ticks', ctypes.c_int64 * 10), ('witness_table', ctypes.c_int64),
+                ('persist_pushes', ctypes.c_int64)]
 
 
 class Progress(ctypes.Structure):

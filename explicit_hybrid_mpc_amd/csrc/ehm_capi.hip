@@ -488,6 +488,7 @@ struct ehm_problem {
     bool check_witness = false; // PersistDeal::check (option "check_witness")
     int work_first = 1;      // 1 = a wavefront of the persistent kernel that splits a node goes on
                              // with one child itself and queues the other (option "work_first")
+    int eager_children = 1;  // PersistDeal::eager (option "eager_children")
     int share_mid = 1;       // 1 = the persistent kernel keeps a table of midpoint optima: the
                              // simplices around an edge solve its midpoint once (DevTree::mt;
                              // option "share_midpoints")
@@ -555,6 +556,7 @@ struct ehm_tree {
         long long n_roots = 0, n_nodes = 0, nf = 0, n_closed = 0, ref_solves = 0;
         long long pre_closed = 0, pre_nodes = 0, pre_solves = 0, given = 0, received = 0;
         long long pre_first = 0;    // first node id of the frontier that was dealt
+        long long pushes = 0;       // persistent kernel: children pushed into its queue
         int sweeps = 0, depth = 0, truncated = 0;
         DevCounters c0{};
         Event ev0;
@@ -1166,6 +1168,10 @@ int ehm_problem_set_option(ehm_problem* P, const char* name, double value) {
     }
     if (!strcmp(name, "check_witness")) {
         P->check_witness = value != 0.0;
+        return EHM_OK;
+    }
+    if (!strcmp(name, "eager_children")) {
+        P->eager_children = value != 0.0;
         return EHM_OK;
     }
     if (!strcmp(name, "budget_keep")) {
@@ -2621,12 +2627,12 @@ static int persistent_run(ehm_tree* T, long long max_pops = 0) {
     const int32_t* cur = (R.cur_is_a ? P->fr_a : P->fr_b).as<int32_t>();
     HIP_TRY(hipMemcpyAsync(slots, cur, (size_t)R.nf * 4, hipMemcpyDeviceToDevice, P->stream),
             EHM_E_HIP);
-    PersistDeal deal{0, 0, 0, 1, 0, 0};
+    PersistDeal deal{0, 0, 0, 1, 0, 0, 0, 0};
     deal.check = P->check_witness ? 1 : 0;
     T->dt.code = nullptr;
     if (dealt) {
         deal = PersistDeal{0, R.deal_depth, R.shard_rank, R.shard_world,
-                           getenv("EHM_DEAL_LOW_BITS") ? 0 : 1, 0, P->check_witness ? 1 : 0};
+                           getenv("EHM_DEAL_LOW_BITS") ? 0 : 1, 0, P->check_witness ? 1 : 0, 0};
         HIP_TRY(T->code.ensure((size_t)T->pool.cap * 4), EHM_E_HIP);
         T->dt.code = T->code.as<uint32_t>();
         std::vector<uint32_t> codes((size_t)R.n_roots);
@@ -2644,6 +2650,7 @@ static int persistent_run(ehm_tree* T, long long max_pops = 0) {
     // more LPs (two gloo ranks on one GPU: 38.2 against 33.4 ms per partition,
     // profiles/r5/bench_2_gloo_ranks_dynamic_budget_keep.json)
     if (deal.pop_limit > 0 && !P->budget_keep) deal.keep = 0;
+    deal.eager = P->eager_children ? 1 : 0;
     PersistCtl h{};
     h.head = 0;
     h.tail = (int)R.nf;
@@ -2691,6 +2698,7 @@ static int persistent_run(ehm_tree* T, long long max_pops = 0) {
         R.cur_is_a = true;
     }
     R.ref_solves += (long long)h.closed + 3LL * (long long)h.splits;
+    R.pushes += (long long)h.pushes;
     if (deal.world > 1) {
         // replicated on every rank: everything above the deal depth (and the nodes AT it, which
         // replicated parents created -- own ones and the other ranks' placeholders alike)
@@ -3113,6 +3121,7 @@ int ehm_partition_finish(ehm_tree* T) {
     T->info.midpoints_shared = (int64_t)(c1.mid_shared - R.c0.mid_shared);
     T->info.witness_table = (int64_t)(c1.wit_table - R.c0.wit_table);
     for (int k = 0; k < 10; ++k) T->info.persist_ticks[k] = (int64_t)(c1.prof[k] - R.c0.prof[k]);
+    T->info.persist_pushes = R.pushes;
     T->info.near_threshold = (int64_t)(c1.routed - R.c0.routed);
     T->info.replicated_closed = R.pre_closed;
     T->info.replicated_nodes = R.pre_nodes;

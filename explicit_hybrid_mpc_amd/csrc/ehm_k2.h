@@ -80,6 +80,7 @@ struct PersistCtl {
     unsigned long long splits;      // expanded nodes     } added once when it leaves
     // sharded launches: the part above the deal depth, grown identically on every rank
     unsigned long long repl_closed, repl_splits, repl_solves;
+    unsigned long long pushes;      // children pushed into the queue (not the nodes put back)
 };
 
 // Sharding of ONE persistent launch over the ranks of a multi-GPU run: every rank starts from
@@ -101,6 +102,12 @@ struct PersistDeal {
                     // open; a node it would close at the same time (t* > 0 and t* < 0 cannot both
                     // hold) is counted in ehm_tree_info.errors.  Test builds of a run, not the default:
                     // it costs the bound for half a million nodes of the headline tree.
+    int eager;      // 1 = eager children (option "eager_children", midpoint-first flow): the
+                    // wavefront that splits a node runs both children's LP-free tests at once; a
+                    // child the tangent-plane bound closes is created closed and never queued, the
+                    // wavefront keeps a child that still needs work, and a node the inherited
+                    // witness proves open allocates its children before its midpoint solve.
+                    // 0 = every child is decided by a visit of its own.  Same tree either way.
 };
 
 // Optional indirection of the batched oracle kernels: the hybrid partition engine

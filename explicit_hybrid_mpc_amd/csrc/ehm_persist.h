@@ -34,7 +34,13 @@
 //     the record.  No L2 write-back anywhere;
 //   * node ids follow the allocation order and differ from run to run; the TREE does not
 //     (a node's fate depends on its own record only).  ehm_tree_export relabels to the
-//     breadth-first order of the level-synchronous engine.
+//     breadth-first order of the level-synchronous engine;
+//   * eager children (PersistDeal::eager, midpoint-first flow): the wavefront that splits a node
+//     runs both children's LP-free tests -- inherited witness, tangent-plane bound -- on the LDS
+//     copies it has just made of them.  A child the bound closes is born closed (flags 3, its
+//     bound in tstar) and never enters the queue or `pending`; the wavefront keeps a child that
+//     still needs work and pushes only a second one.  Same functions on the same numbers as the
+//     child's own visit would run: the tree is the same, most queue round trips are gone.
 #define EHM_PERSIST_WATCHDOG_TICKS (60LL * 100000000LL)    // 60 s of the 100 MHz wall clock
 #ifndef EHM_PERSIST_MIDFIRST
 #define EHM_PERSIST_MIDFIRST 0
@@ -74,8 +80,9 @@ __global__ __launch_bounds__(EHM_K2_THREADS) void kx_persist(
            W_DEPTH, W_TRUNC, W_CERT, W_WIT, W_ROUTED, W_RCLOSED, W_RSPLITS, W_RSOLVES,
            W_INH = 17, W_MT = 18, W_MTPARK = 19,           // slot 16 is *wmargin
            W_TQ = 20, W_TMT = 21, W_TMID = 22, W_TSLK = 23, W_NMT = 24,     // DevCounters::prof
-           W_WITT = 25, W_TPRE = 26, W_TPOST = 27, W_REQ = 28 };
-    if (lane0 < 29 && lane0 != 16) wst[lane0] = 0ULL;
+           W_WITT = 25, W_TPRE = 26, W_TPOST = 27, W_REQ = 28,
+           W_EAGER = 29, W_PUSH = 30 };     // children closed at creation; queue pushes of children
+    if (lane0 < 31 && lane0 != 16) wst[lane0] = 0ULL;
     if (lane0 == 0) *wmargin = 1e300;
     kd::wsync();
     int keep = -1;          // the child this wavefront goes on with (see "work first" below)
@@ -85,6 +92,8 @@ __global__ __launch_bounds__(EHM_K2_THREADS) void kx_persist(
     // consumer pays those; round 3 re-read all of it, four dependent loads per kept child)
     bool hot = false;
     int hot_dep = 0, hot_d = 0;
+    // the kept child's tangent-plane bound (and witness cross-check) ran when it was created
+    bool hot_tested = false;
     const bool keep_child = deal.keep != 0;
     for (;;) {
         int id = -1;
@@ -150,22 +159,68 @@ __global__ __launch_bounds__(EHM_K2_THREADS) void kx_persist(
         }
         kd::wsync();
         // ---- suboptimality test --------------------------------------------------------------
-        // the inherited witness first (a dozen instructions): a node it proves open (t* > 0) cannot
-        // be closed by the tangent-plane bound (t* < 0), whose 45 pairs of planes are then skipped
+#if EHM_PERSIST_MIDFIRST
+        // The two LP-free tests of a node, on LDS copies of its record (vertices | vertex costs),
+        // vertex gradients and witness -- run by the node's own visit and, with eager children, by
+        // the wavefront that creates it: one function, so both reach the same verdict.
+        // The inherited witness first (a dozen instructions): a node it proves open (t* > 0) cannot
+        // be closed by the tangent-plane bound (t* < 0), whose 45 pairs of planes are then skipped.
+        // Returns 1 = open (tw: the slack the witness proves), 2 = closed (bnd: the bound),
+        // 0 = undecided; bound_done: the bound has been evaluated before, the witness alone is asked.
+        auto lp_free_verdict = [&](const double* rec_, const double* g_, const double* w_,
+                                   bool bound_done, double& tw, double& bnd) -> int {
+            bool w_open = false;
+            if (T.wit && sign_only) {
+                const double* Vc = rec_ + rec_off_vcost(p);
+                double vbw = 0.0;
+                for (int q = 0; q <= p; ++q) vbw = fma(w_[1 + q], Vc[q], vbw);
+                const double cw = w_[0];
+                tw = fmin(vbw - cw - P.eps_a, vbw - (1.0 + P.eps_r) * cw);
+                w_open = tw > EHM_ROUTE_TOL * (1.0 + fabs(vbw));
+            }
+            // option "check_witness": the witness says open -- the bound must not say closed
+            if (!(T.grad && sign_only) || bound_done || (w_open && !deal.check)) return w_open ? 1 : 0;
+            // tangent-plane bound of t* (ehm_dev.h, cut_bound): negative => closed, no LP
+            const double thr = -EHM_ROUTE_TOL * (1.0 + fabs(rec_[rec_off_vcost(p)]));
+            bnd = cut_bound(rec_, g_, p, P.eps_a, P.eps_r, lane, nb.lp, thr);
+            if (w_open) {
+                if (bnd < thr && lane == 0) wst[W_ERRORS] += 1;
+                kd::wsync();
+                return 1;
+            }
+            return bnd < thr ? 2 : 0;
+        };
         bool inh_open = false;
         double inh_tw = 0.0;
-#if EHM_PERSIST_MIDFIRST
-        if (T.wit && sign_only) {
-            const double* wit_ = nb.rec + (size_t)wave_doubles - k2_stash_doubles(p, n_u) + n_u + p;
-            const double* Vc = node + rec_off_vcost(p);
-            double vbw = 0.0;
-            for (int q = 0; q <= p; ++q) vbw = fma(wit_[1 + q], Vc[q], vbw);
-            const double cw = wit_[0];
-            const double tw = fmin(vbw - cw - P.eps_a, vbw - (1.0 + P.eps_r) * cw);
-            inh_open = tw > EHM_ROUTE_TOL * (1.0 + fabs(vbw));
-            inh_tw = tw;
+        {
+            double bnd = 0.0;
+            const int verdict = lp_free_verdict(
+                node, hgrad, nb.rec + (size_t)wave_doubles - k2_stash_doubles(p, n_u) + n_u + p,
+                is_hot && hot_tested, inh_tw, bnd);
+            inh_open = verdict == 1;
+            if (verdict == 2) {
+                if (lane == 0) {
+                    const int dep0 = dep;
+                    wst[W_CERT] += 1;
+                    wst[W_CLOSED] += 1;
+                    if (dep0 < deal.depth) wst[W_RCLOSED] += 1;
+                    *wmargin = fmin(*wmargin, -bnd);
+                    if ((unsigned long long)dep0 > wst[W_DEPTH]) wst[W_DEPTH] = (unsigned long long)dep0;
+                    T.tstar[id] = bnd;
+                    // (a kept child's flags are the ones it was created with a moment ago: 2)
+                    if (is_hot) T.flags[id] = 3;
+                    else T.flags[id] |= 1;
+                    atomicSub(&ctl->pending, 1);
+                }
+                kd::wsync();
+                continue;
+            }
         }
-#endif
+#else
+        // (the legacy flow, its text as it always was: it keeps no witnesses, so inh_open stays
+        // false and every visit evaluates the tangent-plane bound)
+        bool inh_open = false;
+        double inh_tw = 0.0;
         if (T.grad && sign_only && inh_open && deal.check) {
             // option "check_witness": the witness says open -- the bound must not say closed
             const double thr = -EHM_ROUTE_TOL * (1.0 + fabs(node[rec_off_vcost(p)]));
@@ -195,6 +250,7 @@ __global__ __launch_bounds__(EHM_K2_THREADS) void kx_persist(
                 continue;
             }
         }
+#endif
 #if EHM_PERSIST_MIDFIRST
         // Midpoint first (-DEHM_PERSIST_MIDFIRST=1, how every instance is built since round 2;
         // validated on the device: identical tree): after the tangent-plane bound has taken out 97 %
@@ -222,6 +278,13 @@ __global__ __launch_bounds__(EHM_K2_THREADS) void kx_persist(
         bool open = false;
         double tst = 0.0, margin = 0.0;
         bool decided = false;
+        // Eager children: a node the inherited witness proves open is certain to split once its
+        // midpoint claim has not sent it back -- its two child records are allocated THEN, and the
+        // allocation's round trip runs under the midpoint solve instead of after it (lane 0 holds
+        // the result until the children are written).  Not before the claim: a node that is put
+        // back must not leave a hole in the pool, n_nodes is the node count.
+        int c0_early = 0;
+        bool alloc_early = false;
         if (T.wit && sign_only) {
             // inherited witness: the point that proved an ancestor open, if it lies in this node
             // (loaded with the record, or left in the stash by the parent's visit; evaluated above)
@@ -280,6 +343,10 @@ __global__ __launch_bounds__(EHM_K2_THREADS) void kx_persist(
                     kd::wsync();
                     continue;
                 }
+                if (deal.eager && decided) {
+                    alloc_early = true;
+                    if (lane == 0) c0_early = atomicAdd(&ctl->n_nodes, 2);
+                }
                 if (mt_res == MT_HIT) {
                     bool same = false;
                     const double ev = mt_read(T.mt, mt_slot, lane, mid, p, &same);
@@ -301,6 +368,9 @@ __global__ __launch_bounds__(EHM_K2_THREADS) void kx_persist(
                 // kernel is short of while it solves
                 if (lane == 0) wst[W_MTPARK] = (unsigned long long)mt_res |
                                                ((unsigned long long)mt_slot << 2);
+            } else if (deal.eager && decided) {
+                alloc_early = true;
+                if (lane == 0) c0_early = atomicAdd(&ctl->n_nodes, 2);
             }
             if (mt_res != MT_HIT)
             {
@@ -506,13 +576,25 @@ __global__ __launch_bounds__(EHM_K2_THREADS) void kx_persist(
         const long long t_post = wall_clock64();
         // the wavefront goes on with child 1 itself (work first, below) unless the children are
         // dealt over ranks at this depth: then its record, gradients and witness also stay in LDS
-        const bool fast = keep_child && !(deal.world > 1 && dep + 1 == deal.depth);
+        const bool dealt = deal.world > 1 && dep + 1 == deal.depth;
+        const bool fast = keep_child && !dealt;
+        // eager children: both are tested here, on LDS copies.  Child 1 is formed where the kept
+        // child always was (record in place, gradients at hgrad, witness in the stash); child 0 in
+        // the wavefront's LP workspace, free between solves, behind the bound's scratch and hgrad:
+        // gradients (<= 72 doubles), witness (<= 10), record (<= 153) -- below the 512 doubles
+        // every instance has.  Not at the deal depth: those children belong to ranks, and every
+        // rank would count the leaf.
+        const bool eager = deal.eager != 0 && sign_only && T.grad && !dealt;
+        const bool stage = fast || eager;
+        double* hg0 = nb.lp + 256;
+        double* cw0 = nb.lp + 328;
+        double* c0rec = nb.lp + 340;
         // the node's own gradients again (the solves have used the workspace they were staged in):
         // the load is under way while the allocation below makes its round trip
         const double gv0 = (T.grad && lane < ng) ? T.grad[(size_t)id * ng + lane] : 0.0;
         const int d = is_hot ? hot_d : T.didx[id];
-        int c0 = 0;
-        if (lane == 0) c0 = atomicAdd(&ctl->n_nodes, 2);
+        int c0 = c0_early;
+        if (!alloc_early && lane == 0) c0 = atomicAdd(&ctl->n_nodes, 2);
         c0 = __builtin_amdgcn_readfirstlane(c0);
         if (c0 + 2 > node_cap) {
             if (lane == 0) {
@@ -531,7 +613,8 @@ __global__ __launch_bounds__(EHM_K2_THREADS) void kx_persist(
                 const double a1 = (k >= bj * p && k < bj * p + p) ? stash[st_g + k - bj * p] : gv;
                 __hip_atomic_store(g0 + k, a0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 __hip_atomic_store(g0 + ng + k, a1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (fast) hgrad[k] = a1;
+                if (stage) hgrad[k] = a1;
+                if (eager) hg0[k] = a0;
             }
         }
         if (T.wit && lane < p + 2) {
@@ -548,7 +631,8 @@ __global__ __launch_bounds__(EHM_K2_THREADS) void kx_persist(
             __hip_atomic_store(w0 + lane, v0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(w0 + (p + 2) + lane, v1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             kd::wsync();                        // every lane has read the parent's witness
-            if (fast) wit[lane] = v1;       // child 1's, for its visit by this wavefront
+            if (stage) wit[lane] = v1;      // child 1's, for its visit by this wavefront
+            if (eager) cw0[lane] = v0;
         }
         if (lane == 0) {
             wst[W_SPLITS] += 1;
@@ -699,9 +783,38 @@ __global__ __launch_bounds__(EHM_K2_THREADS) void kx_persist(
             __hip_atomic_store(rec0 + k, v0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(rec1 + k, v1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #if EHM_PERSIST_MIDFIRST
-            if (fast) node[k] = v1;         // child 1's record, in place (entry k depends on entry k)
+            if (stage) node[k] = v1;        // child 1's record, in place (entry k depends on entry k)
+            if (eager) c0rec[k] = v0;
 #endif
         }
+        // a child closed here, at its creation (eager children), and the bound that closed it
+        int closed0 = 0, closed1 = 0;
+        double cbnd0 = 0.0, cbnd1 = 0.0;
+#if EHM_PERSIST_MIDFIRST
+        if (eager) {
+            kd::wsync();
+#pragma nounroll
+            for (int c = 0; c < 2; ++c) {
+                double tw_c = 0.0, bnd_c = 0.0;
+                const int verdict = lp_free_verdict(c ? node : c0rec, c ? hgrad : hg0,
+                                                    c ? wit : cw0, false, tw_c, bnd_c);
+                if (verdict == 2) {         // tallied as its visit would have tallied it
+                    if (lane == 0) {
+                        wst[W_CERT] += 1;
+                        wst[W_CLOSED] += 1;
+                        wst[W_EAGER] += 1;
+                        if (dep + 1 < deal.depth) wst[W_RCLOSED] += 1;
+                        *wmargin = fmin(*wmargin, -bnd_c);
+                        if ((unsigned long long)(dep + 1) > wst[W_DEPTH])
+                            wst[W_DEPTH] = (unsigned long long)(dep + 1);
+                    }
+                    if (c) { closed1 = 1; cbnd1 = bnd_c; }
+                    else { closed0 = 1; cbnd0 = bnd_c; }
+                }
+                kd::wsync();
+            }
+        }
+#endif
         // sharded launch: the children created at the deal depth go to rank (path code % world)
         int own0 = 1, own1 = 1;
         if (lane == 0) {
@@ -725,10 +838,10 @@ __global__ __launch_bounds__(EHM_K2_THREADS) void kx_persist(
             EHM_WT(&T.didx[c0 + 1], d);
             EHM_WT(&T.depth[c0], dep + 1);
             EHM_WT(&T.depth[c0 + 1], dep + 1);
-            EHM_WT(&T.flags[c0], (uint8_t)(own0 ? 2 : 6));
-            EHM_WT(&T.flags[c0 + 1], (uint8_t)(own1 ? 2 : 6));
-            EHM_WT(&T.tstar[c0], 0.0);
-            EHM_WT(&T.tstar[c0 + 1], 0.0);
+            EHM_WT(&T.flags[c0], (uint8_t)(closed0 ? 3 : own0 ? 2 : 6));
+            EHM_WT(&T.flags[c0 + 1], (uint8_t)(closed1 ? 3 : own1 ? 2 : 6));
+            EHM_WT(&T.tstar[c0], cbnd0);
+            EHM_WT(&T.tstar[c0 + 1], cbnd1);
 #undef EHM_WT
         }
         // the write-through stores above have completed (s_waitcnt) before the slots go out
@@ -746,13 +859,18 @@ __global__ __launch_bounds__(EHM_K2_THREADS) void kx_persist(
             // and the rebalancing rounds move 4x the nodes (38.2 against 33.4 ms for two ranks) --
             // and stays off; with budget_keep = 1 a kept child never enters the queue, so what the
             // launch leaves is still the contiguous slice behind the pop limit.
-            const int nown = own0 + own1;
-            int push0 = own0, push1 = own1;
+            // Eager children: a child closed at its creation needs no visit -- kept is a child that
+            // does (child 1 if both do), only a second one is pushed, and `pending` moves by the
+            // survivors - 1; if neither child needs work the wavefront pops.
+            const int need0 = own0 && !closed0, need1 = own1 && !closed1;
+            const int nown = need0 + need1;
+            int push0 = need0, push1 = need1;
             if (keep_child) {
-                if (own1) { kept = c0 + 1; push1 = 0; }
-                else if (own0) { kept = c0; push0 = 0; }
+                if (need1) { kept = c0 + 1; push1 = 0; }
+                else if (need0) { kept = c0; push0 = 0; }
             }
             const int npush = push0 + push1;
+            wst[W_PUSH] += (unsigned long long)npush;
             const int t = npush ? atomicAdd(&ctl->tail, npush) : 0;
             if (t + npush <= n_slots) {
                 int at = t;
@@ -761,7 +879,7 @@ __global__ __launch_bounds__(EHM_K2_THREADS) void kx_persist(
                 if (push1)
                     __hip_atomic_store(&slots[at], c0 + 1, __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_AGENT);
-                // -1 (this node) + its children, the queued one and the kept one alike
+                // -1 (this node) + its surviving children, the queued one and the kept one alike
                 if (nown != 1) atomicAdd(&ctl->pending, nown - 1);
             } else {
                 kept = -1;
@@ -772,7 +890,14 @@ __global__ __launch_bounds__(EHM_K2_THREADS) void kx_persist(
         }
         keep = __builtin_amdgcn_readfirstlane(kept);
 #if EHM_PERSIST_MIDFIRST
-        hot = fast && keep >= 0;
+        if (eager && keep == c0) {
+            // child 1 is closed and child 0 goes on: its copies move to where a kept child's are
+            for (int k = lane; k < nrec; k += 64) node[k] = c0rec[k];
+            for (int k = lane; k < ng; k += 64) hgrad[k] = hg0[k];
+            if (T.wit && lane < p + 2) wit[lane] = cw0[lane];
+        }
+        hot = stage && keep >= 0;
+        hot_tested = eager;
         hot_dep = dep + 1;
         hot_d = d;
 #endif
@@ -801,6 +926,8 @@ __global__ __launch_bounds__(EHM_K2_THREADS) void kx_persist(
         if (wst[W_TPRE]) atomicAdd(&cnt->prof[6], wst[W_TPRE]);
         if (wst[W_TPOST]) atomicAdd(&cnt->prof[7], wst[W_TPOST]);
         if (wst[W_REQ]) atomicAdd(&cnt->prof[8], wst[W_REQ]);
+        if (wst[W_EAGER]) atomicAdd(&cnt->prof[9], wst[W_EAGER]);
+        if (wst[W_PUSH]) atomicAdd(&ctl->pushes, wst[W_PUSH]);
         if (wst[W_ROUTED]) atomicAdd(&cnt->routed, wst[W_ROUTED]);
         atomicAdd(&ctl->closed, wst[W_CLOSED]);
         atomicAdd(&ctl->splits, wst[W_SPLITS]);

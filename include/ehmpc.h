@@ -170,6 +170,13 @@ int ehm_problem_set_solver(ehm_problem* prob, int generation);
  * the bound for every such node);
  * "work_first" (0|1, default 1): a wavefront of the persistent kernel that splits a node goes on
  * with one of the two children itself and queues the other (EHM_NO_WORKFIRST=1 disables);
+ * "eager_children" (0|1, default 1): that wavefront runs both children's LP-free tests (inherited
+ * witness, tangent-plane bound) on the copies it has in LDS when it creates them: a child the
+ * bound closes is written closed and is never queued, the wavefront keeps a child that still
+ * needs work (child 1 if both do), and a node the inherited witness proves open allocates its
+ * children before its midpoint solve.  0 = every child is decided by a visit of its own.
+ * Identical tree (tests/test_gpu_eager_children.py); ehm_tree_info.persist_ticks[9] counts the
+ * children closed at creation, persist_pushes the queue pushes;
  * "timing" (0|1, default 0): multi-commutation runs record an event pair and a counter snapshot
  * around every batched launch, so that ehm_tree_info carries kernel seconds and solves by problem
  * kind (bench.py sets it; ~25 extra stream commands per sweep otherwise spared). */
@@ -428,11 +435,16 @@ typedef struct ehm_tree_info {
      * solves, [4] in suboptimality-test solves; [5] = number of waits of kind [2]; [6] from the
      * pop of a node to its midpoint claim (record load, tangent-plane bound, inherited witness,
      * longest edge), [7] child records and queue pushes; [8] = nodes put back into the queue
-     * because another wavefront was solving their midpoint; [9] unused */
+     * because another wavefront was solving their midpoint; [9] = children closed by the
+     * tangent-plane bound when they were created (option "eager_children"): leaves that never
+     * entered the queue, a part of cert_closed */
     int64_t persist_ticks[10];
     int64_t witness_table;      /* nodes proved open by the optimum at the midpoint of one of their
                                    OTHER edges, left in the table of midpoint optima by a
                                    neighbouring simplex that had bisected that edge, no LP */
+    int64_t persist_pushes;     /* persistent frontier kernel: children pushed into its queue (the
+                                   kept child of a split and a child closed at its creation are
+                                   not; neither are the nodes put back, persist_ticks[8]) */
 } ehm_tree_info;
 
 int ehm_tree_info_get(const ehm_tree* tree, ehm_tree_info* out);
