@@ -48,7 +48,8 @@ EXPORTED = [
     'ehm_implicit_rollout',
     'ehm_compiled_create', 'ehm_compiled_eval_batch', 'ehm_compiled_info', 'ehm_compiled_export',
     'ehm_compiled_validate', 'ehm_compiled_import', 'ehm_compiled_destroy',
-    'ehm_compiled_last_error',
+    'ehm_compiled_last_error', 'ehm_compiled_set_plant', 'ehm_compiled_set_plant_guarded',
+    'ehm_compiled_set_noise', 'ehm_compiled_rollout', 'ehm_compiled_rollout_noisy',
 ]
 
 
@@ -283,6 +284,11 @@ def load(build_if_missing=True):
     lib.ehm_compiled_validate.argtypes = [vp] * 8
     lib.ehm_compiled_import.argtypes = [i32] + [vp] * 8 + [ctypes.POINTER(vp)]
     lib.ehm_compiled_destroy.argtypes = [vp]
+    lib.ehm_compiled_set_plant.argtypes = lib.ehm_explicit_set_plant.argtypes
+    lib.ehm_compiled_set_plant_guarded.argtypes = lib.ehm_explicit_set_plant_guarded.argtypes
+    lib.ehm_compiled_set_noise.argtypes = lib.ehm_explicit_set_noise.argtypes
+    lib.ehm_compiled_rollout.argtypes = lib.ehm_explicit_rollout.argtypes
+    lib.ehm_compiled_rollout_noisy.argtypes = lib.ehm_explicit_rollout_noisy.argtypes
     lib.ehm_tree_info_get.argtypes = [vp, ctypes.POINTER(TreeInfo)]
     lib.ehm_tree_export.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.ehm_host_alloc.argtypes = [ctypes.c_size_t, ctypes.POINTER(vp)]

@@ -3,14 +3,26 @@ The explicit law compiled for deployment (csrc/ehm_compiled.hip)
 
     law = ExplicitMPC(tree, oracle).compile()     # CompiledLaw, independent of its source
     u = law.evaluate(X)                           # as ExplicitMPC.evaluate
+    res = law.rollout(X0, T, plant=plant)         # as ExplicitMPC.rollout, one kernel launch
     law.save('law.npz'); law = CompiledLaw.load('law.npz')
 
 Every split of the partition is a bisection, so an internal node keeps one hyperplane (the split
 face, p + 1 doubles) next to its two child indices instead of the child's p + p^2 record, and a
 leaf keeps the affine map u = u_0 + K (x - v_0) instead of its vertex inputs.  Nodes whose
 children are no bisection (the data-less spine of a nested reference tree) keep the reference's
-containment test.  The compiled law has no exit test: rollouts stay on ``ExplicitMPC``.  No CPU
-fallback.
+containment test.
+
+``rollout`` closes the loop around the compiled law on the device (k_compiled_rollout), also for a
+law that was only ever loaded from a file.  A step measures z, chooses the root as ``evaluate``
+does, stops with status 1 unless every barycentric weight of z in that root is >= -tol_exit,
+walks the planes and applies the leaf's affine map -- (leaf, u) are ``evaluate(z)`` bit for bit --
+and then steps the plant exactly as ``ExplicitMPC.rollout`` does.  Two differences from that
+rollout: ``tol_exit`` is in units of the root's weights, not the leaf's (the statuses can differ
+only for z within a tol_exit-wide band of the hull), and a state within rounding of a split face
+may go to the sibling leaf, as it does in ``evaluate``.  The mode of a leaf comes from
+``leaf_mode`` (``set_leaf_modes``; ``ExplicitMPC.compile`` attaches it, ``save`` / ``load`` keep
+it): like the plant it is an attachment for rollouts, not part of the law.  Laws with test nodes
+and laws with more than four inputs have no rollout.  No CPU fallback.
 """
 
 import ctypes
@@ -59,6 +71,40 @@ def _marshal(arrays):
     return header, out
 
 
+def check_leaf_mode(leaf_mode, n_leaf):
+    """int32 [n_leaf] of a file's (or a caller's) ``leaf_mode``; ``EhmError`` (EHM_E_INVALID) if
+    its length is not n_leaf or a value is < -1.  Host only."""
+    a = np.asarray(leaf_mode)
+    if a.ndim != 1 or a.size != n_leaf or a.dtype.kind not in 'iu':
+        raise _capi.EhmError(_capi.EHM_E_INVALID, 'compiled law: leaf_mode must be %d integers, '
+                             'not %s %s' % (n_leaf, a.dtype, a.shape))
+    if a.size and (int(a.min()) < -1 or int(a.max()) >= 1 << 31):
+        raise _capi.EhmError(_capi.EHM_E_INVALID, 'compiled law: leaf_mode holds %d (a mode, or '
+                             '-1 for none)' % int(a.min() if a.min() < -1 else a.max()))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def read_file(path):
+    """(arrays, leaf_mode or None) of a file ``save`` wrote, read and checked for its keys on the
+    host; the arrays themselves are validated when they are imported (``validate_arrays``)."""
+    with np.load(path, allow_pickle=False) as z:
+        if 'format_version' not in z.files or int(z['format_version']) != FORMAT_VERSION:
+            raise _capi.EhmError(_capi.EHM_E_INVALID, 'compiled law: %s is not a format-%d '
+                                 'file' % (path, FORMAT_VERSION))
+        missing = [k for k in ('header',) + ARRAYS if k not in z.files]
+        if missing:
+            raise _capi.EhmError(_capi.EHM_E_INVALID, 'compiled law: %s lacks %s' % (
+                path, ', '.join(missing)))
+        arrays = {k: z[k] for k in ('header',) + ARRAYS}
+        leaf_mode = z['leaf_mode'] if 'leaf_mode' in z.files else None
+    if leaf_mode is not None:
+        header = np.asarray(arrays['header']).ravel()
+        if header.size != len(HEADER):
+            raise _capi.EhmError(_capi.EHM_E_INVALID, 'compiled law: bad header')
+        leaf_mode = check_leaf_mode(leaf_mode, int(header[HEADER.index('n_leaf')]))
+    return arrays, leaf_mode
+
+
 def validate_arrays(arrays):
     """Raises ``EhmError`` (EHM_E_INVALID) unless ``arrays`` (``CompiledLaw.arrays()``) are a
     well-formed compiled law: the library's check of ehm_compiled_import, on the host."""
@@ -70,6 +116,12 @@ def validate_arrays(arrays):
 class CompiledLaw:
     """A compiled explicit law on the device.  Made by ``ExplicitMPC.compile()``,
     ``CompiledLaw.load(path)`` or ``CompiledLaw.from_arrays(arrays)``."""
+
+    # class defaults: rollout checks its arguments before it touches anything else
+    mpc = None                  # the source's law (ExplicitMPC.compile): the default plant
+    leaf_mode = None            # int32 [n_leaf]: step-0 mode of every leaf's commutation, -1 none
+    _rollout_plant = None       # the plant the device holds (set_plant)
+    _leaf_node = None
 
     def __init__(self, handle, device, compile_seconds=0.):
         self._lib = _capi.load()
@@ -109,21 +161,18 @@ class CompiledLaw:
     @classmethod
     def load(cls, path, device=0):
         """The law ``save`` wrote (one .npz of plain arrays)."""
-        with np.load(path, allow_pickle=False) as z:
-            if 'format_version' not in z.files or int(z['format_version']) != FORMAT_VERSION:
-                raise _capi.EhmError(_capi.EHM_E_INVALID, 'compiled law: %s is not a format-%d '
-                                     'file' % (path, FORMAT_VERSION))
-            missing = [k for k in ('header',) + ARRAYS if k not in z.files]
-            if missing:
-                raise _capi.EhmError(_capi.EHM_E_INVALID, 'compiled law: %s lacks %s' % (
-                    path, ', '.join(missing)))
-            arrays = {k: z[k] for k in ('header',) + ARRAYS}
-        return cls.from_arrays(arrays, device=device)
+        arrays, leaf_mode = read_file(path)
+        law = cls.from_arrays(arrays, device=device)
+        if leaf_mode is not None:
+            law.set_leaf_modes(leaf_mode)
+        return law
 
     def save(self, path):
-        """Writes the arrays and the format version to ``path`` (.npz)."""
+        """Writes the arrays and the format version to ``path`` (.npz); a law that holds leaf
+        modes also writes the optional key ``leaf_mode``."""
+        extra = {} if self.leaf_mode is None else {'leaf_mode': self.leaf_mode}
         with open(path, 'wb') as f:
-            np.savez(f, format_version=np.int64(FORMAT_VERSION), **self.arrays())
+            np.savez(f, format_version=np.int64(FORMAT_VERSION), **self.arrays(), **extra)
 
     def arrays(self):
         """dict: 'header' (int64 [12], ``HEADER``) and the arrays of ``ARRAYS`` (include/ehmpc.h),
@@ -175,6 +224,132 @@ class CompiledLaw:
         if return_info:
             return u, leaf, depth, secs.value
         return u
+
+    # -- closed loop ---------------------------------------------------------------------------
+    @property
+    def leaf_node(self):
+        """int32 [n_leaf]: the source node id of every leaf (ascending)."""
+        if self._leaf_node is None:
+            out = np.zeros(self._h['n_leaf'], dtype=np.int32)
+            _check(self._lib.ehm_compiled_export(self._handle, None, None, ptr(out), None, None,
+                                                 None, None))
+            self._leaf_node = out
+        return self._leaf_node
+
+    def set_leaf_modes(self, modes):
+        """The step-0 mode of every leaf's commutation, int32 [n_leaf] in the order of the leaf
+        records (-1: no commutation, a trajectory that reaches the leaf stops with status 3);
+        None removes the table.  The next rollout hands it to the device with its plant."""
+        self.leaf_mode = None if modes is None else check_leaf_mode(modes, self._h['n_leaf'])
+        self._rollout_plant = None
+
+    def _plant_modes(self, plant):
+        if plant.n_modes == 1 and not plant.guarded:
+            return np.zeros(self._h['n_leaf'], dtype=np.int32)
+        if self.leaf_mode is None:
+            raise ValueError('a hybrid or guarded plant needs the leaf modes (set_leaf_modes; '
+                             'ExplicitMPC.compile attaches them when its oracle gives them)')
+        return self.leaf_mode
+
+    def set_plant(self, plant):
+        """Hands the plant the rollout closes the loop around to the device (once per plant).  A
+        single-mode nominal plant needs no ``leaf_mode`` (all zeros), any other plant does."""
+        if plant.n_x != self.p or plant.n_u != self.n_u:
+            raise ValueError('plant (n_x %d, n_u %d) does not fit the law (p %d, n_u %d)' % (
+                plant.n_x, plant.n_u, self.p, self.n_u))
+        modes = self._plant_modes(plant)
+        opt = lambda a: ptr(a) if a.size else None
+        A, B, w, Gx, gx, Q, R = (f64(a) for a in (plant.A, plant.B, plant.w, plant.Gx, plant.gx,
+                                                  plant.Q, plant.R))
+        if plant.guarded:
+            gm, row0, ga, gb, gc, gt, st = plant.guard_arrays()
+            ga, gb, gc, gt = f64(ga), f64(gb), f64(gc), f64(gt)
+            fn = self._lib.ehm_compiled_set_plant_guarded
+            own = (plant.substeps, len(gm), opt(gm), ptr(row0), opt(ga), opt(gb), opt(gc), opt(gt),
+                   opt(st), plant.default_mode)
+        else:
+            rows, H, h = plant.region_arrays()
+            E, H, h = f64(plant.E), f64(H), f64(h)
+            fn = self._lib.ehm_compiled_set_plant
+            own = (plant.n_d, opt(E), ptr(rows), opt(H), opt(h))
+        self._rollout_plant = None
+        _check(fn(self._handle, plant.n_modes, ptr(A), ptr(B), ptr(w), *own, plant.gx.size, opt(Gx),
+                  opt(gx), ptr(modes), 0 if plant.cost == 'inf' else 1, ptr(Q), ptr(R)))
+        self._plant_mode = modes
+        self._rollout_plant = plant
+
+    def set_noise(self, model, plant):
+        """Hands the uncertainty model (``noise.NoiseModel``) to the device; a no-op when the
+        device already holds the same packed model for the same n_d."""
+        if (model.n_x, model.n_u, model.n_d) != (self.p, self.n_u, plant.n_d):
+            raise ValueError('noise model (n_x %d, n_u %d, n_d %d) does not fit the law and plant '
+                             '(%d, %d, %d)' % (model.n_x, model.n_u, model.n_d, self.p, self.n_u,
+                                               plant.n_d))
+        desc, data = model.pack()
+        held = getattr(self, '_noise_packed', None)
+        if held is not None and held[2] == plant.n_d and np.array_equal(held[0], desc) \
+                and np.array_equal(held[1], data):
+            return
+        self._noise_packed = None
+        _check(self._lib.ehm_compiled_set_noise(self._handle, desc.shape[0], ptr(desc),
+                                                ptr(data) if data.size else None, data.size,
+                                                plant.n_d))
+        self._noise_packed = (desc, data, plant.n_d)
+
+    def rollout(self, X0, T, d=None, v=None, record=True, tol_exit=1e-9, plant=None, noise=None,
+                seed=0, traj0=0):
+        """
+        Closed loop from the states X0 [n, p] for T steps in ONE kernel launch
+        (ehm_compiled_rollout, one device thread per trajectory), with the signature, status
+        codes, records and conventions of ``ExplicitMPC.rollout`` (simulate.py; the step's
+        contract and its two differences are in the module docstring).  ``plant`` defaults to the
+        plant last set, else to ``Plant.from_mpc`` of the law this one was compiled from.
+        Returns a ``simulate.ClosedLoop``: ``leaf`` holds source node ids, ``mode`` comes from
+        ``leaf_mode`` (None for a guarded plant), ``commutation`` stays None.
+        """
+        from . import simulate
+        X0 = f64(np.atleast_2d(X0))
+        n, p = X0.shape
+        T = int(T)
+        if plant is None:
+            plant = self._rollout_plant
+        if plant is None and self.mpc is not None:
+            plant = simulate.Plant.from_mpc(self.mpc)
+        d, v = simulate._check_rollout_args(plant, noise, d, v, n, p, T)
+        if p != self.p or T < 0:
+            raise ValueError('X0 must be [n, %d] and T >= 0' % self.p)
+        if plant is not self._rollout_plant:
+            self.set_plant(plant)
+        if noise is not None:
+            self.set_noise(noise, plant)
+        rec = lambda shape, dtype=np.float64: np.empty(shape, dtype) if record else None
+        xs, us, leaf = rec((T + 1, n, p)), rec((T, n, self.n_u)), rec((T, n), np.int32)
+        x_final = np.empty((n, p))
+        steps = np.empty(n, dtype=np.int32)
+        status = np.empty(n, dtype=np.int32)
+        cost, unorm, maxv = np.empty(n), np.empty(n), np.empty(n)
+        secs = ctypes.c_double(0.)
+        if noise is None:
+            vs = es = ws = None
+            fn = self._lib.ehm_compiled_rollout
+            head = (ptr(d), ptr(v), float(tol_exit), ptr(xs), ptr(us), ptr(leaf))
+        else:
+            vs, es, ws = rec((T, n, p)), rec((T, n, self.n_u)), rec((T, n, plant.n_d))
+            fn = self._lib.ehm_compiled_rollout_noisy
+            head = (int(seed), int(traj0), float(tol_exit), ptr(xs), ptr(us), ptr(leaf), ptr(vs),
+                    ptr(es), ptr(ws))
+        _check(fn(self._handle, n, T, ptr(X0), *head, ptr(x_final), ptr(steps), ptr(status),
+                  ptr(cost), ptr(unorm), ptr(maxv), ctypes.addressof(secs)))
+        out = simulate.ClosedLoop(x_final=x_final, steps=steps, status=status, cost=cost,
+                                  u_norm_sum=unorm, max_violation=maxv, seconds=secs.value,
+                                  x=xs, u=us, leaf=leaf, v=vs, e=es, w=ws)
+        if record and not plant.guarded:
+            live = leaf >= 0
+            order = np.argsort(self.leaf_node, kind='stable')      # ascending for a compiled law
+            at = np.searchsorted(self.leaf_node, np.maximum(leaf, 0), sorter=order)
+            l = order[np.minimum(at, order.size - 1)]
+            out.mode = np.where(live, self._plant_mode[l], -1).astype(np.int32)
+        return out
 
     def __call__(self, x):
         """(u, t): the input for state x and the evaluation time, as the reference's call."""

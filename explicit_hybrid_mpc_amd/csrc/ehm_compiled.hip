@@ -18,6 +18,12 @@
 // index grows strictly, so no array -- compiled here or imported from a file -- can hold a cycle.
 // One level of the walk is one dependent load (the source evaluator: child pair, then the child's
 // record).  The handle owns copies of all it needs: it outlives its source.
+//
+// k_compiled_rollout closes the loop around the compiled law (one thread per trajectory, the T steps
+// in the kernel): the root as k_compiled_locate / k_compiled_eval choose it, the exit test on the
+// root's weights, the walk and the leaf map of k_compiled_eval, then the step of ehm_rollout_dev.h
+// in the mode leaf_mode gives -- a rollout attachment of the handle like the plant, not part of the
+// law (ehm_compiled_set_plant).
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -33,6 +39,7 @@
 #include "../../include/ehmpc.h"
 #include "ehm_explicit_view.h"
 #include "ehm_host.h"
+#include "ehm_rollout_dev.h"
 
 #define EHM_CP 8                 // max parameter dimension (EHM_MAX_P)
 #define EHM_C_LOCATE_MIN 128     // as EHM_X_LOCATE_MIN: spines at least this long get the locator
@@ -325,6 +332,146 @@ __global__ __launch_bounds__(256) void k_compiled_eval(DevCompiled C, long long 
     if (depth_out) depth_out[q] = visited;
 }
 
+// ---- fused closed-loop rollout ---------------------------------------------------------------------
+
+// (alpha, a0) of x in the [v0 | inv(E)] record r: the sums of c_contains / k_compiled_locate
+template <int P>
+__device__ __forceinline__ void c_weights(const double* __restrict__ r, const double* x,
+                                          double* alpha, double& a0) {
+    double d[P];
+#pragma unroll
+    for (int c = 0; c < P; ++c) d[c] = x[c] - r[c];
+    double s = 0.0;
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+        double a = 0.0;
+#pragma unroll
+        for (int c = 0; c < P; ++c) a = fma(r[P + i * P + c], d[c], a);
+        alpha[i] = a;
+        s += a;
+    }
+    a0 = 1.0 - s;
+}
+
+// The step of k_explicit_rollout around the compiled law.  Laws without test nodes
+// only (ehm_compiled_set_plant refuses the others): a state its root holds ends, by the signs of the
+// planes, in a leaf that holds it to rounding, so the exit test is made once, on the root's weights.
+template <int P, int NU, PlantKind KIND>
+__global__ __launch_bounds__(256) void k_compiled_rollout(DevCompiled C, DevPlant PL, RollArgs R,
+                                                          DevNoise NZ, DevGuard GD) {
+#pragma clang fp contract(off)
+    constexpr int NS = P <= 6 ? 8 : 16;
+    constexpr int NL = (P + 3) / 2;
+    extern __shared__ double sh[];
+    rollout_load<KIND>(PL, NZ, sh);
+    __syncthreads();
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= R.n) return;
+    RollState<P, NU> S;
+    double z[P], alpha[P], u[NU], a0;
+    const uint64_t id = NZ.traj0 + (uint64_t)q;
+    rollout_begin<P, NU>(R, q, S);
+    int status = 0, t = 0;
+    int kr = (int)(q % C.n_roots);          // the visibility walk starts at the last step's root
+    for (; t < R.T; ++t) {
+        rollout_measure<P, NU, KIND>(PL, R, NZ, sh, q, t, id, S, z);
+        // root: k_compiled_locate from kr, else the serial rule of k_compiled_eval
+        bool found = false;
+        if (R.nbr) {
+            int kw = kr;
+            for (int step = 0; step < EHM_C_STEPS; ++step) {
+                c_weights<P>(C.root_rec + (size_t)kw * C.side_stride, z, alpha, a0);
+                double lo = a0;
+                int at = 0;
+#pragma unroll
+                for (int i = 0; i < P; ++i)
+                    if (alpha[i] < lo) {
+                        lo = alpha[i];
+                        at = i + 1;
+                    }
+                if (lo > EHM_C_STRICT) {
+                    found = true;
+                    break;
+                }
+                if (lo >= -EHM_C_STRICT) break;
+                const int k2 = R.nbr[(size_t)kw * (P + 1) + at];
+                if (k2 < 0) break;
+                kw = k2;
+            }
+            if (found) kr = kw;
+        }
+        if (!found) {
+            kr = C.n_roots - 1;
+            for (int r = 0; r + 1 < C.n_roots; ++r)
+                if (c_contains<P>(C.root_rec + (size_t)r * C.side_stride, z)) {
+                    kr = r;
+                    break;
+                }
+            c_weights<P>(C.root_rec + (size_t)kr * C.side_stride, z, alpha, a0);
+        }
+        // exit test on the root's weights (a NaN state fails it)
+        bool inside = a0 >= -R.tol_exit;
+#pragma unroll
+        for (int i = 0; i < P; ++i) inside = inside && (alpha[i] >= -R.tol_exit);
+        if (!inside) {
+            status = 1;
+            break;
+        }
+        // the walk of k_compiled_eval (plane nodes only)
+        int k = C.root_entry[kr];
+        while (k >= 0) {
+            const double2* nd = reinterpret_cast<const double2*>(C.node + (size_t)k * NS);
+            double r[2 * NL];
+#pragma unroll
+            for (int i = 0; i < NL; ++i) {
+                const double2 w = nd[i];
+                r[2 * i] = w.x;
+                r[2 * i + 1] = w.y;
+            }
+            const long long ch = __double_as_longlong(r[P + 1]);
+            double s = 0.0;
+#pragma unroll
+            for (int c = 0; c < P; ++c) s = s + r[c] * z[c];
+            s = s + r[P];
+            k = (s >= -EHM_C_EPS) ? (int)(ch & 0xffffffffll) : (int)(ch >> 32);
+        }
+        const int l = ~k;
+        const double* lr = C.leaf_rec + (size_t)l * C.leaf_stride;
+        const double2* lv = reinterpret_cast<const double2*>(lr);
+        double d[P];
+#pragma unroll
+        for (int c = 0; c + 1 < P; c += 2) {
+            const double2 w = lv[c / 2];
+            d[c] = z[c] - w.x;
+            d[c + 1] = z[c + 1] - w.y;
+        }
+        if (P % 2) d[P - 1] = z[P - 1] - lr[P - 1];
+        const double* Kc = lr + P + NU;
+#pragma unroll
+        for (int c = 0; c < NU; ++c) {
+            double w = 0.0;
+#pragma unroll
+            for (int i = 0; i < P; ++i) w = w + Kc[c * P + i] * d[i];
+            u[c] = lr[P + c] + w;
+        }
+        status = rollout_apply<P, NU, KIND>(PL, R, NZ, GD, sh, q, t, id, R.mode[l],
+                                            C.leaf_node[l], u, S);
+        if (status) break;
+    }
+    rollout_finish<P, NU, KIND>(PL, R, q, t, status, S);
+}
+
+typedef void (*rollout_fn)(DevCompiled, DevPlant, RollArgs, DevNoise, DevGuard);
+#define EHM_R_NU(P, K) &k_compiled_rollout<P, 1, K>, &k_compiled_rollout<P, 2, K>, \
+                       &k_compiled_rollout<P, 3, K>, &k_compiled_rollout<P, 4, K>
+#define EHM_R_ALL(K) {{EHM_R_NU(1, K)}, {EHM_R_NU(2, K)}, {EHM_R_NU(3, K)}, {EHM_R_NU(4, K)}, \
+                      {EHM_R_NU(5, K)}, {EHM_R_NU(6, K)}, {EHM_R_NU(7, K)}, {EHM_R_NU(8, K)}}
+// [kind][p - 1][n_u - 1]
+const rollout_fn k_rollout_table[PK_KINDS][EHM_CP][EHM_R_MAX_NU] = {
+    EHM_R_ALL(PK_NOMINAL), EHM_R_ALL(PK_NOISY), EHM_R_ALL(PK_GUARDED)};
+#undef EHM_R_ALL
+#undef EHM_R_NU
+
 typedef void (*locate_fn)(DevCompiled, long long, const double*, const int32_t*, int32_t*);
 typedef void (*eval_fn)(DevCompiled, long long, const double*, double*, int32_t*, int32_t*,
                         const int32_t*);
@@ -455,6 +602,7 @@ struct ehm_compiled {
     DevBuf node, leaf_rec, leaf_node, test_rec, root_rec, root_entry, nbr;
     DevBuf x, u, leaf, depth, root;         // ehm_compiled_eval_batch, cap queries
     size_t cap = 0;
+    RolloutAttach ro;   // plant, leaf modes and model of the rollouts: not part of the law
     Stream stream;
 
     size_t node_bytes() const { return (size_t)h[H_INT] * h[H_NS] * sizeof(double); }
@@ -714,6 +862,102 @@ int ehm_compiled_eval_batch(ehm_compiled* C, int64_t n, const double* x, double*
     C_TRY(hipStreamSynchronize(C->stream));
     ev.seconds(kernel_seconds);
     return EHM_OK;
+}
+
+// ---- closed loop (ehm_compiled_set_plant .. ehm_compiled_rollout_noisy) ---------------------------
+
+}  // extern "C"
+
+namespace {
+
+// what the plant setters refuse about the law itself
+int rollout_law_ok(const ehm_compiled* C, const char* who) {
+    if (!C) return cfail(EHM_E_INVALID, "%s: a required array is NULL", who);
+    if (C->h[H_TEST] > 0)
+        return cfail(EHM_E_INVALID, "%s: the law has %lld test nodes (children that are no "
+                     "bisection); the rollout's exit test is made on the root and needs a walk "
+                     "by planes alone -- roll such a tree out on the source evaluator", who,
+                     (long long)C->h[H_TEST]);
+    return EHM_OK;
+}
+
+const int32_t* rollout_nbr(const ehm_compiled* C) {
+    return (C->nbr && !locate_off()) ? C->nbr.as<const int32_t>() : nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ehm_compiled_set_plant(ehm_compiled* C, int32_t n_modes, const double* A, const double* B,
+                           const double* w, int32_t n_d, const double* Emat,
+                           const int32_t* region_rows, const double* H, const double* h,
+                           int32_t n_g, const double* Gx, const double* gx,
+                           const int32_t* leaf_mode, int32_t cost_kind, const double* Q,
+                           const double* R) {
+    const int rc = rollout_law_ok(C, "set_plant");
+    if (rc != EHM_OK) return rc;
+    return install_plant(C->ro, cfail, C->device, C->d.p, C->d.n_u, C->h[H_LEAF], "leaf",
+                         "set_plant", n_modes, EHM_R_MAX_MODES, A, B, w, n_g, Gx, gx, leaf_mode,
+                         cost_kind, Q, R, nullptr, [&](Pack& pk, DevPlant& pl, int p, int) {
+                             return pack_nominal(cfail, pk, pl, p, n_modes, n_d, Emat, region_rows,
+                                                 H, h);
+                         });
+}
+
+int ehm_compiled_set_plant_guarded(ehm_compiled* C, int32_t n_modes, const double* A,
+                                   const double* B, const double* w, int32_t substeps,
+                                   int32_t n_guards, const int32_t* guard_mode,
+                                   const int32_t* guard_row0, const double* ga, const double* gb,
+                                   const double* gc, const double* gt, const int32_t* strict,
+                                   int32_t default_mode, int32_t n_g, const double* Gx,
+                                   const double* gx, const int32_t* leaf_mode, int32_t cost_kind,
+                                   const double* Q, const double* R) {
+    const int rc = rollout_law_ok(C, "set_plant_guarded");
+    if (rc != EHM_OK) return rc;
+    DevGuard gd{};
+    return install_plant(C->ro, cfail, C->device, C->d.p, C->d.n_u, C->h[H_LEAF], "leaf",
+                         "set_plant_guarded", n_modes, EHM_G_MAX_MODES, A, B, w, n_g, Gx, gx,
+                         leaf_mode, cost_kind, Q, R, &gd, [&](Pack& pk, DevPlant&, int p, int n_u) {
+                             return pack_guarded(cfail, pk, gd, p, n_u, n_modes, substeps, n_guards,
+                                                 guard_mode, guard_row0, ga, gb, gc, gt, strict,
+                                                 default_mode);
+                         });
+}
+
+int ehm_compiled_set_noise(ehm_compiled* C, int32_t n_terms, const int32_t* desc,
+                           const double* data, int32_t n_data, int32_t n_d) {
+    if (!C) return cfail(EHM_E_INVALID, "set_noise: no handle");
+    return install_noise(C->ro, cfail, C->device, C->d.p, C->d.n_u, n_terms, desc, data, n_data,
+                         n_d);
+}
+
+int ehm_compiled_rollout(ehm_compiled* C, int64_t n, int32_t T, const double* x0,
+                         const double* d, const double* v, double tol_exit, double* x_traj,
+                         double* u_traj, int32_t* leaf_traj, double* x_final, int32_t* steps,
+                         int32_t* status, double* cost, double* u_norm_sum,
+                         double* max_violation, double* kernel_seconds) {
+    if (!C) return cfail(EHM_E_INVALID, "rollout: bad argument");
+    return rollout_run(C->ro, cfail, C->device, C->stream, C->d, C->d.p, C->d.n_u, rollout_nbr(C),
+                       k_rollout_table, n, T, x0, d, v, tol_exit, x_traj, u_traj, leaf_traj,
+                       x_final, steps, status, cost, u_norm_sum, max_violation, kernel_seconds,
+                       nullptr);
+}
+
+int ehm_compiled_rollout_noisy(ehm_compiled* C, int64_t n, int32_t T, const double* x0,
+                               uint64_t seed, uint64_t traj0, double tol_exit, double* x_traj,
+                               double* u_traj, int32_t* leaf_traj, double* v_traj,
+                               double* e_traj, double* w_traj, double* x_final, int32_t* steps,
+                               int32_t* status, double* cost, double* u_norm_sum,
+                               double* max_violation, double* kernel_seconds) {
+    if (!C) return cfail(EHM_E_INVALID, "rollout_noisy: no handle");
+    const int rc = noisy_ready(C->ro, cfail);
+    if (rc != EHM_OK) return rc;
+    const NoisyCall nz{seed, traj0, v_traj, e_traj, w_traj};
+    return rollout_run(C->ro, cfail, C->device, C->stream, C->d, C->d.p, C->d.n_u, rollout_nbr(C),
+                       k_rollout_table, n, T, x0, nullptr, nullptr, tol_exit, x_traj, u_traj,
+                       leaf_traj, x_final, steps, status, cost, u_norm_sum, max_violation,
+                       kernel_seconds, &nz);
 }
 
 }  // extern "C"

@@ -231,21 +231,8 @@ __global__ void k_explicit_eval(DevExplicit E, long long n, const double* __rest
 // (weight < -tol_exit), interpolate u as k_explicit_eval does, step the plant in the step-0 mode of
 // the leaf's commutation, accumulate stage cost / input 2-norm / worst constraint value.  Templated
 // on (p, n_u) so that state, weights and inputs live in VGPRs, and on the plant kind (PlantKind);
-// the plant sits in LDS (its layout, the guards', the model's and the sampler: ehm_rollout_dev.h).
-
-struct RollArgs {
-    long long n;
-    int T;
-    double tol_exit;
-    const double *x0, *d, *v;
-    const int32_t* node_mode;
-    const int32_t* nbr;      // root face adjacency (long spines) or nullptr
-    double *x_traj, *u_traj;
-    int32_t* leaf_traj;
-    double *x_final, *cost, *u_norm, *max_viol;
-    int32_t *steps, *status;
-    double *v_traj, *e_traj, *w_traj;       // records of the noisy rollout
-};
+// the plant sits in LDS (its layout, the guards', the model's and the sampler: ehm_rollout_dev.h,
+// which also states the step once the input is known -- rollout_apply -- and the records).
 
 // the sums of `contains` / `weights` with p fixed at compile time.  Kept outside any fp-contract
 // pragma, as those two are: the compiler fuses the same products into the same FMAs, so the
@@ -289,64 +276,23 @@ __device__ __forceinline__ void weights_t(const DevExplicit& E, long long k, con
     alpha0 = 1.0 - s;
 }
 
-// The plant a rollout kernel closes the loop around.
-// PK_NOISY: the nominal plant, with v, e and w drawn from the model in NZ (noise_kind) instead of
-// read from R.v / R.d: v at the true state and the last commanded input, e and w at the true state
-// and the commanded input, e = 0 where u = 0; the plant steps with u + e, cost and ||u|| stay the
-// commanded input's.
-// PK_GUARDED: the plant of GD -- no mode-region check (status 2), and the commanded u is held over
-// GD.substeps plant steps whose modes the guards choose.
-enum PlantKind { PK_NOMINAL, PK_NOISY, PK_GUARDED, PK_KINDS };
-
 template <int P, int NU, PlantKind KIND>
 __global__ __launch_bounds__(256) void k_explicit_rollout(DevExplicit E, DevPlant PL, RollArgs R,
                                                           DevNoise NZ, DevGuard GD) {
 #pragma clang fp contract(off)
-    constexpr bool NOISY = KIND == PK_NOISY, GUARDED = KIND == PK_GUARDED;
     extern __shared__ double sh[];
-    for (int i = threadIdx.x; i < PL.total; i += blockDim.x) sh[i] = PL.data[i];
-    if constexpr (NOISY)
-        for (int i = threadIdx.x; i < NZ.total; i += blockDim.x) sh[PL.total + i] = NZ.data[i];
+    rollout_load<KIND>(PL, NZ, sh);
     __syncthreads();
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= R.n) return;
-    const long long n = R.n;
-    const double* sQ = sh + PL.oQ;
-    const double* sR = sh + PL.oR;
-    const double* sG = sh + PL.oG;
-    const double* sg = sh + PL.og;
-    const double* sE = sh + PL.oE;
-    double x[P], z[P], alpha[P], u[NU], xn[P], a0;
-    double up[NU], vn[P], en[NU], wn[EHM_R_MAX_D];       // noisy path only
-    const double* sn = sh + PL.total;
+    RollState<P, NU> S;
+    double z[P], alpha[P], u[NU], a0;
     const uint64_t id = NZ.traj0 + (uint64_t)q;
-    if constexpr (NOISY)
-#pragma unroll
-        for (int c = 0; c < NU; ++c) up[c] = 0.0;
-#pragma unroll
-    for (int c = 0; c < P; ++c) x[c] = R.x0[q * P + c];
-    if (R.x_traj)
-#pragma unroll
-        for (int c = 0; c < P; ++c) R.x_traj[(size_t)q * P + c] = x[c];
-    double cost = 0.0, unorm = 0.0, maxv = -__builtin_inf();
+    rollout_begin<P, NU>(R, q, S);
     int status = 0, t = 0;
     int kr = (int)(q % E.n_roots);          // warm start of the root locator: the last step's root
     for (; t < R.T; ++t) {
-        // measure
-        if constexpr (NOISY) {
-            noise_kind<P, NU, P>(NZ, sn, 1, P, id, (uint64_t)t, x, up, vn);
-            if (R.v_traj)
-#pragma unroll
-                for (int c = 0; c < P; ++c) R.v_traj[((size_t)t * n + q) * P + c] = vn[c];
-#pragma unroll
-            for (int c = 0; c < P; ++c) z[c] = t > 0 ? x[c] + vn[c] : x[c];
-        } else if (R.v && t > 0) {
-#pragma unroll
-            for (int c = 0; c < P; ++c) z[c] = x[c] + R.v[((size_t)t * n + q) * P + c];
-        } else {
-#pragma unroll
-            for (int c = 0; c < P; ++c) z[c] = x[c];
-        }
+        rollout_measure<P, NU, KIND>(PL, R, NZ, sh, q, t, id, S, z);
         // locate: the spine (visibility walk from the last root where the spine is long, the
         // serial walk wherever that walk gives up), then left iff inside the left child
         long long k = E.n_roots - 1;
@@ -407,193 +353,12 @@ __global__ __launch_bounds__(256) void k_explicit_rollout(DevExplicit E, DevPlan
             for (int i = 0; i < P; ++i) a += vi[(i + 1) * NU + c] * alpha[i];
             u[c] = a;
         }
-        // the mode the leaf's commutation applies at step 0, and its region
-        const int m = R.node_mode[k];
-        if (m < 0 || (!GUARDED && m >= PL.n_modes)) {
-            status = 3;
-            break;
-        }
-        if constexpr (!GUARDED) {
-            bool in_region = true;
-            for (int r = PL.row0[m]; r < PL.row0[m + 1]; ++r) {
-                double s = 0.0;
-#pragma unroll
-                for (int c = 0; c < P; ++c) s += sh[PL.oH + r * P + c] * x[c];
-                in_region = in_region && (s <= sh[PL.oh + r] + R.tol_exit);
-            }
-            if (!in_region) {
-                status = 2;
-                break;
-            }
-        }
-        if (R.u_traj)
-#pragma unroll
-            for (int c = 0; c < NU; ++c) R.u_traj[((size_t)t * n + q) * NU + c] = u[c];
-        if (R.leaf_traj) R.leaf_traj[(size_t)t * n + q] = (int32_t)k;
-        // stage cost and input 2-norm
-        double su = 0.0;
-#pragma unroll
-        for (int c = 0; c < NU; ++c) su += u[c] * u[c];
-        unorm += sqrt(su);
-        if (PL.cost_kind == 0) {
-            double qx = 0.0, ru = 0.0;
-#pragma unroll
-            for (int i = 0; i < P; ++i) {
-                double s = 0.0;
-#pragma unroll
-                for (int c = 0; c < P; ++c) s += sQ[i * P + c] * x[c];
-                qx = fmax(qx, fabs(s));
-            }
-#pragma unroll
-            for (int i = 0; i < NU; ++i) {
-                double s = 0.0;
-#pragma unroll
-                for (int c = 0; c < NU; ++c) s += sR[i * NU + c] * u[c];
-                ru = fmax(ru, fabs(s));
-            }
-            cost += qx + ru;
-        } else {
-            double s = 0.0;
-#pragma unroll
-            for (int i = 0; i < P; ++i) {
-                double r = 0.0;
-#pragma unroll
-                for (int c = 0; c < P; ++c) r += sQ[i * P + c] * x[c];
-                s += x[i] * r;
-            }
-#pragma unroll
-            for (int i = 0; i < NU; ++i) {
-                double r = 0.0;
-#pragma unroll
-                for (int c = 0; c < NU; ++c) r += sR[i * NU + c] * u[c];
-                s += u[i] * r;
-            }
-            cost += s;
-        }
-        // input error and process noise at (x, u)
-        double ua[NU];
-#pragma unroll
-        for (int c = 0; c < NU; ++c) ua[c] = u[c];
-        if constexpr (NOISY) {
-            noise_kind<P, NU, NU>(NZ, sn, 2, NU, id, (uint64_t)t, x, u, en);
-            if (su == 0.0)
-#pragma unroll
-                for (int c = 0; c < NU; ++c) en[c] = 0.0;
-            noise_kind<P, NU, EHM_R_MAX_D>(NZ, sn, 0, PL.n_d, id, (uint64_t)t, x, u, wn);
-#pragma unroll
-            for (int c = 0; c < NU; ++c) {
-                ua[c] = u[c] + en[c];
-                up[c] = u[c];
-            }
-            if (R.e_traj)
-#pragma unroll
-                for (int c = 0; c < NU; ++c) R.e_traj[((size_t)t * n + q) * NU + c] = en[c];
-            if (R.w_traj)
-#pragma unroll
-                for (int j = 0; j < EHM_R_MAX_D; ++j)
-                    if (j < PL.n_d) R.w_traj[((size_t)t * n + q) * PL.n_d + j] = wn[j];
-        }
-        if constexpr (GUARDED) {
-            // S plant steps with u held, each in the mode the guards choose at (x, u)
-            for (int sub = 0; sub < GD.substeps; ++sub) {
-                int gm = GD.default_mode;
-                for (int g = 0; g < GD.n_guards; ++g) {
-                    bool ok = true;
-                    for (int r = GD.row0[g]; r < GD.row0[g + 1]; ++r) {
-                        double s = 0.0;
-#pragma unroll
-                        for (int c = 0; c < P; ++c) s += sh[GD.oGa + r * P + c] * x[c];
-#pragma unroll
-                        for (int c = 0; c < NU; ++c) s += sh[GD.oGb + r * NU + c] * u[c];
-                        s += sh[GD.oGc + r];
-                        const double t = sh[GD.oGt + r];
-                        ok = ok && (GD.strict[r] ? (s < t) : (s <= t));
-                    }
-                    if (ok) {
-                        gm = GD.mode[g];
-                        break;
-                    }
-                }
-                const double* gA = sh + PL.oA + gm * P * P;
-                const double* gB = sh + PL.oB + gm * P * NU;
-                const double* gw = sh + PL.ow + gm * P;
-#pragma unroll
-                for (int i = 0; i < P; ++i) {
-                    double s = 0.0;
-#pragma unroll
-                    for (int c = 0; c < P; ++c) s += gA[i * P + c] * x[c];
-#pragma unroll
-                    for (int c = 0; c < NU; ++c) s += gB[i * NU + c] * u[c];
-                    xn[i] = s + gw[i];
-                }
-#pragma unroll
-                for (int c = 0; c < P; ++c) x[c] = xn[c];
-            }
-        } else {
-            // plant step x+ = A_m x + B_m u + w_m + E d
-            const double* sA = sh + PL.oA + m * P * P;
-            const double* sB = sh + PL.oB + m * P * NU;
-            const double* sw = sh + PL.ow + m * P;
-            const double* dt = R.d ? R.d + ((size_t)t * n + q) * PL.n_d : nullptr;
-#pragma unroll
-            for (int i = 0; i < P; ++i) {
-                double s = 0.0;
-#pragma unroll
-                for (int c = 0; c < P; ++c) s += sA[i * P + c] * x[c];
-#pragma unroll
-                for (int c = 0; c < NU; ++c) s += sB[i * NU + c] * ua[c];
-                s += sw[i];
-                if constexpr (NOISY) {
-#pragma unroll
-                    for (int j = 0; j < EHM_R_MAX_D; ++j)
-                        if (j < PL.n_d) s += sE[i * PL.n_d + j] * wn[j];
-                } else if (dt) {
-                    for (int j = 0; j < PL.n_d; ++j) s += sE[i * PL.n_d + j] * dt[j];
-                }
-                xn[i] = s;
-            }
-        }
-        for (int j = 0; j < PL.n_g; ++j) {
-            double s = 0.0;
-#pragma unroll
-            for (int c = 0; c < P; ++c) s += sG[j * P + c] * xn[c];
-            maxv = fmax(maxv, s - sg[j]);
-        }
-#pragma unroll
-        for (int c = 0; c < P; ++c) x[c] = xn[c];
-        if (R.x_traj)
-#pragma unroll
-            for (int c = 0; c < P; ++c) R.x_traj[((size_t)(t + 1) * n + q) * P + c] = x[c];
+        // the mode the leaf's commutation applies at step 0; the rest of the step
+        status = rollout_apply<P, NU, KIND>(PL, R, NZ, GD, sh, q, t, id, R.mode[k], (int32_t)k, u,
+                                            S);
+        if (status) break;
     }
-    // the records after a stop: NaN states / inputs, leaf -1
-    const double nan = __builtin_nan("");
-    for (int s = t; s < R.T; ++s) {
-        if (R.x_traj)
-#pragma unroll
-            for (int c = 0; c < P; ++c) R.x_traj[((size_t)(s + 1) * n + q) * P + c] = nan;
-        if (R.u_traj)
-#pragma unroll
-            for (int c = 0; c < NU; ++c) R.u_traj[((size_t)s * n + q) * NU + c] = nan;
-        if (R.leaf_traj) R.leaf_traj[(size_t)s * n + q] = -1;
-        if constexpr (NOISY) {
-            // v of the step a trajectory stopped at was drawn and is kept
-            if (R.v_traj && s > t)
-#pragma unroll
-                for (int c = 0; c < P; ++c) R.v_traj[((size_t)s * n + q) * P + c] = nan;
-            if (R.e_traj)
-#pragma unroll
-                for (int c = 0; c < NU; ++c) R.e_traj[((size_t)s * n + q) * NU + c] = nan;
-            if (R.w_traj)
-                for (int j = 0; j < PL.n_d; ++j) R.w_traj[((size_t)s * n + q) * PL.n_d + j] = nan;
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < P; ++c) R.x_final[q * P + c] = x[c];
-    R.steps[q] = t;
-    R.status[q] = status;
-    R.cost[q] = cost;
-    R.u_norm[q] = unorm;
-    R.max_viol[q] = maxv;
+    rollout_finish<P, NU, KIND>(PL, R, q, t, status, S);
 }
 
 typedef void (*rollout_fn)(DevExplicit, DevPlant, RollArgs, DevNoise, DevGuard);
@@ -654,13 +419,7 @@ struct ehm_explicit {
     DevBuf rec, child, vinput;
     DevBuf x, u, leaf, depth, root;     // ehm_explicit_eval_batch, cap queries
     DevBuf nbr;         // [n_roots][p+1] root across the face opposite vertex i (-1: hull)
-    DevBuf plant, node_mode;                         // ehm_explicit_set_plant(_guarded)
-    DevPlant pl{};
-    PlantKind kind = PK_NOMINAL;                     // PK_GUARDED: ehm_explicit_set_plant_guarded
-    DevGuard gd{};
-    DevBuf noise;                                    // ehm_explicit_set_noise
-    DevNoise nz{};
-    int noise_n_d = 0;
+    RolloutAttach ro;   // plant, node modes and model of the rollouts (ehm_explicit_set_*)
     size_t cap = 0;
     Stream stream;
 };
@@ -813,199 +572,19 @@ int ehm_explicit_eval_batch(ehm_explicit* E, int64_t n, const double* x, double*
     return EHM_OK;
 }
 
-}  // extern "C"
-
-namespace {
-
-// What the two plant setters share: the checks of the common arguments; A, B, w, Gx, gx, Q and R
-// packed, then the setter's own arrays (`own` checks and packs them); node_mode checked (< n_modes
-// for the nominal plant; >= -1 for a guarded one, whose guards choose the modes); the new device
-// buffers swapped in.  gd: the guards of a guarded plant (filled by `own`), nullptr for the nominal.
-template <class Own>
-int install_plant(ehm_explicit* E, const char* who, int32_t n_modes, int max_modes,
-                  const double* A, const double* B, const double* w, int32_t n_g, const double* Gx,
-                  const double* gx, const int32_t* node_mode, int32_t cost_kind, const double* Q,
-                  const double* R, const DevGuard* gd, Own own) {
-    if (!E || !A || !B || !w || !node_mode || !Q || !R)
-        return xfail(EHM_E_INVALID, "%s: a required array is NULL", who);
-    if (n_modes < 1 || n_modes > max_modes)
-        return xfail(EHM_E_INVALID, "%s: %d modes (1..%d)", who, (int)n_modes, max_modes);
-    if (n_g < 0 || n_g > EHM_R_MAX_ROWS || (n_g > 0 && (!Gx || !gx)))
-        return xfail(EHM_E_INVALID, "%s: n_g = %d (0..%d)", who, (int)n_g, EHM_R_MAX_ROWS);
-    if (cost_kind != 0 && cost_kind != 1)
-        return xfail(EHM_E_INVALID, "%s: cost_kind %d (0 inf-norm, 1 quadratic)", who,
-                     (int)cost_kind);
-    const int p = E->d.p, n_u = E->d.n_u;
-    if (n_u > EHM_R_MAX_NU)
-        return xfail(EHM_E_INVALID, "%s: n_u = %d, the rollout takes at most %d inputs", who, n_u,
-                     EHM_R_MAX_NU);
-    DevPlant pl{};
-    pl.n_modes = n_modes;
-    pl.n_g = n_g;
-    pl.cost_kind = cost_kind;
-    Pack pk;
-    pl.oA = pk.put(A, (size_t)n_modes * p * p);
-    pl.oB = pk.put(B, (size_t)n_modes * p * n_u);
-    pl.ow = pk.put(w, (size_t)n_modes * p);
-    pl.oG = pk.put(Gx, (size_t)n_g * p);
-    pl.og = pk.put(gx, (size_t)n_g);
-    pl.oQ = pk.put(Q, (size_t)p * p);
-    pl.oR = pk.put(R, (size_t)n_u * n_u);
-    const int rc = own(pk, pl, p, n_u);
-    if (rc != EHM_OK) return rc;
-    pl.total = (int)pk.buf.size();
-    for (int64_t k = 0; k < E->d.n_nodes; ++k)
-        if (gd ? node_mode[k] < -1 : node_mode[k] >= n_modes)
-            return xfail(EHM_E_INVALID, "%s: node %lld has mode %d of %d", who, (long long)k,
-                         (int)node_mode[k], (int)n_modes);
-    hipError_t e = hipSetDevice(E->device);
-    if (e != hipSuccess) return xfail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
-    DevBuf d_plant, d_mode;
-    if (d_plant.upload(pk.buf.data(), pk.buf.size() * sizeof(double)) != hipSuccess ||
-        d_mode.upload(node_mode, (size_t)E->d.n_nodes * sizeof(int32_t)) != hipSuccess)
-        return xfail(EHM_E_HIP, "%s: device allocation / copy failed", who);
-    E->plant = std::move(d_plant);
-    E->node_mode = std::move(d_mode);
-    pl.data = E->plant.as<const double>();
-    E->pl = pl;
-    E->kind = gd ? PK_GUARDED : PK_NOMINAL;
-    if (gd) E->gd = *gd;
-    return EHM_OK;
-}
-
-// the noisy rollout's extra arguments
-struct NoisyCall {
-    uint64_t seed, traj0;
-    double *v_traj, *e_traj, *w_traj;
-};
-
-// ehm_explicit_rollout (nz == nullptr) and ehm_explicit_rollout_noisy
-int rollout_run(ehm_explicit* E, int64_t n, int32_t T, const double* x0, const double* d,
-                const double* v, double tol_exit, double* x_traj, double* u_traj,
-                int32_t* leaf_traj, double* x_final, int32_t* steps, int32_t* status,
-                double* cost, double* u_norm_sum, double* max_violation, double* kernel_seconds,
-                const NoisyCall* nz) {
-    if (!E || !x0 || !x_final || !steps || !status || !cost || !u_norm_sum || !max_violation ||
-        n < 0 || T < 0 || !(tol_exit >= 0.0))
-        return xfail(EHM_E_INVALID, "rollout: bad argument");
-    if (!E->plant) return xfail(EHM_E_INVALID, "rollout: no plant (ehm_explicit_set_plant)");
-    if (d && E->pl.n_d == 0)
-        return xfail(EHM_E_INVALID, "rollout: a disturbance was given but the plant has no E");
-    // a plant set after the model may have grown past what set_noise checked
-    if (nz && E->kind == PK_GUARDED)
-        return xfail(EHM_E_INVALID, "rollout_noisy: the plant is guarded (noisy guarded plants "
-                                    "are not supported)");
-    if (nz && E->pl.total + E->nz.total > EHM_N_MAX_LDS)
-        return xfail(EHM_E_INVALID, "rollout_noisy: plant and model take %d doubles of LDS (%d)",
-                     E->pl.total + E->nz.total, EHM_N_MAX_LDS);
-    const int p = E->d.p, n_u = E->d.n_u, n_d = E->pl.n_d;
-    if (n == 0) return EHM_OK;
-    if (n > (int64_t)1 << 31) return xfail(EHM_E_INVALID, "rollout: %lld trajectories", (long long)n);
-    hipError_t e = hipSetDevice(E->device);
-    if (e != hipSuccess) return xfail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
-    const size_t N = (size_t)n, nT = (size_t)T, D = sizeof(double), I = sizeof(int32_t);
-    RollArgs R{};
-    R.n = n;
-    R.T = T;
-    R.tol_exit = tol_exit;
-    // the per-trajectory outputs: host array (nullptr: not asked for), the RollArgs pointer its
-    // device buffer goes to, bytes
-    struct Out {
-        void* host;
-        void* field;
-        size_t bytes;
-        DevBuf buf;
-    } out[] = {
-        {x_final, &R.x_final, N * p * D},
-        {steps, &R.steps, N * I},
-        {status, &R.status, N * I},
-        {cost, &R.cost, N * D},
-        {u_norm_sum, &R.u_norm, N * D},
-        {max_violation, &R.max_viol, N * D},
-        {x_traj, &R.x_traj, (nT + 1) * N * p * D},
-        {u_traj, &R.u_traj, nT * N * n_u * D},
-        {leaf_traj, &R.leaf_traj, nT * N * I},
-        {nz ? nz->v_traj : nullptr, &R.v_traj, nT * N * p * D},
-        {nz ? nz->e_traj : nullptr, &R.e_traj, nT * N * n_u * D},
-        {nz ? nz->w_traj : nullptr, &R.w_traj, nT * N * n_d * D},
-    };
-    DevBuf dx0, dd, dv;
-    bool ok = dx0.alloc(N * p * D) == hipSuccess &&
-              (!d || dd.alloc(nT * N * n_d * D) == hipSuccess) &&
-              (!v || dv.alloc(nT * N * p * D) == hipSuccess);
-    for (Out& o : out)
-        if (ok && o.host) {
-            ok = o.buf.alloc(o.bytes) == hipSuccess;
-            std::memcpy(o.field, &o.buf.ptr, sizeof o.buf.ptr);
-        }
-    if (!ok)
-        return xfail(EHM_E_HIP, "rollout: out of device memory for %lld x %d steps",
-                     (long long)n, (int)T);
-    R.x0 = dx0.as<const double>();
-    R.d = dd.as<const double>();
-    R.v = dv.as<const double>();
-    R.node_mode = E->node_mode.as<const int32_t>();
-    R.nbr = (E->nbr && !locate_off()) ? E->nbr.as<const int32_t>() : nullptr;
-    Y_TRY(hipMemcpyAsync(dx0.ptr, x0, N * p * D, hipMemcpyHostToDevice, E->stream));
-    if (d) Y_TRY(hipMemcpyAsync(dd.ptr, d, nT * N * n_d * D, hipMemcpyHostToDevice, E->stream));
-    if (v) Y_TRY(hipMemcpyAsync(dv.ptr, v, nT * N * p * D, hipMemcpyHostToDevice, E->stream));
-    EventPair ev;
-    (void)hipEventRecord(ev.e0, E->stream);
-    DevNoise NZ{};
-    size_t lds = (size_t)E->pl.total * sizeof(double);
-    if (nz) {
-        NZ = E->nz;
-        NZ.seed = nz->seed;
-        NZ.traj0 = nz->traj0;
-        lds += (size_t)NZ.total * sizeof(double);
-    }
-    const rollout_fn fn = k_rollout_table[nz ? PK_NOISY : E->kind][p - 1][n_u - 1];
-    hipLaunchKernelGGL(fn, dim3((unsigned)((n + 255) / 256)), dim3(256), lds, E->stream, E->d,
-                       E->pl, R, NZ, E->gd);
-    (void)hipEventRecord(ev.e1, E->stream);
-    Y_TRY(hipGetLastError());
-    for (const Out& o : out)
-        if (o.host)
-            Y_TRY(hipMemcpyAsync(o.host, o.buf.ptr, o.bytes, hipMemcpyDeviceToHost, E->stream));
-    Y_TRY(hipStreamSynchronize(E->stream));
-    ev.seconds(kernel_seconds);
-    return EHM_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
 int ehm_explicit_set_plant(ehm_explicit* E, int32_t n_modes, const double* A, const double* B,
                            const double* w, int32_t n_d, const double* Emat,
                            const int32_t* region_rows, const double* H, const double* h,
                            int32_t n_g, const double* Gx, const double* gx,
                            const int32_t* node_mode, int32_t cost_kind, const double* Q,
                            const double* R) {
-    return install_plant(
-        E, "set_plant", n_modes, EHM_R_MAX_MODES, A, B, w, n_g, Gx, gx, node_mode, cost_kind, Q,
-        R, nullptr, [&](Pack& pk, DevPlant& pl, int p, int) {
-            if (n_d < 0 || n_d > EHM_R_MAX_D || (n_d > 0 && !Emat))
-                return xfail(EHM_E_INVALID, "set_plant: n_d = %d (0..%d, E needed if > 0)",
-                             (int)n_d, EHM_R_MAX_D);
-            int rows = 0;
-            for (int m = 0; m < n_modes; ++m) {
-                const int r = region_rows ? region_rows[m] : 0;
-                if (r < 0)
-                    return xfail(EHM_E_INVALID, "set_plant: mode %d has %d region rows", m, r);
-                pl.row0[m] = rows;
-                rows += r;
-            }
-            if (rows > EHM_R_MAX_ROWS || (rows > 0 && (!H || !h)))
-                return xfail(EHM_E_INVALID, "set_plant: %d mode-region rows (0..%d)", rows,
-                             EHM_R_MAX_ROWS);
-            for (int m = n_modes; m <= EHM_R_MAX_MODES; ++m) pl.row0[m] = rows;
-            pl.n_d = n_d;
-            pl.oE = pk.put(Emat, (size_t)p * n_d);
-            pl.oH = pk.put(H, (size_t)rows * p);
-            pl.oh = pk.put(h, (size_t)rows);
-            return (int)EHM_OK;
-        });
+    if (!E) return xfail(EHM_E_INVALID, "set_plant: a required array is NULL");
+    return install_plant(E->ro, xfail, E->device, E->d.p, E->d.n_u, E->d.n_nodes, "node",
+                         "set_plant", n_modes, EHM_R_MAX_MODES, A, B, w, n_g, Gx, gx, node_mode,
+                         cost_kind, Q, R, nullptr, [&](Pack& pk, DevPlant& pl, int p, int) {
+                             return pack_nominal(xfail, pk, pl, p, n_modes, n_d, Emat, region_rows,
+                                                 H, h);
+                         });
 }
 
 int ehm_explicit_set_plant_guarded(ehm_explicit* E, int32_t n_modes, const double* A,
@@ -1016,50 +595,15 @@ int ehm_explicit_set_plant_guarded(ehm_explicit* E, int32_t n_modes, const doubl
                                    int32_t default_mode, int32_t n_g, const double* Gx,
                                    const double* gx, const int32_t* node_mode, int32_t cost_kind,
                                    const double* Q, const double* R) {
+    if (!E) return xfail(EHM_E_INVALID, "set_plant_guarded: a required array is NULL");
     DevGuard gd{};
-    return install_plant(
-        E, "set_plant_guarded", n_modes, EHM_G_MAX_MODES, A, B, w, n_g, Gx, gx, node_mode,
-        cost_kind, Q, R, &gd, [&](Pack& pk, DevPlant&, int p, int n_u) {
-            if ((n_guards > 0 && !guard_mode) || !guard_row0)
-                return xfail(EHM_E_INVALID, "set_plant_guarded: a required array is NULL");
-            if (substeps < 1 || substeps > EHM_G_MAX_SUB)
-                return xfail(EHM_E_INVALID, "set_plant_guarded: %d substeps (1..%d)",
-                             (int)substeps, EHM_G_MAX_SUB);
-            if (n_guards < 0 || n_guards > EHM_G_MAX_ROWS)
-                return xfail(EHM_E_INVALID, "set_plant_guarded: %d guards (0..%d)", (int)n_guards,
-                             EHM_G_MAX_ROWS);
-            if (default_mode < 0 || default_mode >= n_modes)
-                return xfail(EHM_E_INVALID, "set_plant_guarded: default mode %d of %d",
-                             (int)default_mode, (int)n_modes);
-            if (guard_row0[0] != 0)
-                return xfail(EHM_E_INVALID, "set_plant_guarded: the rows of guard 0 start at %d",
-                             (int)guard_row0[0]);
-            gd.substeps = substeps;
-            gd.n_guards = n_guards;
-            gd.default_mode = default_mode;
-            for (int g = 0; g <= n_guards; ++g) {
-                if (g < n_guards) {
-                    if (guard_mode[g] < 0 || guard_mode[g] >= n_modes)
-                        return xfail(EHM_E_INVALID,
-                                     "set_plant_guarded: guard %d selects mode %d of %d", g,
-                                     (int)guard_mode[g], (int)n_modes);
-                    if (guard_row0[g + 1] <= guard_row0[g])
-                        return xfail(EHM_E_INVALID, "set_plant_guarded: guard %d has no rows", g);
-                    gd.mode[g] = guard_mode[g];
-                }
-                gd.row0[g] = guard_row0[g];
-            }
-            const int rows = guard_row0[n_guards];
-            if (rows > EHM_G_MAX_ROWS || (rows > 0 && (!ga || !gb || !gc || !gt || !strict)))
-                return xfail(EHM_E_INVALID, "set_plant_guarded: %d guard rows (0..%d)", rows,
-                             EHM_G_MAX_ROWS);
-            for (int r = 0; r < rows; ++r) gd.strict[r] = strict[r] != 0;
-            gd.oGa = pk.put(ga, (size_t)rows * p);
-            gd.oGb = pk.put(gb, (size_t)rows * n_u);
-            gd.oGc = pk.put(gc, (size_t)rows);
-            gd.oGt = pk.put(gt, (size_t)rows);
-            return (int)EHM_OK;
-        });
+    return install_plant(E->ro, xfail, E->device, E->d.p, E->d.n_u, E->d.n_nodes, "node",
+                         "set_plant_guarded", n_modes, EHM_G_MAX_MODES, A, B, w, n_g, Gx, gx,
+                         node_mode, cost_kind, Q, R, &gd, [&](Pack& pk, DevPlant&, int p, int n_u) {
+                             return pack_guarded(xfail, pk, gd, p, n_u, n_modes, substeps, n_guards,
+                                                 guard_mode, guard_row0, ga, gb, gc, gt, strict,
+                                                 default_mode);
+                         });
 }
 
 int ehm_explicit_rollout(ehm_explicit* E, int64_t n, int32_t T, const double* x0,
@@ -1067,33 +611,19 @@ int ehm_explicit_rollout(ehm_explicit* E, int64_t n, int32_t T, const double* x0
                          double* u_traj, int32_t* leaf_traj, double* x_final, int32_t* steps,
                          int32_t* status, double* cost, double* u_norm_sum,
                          double* max_violation, double* kernel_seconds) {
-    return rollout_run(E, n, T, x0, d, v, tol_exit, x_traj, u_traj, leaf_traj, x_final, steps,
-                       status, cost, u_norm_sum, max_violation, kernel_seconds, nullptr);
+    if (!E) return xfail(EHM_E_INVALID, "rollout: bad argument");
+    return rollout_run(E->ro, xfail, E->device, E->stream, E->d, E->d.p, E->d.n_u,
+                       (E->nbr && !locate_off()) ? E->nbr.as<const int32_t>() : nullptr,
+                       k_rollout_table, n, T, x0, d, v, tol_exit, x_traj, u_traj, leaf_traj,
+                       x_final, steps, status, cost, u_norm_sum, max_violation, kernel_seconds,
+                       nullptr);
 }
 
 int ehm_explicit_set_noise(ehm_explicit* E, int32_t n_terms, const int32_t* desc,
                            const double* data, int32_t n_data, int32_t n_d) {
-    if (!E || n_terms < 0 || n_terms > EHM_N_MAX_TERMS || (n_terms > 0 && !desc) || n_data < 0 ||
-        (n_data > 0 && !data) || n_d < 0 || n_d > EHM_R_MAX_D)
-        return xfail(EHM_E_INVALID, "set_noise: bad argument (at most %d terms, n_d <= %d)",
-                     EHM_N_MAX_TERMS, EHM_R_MAX_D);
-    const int p = E->d.p, n_u = E->d.n_u;
-    DevNoise nz{};
-    const int bad = noise_fill(nz, n_terms, desc, n_data, p, n_u, n_d);
-    if (bad >= 0) return xfail(EHM_E_INVALID, "set_noise: term %d has a bad descriptor", bad);
-    if (E->pl.total + n_data > EHM_N_MAX_LDS)
-        return xfail(EHM_E_INVALID, "set_noise: plant and model take %d doubles of LDS (%d)",
-                     E->pl.total + n_data, EHM_N_MAX_LDS);
-    hipError_t e = hipSetDevice(E->device);
-    if (e != hipSuccess) return xfail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
-    DevBuf d_noise;
-    if (d_noise.upload(data, (size_t)n_data * sizeof(double)) != hipSuccess)
-        return xfail(EHM_E_HIP, "set_noise: device allocation / copy failed");
-    E->noise = std::move(d_noise);
-    nz.data = E->noise.as<const double>();
-    E->nz = nz;
-    E->noise_n_d = n_d;
-    return EHM_OK;
+    if (!E) return xfail(EHM_E_INVALID, "set_noise: no handle");
+    return install_noise(E->ro, xfail, E->device, E->d.p, E->d.n_u, n_terms, desc, data, n_data,
+                         n_d);
 }
 
 int ehm_explicit_rollout_noisy(ehm_explicit* E, int64_t n, int32_t T, const double* x0,
@@ -1103,14 +633,14 @@ int ehm_explicit_rollout_noisy(ehm_explicit* E, int64_t n, int32_t T, const doub
                                int32_t* status, double* cost, double* u_norm_sum,
                                double* max_violation, double* kernel_seconds) {
     if (!E) return xfail(EHM_E_INVALID, "rollout_noisy: no handle");
-    if (!E->noise) return xfail(EHM_E_INVALID, "rollout_noisy: no model (ehm_explicit_set_noise)");
-    if (E->plant && E->noise_n_d != E->pl.n_d)
-        return xfail(EHM_E_INVALID, "rollout_noisy: the model has n_d = %d, the plant %d",
-                     E->noise_n_d, E->pl.n_d);
+    const int rc = noisy_ready(E->ro, xfail);
+    if (rc != EHM_OK) return rc;
     const NoisyCall nz{seed, traj0, v_traj, e_traj, w_traj};
-    return rollout_run(E, n, T, x0, nullptr, nullptr, tol_exit, x_traj, u_traj, leaf_traj,
-                       x_final, steps, status, cost, u_norm_sum, max_violation, kernel_seconds,
-                       &nz);
+    return rollout_run(E->ro, xfail, E->device, E->stream, E->d, E->d.p, E->d.n_u,
+                       (E->nbr && !locate_off()) ? E->nbr.as<const int32_t>() : nullptr,
+                       k_rollout_table, n, T, x0, nullptr, nullptr, tol_exit, x_traj, u_traj,
+                       leaf_traj, x_final, steps, status, cost, u_norm_sum, max_violation,
+                       kernel_seconds, &nz);
 }
 
 int ehm_philox_batch(int64_t n, const uint64_t* counters, const uint64_t* key, uint64_t* out) {

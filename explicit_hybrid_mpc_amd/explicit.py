@@ -171,11 +171,17 @@ class ExplicitMPC:
 
     def compile(self):
         """The law as a ``compiled.CompiledLaw``: one hyperplane per internal node, one affine map
-        per leaf, compiled on the device.  It holds its own arrays and outlives this object."""
+        per leaf, compiled on the device.  It holds its own arrays and outlives this object.  For
+        its rollouts it remembers ``mpc`` (the default plant) and, where ``mpc`` tells the step-0
+        mode of a commutation, the mode of every leaf (``CompiledLaw.leaf_mode``)."""
         from .compiled import CompiledLaw
         vertices = self.tree.vertices if isinstance(self.tree, FlatTree) else \
             flatten_tree(self.tree)[0]
-        return CompiledLaw.compile(self, vertices)
+        law = CompiledLaw.compile(self, vertices)
+        law.mpc = self.mpc
+        if self.mpc is not None and hasattr(self.mpc, 'step0_mode'):
+            law.set_leaf_modes(self._step0_modes()[law.leaf_node])
+        return law
 
     def close(self):
         if getattr(self, '_handle', None):
@@ -209,6 +215,10 @@ class ExplicitMPC:
             return np.zeros(self.n_nodes, dtype=np.int32)
         if self.mpc is None or not hasattr(self.mpc, 'step0_mode'):
             raise ValueError('the step-0 modes of a hybrid law need the oracle (its mpc)')
+        return self._step0_modes()
+
+    def _step0_modes(self):
+        """int32 [n_nodes]: step-0 mode of every node's commutation (-1: none), from ``mpc``."""
         if isinstance(self.tree, FlatTree):
             modes = np.array([self.mpc.step0_mode(dl) for dl in self.tree.deltas] + [-1],
                              dtype=np.int32)

@@ -618,6 +618,51 @@ int ehm_explicit_rollout_noisy(ehm_explicit* ex, int64_t n, int32_t T, const dou
  * and out [n][4], key [2] (numpy: np.random.Philox(counter=c - 1, key=key).random_raw(4)). */
 int ehm_philox_batch(int64_t n, const uint64_t* counters, const uint64_t* key, uint64_t* out);
 
+/* ---- closed-loop simulation under the COMPILED law (csrc/ehm_compiled.hip) -------
+ *
+ * The entry points of the explicit law's rollout, argument for argument, on a compiled law -- also
+ * one that was only ever imported.  leaf_mode [n_leaf] (the order of leaf_rec) takes the place of
+ * node_mode [n_nodes]: the step-0 mode of every leaf's commutation, -1: none (status 3).  The mode
+ * table, the plant and the model are attachments of the handle for its rollouts: they are not part
+ * of the law (ehm_compiled_info's bytes, ehm_compiled_export).  Refusals as the explicit law's
+ * (NULL arrays, limits, n_u <= 4, a mode >= n_modes for the nominal plant, the LDS cap, a noisy
+ * guarded plant, d without E), and a law with test nodes (header n_test > 0) is refused by both
+ * plant setters with EHM_E_INVALID.
+ * A step: measure z = x + v (none at t = 0); choose the root as ehm_compiled_eval_batch does -- with
+ * an adjacency table the visibility walk, started at the previous step's root (q mod n_roots at
+ * t = 0), else the first root that contains z, else the last; stop with status 1 unless every
+ * barycentric weight of z in THAT ROOT is >= -tol_exit (a NaN state stops); walk the planes and
+ * apply the leaf's affine map -- (leaf, u) are ehm_compiled_eval_batch's for z, bit for bit;
+ * then the step of ehm_explicit_rollout for the plant kind, bit for bit.  leaf_traj records the
+ * source node id of the leaf. */
+int ehm_compiled_set_plant(ehm_compiled* law, int32_t n_modes, const double* A, const double* B,
+                           const double* w, int32_t n_d, const double* E,
+                           const int32_t* region_rows, const double* H, const double* h,
+                           int32_t n_g, const double* Gx, const double* gx,
+                           const int32_t* leaf_mode, int32_t cost_kind, const double* Q,
+                           const double* R);
+int ehm_compiled_set_plant_guarded(ehm_compiled* law, int32_t n_modes, const double* A,
+                                   const double* B, const double* w, int32_t substeps,
+                                   int32_t n_guards, const int32_t* guard_mode,
+                                   const int32_t* guard_row0, const double* ga, const double* gb,
+                                   const double* gc, const double* gt, const int32_t* strict,
+                                   int32_t default_mode, int32_t n_g, const double* Gx,
+                                   const double* gx, const int32_t* leaf_mode, int32_t cost_kind,
+                                   const double* Q, const double* R);
+int ehm_compiled_set_noise(ehm_compiled* law, int32_t n_terms, const int32_t* desc,
+                           const double* data, int32_t n_data, int32_t n_d);
+int ehm_compiled_rollout(ehm_compiled* law, int64_t n, int32_t T, const double* x0,
+                         const double* d, const double* v, double tol_exit, double* x_traj,
+                         double* u_traj, int32_t* leaf_traj, double* x_final, int32_t* steps,
+                         int32_t* status, double* cost, double* u_norm_sum,
+                         double* max_violation, double* kernel_seconds);
+int ehm_compiled_rollout_noisy(ehm_compiled* law, int64_t n, int32_t T, const double* x0,
+                               uint64_t seed, uint64_t traj0, double tol_exit, double* x_traj,
+                               double* u_traj, int32_t* leaf_traj, double* v_traj,
+                               double* e_traj, double* w_traj, double* x_final, int32_t* steps,
+                               int32_t* status, double* cost, double* u_norm_sum,
+                               double* max_violation, double* kernel_seconds);
+
 /* ---- the closed loop around the IMPLICIT law on the device (csrc/ehm_implicit.hip) ------------
  *
  * simulate.rollout_implicit without its host loop: per step one mixed-integer P_theta for every

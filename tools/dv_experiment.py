@@ -3,7 +3,7 @@
 The reference's closed-loop experiment under its noise model (needs a GPU):
 
     python tools/dv_experiment.py [--n 10000] [--n-implicit 256] [--jobs 1,2,3,4,5] [--seed 0]
-                                  [--implicit-on-device [--implicit-trajectories N]]
+                                  [--implicit-on-device [--implicit-trajectories N]] [--compiled]
 
 lib/post_process.py:553-568: both laws of cwh_z from x0 = 0 for 20 orbits at T_s = 100 s (1 115
 steps, Simulator's time grid), here with NoiseModel.from_mpc (the six terms of
@@ -14,6 +14,8 @@ median, 5 % and 95 % for both laws, the overconsumption on the common trajectori
 paper's single-run numbers (lib/post_process.py:414-417) beside them.  --implicit-on-device runs the
 implicit law's loop on the device (rollout(..., on_device=True)), which makes --implicit-trajectories
 as large as --n affordable (it overrides --n-implicit); the row then also reports the stalled pairs.
+--compiled rolls out the compiled law (ExplicitMPC.compile(), the artefact a user ships) in place of
+the partitioner's tree, in the experiment and in the throughput runs.
 
 Then the throughput of the noisy against the nominal rollout, measured in the same call (1e6
 trajectories x 100 steps from uniform states, applied trajectory-steps per second of kernel time)
@@ -46,12 +48,22 @@ def stats(dv):
                 p5=float(np.percentile(dv, 5)), p95=float(np.percentile(dv, 95)))
 
 
-def experiment(job, n, n_im, seed, on_device=False):
+def law_of(flat, oracle, use_compiled):
+    """The explicit law of a partition, or its compiled form (the source closed)."""
+    ex = explicit.ExplicitMPC(flat, oracle)
+    if not use_compiled:
+        return ex
+    cl = ex.compile()
+    ex.close()
+    return cl
+
+
+def experiment(job, n, n_im, seed, on_device=False, use_compiled=False):
     oracle, flat = cwh_tree(job)
     mpc = oracle.mpc
     T = reference_steps(mpc)
     model = NoiseModel.from_mpc(mpc)
-    ex = explicit.ExplicitMPC(flat, oracle)
+    ex = law_of(flat, oracle, use_compiled)
     im = explicit.ImplicitMPC(oracle)
     t0 = time.perf_counter()
     a = ex.rollout(np.zeros((n, 2)), T, noise=model, seed=seed, record=False)
@@ -63,6 +75,7 @@ def experiment(job, n, n_im, seed, on_device=False):
     dv_ex, dv_im = 1e3 * a.u_norm_sum, 1e3 * b.u_norm_sum
     ok = (a.status[:n_im] == 0) & (b.status == 0)
     row = dict(job=job, leaves=int(np.sum(flat.left < 0)), T=T, seed=seed,
+               law='compiled' if use_compiled else 'explicit',
                explicit=dict(trajectories=n, stopped=int((a.status != 0).sum()),
                              max_violation=float(a.max_violation.max()),
                              kernel_s=a.seconds, wall_s=t_ex, dv_mm_s=stats(dv_ex)),
@@ -86,13 +99,14 @@ def experiment(job, n, n_im, seed, on_device=False):
     return row
 
 
-def throughput(name, mpc, flat, model, n, T, rng):
-    ex = explicit.ExplicitMPC(flat, types.SimpleNamespace(mpc=mpc))
+def throughput(name, mpc, flat, model, n, T, rng, use_compiled=False):
+    ex = law_of(flat, types.SimpleNamespace(mpc=mpc), use_compiled)
     half = examples.theta_box(mpc)
     X0 = rng.uniform(-1, 1, (n, half.size)) * half
     ex.rollout(X0[:1024], T, record=False)
     ex.rollout(X0[:1024], T, record=False, noise=model)
-    row = dict(tree=name, nodes=int(flat.n_nodes), trajectories=n, T=T, terms=len(model.terms))
+    row = dict(tree=name, law='compiled' if use_compiled else 'explicit',
+               nodes=int(flat.n_nodes), trajectories=n, T=T, terms=len(model.terms))
     for label, kw in (('nominal', {}), ('noisy', dict(noise=model, seed=1))):
         res = ex.rollout(X0, T, record=False, **kw)
         applied = int(res.steps.sum())
@@ -114,12 +128,14 @@ def main():
     ap.add_argument('--rate-n', type=int, default=1000000)
     ap.add_argument('--rate-T', type=int, default=100)
     ap.add_argument('--skip-rates', action='store_true')
+    ap.add_argument('--compiled', action='store_true')
     args = ap.parse_args()
     if args.implicit_trajectories is not None:
         if not args.implicit_on_device:
             ap.error('--implicit-trajectories goes with --implicit-on-device')
         args.n_implicit = min(args.implicit_trajectories, args.n)
-    rows = [experiment(int(j), args.n, args.n_implicit, args.seed, args.implicit_on_device)
+    rows = [experiment(int(j), args.n, args.n_implicit, args.seed, args.implicit_on_device,
+                       args.compiled)
             for j in args.jobs.split(',') if j]
     if rows:
         print('\ndelta-v [mm/s] over 20 orbits from x0 = 0 (explicit: %d trajectories, implicit: '
@@ -136,12 +152,12 @@ def main():
         rng = np.random.default_rng(0)
         oracle, flat = cwh_tree(1)
         throughput('cwh_z job 1', oracle.mpc, flat, NoiseModel.from_mpc(oracle.mpc), args.rate_n,
-                   args.rate_T, rng)
+                   args.rate_T, rng, args.compiled)
         oracle.close()
         mpc, flat = headline_tree()
         half = examples.theta_box(mpc)
         throughput('headline (configs[2])', mpc, flat, state_input_model(half, mpc.B[0].shape[1]),
-                   args.rate_n, args.rate_T, rng)
+                   args.rate_n, args.rate_T, rng, args.compiled)
 
 
 if __name__ == '__main__':

@@ -3,6 +3,7 @@
 Closed-loop simulation throughput and the cwh_z delta-v overconsumption table (needs a GPU).
 
     python tools/rollout_bench.py [--n 1000000] [--T 100] [--jobs 1,2,3,4,5] [--n-compare 10000]
+                                  [--laws [--repeats 3]]
 
 Trajectory-steps/s, one JSON line per tree and path:
   (a) fused    ExplicitMPC.rollout: one launch of ehm_explicit_rollout (device time of the kernel,
@@ -11,6 +12,10 @@ Trajectory-steps/s, one JSON line per tree and path:
                without the rollout (wall time; every trajectory runs all T steps, no exit test);
   (c) cpu      the CPU restatement (oracle.explicit_cpu.ExplicitFlatCPU + the numpy plant step),
                one process, a few trajectories, for scale.
+--laws runs, instead of all that, the explicit and the compiled law (ExplicitMPC.compile()) in one
+process with the calls interleaved: --repeats rollouts of each after a warm-up, nominal and under a
+noise model, kernel time; one JSON line per tree and case with the applied trajectory-steps/s of
+both (median, min .. max) and their ratio, and whether the two rollouts ended alike.
 Trees: the headline partition (linear_mpc(0), abs_frac 0.02, eps_r 1e-2, as bench.py) and cwh_z
 job 1.  Then simulate.compare on cwh_z jobs 1..5 (lib/post_process.py:484-526 / make_jobs.sh) from
 uniform initial states in the box, nominal and with a box-bounded process disturbance; the
@@ -29,6 +34,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from explicit_hybrid_mpc_amd import engine, examples, explicit, simulate   # noqa: E402
 from explicit_hybrid_mpc_amd import tools as ehm_tools                   # noqa: E402
+from explicit_hybrid_mpc_amd.noise import NoiseModel, state_input_model  # noqa: E402
 from oracle import geometry                                              # noqa: E402
 from oracle.explicit_cpu import ExplicitFlatCPU                          # noqa: E402
 
@@ -101,6 +107,40 @@ def rates(name, mpc, flat, n, T, rng):
     ex.close()
 
 
+def both_laws(name, mpc, flat, model, n, T, repeats, rng):
+    """The explicit and the compiled law on the same states in one process, calls interleaved."""
+    ex = explicit.ExplicitMPC(flat, types.SimpleNamespace(mpc=mpc))
+    cl = ex.compile()
+    half = examples.theta_box(mpc)
+    X0 = rng.uniform(-1, 1, (n, half.size)) * half
+    for label, kw in (('nominal', {}), ('noisy', dict(noise=model, seed=1))):
+        for law in (ex, cl):
+            law.rollout(X0[:1024], T, record=False, **kw)              # warm-up
+        secs = {'explicit': [], 'compiled': []}
+        for _ in range(repeats):
+            for key, law in (('explicit', ex), ('compiled', cl)):
+                res = law.rollout(X0, T, record=False, **kw)
+                secs[key].append(res.seconds)
+                if key == 'explicit':
+                    a = res
+        row = dict(tree=name, case=label, nodes=int(flat.n_nodes), trajectories=n, T=T,
+                   repeats=repeats, same_steps=int((a.steps == res.steps).sum()),
+                   same_status=int((a.status == res.status).sum()))
+        for key, r in (('explicit', a), ('compiled', res)):
+            applied = int(r.steps.sum())
+            t = np.array(secs[key])
+            row[key] = dict(applied_steps=applied, stopped=int((r.status != 0).sum()),
+                            kernel_s=[float(v) for v in t],
+                            steps_per_s_median=applied / float(np.median(t)),
+                            steps_per_s_min=applied / float(t.max()),
+                            steps_per_s_max=applied / float(t.min()))
+        row['compiled_over_explicit'] = (row['compiled']['steps_per_s_median']
+                                         / row['explicit']['steps_per_s_median'])
+        print(json.dumps(row), flush=True)
+    ex.close()
+    cl.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--n', type=int, default=1000000)
@@ -108,8 +148,21 @@ def main():
     ap.add_argument('--jobs', default='1,2,3,4,5')
     ap.add_argument('--n-compare', type=int, default=10000)
     ap.add_argument('--skip-rates', action='store_true')
+    ap.add_argument('--laws', action='store_true')
+    ap.add_argument('--repeats', type=int, default=3)
     args = ap.parse_args()
     rng = np.random.default_rng(0)
+    if args.laws:
+        mpc, flat = headline_tree()
+        both_laws('headline (configs[2])', mpc, flat,
+                  state_input_model(examples.theta_box(mpc), mpc.B[0].shape[1]), args.n, args.T,
+                  args.repeats, rng)
+        del flat
+        oracle, flat = cwh_tree(1)
+        both_laws('cwh_z job 1', oracle.mpc, flat, NoiseModel.from_mpc(oracle.mpc), args.n, args.T,
+                  args.repeats, rng)
+        oracle.close()
+        return
     if not args.skip_rates:
         mpc, flat = headline_tree()
         rates('headline (configs[2])', mpc, flat, args.n, args.T, rng)
