@@ -50,6 +50,8 @@ EXPORTED = [
     'ehm_compiled_validate', 'ehm_compiled_import', 'ehm_compiled_destroy',
     'ehm_compiled_last_error', 'ehm_compiled_set_plant', 'ehm_compiled_set_plant_guarded',
     'ehm_compiled_set_noise', 'ehm_compiled_rollout', 'ehm_compiled_rollout_noisy',
+    'ehm_compiled_narrow', 'ehm_compiled_export_single', 'ehm_compiled_validate_single',
+    'ehm_compiled_import_single',
 ]
 
 
@@ -284,6 +286,10 @@ def load(build_if_missing=True):
     lib.ehm_compiled_validate.argtypes = [vp] * 8
     lib.ehm_compiled_import.argtypes = [i32] + [vp] * 8 + [ctypes.POINTER(vp)]
     lib.ehm_compiled_destroy.argtypes = [vp]
+    lib.ehm_compiled_narrow.argtypes = [vp, ctypes.POINTER(vp)]
+    lib.ehm_compiled_export_single.argtypes = [vp] * 7
+    lib.ehm_compiled_validate_single.argtypes = [vp] * 7
+    lib.ehm_compiled_import_single.argtypes = [i32] + [vp] * 7 + [ctypes.POINTER(vp)]
     lib.ehm_compiled_set_plant.argtypes = lib.ehm_explicit_set_plant.argtypes
     lib.ehm_compiled_set_plant_guarded.argtypes = lib.ehm_explicit_set_plant_guarded.argtypes
     lib.ehm_compiled_set_noise.argtypes = lib.ehm_explicit_set_noise.argtypes

@@ -5,7 +5,8 @@ CPU-only build container.
 
 Objects: ``ehm_capi.hip`` (C-ABI, host orchestration, generation-1 kernels),
 ``ehm_explicit.hip`` and ``ehm_implicit.hip`` (the closed loops around the two laws),
-``ehm_compiled.hip`` (the explicit law compiled into a hyperplane tree), one
+``ehm_compiled.hip`` (the explicit law compiled into a hyperplane tree) and
+``ehm_compiled32.hip`` (the kernels of its single-precision form), one
 instance of ``ehm_k2.hip`` per (column capacity NP, row slots) pair -- the solver keeps a
 row of the normal matrix and the LP's row vectors in registers, so both are compile-time
 sizes --, one instance of ``ehm_kp.hip`` per (decide NP, expand NP, row slots) triple and flow
@@ -139,7 +140,9 @@ def _objects():
             (os.path.join(OBJ_DIR, 'ehm_implicit.o'), os.path.join(SRC_DIR, 'ehm_implicit.hip'),
              []),
             (os.path.join(OBJ_DIR, 'ehm_compiled.o'), os.path.join(SRC_DIR, 'ehm_compiled.hip'),
-             [])]
+             []),
+            (os.path.join(OBJ_DIR, 'ehm_compiled32.o'),
+             os.path.join(SRC_DIR, 'ehm_compiled32.hip'), [])]
     for np_ in K2_NPS:
         for sl in K2_SLOTS:
             objs.append((os.path.join(OBJ_DIR, 'ehm_k2_%d_%d.o' % (np_, sl)),
@@ -180,7 +183,8 @@ def is_stale():
     t = os.path.getmtime(LIB)
     srcs = [os.path.join(SRC_DIR, f)
             for f in ('ehm_capi.hip', 'ehm_k2.hip', 'ehm_k3.hip', 'ehm_k4.hip', 'ehm_kp.hip',
-                      'ehm_explicit.hip', 'ehm_implicit.hip', 'ehm_compiled.hip')]
+                      'ehm_explicit.hip', 'ehm_implicit.hip', 'ehm_compiled.hip',
+                      'ehm_compiled32.hip')]
     return max([_dep_mtime()] + [os.path.getmtime(s)
                                  for s in srcs + SEARCH_DEPS + FRONTIER_DEPS]) > t
 

@@ -23,6 +23,18 @@ may go to the sibling leaf, as it does in ``evaluate``.  The mode of a leaf come
 ``leaf_mode`` (``set_leaf_modes``; ``ExplicitMPC.compile`` attaches it, ``save`` / ``load`` keep
 it): like the plant it is an attachment for rollouts, not part of the law.  Laws with test nodes
 and laws with more than four inputs have no rollout.  No CPU fallback.
+
+    single = law.to_single()                      # or ExplicitMPC.compile(dtype=np.float32)
+
+is the same law with its internal and leaf records in single precision (``dtype`` np.float32), as a
+flight computer holds it: a new, independent ``CompiledLaw`` with everything above.  The root is
+still chosen in double on the double state (and the rollout's exit test made there), so both laws
+choose the same root for every state; below it xs = (float) x, the plane sums and the leaf map run
+in float, one rounding per product and per sum, left iff s >= -2^-23, and u is widened to double.
+A turn can differ from the double law's only where |s| is within the rounding bound of the sum,
+and in the same leaf the inputs differ by at most a like bound (DESIGN.md 3.8c states both).  Laws
+with test nodes, and laws a value of which overflows or leaves the normal range of a float, have
+no single form (``EhmError``, EHM_E_INVALID).  ``save`` marks the file with the key ``precision``.
 """
 
 import ctypes
@@ -38,6 +50,17 @@ HEADER = ('version', 'p', 'n_u', 'n_roots', 'n_int', 'n_leaf', 'n_test', 'node_s
           'leaf_stride', 'side_stride', 'has_nbr', 'n_source_nodes')
 ARRAYS = ('node', 'leaf_rec', 'leaf_node', 'test_rec', 'root_rec', 'root_entry', 'nbr')
 _INT_ARRAYS = ('leaf_node', 'root_entry', 'nbr')
+_NARROWED = ('node', 'leaf_rec')        # float32 in a single law; everything else as in a double one
+
+
+def node_stride32(p):
+    """Floats of an internal record of a single law: [a (p) | b | left, right] rounded up to 32 B."""
+    return 8 * ((p + 3 + 7) // 8)
+
+
+def leaf_stride32(p, n_u):
+    """Floats of a leaf record of a single law: [v_0 | u_0 | K] rounded up to 16 B."""
+    return 4 * ((p + n_u + n_u * p + 3) // 4)
 
 
 def _check(rc):
@@ -53,9 +76,21 @@ def _shapes(h):
             'nbr': (h['n_roots'] if h['has_nbr'] else 0, h['p'] + 1)}
 
 
+def precision_of(arrays):
+    """32 if ``arrays`` are a single law's (node and leaf_rec float32), else 64; ``EhmError`` if only
+    one of the two is float32."""
+    single = [np.asarray(arrays[k]).dtype == np.float32 for k in _NARROWED]
+    if single[0] != single[1]:
+        raise _capi.EhmError(_capi.EHM_E_INVALID, 'compiled law: node is %s, leaf_rec %s' % tuple(
+            np.asarray(arrays[k]).dtype for k in _NARROWED))
+    return 32 if single[0] else 64
+
+
 def _marshal(arrays):
-    """(header int64 [12], the seven arrays contiguous in their dtypes); the arrays must have the
-    sizes the header states -- the library reads that many elements."""
+    """(header int64 [12], the seven arrays contiguous in their dtypes, precision); the arrays must
+    have the sizes the header states -- the library reads that many elements."""
+    precision = precision_of(arrays)
+    real = {k: np.float32 if precision == 32 and k in _NARROWED else np.float64 for k in ARRAYS}
     header = np.ascontiguousarray(arrays['header'], dtype=np.int64).ravel()
     if header.size != len(HEADER) or (header[1:] < 0).any() or (header > 1 << 40).any():
         raise _capi.EhmError(_capi.EHM_E_INVALID, 'compiled law: bad header')
@@ -63,12 +98,17 @@ def _marshal(arrays):
     out = []
     for name, shape in _shapes(h).items():
         a = np.ascontiguousarray(arrays[name],
-                                 dtype=np.int32 if name in _INT_ARRAYS else np.float64)
+                                 dtype=np.int32 if name in _INT_ARRAYS else real[name])
         if a.size != int(np.prod(shape)):
             raise _capi.EhmError(_capi.EHM_E_INVALID, 'compiled law: %s has %d elements, the '
                                  'header states %s' % (name, a.size, shape))
         out.append(a.reshape(shape))
-    return header, out
+    if precision == 32:
+        if out[3].size:
+            raise _capi.EhmError(_capi.EHM_E_INVALID, 'compiled law: a single-precision law has '
+                                 'no test records')
+        del out[3]              # the _single entry points take no test_rec
+    return header, out, precision
 
 
 def check_leaf_mode(leaf_mode, n_leaf):
@@ -97,6 +137,20 @@ def read_file(path):
                 path, ', '.join(missing)))
         arrays = {k: z[k] for k in ('header',) + ARRAYS}
         leaf_mode = z['leaf_mode'] if 'leaf_mode' in z.files else None
+        precision = int(z['precision']) if 'precision' in z.files else None
+    if precision is None:
+        # a file from before the key: a double law, whatever dtype its arrays were stored in
+        for k in _NARROWED:
+            arrays[k] = np.asarray(arrays[k], dtype=np.float64)
+    else:
+        if precision not in (32, 64):
+            raise _capi.EhmError(_capi.EHM_E_INVALID, 'compiled law: %s states precision %d (32 '
+                                 'or 64)' % (path, precision))
+        want = np.float32 if precision == 32 else np.float64
+        for k in _NARROWED:
+            if arrays[k].dtype != want:
+                raise _capi.EhmError(_capi.EHM_E_INVALID, 'compiled law: %s states precision %d, '
+                                     'its %s is %s' % (path, precision, k, arrays[k].dtype))
     if leaf_mode is not None:
         header = np.asarray(arrays['header']).ravel()
         if header.size != len(HEADER):
@@ -105,12 +159,25 @@ def read_file(path):
     return arrays, leaf_mode
 
 
+def write_file(path, arrays, leaf_mode=None):
+    """What ``CompiledLaw.save`` writes, from ``arrays`` on the host: the format version, the
+    arrays, ``leaf_mode`` if given, and for a single law (``precision_of``) the key ``precision`` =
+    32.  A double law's file carries no such key: it is the file every earlier version wrote."""
+    extra = {} if leaf_mode is None else {'leaf_mode': leaf_mode}
+    if precision_of(arrays) == 32:
+        extra['precision'] = np.int64(32)
+    with open(path, 'wb') as f:
+        np.savez(f, format_version=np.int64(FORMAT_VERSION), **arrays, **extra)
+
+
 def validate_arrays(arrays):
     """Raises ``EhmError`` (EHM_E_INVALID) unless ``arrays`` (``CompiledLaw.arrays()``) are a
-    well-formed compiled law: the library's check of ehm_compiled_import, on the host."""
-    header, arrs = _marshal(arrays)
-    _check(_capi.load().ehm_compiled_validate(ptr(header), *[ptr(a) if a.size else None
-                                                             for a in arrs]))
+    well-formed compiled law of their precision: the library's check of ehm_compiled_import /
+    _import_single, on the host."""
+    header, arrs, precision = _marshal(arrays)
+    fn = _capi.load().ehm_compiled_validate_single if precision == 32 else \
+        _capi.load().ehm_compiled_validate
+    _check(fn(ptr(header), *[ptr(a) if a.size else None for a in arrs]))
 
 
 class CompiledLaw:
@@ -123,9 +190,10 @@ class CompiledLaw:
     _rollout_plant = None       # the plant the device holds (set_plant)
     _leaf_node = None
 
-    def __init__(self, handle, device, compile_seconds=0.):
+    def __init__(self, handle, device, compile_seconds=0., dtype=np.float64):
         self._lib = _capi.load()
         self._handle = handle
+        self.dtype = np.dtype(dtype).type       # np.float64, or np.float32 for a single law
         self.device = int(device)
         self.compile_seconds = float(compile_seconds)
         info = (ctypes.c_int64 * 14)()
@@ -151,16 +219,32 @@ class CompiledLaw:
     def from_arrays(cls, arrays, device=0):
         """A law from ``arrays()``.  ``ehm_compiled_import`` validates what it is given before
         anything reaches the device (``validate_arrays`` is the same check without a device)."""
-        header, arrs = _marshal(arrays)
+        header, arrs, precision = _marshal(arrays)
         handle = ctypes.c_void_p()
-        _check(_capi.load().ehm_compiled_import(int(device), ptr(header),
-                                                *[ptr(a) if a.size else None for a in arrs],
-                                                ctypes.byref(handle)))
-        return cls(handle, device)
+        fn = _capi.load().ehm_compiled_import_single if precision == 32 else \
+            _capi.load().ehm_compiled_import
+        _check(fn(int(device), ptr(header), *[ptr(a) if a.size else None for a in arrs],
+                  ctypes.byref(handle)))
+        return cls(handle, device, dtype=np.float32 if precision == 32 else np.float64)
+
+    def to_single(self):
+        """The law in single precision: a new, independent ``CompiledLaw`` (``dtype`` np.float32)
+        whose internal and leaf records were rounded to nearest float on the device
+        (ehm_compiled_narrow).  It keeps ``mpc`` and the leaf modes.  ``EhmError`` for a law with
+        test nodes, or one a value of which overflows, becomes zero or subnormal, or whose plane
+        loses its normal."""
+        handle = ctypes.c_void_p()
+        _check(self._lib.ehm_compiled_narrow(self._handle, ctypes.byref(handle)))
+        law = type(self)(handle, self.device, self.compile_seconds, dtype=np.float32)
+        law.mpc = self.mpc
+        if self.leaf_mode is not None:
+            law.set_leaf_modes(self.leaf_mode)
+        return law
 
     @classmethod
     def load(cls, path, device=0):
-        """The law ``save`` wrote (one .npz of plain arrays)."""
+        """The law ``save`` wrote (one .npz of plain arrays): a single law where the file says
+        ``precision`` = 32."""
         arrays, leaf_mode = read_file(path)
         law = cls.from_arrays(arrays, device=device)
         if leaf_mode is not None:
@@ -169,31 +253,43 @@ class CompiledLaw:
 
     def save(self, path):
         """Writes the arrays and the format version to ``path`` (.npz); a law that holds leaf
-        modes also writes the optional key ``leaf_mode``."""
-        extra = {} if self.leaf_mode is None else {'leaf_mode': self.leaf_mode}
-        with open(path, 'wb') as f:
-            np.savez(f, format_version=np.int64(FORMAT_VERSION), **self.arrays(), **extra)
+        modes also writes the optional key ``leaf_mode``, a single law ``precision`` = 32 and its
+        ``node`` and ``leaf_rec`` as float32."""
+        write_file(path, self.arrays(), self.leaf_mode)
 
     def arrays(self):
         """dict: 'header' (int64 [12], ``HEADER``) and the arrays of ``ARRAYS`` (include/ehmpc.h),
-        copied from the device."""
+        copied from the device; ``node`` and ``leaf_rec`` of a single law are float32."""
         out = {'header': np.array([self._h[k] for k in HEADER], dtype=np.int64)}
+        single = self.dtype is np.float32
         for name, shape in _shapes(self._h).items():
-            out[name] = np.zeros(shape, dtype=np.int32 if name in _INT_ARRAYS else np.float64)
-        _check(self._lib.ehm_compiled_export(self._handle, *[ptr(out[k]) if out[k].size else None
-                                                             for k in ARRAYS]))
+            real = np.float32 if single and name in _NARROWED else np.float64
+            out[name] = np.zeros(shape, dtype=np.int32 if name in _INT_ARRAYS else real)
+        self._export(*[ptr(out[k]) if out[k].size else None for k in ARRAYS])
         return out
+
+    def _export(self, node, leaf_rec, leaf_node, test_rec, root_rec, root_entry, nbr):
+        if self.dtype is np.float32:
+            _check(self._lib.ehm_compiled_export_single(self._handle, node, leaf_rec, leaf_node,
+                                                   root_rec, root_entry, nbr))
+        else:
+            _check(self._lib.ehm_compiled_export(self._handle, node, leaf_rec, leaf_node,
+                                                 test_rec, root_rec, root_entry, nbr))
 
     @property
     def stats(self):
         """Record counts, strides in bytes, ``bytes`` the law holds on the device and
         ``source_bytes``, what the source evaluator holds for the same tree (0 for a loaded law).
         bytes = (n_plane + n_test) node_stride + n_leaf (leaf_stride + 4) + n_test side_stride
-        + n_roots (side_stride + 4) + nbr_bytes."""
+        + n_roots (side_stride + 4) + nbr_bytes.  A double law: node_stride = 64 (p <= 6) or 128,
+        leaf_stride = 8 (p + n_u + n_u p) rounded up to 16.  A single law: node_stride =
+        4 (p + 3) rounded up to 32 (32 for p <= 5, else 64), leaf_stride = 4 (p + n_u + n_u p)
+        rounded up to 16, n_test = 0.  side_stride = 8 (p + p^2) rounded up to 16 in both."""
         h = self._h
+        scalar = 4 if self.dtype is np.float32 else 8
         return {'n_plane': h['n_int'] - h['n_test'], 'n_test': h['n_test'], 'n_leaf': h['n_leaf'],
-                'n_roots': h['n_roots'], 'node_stride': 8 * h['node_stride'],
-                'leaf_stride': 8 * h['leaf_stride'], 'side_stride': 8 * h['side_stride'],
+                'n_roots': h['n_roots'], 'node_stride': scalar * h['node_stride'],
+                'leaf_stride': scalar * h['leaf_stride'], 'side_stride': 8 * h['side_stride'],
                 'nbr_bytes': 4 * h['n_roots'] * (h['p'] + 1) if h['has_nbr'] else 0,
                 'bytes': self._bytes, 'source_bytes': self._source_bytes}
 
@@ -231,8 +327,7 @@ class CompiledLaw:
         """int32 [n_leaf]: the source node id of every leaf (ascending)."""
         if self._leaf_node is None:
             out = np.zeros(self._h['n_leaf'], dtype=np.int32)
-            _check(self._lib.ehm_compiled_export(self._handle, None, None, ptr(out), None, None,
-                                                 None, None))
+            self._export(None, None, ptr(out), None, None, None, None)
             self._leaf_node = out
         return self._leaf_node
 

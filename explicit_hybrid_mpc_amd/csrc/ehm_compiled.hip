@@ -37,34 +37,17 @@
 #include <vector>
 
 #include "../../include/ehmpc.h"
+#include "ehm_compiled_dev.h"
 #include "ehm_explicit_view.h"
 #include "ehm_host.h"
-#include "ehm_rollout_dev.h"
 
-#define EHM_CP 8                 // max parameter dimension (EHM_MAX_P)
-#define EHM_C_LOCATE_MIN 128     // as EHM_X_LOCATE_MIN: spines at least this long get the locator
-#define EHM_C_STRICT 1e-9        // as EHM_X_STRICT
-#define EHM_C_STEPS 96           // as EHM_X_STEPS
 #define EHM_C_VERSION 1          // format of the arrays (ehm_compiled_export / _import)
 #define EHM_C_HEADER 12          // int64 entries of the header
-#define EHM_C_EPS 2.220446049250313e-16
+
+// the kernels of the single-precision law (ehm_compiled32.hip)
+extern "C" const ehm::Compiled32Api* ehm_compiled32_api();
 
 namespace {
-
-// doubles per internal record, per leaf record, per [v0 | inv(E)] record
-__host__ __device__ inline int node_stride_of(int p) { return p <= 6 ? 8 : 16; }
-inline int leaf_stride_of(int p, int n_u) { return ((p + n_u + n_u * p + 1) / 2) * 2; }
-inline int side_stride_of(int p) { return ((p + p * p + 1) / 2) * 2; }
-
-struct DevCompiled {
-    const double* node;
-    const double* leaf_rec;
-    const int32_t* leaf_node;
-    const double* test_rec;
-    const double* root_rec;
-    const int32_t* root_entry;
-    int leaf_stride, side_stride, p, n_u, n_roots;
-};
 
 // ---- compile kernels: one thread per source node -------------------------------------------------
 
@@ -183,26 +166,6 @@ __global__ void k_compiled_roots(int n_roots, int p, int rec_stride, int side_st
 }
 
 // ---- evaluation ----------------------------------------------------------------------------------
-
-// The sums of `contains` / `weights` of ehm_explicit.hip (their products fused into the sums, as the
-// compiler fuses them there), written out: a = fma(Minv[q][c], x_c - v0_c, a) from 0.0.
-template <int P>
-__device__ __forceinline__ bool c_contains(const double* __restrict__ r, const double* x) {
-    double d[P];
-#pragma unroll
-    for (int c = 0; c < P; ++c) d[c] = x[c] - r[c];
-    double s = 0.0;
-#pragma unroll
-    for (int q = 0; q < P; ++q) {
-        double a = 0.0;
-#pragma unroll
-        for (int c = 0; c < P; ++c) a = fma(r[P + q * P + c], d[c], a);
-        if (!((a >= -EHM_C_EPS) && (a <= 1.0 + EHM_C_EPS))) return false;
-        s += a;
-    }
-    const double a0 = 1.0 - s;
-    return (a0 >= -EHM_C_EPS) && (a0 <= 1.0 + EHM_C_EPS);
-}
 
 // k_explicit_locate on the compiled law's own root records: a visibility walk over the face
 // adjacency, root[q] = found | steps << 20, or -1 (the serial walk decides).
@@ -332,138 +295,11 @@ __global__ __launch_bounds__(256) void k_compiled_eval(DevCompiled C, long long 
     if (depth_out) depth_out[q] = visited;
 }
 
-// ---- fused closed-loop rollout ---------------------------------------------------------------------
-
-// (alpha, a0) of x in the [v0 | inv(E)] record r: the sums of c_contains / k_compiled_locate
-template <int P>
-__device__ __forceinline__ void c_weights(const double* __restrict__ r, const double* x,
-                                          double* alpha, double& a0) {
-    double d[P];
-#pragma unroll
-    for (int c = 0; c < P; ++c) d[c] = x[c] - r[c];
-    double s = 0.0;
-#pragma unroll
-    for (int i = 0; i < P; ++i) {
-        double a = 0.0;
-#pragma unroll
-        for (int c = 0; c < P; ++c) a = fma(r[P + i * P + c], d[c], a);
-        alpha[i] = a;
-        s += a;
-    }
-    a0 = 1.0 - s;
-}
-
-// The step of k_explicit_rollout around the compiled law.  Laws without test nodes
-// only (ehm_compiled_set_plant refuses the others): a state its root holds ends, by the signs of the
-// planes, in a leaf that holds it to rounding, so the exit test is made once, on the root's weights.
-template <int P, int NU, PlantKind KIND>
-__global__ __launch_bounds__(256) void k_compiled_rollout(DevCompiled C, DevPlant PL, RollArgs R,
-                                                          DevNoise NZ, DevGuard GD) {
-#pragma clang fp contract(off)
-    constexpr int NS = P <= 6 ? 8 : 16;
-    constexpr int NL = (P + 3) / 2;
-    extern __shared__ double sh[];
-    rollout_load<KIND>(PL, NZ, sh);
-    __syncthreads();
-    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= R.n) return;
-    RollState<P, NU> S;
-    double z[P], alpha[P], u[NU], a0;
-    const uint64_t id = NZ.traj0 + (uint64_t)q;
-    rollout_begin<P, NU>(R, q, S);
-    int status = 0, t = 0;
-    int kr = (int)(q % C.n_roots);          // the visibility walk starts at the last step's root
-    for (; t < R.T; ++t) {
-        rollout_measure<P, NU, KIND>(PL, R, NZ, sh, q, t, id, S, z);
-        // root: k_compiled_locate from kr, else the serial rule of k_compiled_eval
-        bool found = false;
-        if (R.nbr) {
-            int kw = kr;
-            for (int step = 0; step < EHM_C_STEPS; ++step) {
-                c_weights<P>(C.root_rec + (size_t)kw * C.side_stride, z, alpha, a0);
-                double lo = a0;
-                int at = 0;
-#pragma unroll
-                for (int i = 0; i < P; ++i)
-                    if (alpha[i] < lo) {
-                        lo = alpha[i];
-                        at = i + 1;
-                    }
-                if (lo > EHM_C_STRICT) {
-                    found = true;
-                    break;
-                }
-                if (lo >= -EHM_C_STRICT) break;
-                const int k2 = R.nbr[(size_t)kw * (P + 1) + at];
-                if (k2 < 0) break;
-                kw = k2;
-            }
-            if (found) kr = kw;
-        }
-        if (!found) {
-            kr = C.n_roots - 1;
-            for (int r = 0; r + 1 < C.n_roots; ++r)
-                if (c_contains<P>(C.root_rec + (size_t)r * C.side_stride, z)) {
-                    kr = r;
-                    break;
-                }
-            c_weights<P>(C.root_rec + (size_t)kr * C.side_stride, z, alpha, a0);
-        }
-        // exit test on the root's weights (a NaN state fails it)
-        bool inside = a0 >= -R.tol_exit;
-#pragma unroll
-        for (int i = 0; i < P; ++i) inside = inside && (alpha[i] >= -R.tol_exit);
-        if (!inside) {
-            status = 1;
-            break;
-        }
-        // the walk of k_compiled_eval (plane nodes only)
-        int k = C.root_entry[kr];
-        while (k >= 0) {
-            const double2* nd = reinterpret_cast<const double2*>(C.node + (size_t)k * NS);
-            double r[2 * NL];
-#pragma unroll
-            for (int i = 0; i < NL; ++i) {
-                const double2 w = nd[i];
-                r[2 * i] = w.x;
-                r[2 * i + 1] = w.y;
-            }
-            const long long ch = __double_as_longlong(r[P + 1]);
-            double s = 0.0;
-#pragma unroll
-            for (int c = 0; c < P; ++c) s = s + r[c] * z[c];
-            s = s + r[P];
-            k = (s >= -EHM_C_EPS) ? (int)(ch & 0xffffffffll) : (int)(ch >> 32);
-        }
-        const int l = ~k;
-        const double* lr = C.leaf_rec + (size_t)l * C.leaf_stride;
-        const double2* lv = reinterpret_cast<const double2*>(lr);
-        double d[P];
-#pragma unroll
-        for (int c = 0; c + 1 < P; c += 2) {
-            const double2 w = lv[c / 2];
-            d[c] = z[c] - w.x;
-            d[c + 1] = z[c + 1] - w.y;
-        }
-        if (P % 2) d[P - 1] = z[P - 1] - lr[P - 1];
-        const double* Kc = lr + P + NU;
-#pragma unroll
-        for (int c = 0; c < NU; ++c) {
-            double w = 0.0;
-#pragma unroll
-            for (int i = 0; i < P; ++i) w = w + Kc[c * P + i] * d[i];
-            u[c] = lr[P + c] + w;
-        }
-        status = rollout_apply<P, NU, KIND>(PL, R, NZ, GD, sh, q, t, id, R.mode[l],
-                                            C.leaf_node[l], u, S);
-        if (status) break;
-    }
-    rollout_finish<P, NU, KIND>(PL, R, q, t, status, S);
-}
+// ---- dispatch tables (k_compiled_rollout: ehm_compiled_dev.h) ------------------------------------------
 
 typedef void (*rollout_fn)(DevCompiled, DevPlant, RollArgs, DevNoise, DevGuard);
-#define EHM_R_NU(P, K) &k_compiled_rollout<P, 1, K>, &k_compiled_rollout<P, 2, K>, \
-                       &k_compiled_rollout<P, 3, K>, &k_compiled_rollout<P, 4, K>
+#define EHM_R_NU(P, K) &k_compiled_rollout<double, P, 1, K>, &k_compiled_rollout<double, P, 2, K>, \
+                       &k_compiled_rollout<double, P, 3, K>, &k_compiled_rollout<double, P, 4, K>
 #define EHM_R_ALL(K) {{EHM_R_NU(1, K)}, {EHM_R_NU(2, K)}, {EHM_R_NU(3, K)}, {EHM_R_NU(4, K)}, \
                       {EHM_R_NU(5, K)}, {EHM_R_NU(6, K)}, {EHM_R_NU(7, K)}, {EHM_R_NU(8, K)}}
 // [kind][p - 1][n_u - 1]
@@ -471,6 +307,21 @@ const rollout_fn k_rollout_table[PK_KINDS][EHM_CP][EHM_R_MAX_NU] = {
     EHM_R_ALL(PK_NOMINAL), EHM_R_ALL(PK_NOISY), EHM_R_ALL(PK_GUARDED)};
 #undef EHM_R_ALL
 #undef EHM_R_NU
+
+// the same table of the single law's instances: the kernels of ehm_compiled32.hip under the types
+// rollout_run launches them with
+typedef void (*rollout32_fn)(DevLaw<float>, DevPlant, RollArgs, DevNoise, DevGuard);
+struct Rollout32Table {
+    rollout32_fn fn[PK_KINDS][EHM_CP][EHM_R_MAX_NU];
+    Rollout32Table() {
+        const ehm::Compiled32Api* api = ehm_compiled32_api();
+        for (int k = 0; k < PK_KINDS; ++k)
+            for (int p = 0; p < EHM_CP; ++p)
+                for (int u = 0; u < EHM_R_MAX_NU; ++u)
+                    fn[k][p][u] = reinterpret_cast<rollout32_fn>(
+                        const_cast<void*>(api->rollout[k][p][u]));
+    }
+};
 
 typedef void (*locate_fn)(DevCompiled, long long, const double*, const int32_t*, int32_t*);
 typedef void (*eval_fn)(DevCompiled, long long, const double*, double*, int32_t*, int32_t*,
@@ -512,9 +363,18 @@ int cfail(int code, const char* fmt, ...) {
 // leaf_stride, side_stride, has_nbr, n_source_nodes]
 enum { H_VERSION, H_P, H_NU, H_ROOTS, H_INT, H_LEAF, H_TEST, H_NS, H_LS, H_SS, H_NBR, H_SRC };
 
-bool all_finite(const double* a, size_t n) {
+template <class T>
+bool all_finite(const T* a, size_t n) {
     for (size_t i = 0; i < n; ++i)
         if (!std::isfinite(a[i])) return false;
+    return true;
+}
+
+// a single law holds zeros and normal floats only: its arithmetic must not depend on how a device
+// treats subnormal numbers
+bool all_normal(const float* a, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (a[i] != 0.0f && !std::isnormal(a[i])) return false;
     return true;
 }
 
@@ -522,10 +382,14 @@ bool entry_ok(int64_t c, int64_t n_int, int64_t n_leaf) {
     return c >= 0 ? c < n_int : ~c < n_leaf;
 }
 
-// A file is untrusted input: every index the kernels follow is checked here.
-int validate(const int64_t* h, const double* node, const double* leaf_rec,
+// A file is untrusted input: every index the kernels follow is checked here.  T = float: the arrays
+// of a single law (node and leaf_rec in floats at their own strides, no test nodes, no zero normal,
+// no subnormal value).
+template <class T>
+int validate(const int64_t* h, const T* node, const T* leaf_rec,
              const int32_t* leaf_node, const double* test_rec, const double* root_rec,
              const int32_t* root_entry, const int32_t* nbr) {
+    constexpr bool SINGLE = sizeof(T) == sizeof(float);
     if (!h) return cfail(EHM_E_INVALID, "compiled law: no header");
     if (h[H_VERSION] != EHM_C_VERSION)
         return cfail(EHM_E_INVALID, "compiled law: format version %lld (this library reads %d)",
@@ -540,7 +404,11 @@ int validate(const int64_t* h, const double* node, const double* leaf_rec,
         n_int >= lim || n_leaf >= lim || n_roots > n_int + n_leaf || h[H_SRC] < n_leaf ||
         h[H_SRC] >= lim)
         return cfail(EHM_E_INVALID, "compiled law: bad counts");
-    const int ns = node_stride_of((int)p), ls = leaf_stride_of((int)p, (int)n_u),
+    if (SINGLE && n_test > 0)
+        return cfail(EHM_E_INVALID, "compiled law: a single-precision law has no test nodes (%lld)",
+                     (long long)n_test);
+    const int ns = SINGLE ? node_stride32_of((int)p) : node_stride_of((int)p),
+              ls = SINGLE ? leaf_stride32_of((int)p, (int)n_u) : leaf_stride_of((int)p, (int)n_u),
               ss = side_stride_of((int)p);
     if (h[H_NS] != ns || h[H_LS] != ls || h[H_SS] != ss)
         return cfail(EHM_E_INVALID, "compiled law: record strides %lld / %lld / %lld, not "
@@ -555,7 +423,7 @@ int validate(const int64_t* h, const double* node, const double* leaf_rec,
         !root_entry || (h[H_NBR] && !nbr))
         return cfail(EHM_E_INVALID, "compiled law: an array is missing");
     for (int64_t k = 0; k < n_int; ++k) {
-        const double* r = node + (size_t)k * ns;
+        const T* r = node + (size_t)k * ns;
         if (!all_finite(r, (size_t)p + 1))
             return cfail(EHM_E_INVALID, "compiled law: node %lld is not finite", (long long)k);
         int32_t ch[2];
@@ -572,6 +440,14 @@ int validate(const int64_t* h, const double* node, const double* leaf_rec,
         if (zero && !(bits && r[p] >= 0.0 && r[p] < (double)n_test && r[p] == std::floor(r[p])))
             return cfail(EHM_E_INVALID, "compiled law: node %lld has a zero normal and names no "
                          "test record", (long long)k);
+    }
+    if constexpr (SINGLE) {
+        bool normal = all_normal(leaf_rec, (size_t)n_leaf * ls);
+        for (int64_t k = 0; k < n_int && normal; ++k)
+            normal = all_normal(node + (size_t)k * ns, (size_t)p + 1);
+        if (!normal)
+            return cfail(EHM_E_INVALID, "compiled law: a single-precision record holds a "
+                         "subnormal or non-finite value");
     }
     if (!all_finite(leaf_rec, (size_t)n_leaf * ls) || (n_test && !all_finite(test_rec, (size_t)n_test * ss)) ||
         !all_finite(root_rec, (size_t)n_roots * ss))
@@ -596,7 +472,9 @@ int validate(const int64_t* h, const double* node, const double* leaf_rec,
 
 struct ehm_compiled {
     int device = 0;
-    DevCompiled d{};
+    bool single = false;        // node and leaf_rec hold floats (ehm_compiled_narrow, _import_single)
+    DevCompiled d{};            // a single law: its root arrays only (the locator)
+    DevLaw<float> d32{};        // a single law
     int64_t h[EHM_C_HEADER] = {};
     int64_t source_bytes = 0;
     DevBuf node, leaf_rec, leaf_node, test_rec, root_rec, root_entry, nbr;
@@ -605,8 +483,9 @@ struct ehm_compiled {
     RolloutAttach ro;   // plant, leaf modes and model of the rollouts: not part of the law
     Stream stream;
 
-    size_t node_bytes() const { return (size_t)h[H_INT] * h[H_NS] * sizeof(double); }
-    size_t leaf_bytes() const { return (size_t)h[H_LEAF] * h[H_LS] * sizeof(double); }
+    size_t scalar() const { return single ? sizeof(float) : sizeof(double); }
+    size_t node_bytes() const { return (size_t)h[H_INT] * h[H_NS] * scalar(); }
+    size_t leaf_bytes() const { return (size_t)h[H_LEAF] * h[H_LS] * scalar(); }
     size_t leaf_node_bytes() const { return (size_t)h[H_LEAF] * sizeof(int32_t); }
     size_t test_bytes() const { return (size_t)h[H_TEST] * h[H_SS] * sizeof(double); }
     size_t root_bytes() const { return (size_t)h[H_ROOTS] * h[H_SS] * sizeof(double); }
@@ -619,8 +498,8 @@ struct ehm_compiled {
                entry_bytes() + nbr_bytes();
     }
     void bind() {
-        d.node = node.as<const double>();
-        d.leaf_rec = leaf_rec.as<const double>();
+        d.node = single ? nullptr : node.as<const double>();
+        d.leaf_rec = single ? nullptr : leaf_rec.as<const double>();
         d.leaf_node = leaf_node.as<const int32_t>();
         d.test_rec = test_rec.as<const double>();
         d.root_rec = root_rec.as<const double>();
@@ -630,8 +509,73 @@ struct ehm_compiled {
         d.p = (int)h[H_P];
         d.n_u = (int)h[H_NU];
         d.n_roots = (int)h[H_ROOTS];
+        d32 = DevLaw<float>{single ? node.as<const float>() : nullptr,
+                            single ? leaf_rec.as<const float>() : nullptr,
+                            d.leaf_node, d.test_rec, d.root_rec, d.root_entry,
+                            d.leaf_stride, d.side_stride, d.p, d.n_u, d.n_roots};
     }
 };
+
+namespace {
+
+typedef std::unique_ptr<ehm_compiled, int (*)(ehm_compiled*)> LawPtr;
+
+// ehm_compiled_import / _import_single
+template <class T>
+int import_law(int device, const int64_t* header, const T* node, const T* leaf_rec,
+               const int32_t* leaf_node, const double* test_rec, const double* root_rec,
+               const int32_t* root_entry, const int32_t* nbr, ehm_compiled** out) {
+    if (!out) return cfail(EHM_E_INVALID, "import: bad argument");
+    *out = nullptr;
+    const int rc = validate(header, node, leaf_rec, leaf_node, test_rec, root_rec, root_entry, nbr);
+    if (rc != EHM_OK) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+        return cfail(EHM_E_NO_DEVICE, "no HIP device %d (libehmpc has no CPU fallback)", device);
+    LawPtr C(new ehm_compiled(), ehm_compiled_destroy);
+    C->device = device;
+    C->single = sizeof(T) == sizeof(float);
+    std::memcpy(C->h, header, sizeof C->h);
+    C_TRY(hipSetDevice(device));
+    C_TRY(C->stream.create());
+    C_TRY(C->node.upload(node, C->node_bytes()));
+    C_TRY(C->leaf_rec.upload(leaf_rec, C->leaf_bytes()));
+    C_TRY(C->leaf_node.upload(leaf_node, C->leaf_node_bytes()));
+    C_TRY(C->test_rec.upload(test_rec, C->test_bytes()));
+    C_TRY(C->root_rec.upload(root_rec, C->root_bytes()));
+    C_TRY(C->root_entry.upload(root_entry, C->entry_bytes()));
+    if (header[H_NBR]) C_TRY(C->nbr.upload(nbr, C->nbr_bytes()));
+    C->bind();
+    *out = C.release();
+    return EHM_OK;
+}
+
+// ehm_compiled_export / _export_single
+int export_law(ehm_compiled* C, bool single, void* node, void* leaf_rec, int32_t* leaf_node,
+               double* test_rec, double* root_rec, int32_t* root_entry, int32_t* nbr) {
+    if (!C) return cfail(EHM_E_INVALID, "export: bad argument");
+    if (C->single != single)
+        return cfail(EHM_E_INVALID, "export: the law is in %s precision (ehm_compiled_export%s)",
+                     C->single ? "single" : "double", C->single ? "_single" : "");
+    C_TRY(hipSetDevice(C->device));
+    struct {
+        void* host;
+        const DevBuf* buf;
+        size_t bytes;
+    } parts[] = {{node, &C->node, C->node_bytes()},
+                 {leaf_rec, &C->leaf_rec, C->leaf_bytes()},
+                 {leaf_node, &C->leaf_node, C->leaf_node_bytes()},
+                 {test_rec, &C->test_rec, C->test_bytes()},
+                 {root_rec, &C->root_rec, C->root_bytes()},
+                 {root_entry, &C->root_entry, C->entry_bytes()},
+                 {nbr, &C->nbr, C->nbr_bytes()}};
+    for (const auto& part : parts)
+        if (part.host && part.bytes)
+            C_TRY(hipMemcpy(part.host, part.buf->ptr, part.bytes, hipMemcpyDeviceToHost));
+    return EHM_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -653,8 +597,7 @@ int ehm_compiled_create(ehm_explicit* src, const double* vertices, ehm_compiled*
     const int p = v.p, n_u = v.n_u;
     const int64_t n = v.n_nodes;
     if (n >= ((int64_t)1 << 31)) return cfail(EHM_E_INVALID, "compile: %lld nodes", (long long)n);
-    std::unique_ptr<ehm_compiled, int (*)(ehm_compiled*)> C(new ehm_compiled(),
-                                                            ehm_compiled_destroy);
+    LawPtr C(new ehm_compiled(), ehm_compiled_destroy);
     C->device = v.device;
     C_TRY(hipSetDevice(v.device));
     C_TRY(C->stream.create());
@@ -759,30 +702,95 @@ int ehm_compiled_validate(const int64_t* header, const double* node, const doubl
     return validate(header, node, leaf_rec, leaf_node, test_rec, root_rec, root_entry, nbr);
 }
 
+int ehm_compiled_validate_single(const int64_t* header, const float* node, const float* leaf_rec,
+                            const int32_t* leaf_node, const double* root_rec,
+                            const int32_t* root_entry, const int32_t* nbr) {
+    return validate(header, node, leaf_rec, leaf_node, (const double*)nullptr, root_rec, root_entry,
+                    nbr);
+}
+
 int ehm_compiled_import(int device, const int64_t* header, const double* node,
                         const double* leaf_rec, const int32_t* leaf_node, const double* test_rec,
                         const double* root_rec, const int32_t* root_entry, const int32_t* nbr,
                         ehm_compiled** out) {
-    if (!out) return cfail(EHM_E_INVALID, "import: bad argument");
+    return import_law(device, header, node, leaf_rec, leaf_node, test_rec, root_rec, root_entry,
+                      nbr, out);
+}
+
+int ehm_compiled_import_single(int device, const int64_t* header, const float* node,
+                          const float* leaf_rec, const int32_t* leaf_node, const double* root_rec,
+                          const int32_t* root_entry, const int32_t* nbr, ehm_compiled** out) {
+    return import_law(device, header, node, leaf_rec, leaf_node, (const double*)nullptr, root_rec,
+                      root_entry, nbr, out);
+}
+
+// The single-precision law of a double law: a new handle with the records narrowed on the device.
+int ehm_compiled_narrow(ehm_compiled* src, ehm_compiled** out) {
+    if (!src || !out) return cfail(EHM_E_INVALID, "narrow: bad argument");
     *out = nullptr;
-    const int rc = validate(header, node, leaf_rec, leaf_node, test_rec, root_rec, root_entry, nbr);
-    if (rc != EHM_OK) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return cfail(EHM_E_NO_DEVICE, "no HIP device %d (libehmpc has no CPU fallback)", device);
-    std::unique_ptr<ehm_compiled, int (*)(ehm_compiled*)> C(new ehm_compiled(),
-                                                            ehm_compiled_destroy);
-    C->device = device;
-    std::memcpy(C->h, header, sizeof C->h);
-    C_TRY(hipSetDevice(device));
+    if (src->single) return cfail(EHM_E_INVALID, "narrow: the law is in single precision already");
+    if (src->h[H_TEST] > 0)
+        return cfail(EHM_E_INVALID, "narrow: the law has %lld test nodes (children that are no "
+                     "bisection); only a walk by planes alone has a single-precision form",
+                     (long long)src->h[H_TEST]);
+    const int p = src->d.p, n_u = src->d.n_u;
+    LawPtr C(new ehm_compiled(), ehm_compiled_destroy);
+    C->device = src->device;
+    C->single = true;
+    std::memcpy(C->h, src->h, sizeof C->h);
+    C->h[H_NS] = node_stride32_of(p);
+    C->h[H_LS] = leaf_stride32_of(p, n_u);
+    C->source_bytes = src->source_bytes;
+    C_TRY(hipSetDevice(C->device));
     C_TRY(C->stream.create());
-    C_TRY(C->node.upload(node, C->node_bytes()));
-    C_TRY(C->leaf_rec.upload(leaf_rec, C->leaf_bytes()));
-    C_TRY(C->leaf_node.upload(leaf_node, C->leaf_node_bytes()));
-    C_TRY(C->test_rec.upload(test_rec, C->test_bytes()));
-    C_TRY(C->root_rec.upload(root_rec, C->root_bytes()));
-    C_TRY(C->root_entry.upload(root_entry, C->entry_bytes()));
-    if (header[H_NBR]) C_TRY(C->nbr.upload(nbr, C->nbr_bytes()));
+    C_TRY(C->node.alloc(C->node_bytes()));
+    C_TRY(C->leaf_rec.alloc(C->leaf_bytes()));
+    C_TRY(C->test_rec.alloc(0));
+    struct {
+        DevBuf* dst;
+        const DevBuf* from;
+        size_t bytes;
+    } same[] = {{&C->leaf_node, &src->leaf_node, C->leaf_node_bytes()},
+                {&C->root_rec, &src->root_rec, C->root_bytes()},
+                {&C->root_entry, &src->root_entry, C->entry_bytes()},
+                {&C->nbr, &src->nbr, C->nbr_bytes()}};
+    for (const auto& part : same) {
+        if (!part.bytes) continue;
+        C_TRY(part.dst->alloc(part.bytes));
+        C_TRY(hipMemcpyAsync(part.dst->ptr, part.from->ptr, part.bytes, hipMemcpyDeviceToDevice,
+                             C->stream));
+    }
+    DevBuf d_flags;
+    C_TRY(d_flags.alloc(sizeof(int)));
+    C_TRY(hipMemsetAsync(d_flags.ptr, 0, sizeof(int), C->stream));
+    NarrowArgs A{};
+    A.n_int = src->h[H_INT];
+    A.n_leaf = src->h[H_LEAF];
+    A.p = p;
+    A.leaf_used = p + n_u + n_u * p;
+    A.ns64 = (int)src->h[H_NS];
+    A.ns32 = (int)C->h[H_NS];
+    A.ls64 = (int)src->h[H_LS];
+    A.ls32 = (int)C->h[H_LS];
+    A.node = src->node.as<const double>();
+    A.leaf_rec = src->leaf_rec.as<const double>();
+    A.node32 = C->node.as<float>();
+    A.leaf32 = C->leaf_rec.as<float>();
+    A.flags = d_flags.as<int>();
+    void* args[] = {&A};
+    // the source's arrays were written on its own stream (create) or by blocking copies (import)
+    C_TRY(hipStreamSynchronize(src->stream));
+    C_TRY(hipLaunchKernel(ehm_compiled32_api()->narrow,
+                          dim3((unsigned)((A.n_int + A.n_leaf + 255) / 256)), dim3(256), args, 0,
+                          C->stream));
+    int flags = 0;
+    C_TRY(hipMemcpyAsync(&flags, d_flags.ptr, sizeof flags, hipMemcpyDeviceToHost, C->stream));
+    C_TRY(hipStreamSynchronize(C->stream));
+    if (flags)
+        return cfail(EHM_E_INVALID, "narrow: the law has no single-precision form:%s%s%s",
+                     flags & NARROW_OVERFLOW ? " a value overflows or is not finite;" : "",
+                     flags & NARROW_UNDERFLOW ? " a nonzero value becomes zero or subnormal;" : "",
+                     flags & NARROW_ZERO_NORMAL ? " a plane's normal becomes zero;" : "");
     C->bind();
     *out = C.release();
     return EHM_OK;
@@ -798,23 +806,12 @@ int ehm_compiled_info(const ehm_compiled* C, int64_t* info) {
 
 int ehm_compiled_export(ehm_compiled* C, double* node, double* leaf_rec, int32_t* leaf_node,
                         double* test_rec, double* root_rec, int32_t* root_entry, int32_t* nbr) {
-    if (!C) return cfail(EHM_E_INVALID, "export: bad argument");
-    C_TRY(hipSetDevice(C->device));
-    struct {
-        void* host;
-        const DevBuf* buf;
-        size_t bytes;
-    } parts[] = {{node, &C->node, C->node_bytes()},
-                 {leaf_rec, &C->leaf_rec, C->leaf_bytes()},
-                 {leaf_node, &C->leaf_node, C->leaf_node_bytes()},
-                 {test_rec, &C->test_rec, C->test_bytes()},
-                 {root_rec, &C->root_rec, C->root_bytes()},
-                 {root_entry, &C->root_entry, C->entry_bytes()},
-                 {nbr, &C->nbr, C->nbr_bytes()}};
-    for (const auto& part : parts)
-        if (part.host && part.bytes)
-            C_TRY(hipMemcpy(part.host, part.buf->ptr, part.bytes, hipMemcpyDeviceToHost));
-    return EHM_OK;
+    return export_law(C, false, node, leaf_rec, leaf_node, test_rec, root_rec, root_entry, nbr);
+}
+
+int ehm_compiled_export_single(ehm_compiled* C, float* node, float* leaf_rec, int32_t* leaf_node,
+                          double* root_rec, int32_t* root_entry, int32_t* nbr) {
+    return export_law(C, true, node, leaf_rec, leaf_node, nullptr, root_rec, root_entry, nbr);
 }
 
 int ehm_compiled_eval_batch(ehm_compiled* C, int64_t n, const double* x, double* u,
@@ -845,10 +842,19 @@ int ehm_compiled_eval_batch(ehm_compiled* C, int64_t n, const double* x, double*
         hipLaunchKernelGGL(k_locate_table[p - 1], grid, block, 0, C->stream, C->d, (long long)n,
                            C->x.as<const double>(), C->nbr.as<const int32_t>(),
                            C->root.as<int32_t>());
-    hipLaunchKernelGGL(k_eval_table[p - 1], grid, block, 0, C->stream, C->d, (long long)n,
-                       C->x.as<const double>(), C->u.as<double>(), C->leaf.as<int32_t>(),
-                       C->depth.as<int32_t>(),
-                       locate ? C->root.as<const int32_t>() : (const int32_t*)nullptr);
+    const int32_t* root = locate ? C->root.as<const int32_t>() : nullptr;
+    if (C->single) {
+        long long nn = n;
+        const double* xp = C->x.as<const double>();
+        double* up = C->u.as<double>();
+        int32_t *lp = C->leaf.as<int32_t>(), *dp = C->depth.as<int32_t>();
+        void* args[] = {&C->d32, &nn, &xp, &up, &lp, &dp, &root};
+        C_TRY(hipLaunchKernel(ehm_compiled32_api()->eval[p - 1], grid, block, args, 0, C->stream));
+    } else {
+        hipLaunchKernelGGL(k_eval_table[p - 1], grid, block, 0, C->stream, C->d, (long long)n,
+                           C->x.as<const double>(), C->u.as<double>(), C->leaf.as<int32_t>(),
+                           C->depth.as<int32_t>(), root);
+    }
     (void)hipEventRecord(ev.e1, C->stream);
     C_TRY(hipGetLastError());
     C_TRY(hipMemcpyAsync(u, C->u.ptr, (size_t)n * n_u * sizeof(double), hipMemcpyDeviceToHost,
@@ -879,6 +885,11 @@ int rollout_law_ok(const ehm_compiled* C, const char* who) {
                      "by planes alone -- roll such a tree out on the source evaluator", who,
                      (long long)C->h[H_TEST]);
     return EHM_OK;
+}
+
+const Rollout32Table& rollout32_table() {
+    static const Rollout32Table table;
+    return table;
 }
 
 const int32_t* rollout_nbr(const ehm_compiled* C) {
@@ -938,6 +949,11 @@ int ehm_compiled_rollout(ehm_compiled* C, int64_t n, int32_t T, const double* x0
                          int32_t* status, double* cost, double* u_norm_sum,
                          double* max_violation, double* kernel_seconds) {
     if (!C) return cfail(EHM_E_INVALID, "rollout: bad argument");
+    if (C->single)
+        return rollout_run(C->ro, cfail, C->device, C->stream, C->d32, C->d.p, C->d.n_u,
+                           rollout_nbr(C), rollout32_table().fn, n, T, x0, d, v, tol_exit, x_traj,
+                           u_traj, leaf_traj, x_final, steps, status, cost, u_norm_sum,
+                           max_violation, kernel_seconds, nullptr);
     return rollout_run(C->ro, cfail, C->device, C->stream, C->d, C->d.p, C->d.n_u, rollout_nbr(C),
                        k_rollout_table, n, T, x0, d, v, tol_exit, x_traj, u_traj, leaf_traj,
                        x_final, steps, status, cost, u_norm_sum, max_violation, kernel_seconds,
@@ -954,6 +970,11 @@ int ehm_compiled_rollout_noisy(ehm_compiled* C, int64_t n, int32_t T, const doub
     const int rc = noisy_ready(C->ro, cfail);
     if (rc != EHM_OK) return rc;
     const NoisyCall nz{seed, traj0, v_traj, e_traj, w_traj};
+    if (C->single)
+        return rollout_run(C->ro, cfail, C->device, C->stream, C->d32, C->d.p, C->d.n_u,
+                           rollout_nbr(C), rollout32_table().fn, n, T, x0, nullptr, nullptr,
+                           tol_exit, x_traj, u_traj, leaf_traj, x_final, steps, status, cost,
+                           u_norm_sum, max_violation, kernel_seconds, &nz);
     return rollout_run(C->ro, cfail, C->device, C->stream, C->d, C->d.p, C->d.n_u, rollout_nbr(C),
                        k_rollout_table, n, T, x0, nullptr, nullptr, tol_exit, x_traj, u_traj,
                        leaf_traj, x_final, steps, status, cost, u_norm_sum, max_violation,

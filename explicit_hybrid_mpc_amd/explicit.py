@@ -169,18 +169,28 @@ class ExplicitMPC:
                                              ptr(left), ptr(right), ptr(vertices), ptr(vinput),
                                              ctypes.byref(self._handle)))
 
-    def compile(self):
+    def compile(self, dtype=np.float64):
         """The law as a ``compiled.CompiledLaw``: one hyperplane per internal node, one affine map
         per leaf, compiled on the device.  It holds its own arrays and outlives this object.  For
         its rollouts it remembers ``mpc`` (the default plant) and, where ``mpc`` tells the step-0
-        mode of a commutation, the mode of every leaf (``CompiledLaw.leaf_mode``)."""
+        mode of a commutation, the mode of every leaf (``CompiledLaw.leaf_mode``).
+        ``dtype=np.float32``: the law in single precision (``CompiledLaw.to_single``)."""
         from .compiled import CompiledLaw
+        dtype = np.dtype(dtype).type
+        if dtype not in (np.float64, np.float32):
+            raise ValueError('dtype must be np.float64 or np.float32')
         vertices = self.tree.vertices if isinstance(self.tree, FlatTree) else \
             flatten_tree(self.tree)[0]
         law = CompiledLaw.compile(self, vertices)
         law.mpc = self.mpc
         if self.mpc is not None and hasattr(self.mpc, 'step0_mode'):
             law.set_leaf_modes(self._step0_modes()[law.leaf_node])
+        if dtype is np.float32:
+            double = law
+            try:
+                law = double.to_single()
+            finally:
+                double.close()
         return law
 
     def close(self):

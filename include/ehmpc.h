@@ -530,6 +530,35 @@ int ehm_compiled_import(int device, const int64_t* header, const double* node,
                         const double* leaf_rec, const int32_t* leaf_node, const double* test_rec,
                         const double* root_rec, const int32_t* root_entry, const int32_t* nbr,
                         ehm_compiled** out);
+
+/* ---- the compiled law in single precision ------------------------------------------------------
+ *
+ * The law a flight computer runs: the reference sizes it for an on-board computer
+ * (get_opt_memreq, lib/post_process.py:99-142).  Only node and leaf_rec become floats, at strides of
+ * their own (in floats): node [a (p) | b | left, right int32], 8 floats (p <= 5) or 16; leaf_rec
+ * [v_0 | u_0 | K] rounded up to a multiple of 4.  leaf_node, root_rec, root_entry and nbr stay as
+ * they are, and so does the choice of the root, made in double on the double state.  Below the root
+ * xs = (float) x; s = ((0 + a_0 xs_0) + .. + a_(p-1) xs_(p-1)) + b, left iff s >= -2^-23; at the
+ * leaf u_c = u_0c + ((0 + K_c0 d_0) + ..) with d = xs - v_0, widened to double; every product and
+ * every sum rounded once to float.  ehm_compiled_eval_batch, the plant and noise setters and the two
+ * rollouts take a handle of either precision.
+ *
+ * narrow: a new, independent single law from a double one, its records rounded to nearest on the
+ * device.  EHM_E_INVALID for a law with test nodes, a value that overflows, a nonzero value that
+ * becomes zero or subnormal, a plane whose normal becomes zero. */
+int ehm_compiled_narrow(ehm_compiled* law, ehm_compiled** out);
+/* ehm_compiled_export for a single law (EHM_E_INVALID for a double one, as ehm_compiled_export is
+ * for a single one); a single law has no test_rec. */
+int ehm_compiled_export_single(ehm_compiled* law, float* node, float* leaf_rec, int32_t* leaf_node,
+                          double* root_rec, int32_t* root_entry, int32_t* nbr);
+/* ehm_compiled_validate / _import for the arrays of a single law: the same checks at the single
+ * strides, and no test node, no zero normal, every float of node and leaf_rec zero or normal. */
+int ehm_compiled_validate_single(const int64_t* header, const float* node, const float* leaf_rec,
+                            const int32_t* leaf_node, const double* root_rec,
+                            const int32_t* root_entry, const int32_t* nbr);
+int ehm_compiled_import_single(int device, const int64_t* header, const float* node,
+                          const float* leaf_rec, const int32_t* leaf_node, const double* root_rec,
+                          const int32_t* root_entry, const int32_t* nbr, ehm_compiled** out);
 int ehm_compiled_destroy(ehm_compiled* law);
 const char* ehm_compiled_last_error(void);
 

@@ -9,6 +9,13 @@ tens of milliseconds and not one 2 ms launch --, plus the compile time and the d
 (lib/post_process.py:99-142, get_opt_memreq).
 
     python tools/compiled_bench.py [--queries N] [--repeats R] [--out FILE]
+
+``--single`` (default output profiles/compiled/single_bench.txt): instead, the double compiled law
+against its single-precision form (``CompiledLaw.to_single``) on the same two trees and the same
+states in one process, the calls interleaved in the same way: kernel times, their ratio and spread
+(a ratio below 1 is reported as such), the device bytes of both laws against the stride formulas,
+and how far the two laws agree.  A tree whose law has no single form is reported with the values
+that refuse it.
 """
 import argparse
 import os
@@ -85,6 +92,79 @@ def run_case(name, flat, half, n_q, repeats, calls, rng, out):
     cl.close()
 
 
+def single_bytes(st, p, n_u):
+    """``stats['bytes']`` of a single law from the stride formulas (CompiledLaw.stats)."""
+    node = 32 if p <= 5 else 64
+    leaf = 16 * ((4 * (p + n_u + n_u * p) + 15) // 16)
+    return st['n_plane'] * node + st['n_leaf'] * (leaf + 4) + st['n_roots'] * (st['side_stride'] + 4) \
+        + st['nbr_bytes']
+
+
+def run_single_case(name, flat, half, n_q, repeats, calls, rng, out):
+    from explicit_hybrid_mpc_amd import _capi
+    ex = explicit.ExplicitMPC(flat)
+    cl = ex.compile()
+    ex.close()
+    p, n_u, st = cl.p, cl.n_u, cl.stats
+    out('case %s: %d nodes, %d roots, p = %d, n_u = %d, %d states; %d repeats, each the mean kernel '
+        'time of %d calls' % (name, flat.n_nodes, flat.info['n_roots'], p, n_u, n_q, repeats, calls))
+    try:
+        t0 = time.perf_counter()
+        single = cl.to_single()
+        wall = time.perf_counter() - t0
+    except _capi.EhmError as err:
+        a = cl.arrays()
+        tiny = float(np.finfo(np.float32).tiny)
+        used = {'node': p + 1, 'leaf_rec': p + n_u + n_u * p}
+        out('  no single form: %s' % err)
+        for key, cols in used.items():
+            v = np.abs(a[key][:, :cols])
+            low = (v > 0) & (v < tiny)
+            out('  %s: %d of %d values nonzero and below FLT_MIN (in %d of %d records), %d above '
+                'FLT_MAX' % (key, int(low.sum()), v.size, int(low.any(axis=1).sum()), v.shape[0],
+                             int((v > np.finfo(np.float32).max).sum())))
+        cl.close()
+        return
+    s32 = single.stats
+    X = rng.uniform(-1, 1, (n_q, half.size)) * half
+    laws = ((cl, 'double'), (single, 'single'))
+    for _ in range(3):                                      # warm-up: buffers, clocks, caches
+        for law, _ in laws:
+            law.evaluate(X)
+    times = {'double': [], 'single': []}
+    res = {}
+    for _ in range(repeats):
+        total = {'double': 0., 'single': 0.}
+        for _ in range(calls):                              # interleaved: drift hits both alike
+            for law, key in laws:
+                u, leaf, vis, secs = law.evaluate(X, return_info=True)
+                total[key] += secs
+                res[key] = (u, leaf, float(vis.mean()))
+        for key in total:
+            times[key].append(total[key] / calls)
+    for key in ('double', 'single'):
+        t = np.array(times[key])
+        out('  %-6s kernel ms: median %.3f  min %.3f  max %.3f  (%.3g states/s, %.1f decisions per '
+            'state)' % (key, 1e3 * np.median(t), 1e3 * t.min(), 1e3 * t.max(), n_q / np.median(t),
+                        res[key][2]))
+    td, ts = np.median(times['double']), np.median(times['single'])
+    spread = max(np.ptp(times['double']), np.ptp(times['single']))
+    out('  double / single of the medians: %.3fx  (difference %.3f ms, largest spread %.3f ms)%s' % (
+        td / ts, 1e3 * (td - ts), 1e3 * spread, '' if td >= ts else '  -- the single law is SLOWER'))
+    same = res['double'][1] == res['single'][1]
+    du = float(np.abs(res['double'][0] - res['single'][0])[same].max()) if same.any() else float('nan')
+    out('  same leaf for %.4f %% of the states; max |u_single - u_double| there %.3g' % (
+        100 * same.mean(), du))
+    out('  narrowing: %.1f ms with the allocations' % (1e3 * wall))
+    out('  device bytes: double %d (node %d B, leaf %d B), single %d (node %d B, leaf %d B): '
+        '%.3fx; the stride formula gives %d for the single law (%s)' % (
+            st['bytes'], st['node_stride'], st['leaf_stride'], s32['bytes'], s32['node_stride'],
+            s32['leaf_stride'], st['bytes'] / s32['bytes'], single_bytes(s32, p, n_u),
+            'matches' if single_bytes(s32, p, n_u) == s32['bytes'] else 'DOES NOT MATCH'))
+    cl.close()
+    single.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--queries', type=int, default=1 << 21)
@@ -92,7 +172,12 @@ def main():
     ap.add_argument('--calls', type=int, default=20)
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--single', action='store_true',
+                    help='the double compiled law against its single-precision form')
     args = ap.parse_args()
+    case = run_single_case if args.single else run_case
+    if args.single and args.out is None:
+        args.out = os.path.join(ROOT, 'profiles', 'compiled', 'single_bench.txt')
     lines = []
 
     def out(s):
@@ -109,7 +194,7 @@ def main():
     roots, _ = ehm_tools.delaunay_roots(V)
     flat = gp.partition(roots, action='ecc', export=True, with_volume=False)
     gp.close()
-    run_case('headline_tree', flat, half, args.queries, args.repeats, args.calls, rng, out)
+    case('headline_tree', flat, half, args.queries, args.repeats, args.calls, rng, out)
     mpc8 = examples.pwa4_mpc(N=bench.CONFIG5['N'], seed=args.seed)
     half8 = examples.theta_box(mpc8)
     roots8 = np.asarray(ehm_tools.delaunay_roots(examples.box_vertices(half8))[0], dtype=np.float64)
@@ -119,7 +204,7 @@ def main():
     flat8 = engine.FlatTree(roots8, leafs, leafs.copy(), np.zeros(K, dtype=np.int32),
                             np.zeros((K, p8 + 1)), np.zeros((K, p8 + 1, n_u8)),
                             np.zeros(K, dtype=np.uint8), np.zeros(K), {'n_roots': K}, None)
-    run_case('p8_spine', flat8, half8, args.queries, args.repeats, args.calls, rng, out)
+    case('p8_spine', flat8, half8, args.queries, args.repeats, args.calls, rng, out)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, 'w') as f:

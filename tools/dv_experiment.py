@@ -15,7 +15,11 @@ paper's single-run numbers (lib/post_process.py:414-417) beside them.  --implici
 implicit law's loop on the device (rollout(..., on_device=True)), which makes --implicit-trajectories
 as large as --n affordable (it overrides --n-implicit); the row then also reports the stalled pairs.
 --compiled rolls out the compiled law (ExplicitMPC.compile(), the artefact a user ships) in place of
-the partitioner's tree, in the experiment and in the throughput runs.
+the partitioner's tree, in the experiment and in the throughput runs, and beside it its
+single-precision form (CompiledLaw.to_single()) on the same seed and trajectory ids: per job the
+mean and the 5-95 % band of the delta-v under both laws and the largest difference on one
+trajectory go to --single-out (default profiles/compiled/dv_single.txt), a line per job as it
+finishes.
 
 Then the throughput of the noisy against the nominal rollout, measured in the same call (1e6
 trajectories x 100 steps from uniform states, applied trajectory-steps per second of kernel time)
@@ -58,6 +62,46 @@ def law_of(flat, oracle, use_compiled):
     return cl
 
 
+def single_law_row(cl, a, n, T, model, seed):
+    """The single-precision form of the compiled law ``cl`` on the trajectories of its rollout
+    ``a``: the same figures, and how far the two laws part; the refusal if it has no single form."""
+    from explicit_hybrid_mpc_amd import _capi
+    try:
+        single = cl.to_single()
+    except _capi.EhmError as err:
+        return dict(refused=str(err))
+    t0 = time.perf_counter()
+    c = single.rollout(np.zeros((n, 2)), T, noise=model, seed=seed, record=False)
+    wall = time.perf_counter() - t0
+    both = (a.status == 0) & (c.status == 0)
+    diff = 1e3 * np.abs(c.u_norm_sum - a.u_norm_sum)[both]
+    row = dict(trajectories=n, stopped=int((c.status != 0).sum()),
+               max_violation=float(c.max_violation.max()), kernel_s=c.seconds, wall_s=wall,
+               dv_mm_s=stats(1e3 * c.u_norm_sum), bytes=single.stats['bytes'],
+               double_bytes=cl.stats['bytes'], same_status=int((a.status == c.status).sum()),
+               same_steps=int((a.steps == c.steps).sum()),
+               dv_diff_max_mm_s=float(diff.max()) if diff.size else None,
+               dv_diff_mean_mm_s=float(diff.mean()) if diff.size else None)
+    single.close()
+    return row
+
+
+def single_line(r):
+    """One job's line of --single-out."""
+    e, s = r['explicit'], r['single']
+    head = 'job %d  %6d leaves  double: mean %.4f  5%% %.4f  95%% %.4f  stopped %d' % (
+        r['job'], r['leaves'], e['dv_mm_s']['mean'], e['dv_mm_s']['p5'], e['dv_mm_s']['p95'],
+        e['stopped'])
+    if 'refused' in s:
+        return head + '  |  single: ' + s['refused']
+    d = s['dv_mm_s']
+    return head + ('  |  single: mean %.4f  5%% %.4f  95%% %.4f  stopped %d  |  same status %d / %d, '
+                   'per trajectory |dv32 - dv64| max %.3g mean %.3g  |  bytes %d -> %d' % (
+                       d['mean'], d['p5'], d['p95'], s['stopped'], s['same_status'],
+                       s['trajectories'], s['dv_diff_max_mm_s'], s['dv_diff_mean_mm_s'],
+                       s['double_bytes'], s['bytes']))
+
+
 def experiment(job, n, n_im, seed, on_device=False, use_compiled=False):
     oracle, flat = cwh_tree(job)
     mpc = oracle.mpc
@@ -72,6 +116,7 @@ def experiment(job, n, n_im, seed, on_device=False, use_compiled=False):
     b = im.rollout(np.zeros((n_im, 2)), T, noise=model, seed=seed, record=False,
                    **(dict(on_device=True) if on_device else {}))
     t_im = time.perf_counter() - t0
+    single = single_law_row(ex, a, n, T, model, seed) if use_compiled else None
     dv_ex, dv_im = 1e3 * a.u_norm_sum, 1e3 * b.u_norm_sum
     ok = (a.status[:n_im] == 0) & (b.status == 0)
     row = dict(job=job, leaves=int(np.sum(flat.left < 0)), T=T, seed=seed,
@@ -93,6 +138,8 @@ def experiment(job, n, n_im, seed, on_device=False, use_compiled=False):
                paper_implicit=PAPER_IMPLICIT[job - 1], paper_explicit=PAPER_EXPLICIT[job - 1],
                paper_overconsumption_pct=100. * (PAPER_EXPLICIT[job - 1] - PAPER_IMPLICIT[job - 1])
                / PAPER_IMPLICIT[job - 1])
+    if single is not None:
+        row['single'] = single
     print(json.dumps(row), flush=True)
     ex.close()
     oracle.close()
@@ -129,14 +176,26 @@ def main():
     ap.add_argument('--rate-T', type=int, default=100)
     ap.add_argument('--skip-rates', action='store_true')
     ap.add_argument('--compiled', action='store_true')
+    ap.add_argument('--single-out', default=os.path.join(
+        os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles', 'compiled',
+        'dv_single.txt'))
     args = ap.parse_args()
     if args.implicit_trajectories is not None:
         if not args.implicit_on_device:
             ap.error('--implicit-trajectories goes with --implicit-on-device')
         args.n_implicit = min(args.implicit_trajectories, args.n)
-    rows = [experiment(int(j), args.n, args.n_implicit, args.seed, args.implicit_on_device,
-                       args.compiled)
-            for j in args.jobs.split(',') if j]
+    rows = []
+    for j in (int(j) for j in args.jobs.split(',') if j):
+        rows.append(experiment(j, args.n, args.n_implicit, args.seed, args.implicit_on_device,
+                               args.compiled))
+        if args.compiled:
+            os.makedirs(os.path.dirname(os.path.abspath(args.single_out)), exist_ok=True)
+            with open(args.single_out, 'w' if len(rows) == 1 else 'a') as f:
+                if len(rows) == 1:
+                    f.write('delta-v [mm/s] over 20 orbits from x0 = 0 under NoiseModel.from_mpc: '
+                            'the compiled law and its single-precision form, %d trajectories each, '
+                            'seed %d, the same trajectory ids\n' % (args.n, args.seed))
+                f.write(single_line(rows[-1]) + '\n')
     if rows:
         print('\ndelta-v [mm/s] over 20 orbits from x0 = 0 (explicit: %d trajectories, implicit: '
               'the first %d, common random numbers)' % (args.n, args.n_implicit))

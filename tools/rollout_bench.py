@@ -12,10 +12,12 @@ Trajectory-steps/s, one JSON line per tree and path:
                without the rollout (wall time; every trajectory runs all T steps, no exit test);
   (c) cpu      the CPU restatement (oracle.explicit_cpu.ExplicitFlatCPU + the numpy plant step),
                one process, a few trajectories, for scale.
---laws runs, instead of all that, the explicit and the compiled law (ExplicitMPC.compile()) in one
-process with the calls interleaved: --repeats rollouts of each after a warm-up, nominal and under a
-noise model, kernel time; one JSON line per tree and case with the applied trajectory-steps/s of
-both (median, min .. max) and their ratio, and whether the two rollouts ended alike.
+--laws runs, instead of all that, the explicit law, the compiled law (ExplicitMPC.compile()) and its
+single-precision form (CompiledLaw.to_single()) in one process with the calls interleaved:
+--repeats rollouts of each after a warm-up, nominal and under a noise model, kernel time; one JSON
+line per tree and case with the applied trajectory-steps/s of each (median, min .. max), the ratios
+compiled / explicit and single / compiled, and whether the rollouts ended alike.  A law without a
+single form is reported (``single`` holds the refusal) and the other two run.
 Trees: the headline partition (linear_mpc(0), abs_frac 0.02, eps_r 1e-2, as bench.py) and cwh_z
 job 1.  Then simulate.compare on cwh_z jobs 1..5 (lib/post_process.py:484-526 / make_jobs.sh) from
 uniform initial states in the box, nominal and with a box-bounded process disturbance; the
@@ -108,25 +110,33 @@ def rates(name, mpc, flat, n, T, rng):
 
 
 def both_laws(name, mpc, flat, model, n, T, repeats, rng):
-    """The explicit and the compiled law on the same states in one process, calls interleaved."""
+    """The explicit law, the compiled law and its single-precision form on the same states in one
+    process, calls interleaved."""
+    from explicit_hybrid_mpc_amd import _capi
     ex = explicit.ExplicitMPC(flat, types.SimpleNamespace(mpc=mpc))
     cl = ex.compile()
+    laws = [('explicit', ex), ('compiled', cl)]
+    refusal = None
+    try:
+        laws.append(('single', cl.to_single()))
+    except _capi.EhmError as err:
+        refusal = str(err)
     half = examples.theta_box(mpc)
     X0 = rng.uniform(-1, 1, (n, half.size)) * half
     for label, kw in (('nominal', {}), ('noisy', dict(noise=model, seed=1))):
-        for law in (ex, cl):
+        for _, law in laws:
             law.rollout(X0[:1024], T, record=False, **kw)              # warm-up
-        secs = {'explicit': [], 'compiled': []}
+        secs = {key: [] for key, _ in laws}
+        last = {}
         for _ in range(repeats):
-            for key, law in (('explicit', ex), ('compiled', cl)):
-                res = law.rollout(X0, T, record=False, **kw)
-                secs[key].append(res.seconds)
-                if key == 'explicit':
-                    a = res
+            for key, law in laws:
+                last[key] = law.rollout(X0, T, record=False, **kw)
+                secs[key].append(last[key].seconds)
+        a, res = last['explicit'], last['compiled']
         row = dict(tree=name, case=label, nodes=int(flat.n_nodes), trajectories=n, T=T,
                    repeats=repeats, same_steps=int((a.steps == res.steps).sum()),
                    same_status=int((a.status == res.status).sum()))
-        for key, r in (('explicit', a), ('compiled', res)):
+        for key, r in last.items():
             applied = int(r.steps.sum())
             t = np.array(secs[key])
             row[key] = dict(applied_steps=applied, stopped=int((r.status != 0).sum()),
@@ -136,9 +146,21 @@ def both_laws(name, mpc, flat, model, n, T, repeats, rng):
                             steps_per_s_max=applied / float(t.min()))
         row['compiled_over_explicit'] = (row['compiled']['steps_per_s_median']
                                          / row['explicit']['steps_per_s_median'])
+        if 'single' in last:
+            s = last['single']
+            row['single_over_compiled'] = (row['single']['steps_per_s_median']
+                                           / row['compiled']['steps_per_s_median'])
+            row['single_same_steps'] = int((s.steps == res.steps).sum())
+            row['single_same_status'] = int((s.status == res.status).sum())
+            both = (s.status == 0) & (res.status == 0)
+            row['single_u_norm_rel_max'] = float(np.max(
+                np.abs(s.u_norm_sum - res.u_norm_sum)[both]
+                / np.maximum(res.u_norm_sum[both], 1e-300))) if both.any() else None
+        else:
+            row['single'] = refusal
         print(json.dumps(row), flush=True)
-    ex.close()
-    cl.close()
+    for _, law in laws:
+        law.close()
 
 
 def main():
