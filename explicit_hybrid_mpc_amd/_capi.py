@@ -51,8 +51,10 @@ EXPORTED = [
     'ehm_compiled_last_error', 'ehm_compiled_set_plant', 'ehm_compiled_set_plant_guarded',
     'ehm_compiled_set_noise', 'ehm_compiled_rollout', 'ehm_compiled_rollout_noisy',
     'ehm_compiled_narrow', 'ehm_compiled_export_single', 'ehm_compiled_validate_single',
-    'ehm_compiled_import_single',
+    'ehm_compiled_import_single', 'ehm_compiled_create_opts', 'ehm_compiled_narrow_opts',
 ]
+EHM_COMPILE_SPINE_ROOTS = 1     # ehm_compiled_create_opts
+EHM_NARROW_FLUSH = 1            # ehm_compiled_narrow_opts
 
 
 # every symbol include/ehm_search.h declares (host bookkeeping of the prefix searches)
@@ -287,6 +289,8 @@ def load(build_if_missing=True):
     lib.ehm_compiled_import.argtypes = [i32] + [vp] * 8 + [ctypes.POINTER(vp)]
     lib.ehm_compiled_destroy.argtypes = [vp]
     lib.ehm_compiled_narrow.argtypes = [vp, ctypes.POINTER(vp)]
+    lib.ehm_compiled_create_opts.argtypes = [vp, vp, i32, ctypes.POINTER(vp), vp]
+    lib.ehm_compiled_narrow_opts.argtypes = [vp, i32, vp, ctypes.POINTER(vp)]
     lib.ehm_compiled_export_single.argtypes = [vp] * 7
     lib.ehm_compiled_validate_single.argtypes = [vp] * 7
     lib.ehm_compiled_import_single.argtypes = [i32] + [vp] * 7 + [ctypes.POINTER(vp)]

@@ -35,6 +35,14 @@ A turn can differ from the double law's only where |s| is within the rounding bo
 and in the same leaf the inputs differ by at most a like bound (DESIGN.md 3.8c states both).  Laws
 with test nodes, and laws a value of which overflows or leaves the normal range of a float, have
 no single form (``EhmError``, EHM_E_INVALID).  ``save`` marks the file with the key ``precision``.
+
+Two options open both forms to the laws people hold (both off by default).  ``compile(spine='roots')``
+turns the data-less right spine of a nested reference tree into the law's root table: the spine's
+test nodes go, the simplices that hang off it become the roots (and get the locator from 128 on), so
+the law has a rollout and a single form like one compiled from the flat forest, with the same
+(u, leaf) as under the default.  ``to_single(flush=True)`` (``compile(dtype=np.float32, flush=True)``)
+stores a value below the normal range of a float as +0.0 instead of refusing the law and counts
+those in ``flushed``.
 """
 
 import ctypes
@@ -189,6 +197,7 @@ class CompiledLaw:
     leaf_mode = None            # int32 [n_leaf]: step-0 mode of every leaf's commutation, -1 none
     _rollout_plant = None       # the plant the device holds (set_plant)
     _leaf_node = None
+    flushed = None              # to_single(flush=True): the counts of the values set to zero
 
     def __init__(self, handle, device, compile_seconds=0., dtype=np.float64):
         self._lib = _capi.load()
@@ -203,16 +212,22 @@ class CompiledLaw:
         self._bytes, self._source_bytes = int(info[12]), int(info[13])
 
     @classmethod
-    def compile(cls, explicit, vertices):
+    def compile(cls, explicit, vertices, spine='tests'):
         """Compiles the law an ``ExplicitMPC`` holds; ``vertices`` [n_nodes, p+1, p] as it was
-        set up from."""
+        set up from.  ``spine='roots'``: the data-less right spine of a nested tree -- the chain
+        of test nodes from node 0 along the right children -- gets no records, and the simplices
+        that hang off it become the law's roots (ehm_compiled_create_opts); a tree without such a
+        chain, and a forest, compile as under the default ``'tests'``."""
+        if spine not in ('tests', 'roots'):
+            raise ValueError("spine must be 'tests' or 'roots'")
         vertices = f64(vertices)
         if vertices.shape != (explicit.n_nodes, explicit.p + 1, explicit.p):
             raise ValueError('vertices must be [%d, %d, %d]' % (explicit.n_nodes, explicit.p + 1,
                                                                 explicit.p))
         handle, secs = ctypes.c_void_p(), ctypes.c_double(0.)
-        _check(_capi.load().ehm_compiled_create(explicit._handle, ptr(vertices),
-                                                ctypes.byref(handle), ctypes.addressof(secs)))
+        flags = _capi.EHM_COMPILE_SPINE_ROOTS if spine == 'roots' else 0
+        _check(_capi.load().ehm_compiled_create_opts(explicit._handle, ptr(vertices), flags,
+                                                     ctypes.byref(handle), ctypes.addressof(secs)))
         return cls(handle, explicit.device, secs.value)
 
     @classmethod
@@ -227,15 +242,23 @@ class CompiledLaw:
                   ctypes.byref(handle)))
         return cls(handle, device, dtype=np.float32 if precision == 32 else np.float64)
 
-    def to_single(self):
+    def to_single(self, flush=False):
         """The law in single precision: a new, independent ``CompiledLaw`` (``dtype`` np.float32)
         whose internal and leaf records were rounded to nearest float on the device
         (ehm_compiled_narrow).  It keeps ``mpc`` and the leaf modes.  ``EhmError`` for a law with
         test nodes, or one a value of which overflows, becomes zero or subnormal, or whose plane
-        loses its normal."""
+        loses its normal.  ``flush=True``: a nonzero value whose float is zero or subnormal (it is
+        below 2^-126 in magnitude: elimination noise of an inverse) is stored as +0.0 instead of
+        refused, and ``flushed`` of the new law counts them: {'a': plane coefficients, 'b': plane
+        offsets, 'leaf': leaf values} (DESIGN.md 3.8c states what that adds to the two bounds)."""
         handle = ctypes.c_void_p()
-        _check(self._lib.ehm_compiled_narrow(self._handle, ctypes.byref(handle)))
+        gone = (ctypes.c_int64 * 3)()
+        _check(self._lib.ehm_compiled_narrow_opts(
+            self._handle, _capi.EHM_NARROW_FLUSH if flush else 0, ctypes.addressof(gone),
+            ctypes.byref(handle)))
         law = type(self)(handle, self.device, self.compile_seconds, dtype=np.float32)
+        if flush:
+            law.flushed = dict(zip(('a', 'b', 'leaf'), (int(v) for v in gone)))
         law.mpc = self.mpc
         if self.leaf_mode is not None:
             law.set_leaf_modes(self.leaf_mode)

@@ -18,6 +18,9 @@
 // index grows strictly, so no array -- compiled here or imported from a file -- can hold a cycle.
 // One level of the walk is one dependent load (the source evaluator: child pair, then the child's
 // record).  The handle owns copies of all it needs: it outlives its source.
+// ehm_compiled_create_opts with EHM_COMPILE_SPINE_ROOTS turns the chain of test nodes on top of a
+// nested tree (node 0 and on along the right children) into the root table instead: those nodes get
+// no record, and what hangs off them is the law's roots, with the locator's adjacency from 128 on.
 //
 // k_compiled_rollout closes the loop around the compiled law (one thread per trajectory, the T steps
 // in the kernel): the root as k_compiled_locate / k_compiled_eval choose it, the exit test on the
@@ -89,6 +92,10 @@ __global__ void k_compiled_classify(long long n_nodes, int p, const int2* __rest
     cls[k] = plane ? 1 + j : 0;
 }
 
+// what the host writes over the class of a spine node that became the root table
+// (EHM_COMPILE_SPINE_ROOTS)
+#define CLS_SPINE (-2)
+
 struct CompileArgs {
     long long n_nodes;
     int p, n_u, rec_stride, node_stride, leaf_stride, side_stride;
@@ -107,6 +114,7 @@ __global__ void k_compiled_write(CompileArgs A) {
     const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= A.n_nodes) return;
     const int p = A.p, n_u = A.n_u;
+    if (A.cls[k] == CLS_SPINE) return;      // its children are roots of the law: no record
     const int id = A.newid[k];
     if (id < 0) {
         // leaf: u = u_0 + K (x - v_0), K = (U_1..p - u_0)^T inv(E)
@@ -156,13 +164,16 @@ __global__ void k_compiled_write(CompileArgs A) {
     *cp = make_int2(A.newid[ch.x], A.newid[ch.y]);
 }
 
-// rows 0..n_roots-1 of the source's records, repacked at the side stride
+// the source's records of the nodes ids[0..n_roots-1] (ids nullptr: rows 0..n_roots-1), repacked
+// at the side stride
 __global__ void k_compiled_roots(int n_roots, int p, int rec_stride, int side_stride,
-                                 const double* __restrict__ rec, double* __restrict__ root_rec) {
+                                 const int32_t* __restrict__ ids, const double* __restrict__ rec,
+                                 double* __restrict__ root_rec) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_roots) return;
+    const size_t from = ids ? (size_t)ids[k] : (size_t)k;
     for (int c = 0; c < side_stride; ++c)
-        root_rec[(size_t)k * side_stride + c] = c < p + p * p ? rec[(size_t)k * rec_stride + c] : 0.0;
+        root_rec[(size_t)k * side_stride + c] = c < p + p * p ? rec[from * rec_stride + c] : 0.0;
 }
 
 // ---- evaluation ----------------------------------------------------------------------------------
@@ -590,8 +601,15 @@ int ehm_compiled_destroy(ehm_compiled* C) {
 
 int ehm_compiled_create(ehm_explicit* src, const double* vertices, ehm_compiled** out,
                         double* compile_seconds) {
+    return ehm_compiled_create_opts(src, vertices, 0, out, compile_seconds);
+}
+
+int ehm_compiled_create_opts(ehm_explicit* src, const double* vertices, int32_t flags,
+                             ehm_compiled** out, double* compile_seconds) {
     if (!src || !vertices || !out) return cfail(EHM_E_INVALID, "compile: bad argument");
     *out = nullptr;
+    if (flags & ~EHM_COMPILE_SPINE_ROOTS)
+        return cfail(EHM_E_INVALID, "compile: unknown flags %d", (int)flags);
     ehm_explicit_view v{};
     ehm_explicit_get_view(src, &v);
     const int p = v.p, n_u = v.n_u;
@@ -623,7 +641,6 @@ int ehm_compiled_create(ehm_explicit* src, const double* vertices, ehm_compiled*
     DevBuf d_vert, d_cls, d_newid, d_tidx;
     C_TRY(d_vert.upload(vertices, (size_t)n * (p + 1) * p * sizeof(double)));
     C_TRY(d_cls.alloc((size_t)n * sizeof(int32_t)));
-    C_TRY(d_newid.upload(newid.data(), newid.size() * sizeof(int32_t)));
     const dim3 grid((unsigned)((n + 127) / 128)), block(128);
     hipLaunchKernelGGL(k_compiled_classify, grid, block, 0, C->stream, (long long)n, p, v.child,
                        d_vert.as<const double>(), d_cls.as<int32_t>());
@@ -633,6 +650,29 @@ int ehm_compiled_create(ehm_explicit* src, const double* vertices, ehm_compiled*
                          hipMemcpyDeviceToHost, C->stream));
     C_TRY(hipStreamSynchronize(C->stream));
     d_vert.reset();             // the vertices were needed for the classification only
+    // EHM_COMPILE_SPINE_ROOTS: the chain of test nodes from node 0 along the right children gets
+    // no records, and what hangs off it becomes the roots (source ids in root_ids; empty: the
+    // source's own roots).  The rest is numbered again without the chain, in source order.
+    std::vector<int32_t> root_ids;
+    if ((flags & EHM_COMPILE_SPINE_ROOTS) && v.n_roots == 1) {
+        int64_t k = 0;
+        while (ch[(size_t)k].x >= 0 && cls[(size_t)k] == 0) {
+            cls[(size_t)k] = CLS_SPINE;
+            root_ids.push_back(ch[(size_t)k].x);
+            k = ch[(size_t)k].y;
+        }
+        if (!root_ids.empty()) {
+            root_ids.push_back((int32_t)k);
+            C_TRY(hipMemcpyAsync(d_cls.ptr, cls.data(), cls.size() * sizeof(int32_t),
+                                 hipMemcpyHostToDevice, C->stream));
+            n_int = 0;
+            for (int64_t i = 0; i < n; ++i)
+                if (ch[(size_t)i].x >= 0)
+                    newid[(size_t)i] = cls[(size_t)i] == CLS_SPINE ? 0 : (int32_t)n_int++;
+        }
+    }
+    const int64_t n_roots = root_ids.empty() ? (int64_t)v.n_roots : (int64_t)root_ids.size();
+    C_TRY(d_newid.upload(newid.data(), newid.size() * sizeof(int32_t)));
     int64_t n_test = 0;
     for (int64_t k = 0; k < n; ++k)
         if (cls[(size_t)k] == 0) tidx[(size_t)k] = (int32_t)n_test++;
@@ -641,25 +681,39 @@ int ehm_compiled_create(ehm_explicit* src, const double* vertices, ehm_compiled*
     h[H_VERSION] = EHM_C_VERSION;
     h[H_P] = p;
     h[H_NU] = n_u;
-    h[H_ROOTS] = v.n_roots;
+    h[H_ROOTS] = n_roots;
     h[H_INT] = n_int;
     h[H_LEAF] = n_leaf;
     h[H_TEST] = n_test;
     h[H_NS] = ns;
     h[H_LS] = ls;
     h[H_SS] = ss;
-    h[H_NBR] = v.nbr ? 1 : 0;
+    const bool own_nbr = !root_ids.empty() && n_roots >= EHM_C_LOCATE_MIN && n_roots < (1 << 20);
+    h[H_NBR] = (root_ids.empty() ? v.nbr != nullptr : own_nbr) ? 1 : 0;
     h[H_SRC] = n;
     C_TRY(C->node.alloc(C->node_bytes()));
     C_TRY(C->leaf_rec.alloc(C->leaf_bytes()));
     C_TRY(C->leaf_node.alloc(C->leaf_node_bytes()));
     C_TRY(C->test_rec.alloc(C->test_bytes()));
     C_TRY(C->root_rec.alloc(C->root_bytes()));
-    C_TRY(C->root_entry.upload(newid.data(), C->entry_bytes()));
-    if (v.nbr) {
-        C_TRY(C->nbr.alloc(C->nbr_bytes()));
-        C_TRY(hipMemcpyAsync(C->nbr.ptr, v.nbr, C->nbr_bytes(), hipMemcpyDeviceToDevice,
-                             C->stream));
+    DevBuf d_root_ids;
+    if (root_ids.empty()) {
+        C_TRY(C->root_entry.upload(newid.data(), C->entry_bytes()));
+        if (v.nbr) {
+            C_TRY(C->nbr.alloc(C->nbr_bytes()));
+            C_TRY(hipMemcpyAsync(C->nbr.ptr, v.nbr, C->nbr_bytes(), hipMemcpyDeviceToDevice,
+                                 C->stream));
+        }
+    } else {
+        std::vector<int32_t> entry(root_ids.size());
+        for (size_t i = 0; i < root_ids.size(); ++i) entry[i] = newid[(size_t)root_ids[i]];
+        C_TRY(C->root_entry.upload(entry.data(), C->entry_bytes()));
+        C_TRY(d_root_ids.upload(root_ids.data(), root_ids.size() * sizeof(int32_t)));
+        if (own_nbr) {
+            std::vector<int32_t> nbr;
+            ehm_root_adjacency(n_roots, p, vertices, root_ids.data(), nbr);
+            C_TRY(C->nbr.upload(nbr.data(), C->nbr_bytes()));
+        }
     }
     CompileArgs A{};
     A.n_nodes = n;
@@ -680,16 +734,16 @@ int ehm_compiled_create(ehm_explicit* src, const double* vertices, ehm_compiled*
     A.test_rec = C->test_rec.as<double>();
     A.leaf_node = C->leaf_node.as<int32_t>();
     hipLaunchKernelGGL(k_compiled_write, grid, block, 0, C->stream, A);
-    hipLaunchKernelGGL(k_compiled_roots, dim3((unsigned)((v.n_roots + 127) / 128)), block, 0,
-                       C->stream, v.n_roots, p, v.rec_stride, ss, v.rec,
-                       C->root_rec.as<double>());
+    hipLaunchKernelGGL(k_compiled_roots, dim3((unsigned)((n_roots + 127) / 128)), block, 0,
+                       C->stream, (int)n_roots, p, v.rec_stride, ss,
+                       d_root_ids.as<const int32_t>(), v.rec, C->root_rec.as<double>());
     C_TRY(hipGetLastError());
     C_TRY(hipStreamSynchronize(C->stream));
     if (compile_seconds)
         *compile_seconds =
             std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     C->source_bytes = n * ((int64_t)v.rec_stride * 8 + 8 + (int64_t)(p + 1) * n_u * 8) +
-                      (int64_t)C->nbr_bytes();
+                      (v.nbr ? (int64_t)v.n_roots * (p + 1) * (int64_t)sizeof(int32_t) : 0);
     C->bind();
     *out = C.release();
     return EHM_OK;
@@ -726,8 +780,16 @@ int ehm_compiled_import_single(int device, const int64_t* header, const float* n
 
 // The single-precision law of a double law: a new handle with the records narrowed on the device.
 int ehm_compiled_narrow(ehm_compiled* src, ehm_compiled** out) {
+    return ehm_compiled_narrow_opts(src, 0, nullptr, out);
+}
+
+int ehm_compiled_narrow_opts(ehm_compiled* src, int32_t opts, int64_t* flushed,
+                             ehm_compiled** out) {
     if (!src || !out) return cfail(EHM_E_INVALID, "narrow: bad argument");
     *out = nullptr;
+    if (flushed) flushed[0] = flushed[1] = flushed[2] = 0;
+    if (opts & ~EHM_NARROW_FLUSH)
+        return cfail(EHM_E_INVALID, "narrow: unknown flags %d", (int)opts);
     if (src->single) return cfail(EHM_E_INVALID, "narrow: the law is in single precision already");
     if (src->h[H_TEST] > 0)
         return cfail(EHM_E_INVALID, "narrow: the law has %lld test nodes (children that are no "
@@ -760,9 +822,14 @@ int ehm_compiled_narrow(ehm_compiled* src, ehm_compiled** out) {
         C_TRY(hipMemcpyAsync(part.dst->ptr, part.from->ptr, part.bytes, hipMemcpyDeviceToDevice,
                              C->stream));
     }
-    DevBuf d_flags;
+    DevBuf d_flags, d_flushed;
     C_TRY(d_flags.alloc(sizeof(int)));
     C_TRY(hipMemsetAsync(d_flags.ptr, 0, sizeof(int), C->stream));
+    unsigned long long gone[3] = {0, 0, 0};
+    if (opts & EHM_NARROW_FLUSH) {
+        C_TRY(d_flushed.alloc(sizeof gone));
+        C_TRY(hipMemsetAsync(d_flushed.ptr, 0, sizeof gone, C->stream));
+    }
     NarrowArgs A{};
     A.n_int = src->h[H_INT];
     A.n_leaf = src->h[H_LEAF];
@@ -777,6 +844,7 @@ int ehm_compiled_narrow(ehm_compiled* src, ehm_compiled** out) {
     A.node32 = C->node.as<float>();
     A.leaf32 = C->leaf_rec.as<float>();
     A.flags = d_flags.as<int>();
+    A.flushed = d_flushed.as<unsigned long long>();
     void* args[] = {&A};
     // the source's arrays were written on its own stream (create) or by blocking copies (import)
     C_TRY(hipStreamSynchronize(src->stream));
@@ -785,12 +853,16 @@ int ehm_compiled_narrow(ehm_compiled* src, ehm_compiled** out) {
                           C->stream));
     int flags = 0;
     C_TRY(hipMemcpyAsync(&flags, d_flags.ptr, sizeof flags, hipMemcpyDeviceToHost, C->stream));
+    if (d_flushed)
+        C_TRY(hipMemcpyAsync(gone, d_flushed.ptr, sizeof gone, hipMemcpyDeviceToHost, C->stream));
     C_TRY(hipStreamSynchronize(C->stream));
     if (flags)
         return cfail(EHM_E_INVALID, "narrow: the law has no single-precision form:%s%s%s",
                      flags & NARROW_OVERFLOW ? " a value overflows or is not finite;" : "",
                      flags & NARROW_UNDERFLOW ? " a nonzero value becomes zero or subnormal;" : "",
                      flags & NARROW_ZERO_NORMAL ? " a plane's normal becomes zero;" : "");
+    if (flushed)
+        for (int i = 0; i < 3; ++i) flushed[i] = (int64_t)gone[i];
     C->bind();
     *out = C.release();
     return EHM_OK;

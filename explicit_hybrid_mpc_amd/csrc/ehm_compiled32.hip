@@ -16,24 +16,33 @@ namespace {
 
 // ---- narrowing: one thread per record ----------------------------------------------------------------
 
-// round to nearest float; a value that leaves the normal range (or was not finite) raises its flag
-__device__ __forceinline__ float narrow_value(double v, int& flags) {
+// round to nearest float; a value that leaves the normal range (or was not finite) raises its flag.
+// Under `flush` a nonzero value whose float is zero or subnormal (|v| < 2^-126) becomes +0.0f and is
+// counted in `flushed` instead.
+__device__ __forceinline__ float narrow_value(double v, int& flags, bool flush, int& flushed) {
     const float f = (float)v;
     if (!(fabsf(f) <= FLT_MAX)) flags |= NARROW_OVERFLOW;
-    else if (v != 0.0 && fabsf(f) < FLT_MIN) flags |= NARROW_UNDERFLOW;
+    else if (v != 0.0 && fabsf(f) < FLT_MIN) {
+        if (!flush) flags |= NARROW_UNDERFLOW;
+        else {
+            ++flushed;
+            return 0.0f;
+        }
+    }
     return f;
 }
 
 __global__ __launch_bounds__(256) void k_compiled_narrow(NarrowArgs A) {
     const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= A.n_int + A.n_leaf) return;
-    int flags = 0;
+    const bool flush = A.flushed != nullptr;
+    int flags = 0, gone[3] = {0, 0, 0};     // flushed plane coefficients, offsets, leaf values
     if (k < A.n_int) {
         const double* r = A.node + (size_t)k * A.ns64;
         float* out = A.node32 + (size_t)k * A.ns32;
         bool zero = true;
         for (int c = 0; c <= A.p; ++c) {
-            const float f = narrow_value(r[c], flags);
+            const float f = narrow_value(r[c], flags, flush, gone[c < A.p ? 0 : 1]);
             if (c < A.p) zero = zero && f == 0.0f;
             out[c] = f;
         }
@@ -47,10 +56,12 @@ __global__ __launch_bounds__(256) void k_compiled_narrow(NarrowArgs A) {
         const long long l = k - A.n_int;
         const double* r = A.leaf_rec + (size_t)l * A.ls64;
         float* out = A.leaf32 + (size_t)l * A.ls32;
-        for (int c = 0; c < A.leaf_used; ++c) out[c] = narrow_value(r[c], flags);
+        for (int c = 0; c < A.leaf_used; ++c) out[c] = narrow_value(r[c], flags, flush, gone[2]);
         for (int c = A.leaf_used; c < A.ls32; ++c) out[c] = 0.0f;
     }
     if (flags) atomicOr(A.flags, flags);
+    for (int i = 0; i < 3; ++i)
+        if (gone[i]) atomicAdd(A.flushed + i, (unsigned long long)gone[i]);
 }
 
 // ---- evaluation ----------------------------------------------------------------------------------------

@@ -67,6 +67,9 @@ struct NarrowArgs {
     const double *node, *leaf_rec;
     float *node32, *leaf32;
     int* flags;
+    // EHM_NARROW_FLUSH (else nullptr): counters of the plane coefficients, plane offsets and leaf
+    // values whose float is zero or subnormal and which are stored as +0.0f instead of refused
+    unsigned long long* flushed;
 };
 
 // The sums of `contains` / `weights` of ehm_explicit.hip (their products fused into the sums, as the

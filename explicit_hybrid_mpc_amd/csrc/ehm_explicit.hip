@@ -431,6 +431,45 @@ void ehm_explicit_get_view(const ehm_explicit* E, ehm_explicit_view* out) {
                              E->d.n_roots, E->d.n_nodes};
 }
 
+// face adjacency of the roots (ehm_explicit_view.h): vertices by value, faces by their sorted
+// vertex ids (the key holds -0.0 as 0.0: one vertex however a root writes its zero coordinates)
+void ehm_root_adjacency(int64_t n_roots, int p, const double* vertices, const int32_t* ids_of,
+                        std::vector<int32_t>& nbr) {
+    std::unordered_map<std::string, int32_t> vid;
+    std::vector<int32_t> ids((size_t)n_roots * (p + 1));
+    double vk[EHM_XP];
+    for (int64_t r = 0; r < n_roots; ++r) {
+        const size_t node = ids_of ? (size_t)ids_of[r] : (size_t)r;
+        for (int i = 0; i <= p; ++i) {
+            const double* v = vertices + (node * (p + 1) + i) * p;
+            for (int c = 0; c < p; ++c) vk[c] = (v[c] == 0.0) ? 0.0 : v[c];
+            std::string key((const char*)vk, sizeof(double) * p);
+            auto it = vid.find(key);
+            if (it == vid.end()) it = vid.emplace(std::move(key), (int32_t)vid.size()).first;
+            ids[(size_t)r * (p + 1) + i] = it->second;
+        }
+    }
+    nbr.assign((size_t)n_roots * (p + 1), -1);
+    std::unordered_map<std::string, int64_t> face;      // key -> root * (p+1) + i of the first owner
+    std::vector<int32_t> f((size_t)p);
+    for (int64_t r = 0; r < n_roots; ++r)
+        for (int i = 0; i <= p; ++i) {
+            int w = 0;
+            for (int j = 0; j <= p; ++j)
+                if (j != i) f[(size_t)w++] = ids[(size_t)r * (p + 1) + j];
+            std::sort(f.begin(), f.end());
+            std::string key((const char*)f.data(), sizeof(int32_t) * p);
+            auto it = face.find(key);
+            if (it == face.end()) {
+                face.emplace(std::move(key), r * (p + 1) + i);
+            } else {
+                const int64_t o = it->second;
+                nbr[(size_t)r * (p + 1) + i] = (int32_t)(o / (p + 1));
+                nbr[(size_t)o] = (int32_t)r;
+            }
+        }
+}
+
 extern "C" {
 
 const char* ehm_explicit_last_error(void) { return x_err.c_str(); }
@@ -477,39 +516,8 @@ int ehm_explicit_create(int device, int64_t n_nodes, int32_t n_roots, int32_t p,
     Y_TRY(hipStreamSynchronize(E->stream));
     if (sing) return xfail(EHM_E_NUMERIC, "%d degenerate simplices in the partition", (int)sing);
     if (n_roots >= EHM_X_LOCATE_MIN && n_roots < (1 << 20)) {
-        // face adjacency of the roots: vertices by value, faces by their sorted vertex ids
-        // (the key holds -0.0 as 0.0: one vertex however a root writes its zero coordinates)
-        std::unordered_map<std::string, int32_t> vid;
-        std::vector<int32_t> ids((size_t)n_roots * (p + 1));
-        double vk[EHM_XP];
-        for (int64_t r = 0; r < n_roots; ++r)
-            for (int i = 0; i <= p; ++i) {
-                const double* v = vertices + ((size_t)r * (p + 1) + i) * p;
-                for (int c = 0; c < p; ++c) vk[c] = (v[c] == 0.0) ? 0.0 : v[c];
-                std::string key((const char*)vk, sizeof(double) * p);
-                auto it = vid.find(key);
-                if (it == vid.end()) it = vid.emplace(std::move(key), (int32_t)vid.size()).first;
-                ids[(size_t)r * (p + 1) + i] = it->second;
-            }
-        std::vector<int32_t> nbr((size_t)n_roots * (p + 1), -1);
-        std::unordered_map<std::string, int64_t> face;      // key -> root * (p+1) + i of the first owner
-        std::vector<int32_t> f((size_t)p);
-        for (int64_t r = 0; r < n_roots; ++r)
-            for (int i = 0; i <= p; ++i) {
-                int w = 0;
-                for (int j = 0; j <= p; ++j)
-                    if (j != i) f[(size_t)w++] = ids[(size_t)r * (p + 1) + j];
-                std::sort(f.begin(), f.end());
-                std::string key((const char*)f.data(), sizeof(int32_t) * p);
-                auto it = face.find(key);
-                if (it == face.end()) {
-                    face.emplace(std::move(key), r * (p + 1) + i);
-                } else {
-                    const int64_t o = it->second;
-                    nbr[(size_t)r * (p + 1) + i] = (int32_t)(o / (p + 1));
-                    nbr[(size_t)o] = (int32_t)r;
-                }
-            }
+        std::vector<int32_t> nbr;
+        ehm_root_adjacency(n_roots, p, vertices, nullptr, nbr);
         Y_TRY(E->nbr.upload(nbr.data(), nbr.size() * sizeof(int32_t)));
     }
     E->d.rec = E->rec.as<const double>();

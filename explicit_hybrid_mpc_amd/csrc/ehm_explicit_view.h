@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <vector>
 
 #include "../../include/ehmpc.h"
 
@@ -19,3 +20,9 @@ struct ehm_explicit_view {
 };
 
 void ehm_explicit_get_view(const ehm_explicit* E, ehm_explicit_view* out);
+
+// Face adjacency of n_roots simplices (host): nbr [n_roots][p+1], the root across the face opposite
+// vertex i, -1 on the hull.  Root r has the vertices [p+1][p] of node ids[r] (ids nullptr: node r).
+// Vertices are one vertex by value (-0.0 == 0.0), faces are matched by their sorted vertex ids.
+void ehm_root_adjacency(int64_t n_roots, int p, const double* vertices, const int32_t* ids,
+                        std::vector<int32_t>& nbr);

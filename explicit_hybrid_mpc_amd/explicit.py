@@ -169,26 +169,33 @@ class ExplicitMPC:
                                              ptr(left), ptr(right), ptr(vertices), ptr(vinput),
                                              ctypes.byref(self._handle)))
 
-    def compile(self, dtype=np.float64):
+    def compile(self, dtype=np.float64, spine='tests', flush=False):
         """The law as a ``compiled.CompiledLaw``: one hyperplane per internal node, one affine map
         per leaf, compiled on the device.  It holds its own arrays and outlives this object.  For
         its rollouts it remembers ``mpc`` (the default plant) and, where ``mpc`` tells the step-0
         mode of a commutation, the mode of every leaf (``CompiledLaw.leaf_mode``).
-        ``dtype=np.float32``: the law in single precision (``CompiledLaw.to_single``)."""
+        ``dtype=np.float32``: the law in single precision (``CompiledLaw.to_single``), with
+        ``flush=True`` its values below the normal range of a float set to zero instead of
+        refused.  ``spine='roots'``: the data-less spine of a nested tree becomes the law's root
+        table instead of test nodes (``CompiledLaw.compile``)."""
         from .compiled import CompiledLaw
         dtype = np.dtype(dtype).type
         if dtype not in (np.float64, np.float32):
             raise ValueError('dtype must be np.float64 or np.float32')
+        if spine not in ('tests', 'roots'):
+            raise ValueError("spine must be 'tests' or 'roots'")
+        if flush and dtype is np.float64:
+            raise ValueError('flush=True narrows the law: it needs dtype=np.float32')
         vertices = self.tree.vertices if isinstance(self.tree, FlatTree) else \
             flatten_tree(self.tree)[0]
-        law = CompiledLaw.compile(self, vertices)
+        law = CompiledLaw.compile(self, vertices, spine=spine)
         law.mpc = self.mpc
         if self.mpc is not None and hasattr(self.mpc, 'step0_mode'):
             law.set_leaf_modes(self._step0_modes()[law.leaf_node])
         if dtype is np.float32:
             double = law
             try:
-                law = double.to_single()
+                law = double.to_single(flush=bool(flush))
             finally:
                 double.close()
         return law

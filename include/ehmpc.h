@@ -509,6 +509,15 @@ const char* ehm_explicit_last_error(void);
 typedef struct ehm_compiled ehm_compiled;
 int ehm_compiled_create(ehm_explicit* src, const double* vertices, ehm_compiled** out,
                         double* compile_seconds);
+/* create with a flags word (create is flags = 0).  EHM_COMPILE_SPINE_ROOTS: where `src` has one
+ * root and the chain s_0 = 0, s_(i+1) = right(s_i) of internal test nodes has m > 0 nodes (the
+ * data-less spine of a nested tree), those nodes get no record and the law gets the m + 1 roots
+ * left(s_0), .., left(s_(m-1)), right(s_(m-1)) instead: root_rec their [v_0 | inv(E)] records,
+ * root_entry their indices, nbr their face adjacency (from `vertices`) from 128 roots on.  Without
+ * such a chain, or with more than one root, the flag changes nothing. */
+#define EHM_COMPILE_SPINE_ROOTS 1
+int ehm_compiled_create_opts(ehm_explicit* src, const double* vertices, int32_t flags,
+                             ehm_compiled** out, double* compile_seconds);
 /* As ehm_explicit_eval_batch: leaf [n] = source node id of the leaf, depth [n] = decisions made
  * (root tests or locator steps, then one per level); both and kernel_seconds may be NULL. */
 int ehm_compiled_eval_batch(ehm_compiled* law, int64_t n, const double* x, double* u,
@@ -547,6 +556,14 @@ int ehm_compiled_import(int device, const int64_t* header, const double* node,
  * device.  EHM_E_INVALID for a law with test nodes, a value that overflows, a nonzero value that
  * becomes zero or subnormal, a plane whose normal becomes zero. */
 int ehm_compiled_narrow(ehm_compiled* law, ehm_compiled** out);
+/* narrow with a flags word (narrow is flags = 0).  EHM_NARROW_FLUSH: a nonzero value whose float
+ * is zero or subnormal (every such value is below 2^-126 in magnitude) is stored as +0.0f instead
+ * of being refused; flushed [3] (may be NULL) receives how many plane coefficients, plane offsets
+ * and leaf values were set to zero (all 0 without the flag).  Still EHM_E_INVALID: test nodes, an
+ * overflow, a plane whose normal is zero after narrowing and flushing. */
+#define EHM_NARROW_FLUSH 1
+int ehm_compiled_narrow_opts(ehm_compiled* law, int32_t flags, int64_t* flushed,
+                             ehm_compiled** out);
 /* ehm_compiled_export for a single law (EHM_E_INVALID for a double one, as ehm_compiled_export is
  * for a single one); a single law has no test_rec. */
 int ehm_compiled_export_single(ehm_compiled* law, float* node, float* leaf_rec, int32_t* leaf_node,

@@ -15,7 +15,14 @@ against its single-precision form (``CompiledLaw.to_single``) on the same two tr
 states in one process, the calls interleaved in the same way: kernel times, their ratio and spread
 (a ratio below 1 is reported as such), the device bytes of both laws against the stride formulas,
 and how far the two laws agree.  A tree whose law has no single form is reported with the values
-that refuse it.
+that refuse it.  ``--single --flush`` (profiles/compiled/single_flush_bench.txt): the headline tree
+alone, narrowed with ``to_single(flush=True)``; the counts of the values set to zero are reported.
+
+``--nested`` (profiles/compiled/nested_bench.txt): the p = 8 spine in the reference's nested layout
+(a right spine of data-less nodes, built without recursion), ``compile()`` -- a walk of test nodes --
+against ``compile(spine='roots')`` -- the root table and its locator -- on the same states.  The
+serial walk makes thousands of containment tests per state, so this case runs ``--nested-queries``
+states (default 2^14) and at most 5 calls per repeat.
 """
 import argparse
 import os
@@ -100,7 +107,7 @@ def single_bytes(st, p, n_u):
         + st['nbr_bytes']
 
 
-def run_single_case(name, flat, half, n_q, repeats, calls, rng, out):
+def run_single_case(name, flat, half, n_q, repeats, calls, rng, out, flush=False):
     from explicit_hybrid_mpc_amd import _capi
     ex = explicit.ExplicitMPC(flat)
     cl = ex.compile()
@@ -110,7 +117,7 @@ def run_single_case(name, flat, half, n_q, repeats, calls, rng, out):
         'time of %d calls' % (name, flat.n_nodes, flat.info['n_roots'], p, n_u, n_q, repeats, calls))
     try:
         t0 = time.perf_counter()
-        single = cl.to_single()
+        single = cl.to_single(flush=flush)
         wall = time.perf_counter() - t0
     except _capi.EhmError as err:
         a = cl.arrays()
@@ -126,6 +133,9 @@ def run_single_case(name, flat, half, n_q, repeats, calls, rng, out):
         cl.close()
         return
     s32 = single.stats
+    if flush:
+        out('  flushed to zero: %d plane coefficients, %d plane offsets, %d leaf values' % (
+            single.flushed['a'], single.flushed['b'], single.flushed['leaf']))
     X = rng.uniform(-1, 1, (n_q, half.size)) * half
     laws = ((cl, 'double'), (single, 'single'))
     for _ in range(3):                                      # warm-up: buffers, clocks, caches
@@ -165,6 +175,65 @@ def run_single_case(name, flat, half, n_q, repeats, calls, rng, out):
     single.close()
 
 
+def nested_spine(roots, n_u):
+    """The roots (leaves with zero inputs) hung off a right spine of data-less nodes, as the
+    reference nests its Delaunay pre-partition; iterative: the spine is as deep as it is long."""
+    from explicit_hybrid_mpc_amd.tree import NodeData, Tree
+    p1 = roots.shape[1]
+    leaf = lambda r: Tree(NodeData(roots[r], vertex_inputs=np.zeros((p1, n_u))), top=False)
+    R = roots.shape[0]
+    root = at = Tree(None)
+    for r in range(R - 1):
+        at.left = leaf(r)
+        at.right = leaf(r + 1) if r == R - 2 else Tree(None, top=False)
+        at = at.right
+    return root
+
+
+def run_nested_case(name, roots, n_u, half, n_q, repeats, calls, rng, out):
+    t0 = time.perf_counter()
+    tree = nested_spine(roots, n_u)
+    ex = explicit.ExplicitMPC(tree)
+    built = time.perf_counter() - t0
+    laws = []
+    for key, spine in (('tests', 'tests'), ('roots', 'roots')):
+        t0 = time.perf_counter()
+        laws.append((ex.compile(spine=spine), key, time.perf_counter() - t0))
+    ex.close()
+    X = rng.uniform(-1, 1, (n_q, half.size)) * half
+    out('case %s: nested layout, %d roots on a spine of %d data-less nodes (built and set up in '
+        '%.1f s), p = %d, n_u = %d, %d states; %d repeats, each the mean kernel time of %d calls' % (
+            name, roots.shape[0], roots.shape[0] - 1, built, roots.shape[2], n_u, n_q, repeats,
+            calls))
+    for law, _, _ in laws:                                  # warm-up: buffers, clocks, caches
+        law.evaluate(X)
+    times = {key: [] for _, key, _ in laws}
+    res = {}
+    for _ in range(repeats):
+        total = dict.fromkeys(times, 0.)
+        for _ in range(calls):                              # interleaved: drift hits both alike
+            for law, key, _ in laws:
+                u, leaf, vis, secs = law.evaluate(X, return_info=True)
+                total[key] += secs
+                res[key] = (u, leaf, float(vis.mean()))
+        for key in total:
+            times[key].append(total[key] / calls)
+    for law, key, wall in laws:
+        t, st = np.array(times[key]), law.stats
+        out("  spine='%s' kernel ms: median %.3f  min %.3f  max %.3f  (%.3g states/s, %.1f decisions "
+            'per state); %d test nodes, %d roots, %d device bytes, compile %.1f ms' % (
+                key, 1e3 * np.median(t), 1e3 * t.min(), 1e3 * t.max(), n_q / np.median(t),
+                res[key][2], st['n_test'], st['n_roots'], st['bytes'], 1e3 * wall))
+    tt, tr = np.median(times['tests']), np.median(times['roots'])
+    out('  tests / roots of the medians: %.1fx  (largest spread %.3f ms)' % (
+        tt / tr, 1e3 * max(np.ptp(times['tests']), np.ptp(times['roots']))))
+    same = res['tests'][1] == res['roots'][1]
+    out('  same leaf for %.4f %% of the states; inputs bit-equal there: %s' % (
+        100 * same.mean(), bool(np.array_equal(res['tests'][0][same], res['roots'][0][same]))))
+    for law, _, _ in laws:
+        law.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--queries', type=int, default=1 << 21)
@@ -174,17 +243,40 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--single', action='store_true',
                     help='the double compiled law against its single-precision form')
+    ap.add_argument('--flush', action='store_true',
+                    help='--single: the headline tree narrowed with flush=True')
+    ap.add_argument('--nested', action='store_true',
+                    help="the nested p = 8 spine: compile() against compile(spine='roots')")
+    ap.add_argument('--nested-queries', type=int, default=1 << 14)
     args = ap.parse_args()
+    if args.flush and not args.single:
+        ap.error('--flush goes with --single')
     case = run_single_case if args.single else run_case
-    if args.single and args.out is None:
-        args.out = os.path.join(ROOT, 'profiles', 'compiled', 'single_bench.txt')
+    if args.out is None and (args.single or args.nested):
+        args.out = os.path.join(ROOT, 'profiles', 'compiled',
+                                'nested_bench.txt' if args.nested else
+                                'single_flush_bench.txt' if args.flush else 'single_bench.txt')
     lines = []
 
     def out(s):
         print(s, flush=True)
         lines.append(s)
 
+    def save():
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, 'w') as f:
+                f.write('\n'.join(lines) + '\n')
+
     rng = np.random.default_rng(args.seed)
+    if args.nested:
+        mpc8 = examples.pwa4_mpc(N=bench.CONFIG5['N'], seed=args.seed)
+        half8 = examples.theta_box(mpc8)
+        roots8 = np.asarray(ehm_tools.delaunay_roots(examples.box_vertices(half8))[0],
+                            dtype=np.float64)
+        run_nested_case('p8_spine', roots8, int(mpc8.n_u), half8, args.nested_queries, args.repeats,
+                        min(args.calls, 5), rng, out)
+        return save()
     mpc = bench.make_mpc('config2', args.seed)
     gp = engine.GpuProblem(mpc.compile(), 1., 1.)
     half = examples.theta_box(mpc)
@@ -194,6 +286,10 @@ def main():
     roots, _ = ehm_tools.delaunay_roots(V)
     flat = gp.partition(roots, action='ecc', export=True, with_volume=False)
     gp.close()
+    if args.flush:
+        run_single_case('headline_tree', flat, half, args.queries, args.repeats, args.calls, rng, out,
+                        flush=True)
+        return save()
     case('headline_tree', flat, half, args.queries, args.repeats, args.calls, rng, out)
     mpc8 = examples.pwa4_mpc(N=bench.CONFIG5['N'], seed=args.seed)
     half8 = examples.theta_box(mpc8)
@@ -205,10 +301,7 @@ def main():
                             np.zeros((K, p8 + 1)), np.zeros((K, p8 + 1, n_u8)),
                             np.zeros(K, dtype=np.uint8), np.zeros(K), {'n_roots': K}, None)
     case('p8_spine', flat8, half8, args.queries, args.repeats, args.calls, rng, out)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, 'w') as f:
-            f.write('\n'.join(lines) + '\n')
+    save()
 
 
 if __name__ == '__main__':

@@ -3,7 +3,7 @@
 Closed-loop simulation throughput and the cwh_z delta-v overconsumption table (needs a GPU).
 
     python tools/rollout_bench.py [--n 1000000] [--T 100] [--jobs 1,2,3,4,5] [--n-compare 10000]
-                                  [--laws [--repeats 3]]
+                                  [--laws [--repeats 3] [--flush]]
 
 Trajectory-steps/s, one JSON line per tree and path:
   (a) fused    ExplicitMPC.rollout: one launch of ehm_explicit_rollout (device time of the kernel,
@@ -17,7 +17,9 @@ single-precision form (CompiledLaw.to_single()) in one process with the calls in
 --repeats rollouts of each after a warm-up, nominal and under a noise model, kernel time; one JSON
 line per tree and case with the applied trajectory-steps/s of each (median, min .. max), the ratios
 compiled / explicit and single / compiled, and whether the rollouts ended alike.  A law without a
-single form is reported (``single`` holds the refusal) and the other two run.
+single form is reported (``single`` holds the refusal) and the other two run; with --flush such a
+law is narrowed with ``to_single(flush=True)`` instead and the line carries ``flushed``, the counts
+of the values set to zero.
 Trees: the headline partition (linear_mpc(0), abs_frac 0.02, eps_r 1e-2, as bench.py) and cwh_z
 job 1.  Then simulate.compare on cwh_z jobs 1..5 (lib/post_process.py:484-526 / make_jobs.sh) from
 uniform initial states in the box, nominal and with a box-bounded process disturbance; the
@@ -109,7 +111,7 @@ def rates(name, mpc, flat, n, T, rng):
     ex.close()
 
 
-def both_laws(name, mpc, flat, model, n, T, repeats, rng):
+def both_laws(name, mpc, flat, model, n, T, repeats, rng, flush=False):
     """The explicit law, the compiled law and its single-precision form on the same states in one
     process, calls interleaved."""
     from explicit_hybrid_mpc_amd import _capi
@@ -121,6 +123,9 @@ def both_laws(name, mpc, flat, model, n, T, repeats, rng):
         laws.append(('single', cl.to_single()))
     except _capi.EhmError as err:
         refusal = str(err)
+        if flush:
+            laws.append(('single', cl.to_single(flush=True)))
+    flushed = laws[-1][1].flushed if laws[-1][0] == 'single' else None
     half = examples.theta_box(mpc)
     X0 = rng.uniform(-1, 1, (n, half.size)) * half
     for label, kw in (('nominal', {}), ('noisy', dict(noise=model, seed=1))):
@@ -158,6 +163,9 @@ def both_laws(name, mpc, flat, model, n, T, repeats, rng):
                 / np.maximum(res.u_norm_sum[both], 1e-300))) if both.any() else None
         else:
             row['single'] = refusal
+        if flushed is not None:
+            row['flushed'] = flushed
+            row['refusal_without_flush'] = refusal
         print(json.dumps(row), flush=True)
     for _, law in laws:
         law.close()
@@ -172,17 +180,19 @@ def main():
     ap.add_argument('--skip-rates', action='store_true')
     ap.add_argument('--laws', action='store_true')
     ap.add_argument('--repeats', type=int, default=3)
+    ap.add_argument('--flush', action='store_true',
+                    help='--laws: narrow with flush=True where the plain narrowing refuses')
     args = ap.parse_args()
     rng = np.random.default_rng(0)
     if args.laws:
         mpc, flat = headline_tree()
         both_laws('headline (configs[2])', mpc, flat,
                   state_input_model(examples.theta_box(mpc), mpc.B[0].shape[1]), args.n, args.T,
-                  args.repeats, rng)
+                  args.repeats, rng, args.flush)
         del flat
         oracle, flat = cwh_tree(1)
         both_laws('cwh_z job 1', oracle.mpc, flat, NoiseModel.from_mpc(oracle.mpc), args.n, args.T,
-                  args.repeats, rng)
+                  args.repeats, rng, args.flush)
         oracle.close()
         return
     if not args.skip_rates:
