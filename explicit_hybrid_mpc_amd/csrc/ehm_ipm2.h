@@ -150,6 +150,28 @@ __device__ __forceinline__ double dpp_move(double identity, double v) {
                                                ROW_MASK, 0xf, false);
     return __hiloint2double(hi, lo);
 }
+// Some VGPR, whatever it holds, at no instruction: the `old` operand of a DPP move whose result
+// is never read in the lanes that keep `old` (volatile: a fresh register at every use, so that
+// the move's destination needs no copy).
+__device__ __forceinline__ int any_vgpr() {
+    int x;
+    asm volatile("" : "=v"(x));
+    return x;
+}
+// The same move with zero fill (bound_ctrl): a lane whose source lies outside its row receives 0.
+// With every row written (ROW_MASK 0xf) `old` is dead and the two v_mov_b32 0 a stage of the
+// identity form pays, with the hazard no-op behind them, are not emitted.  Exact for sums; for a
+// maximum only where every operand is >= +0.0.  A row broadcast (ROW_MASK 0xa / 0xc) leaves the
+// rows outside the mask with `old`: the reductions below read their result in lane 63 (a row of
+// both masks) only, so those rows may keep anything.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_fill0(double v) {
+    const int olo = (ROW_MASK == 0xf) ? 0 : any_vgpr();
+    const int ohi = (ROW_MASK == 0xf) ? 0 : any_vgpr();
+    const int lo = __builtin_amdgcn_update_dpp(olo, __double2loint(v), CTRL, ROW_MASK, 0xf, true);
+    const int hi = __builtin_amdgcn_update_dpp(ohi, __double2hiint(v), CTRL, ROW_MASK, 0xf, true);
+    return __hiloint2double(hi, lo);
+}
 __device__ __forceinline__ double lane63(double v) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63);
     const int hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
@@ -178,8 +200,48 @@ __device__ __forceinline__ double wave_max(double v) {
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
     return v;
 }
+__device__ __forceinline__ double wave_max_nn(double v) { return wave_max(v); }
+template <int N>
+__device__ __forceinline__ void wave_sums(double (&v)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = wave_sum(v[i]);
+}
+template <int N>
+__device__ __forceinline__ void wave_maxs_nn(double (&v)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = wave_max(v[i]);
+}
 #else
-__device__ __forceinline__ double wave_sum(double v) { EHM2_DPP_REDUCE(op_add, 0.0) }
+// N independent reductions, stage by stage: the DPP chain of one (move, move, add -- each waits for
+// the one before) fills the issue slots the others leave.  Every chain is the single reduction's.
+#define EHM2_DPP_STAGE(OP, CTRL, ROW_MASK)                                                 \
+    _Pragma("unroll") for (int i = 0; i < N; ++i)                                          \
+        v[i] = OP(v[i], dpp_fill0<CTRL, ROW_MASK>(v[i]));
+#define EHM2_DPP_REDUCE_FILL0(OP)                                        \
+    EHM2_DPP_STAGE(OP, 0x111, 0xf)                                       \
+    EHM2_DPP_STAGE(OP, 0x112, 0xf)                                       \
+    EHM2_DPP_STAGE(OP, 0x114, 0xf)                                       \
+    EHM2_DPP_STAGE(OP, 0x118, 0xf)                                       \
+    EHM2_DPP_STAGE(OP, 0x142, 0xa)                                       \
+    EHM2_DPP_STAGE(OP, 0x143, 0xc)                                       \
+    _Pragma("unroll") for (int i = 0; i < N; ++i) v[i] = lane63(v[i]);
+template <int N>
+__device__ __forceinline__ void wave_sums(double (&v)[N]) { EHM2_DPP_REDUCE_FILL0(op_add) }
+// maxima of operands that are all >= +0.0 (the zero fill takes part in the maximum)
+template <int N>
+__device__ __forceinline__ void wave_maxs_nn(double (&v)[N]) { EHM2_DPP_REDUCE_FILL0(op_max) }
+__device__ __forceinline__ double wave_sum(double x) {
+    double v[1] = {x};
+    wave_sums(v);
+    return v[0];
+}
+__device__ __forceinline__ double wave_max_nn(double x) {
+    double v[1] = {x};
+    wave_maxs_nn(v);
+    return v[0];
+}
+// operands of any sign: the identity form (the self-test of ehm_k2.hip is the one call site;
+// every maximum of ipm_solve is taken over non-negative operands, see there)
 __device__ __forceinline__ double wave_max(double v) {
     EHM2_DPP_REDUCE(op_max, -__builtin_huge_val())
 }
@@ -201,6 +263,64 @@ __device__ __forceinline__ int pin(int x) {
 typedef __attribute__((address_space(3))) const volatile double lds_cvdouble;
 __device__ __forceinline__ double lds1(const double* p) {
     return *(lds_cvdouble*)p;      // explicit LDS pointer: a volatile generic load stays flat
+}
+// An LDS address held in a VGPR: what a loop derives from it (p += stride) is vector arithmetic.
+// The kernels that inline this solver have no scalar register to spare; a uniform address that
+// the compiler keeps in one costs a spill somewhere else.
+typedef __attribute__((address_space(3))) const volatile double* lds_vptr;
+__device__ __forceinline__ lds_vptr lds_pin(const double* p) {
+    lds_vptr q = (lds_vptr)p;
+    asm volatile("" : "+v"(q));
+    return q;
+}
+// acc <- fma(+-a[k sa], b[k sb], acc) for k = 0 .. cnt-1, one after the other on the ONE
+// accumulator: every operation of the plain loop, in its order (bit for bit its result).  What
+// changes is the issue: the 2 B loads of B trips are in flight behind one wait and the loop control
+// is paid once per B trips, where the plain loop waits for an LDS round trip per FMA.  The last
+// cnt % B trips run singly (no padding: nothing outside [0, cnt) is read).  a, b: LDS.
+template <int B, bool NEG>
+__device__ __forceinline__ double fma_run(const double* a_, int sa, const double* b_, int sb,
+                                          int cnt, double acc) {
+    lds_vptr a = lds_pin(a_), b = lds_pin(b_);
+    int r = cnt;        // counted down: one scalar register for both loops
+    for (; r >= B; r -= B) {
+        double av[B], bv[B];
+#pragma unroll
+        for (int u = 0; u < B; ++u) {
+            av[u] = *a;
+            bv[u] = *b;
+            a += sa;
+            b += sb;
+        }
+#pragma unroll
+        for (int u = 0; u < B; ++u) acc = fma(NEG ? -av[u] : av[u], bv[u], acc);
+    }
+    for (; r > 0; --r) {
+        const double av = *a;
+        acc = fma(NEG ? -av : av, *b, acc);
+        a += sa;
+        b += sb;
+    }
+    return acc;
+}
+// acc <- acc + a[k], k = 0 .. cnt-1, in that order: the same for a plain sum
+template <int B>
+__device__ __forceinline__ double add_run(const double* a_, int cnt, double acc) {
+    lds_vptr a = lds_pin(a_);
+    int r = cnt;
+    for (; r >= B; r -= B) {
+        double av[B];
+#pragma unroll
+        for (int u = 0; u < B; ++u) av[u] = a[u];
+#pragma unroll
+        for (int u = 0; u < B; ++u) acc += av[u];
+        a += B;
+    }
+    for (; r > 0; --r) {
+        acc += *a;
+        ++a;
+    }
+    return acc;
 }
 // A wave-uniform double parked in an SGPR pair: there is no scalar FP unit, so uniform doubles
 // (norms, tolerances, the best merit) otherwise occupy two VGPRs each for the whole solve.
@@ -576,13 +696,26 @@ __device__ __forceinline__ void rows_times(const Shared& S, const Wave& W, int l
         pa += UR * lda;
         pb += UR * str;
     }
-    for (; j < W.n_lin; ++j) {
-        const double yj = y[j];
+    if (j < W.n_lin) {      // n_lin % UR columns are left: the loads of all of them, then the FMAs
+        constexpr int UL = (UR > 1) ? UR - 1 : 1;
+        double a[UL][SLOTS], yj[UL], vl[UL];
+        const int left = W.n_lin - j;
 #pragma unroll
-        for (int sl = 0; sl < SLOTS - 1; ++sl) out[sl] = fma(lds1(pa + 64 * sl), yj, out[sl]);
-        out[SLOTS - 1] = fma(lds1(pb), lds1(pv + j), out[SLOTS - 1]);
-        pa += lda;
-        pb += str;
+        for (int u = 0; u < UL; ++u)
+            if (u < left) {
+                yj[u] = y[j + u];
+                vl[u] = lds1(pv + j + u);
+#pragma unroll
+                for (int sl = 0; sl < SLOTS - 1; ++sl) a[u][sl] = lds1(pa + u * lda + 64 * sl);
+                a[u][SLOTS - 1] = lds1(pb + u * str);
+            }
+#pragma unroll
+        for (int u = 0; u < UL; ++u)
+            if (u < left) {
+#pragma unroll
+                for (int sl = 0; sl < SLOTS - 1; ++sl) out[sl] = fma(a[u][sl], yj[u], out[sl]);
+                out[SLOTS - 1] = fma(a[u][SLOTS - 1], vl[u], out[SLOTS - 1]);
+            }
     }
     if (W.n_lin < W.nr) {
         const double vj = v[W.n_lin];       // the special column is not a beta column
@@ -605,15 +738,12 @@ __device__ __forceinline__ void rows_times(const Shared& S, const Wave& W, int l
         if (rm.last_extra) {
             const int xe = rm.lane + 64 * (SLOTS - 1) - W.xbase - W.nsx;
             const double* xr = W.X + (size_t)W.nr * W.ldx + xe;
-            double a = 0.0;
-            for (int e = 0; e < W.nE; ++e) a = fma(xr[(size_t)e * W.ldx], vE[e], a);
-            out[SLOTS - 1] += a;
+            out[SLOTS - 1] += fma_run<4, false>(xr, pin(W.ldx), vE, 1, W.nE, 0.0);
         }
     }
     if (W.nsx > 0) {
         // the simplex rows: -beta_e, and the sum of the weights for the last one
-        double sb = 0.0;
-        for (int q = 0; q < W.npsi; ++q) sb += v[W.psi0 + q];
+        const double sb = add_run<4>(v + W.psi0, W.npsi, 0.0);
         if (rm.last_sx >= 0)
             out[SLOTS - 1] = (rm.last_sx < W.npsi) ? -v[W.psi0 + (rm.last_sx < W.npsi ? rm.last_sx : 0)]
                                                   : sb;
@@ -1073,16 +1203,36 @@ __device__ __forceinline__ void form_eliminated(const Shared& S, const Wave& W, 
 
 // Sum over the lanes 0..15 (one DPP row), returned to every lane; lanes >= 16 must pass 0 --
 // 14 instructions where the wave reduction takes 22.
-__device__ __forceinline__ double row16_sum(double v) {
-    v += dpp_move<0x111, 0xf>(0.0, v);
-    v += dpp_move<0x112, 0xf>(0.0, v);
-    v += dpp_move<0x114, 0xf>(0.0, v);
-    v += dpp_move<0x118, 0xf>(0.0, v);
-    return readlane_d(v, 15);
+// (N independent sums side by side, like wave_sums.)
+template <int N>
+__device__ __forceinline__ void row16_sums(double (&v)[N]) {
+#ifdef EHM2_REDUCE_SHFL
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        v[i] += dpp_move<0x111, 0xf>(0.0, v[i]);
+        v[i] += dpp_move<0x112, 0xf>(0.0, v[i]);
+        v[i] += dpp_move<0x114, 0xf>(0.0, v[i]);
+        v[i] += dpp_move<0x118, 0xf>(0.0, v[i]);
+    }
+#else
+    EHM2_DPP_STAGE(op_add, 0x111, 0xf)
+    EHM2_DPP_STAGE(op_add, 0x112, 0xf)
+    EHM2_DPP_STAGE(op_add, 0x114, 0xf)
+    EHM2_DPP_STAGE(op_add, 0x118, 0xf)
+#endif
+#pragma unroll
+    for (int i = 0; i < N; ++i) v[i] = readlane_d(v[i], 15);
 }
-// sum of v over the lanes [0, cnt) (0 elsewhere): one DPP row when they fit, else the wave
-__device__ __forceinline__ double few_sum(double v, int cnt) {
-    return (cnt <= 16) ? row16_sum(v) : wave_sum(v);
+// sums of v[.] over the lanes [0, cnt) (0 elsewhere): one DPP row when they fit, else the wave
+template <int N>
+__device__ __forceinline__ void few_sums(double (&v)[N], int cnt) {
+    if (cnt <= 16) row16_sums(v);
+    else wave_sums(v);
+}
+__device__ __forceinline__ double few_sum(double x, int cnt) {
+    double v[1] = {x};
+    few_sums(v, cnt);
+    return v[0];
 }
 
 // psi-form -> beta-form of the weight block of the square matrix in LDS and of the eliminated
@@ -1336,16 +1486,43 @@ __device__ __forceinline__ void dense_prep(const Shared& S, const Wave& W, const
             W.hX[nEp + lane] = h1;
         }
         wsync();
-        if (lane < W.nr)
-            for (int e = 0; e < W.nE; ++e) {
-                const double g = W.gE[e * GS + lane];
-                x0 = fma(-W.hX[e], g, x0);
-                x1 = fma(-W.hX[nEp + e], g, x1);
+        if (lane < W.nr) {
+            // five columns' loads behind one wait; each accumulator takes its FMAs in the plain
+            // loop's order (the last nE % 5 columns singly)
+            lds_vptr pg = lds_pin(W.gE + lane), ph = lds_pin(W.hX);
+            int left = W.nE;
+            for (; left >= 5; left -= 5) {
+                double g[5], a0[5], a1[5];
+#pragma unroll
+                for (int u = 0; u < 5; ++u) {
+                    g[u] = pg[u * GS];
+                    a0[u] = ph[u];
+                    a1[u] = ph[nEp + u];
+                }
+#pragma unroll
+                for (int u = 0; u < 5; ++u) {
+                    x0 = fma(-a0[u], g[u], x0);
+                    x1 = fma(-a1[u], g[u], x1);
+                }
+                pg += 5 * GS;
+                ph += 5;
             }
-        g11 += few_sum(h0 * xe0, W.nE);
-        if (two) {
-            g12 = few_sum(h0 * xe1, W.nE);
-            g22 += few_sum(h1 * xe1, W.nE);
+            for (; left > 0; --left) {
+                const double g = *pg;
+                x0 = fma(-*ph, g, x0);
+                x1 = fma(-ph[nEp], g, x1);
+                pg += GS;
+                ++ph;
+            }
+        }
+        if (two) {      // three independent sums, reduced side by side
+            double gs[3] = {h0 * xe0, h0 * xe1, h1 * xe1};
+            few_sums(gs, W.nE);
+            g11 += gs[0];
+            g12 = gs[1];
+            g22 += gs[2];
+        } else {
+            g11 += few_sum(h0 * xe0, W.nE);
         }
     }
     const double i1 = frcp(g11);
@@ -1379,14 +1556,19 @@ __device__ __forceinline__ double solve_full(const double (&row)[NP], const Shar
     if (W.nE > 0) {
         if (el) W.qE[e] = rhs * W.iD[e];
         wsync();
-        if (lane < W.nr)
-            for (int e2 = 0; e2 < W.nE; ++e2) rr = fma(-W.gE[e2 * GS + lane], W.qE[e2], rr);
+        if (lane < W.nr) rr = fma_run<5, true>(W.gE + lane, GS, W.qE, 1, W.nE, rr);
         if (kd > 0) {       // rho = X_E Delta^-1 r_E
             const bool l2 = lane < W.nE;
             const double* xr = W.X + (size_t)(W.nr + (l2 ? lane : 0)) * W.ldx;
             const double q = l2 ? W.qE[l2 ? lane : 0] : 0.0;
-            rho0 = few_sum(l2 ? xr[0] * q : 0.0, W.nE);
-            if (two) rho1 = few_sum(l2 ? xr[1] * q : 0.0, W.nE);
+            if (two) {      // the two rows' sums are independent: reduced side by side
+                double rs2[2] = {l2 ? xr[0] * q : 0.0, l2 ? xr[1] * q : 0.0};
+                few_sums(rs2, W.nE);
+                rho0 = rs2[0];
+                rho1 = rs2[1];
+            } else {
+                rho0 = few_sum(l2 ? xr[0] * q : 0.0, W.nE);
+            }
         }
     }
     double l = 0.0, i1 = 0.0, i2 = 0.0;
@@ -1402,8 +1584,15 @@ __device__ __forceinline__ double solve_full(const double (&row)[NP], const Shar
     double y0 = 0.0, y1 = 0.0;
     if (kd > 0 && W.nE > 0) {       // (without eliminated columns nothing needs y)
         const bool lr = lane < W.nr;
-        const double v0 = few_sum(lr ? W.xh[jl] * xD : 0.0, W.nr) + rho0;
-        const double v1 = two ? (few_sum(lr ? W.xh[NP + jl] * xD : 0.0, W.nr) + rho1) : 0.0;
+        double v0, v1 = 0.0;
+        if (two) {
+            double vs[2] = {lr ? W.xh[jl] * xD : 0.0, lr ? W.xh[NP + jl] * xD : 0.0};
+            few_sums(vs, W.nr);
+            v0 = vs[0] + rho0;
+            v1 = vs[1] + rho1;
+        } else {
+            v0 = few_sum(lr ? W.xh[jl] * xD : 0.0, W.nr) + rho0;
+        }
         y1 = v1 * i2;
         y0 = fma(-l, y1, v0 * i1);
     }
@@ -1412,6 +1601,8 @@ __device__ __forceinline__ double solve_full(const double (&row)[NP], const Shar
         if (el) {
             double acc = rhs;
             const double* ge = W.gE + e * GS;
+            // (left rolled: row[] is live here, and as a run of fma_run -- at every block size
+            // from 2 to 5 -- the two-width persistent kernel no longer fits its registers)
             for (int j = 0; j < W.nr; ++j) acc = fma(-ge[j], W.t[j], acc);
             if (kd > 0) {
                 const double* xr = W.X + (size_t)(W.nr + e) * W.ldx;
@@ -1453,9 +1644,9 @@ __device__ __forceinline__ IpmResult ipm_solve(const Shared& S, const Wave& W, c
         lam[sl] = rm.valid[sl] ? 1.0 : 0.0;
         bmax = fmax(bmax, fabs(v[sl]));
     }
-    const double bnorm = uniform_d(1.0 + wave_max(bmax));
+    const double bnorm = uniform_d(1.0 + wave_max_nn(bmax));      // |b_i| >= 0
     const double cj = (lane < n) ? W.c[lane] : 0.0;
-    const double cnorm = uniform_d(1.0 + wave_max(fabs(cj)));
+    const double cnorm = uniform_d(1.0 + wave_max_nn(fabs(cj)));
     step_frac = uniform_d(step_frac);
     if (lane < n) {
         W.x[lane] = 0.0;
@@ -1550,8 +1741,8 @@ __device__ __forceinline__ IpmResult ipm_solve(const Shared& S, const Wave& W, c
         // the dual residual in the metric of the Hessian's diagonal (see ehm_ipm.h)
         const double r_d = (lane < n) ? (atl + cjj + gjj) *
             (W.quad ? rsqrt(1.0 + W.Q[lane * LDM + lane]) : 1.0) : 0.0;
-        const double cn = W.quad ? (1.0 + wave_max(fmax(fabs(cjj), fabs(gjj)))) : cnorm;
-        const double emax = wave_max(fmax(rpmax / bnorm, fabs(r_d) / cn));
+        const double cn = W.quad ? (1.0 + wave_max_nn(fmax(fabs(cjj), fabs(gjj)))) : cnorm;
+        const double emax = wave_max_nn(fmax(rpmax / bnorm, fabs(r_d) / cn));
         const double sl_tot = wave_sum(sl_sum);
         const double mu = sl_tot * inv_m;
         double pobj = wave_sum(cjj * xjj);
@@ -1563,11 +1754,14 @@ __device__ __forceinline__ IpmResult ipm_solve(const Shared& S, const Wave& W, c
         const double e_g = fabs(pobj - dobj) / (1.0 + fabs(pobj));
 #else
         const double r_d = (lane < n) ? (atl + cjj) : 0.0;
-        const double emax = wave_max(fmax(rpmax / bnorm, fabs(r_d) / cnorm));
-        const double mu = wave_sum(sl_sum) * inv_m;
+        // (rpmax and the absolute value are >= +0, the norms > 0: the zero-fill maximum is exact)
+        const double emax = wave_max_nn(fmax(rpmax / bnorm, fabs(r_d) / cnorm));
         // b^T lam = v^T lam + x^T (A^T lam)
-        const double dobj = -wave_sum(vl_sum + xjj * atl);
-        const double pobj = wave_sum(cjj * xjj);
+        double sums[3] = {sl_sum, vl_sum + xjj * atl, cjj * xjj};
+        wave_sums(sums);
+        const double mu = sums[0] * inv_m;
+        const double dobj = -sums[1];
+        const double pobj = sums[2];
         const double e_g = fabs(pobj - dobj) / (1.0 + fabs(pobj));
 #endif
         const double merit = fmax(emax / const_d(EHM2_TOL_RES), e_g / const_d(EHM2_TOL_GAP));
@@ -1710,8 +1904,12 @@ __device__ __forceinline__ IpmResult ipm_solve(const Shared& S, const Wave& W, c
             rho_p = fmax(rho_p, -ds_a[sl] * rs[sl]);
             rho_d = fmax(rho_d, rm.valid[sl] ? fma(ds_a[sl], rs[sl], 1.0) : 0.0);
         }
-        rho_p = wave_max(rho_p);
-        rho_d = wave_max(rho_d);
+        {   // both start from 0.0 under fmax: >= 0 in every lane
+            double rho[2] = {rho_p, rho_d};
+            wave_maxs_nn(rho);
+            rho_p = rho[0];
+            rho_d = rho[1];
+        }
         double ap = (rho_p > 1.0) ? 1.0 / rho_p : 1.0;
         double ad = (rho_d > 1.0) ? 1.0 / rho_d : 1.0;
 #if EHM2_QUAD
@@ -1757,8 +1955,12 @@ __device__ __forceinline__ IpmResult ipm_solve(const Shared& S, const Wave& W, c
             rho_p = fmax(rho_p, -ds[sl] * rs[sl]);
             rho_d = fmax(rho_d, -dl[sl] * rl);
         }
-        rho_p = wave_max(rho_p);
-        rho_d = wave_max(rho_d);
+        {
+            double rho[2] = {rho_p, rho_d};
+            wave_maxs_nn(rho);
+            rho_p = rho[0];
+            rho_d = rho[1];
+        }
         ap = (rho_p > step_frac) ? step_frac / rho_p : 1.0;
         ad = (rho_d > step_frac) ? step_frac / rho_d : 1.0;
 #if EHM2_QUAD
