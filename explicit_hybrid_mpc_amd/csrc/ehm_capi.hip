@@ -489,6 +489,7 @@ struct ehm_problem {
     int work_first = 1;      // 1 = a wavefront of the persistent kernel that splits a node goes on
                              // with one child itself and queues the other (option "work_first")
     int eager_children = 1;  // PersistDeal::eager (option "eager_children")
+    int requeue_undecided = 1;  // PersistDeal::requeue (option "requeue_undecided")
     int share_mid = 1;       // 1 = the persistent kernel keeps a table of midpoint optima: the
                              // simplices around an edge solve its midpoint once (DevTree::mt;
                              // option "share_midpoints")
@@ -1172,6 +1173,10 @@ int ehm_problem_set_option(ehm_problem* P, const char* name, double value) {
     }
     if (!strcmp(name, "eager_children")) {
         P->eager_children = value != 0.0;
+        return EHM_OK;
+    }
+    if (!strcmp(name, "requeue_undecided")) {
+        P->requeue_undecided = value != 0.0;
         return EHM_OK;
     }
     if (!strcmp(name, "budget_keep")) {
@@ -2651,6 +2656,7 @@ static int persistent_run(ehm_tree* T, long long max_pops = 0) {
     // profiles/r5/bench_2_gloo_ranks_dynamic_budget_keep.json)
     if (deal.pop_limit > 0 && !P->budget_keep) deal.keep = 0;
     deal.eager = P->eager_children ? 1 : 0;
+    deal.requeue = P->requeue_undecided ? 1 : 0;
     PersistCtl h{};
     h.head = 0;
     h.tail = (int)R.nf;

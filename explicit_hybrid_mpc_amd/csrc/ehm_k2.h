@@ -108,6 +108,9 @@ struct PersistDeal {
                     // wavefront keeps a child that still needs work, and a node the inherited
                     // witness proves open allocates its children before its midpoint solve.
                     // 0 = every child is decided by a visit of its own.  Same tree either way.
+    int requeue;    // 1 = a node whose midpoint another wavefront is solving goes back into the
+                    // queue (once) whether or not its fate is known (option "requeue_undecided");
+                    // 0 = only nodes the inherited witness has already opened do.
 };
 
 // Optional indirection of the batched oracle kernels: the hybrid partition engine

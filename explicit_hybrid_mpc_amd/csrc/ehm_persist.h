@@ -317,8 +317,11 @@ __global__ __launch_bounds__(EHM_K2_THREADS) void kx_persist(
                     // into the queue -- once -- and this wavefront takes another one instead of
                     // sleeping through the solve.  (Not in budgeted launches: their left-over
                     // must stay the contiguous slice behind the pop limit.)
-                    const bool may_requeue = decided && !came_back && deal.pop_limit <= 0 &&
-                                             id < EHM_REQUEUED;
+                    // With PersistDeal::requeue so does a node whose fate is still open: its
+                    // record, gradients and witness are in global memory like any queued node's,
+                    // and it has spent nothing yet that the second visit repeats but the loads.
+                    const bool may_requeue = (decided || deal.requeue) && !came_back &&
+                                             deal.pop_limit <= 0 && id < EHM_REQUEUED;
                     mt_res = mt_claim(T.mt, mt_tg, mt_i, t_start, EHM_PERSIST_WATCHDOG_TICKS,
                                       &mt_slot, &waited, may_requeue);
                     if (mt_res == MT_BUSY) {

@@ -176,7 +176,8 @@ class GpuProblem:
         check(self._lib.ehm_problem_set_solver(self._handle, int(generation)))
 
     def set_option(self, name, value):
-        """Named options of the handle (include/ehmpc.h: "solver", "decide_full")."""
+        """Named options of the handle (include/ehmpc.h: "solver", "decide_full", ...; for the
+        persistent frontier kernel "work_first", "eager_children", "requeue_undecided")."""
         check(self._lib.ehm_problem_set_option(self._handle, name.encode(), float(value)))
 
     # -- helpers ------------------------------------------------------------------------

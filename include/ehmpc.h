@@ -177,6 +177,10 @@ int ehm_problem_set_solver(ehm_problem* prob, int generation);
  * children before its midpoint solve.  0 = every child is decided by a visit of its own.
  * Identical tree (tests/test_gpu_eager_children.py); ehm_tree_info.persist_ticks[9] counts the
  * children closed at creation, persist_pushes the queue pushes;
+ * "requeue_undecided" (0|1, default 1): a node that finds its midpoint being solved by another
+ * wavefront goes back into the queue once whether or not its fate is known (0: only the nodes the
+ * inherited witness has opened, the others sleep through the solve); never in budgeted launches.
+ * Identical tree (tests/test_gpu_persist_idle.py); persist_ticks[8] counts the nodes put back;
  * "timing" (0|1, default 0): multi-commutation runs record an event pair and a counter snapshot
  * around every batched launch, so that ehm_tree_info carries kernel seconds and solves by problem
  * kind (bench.py sets it; ~25 extra stream commands per sweep otherwise spared). */
