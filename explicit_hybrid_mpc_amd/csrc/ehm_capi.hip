@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <set>
 #include <string>
@@ -15,6 +16,7 @@
 
 #include "../../include/ehmpc.h"
 #include "ehm_host.h"
+#include "ehm_batch_host.h"
 
 #define EHM_MAX_P_DEV 8
 #include "ehm_kernels.h"
@@ -715,18 +717,6 @@ static int k2_config(ehm_problem* P, int kind_a, int kind_b, long long n_items, 
     return EHM_OK;
 }
 
-// stable counting sort of a batch by commutation index: order[k] = original position of the
-// k-th instance of the sorted batch, seg[d] = first sorted position of commutation d
-static void sort_by_commutation(int nd, int64_t n, const int32_t* didx, std::vector<int64_t>& order,
-                                std::vector<int32_t>& seg) {
-    seg.assign((size_t)nd + 1, 0);
-    for (int64_t k = 0; k < n; ++k) seg[(size_t)didx[k] + 1]++;
-    for (int d = 0; d < nd; ++d) seg[(size_t)d + 1] += seg[(size_t)d];
-    std::vector<int32_t> pos(seg.begin(), seg.end() - 1);
-    order.resize((size_t)n);
-    for (int64_t k = 0; k < n; ++k) order[(size_t)pos[(size_t)didx[k]]++] = k;
-}
-
 // ---- eliminated columns (ehm_ipm2.h) ---------------------------------------
 #define EHM_ELIM_MAX_ROWS 16    // rows one eliminated column may have (Shared::LE)
 
@@ -1226,121 +1216,170 @@ int ehm_stats(ehm_problem* P, ehm_counters* out) {
 }
 
 // ---- batched oracles --------------------------------------------------------------------
+// Every batched oracle goes through run_batch: the caller describes its columns (per-instance
+// rows of host memory and the device buffers they are staged in) and passes the launch.
+// Inputs with host == nullptr are not uploaded and outputs with host == nullptr not fetched;
+// their device buffers are sized and handed to the launch all the same.
+struct BatchIn {
+    const double* host;
+    size_t width;            // doubles per instance
+    DevBuf* dev;
+};
+struct BatchOut {
+    void* host;
+    size_t bytes;            // per instance
+    DevBuf* dev;
+    size_t dev_off;          // byte offset in dev (the iteration counts live behind the status words)
+};
+// what a launch sees: the staged columns in the order they were described
+struct BatchDev {
+    long long n;
+    const double* in[2];     // (no oracle has more than two inputs and four outputs)
+    void* out[4];
+    bool want[4];            // the caller asked for this output
+    const int32_t* idx;      // generation 2: segment table [n_delta + 1]; generation 1: the
+                             // commutation of every instance
+};
+
+// synchronises the stream when the scope ends, however it ends: host memory that enqueued copies
+// read or write is declared before the guard and so outlives them
+struct StreamDrain {
+    hipStream_t s;
+    bool armed = true;
+    ~StreamDrain() {
+        if (armed) (void)hipStreamSynchronize(s);
+    }
+};
+
+// out[0] is the status word of every instance (int32).  generation 2: the instances travel sorted
+// by commutation (one constant block in LDS per run), the launch is timed into batch_seconds[slot]
+// and at most max_retry stalled instances are repeated on generation 1.
+// launch(cfg, dev): cfg = the picked K2Cfg, null on generation 1.
+using BatchLaunch = std::function<void(const K2Cfg*, const BatchDev&)>;
+static int run_batch(ehm_problem* P, int64_t n_inst, const int32_t* didx, int generation,
+                     int kind, int slot, int64_t max_retry, const std::vector<BatchIn>& in,
+                     const std::vector<BatchOut>& out, const BatchLaunch& launch) {
+    if (n_inst == 0) return EHM_OK;
+    HIP_TRY(hipSetDevice(P->device), EHM_E_HIP);
+    const bool sorted = generation == 2;
+    const size_t n = (size_t)n_inst;
+    std::vector<int64_t> order;
+    std::vector<int32_t> seg;
+    std::vector<std::vector<double>> in_stage(in.size());
+    std::vector<std::vector<char>> out_stage(out.size());
+    if (sorted) sort_by_commutation(P->dp.n_delta, n_inst, didx, order, seg);
+    DevBuf& idx_buf = sorted ? P->seg : P->in1;
+    const int32_t* idx_host = sorted ? seg.data() : didx;
+    const size_t idx_bytes = (sorted ? seg.size() : n) * sizeof(int32_t);
+    for (const BatchIn& c : in) HIP_TRY(c.dev->ensure(n * c.width * sizeof(double)), EHM_E_HIP);
+    for (const BatchOut& c : out) HIP_TRY(c.dev->ensure(c.dev_off + n * c.bytes), EHM_E_HIP);
+    HIP_TRY(idx_buf.ensure(idx_bytes), EHM_E_HIP);
+    K2Cfg cfg;
+    if (sorted)
+        if (int rc = k2_config(P, kind, kind, n_inst, cfg)) return rc;
+
+    StreamDrain drain{P->stream};
+    BatchDev dev{};
+    dev.n = (long long)n_inst;
+    dev.idx = idx_buf.as<int32_t>();
+    for (size_t i = 0; i < in.size(); ++i) {       // each input once, in its final order
+        const BatchIn& c = in[i];
+        dev.in[i] = c.dev->as<double>();
+        if (!c.host) continue;
+        if (sorted) in_stage[i] = gathered(c.host, order, c.width);
+        HIP_TRY(hipMemcpyAsync(c.dev->ptr, sorted ? in_stage[i].data() : c.host,
+                               n * c.width * sizeof(double), hipMemcpyHostToDevice, P->stream),
+                EHM_E_HIP);
+    }
+    HIP_TRY(hipMemcpyAsync(idx_buf.ptr, idx_host, idx_bytes, hipMemcpyHostToDevice, P->stream),
+            EHM_E_HIP);
+    for (size_t i = 0; i < out.size(); ++i) {
+        dev.out[i] = out[i].dev->as<char>() + out[i].dev_off;
+        dev.want[i] = out[i].host != nullptr;
+    }
+    if (sorted) (void)hipEventRecord(P->bev[0], P->stream);
+    launch(sorted ? &cfg : nullptr, dev);
+    if (sorted) (void)hipEventRecord(P->bev[1], P->stream);
+    P->launches++;
+    HIP_TRY(hipGetLastError(), EHM_E_HIP);
+    for (size_t i = 0; i < out.size(); ++i) {
+        const BatchOut& c = out[i];
+        if (!c.host && !(sorted && i == 0)) continue;
+        if (sorted) out_stage[i].resize(n * c.bytes);
+        HIP_TRY(hipMemcpyAsync(sorted ? (void*)out_stage[i].data() : c.host, dev.out[i],
+                               n * c.bytes, hipMemcpyDeviceToHost, P->stream), EHM_E_HIP);
+    }
+    HIP_TRY(hipStreamSynchronize(P->stream), EHM_E_HIP);
+    drain.armed = false;
+    if (!sorted) return EHM_OK;
+
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, P->bev[0], P->bev[1]) == hipSuccess) {
+        P->batch_seconds[slot] += 1e-3 * ms;
+        P->batch_launches[slot]++;
+    }
+    for (size_t i = 0; i < out.size(); ++i)
+        if (out[i].host)
+            scatter_rows((char*)out[i].host, out_stage[i].data(), order, out[i].bytes);
+    const int32_t* st = reinterpret_cast<const int32_t*>(out_stage[0].data());
+    std::vector<int64_t> bad;
+    for (size_t k = 0; k < n; ++k)
+        if (st[k] != 0) bad.push_back(order[k]);
+    // numerical safety net: an LP the shared-block kernels (psi-coordinates) could not bring
+    // to tolerance is repeated by the generation-1 kernel (barycentric coordinates, private
+    // copy of the LP) -- a few per ten million on hybrid instances (an infeasible instance
+    // stays "stalled")
+    if (bad.empty() || !P->v1_ok || (int64_t)bad.size() > max_retry) return EHM_OK;
+    const std::vector<int32_t> d2 = gathered(didx, bad, 1);
+    std::vector<BatchIn> in2 = in;
+    std::vector<BatchOut> out2 = out;
+    std::vector<std::vector<double>> in_retry(in.size());
+    std::vector<std::vector<char>> out_retry(out.size());
+    for (size_t i = 0; i < in.size(); ++i)
+        if (in[i].host) {
+            in_retry[i] = gathered(in[i].host, bad, in[i].width);
+            in2[i].host = in_retry[i].data();
+        }
+    for (size_t i = 0; i < out.size(); ++i)
+        if (out[i].host || i == 0) {
+            out_retry[i].resize(bad.size() * out[i].bytes);
+            out2[i].host = out_retry[i].data();
+        }
+    if (int rc = run_batch(P, (int64_t)bad.size(), d2.data(), 1, kind, slot, 0, in2, out2, launch))
+        return rc;
+    const int32_t* st2 = reinterpret_cast<const int32_t*>(out_retry[0].data());
+    int64_t taken = 0;
+    for (size_t i = 0; i < out.size(); ++i)
+        if (out[i].host)
+            taken = merge_retried((char*)out[i].host, out_retry[i].data(), bad, st2, out[i].bytes);
+    P->fallbacks += taken;
+    return EHM_OK;
+}
+
 static int point_batch(ehm_problem* P, int64_t n_inst, const double* theta,
                        const int32_t* didx_host, int feas, double* J, double* u0,
                        int32_t* status, int32_t* iters) {
-    if (n_inst == 0) return EHM_OK;
-    HIP_TRY(hipSetDevice(P->device), EHM_E_HIP);
-    const int p = P->dp.p, n_u = P->dp.n_u;
-    int rc;
-    HIP_TRY(P->in0.ensure((size_t)n_inst * p * sizeof(double)), EHM_E_HIP);
-    HIP_TRY(P->in1.ensure((size_t)n_inst * sizeof(int32_t)), EHM_E_HIP);
-    HIP_TRY(P->out0.ensure((size_t)n_inst * sizeof(double)), EHM_E_HIP);
-    HIP_TRY(P->out1.ensure((size_t)n_inst * n_u * sizeof(double)), EHM_E_HIP);
-    HIP_TRY(P->out2.ensure((size_t)n_inst * 2 * sizeof(int32_t)), EHM_E_HIP);
-    HIP_TRY(hipMemcpyAsync(P->in0.ptr, theta, (size_t)n_inst * p * sizeof(double),
-                           hipMemcpyHostToDevice, P->stream), EHM_E_HIP);
-    HIP_TRY(hipMemcpyAsync(P->in1.ptr, didx_host, (size_t)n_inst * sizeof(int32_t),
-                           hipMemcpyHostToDevice, P->stream), EHM_E_HIP);
-    int32_t* d_status = P->out2.as<int32_t>();
-    int32_t* d_iters = d_status + n_inst;
-    if (P->solver_gen == 2) {
-        // instances travel sorted by commutation (one constant block in LDS per run)
-        const int nd = P->dp.n_delta;
-        std::vector<int64_t> order;
-        std::vector<int32_t> seg;
-        sort_by_commutation(nd, n_inst, didx_host, order, seg);
-        std::vector<double> th((size_t)n_inst * p);
-        for (int64_t k = 0; k < n_inst; ++k)
-            std::memcpy(&th[(size_t)k * p], theta + (size_t)order[(size_t)k] * p, p * sizeof(double));
-        HIP_TRY(P->seg.ensure(seg.size() * sizeof(int32_t)), EHM_E_HIP);
-        HIP_TRY(hipMemcpyAsync(P->in0.ptr, th.data(), th.size() * sizeof(double),
-                               hipMemcpyHostToDevice, P->stream), EHM_E_HIP);
-        HIP_TRY(hipMemcpyAsync(P->seg.ptr, seg.data(), seg.size() * sizeof(int32_t),
-                               hipMemcpyHostToDevice, P->stream), EHM_E_HIP);
-        K2Cfg cfg;
-        if ((rc = k2_config(P, feas ? LP_FEAS : LP_POINT, feas ? LP_FEAS : LP_POINT, n_inst, cfg)))
-            return rc;
-        (void)hipEventRecord(P->bev[0], P->stream);
-        cfg.api->point(cfg.L, P->dp, (long long)n_inst, P->in0.as<double>(),
-                       P->seg.as<int32_t>(), feas, P->out0.as<double>(), P->out1.as<double>(),
-                       d_status, d_iters, P->counters(), K2Gather{});
-        (void)hipEventRecord(P->bev[1], P->stream);
-        P->launches++;
-        HIP_TRY(hipGetLastError(), EHM_E_HIP);
-        std::vector<double> Js((size_t)n_inst), us(u0 ? (size_t)n_inst * n_u : 0);
-        std::vector<int32_t> sts((size_t)n_inst), its((size_t)n_inst);
-        HIP_TRY(hipMemcpyAsync(Js.data(), P->out0.ptr, (size_t)n_inst * sizeof(double),
-                               hipMemcpyDeviceToHost, P->stream), EHM_E_HIP);
-        if (u0)
-            HIP_TRY(hipMemcpyAsync(us.data(), P->out1.ptr, (size_t)n_inst * n_u * sizeof(double),
-                                   hipMemcpyDeviceToHost, P->stream), EHM_E_HIP);
-        HIP_TRY(hipMemcpyAsync(sts.data(), d_status, (size_t)n_inst * sizeof(int32_t),
-                               hipMemcpyDeviceToHost, P->stream), EHM_E_HIP);
-        HIP_TRY(hipMemcpyAsync(its.data(), d_iters, (size_t)n_inst * sizeof(int32_t),
-                               hipMemcpyDeviceToHost, P->stream), EHM_E_HIP);
-        HIP_TRY(hipStreamSynchronize(P->stream), EHM_E_HIP);
-        {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, P->bev[0], P->bev[1]) == hipSuccess) {
-                P->batch_seconds[0] += 1e-3 * ms;
-                P->batch_launches[0]++;
-            }
-        }
-        std::vector<int64_t> bad;
-        for (int64_t k = 0; k < n_inst; ++k) {
-            const int64_t o = order[(size_t)k];
-            J[o] = Js[(size_t)k];
-            if (u0) std::memcpy(u0 + (size_t)o * n_u, &us[(size_t)k * n_u], n_u * sizeof(double));
-            if (status) status[o] = sts[(size_t)k];
-            if (iters) iters[o] = its[(size_t)k];
-            if (sts[(size_t)k] != 0) bad.push_back(o);
-        }
-        // same safety net as in simplex_batch (an infeasible instance stays "stalled")
-        if (!bad.empty() && P->v1_ok && (int64_t)bad.size() * 4 <= n_inst) {
-            const int64_t nb = (int64_t)bad.size();
-            std::vector<double> t2((size_t)nb * p), J2((size_t)nb), u2((size_t)nb * n_u);
-            std::vector<int32_t> d2((size_t)nb), s2((size_t)nb), i2((size_t)nb);
-            for (int64_t k = 0; k < nb; ++k) {
-                std::memcpy(&t2[(size_t)k * p], theta + (size_t)bad[(size_t)k] * p, p * sizeof(double));
-                d2[(size_t)k] = didx_host[bad[(size_t)k]];
-            }
-            P->solver_gen = 1;
-            rc = point_batch(P, nb, t2.data(), d2.data(), feas, J2.data(), u2.data(), s2.data(),
-                             i2.data());
-            P->solver_gen = 2;
-            if (rc) return rc;
-            for (int64_t k = 0; k < nb; ++k) {
-                if (s2[(size_t)k] != 0) continue;
-                const int64_t o = bad[(size_t)k];
-                J[o] = J2[(size_t)k];
-                if (u0) std::memcpy(u0 + (size_t)o * n_u, &u2[(size_t)k * n_u], n_u * sizeof(double));
-                if (status) status[o] = 0;
-                if (iters) iters[o] = i2[(size_t)k];
-                P->fallbacks++;
-            }
-        }
-        return EHM_OK;
-    }
-    hipLaunchKernelGGL(k_point_batch, dim3(grid_for(P, n_inst)), dim3(64), P->lds_point,
-                       P->stream, P->dp, (long long)n_inst, P->in0.as<double>(),
-                       P->in1.as<int32_t>(), feas, P->out0.as<double>(), P->out1.as<double>(),
-                       d_status, d_iters, P->counters(), K2Gather{});
-    P->launches++;
-    HIP_TRY(hipGetLastError(), EHM_E_HIP);
-    HIP_TRY(hipMemcpyAsync(J, P->out0.ptr, (size_t)n_inst * sizeof(double),
-                           hipMemcpyDeviceToHost, P->stream), EHM_E_HIP);
-    if (u0)
-        HIP_TRY(hipMemcpyAsync(u0, P->out1.ptr, (size_t)n_inst * n_u * sizeof(double),
-                               hipMemcpyDeviceToHost, P->stream), EHM_E_HIP);
-    if (status)
-        HIP_TRY(hipMemcpyAsync(status, d_status, (size_t)n_inst * sizeof(int32_t),
-                               hipMemcpyDeviceToHost, P->stream), EHM_E_HIP);
-    if (iters)
-        HIP_TRY(hipMemcpyAsync(iters, d_iters, (size_t)n_inst * sizeof(int32_t),
-                               hipMemcpyDeviceToHost, P->stream), EHM_E_HIP);
-    HIP_TRY(hipStreamSynchronize(P->stream), EHM_E_HIP);
-    return EHM_OK;
+    const size_t p = P->dp.p, n_u = P->dp.n_u;
+    auto launch = [P, feas](const K2Cfg* cfg, const BatchDev& d) {
+        double* dJ = (double*)d.out[1];
+        double* du0 = (double*)d.out[2];
+        int32_t* dst = (int32_t*)d.out[0];
+        int32_t* dit = (int32_t*)d.out[3];
+        if (cfg)
+            cfg->api->point(cfg->L, P->dp, d.n, d.in[0], d.idx, feas, dJ, du0, dst, dit,
+                            P->counters(), K2Gather{});
+        else
+            hipLaunchKernelGGL(k_point_batch, dim3(grid_for(P, d.n)), dim3(64), P->lds_point,
+                               P->stream, P->dp, d.n, d.in[0], d.idx, feas, dJ, du0, dst, dit,
+                               P->counters(), K2Gather{});
+    };
+    return run_batch(P, n_inst, didx_host, P->solver_gen, feas ? LP_FEAS : LP_POINT, 0,
+                     n_inst / 4, {{theta, p, &P->in0}},
+                     {{status, sizeof(int32_t), &P->out2, 0},
+                      {J, sizeof(double), &P->out0, 0},
+                      {u0, n_u * sizeof(double), &P->out1, 0},
+                      {iters, sizeof(int32_t), &P->out2, (size_t)n_inst * sizeof(int32_t)}},
+                     launch);
 }
 
 int ehm_solve_ptd_batch(ehm_problem* P, int64_t n_inst, const double* theta,
@@ -1373,134 +1412,34 @@ int ehm_feas_ptd_batch(ehm_problem* P, int64_t n_inst, const double* theta,
     return EHM_OK;
 }
 
+// the point form retries only where few instances stalled; this one whenever the generation-1
+// kernels fit
 static int simplex_batch(ehm_problem* P, int64_t n_inst, const double* R, const double* Vbar,
                          const int32_t* didx_host, int slack, double* obj, double* alpha,
                          int32_t* status) {
-    if (n_inst == 0) return EHM_OK;
-    HIP_TRY(hipSetDevice(P->device), EHM_E_HIP);
-    const int p = P->dp.p;
-    const size_t nR = (size_t)(p + 1) * p;
-    int rc;
-    HIP_TRY(P->in0.ensure((size_t)n_inst * nR * sizeof(double)), EHM_E_HIP);
-    HIP_TRY(P->in1.ensure((size_t)n_inst * sizeof(int32_t)), EHM_E_HIP);
-    HIP_TRY(P->in2.ensure((size_t)n_inst * (p + 1) * sizeof(double)), EHM_E_HIP);
-    HIP_TRY(P->out0.ensure((size_t)n_inst * sizeof(double)), EHM_E_HIP);
-    HIP_TRY(P->out1.ensure((size_t)n_inst * (p + 1) * sizeof(double)), EHM_E_HIP);
-    HIP_TRY(P->out2.ensure((size_t)n_inst * 2 * sizeof(int32_t)), EHM_E_HIP);
-    HIP_TRY(hipMemcpyAsync(P->in0.ptr, R, (size_t)n_inst * nR * sizeof(double),
-                           hipMemcpyHostToDevice, P->stream), EHM_E_HIP);
-    HIP_TRY(hipMemcpyAsync(P->in1.ptr, didx_host, (size_t)n_inst * sizeof(int32_t),
-                           hipMemcpyHostToDevice, P->stream), EHM_E_HIP);
-    if (slack == SX_SLACK)
-        HIP_TRY(hipMemcpyAsync(P->in2.ptr, Vbar, (size_t)n_inst * (p + 1) * sizeof(double),
-                               hipMemcpyHostToDevice, P->stream), EHM_E_HIP);
-    int32_t* d_status = P->out2.as<int32_t>();
-    if (P->solver_gen == 2) {
-        const int nd = P->dp.n_delta, nv = p + 1;
-        std::vector<int64_t> order;
-        std::vector<int32_t> seg;
-        sort_by_commutation(nd, n_inst, didx_host, order, seg);
-        std::vector<double> Rs((size_t)n_inst * nR), Vs(slack == SX_SLACK ? (size_t)n_inst * nv : 0);
-        for (int64_t k = 0; k < n_inst; ++k) {
-            const int64_t o = order[(size_t)k];
-            std::memcpy(&Rs[(size_t)k * nR], R + (size_t)o * nR, nR * sizeof(double));
-            if (slack == SX_SLACK)
-                std::memcpy(&Vs[(size_t)k * nv], Vbar + (size_t)o * nv, nv * sizeof(double));
-        }
-        HIP_TRY(P->seg.ensure(seg.size() * sizeof(int32_t)), EHM_E_HIP);
-        HIP_TRY(hipMemcpyAsync(P->in0.ptr, Rs.data(), Rs.size() * sizeof(double),
-                               hipMemcpyHostToDevice, P->stream), EHM_E_HIP);
-        if (slack == SX_SLACK)
-            HIP_TRY(hipMemcpyAsync(P->in2.ptr, Vs.data(), Vs.size() * sizeof(double),
-                                   hipMemcpyHostToDevice, P->stream), EHM_E_HIP);
-        HIP_TRY(hipMemcpyAsync(P->seg.ptr, seg.data(), seg.size() * sizeof(int32_t),
-                               hipMemcpyHostToDevice, P->stream), EHM_E_HIP);
-        const int kind = (slack == SX_SLACK) ? LP_SLACK
-                         : (slack == SX_FEAS) ? LP_FEAS_SIMPLEX : LP_MIN_SIMPLEX;
-        K2Cfg cfg;
-        if ((rc = k2_config(P, kind, kind, n_inst, cfg))) return rc;
-        (void)hipEventRecord(P->bev[0], P->stream);
-        cfg.api->simplex(cfg.L, P->dp, (long long)n_inst, P->in0.as<double>(),
-                         P->in2.as<double>(), P->seg.as<int32_t>(), slack, P->out0.as<double>(),
-                         alpha ? P->out1.as<double>() : (double*)nullptr, d_status,
-                         d_status + n_inst, P->counters(), K2Gather{});
-        (void)hipEventRecord(P->bev[1], P->stream);
-        P->launches++;
-        HIP_TRY(hipGetLastError(), EHM_E_HIP);
-        std::vector<double> objs((size_t)n_inst), als(alpha ? (size_t)n_inst * nv : 0);
-        std::vector<int32_t> sts((size_t)n_inst);
-        HIP_TRY(hipMemcpyAsync(objs.data(), P->out0.ptr, (size_t)n_inst * sizeof(double),
-                               hipMemcpyDeviceToHost, P->stream), EHM_E_HIP);
-        if (alpha)
-            HIP_TRY(hipMemcpyAsync(als.data(), P->out1.ptr, (size_t)n_inst * nv * sizeof(double),
-                                   hipMemcpyDeviceToHost, P->stream), EHM_E_HIP);
-        HIP_TRY(hipMemcpyAsync(sts.data(), d_status, (size_t)n_inst * sizeof(int32_t),
-                               hipMemcpyDeviceToHost, P->stream), EHM_E_HIP);
-        HIP_TRY(hipStreamSynchronize(P->stream), EHM_E_HIP);
-        {
-            float ms = 0.f;
-            if (hipEventElapsedTime(&ms, P->bev[0], P->bev[1]) == hipSuccess) {
-                P->batch_seconds[1] += 1e-3 * ms;
-                P->batch_launches[1]++;
-            }
-        }
-        std::vector<int64_t> bad;
-        for (int64_t k = 0; k < n_inst; ++k) {
-            const int64_t o = order[(size_t)k];
-            obj[o] = objs[(size_t)k];
-            if (alpha) std::memcpy(alpha + (size_t)o * nv, &als[(size_t)k * nv], nv * sizeof(double));
-            if (status) status[o] = sts[(size_t)k];
-            if (sts[(size_t)k] != 0) bad.push_back(o);
-        }
-        // numerical safety net: an LP the shared-block kernels (psi-coordinates) could not bring
-        // to tolerance is repeated by the generation-1 kernel (barycentric coordinates, private
-        // copy of the LP) -- a few per ten million on hybrid instances
-        if (!bad.empty() && P->v1_ok) {
-            const int64_t nb = (int64_t)bad.size();
-            std::vector<double> R2((size_t)nb * nR), V2((size_t)nb * nv, 0.0), o2((size_t)nb),
-                a2((size_t)nb * nv);
-            std::vector<int32_t> d2((size_t)nb), s2((size_t)nb);
-            for (int64_t k = 0; k < nb; ++k) {
-                std::memcpy(&R2[(size_t)k * nR], R + (size_t)bad[(size_t)k] * nR, nR * sizeof(double));
-                if (slack == SX_SLACK)
-                    std::memcpy(&V2[(size_t)k * nv], Vbar + (size_t)bad[(size_t)k] * nv,
-                                nv * sizeof(double));
-                d2[(size_t)k] = didx_host[bad[(size_t)k]];
-            }
-            P->solver_gen = 1;
-            rc = simplex_batch(P, nb, R2.data(), V2.data(), d2.data(), slack, o2.data(),
-                               a2.data(), s2.data());
-            P->solver_gen = 2;
-            if (rc) return rc;
-            for (int64_t k = 0; k < nb; ++k) {
-                if (s2[(size_t)k] != 0) continue;
-                const int64_t o = bad[(size_t)k];
-                obj[o] = o2[(size_t)k];
-                if (alpha)
-                    std::memcpy(alpha + (size_t)o * nv, &a2[(size_t)k * nv], nv * sizeof(double));
-                if (status) status[o] = 0;
-                P->fallbacks++;
-            }
-        }
-        return EHM_OK;
-    }
-    hipLaunchKernelGGL(k_simplex_batch, dim3(grid_for(P, n_inst)), dim3(64), P->lds_simplex,
-                       P->stream, P->dp, (long long)n_inst, P->in0.as<double>(),
-                       P->in2.as<double>(), P->in1.as<int32_t>(), slack, P->out0.as<double>(),
-                       alpha ? P->out1.as<double>() : (double*)nullptr, d_status,
-                       d_status + n_inst, P->counters(), K2Gather{});
-    P->launches++;
-    HIP_TRY(hipGetLastError(), EHM_E_HIP);
-    HIP_TRY(hipMemcpyAsync(obj, P->out0.ptr, (size_t)n_inst * sizeof(double),
-                           hipMemcpyDeviceToHost, P->stream), EHM_E_HIP);
-    if (alpha)
-        HIP_TRY(hipMemcpyAsync(alpha, P->out1.ptr, (size_t)n_inst * (p + 1) * sizeof(double),
-                               hipMemcpyDeviceToHost, P->stream), EHM_E_HIP);
-    if (status)
-        HIP_TRY(hipMemcpyAsync(status, d_status, (size_t)n_inst * sizeof(int32_t),
-                               hipMemcpyDeviceToHost, P->stream), EHM_E_HIP);
-    HIP_TRY(hipStreamSynchronize(P->stream), EHM_E_HIP);
-    return EHM_OK;
+    const size_t nv = (size_t)P->dp.p + 1, nR = nv * P->dp.p;
+    auto launch = [P, slack](const K2Cfg* cfg, const BatchDev& d) {
+        double* dobj = (double*)d.out[1];
+        double* dal = d.want[2] ? (double*)d.out[2] : nullptr;
+        int32_t* dst = (int32_t*)d.out[0];
+        int32_t* dit = (int32_t*)d.out[3];
+        if (cfg)
+            cfg->api->simplex(cfg->L, P->dp, d.n, d.in[0], d.in[1], d.idx, slack, dobj, dal,
+                              dst, dit, P->counters(), K2Gather{});
+        else
+            hipLaunchKernelGGL(k_simplex_batch, dim3(grid_for(P, d.n)), dim3(64),
+                               P->lds_simplex, P->stream, P->dp, d.n, d.in[0], d.in[1], d.idx,
+                               slack, dobj, dal, dst, dit, P->counters(), K2Gather{});
+    };
+    const int kind = (slack == SX_SLACK) ? LP_SLACK
+                     : (slack == SX_FEAS) ? LP_FEAS_SIMPLEX : LP_MIN_SIMPLEX;
+    return run_batch(P, n_inst, didx_host, P->solver_gen, kind, 1, n_inst,
+                     {{R, nR, &P->in0}, {slack == SX_SLACK ? Vbar : nullptr, nv, &P->in2}},
+                     {{status, sizeof(int32_t), &P->out2, 0},
+                      {obj, sizeof(double), &P->out0, 0},
+                      {alpha, nv * sizeof(double), &P->out1, 0},
+                      {nullptr, sizeof(int32_t), &P->out2, (size_t)n_inst * sizeof(int32_t)}},
+                     launch);
 }
 
 int ehm_slack_batch(ehm_problem* P, int64_t n_inst, const double* R, const double* Vbar,
@@ -1550,6 +1489,8 @@ int ehm_min_simplex_batch(ehm_problem* P, int64_t n_inst, const double* R,
 // one LP each" (SURVEY.md section 8a); these entry points expand the (instance,
 // commutation[, vertex]) pairs on the host and run them as ONE batched launch per stage.
 // Canonical choice rules: DESIGN.md "canonical commutation rule".
+// Sub-batches are rows picked by index lists: where / gather_rows / scatter_rows,
+// ehm_batch_host.h.
 
 // feasibility of (theta_k, d_k) pairs through the phase-one LP
 static int feas_pairs(ehm_problem* P, int64_t K, const double* theta, const int32_t* didx,
@@ -1557,62 +1498,69 @@ static int feas_pairs(ehm_problem* P, int64_t K, const double* theta, const int3
     std::vector<double> tau((size_t)K);
     int rc = point_batch(P, K, theta, didx, 1, tau.data(), nullptr, nullptr, nullptr);
     if (rc) return rc;
-    ok.resize((size_t)K);
-    for (int64_t k = 0; k < K; ++k) ok[(size_t)k] = tau[(size_t)k] <= EHM_FEAS_TOL;
+    ok.resize(tau.size());
+    for (size_t k = 0; k < tau.size(); ++k) ok[k] = tau[k] <= EHM_FEAS_TOL;
     return EHM_OK;
+}
+
+// feasibility of every (parameter, commutation) pair: ok[k*nd + d]; th, di: the expanded pairs
+static int feas_all_pairs(ehm_problem* P, int64_t n_inst, const double* theta,
+                          std::vector<double>& th, std::vector<int32_t>& di,
+                          std::vector<uint8_t>& ok) {
+    const int nd = P->dp.n_delta;
+    std::vector<int64_t> inst((size_t)(n_inst * nd));
+    di.resize(inst.size());
+    for (size_t q = 0; q < inst.size(); ++q) {
+        inst[q] = (int64_t)q / nd;
+        di[q] = (int32_t)(q % nd);
+    }
+    th = gathered(theta, inst, P->dp.p);
+    return feas_pairs(P, n_inst * nd, th.data(), di.data(), ok);
 }
 
 int ehm_solve_pt_batch(ehm_problem* P, int64_t n_inst, const double* theta, double* J,
                        double* u0, int32_t* delta_idx) {
     if (!P || !theta || !J || n_inst < 0) return fail(EHM_E_INVALID, "bad argument");
-    const int nd = P->dp.n_delta, p = P->dp.p, n_u = P->dp.n_u;
-    const int64_t K = n_inst * nd;
-    std::vector<double> th((size_t)K * p);
-    std::vector<int32_t> di((size_t)K);
-    for (int64_t k = 0; k < n_inst; ++k)
-        for (int d = 0; d < nd; ++d) {
-            std::memcpy(&th[(size_t)(k * nd + d) * p], theta + (size_t)k * p, p * sizeof(double));
-            di[(size_t)(k * nd + d)] = d;
-        }
+    const int nd = P->dp.n_delta;
+    const size_t p = P->dp.p, n_u = P->dp.n_u;
+    std::vector<double> th;
+    std::vector<int32_t> di;
     std::vector<uint8_t> ok;
-    int rc = feas_pairs(P, K, th.data(), di.data(), ok);
+    int rc = feas_all_pairs(P, n_inst, theta, th, di, ok);
     if (rc) return rc;
     // solve only the feasible pairs
-    std::vector<int64_t> sel;
-    for (int64_t q = 0; q < K; ++q)
-        if (ok[(size_t)q]) sel.push_back(q);
-    const int64_t F = (int64_t)sel.size();
-    std::vector<double> th2((size_t)F * p), J2((size_t)F), u2((size_t)F * n_u);
-    std::vector<int32_t> di2((size_t)F), st2((size_t)F);
-    for (int64_t f = 0; f < F; ++f) {
-        std::memcpy(&th2[(size_t)f * p], &th[(size_t)sel[(size_t)f] * p], p * sizeof(double));
-        di2[(size_t)f] = di[(size_t)sel[(size_t)f]];
-    }
-    rc = point_batch(P, F, th2.data(), di2.data(), 0, J2.data(), u2.data(), st2.data(), nullptr);
+    const std::vector<int64_t> sel = where(n_inst * nd, [&](int64_t q) { return ok[q] != 0; });
+    const size_t F = sel.size();
+    const std::vector<double> th2 = gathered(th.data(), sel, p);
+    const std::vector<int32_t> di2 = gathered(di.data(), sel, 1);
+    std::vector<double> J2(F), u2(F * n_u);
+    std::vector<int32_t> st2(F);
+    rc = point_batch(P, (int64_t)F, th2.data(), di2.data(), 0, J2.data(), u2.data(), st2.data(),
+                     nullptr);
     if (rc) return rc;
     for (int64_t k = 0; k < n_inst; ++k) {
         J[k] = INFINITY;
         if (delta_idx) delta_idx[k] = -1;
         if (u0)
-            for (int c = 0; c < n_u; ++c) u0[k * n_u + c] = NAN;
+            for (size_t c = 0; c < n_u; ++c) u0[k * n_u + c] = NAN;
     }
     std::vector<double> Jmin((size_t)n_inst, INFINITY);
-    for (int64_t f = 0; f < F; ++f) {
-        if (st2[(size_t)f] != 0) continue;
-        const int64_t k = sel[(size_t)f] / nd;
-        Jmin[(size_t)k] = std::min(Jmin[(size_t)k], J2[(size_t)f]);
+    for (size_t f = 0; f < F; ++f) {
+        if (st2[f] != 0) continue;
+        const size_t k = sel[f] / nd;
+        Jmin[k] = std::min(Jmin[k], J2[f]);
     }
     std::vector<uint8_t> done((size_t)n_inst, 0);
-    for (int64_t f = 0; f < F; ++f) {      // f ascends with the commutation index
-        if (st2[(size_t)f] != 0) continue;
-        const int64_t k = sel[(size_t)f] / nd;
-        if (done[(size_t)k]) continue;
-        const double jm = Jmin[(size_t)k];
-        if (J2[(size_t)f] <= jm + EHM_TIE_TOL * (1.0 + std::fabs(jm))) {
-            done[(size_t)k] = 1;
-            J[k] = J2[(size_t)f];
-            if (delta_idx) delta_idx[k] = di2[(size_t)f];
-            if (u0) std::memcpy(u0 + k * n_u, &u2[(size_t)f * n_u], n_u * sizeof(double));
+    for (size_t f = 0; f < F; ++f) {      // f ascends with the commutation index
+        if (st2[f] != 0) continue;
+        const size_t k = sel[f] / nd;
+        if (done[k]) continue;
+        const double jm = Jmin[k];
+        if (J2[f] <= jm + EHM_TIE_TOL * (1.0 + std::fabs(jm))) {
+            done[k] = 1;
+            J[k] = J2[f];
+            if (delta_idx) delta_idx[k] = di2[f];
+            if (u0) std::memcpy(u0 + k * n_u, &u2[f * n_u], n_u * sizeof(double));
         }
     }
     return EHM_OK;
@@ -1651,22 +1599,20 @@ int ehm_imp_point(ehm_problem* P, int feas, long long max_items, const double* b
 static int vertex_feasible_mask(ehm_problem* P, int64_t n_inst, const double* R,
                                 std::vector<uint8_t>& mask) {
     const int nd = P->dp.n_delta, p = P->dp.p, nv = p + 1;
-    const int64_t K = n_inst * nd * nv;
-    std::vector<double> th((size_t)K * p);
-    std::vector<int32_t> di((size_t)K);
-    for (int64_t k = 0; k < n_inst; ++k)
-        for (int d = 0; d < nd; ++d)
-            for (int v = 0; v < nv; ++v) {
-                const int64_t q = (k * nd + d) * nv + v;
-                std::memcpy(&th[(size_t)q * p], R + ((size_t)k * nv + v) * p, p * sizeof(double));
-                di[(size_t)q] = d;
-            }
+    // pair q = (k*nd + d)*nv + v: vertex row k*nv + v of R under commutation d
+    std::vector<int64_t> rows((size_t)(n_inst * nd * nv));
+    std::vector<int32_t> di(rows.size());
+    for (size_t q = 0; q < rows.size(); ++q) {
+        rows[q] = (int64_t)(q / ((size_t)nd * nv)) * nv + (int64_t)(q % nv);
+        di[q] = (int32_t)((q / nv) % nd);
+    }
+    const std::vector<double> th = gathered(R, rows, p);
     std::vector<uint8_t> ok;
-    int rc = feas_pairs(P, K, th.data(), di.data(), ok);
+    int rc = feas_pairs(P, (int64_t)rows.size(), th.data(), di.data(), ok);
     if (rc) return rc;
     mask.assign((size_t)(n_inst * nd), 1);
-    for (int64_t q = 0; q < K; ++q)
-        if (!ok[(size_t)q]) mask[(size_t)(q / nv)] = 0;
+    for (size_t q = 0; q < ok.size(); ++q)
+        if (!ok[q]) mask[q / nv] = 0;
     return EHM_OK;
 }
 
@@ -1674,30 +1620,24 @@ static int vertex_feasible_mask(ehm_problem* P, int64_t n_inst, const double* R,
 static int vertex_solves(ehm_problem* P, int64_t n_inst, const double* R, const int32_t* dsel,
                          double* vJ, double* vu0, bool& all_ok) {
     const int p = P->dp.p, nv = p + 1, n_u = P->dp.n_u;
-    std::vector<int64_t> sel;
+    // the vertex rows of the selected simplices
+    std::vector<int64_t> rows;
+    std::vector<int32_t> di;
     for (int64_t k = 0; k < n_inst; ++k)
-        if (dsel[k] >= 0) sel.push_back(k);
-    const int64_t F = (int64_t)sel.size() * nv;
-    std::vector<double> th((size_t)F * p), J((size_t)F), u((size_t)F * n_u);
-    std::vector<int32_t> di((size_t)F), st((size_t)F);
-    for (size_t f = 0; f < sel.size(); ++f)
-        for (int v = 0; v < nv; ++v) {
-            std::memcpy(&th[(f * nv + v) * p], R + ((size_t)sel[f] * nv + v) * p,
-                        p * sizeof(double));
-            di[f * nv + v] = dsel[sel[f]];
+        for (int v = 0; v < nv && dsel[k] >= 0; ++v) {
+            rows.push_back(k * nv + v);
+            di.push_back(dsel[k]);
         }
-    int rc = point_batch(P, F, th.data(), di.data(), 0, J.data(), u.data(), st.data(), nullptr);
+    const size_t F = rows.size();
+    const std::vector<double> th = gathered(R, rows, p);
+    std::vector<double> J(F), u(F * n_u);
+    std::vector<int32_t> st(F);
+    int rc = point_batch(P, (int64_t)F, th.data(), di.data(), 0, J.data(), u.data(), st.data(),
+                         nullptr);
     if (rc) return rc;
-    all_ok = true;
-    for (size_t f = 0; f < sel.size(); ++f)
-        for (int v = 0; v < nv; ++v) {
-            const size_t q = f * nv + v;
-            if (st[q] != 0) all_ok = false;
-            if (vJ) vJ[(size_t)sel[f] * nv + v] = J[q];
-            if (vu0)
-                std::memcpy(vu0 + ((size_t)sel[f] * nv + v) * n_u, &u[q * n_u],
-                            n_u * sizeof(double));
-        }
+    all_ok = std::all_of(st.begin(), st.end(), [](int32_t s) { return s == 0; });
+    if (vJ) scatter_rows(vJ, J.data(), rows, 1);
+    if (vu0) scatter_rows(vu0, u.data(), rows, n_u);
     return EHM_OK;
 }
 
@@ -1732,95 +1672,71 @@ static int slack_all(ehm_problem* P, int64_t n_inst, const double* R, const doub
     // known[k*nd + d] (optional): 0 = run the phase-one problem, 1 = the commutation is known to
     // be feasible somewhere on the simplex (e.g. at a vertex), 2 = known to be infeasible on it
     // (e.g. on the parent simplex).  feas_out: the verdicts (1 = feasible with an interior).
-    const int nd = P->dp.n_delta, p = P->dp.p, nv = p + 1;
-    const size_t nR = (size_t)nv * p;
-    std::vector<int64_t> sel;
-    for (int64_t q = 0; q < n_inst * nd; ++q)
-        if ((!restrict_mask || (*restrict_mask)[(size_t)q]) && !(known && known[q] == 2))
-            sel.push_back(q);
-    int64_t F = (int64_t)sel.size();
-    std::vector<double> R2((size_t)F * nR), V2((size_t)F * nv), obj((size_t)F);
-    std::vector<int32_t> di((size_t)F), st((size_t)F);
-    for (int64_t f = 0; f < F; ++f) {
-        const int64_t k = sel[(size_t)f] / nd;
-        std::memcpy(&R2[(size_t)f * nR], R + (size_t)k * nR, nR * sizeof(double));
-        std::memcpy(&V2[(size_t)f * nv], Vbar + (size_t)k * nv, nv * sizeof(double));
-        di[(size_t)f] = (int32_t)(sel[(size_t)f] % nd);
+    const int nd = P->dp.n_delta, p = P->dp.p;
+    const size_t nv = (size_t)p + 1, nR = nv * p;
+    // the selected pairs f: pair sel[f] = k*nd + d, its simplex, bounds and commutation
+    std::vector<int64_t> sel = where(n_inst * nd, [&](int64_t q) {
+        return (!restrict_mask || (*restrict_mask)[(size_t)q]) && !(known && known[q] == 2);
+    });
+    std::vector<int64_t> inst(sel.size());
+    std::vector<int32_t> di(sel.size());
+    for (size_t f = 0; f < sel.size(); ++f) {
+        inst[f] = sel[f] / nd;
+        di[f] = (int32_t)(sel[f] % nd);
     }
+    std::vector<double> R2 = gathered(R, inst, nR), V2 = gathered(Vbar, inst, nv);
     tall.assign((size_t)(n_inst * nd), -INFINITY);
     if (alpha_all) alpha_all->assign((size_t)(n_inst * nd) * nv, 0.0);
     if (feas_out) feas_out->assign((size_t)(n_inst * nd), 0);
+    // phase one over the simplex for a subset of the selected pairs
+    auto phase_one = [&](const std::vector<int64_t>& sub, std::vector<double>& tau) {
+        const std::vector<double> Ra = gathered(R2.data(), sub, nR);
+        const std::vector<int32_t> da = gathered(di.data(), sub, 1);
+        std::vector<int32_t> sa(sub.size());
+        tau.resize(sub.size());
+        return simplex_batch(P, (int64_t)sub.size(), Ra.data(), nullptr, da.data(), SX_FEAS,
+                             tau.data(), nullptr, sa.data());
+    };
     std::vector<double> tau_sel;      // phase-one optimum of every pair that stays selected
     if (nd > 1) {
         // drop pairs whose commutation is infeasible on the whole simplex: phase one for the
         // pairs nothing is known about
-        std::vector<int64_t> ask;
-        for (int64_t f = 0; f < F; ++f)
-            if (!(known && known[sel[(size_t)f]] == 1)) ask.push_back(f);
-        const int64_t A = (int64_t)ask.size();
-        std::vector<double> Ra((size_t)A * nR), tau_a((size_t)A);
-        std::vector<int32_t> da((size_t)A), sa((size_t)A);
-        for (int64_t a = 0; a < A; ++a) {
-            const int64_t f = ask[(size_t)a];
-            std::memcpy(&Ra[(size_t)a * nR], &R2[(size_t)f * nR], nR * sizeof(double));
-            da[(size_t)a] = di[(size_t)f];
-        }
-        if (A > 0) {
-            int rc = simplex_batch(P, A, Ra.data(), nullptr, da.data(), SX_FEAS, tau_a.data(),
-                                   nullptr, sa.data());
-            if (rc) return rc;
-        }
+        const std::vector<int64_t> ask = where((int64_t)sel.size(), [&](int64_t f) {
+            return !(known && known[sel[(size_t)f]] == 1);
+        });
+        std::vector<double> tau_a;
+        if (int rc = phase_one(ask, tau_a)) return rc;
         // tau of a pair known to be feasible: far from the sliver band
-        std::fill(obj.begin(), obj.end(), -1.0);
-        for (int64_t a = 0; a < A; ++a) obj[(size_t)ask[(size_t)a]] = tau_a[(size_t)a];
-        std::vector<int64_t> sel2;
-        for (int64_t f = 0; f < F; ++f)
-            if (obj[(size_t)f] <= EHM_FEAS_TOL) sel2.push_back(f);
-        const int64_t F2 = (int64_t)sel2.size();
-        std::vector<double> R3((size_t)F2 * nR), V3((size_t)F2 * nv);
-        std::vector<int32_t> di3((size_t)F2);
-        std::vector<int64_t> sel3((size_t)F2);
-        for (int64_t g = 0; g < F2; ++g) {
-            const int64_t f = sel2[(size_t)g];
-            std::memcpy(&R3[(size_t)g * nR], &R2[(size_t)f * nR], nR * sizeof(double));
-            std::memcpy(&V3[(size_t)g * nv], &V2[(size_t)f * nv], nv * sizeof(double));
-            di3[(size_t)g] = di[(size_t)f];
-            sel3[(size_t)g] = sel[(size_t)f];
-            tau_sel.push_back(obj[(size_t)f]);
-        }
-        R2.swap(R3); V2.swap(V3); di.swap(di3); sel.swap(sel3);
-        F = F2;
-        obj.resize((size_t)F);
-        st.resize((size_t)F);
+        std::vector<double> tau(sel.size(), -1.0);
+        scatter_rows(tau.data(), tau_a.data(), ask, 1);
+        const std::vector<int64_t> keep = where((int64_t)sel.size(), [&](int64_t f) {
+            return tau[(size_t)f] <= EHM_FEAS_TOL;
+        });
+        R2 = gathered(R2.data(), keep, nR);
+        V2 = gathered(V2.data(), keep, nv);
+        di = gathered(di.data(), keep, 1);
+        sel = gathered(sel.data(), keep, 1);
+        tau_sel = gathered(tau.data(), keep, 1);
     }
-    std::vector<double> al((size_t)F * nv);
-    int rc = simplex_batch(P, F, R2.data(), V2.data(), di.data(), SX_SLACK, obj.data(),
+    const size_t F = sel.size();
+    std::vector<double> obj(F), al(F * nv);
+    std::vector<int32_t> st(F);
+    int rc = simplex_batch(P, (int64_t)F, R2.data(), V2.data(), di.data(), SX_SLACK, obj.data(),
                            al.data(), st.data());
     if (rc) return rc;
     if (known && !tau_sel.empty()) {
         // a pair taken as feasible on the caller's word (feasible at a vertex WITHIN the phase-one
         // tolerance) whose slack problem stalls: get its phase-one optimum now, so that the
         // sliver rule below judges it exactly as it would have without the hint
-        std::vector<int64_t> redo;
-        for (int64_t f = 0; f < F; ++f)
-            if (st[(size_t)f] != 0 && known[sel[(size_t)f]] == 1) redo.push_back(f);
-        const int64_t A = (int64_t)redo.size();
-        if (A > 0) {
-            std::vector<double> Ra((size_t)A * nR), tau_a((size_t)A);
-            std::vector<int32_t> da((size_t)A), sa((size_t)A);
-            for (int64_t a = 0; a < A; ++a) {
-                const int64_t f = redo[(size_t)a];
-                std::memcpy(&Ra[(size_t)a * nR], &R2[(size_t)f * nR], nR * sizeof(double));
-                da[(size_t)a] = di[(size_t)f];
-            }
-            rc = simplex_batch(P, A, Ra.data(), nullptr, da.data(), SX_FEAS, tau_a.data(), nullptr,
-                               sa.data());
-            if (rc) return rc;
-            for (int64_t a = 0; a < A; ++a) tau_sel[(size_t)redo[(size_t)a]] = tau_a[(size_t)a];
-        }
+        const std::vector<int64_t> redo = where((int64_t)F, [&](int64_t f) {
+            return st[(size_t)f] != 0 && known[sel[(size_t)f]] == 1;
+        });
+        std::vector<double> tau_a;
+        if ((rc = phase_one(redo, tau_a))) return rc;
+        scatter_rows(tau_sel.data(), tau_a.data(), redo, 1);
     }
-    for (int64_t f = 0; f < F; ++f) {
-        if (st[(size_t)f] != 0 && !tau_sel.empty() && tau_sel[(size_t)f] > -EHM_SLIVER_TOL) {
+    for (size_t f = 0; f < F; ++f) {
+        if (st[f] != 0 && !tau_sel.empty() && tau_sel[f] > -EHM_SLIVER_TOL) {
             // the commutation is feasible on the simplex only within the accuracy of the
             // phase-one optimum (|tau*| <= 1e-8 .. 1e-7 in row units): its feasible set has no
             // interior an interior-point method could work in.  It is treated as infeasible
@@ -1829,25 +1745,24 @@ static int slack_all(ehm_problem* P, int64_t n_inst, const double* R, const doub
             P->slivers++;
             continue;
         }
-        if (st[(size_t)f] != 0) {
+        if (st[f] != 0) {
             if (const char* path = getenv("EHM_DUMP_FAIL")) {     // debugging aid: the instance
                 if (FILE* fp = fopen(path, "w")) {
-                    fprintf(fp, "%d %d %.17g\n", (int)(sel[(size_t)f] % nd), p, obj[(size_t)f]);
-                    for (size_t q = 0; q < nR; ++q) fprintf(fp, "%.17g ", R2[(size_t)f * nR + q]);
+                    fprintf(fp, "%d %d %.17g\n", (int)(sel[f] % nd), p, obj[f]);
+                    for (size_t q = 0; q < nR; ++q) fprintf(fp, "%.17g ", R2[f * nR + q]);
                     fprintf(fp, "\n");
-                    for (int q = 0; q < nv; ++q) fprintf(fp, "%.17g ", V2[(size_t)f * nv + q]);
+                    for (size_t q = 0; q < nv; ++q) fprintf(fp, "%.17g ", V2[f * nv + q]);
                     fprintf(fp, "\n%.17g %.17g\n", P->dp.eps_a, P->dp.eps_r);
                     fclose(fp);
                 }
             }
             return fail(EHM_E_NUMERIC, "slack LP (instance %lld, commutation %d) did not converge",
-                        (long long)(sel[(size_t)f] / nd), (int)(sel[(size_t)f] % nd));
+                        (long long)(sel[f] / nd), (int)(sel[f] % nd));
         }
-        tall[(size_t)sel[(size_t)f]] = obj[(size_t)f];
-        if (feas_out) (*feas_out)[(size_t)sel[(size_t)f]] = 1;
+        tall[(size_t)sel[f]] = obj[f];
+        if (feas_out) (*feas_out)[(size_t)sel[f]] = 1;
         if (alpha_all)
-            std::memcpy(&(*alpha_all)[(size_t)sel[(size_t)f] * nv], &al[(size_t)f * nv],
-                        nv * sizeof(double));
+            std::memcpy(&(*alpha_all)[(size_t)sel[f] * nv], &al[f * nv], nv * sizeof(double));
     }
     return EHM_OK;
 }
@@ -1900,44 +1815,37 @@ static int bar_d_finish(ehm_problem* P, int64_t n_inst, const double* R, const d
                 ths[(size_t)k * p + c] = acc;
             }
         }
-        if (theta_star)
-            std::memcpy(theta_star + (size_t)k * p, &ths[(size_t)k * p], p * sizeof(double));
         if (var_small) var_small[k] = 0;
     }
+    if (theta_star) std::copy(ths.begin(), ths.end(), theta_star);
     bool all_ok = true;
     int rc = vertex_solves(P, n_inst, R, delta_idx, vJ, vu0, all_ok);
     if (rc) return rc;
     if (!all_ok) return fail(EHM_E_NUMERIC, "a vertex solve of bar_D did not converge");
     // in_variability_ball (lib/oracle.py:220-283) for the instances with a better commutation
-    std::vector<int64_t> sel;
-    for (int64_t k = 0; k < n_inst; ++k)
-        if (delta_idx[k] >= 0) sel.push_back(k);
-    const int64_t F = (int64_t)sel.size();
+    const std::vector<int64_t> sel = where(n_inst, [&](int64_t k) { return delta_idx[k] >= 0; });
+    const size_t F = sel.size();
     if (F > 0 && var_small) {
-        const size_t nR = (size_t)nv * p;
-        std::vector<double> R2((size_t)F * nR), Jmin((size_t)F), th2((size_t)F * p), Jth((size_t)F);
-        std::vector<int32_t> d_ref2((size_t)F), d_star2((size_t)F), st((size_t)F), st2((size_t)F);
-        for (int64_t f = 0; f < F; ++f) {
-            const int64_t k = sel[(size_t)f];
-            std::memcpy(&R2[(size_t)f * nR], R + (size_t)k * nR, nR * sizeof(double));
-            std::memcpy(&th2[(size_t)f * p], &ths[(size_t)k * p], p * sizeof(double));
-            d_ref2[(size_t)f] = dref[(size_t)k];
-            d_star2[(size_t)f] = delta_idx[k];
-        }
-        rc = simplex_batch(P, F, R2.data(), nullptr, d_ref2.data(), SX_MIN, Jmin.data(), nullptr,
-                           st.data());
+        const std::vector<double> R2 = gathered(R, sel, (size_t)nv * p),
+                                  th2 = gathered(ths.data(), sel, p);
+        const std::vector<int32_t> d_ref2 = gathered(dref.data(), sel, 1),
+                                   d_star2 = gathered(delta_idx, sel, 1);
+        std::vector<double> Jmin(F), Jth(F);
+        std::vector<int32_t> st(F), st2(F);
+        rc = simplex_batch(P, (int64_t)F, R2.data(), nullptr, d_ref2.data(), SX_MIN, Jmin.data(),
+                           nullptr, st.data());
         if (rc) return rc;
-        rc = point_batch(P, F, th2.data(), d_star2.data(), 0, Jth.data(), nullptr, st2.data(),
-                         nullptr);
+        rc = point_batch(P, (int64_t)F, th2.data(), d_star2.data(), 0, Jth.data(), nullptr,
+                         st2.data(), nullptr);
         if (rc) return rc;
-        for (int64_t f = 0; f < F; ++f) {
-            if (st[(size_t)f] != 0 || st2[(size_t)f] != 0)
+        for (size_t f = 0; f < F; ++f) {
+            if (st[f] != 0 || st2[f] != 0)
                 return fail(EHM_E_NUMERIC, "in_variability_ball solve did not converge");
-            const int64_t k = sel[(size_t)f];
+            const int64_t k = sel[f];
             double vmax = -INFINITY;
             for (int v = 0; v < nv; ++v) vmax = std::max(vmax, Vbar[(size_t)k * nv + v]);
-            const double rhs = std::max(P->dp.eps_a, P->dp.eps_r * Jth[(size_t)f]);
-            var_small[k] = (vmax - Jmin[(size_t)f] < rhs) ? 1 : 0;
+            const double rhs = std::max(P->dp.eps_a, P->dp.eps_r * Jth[f]);
+            var_small[k] = (vmax - Jmin[f] < rhs) ? 1 : 0;
         }
     }
     return EHM_OK;
@@ -1963,19 +1871,12 @@ int ehm_bar_d_batch(ehm_problem* P, int64_t n_inst, const double* R, const doubl
 // P_theta_delta(theta, d, check_feasibility=True) for EVERY commutation d: feasible[k*nd + d].
 int ehm_feas_all_batch(ehm_problem* P, int64_t n_inst, const double* theta, uint8_t* feasible) {
     if (!P || !theta || !feasible || n_inst < 0) return fail(EHM_E_INVALID, "bad argument");
-    const int nd = P->dp.n_delta, p = P->dp.p;
-    const int64_t K = n_inst * nd;
-    std::vector<double> th((size_t)K * p);
-    std::vector<int32_t> di((size_t)K);
-    for (int64_t k = 0; k < n_inst; ++k)
-        for (int d = 0; d < nd; ++d) {
-            std::memcpy(&th[(size_t)(k * nd + d) * p], theta + (size_t)k * p, p * sizeof(double));
-            di[(size_t)(k * nd + d)] = d;
-        }
+    std::vector<double> th;
+    std::vector<int32_t> di;
     std::vector<uint8_t> ok;
-    int rc = feas_pairs(P, K, th.data(), di.data(), ok);
+    int rc = feas_all_pairs(P, n_inst, theta, th, di, ok);
     if (rc) return rc;
-    for (int64_t q = 0; q < K; ++q) feasible[q] = ok[(size_t)q];
+    std::copy(ok.begin(), ok.end(), feasible);
     return EHM_OK;
 }
 
@@ -2017,54 +1918,38 @@ int ehm_lcss_batch(ehm_problem* P, int64_t n_inst, const double* R, const double
     std::vector<uint8_t> feas;
     rc = slack_all(P, n_inst, R, Vbar, nullptr, tall, &alpha_all, known.data(), &feas);
     if (rc) return rc;
-    std::vector<int64_t> open;
     for (int64_t k = 0; k < n_inst; ++k) {
         double tb = -INFINITY;
         for (int d = 0; d < nd; ++d) tb = std::max(tb, tall[(size_t)(k * nd + d)]);
         closed[k] = (tb >= 0.0) ? 0 : 1;
         if (tbest) tbest[k] = tb;
-        if (cand_out)
-            std::memcpy(cand_out + (size_t)k * nd, &feas[(size_t)k * nd], (size_t)nd);
         delta_idx[k] = -1;
         if (var_small) var_small[k] = 0;
-        if (!closed[k]) open.push_back(k);
     }
-    const int64_t M = (int64_t)open.size();
+    if (cand_out) std::copy(feas.begin(), feas.end(), cand_out);
+    const std::vector<int64_t> open = where(n_inst, [&](int64_t k) { return !closed[k]; });
+    const size_t M = open.size();
     if (M == 0) return EHM_OK;
     // bar_D for the open nodes, on compacted copies
-    const size_t nR = (size_t)nv * p;
-    const int n_u = P->dp.n_u;
-    std::vector<double> R2((size_t)M * nR), V2((size_t)M * nv), t2((size_t)(M * nd)),
-        a2((size_t)(M * nd) * nv), ths((size_t)M * p), vJ2((size_t)M * nv),
-        vu2((size_t)M * nv * n_u);
-    std::vector<uint8_t> m2((size_t)(M * nd)), vs2((size_t)M);
-    std::vector<int32_t> dr2((size_t)M), di2((size_t)M);
-    for (int64_t q = 0; q < M; ++q) {
-        const int64_t k = open[(size_t)q];
-        std::memcpy(&R2[(size_t)q * nR], R + (size_t)k * nR, nR * sizeof(double));
-        std::memcpy(&V2[(size_t)q * nv], Vbar + (size_t)k * nv, nv * sizeof(double));
-        std::memcpy(&t2[(size_t)q * nd], &tall[(size_t)k * nd], nd * sizeof(double));
-        std::memcpy(&a2[(size_t)q * nd * nv], &alpha_all[(size_t)k * nd * nv],
-                    (size_t)nd * nv * sizeof(double));
-        // commutations feasible at every vertex AND with an interior on the simplex
-        for (int d = 0; d < nd; ++d)
-            m2[(size_t)(q * nd + d)] = vall[(size_t)(k * nd + d)] && feas[(size_t)(k * nd + d)];
-        dr2[(size_t)q] = dref[(size_t)k];
-    }
-    rc = bar_d_finish(P, M, R2.data(), V2.data(), dr2, m2, t2, a2, di2.data(), ths.data(),
+    const size_t n_u = P->dp.n_u;
+    // commutations feasible at every vertex AND with an interior on the simplex
+    for (size_t q = 0; q < vall.size(); ++q) vall[q] = vall[q] && feas[q];
+    const std::vector<double> R2 = gathered(R, open, (size_t)nv * p), V2 = gathered(Vbar, open, nv),
+                              t2 = gathered(tall.data(), open, nd),
+                              a2 = gathered(alpha_all.data(), open, (size_t)nd * nv);
+    const std::vector<uint8_t> m2 = gathered(vall.data(), open, nd);
+    const std::vector<int32_t> dr2 = gathered(dref.data(), open, 1);
+    std::vector<double> ths(M * p), vJ2(M * nv), vu2(M * nv * n_u);
+    std::vector<uint8_t> vs2(M);
+    std::vector<int32_t> di2(M);
+    rc = bar_d_finish(P, (int64_t)M, R2.data(), V2.data(), dr2, m2, t2, a2, di2.data(), ths.data(),
                       vJ2.data(), vu2.data(), vs2.data());
     if (rc) return rc;
-    for (int64_t q = 0; q < M; ++q) {
-        const int64_t k = open[(size_t)q];
-        delta_idx[k] = di2[(size_t)q];
-        if (theta_star)
-            std::memcpy(theta_star + (size_t)k * p, &ths[(size_t)q * p], p * sizeof(double));
-        if (vJ) std::memcpy(vJ + (size_t)k * nv, &vJ2[(size_t)q * nv], nv * sizeof(double));
-        if (vu0)
-            std::memcpy(vu0 + (size_t)k * nv * n_u, &vu2[(size_t)q * nv * n_u],
-                        (size_t)nv * n_u * sizeof(double));
-        if (var_small) var_small[k] = vs2[(size_t)q];
-    }
+    scatter_rows(delta_idx, di2.data(), open, 1);
+    if (theta_star) scatter_rows(theta_star, ths.data(), open, p);
+    if (vJ) scatter_rows(vJ, vJ2.data(), open, nv);
+    if (vu0) scatter_rows(vu0, vu2.data(), open, nv * n_u);
+    if (var_small) scatter_rows(var_small, vs2.data(), open, 1);
     return EHM_OK;
 }
 
