@@ -23,6 +23,9 @@ EHM_E_INFEASIBLE = -5
 EHM_E_NUMERIC = -6
 # ehm_tree_persist_kernel families, by their EHM_PERSIST_* value (include/ehmpc.h)
 PERSIST_FAMILIES = ('none', 'k2', 'kp', 'kpm', 'k4')
+# ehm_problem_batch_kernel: families by their EHM_BATCH_* value, LP kinds by name
+BATCH_FAMILIES = (None, 'k1', 'k2', 'k3', 'k4')
+LP_KINDS = {'point': 0, 'feas': 1, 'min_simplex': 2, 'slack': 3, 'feas_simplex': 4}
 EHM_MAX_P = 8           # include/ehmpc.h
 
 # every symbol include/ehmpc.h declares
@@ -52,6 +55,7 @@ EXPORTED = [
     'ehm_compiled_set_noise', 'ehm_compiled_rollout', 'ehm_compiled_rollout_noisy',
     'ehm_compiled_narrow', 'ehm_compiled_export_single', 'ehm_compiled_validate_single',
     'ehm_compiled_import_single', 'ehm_compiled_create_opts', 'ehm_compiled_narrow_opts',
+    'ehm_problem_batch_kernel',
 ]
 EHM_COMPILE_SPINE_ROOTS = 1     # ehm_compiled_create_opts
 EHM_NARROW_FLUSH = 1            # ehm_compiled_narrow_opts
@@ -308,6 +312,7 @@ def load(build_if_missing=True):
     lib.ehm_solver_phase_ticks.argtypes = [vp, vp]
     lib.ehm_problem_layout.argtypes = [vp, vp]
     lib.ehm_tree_persist_kernel.argtypes = [vp, vp]
+    lib.ehm_problem_batch_kernel.argtypes = [vp, ctypes.c_int32, vp]
     for name in EXPORTED:
         fn = getattr(lib, name)
         if name not in ('ehm_last_error', 'ehm_version', 'ehm_stream',

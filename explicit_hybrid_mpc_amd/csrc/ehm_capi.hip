@@ -2095,6 +2095,29 @@ int ehm_tree_persist_kernel(const ehm_tree* T, int32_t out[4]) {
     return EHM_OK;
 }
 
+int ehm_problem_batch_kernel(ehm_problem* P, int32_t kind, int32_t out[4]) {
+    if (!P || !out) return fail(EHM_E_INVALID, "null argument");
+    if (kind < LP_POINT || kind > LP_FEAS_SIMPLEX) return fail(EHM_E_INVALID, "LP kind 0..4");
+    if (P->solver_gen == 1) {       // one wavefront per LP, sized at run time
+        int n_lp, ne;
+        kind_dims(P->dp, kind, n_lp, ne);
+        out[0] = EHM_BATCH_K1;
+        out[1] = EHM_V1_MAX_N;
+        out[2] = lp_slots(P->dp.m, ne);
+        out[3] = 64;
+        return EHM_OK;
+    }
+    HIP_TRY(hipSetDevice(P->device), EHM_E_HIP);
+    K2Cfg cfg;
+    if (int rc = k2_config(P, kind, kind, 1LL << 40, cfg)) return rc;
+    out[0] = cfg.api->fits ? EHM_BATCH_K4
+        : cfg.api->threads_per_lp > 64 ? EHM_BATCH_K3 : EHM_BATCH_K2;
+    out[1] = cfg.api->np;
+    out[2] = cfg.api->slots;
+    out[3] = cfg.api->threads_per_lp;
+    return EHM_OK;
+}
+
 int ehm_solver_phase_ticks(ehm_problem* P, int64_t out[24]) {
     if (!P || !out) return fail(EHM_E_INVALID, "null argument");
     HIP_TRY(hipSetDevice(P->device), EHM_E_HIP);

@@ -448,6 +448,14 @@ class GpuProblem:
         check(self._lib.ehm_problem_layout(self._handle, ctypes.addressof(out)))
         return dict(nd0=int(out[0]), nE=int(out[1]), LE=int(out[2]), lda=int(out[3]))
 
+    def batch_kernel(self, kind='slack'):
+        """ehm_problem_batch_kernel: (family, column capacity, row slots, threads per LP) of the
+        instance a batch of LP kind ``kind`` (a key of _capi.LP_KINDS, or its number) runs on."""
+        out = (ctypes.c_int32 * 4)()
+        check(self._lib.ehm_problem_batch_kernel(self._handle, _capi.LP_KINDS.get(kind, kind),
+                                                 ctypes.addressof(out)))
+        return (_capi.BATCH_FAMILIES[out[0]], int(out[1]), int(out[2]), int(out[3]))
+
     def stats(self):
         c = _capi.Counters()
         check(self._lib.ehm_stats(self._handle, ctypes.byref(c)))

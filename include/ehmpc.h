@@ -830,6 +830,22 @@ int ehm_problem_layout(ehm_problem* prob, int32_t out[4]);
 #define EHM_PERSIST_K4   4
 int ehm_tree_persist_kernel(const ehm_tree* tree, int32_t out[4]);
 
+/* The kernel instance a batched solve of LP kind `kind` would run on this handle now: 0 = point,
+ * 1 = point feasibility, 2 = minimum over a simplex, 3 = slack (suboptimality test), 4 = simplex
+ * feasibility.  out = { family, column capacity (factorised columns), row slots of 64 rows,
+ * threads per LP }.  family: EHM_BATCH_K1 (the generation-1 kernels, ehm_problem_set_solver; sized
+ * at run time, they report their column limit and the LP's own slots), _K2 (shared-block
+ * instances of ehm_k2.hip, one wavefront per LP), _K3 (streaming wide kernels, ehm_k3.hip: 8 or
+ * 16 slots), _K4 (LDS-resident wide family, ehm_k4.hip).  The sweeps of a partition (decide,
+ * expand, vertex solves) take the instance of the same kinds.  Follows the handle's solver
+ * generation, its eliminated columns and the EHM_K4* environment exactly as the launches do.
+ * Reporting only; no reference counterpart. */
+#define EHM_BATCH_K1 1
+#define EHM_BATCH_K2 2
+#define EHM_BATCH_K3 3
+#define EHM_BATCH_K4 4
+int ehm_problem_batch_kernel(ehm_problem* prob, int32_t kind, int32_t out[4]);
+
 /* Device self test of the wave-level primitives (DPP reductions, reciprocal) of every
  * compiled kernel instance: out[5*k .. 5*k+4] for instance k, expected
  * {1072, 99, 25, 1/3, -1}.  Test hook, not part of the reference's surface. */

@@ -20,10 +20,12 @@ def make_instance(kind, seed=0):
         return examples.pwa_mpc(seed)
     if kind == 'chain':
         # config 4 (n_x = 6, n_u = 3, N = 10, box constraints): LPs of 50..57 columns, 360..369
-        # rows -- the wide kernels (ehm_k3.hip)
+        # rows -- the LDS-resident wide kernels (ehm_k4.hip); the streaming ones (ehm_k3.hip) when
+        # the handle eliminates nothing (STREAMING_CHAIN)
         return examples.integrator_chain_mpc()
     if kind == 'chain_small':
-        # same family, n_x = 4, n_u = 2, N = 8: 32 + 4 + 1 = 37 columns, 3-tile normal matrix
+        # same family, n_x = 4, n_u = 2, N = 8: 32 + 4 + 1 = 37 columns, 21 of them factorised (a
+        # shared-block case, ehm_k2.hip)
         mpc = examples.integrator_chain_mpc(n_axes=2, N=8)
         examples.THETA_SCALE.setdefault(mpc.name, CHAIN_SMALL_SCALE)
         return mpc
@@ -135,6 +137,53 @@ def persistent_width_scale(row, tol=1e-4):
     from tools.calibrate_configs import max_feasible_scale
     s = max_feasible_scale(persistent_width_instance(row[:9] + (0.0,)), tol=tol)
     return math.floor(1e4 * s * examples.THETA_SAFETY) / 1e4
+
+
+def make_gp(row, can, eps_a, eps_r):
+    """GpuProblem of the row; EHM_SPARSE=0 while the handle is created for the s0 rows."""
+    import os
+    from explicit_hybrid_mpc_amd import engine
+    old = os.environ.get('EHM_SPARSE')
+    if row[8]:
+        os.environ['EHM_SPARSE'] = '0'
+    try:
+        gp = engine.GpuProblem(can, eps_a, eps_r)
+    finally:
+        if old is None:
+            os.environ.pop('EHM_SPARSE', None)
+        else:
+            os.environ['EHM_SPARSE'] = old
+    if row[8]:
+        assert gp.layout()['nE'] == 0
+    return gp
+
+
+# ---- laws the LDS-resident wide family refuses: the streaming wide kernels (ehm_k3.hip) ----------
+# Rows in the format above (family, np, np, slots, n_x, n_u, N, n_random, s0, theta scale); k3's two
+# instances hold 64 columns x 8 or 16 row slots.  What k4 refuses them for (K2Api::fits):
+#   B   30 x 520, p 4 (35 columns): more than 512 rows -- the 16-slot instance; 3-tile normal
+#       matrix, on a handle WITH eliminated columns (k3 ignores DevProblem::Wc4)
+#   C   50 x 520, p 4 (55 columns, all of which k3 factorises): more than 512 rows; 4 tiles
+#   D   40 x 440, p 4 (45 columns), s0: the reduced block does not fit the LDS budget; 3 tiles
+#   D4  the same law on a default handle (20 of 40 columns factorised): k4 takes it -- D's partner
+# ('chain' with s0 -- 57 factorised columns, 8 slots, 4 tiles -- is the fifth, see STREAMING_CHAIN)
+STREAMING_WIDE_ROWS = {
+    'B': ('k3', 64, 64, 16, 4, 1, 10, 32, False, 0.5378),
+    'C': ('k3', 64, 64, 16, 4, 3, 10, 24, False, 0.4582),
+    'D': ('k3', 64, 64, 8, 4, 2, 10, 20, True, 0.4962),
+    'D4': ('k4', 48, 48, 8, 4, 2, 10, 20, False, 0.4962),
+}
+STREAMING_CHAIN = ('k3', 64, 64, 8, None, None, None, None, True, 0.)     # make_instance('chain')
+# multi-commutation law on the 16-slot instance: 15 x 515, p 2, 32 commutations
+STREAMING_PWA = dict(n_x=2, n_u=1, N=5, n_random=90)
+STREAMING_PWA_SCALE = 0.2309     # 0.9 x max feasible scale (tools/calibrate_configs.py)
+
+
+def streaming_pwa_instance():
+    mpc = examples.pwa_mpc(seed=0, **STREAMING_PWA)
+    mpc.name = 'pwa_nx2_nu1_N5_r90_seed0'
+    examples.THETA_SCALE.setdefault(mpc.name, STREAMING_PWA_SCALE)
+    return mpc
 
 
 # ---- shared assertions of the sharded persistent runs (GPU tests) --------------------------------

@@ -293,9 +293,10 @@ def test_sharded_hybrid_runs_tile_the_tree():
 def test_hybrid_engine_on_the_wide_kernels():
     """
     256 commutations on LPs of 33..37 columns: the multi-commutation engine through the wide
-    (one workgroup per LP, MFMA normal matrix) kernels of ehm_k3.hip -- the kernel family of
-    BASELINE.json's configs[3] / configs[4].  Batched oracles and a sub-forest of a truncated
-    partition against the CPU oracle.
+    (one workgroup per LP, MFMA normal matrix) kernels -- the LDS-resident family of ehm_k4.hip,
+    which BASELINE.json's configs[3] / configs[4] run on; tests/test_gpu_streaming_wide.py has
+    the engine on the streaming family (ehm_k3.hip).  Batched oracles and a sub-forest of a
+    truncated partition against the CPU oracle.
     """
     from explicit_hybrid_mpc_amd import engine, examples
     from oracle.oracle_cpu import OracleCPU

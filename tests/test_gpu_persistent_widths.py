@@ -16,8 +16,6 @@ with the row-major image of the wide kernels (DevProblem::Wr3), pins the guard o
 sweeps when dealt and refuses a budget.
 """
 
-import os
-
 import numpy as np
 import pytest
 
@@ -65,22 +63,7 @@ def expected_kernel(row, mid_first=1, decide_full=0, restricted=False):
     return (fam, d, e, sl)
 
 
-def make_gp(row, can, eps_a, eps_r):
-    """GpuProblem of the row; EHM_SPARSE=0 while the handle is created for the s0 rows."""
-    from explicit_hybrid_mpc_amd import engine
-    old = os.environ.get('EHM_SPARSE')
-    if row[8]:
-        os.environ['EHM_SPARSE'] = '0'
-    try:
-        gp = engine.GpuProblem(can, eps_a, eps_r)
-    finally:
-        if old is None:
-            os.environ.pop('EHM_SPARSE', None)
-        else:
-            os.environ['EHM_SPARSE'] = old
-    if row[8]:
-        assert gp.layout()['nE'] == 0
-    return gp
+make_gp = helpers.make_gp
 
 
 def root_of(tree):

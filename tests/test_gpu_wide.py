@@ -1,8 +1,18 @@
 """
-The wide kernels (ehm_k3.hip: one workgroup per LP, constant block from L2, normal matrix on
-the matrix cores) against the CPU oracle, through the C-ABI: BASELINE.json config 4
-(n_x = 6, n_u = 3, N = 10, box constraints -- LPs of 50..57 columns and 360..369 rows) and a
-smaller member of the same family whose normal matrix needs three tiles instead of four.
+The laws with more than 32 LP columns against the CPU oracle, through the C-ABI: BASELINE.json
+config 4 ('chain': n_x = 6, n_u = 3, N = 10, box constraints -- LPs of 50..57 columns and 360..369
+rows), a smaller member of the same family ('chain_small', 32..37 columns x 192..199 rows) and a
+256-commutation PWA law.  They were the test of the streaming wide kernels (ehm_k3.hip) until
+k2_pick came to prefer other families; what the handles run now is asserted below
+(ehm_problem_batch_kernel):
+
+- chain and the PWA law: the LDS-resident wide family (ehm_k4.hip) -- 20 resp. 16 columns are
+  eliminated, the 37 resp. 21 factorised ones make a 3- resp. 2-tile normal matrix;
+- chain_small: with 16 of its columns eliminated it is a SHARED-BLOCK case (ehm_k2.hip, one
+  wavefront per LP, 16..24 factorised columns), although the handle carries the row-major image of
+  the wide kernels.
+
+The streaming kernels have their own module, tests/test_gpu_streaming_wide.py.
 Same bars as the narrow kernels: optimal values within 1e-7 (1 + |value|), feasibility
 verdicts equal, identical tree on a sub-forest the CPU oracle finishes in about a minute.
 """
@@ -29,6 +39,22 @@ def wide(request):
     orc = OracleCPU(mpc, eps_a, eps_r)
     yield mpc, gp, orc
     gp.close()
+
+
+# (family, column capacity, row slots, threads per LP) per LP kind: point, feasibility, minimum over
+# a simplex, slack
+K4 = ('k4', 48, 8, 512)
+ROUTES = {'chain': (K4, K4, K4, K4),
+          'chain_small': (('k2', 16, 3, 64), ('k2', 20, 4, 64), ('k2', 20, 4, 64),
+                          ('k2', 24, 4, 64))}
+KINDS = ('point', 'feas', 'min_simplex', 'slack')
+
+
+def test_fixtures_route_to_the_families_the_docstring_names(wide):
+    mpc, gp, _ = wide
+    kind = 'chain' if gp.can.n == 50 else 'chain_small'
+    assert gp.layout()['nE'] == (20 if kind == 'chain' else 16)
+    assert tuple(gp.batch_kernel(k) for k in KINDS) == ROUTES[kind]
 
 
 def test_selftest_covers_the_wide_instances():
@@ -116,9 +142,9 @@ def test_sub_forest_identical_to_cpu_partition(wide):
 
 def test_wide_hybrid_batches_match_oracle():
     """
-    Multi-commutation instance on the wide kernels (2-mode PWA, N = 8: 256 commutations, LPs of
-    32..37 columns x 264..271 rows): instances arrive unsorted, the batch kernels walk the
-    commutation segments.
+    Multi-commutation instance on the LDS-resident wide kernels (2-mode PWA, N = 8: 256
+    commutations, LPs of 32..37 columns x 264..271 rows): instances arrive unsorted, the batch
+    kernels walk the commutation segments.
     """
     from explicit_hybrid_mpc_amd import engine, examples
     from oracle.oracle_cpu import OracleCPU
@@ -126,6 +152,7 @@ def test_wide_hybrid_batches_match_oracle():
     can = mpc.compile()
     assert can.n_delta == 256 and can.n + can.p + 1 > 32
     gp = engine.GpuProblem(can, 0.05, 0.1)
+    assert all(gp.batch_kernel(k) == K4 for k in KINDS)
     orc = OracleCPU(mpc, 0.05, 0.1)
     rng = np.random.default_rng(21)
     half = examples.theta_box(mpc, scale=0.45)
