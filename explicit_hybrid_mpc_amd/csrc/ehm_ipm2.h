@@ -251,6 +251,49 @@ __device__ __forceinline__ double readlane_d(double v, int src) {
     const int hi = __builtin_amdgcn_readlane(__double2hiint(v), src);
     return __hiloint2double(hi, lo);
 }
+// Instances of at most 16 columns: every lane the triangular solves exchange values between sits
+// in DPP row 0, and gfx950's double-precision DPP takes row_newbcast (lane K of each 16-lane row
+// to all lanes of that row) -- the broadcast is the operand of the arithmetic instruction, or one
+// v_mov_b64_dpp, where readlane_d is two lane reads into scalars and a hazard no-op.  Lanes 16..63
+// receive lane K of THEIR row, so there they compute values of their own; lu_solve says why none
+// of them is read.  The source lane must be active: like the reductions above, the broadcasts run
+// with every lane enabled.
+constexpr bool ROW_BCAST = NP <= 16;
+template <int K>
+__device__ __forceinline__ double row_bcast_at(double v) {
+    // zero fill + every row written: `old` is dead and costs no instruction (see dpp_fill0)
+    const long long r = __builtin_amdgcn_update_dpp(0ll, __builtin_bit_cast(long long, v),
+                                                    0x150 + K, 0xf, 0xf, true);
+    return __builtin_bit_cast(double, r);
+}
+// bv <- fma(-l, bv of lane K of the row, bv) as ONE instruction: bv is accumulator and DPP operand.
+// (s_nop 1: a DPP operand written by the vector instruction before it needs two wait states, and
+// the hazard recogniser does not look into an asm block.)
+template <int K>
+__device__ __forceinline__ void row_bcast_fnma_at(double& bv, double l) {
+    asm volatile("s_nop 1\n\t"
+                 "v_fmac_f64_dpp %0, %0, -%1 row_newbcast:%2 row_mask:0xf bank_mask:0xf"
+                 : "+v"(bv)
+                 : "v"(l), "i"(K));
+}
+// k: a constant once the caller's loop is unrolled (the DPP control is an immediate)
+#define EHM2_ROW16_SWITCH(CALL)                                                              \
+    switch (k) {                                                                             \
+        case 0: CALL(0); case 1: CALL(1); case 2: CALL(2); case 3: CALL(3); case 4: CALL(4); \
+        case 5: CALL(5); case 6: CALL(6); case 7: CALL(7); case 8: CALL(8); case 9: CALL(9); \
+        case 10: CALL(10); case 11: CALL(11); case 12: CALL(12); case 13: CALL(13);          \
+        case 14: CALL(14); default: CALL(15);                                                \
+    }
+__device__ __forceinline__ double row_bcast(double v, int k) {
+#define EHM2_CALL(K) return row_bcast_at<K>(v)
+    EHM2_ROW16_SWITCH(EHM2_CALL)
+#undef EHM2_CALL
+}
+__device__ __forceinline__ void row_bcast_fnma(double& bv, double l, int k) {
+#define EHM2_CALL(K) row_bcast_fnma_at<K>(bv, l); return
+    EHM2_ROW16_SWITCH(EHM2_CALL)
+#undef EHM2_CALL
+}
 // Keeps everything derived from x inside the current loop iteration: without it LLVM hoists
 // dozens of loop-invariant per-lane LDS addresses out of the IPM iteration and spills them.
 __device__ __forceinline__ int pin(int x) {
@@ -1378,6 +1421,8 @@ __device__ __forceinline__ void lu_factor(double (&row)[NP], const Wave& W, int 
         if (lane >= kk && lane < NP) U[uoff(k) + lane] = row[k];
         // the pivot itself comes from lane k's register: its reciprocal (v_rcp + two Newton steps)
         // is under way while the column travels through LDS
+        // (a row broadcast instead, for NP <= 16, saves nothing here: the pivot test turns from a
+        // scalar branch into a divergent one, one vector move per lane read saved comes back)
         double piv = readlane_d(row[k], k);
         const double orig = W.db[k];
         wsync();
@@ -1425,28 +1470,53 @@ __device__ __forceinline__ void masked_fnma(double& bv, double a, double s, unsi
                  : [a] "v"(a), [s] "s"(s), [m] "s"(mask)
                  : "scc");
 }
+// The same with s in a vector register pair (a row broadcast): nothing reads a lane afterwards.
+__device__ __forceinline__ void masked_fnma_v(double& bv, double a, double s, unsigned long long mask) {
+    unsigned long long sv;
+    asm volatile("s_and_saveexec_b64 %[sv], %[m]\n\t"
+                 "v_fma_f64 %[bv], -%[a], %[s], %[bv]\n\t"
+                 "s_mov_b64 exec, %[sv]"
+                 : [bv] "+v"(bv), [sv] "=&s"(sv)
+                 : [a] "v"(a), [s] "v"(s), [m] "s"(mask)
+                 : "scc");
+}
 
 // Solve (LU) x = rhs; lane j passes rhs_j and 1/U[j][j], receives x_j; W.t[0..nr) gets x too.
 // Forward: L (the multipliers row[k], k < lane, zeros elsewhere) with the right-hand side in a
 // register row; step k broadcasts y_k by v_readlane and every lane subtracts row[k] y_k.  Backward: U row `lane` from LDS, step k
 // broadcasts x_k and updates the lanes < k.  No LDS writes, no per-step lane compares: round 3
-// parked every y_k / x_k in LDS through lane 0 (9 instructions a step; 3 now).
+// parked every y_k / x_k in LDS through lane 0 (9 instructions a step; 3 now).  ROW_BCAST instances
+// broadcast inside the DPP row instead: one instruction a forward step, three a backward step.
 __device__ __forceinline__ double lu_solve(const double (&row)[NP], const Wave& W, double rinv,
                                            double rhs, int lane) {
     double bv = rhs;
     // (row[k] = 0 for k >= lane, see ipm_solve: a finished component is not touched again)
 #pragma unroll
     for (int k = 0; k < NP - 1; ++k) {
-        const double yk = readlane_d(bv, k);
-        bv = fma(-row[k], yk, bv);
+        if (ROW_BCAST) {
+            row_bcast_fnma(bv, row[k], k);
+        } else {
+            const double yk = readlane_d(bv, k);
+            bv = fma(-row[k], yk, bv);
+        }
     }
     const int jl = (lane < NP) ? lane : (NP - 1);
     const double* urow = W.M + uoff(jl);
 #pragma unroll
     for (int k = NP - 1; k >= 1; --k) {
-        const double xk = readlane_d(bv * rinv, k);
-        masked_fnma(bv, urow[k], xk, (1ull << k) - 1ull);
+        if (ROW_BCAST) {
+            // the broadcast before the mask: lane k is outside it, and a DPP source must be active
+            const double xk = row_bcast(bv * rinv, k);
+            masked_fnma_v(bv, urow[k], xk, (1ull << k) - 1ull);
+        } else {
+            const double xk = readlane_d(bv * rinv, k);
+            masked_fnma(bv, urow[k], xk, (1ull << k) - 1ull);
+        }
     }
+    // (ROW_BCAST: lanes >= 16 solved with their own rows' values.  What leaves here is W.t, written
+    // by the lanes < nr <= NP, and x: solve_full hands the eliminated lanes nr .. nr+nE-1, which may
+    // lie beyond lane 15, xE computed from W.t instead, and masks its sums of x to the lanes < nr;
+    // ipm_solve uses the result in the lanes < n_lp only.)
     const double x = bv * rinv;
     if (lane < W.nr) W.t[lane] = x;
     wsync();
