@@ -56,7 +56,10 @@ EXPORTED = [
     'ehm_compiled_narrow', 'ehm_compiled_export_single', 'ehm_compiled_validate_single',
     'ehm_compiled_import_single', 'ehm_compiled_create_opts', 'ehm_compiled_narrow_opts',
     'ehm_problem_batch_kernel',
+    'ehm_explicit_set_costs', 'ehm_explicit_sample', 'ehm_explicit_audit', 'ehm_explicit_records',
+    'ehm_audit_abi_sizes',
 ]
+EHM_AUDIT_MODES = {'uniform': 0, 'per_leaf': 1}     # EHM_AUDIT_UNIFORM / _PER_LEAF
 EHM_COMPILE_SPINE_ROOTS = 1     # ehm_compiled_create_opts
 EHM_NARROW_FLUSH = 1            # ehm_compiled_narrow_opts
 
@@ -191,6 +194,29 @@ class Counters(ctypes.Structure):
                 ('batch_seconds', ctypes.c_double * 2), ('batch_launches', ctypes.c_int64 * 2)]
 
 
+class AuditOpts(ctypes.Structure):
+    _fields_ = [('mode', ctypes.c_int32), ('k', ctypes.c_int32), ('n', ctypes.c_int64),
+                ('first', ctypes.c_uint64), ('seed', ctypes.c_uint64),
+                ('n_cells', ctypes.c_int64), ('cell_vertices', ctypes.c_void_p),
+                ('cell_node', ctypes.c_void_p), ('cdf', ctypes.c_void_p),
+                ('rtol', ctypes.c_double), ('eps_a', ctypes.c_double),
+                ('eps_r', ctypes.c_double), ('chunk', ctypes.c_int64)]
+
+
+class AuditResult(ctypes.Structure):
+    _fields_ = [('counts', ctypes.c_int64 * 5), ('relocated', ctypes.c_int64),
+                ('histogram', ctypes.c_int64 * 33), ('worst_id', ctypes.c_int64),
+                ('worst_leaf', ctypes.c_int32), ('worst_cell', ctypes.c_int32),
+                ('max_ratio', ctypes.c_double), ('worst_vbar', ctypes.c_double),
+                ('worst_vstar', ctypes.c_double), ('worst_bound', ctypes.c_double),
+                ('worst_x', ctypes.c_double * 8), ('seconds', ctypes.c_double * 3)]
+
+
+class AuditSamples(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ('x', 'cell', 'leaf', 'vbar', 'wmin', 'vstar',
+                                               'delta_idx', 'status')]
+
+
 _lib = None
 
 
@@ -224,6 +250,19 @@ def load(build_if_missing=True):
         raise EhmError(EHM_E_INVALID, 'libehmpc.so and its ctypes binding disagree about the public '
                        'structs: %s against %s (rebuild the library)' % (
                            [int(v) for v in sizes], [ctypes.sizeof(m) for m in mirrors]))
+    mirrors = (AuditOpts, AuditResult, AuditSamples)        # the audit's structs: a list of its own
+    sizes = (i64 * len(mirrors))()
+    lib.ehm_audit_abi_sizes.argtypes = [vp, i32]
+    if lib.ehm_audit_abi_sizes(ctypes.addressof(sizes), len(mirrors)) != len(mirrors) or any(
+            int(sizes[k]) != ctypes.sizeof(m) for k, m in enumerate(mirrors)):
+        raise EhmError(EHM_E_INVALID, 'libehmpc.so and its ctypes binding disagree about the '
+                       "audit's structs: %s against %s (rebuild the library)" % (
+                           [int(v) for v in sizes], [ctypes.sizeof(m) for m in mirrors]))
+    lib.ehm_explicit_set_costs.argtypes = [vp, vp, vp]
+    lib.ehm_explicit_sample.argtypes = [vp, ctypes.POINTER(AuditOpts), vp, vp]
+    lib.ehm_explicit_audit.argtypes = [vp, vp, ctypes.POINTER(AuditOpts),
+                                       ctypes.POINTER(AuditResult), ctypes.POINTER(AuditSamples)]
+    lib.ehm_explicit_records.argtypes = [vp, vp]
     lib.ehm_last_error.restype = ctypes.c_char_p
     lib.ehm_version.restype = ctypes.c_char_p
     lib.ehm_stream.restype = vp

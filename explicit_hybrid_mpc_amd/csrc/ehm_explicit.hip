@@ -29,23 +29,15 @@
 #include <vector>
 
 #include "../../include/ehmpc.h"
+#include "ehm_explicit_dev.h"
 #include "ehm_explicit_view.h"
 #include "ehm_host.h"
 #include "ehm_philox.h"
 #include "ehm_rollout_dev.h"
 
-#define EHM_XP 8   // max parameter dimension (EHM_MAX_P)
 #define EHM_X_LOCATE_MIN 128     // spines at least this long get the root locator
 
 namespace {
-
-struct DevExplicit {
-    const double* rec;       // [n_nodes][rec_stride]: v0 | Minv
-    const int2* child;       // (left, right), -1 for a leaf
-    const double* vinput;    // [n_nodes][(p+1) n_u]
-    int rec_stride, p, n_u, n_roots;
-    long long n_nodes;
-};
 
 // Minv per node from its vertices [(p+1) p]
 __global__ void k_explicit_setup(long long n_nodes, int p, int rec_stride,
@@ -93,91 +85,16 @@ __global__ void k_explicit_setup(long long n_nodes, int p, int rec_stride,
     if (bad) atomicAdd(singular, 1);
 }
 
-// barycentric weights of x in node k; returns containment (lib/mpc_library.py:714-735)
-__device__ __forceinline__ bool weights(const DevExplicit& E, long long k, const double* x,
-                                        double* alpha, double& alpha0) {
-    const double* r = E.rec + (size_t)k * E.rec_stride;
-    const int p = E.p;
-    const double eps = 2.220446049250313e-16;
-    double d[EHM_XP];
-    for (int c = 0; c < p; ++c) d[c] = x[c] - r[c];
-    double s = 0.0;
-    bool in = true;
-    for (int q = 0; q < p; ++q) {
-        double a = 0.0;
-        for (int c = 0; c < p; ++c) a += r[p + q * p + c] * d[c];     // Minv.dot(x - c)
-        alpha[q] = a;
-        s += a;
-        in = in && (a >= -eps) && (a <= 1.0 + eps);
-    }
-    alpha0 = 1.0 - s;
-    return in && (alpha0 >= -eps) && (alpha0 <= 1.0 + eps);
-}
-
-// Containment only, the coordinates tested one after the other and the test left at the first
-// weight outside [-eps, 1+eps]: the SAME sums in the same order as `weights`, so the verdict is
-// bit-identical -- but a root that does not hold x is usually dismissed after one or two rows of
-// Minv instead of p (the spine walk reads 3p instead of p + p^2 doubles per dismissed root).
-__device__ __forceinline__ bool contains(const DevExplicit& E, long long k, const double* x) {
-    const double* r = E.rec + (size_t)k * E.rec_stride;
-    const int p = E.p;
-    const double eps = 2.220446049250313e-16;
-    double d[EHM_XP];
-    for (int c = 0; c < p; ++c) d[c] = x[c] - r[c];
-    double s = 0.0;
-    for (int q = 0; q < p; ++q) {
-        double a = 0.0;
-        for (int c = 0; c < p; ++c) a += r[p + q * p + c] * d[c];
-        if (!((a >= -eps) && (a <= 1.0 + eps))) return false;
-        s += a;
-    }
-    const double a0 = 1.0 - s;
-    return (a0 >= -eps) && (a0 <= 1.0 + eps);
-}
-
-// Root locator for long spines (tools.delaunay of a p = 8 box: 34 871 roots).  The reference walks
-// the right spine and takes the FIRST root, in spine order, that contains x
-// (lib/mpc_library.py:737-767): 17 000 containment tests per state on that spine, and one
-// wavefront per query testing 64 roots at a time costs the same lane-steps (measured: 0.85 M
-// against 0.95 M states/s).  The roots are a triangulation, so a state in the INTERIOR of a root
-// (every barycentric weight > EHM_X_STRICT) is in no other root and the first one in spine order
-// is that one -- found by a visibility walk over the face adjacency of the roots (built at
-// set-up): from the current root cross the face opposite its most negative weight.  A state
-// within EHM_X_STRICT of a face, a walk that leaves the hull or does not end in EHM_X_STEPS steps
-// gets root = -1 and the reference's serial walk (k_explicit_eval): same leaf in every case.
-#define EHM_X_STRICT 1e-9
-#define EHM_X_STEPS 96
+// the root locator of long spines (explicit_locate_root, ehm_explicit_dev.h), one thread per state
 __global__ void k_explicit_locate(DevExplicit E, long long n, const double* __restrict__ X,
                                   const int32_t* __restrict__ nbr, int32_t* __restrict__ root) {
 #pragma clang fp contract(off)
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n) return;
     const int p = E.p;
-    double x[EHM_XP], alpha[EHM_XP], a0;
+    double x[EHM_XP];
     for (int c = 0; c < p; ++c) x[c] = X[q * p + c];
-    int k = (int)(q % E.n_roots);           // any start: the walk is short from everywhere
-    int found = -1, steps = 0;
-    for (int step = 0; step < EHM_X_STEPS; ++step) {
-        ++steps;
-        (void)weights(E, k, x, alpha, a0);
-        double lo = a0;
-        int at = 0;
-        for (int i = 0; i < p; ++i)
-            if (alpha[i] < lo) {
-                lo = alpha[i];
-                at = i + 1;
-            }
-        if (lo > EHM_X_STRICT) {            // strictly inside: the only root that holds x
-            found = k;
-            break;
-        }
-        if (lo >= -EHM_X_STRICT) break;     // on a face: the serial walk decides
-        const int k2 = nbr[(size_t)k * (p + 1) + at];
-        if (k2 < 0) break;                  // left the hull (x outside the set, or rounding)
-        k = k2;
-    }
-    // (the containment tests made ride in the upper bits: `visited` reports the device's work)
-    root[q] = (found < 0) ? -1 : (found | (steps << 20));
+    root[q] = explicit_locate_root(E, x, q, nbr);
 }
 
 __global__ void k_explicit_eval(DevExplicit E, long long n, const double* __restrict__ X,
@@ -190,29 +107,9 @@ __global__ void k_explicit_eval(DevExplicit E, long long n, const double* __rest
     const int p = E.p, n_u = E.n_u;
     double x[EHM_XP], alpha[EHM_XP], a0;
     for (int c = 0; c < p; ++c) x[c] = X[q * p + c];
-    // spine: first root that contains x, the last one without a test (found by k_explicit_locate
-    // where the spine is long; `visited` counts the tests the reference's walk makes)
-    long long k = E.n_roots - 1;
+    // spine (the root k_explicit_locate found where the spine is long), then the partition subtree
     int visited = 0;
-    if (root && root[q] >= 0) {
-        k = root[q] & 0xfffff;
-        visited = root[q] >> 20;
-    } else {
-        for (int r = 0; r + 1 < E.n_roots; ++r) {
-            ++visited;
-            if (contains(E, r, x)) {
-                k = r;
-                break;
-            }
-        }
-    }
-    // partition subtree: left iff inside the left child
-    for (;;) {
-        const int2 ch = E.child[k];
-        if (ch.x < 0) break;
-        ++visited;
-        k = contains(E, ch.x, x) ? ch.x : ch.y;
-    }
+    const long long k = explicit_walk(E, x, root ? root[q] : -1, visited);
     (void)weights(E, k, x, alpha, a0);
     const double* vi = E.vinput + (size_t)k * (p + 1) * n_u;
     for (int c = 0; c < n_u; ++c) {
@@ -419,6 +316,7 @@ struct ehm_explicit {
     DevBuf rec, child, vinput;
     DevBuf x, u, leaf, depth, root;     // ehm_explicit_eval_batch, cap queries
     DevBuf nbr;         // [n_roots][p+1] root across the face opposite vertex i (-1: hull)
+    DevBuf vcost, nflags;   // ehm_explicit_set_costs: [n_nodes][p+1] doubles, [n_nodes] bytes
     RolloutAttach ro;   // plant, node modes and model of the rollouts (ehm_explicit_set_*)
     size_t cap = 0;
     Stream stream;
@@ -428,7 +326,19 @@ struct ehm_explicit {
 void ehm_explicit_get_view(const ehm_explicit* E, ehm_explicit_view* out) {
     *out = ehm_explicit_view{E->device, E->d.rec, E->d.child, E->d.vinput,
                              E->nbr.as<const int32_t>(), E->d.rec_stride, E->d.p, E->d.n_u,
-                             E->d.n_roots, E->d.n_nodes};
+                             E->d.n_roots, E->d.n_nodes,
+                             E->vcost.as<const double>(), E->nflags.as<const uint8_t>(),
+                             E->stream};
+}
+
+int ehm_explicit_fail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    x_err = buf;
+    return code;
 }
 
 // face adjacency of the roots (ehm_explicit_view.h): vertices by value, faces by their sorted
@@ -577,6 +487,27 @@ int ehm_explicit_eval_batch(ehm_explicit* E, int64_t n, const double* x, double*
                              hipMemcpyDeviceToHost, E->stream));
     Y_TRY(hipStreamSynchronize(E->stream));
     ev.seconds(kernel_seconds);
+    return EHM_OK;
+}
+
+int ehm_explicit_set_costs(ehm_explicit* E, const double* vcost, const uint8_t* flags) {
+    if (!E || !vcost || !flags) return xfail(EHM_E_INVALID, "set_costs: a required array is NULL");
+    Y_TRY(hipSetDevice(E->device));
+    const size_t n = (size_t)E->d.n_nodes;
+    DevBuf c, f;        // the handle keeps its earlier pair if an upload fails
+    Y_TRY(c.upload(vcost, n * (size_t)(E->d.p + 1) * sizeof(double)));
+    Y_TRY(f.upload(flags, n * sizeof(uint8_t)));
+    E->vcost = std::move(c);
+    E->nflags = std::move(f);
+    return EHM_OK;
+}
+
+int ehm_explicit_records(ehm_explicit* E, double* rec) {
+    if (!E || !rec) return xfail(EHM_E_INVALID, "records: bad argument");
+    Y_TRY(hipSetDevice(E->device));
+    const size_t w = (size_t)(E->d.p + E->d.p * E->d.p) * sizeof(double);
+    Y_TRY(hipMemcpy2D(rec, w, E->rec.ptr, (size_t)E->d.rec_stride * sizeof(double), w,
+                      (size_t)E->d.n_nodes, hipMemcpyDeviceToHost));
     return EHM_OK;
 }
 

@@ -1,5 +1,6 @@
-// What the compile step of ehm_compiled.hip reads of an ehm_explicit handle (ehm_explicit.hip owns
-// the struct): device pointers that stay the handle's, valid while it lives.  Not exported.
+// What the compile step of ehm_compiled.hip and the audit of ehm_audit.hip read of an ehm_explicit
+// handle (ehm_explicit.hip owns the struct): device pointers that stay the handle's, valid while it
+// lives.  Not exported.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -17,9 +18,17 @@ struct ehm_explicit_view {
     const int32_t* nbr;         // [n_roots][p+1] face adjacency of the roots, or nullptr
     int rec_stride, p, n_u, n_roots;
     long long n_nodes;
+    // what the audit (ehm_audit.hip) reads besides: the costs and flags of ehm_explicit_set_costs
+    // (nullptr until set) and the handle's stream
+    const double* vcost;        // [n_nodes][p+1]
+    const uint8_t* nflags;      // [n_nodes]
+    hipStream_t stream;
 };
 
 void ehm_explicit_get_view(const ehm_explicit* E, ehm_explicit_view* out);
+// sets the message of ehm_explicit_last_error and returns `code` (the error channel of every entry
+// point that takes an ehm_explicit handle)
+int ehm_explicit_fail(int code, const char* fmt, ...);
 
 // Face adjacency of n_roots simplices (host): nbr [n_roots][p+1], the root across the face opposite
 // vertex i, -1 on the hull.  Root r has the vertices [p+1][p] of node ids[r] (ids nullptr: node r).

@@ -34,13 +34,16 @@ def node_commutation(nd):
     return None if c is None else np.asarray(c, dtype=np.float64)
 
 
-def flatten_tree(root, commutations=False):
+def flatten_tree(root, commutations=False, costs=False):
     """
     Nested ``tree.Tree`` (reference layout) -> flat arrays with node 0 = root, children after
     their parents: (vertices, vertex_inputs, left, right, nodes).  Data-less spine nodes and
     nodes without inputs get placeholders; they are never tested (only left children and final
     leaves are, lib/mpc_library.py:703-711) or never returned.  With ``commutations`` also the
-    list of every node's commutation vector (None where the node has none).
+    list of every node's commutation vector (None where the node has none).  With ``costs`` also
+    a dict of what the audit reads: ``vertex_costs`` [K, p+1] (NaN where a node has none),
+    ``flags`` uint8 [K] (bit 0: is_epsilon_suboptimal, as FlatTree.flags) and ``simplex`` bool [K]
+    (the node's data holds a simplex, i.e. it is no spine node).
     """
     first, stack = None, [root]
     while stack:                        # any node with vertex inputs tells the shapes
@@ -78,8 +81,77 @@ def flatten_tree(root, commutations=False):
             vinput[k] = np.asarray(d.vertex_inputs, dtype=np.float64)
     out = (vertices, vinput, np.array(left, dtype=np.int32), np.array(right, dtype=np.int32), nodes)
     if commutations:
-        return out + ([node_commutation(nd) for nd in nodes],)
+        out = out + ([node_commutation(nd) for nd in nodes],)
+    if costs:
+        vcost = np.full((K, p + 1), np.nan)
+        flags = np.zeros(K, dtype=np.uint8)
+        simplex = np.zeros(K, dtype=bool)
+        for k, nd in enumerate(nodes):
+            d = nd.data
+            if d is None:
+                continue
+            simplex[k] = np.asarray(d.vertices).shape == (p + 1, p)
+            if hasattr(d, 'vertex_costs'):
+                vcost[k] = np.asarray(d.vertex_costs, dtype=np.float64)
+            flags[k] = 1 if getattr(d, 'is_epsilon_suboptimal', False) else 0
+        out = out + (dict(vertex_costs=vcost, flags=flags, simplex=simplex),)
     return out
+
+
+def forest_order(left, right, spine):
+    """
+    Node ids of a flattened nested tree in the numbering of the engine's flat export: the roots
+    (the first nodes below the spine, in spine order), then breadth first over all of them, the
+    left child before the right one.  ``spine`` [K] marks the nodes above the roots.
+    """
+    roots, stack = [], [0]
+    while stack:
+        k = stack.pop()
+        if spine[k] and left[k] >= 0:
+            stack += [int(right[k]), int(left[k])]
+        else:
+            roots.append(k)
+    order, head = roots, 0
+    while head < len(order):
+        k = order[head]
+        head += 1
+        if left[k] >= 0:
+            order += [int(left[k]), int(right[k])]
+    return np.array(order, dtype=np.int64)
+
+
+STATUS_NAMES = ('within', 'violation', 'negative', 'open', 'infeasible')    # by status value
+
+
+class AuditResult:
+    """
+    What ``ExplicitMPC.audit`` found (a sampled check, not a certificate):
+    ``counts`` samples by status name (STATUS_NAMES), ``relocated`` samples located in a leaf other
+    than the cell they were drawn in, ``max_ratio`` the largest (Vbar - V*) / bound over statuses
+    0-2 (-inf if there is none), ``worst`` that sample (id, x, cell, leaf, vbar, vstar, bound; None
+    if there is none), ``histogram`` int64 [33] of the ratio (32 bins over [0, 1], one above),
+    ``open_volume_fraction`` the volume of the leaves that are not closed over the volume of all
+    leaves (exact, from flags and volumes, not sampled), ``seconds`` (sampling kernel, locate and
+    reduce kernels, P_theta batches), ``n``, and with ``return_samples`` the arrays ``x, cell,
+    leaf, vbar, wmin, vstar, delta_idx, status``.  ``passed``: no violation, no negative, no
+    infeasible, and no open leaf unless ``allow_open``.
+    """
+
+    def __init__(self, **kw):
+        self.x = self.cell = self.leaf = self.vbar = self.wmin = self.vstar = None
+        self.delta_idx = self.status = None
+        self.__dict__.update(kw)
+
+    @property
+    def passed(self):
+        c = self.counts
+        bad = c['violation'] + c['negative'] + c['infeasible']
+        return bad == 0 and (self.allow_open or c['open'] == 0)
+
+    def __repr__(self):
+        return 'AuditResult(n=%d, passed=%s, counts=%r, max_ratio=%.6g, relocated=%d, ' \
+            'open_volume_fraction=%.6g)' % (self.n, self.passed, self.counts, self.max_ratio,
+                                            self.relocated, self.open_volume_fraction)
 
 
 class ImplicitMPC:
@@ -145,6 +217,9 @@ class ExplicitMPC:
         if hasattr(mpc, 'specs'):
             self.specs = mpc.specs
         self.tree = tree
+        self._oracle = oracle       # audit: P_theta of the oracle the law was built with
+        self._cells = None          # audit, sample: the leaves as cells (built on first use)
+        self._costs_set = False
         self.device = int(device)
         self._lib = _capi.load()
         self._handle = ctypes.c_void_p()
@@ -165,6 +240,7 @@ class ExplicitMPC:
             n_roots = 1
         self.n_nodes, self.p, self.n_u = vertices.shape[0], vertices.shape[2], vinput.shape[2]
         self.eps = np.finfo(np.float64).eps
+        self._costs_set = False     # a new handle holds no costs yet
         _check(self._lib.ehm_explicit_create(self.device, self.n_nodes, n_roots, self.p, self.n_u,
                                              ptr(left), ptr(right), ptr(vertices), ptr(vinput),
                                              ctypes.byref(self._handle)))
@@ -224,6 +300,155 @@ class ExplicitMPC:
         if return_info:
             return u, leaf, visited, secs.value
         return u
+
+    # -- uniform sampling and the audit of the epsilon-suboptimality contract --
+    def cells(self):
+        """
+        The leaves as the sampler's cells: dict of ``node`` int32 [n_cells] (their node ids as
+        ``evaluate`` reports leaves), ``vertices`` [n_cells, p+1, p], ``volume`` [n_cells]
+        (``ehm_volume_batch``), ``cdf`` (its running sum), ``closed`` bool [n_cells], and the
+        per-node ``vertex_costs`` [n_nodes, p+1] and ``flags`` uint8 [n_nodes].  A flat forest's
+        cells are its leaves in ascending node id; a nested tree's are its leaves that hold a
+        simplex, in the same order (``forest_order``), so both forms of one partition draw the
+        same points.
+        """
+        if self._cells is not None:
+            return self._cells
+        from . import engine
+        if isinstance(self.tree, FlatTree):
+            t = self.tree
+            vertices, vcost = f64(t.vertices), f64(t.vertex_costs)
+            flags = np.ascontiguousarray(t.flags, dtype=np.uint8)
+            node = np.nonzero(np.asarray(t.left) < 0)[0]
+        else:
+            vertices, _, left, right, _, extra = flatten_tree(self.tree, costs=True)
+            vcost, flags = extra['vertex_costs'], extra['flags']
+            order = forest_order(left, right, ~extra['simplex'])
+            node = order[(left[order] < 0) & extra['simplex'][order]]
+        node = np.ascontiguousarray(node, dtype=np.int32)
+        if node.size == 0:
+            raise ValueError('the tree has no leaf to sample')
+        cv = f64(vertices[node])
+        vol = engine.volume_batch(cv, device=self.device)
+        self._cells = dict(node=node, vertices=cv, volume=vol, cdf=f64(np.cumsum(vol)),
+                           closed=(flags[node] & 1).astype(bool), vertex_costs=f64(vcost),
+                           flags=flags)
+        return self._cells
+
+    def _audit_opts(self, n, seed, mode, per_leaf, first, chunk):
+        """(AuditOpts, n) for the sampler's arguments; the cells' arrays stay alive in cells()."""
+        if not getattr(self, '_handle', None):
+            raise ValueError('the law is closed')
+        if mode is None:
+            mode = 'uniform' if per_leaf is None else 'per_leaf'
+        if mode not in _capi.EHM_AUDIT_MODES:
+            raise ValueError("mode must be 'uniform' or 'per_leaf', not %r" % (mode,))
+        first = int(first)
+        if first < 0:
+            raise ValueError('first must be >= 0')
+        cells = self.cells()
+        n_cells = cells['node'].size
+        if mode == 'per_leaf':
+            if per_leaf is None or int(per_leaf) < 1:
+                raise ValueError("mode 'per_leaf' needs per_leaf >= 1")
+            total = n_cells * int(per_leaf)
+            if n is None:
+                n = total - first
+            if n < 0 or first + n > total:
+                raise ValueError('per-leaf ids end at leaves x per_leaf = %d' % total)
+        else:
+            if per_leaf is not None:
+                raise ValueError("per_leaf goes with mode 'per_leaf'")
+            if n is None or int(n) < 0:
+                raise ValueError("mode 'uniform' needs n >= 0")
+        opts = _capi.AuditOpts(mode=_capi.EHM_AUDIT_MODES[mode], k=int(per_leaf or 0), n=int(n),
+                               first=first, seed=int(seed) & ((1 << 64) - 1), n_cells=n_cells,
+                               cell_vertices=ptr(cells['vertices']), cell_node=ptr(cells['node']),
+                               cdf=ptr(cells['cdf']), chunk=int(chunk))
+        return opts, int(n)
+
+    def sample(self, n=None, seed=0, mode=None, per_leaf=None, first=0, chunk=0):
+        """
+        Points of the partitioned set drawn on the device (k_audit_sample): X [n, p] and the cell
+        [n] (index into ``cells()``) each was drawn in.  ``mode='uniform'``: uniform in the set --
+        a cell chosen by volume, a uniform point in it; ``mode='per_leaf'`` with ``per_leaf=k``:
+        exactly k uniform points in every leaf, sample s in cell s // k (n defaults to all of them).
+        Sample ids are global, ``first`` .. ``first + n - 1``: a point depends on (seed, id) only,
+        not on n, ``chunk`` (samples per launch) or how a range of ids is split over calls.
+        """
+        opts, n = self._audit_opts(n, seed, mode, per_leaf, first, chunk)
+        X = np.empty((n, self.p))
+        cell = np.empty(n, dtype=np.int32)
+        _check(self._lib.ehm_explicit_sample(self._handle, ctypes.byref(opts), ptr(X), ptr(cell)))
+        return X, cell
+
+    def records(self):
+        """[n_nodes, p + p p]: [v_0 | inv([v_1 - v_0 .. v_p - v_0])] of every node as the device
+        holds them (what a host mirror of the weights needs)."""
+        rec = np.empty((self.n_nodes, self.p + self.p * self.p))
+        _check(self._lib.ehm_explicit_records(self._handle, ptr(rec)))
+        return rec
+
+    def audit(self, n=None, seed=0, mode=None, per_leaf=None, rtol=1e-7, return_samples=False,
+              oracle=None, allow_open=False, first=0, chunk=0):
+        """
+        Samples the partitioned set as ``sample`` does and checks the law's contract at every
+        point:  0 <= Vbar(x) - V*(x) <= max(eps_a, eps_r V*(x)),  Vbar the interpolated vertex
+        costs of the leaf the deployed walk ends in, V* the optimal cost ``P_theta(x)`` of
+        ``oracle`` (default: the one the law was built with), each side with the slack
+        rtol (1 + |V*|).  Give ``n`` (uniform) or ``per_leaf``, not both.  ``allow_open``: leaves
+        left open by a depth limit do not fail ``passed``.  ``first``: id of the first sample (a
+        shard audits its range of ids); ``chunk``: samples per pass (the length of the P_theta
+        batches; no result depends on it).  ``return_samples``: the per-sample arrays too.
+        Raises ValueError without an oracle and EhmError for an oracle without a batched P_theta
+        (branch and bound over mode prefixes).  Returns an ``AuditResult``.  A sampled check, not
+        a certificate.
+        """
+        oracle = self._oracle if oracle is None else oracle
+        if oracle is None:
+            raise ValueError('audit needs an oracle: the law was built without one')
+        if n is not None and per_leaf is not None:
+            raise ValueError('per_leaf fixes the number of samples (leaves x per_leaf): give n or '
+                             'per_leaf, not both')
+        opts, n = self._audit_opts(n, seed, mode, per_leaf, first, chunk)
+        gp = getattr(oracle, 'gpu', None)
+        if gp is None:
+            raise _capi.EhmError(_capi.EHM_E_INVALID, 'audit needs the batched P_theta of an '
+                                 'enumerating oracle; this one (branch and bound over mode '
+                                 'prefixes) has none')
+        if gp.can.p != self.p:
+            raise ValueError('the oracle has parameter dimension %d, the law %d' % (gp.can.p,
+                                                                                   self.p))
+        cells = self.cells()
+        if not self._costs_set:
+            _check(self._lib.ehm_explicit_set_costs(self._handle, ptr(cells['vertex_costs']),
+                                                    ptr(cells['flags'])))
+            self._costs_set = True
+        opts.rtol, opts.eps_a, opts.eps_r = float(rtol), float(oracle.eps_a), float(oracle.eps_r)
+        res = _capi.AuditResult()
+        arrays = {}
+        smp = None
+        if return_samples:
+            arrays = dict(x=np.empty((n, self.p)), cell=np.empty(n, np.int32),
+                          leaf=np.empty(n, np.int32), vbar=np.empty(n), wmin=np.empty(n),
+                          vstar=np.empty(n), delta_idx=np.empty(n, np.int32),
+                          status=np.empty(n, np.int32))
+            smp = ctypes.byref(_capi.AuditSamples(**{k: ptr(a) for k, a in arrays.items()}))
+        _check(self._lib.ehm_explicit_audit(self._handle, gp._handle, ctypes.byref(opts),
+                                            ctypes.byref(res), smp))
+        worst = None
+        if res.worst_id >= 0:
+            worst = dict(id=int(res.worst_id), x=np.array(res.worst_x[:self.p]),
+                         cell=int(res.worst_cell), leaf=int(res.worst_leaf),
+                         vbar=res.worst_vbar, vstar=res.worst_vstar, bound=res.worst_bound)
+        vol = cells['volume']
+        return AuditResult(n=n, counts={name: int(res.counts[k])
+                                        for k, name in enumerate(STATUS_NAMES)},
+                           relocated=int(res.relocated), max_ratio=float(res.max_ratio),
+                           worst=worst, histogram=np.array(res.histogram[:], dtype=np.int64),
+                           open_volume_fraction=float(vol[~cells['closed']].sum() / vol.sum()),
+                           allow_open=bool(allow_open), rtol=float(rtol),
+                           seconds=tuple(res.seconds[:]), **arrays)
 
     def node_modes(self, plant):
         """int32 [n_nodes]: step-0 mode of every node's commutation (-1: none); all 0 for a

@@ -668,6 +668,98 @@ int ehm_explicit_rollout_noisy(ehm_explicit* ex, int64_t n, int32_t T, const dou
  * and out [n][4], key [2] (numpy: np.random.Philox(counter=c - 1, key=key).random_raw(4)). */
 int ehm_philox_batch(int64_t n, const uint64_t* counters, const uint64_t* key, uint64_t* out);
 
+/* ---- sampled audit of a law's epsilon-suboptimality (csrc/ehm_audit.hip) --------
+ *
+ * What the reference's PostProcessor asks of invariant_set.randomPoint after a partition: points
+ * uniform in the partitioned set, the law as deployed priced at each of them against the implicit
+ * law's optimal cost, and the contract  0 <= Vbar(x) - V*(x) <= max(eps_a, eps_r V*(x))  judged
+ * per point.  A sampled check, not a certificate.
+ *
+ * The cells are the leaves the caller lists, in the order it lists them (for a flat export: the
+ * leaves in ascending node id): cell_vertices [n_cells][p+1][p] (the handle keeps only their
+ * inverses), cell_node [n_cells] their node ids.  Sample s -- a GLOBAL id, first + q for the q-th
+ * sample of a call, so that neither the chunk size nor a split of the ids over calls or devices
+ * changes a point -- takes its random words from Philox4x64-10 under the key (seed, 1) (the noise
+ * model owns (seed, 0)): word k is word k % 4 of the block with counter (s, k / 4, 0, 0).  Word 0
+ * chooses the cell, words 1..p become the uniforms g = (r >> 11) * 2^-53 in [0, 1).
+ *   mode EHM_AUDIT_UNIFORM:  cdf [n_cells] = running sum of the cells' volumes; with
+ *        t = u * cdf[n_cells - 1], u the uniform of word 0, the cell is the first i with
+ *        cdf[i] > t (binary search), at most the last cell;
+ *   mode EHM_AUDIT_PER_LEAF: the cell is s / k; every cell gets exactly k samples
+ *        (first + n <= n_cells * k).
+ * The point: the p uniforms sorted ascending (insertion sort) g_1 <= .. <= g_p, their spacings
+ * w_0 = g_1, w_i = g_(i+1) - g_i, w_p = 1 - g_p as barycentric weights,
+ * x_c = w_0 v_0c, then + w_i v_ic for i = 1..p in that order; every product and sum rounded once. */
+#define EHM_AUDIT_UNIFORM  0
+#define EHM_AUDIT_PER_LEAF 1
+typedef struct ehm_audit_opts {
+    int32_t mode;           /* EHM_AUDIT_UNIFORM | EHM_AUDIT_PER_LEAF                          */
+    int32_t k;              /* samples per cell (per-leaf mode)                                */
+    int64_t n;              /* samples of this call                                            */
+    uint64_t first;         /* global id of its first sample                                   */
+    uint64_t seed;
+    int64_t n_cells;
+    const double*  cell_vertices;   /* [n_cells][p+1][p]                                       */
+    const int32_t* cell_node;       /* [n_cells] (the sampler alone does not read it)          */
+    const double*  cdf;             /* [n_cells], uniform mode                                 */
+    double rtol;            /* slack = rtol (1 + |V*|) on both sides of the contract           */
+    double eps_a, eps_r;    /* the tolerances the law was built with                           */
+    int64_t chunk;          /* samples per pass (0: 65536); the LP batches are this long       */
+} ehm_audit_opts;
+/* Statuses, the first that applies: 4 infeasible (no commutation feasible at x), 3 open (the
+ * located leaf is not closed), 2 negative (not gap >= -slack), 1 violation (gap > bound + slack),
+ * 0 within contract; gap = Vbar - V*, bound = max(eps_a, eps_r V*). */
+typedef struct ehm_audit_result {
+    int64_t counts[5];      /* samples by status                                               */
+    int64_t relocated;      /* samples located in a leaf other than their cell                 */
+    int64_t histogram[33];  /* of gap / bound over statuses 0-2: 32 bins over [0, 1] (negative
+                               ratios in bin 0, ratio 1 in bin 31), bin 32 = above 1           */
+    int64_t worst_id;       /* the sample with the largest gap / bound among statuses 0-2, the
+                               smallest id on ties; -1: no such sample                         */
+    int32_t worst_leaf;
+    int32_t worst_cell;
+    double  max_ratio;      /* its gap / bound (-inf: no such sample)                          */
+    double  worst_vbar, worst_vstar, worst_bound;
+    double  worst_x[8];
+    double  seconds[3];     /* [0] sampling kernel, [1] locate + cost + reduce kernels (device
+                               time), [2] the P_theta batches (host wall time)                 */
+} ehm_audit_result;
+/* Per-sample outputs of an audit, each [n] ([n][p] for x) or NULL. */
+typedef struct ehm_audit_samples {
+    double*  x;
+    int32_t* cell;
+    int32_t* leaf;          /* the located leaf                                                */
+    double*  vbar;
+    double*  wmin;          /* smallest barycentric weight of x in the located leaf            */
+    double*  vstar;
+    int32_t* delta_idx;
+    int32_t* status;
+} ehm_audit_samples;
+/* The per-node data the audit prices the law with: vcost [n_nodes][p+1] and flags [n_nodes] (bit 0:
+ * the node is closed) of the tree the handle was created from.  Replaces an earlier pair. */
+int ehm_explicit_set_costs(ehm_explicit* ex, const double* vcost, const uint8_t* flags);
+/* The sampler alone: x [n][p], cell [n] (either may be NULL).  Reads mode, k, n, first, seed, the
+ * cells and chunk of opts. */
+int ehm_explicit_sample(ehm_explicit* ex, const ehm_audit_opts* opts, double* x, int32_t* cell);
+/* The audit: samples as ehm_explicit_sample draws them; each located with the walk of
+ * ehm_explicit_eval_batch (root locator included), weights alpha in the located leaf, priced as
+ * Vbar = alpha_0 c_0, then + c_(i+1) alpha_(i+1) in order (one rounding per operation, the order
+ * of the input interpolation); V* and delta_idx from ehm_solve_pt_batch on `prob` (the points of
+ * a chunk make one round trip through the host; prob must have the law's parameter dimension),
+ * bit for bit what that entry point returns for the same points; statuses, counts and histogram
+ * by integer atomics, the worst sample by a reduction with ties to the smaller id: no result
+ * depends on the launch shape or the chunk size.  samples may be NULL.  Needs
+ * ehm_explicit_set_costs.  Errors of the LP batches are reported through
+ * ehm_explicit_last_error like the others. */
+int ehm_explicit_audit(ehm_explicit* ex, ehm_problem* prob, const ehm_audit_opts* opts,
+                       ehm_audit_result* result, const ehm_audit_samples* samples);
+/* [v_0 (p) | inv([v_1 - v_0 .. v_p - v_0]) (p x p, row-major)] of every node as the handle holds
+ * them: rec [n_nodes][p + p p].  What a host mirror needs to repeat the device's weights. */
+int ehm_explicit_records(ehm_explicit* ex, double* rec);
+/* ehm_abi_sizes for the structs of this section, in this order: ehm_audit_opts, ehm_audit_result,
+ * ehm_audit_samples.  A list of its own: ehm_abi_sizes keeps returning the six it always has. */
+int ehm_audit_abi_sizes(int64_t* sizes, int32_t n);
+
 /* ---- closed-loop simulation under the COMPILED law (csrc/ehm_compiled.hip) -------
  *
  * The entry points of the explicit law's rollout, argument for argument, on a compiled law -- also
