@@ -58,6 +58,7 @@ EXPORTED = [
     'ehm_problem_batch_kernel',
     'ehm_explicit_set_costs', 'ehm_explicit_sample', 'ehm_explicit_audit', 'ehm_explicit_records',
     'ehm_audit_abi_sizes',
+    'ehm_compiled_audit', 'ehm_applied_last_error', 'ehm_applied_abi_sizes',
 ]
 EHM_AUDIT_MODES = {'uniform': 0, 'per_leaf': 1}     # EHM_AUDIT_UNIFORM / _PER_LEAF
 EHM_COMPILE_SPINE_ROOTS = 1     # ehm_compiled_create_opts
@@ -217,6 +218,34 @@ class AuditSamples(ctypes.Structure):
                                                'delta_idx', 'status')]
 
 
+class AppliedOpts(ctypes.Structure):
+    _fields_ = [('n', ctypes.c_int64), ('first', ctypes.c_uint64), ('seed', ctypes.c_uint64),
+                ('chunk', ctypes.c_int64), ('n_cells', ctypes.c_int64),
+                ('cell_vertices', ctypes.c_void_p), ('cdf', ctypes.c_void_p),
+                ('x', ctypes.c_void_p), ('u', ctypes.c_void_p), ('source', ctypes.c_void_p),
+                ('relaxed', ctypes.c_void_p), ('cost_u', ctypes.c_void_p),
+                ('p', ctypes.c_int32), ('n_u', ctypes.c_int32),
+                ('device', ctypes.c_int32), ('reserved', ctypes.c_int32),
+                ('rtol', ctypes.c_double), ('eps_a', ctypes.c_double),
+                ('eps_r', ctypes.c_double)]
+
+
+class AppliedResult(ctypes.Structure):
+    _fields_ = [('counts', ctypes.c_int64 * 6), ('histogram', ctypes.c_int64 * 33),
+                ('worst_id', ctypes.c_int64), ('worst_leaf', ctypes.c_int32),
+                ('reserved', ctypes.c_int32), ('relaxed', ctypes.c_int64),
+                ('max_ratio', ctypes.c_double), ('worst_vu', ctypes.c_double),
+                ('worst_vstar', ctypes.c_double),
+                ('worst_bound', ctypes.c_double), ('worst_x', ctypes.c_double * 8),
+                ('worst_u', ctypes.c_double * 8), ('seconds', ctypes.c_double * 5)]
+
+
+class AppliedSamples(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ('x', 'root', 'leaf', 'u', 'vu', 'vstar',
+                                               'delta_idx', 'delta_idx_applied', 'status',
+                                               'relaxed')]
+
+
 _lib = None
 
 
@@ -258,6 +287,18 @@ def load(build_if_missing=True):
         raise EhmError(EHM_E_INVALID, 'libehmpc.so and its ctypes binding disagree about the '
                        "audit's structs: %s against %s (rebuild the library)" % (
                            [int(v) for v in sizes], [ctypes.sizeof(m) for m in mirrors]))
+    mirrors = (AppliedOpts, AppliedResult, AppliedSamples)  # ... and the applied-input audit's
+    sizes = (i64 * len(mirrors))()
+    lib.ehm_applied_abi_sizes.argtypes = [vp, i32]
+    if lib.ehm_applied_abi_sizes(ctypes.addressof(sizes), len(mirrors)) != len(mirrors) or any(
+            int(sizes[k]) != ctypes.sizeof(m) for k, m in enumerate(mirrors)):
+        raise EhmError(EHM_E_INVALID, 'libehmpc.so and its ctypes binding disagree about the '
+                       "applied-input audit's structs: %s against %s (rebuild the library)" % (
+                           [int(v) for v in sizes], [ctypes.sizeof(m) for m in mirrors]))
+    lib.ehm_compiled_audit.argtypes = [vp, vp, vp, ctypes.POINTER(AppliedOpts),
+                                       ctypes.POINTER(AppliedResult),
+                                       ctypes.POINTER(AppliedSamples)]
+    lib.ehm_applied_last_error.restype = ctypes.c_char_p
     lib.ehm_explicit_set_costs.argtypes = [vp, vp, vp]
     lib.ehm_explicit_sample.argtypes = [vp, ctypes.POINTER(AuditOpts), vp, vp]
     lib.ehm_explicit_audit.argtypes = [vp, vp, ctypes.POINTER(AuditOpts),
@@ -356,7 +397,7 @@ def load(build_if_missing=True):
         fn = getattr(lib, name)
         if name not in ('ehm_last_error', 'ehm_version', 'ehm_stream',
                         'ehm_explicit_last_error', 'ehm_implicit_last_error',
-                        'ehm_compiled_last_error'):
+                        'ehm_compiled_last_error', 'ehm_applied_last_error'):
             fn.restype = i32
     lib.ehm_search_last_error.restype = ctypes.c_char_p
     lib.ehm_search_create.argtypes = [i32, i32, i32, ctypes.POINTER(vp)]

@@ -5,7 +5,8 @@ CPU-only build container.
 
 Objects: ``ehm_capi.hip`` (C-ABI, host orchestration, generation-1 kernels),
 ``ehm_explicit.hip`` and ``ehm_implicit.hip`` (the closed loops around the two laws),
-``ehm_audit.hip`` (the sampled audit of the explicit law),
+``ehm_audit.hip`` (the sampled audit of the explicit law), ``ehm_applied.hip`` (the audit of a
+law by the cost of the input it applies),
 ``ehm_compiled.hip`` (the explicit law compiled into a hyperplane tree) and
 ``ehm_compiled32.hip`` (the kernels of its single-precision form), one
 instance of ``ehm_k2.hip`` per (column capacity NP, row slots) pair -- the solver keeps a
@@ -141,6 +142,8 @@ def _objects():
             (os.path.join(OBJ_DIR, 'ehm_implicit.o'), os.path.join(SRC_DIR, 'ehm_implicit.hip'),
              []),
             (os.path.join(OBJ_DIR, 'ehm_audit.o'), os.path.join(SRC_DIR, 'ehm_audit.hip'), []),
+            (os.path.join(OBJ_DIR, 'ehm_applied.o'), os.path.join(SRC_DIR, 'ehm_applied.hip'),
+             []),
             (os.path.join(OBJ_DIR, 'ehm_compiled.o'), os.path.join(SRC_DIR, 'ehm_compiled.hip'),
              []),
             (os.path.join(OBJ_DIR, 'ehm_compiled32.o'),
@@ -185,8 +188,8 @@ def is_stale():
     t = os.path.getmtime(LIB)
     srcs = [os.path.join(SRC_DIR, f)
             for f in ('ehm_capi.hip', 'ehm_k2.hip', 'ehm_k3.hip', 'ehm_k4.hip', 'ehm_kp.hip',
-                      'ehm_explicit.hip', 'ehm_implicit.hip', 'ehm_audit.hip', 'ehm_compiled.hip',
-                      'ehm_compiled32.hip')]
+                      'ehm_explicit.hip', 'ehm_implicit.hip', 'ehm_audit.hip', 'ehm_applied.hip',
+                      'ehm_compiled.hip', 'ehm_compiled32.hip')]
     return max([_dep_mtime()] + [os.path.getmtime(s)
                                  for s in srcs + SEARCH_DEPS + FRONTIER_DEPS]) > t
 

@@ -43,6 +43,12 @@ the law has a rollout and a single form like one compiled from the flat forest, 
 (u, leaf) as under the default.  ``to_single(flush=True)`` (``compile(dtype=np.float32, flush=True)``)
 stores a value below the normal range of a float as +0.0 instead of refusing the law and counts
 those in ``flushed``.
+
+    res = law.audit(oracle, n=100000)             # applied.AppliedAuditResult
+
+checks the law's contract at sampled states by what its input costs (applied.py): a
+compiled law keeps no costs, so the input it applies is priced by P_theta with the first input
+fixed to it, against P_theta itself.  For double and single laws, compiled here or only loaded.
 """
 
 import ctypes
@@ -198,6 +204,8 @@ class CompiledLaw:
     _rollout_plant = None       # the plant the device holds (set_plant)
     _leaf_node = None
     flushed = None              # to_single(flush=True): the counts of the values set to zero
+    _root_cells = None          # audit: the roots as the sampler's cells (built on first use)
+    _input_scale = None         # audit: the default input_tol
 
     def __init__(self, handle, device, compile_seconds=0., dtype=np.float64):
         self._lib = _capi.load()
@@ -289,6 +297,15 @@ class CompiledLaw:
             real = np.float32 if single and name in _NARROWED else np.float64
             out[name] = np.zeros(shape, dtype=np.int32 if name in _INT_ARRAYS else real)
         self._export(*[ptr(out[k]) if out[k].size else None for k in ARRAYS])
+        return out
+
+    def array(self, name):
+        """One array of ``arrays()`` (a name of ``ARRAYS``), copied from the device alone."""
+        single = self.dtype is np.float32
+        real = np.float32 if single and name in _NARROWED else np.float64
+        out = np.zeros(_shapes(self._h)[name], dtype=np.int32 if name in _INT_ARRAYS else real)
+        if out.size:
+            self._export(*[ptr(out) if k == name else None for k in ARRAYS])
         return out
 
     def _export(self, node, leaf_rec, leaf_node, test_rec, root_rec, root_entry, nbr):
@@ -468,6 +485,47 @@ class CompiledLaw:
             l = order[np.minimum(at, order.size - 1)]
             out.mode = np.where(live, self._plant_mode[l], -1).astype(np.int32)
         return out
+
+    # -- audit by the cost of the applied input (applied.py) ----------------------
+    def audit(self, oracle, n=None, X=None, seed=0, rtol=1e-7, input_tol=None,
+              return_samples=False, first=0, chunk=0):
+        """
+        Checks the law's contract at sampled states by what its input costs:
+        0 <= V_u(x) - V*(x) <= max(eps_a, eps_r V*(x)),  V_u the optimum of P_theta with the first
+        input fixed to ``evaluate(x)`` (``applied.applied_input_problem``), V* the optimum of
+        P_theta, both from the batched P_theta of ``oracle`` -- an argument, because a loaded law
+        has none --, each side with the slack rtol (1 + |V*|).  Give ``n`` -- points drawn uniform
+        in the law's roots (``applied.root_cells``) with the sampler, key and global ids
+        ``first`` .. ``first + n - 1`` of ``ExplicitMPC.sample`` -- or the states ``X``, not both.
+        ``input_tol``: by how much (infinity norm) the input may be moved to meet a row, a
+        relaxation (None: 1e-7 max(1, largest |u_0| of the leaf records)); it is used only at a
+        sample whose input is not admissible as it stands (``relaxed``, ``n_relaxed``), every
+        other V_u is the exact substitution's.  ``chunk``: samples per
+        pass; no result depends on it.  Works for double and single laws, compiled here or loaded.
+        ``EhmError`` for a law with test nodes (``compile(spine='roots')`` has none) and for an
+        oracle without a batched P_theta; ``ValueError`` for p + n_u > 8.  Returns an
+        ``applied.AppliedAuditResult``.  A sampled check, not a certificate.
+        """
+        from . import applied
+        if not getattr(self, '_handle', None):
+            raise ValueError('the law is closed')
+        if (n is None) == (X is None):
+            raise ValueError('give n (points drawn in the roots) or X, not both')
+        applied.oracle_gpu(oracle)
+        if self._h['n_test'] > 0:
+            raise _capi.EhmError(_capi.EHM_E_INVALID, 'the law has %d test nodes: its roots do '
+                                 "not tile the set -- compile(spine='roots') has none" %
+                                 self._h['n_test'])
+        if input_tol is None:
+            if self._input_scale is None:
+                u0 = self.array('leaf_rec')[:, self.p:self.p + self.n_u]
+                self._input_scale = applied.default_input_tol(u0)
+            input_tol = self._input_scale
+        if X is None and self._root_cells is None:
+            self._root_cells = applied.root_cells(self)
+        return applied.run(oracle, self.p, self.n_u, self.device, input_tol, law=self._handle,
+                           X=X, cells=self._root_cells, n=n, seed=seed, rtol=rtol,
+                           return_samples=return_samples, first=first, chunk=chunk)
 
     def __call__(self, x):
         """(u, t): the input for state x and the evaluation time, as the reference's call."""

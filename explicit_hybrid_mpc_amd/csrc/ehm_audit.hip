@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/ehmpc.h"
+#include "ehm_audit_sample.h"
 #include "ehm_explicit_dev.h"
 #include "ehm_explicit_view.h"
 #include "ehm_host.h"
@@ -243,12 +244,19 @@ struct Cells {
 
 void launch_sample(const ehm_explicit_view& v, const ehm_audit_opts* o, const Cells& C,
                    long long nc, uint64_t first, double* x, int32_t* cell) {
-    hipLaunchKernelGGL(k_audit_sample, dim3(blocks_of(nc)), dim3(EHM_AUDIT_BLOCK), 0, v.stream, nc,
-                       first, (int)o->mode, (int)o->k, o->seed, v.p, (long long)o->n_cells,
-                       C.cdf.as<const double>(), C.vert.as<const double>(), x, cell);
+    ehm_audit_launch_sample(v.stream, nc, first, (int)o->mode, (int)o->k, o->seed, v.p,
+                            (long long)o->n_cells, C.cdf.as<const double>(),
+                            C.vert.as<const double>(), x, cell);
 }
 
 }  // namespace
+
+void ehm_audit_launch_sample(hipStream_t stream, long long n, uint64_t first, int mode, int kper,
+                             uint64_t seed, int p, long long n_cells, const double* cdf,
+                             const double* V, double* X, int32_t* cell) {
+    hipLaunchKernelGGL(k_audit_sample, dim3(blocks_of(n)), dim3(EHM_AUDIT_BLOCK), 0, stream, n,
+                       first, mode, kper, seed, p, n_cells, cdf, V, X, cell);
+}
 
 extern "C" {
 

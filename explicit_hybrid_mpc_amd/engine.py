@@ -123,6 +123,10 @@ class FlatTree:
 class GpuProblem:
     """Device-resident canonical MPC instance (one GPU, one HIP stream)."""
 
+    # the applied-input problems of this instance (applied.applied_gpu): the exact substitution
+    # and the last relaxed one, closed with it
+    _applied = None
+
     def __init__(self, canonical, eps_a, eps_r, device=0):
         self.can = canonical
         self.device = int(device)
@@ -157,6 +161,9 @@ class GpuProblem:
             run = run() if run is not None else None
             if run is not None:
                 run.abort()
+            for gp in (self._applied or {}).values():
+                gp.close()
+            self._applied = None
             self._lib.ehm_problem_destroy(self._handle)
             self._handle = ctypes.c_void_p()
 

@@ -208,6 +208,7 @@ class ExplicitMPC:
     # class defaults: rollout checks its arguments before it touches anything else
     mpc = None
     _rollout_plant = None       # the plant the device holds (set_plant)
+    _input_scale = None         # audit_applied: the default input_tol (built on first use)
 
     def __init__(self, tree, oracle=None, device=0):
         mpc = getattr(oracle, 'mpc', None)
@@ -449,6 +450,42 @@ class ExplicitMPC:
                            open_volume_fraction=float(vol[~cells['closed']].sum() / vol.sum()),
                            allow_open=bool(allow_open), rtol=float(rtol),
                            seconds=tuple(res.seconds[:]), **arrays)
+
+    def audit_applied(self, n=None, seed=0, mode=None, per_leaf=None, rtol=1e-7, input_tol=None,
+                      return_samples=False, oracle=None, first=0, chunk=0):
+        """
+        The judgement of ``CompiledLaw.audit`` (applied.py) for this law: at the
+        points of ``sample`` (same arguments, so ``per_leaf`` works) the input of
+        ``evaluate`` is priced by P_theta with the first input fixed to it, against V* =
+        P_theta(x).  ``input_tol`` None: 1e-7 max(1, largest |u| of the leaves' vertex inputs).
+        Returns an ``applied.AppliedAuditResult`` (``root`` is -1: the points were drawn in the
+        leaves, ``sample`` tells in which).
+        """
+        from . import applied
+        oracle = self._oracle if oracle is None else oracle
+        if oracle is None:
+            raise ValueError('audit_applied needs an oracle: the law was built without one')
+        if n is not None and per_leaf is not None:
+            raise ValueError('per_leaf fixes the number of samples (leaves x per_leaf): give n or '
+                             'per_leaf, not both')
+        applied.oracle_gpu(oracle)
+        if self.p + self.n_u > _capi.EHM_MAX_P:
+            raise ValueError('the applied-input problem adds one parameter per input: p + n_u = '
+                             '%d exceeds EHM_MAX_P = %d' % (self.p + self.n_u, _capi.EHM_MAX_P))
+        X, _ = self.sample(n=n, seed=seed, mode=mode, per_leaf=per_leaf, first=first, chunk=chunk)
+        if input_tol is None:
+            if self._input_scale is None:
+                t = self.tree
+                if isinstance(t, FlatTree):
+                    vin = np.asarray(t.vertex_inputs)[np.asarray(t.left) < 0]
+                else:
+                    _, vin, left, _, _ = flatten_tree(t)
+                    vin = vin[left < 0]
+                self._input_scale = applied.default_input_tol(vin)
+            input_tol = self._input_scale
+        res = applied.run(oracle, self.p, self.n_u, self.device, input_tol, source=self._handle,
+                          X=X, rtol=rtol, return_samples=return_samples, first=first, chunk=chunk)
+        return res
 
     def node_modes(self, plant):
         """int32 [n_nodes]: step-0 mode of every node's commutation (-1: none); all 0 for a

@@ -760,6 +760,93 @@ int ehm_explicit_records(ehm_explicit* ex, double* rec);
  * ehm_audit_samples.  A list of its own: ehm_abi_sizes keeps returning the six it always has. */
 int ehm_audit_abi_sizes(int64_t* sizes, int32_t n);
 
+/* ---- audit of a law by the cost of the input it applies (csrc/ehm_applied.hip) ---
+ *
+ * At every point x the law's input ubar is priced by the fixed-first-input problem: V_u(x) = the
+ * optimum of P_theta with u_0 = ubar, against V*(x) = P_theta(x).  `applied` holds that problem
+ * (applied.applied_input_problem: the canonical form with the columns of u_0 moved to the
+ * parameters, theta' = (x, ubar), p + n_u <= EHM_MAX_P), `oracle` the problem the law was built
+ * for.  Both optima come from ehm_solve_pt_batch, bit for bit what it returns for the same points.
+ *
+ * Points: x [n][p] of the caller, or (x NULL) drawn as ehm_explicit_sample draws them in uniform
+ * mode from the cells listed -- for a compiled law its roots -- with the same key (seed, 1) and the
+ * same global ids first .. first + n - 1.
+ * Input: of `law` (ehm_compiled_eval_batch: u and leaf are that entry point's, for a double and a
+ * single law), else of `source` (ehm_explicit_eval_batch), else the caller's u [n][n_u].
+ * Per sample (k_applied_pack): theta' = (x, ubar), with 0 in place of a component of ubar that is
+ * not finite and the sample flagged; constant = 0 + cost_u[0] ubar_0 + cost_u[1] ubar_1 + .., one
+ * rounding per operation; V_u = (optimum of `applied` at theta') + constant.
+ * `applied` is the exact substitution.  opts->relaxed (may be NULL) is the same problem with its
+ * rows widened by input_tol (applied_input_problem(can, input_tol)): a sample at which x is feasible
+ * and no commutation of `applied` is, is solved again there, and if a commutation of `relaxed` is
+ * feasible its optimum and commutation take the place of `applied`'s (the sample counts in
+ * result->relaxed).  So the cost of an input that is admissible as it stands is never lowered by
+ * the relaxation, and V_u >= V* holds for it in exact arithmetic. */
+typedef struct ehm_applied_opts {
+    int64_t n;              /* samples of this call                                            */
+    uint64_t first;         /* global id of its first sample                                   */
+    uint64_t seed;
+    int64_t chunk;          /* samples per pass (0: 65536); the LP batches are this long       */
+    int64_t n_cells;        /* drawn points: the cells                                         */
+    const double* cell_vertices;    /* [n_cells][p+1][p]                                       */
+    const double* cdf;              /* [n_cells] running sum of their volumes                  */
+    const double* x;        /* the caller's points [n][p], or NULL: draw them                  */
+    const double* u;        /* the caller's inputs [n][n_u] (law and source NULL)              */
+    ehm_explicit* source;   /* the evaluator when law is NULL                                  */
+    ehm_problem* relaxed;   /* the applied problem widened by input_tol, or NULL               */
+    const double* cost_u;   /* [n_u] cost of u_0 that `applied` does not hold                  */
+    int32_t p, n_u;         /* of the law; applied has p + n_u parameters                      */
+    int32_t device;
+    int32_t reserved;
+    double rtol;            /* slack = rtol (1 + |V*|)                                         */
+    double eps_a, eps_r;
+} ehm_applied_opts;
+/* Statuses, the first that applies: 5 infeasible (no commutation feasible at x), 4 no_law (an
+ * input that is not finite), 3 inadmissible (x feasible, no commutation feasible with ubar
+ * applied), 2 negative (not gap >= -slack), 1 violation (gap > bound + slack), 0 within;
+ * gap = V_u - V*, bound = max(eps_a, eps_r V*). */
+typedef struct ehm_applied_result {
+    int64_t counts[6];      /* samples by status                                               */
+    int64_t histogram[33];  /* of gap / bound over statuses 0-2, binned as ehm_audit_result's  */
+    int64_t worst_id;       /* largest gap / bound among statuses 0-2, the smallest id on ties;
+                               -1: no such sample                                              */
+    int32_t worst_leaf;
+    int32_t reserved;
+    int64_t relaxed;        /* samples whose V_u comes from opts->relaxed                      */
+    double  max_ratio;      /* -inf: no such sample                                            */
+    double  worst_vu, worst_vstar, worst_bound;
+    double  worst_x[8];
+    double  worst_u[8];
+    double  seconds[5];     /* [0] sampling kernel, [1] evaluation kernel, [2] pack + reduce
+                               kernels (device time), [3] the P_theta batches of `oracle`,
+                               [4] those of `applied` and `relaxed` (host wall time)           */
+} ehm_applied_result;
+/* Per-sample outputs, each [n] ([n][p] for x, [n][n_u] for u) or NULL.  root: the cell a drawn
+ * point was drawn in, -1 for a caller's point; leaf: -1 for a caller's input. */
+typedef struct ehm_applied_samples {
+    double*  x;
+    int32_t* root;
+    int32_t* leaf;
+    double*  u;
+    double*  vu;
+    double*  vstar;
+    int32_t* delta_idx;
+    int32_t* delta_idx_applied;
+    int32_t* status;
+    int32_t* relaxed;       /* 1 where V_u comes from opts->relaxed, else 0                    */
+} ehm_applied_samples;
+/* Statuses and counts by integer atomics, the worst sample by a reduction with ties to the smaller
+ * id, no floating-point sum across samples: nothing reported depends on the launch shape or the
+ * chunk size.  A law with test nodes is refused (EHM_E_INVALID).  samples may be NULL.  Errors,
+ * those of the evaluators and of the LP batches included, are reported through
+ * ehm_applied_last_error. */
+int ehm_compiled_audit(ehm_compiled* law, ehm_problem* oracle, ehm_problem* applied,
+                       const ehm_applied_opts* opts, ehm_applied_result* result,
+                       const ehm_applied_samples* samples);
+const char* ehm_applied_last_error(void);
+/* ehm_abi_sizes for ehm_applied_opts, ehm_applied_result, ehm_applied_samples, in this order. */
+int ehm_applied_abi_sizes(int64_t* sizes, int32_t n);
+
 /* ---- closed-loop simulation under the COMPILED law (csrc/ehm_compiled.hip) -------
  *
  * The entry points of the explicit law's rollout, argument for argument, on a compiled law -- also
