@@ -59,10 +59,13 @@ EXPORTED = [
     'ehm_explicit_set_costs', 'ehm_explicit_sample', 'ehm_explicit_audit', 'ehm_explicit_records',
     'ehm_audit_abi_sizes',
     'ehm_compiled_audit', 'ehm_applied_last_error', 'ehm_applied_abi_sizes',
+    'ehm_compiled_cells', 'ehm_certify_last_error', 'ehm_compiled_certify',
+    'ehm_certify_abi_sizes',
 ]
 EHM_AUDIT_MODES = {'uniform': 0, 'per_leaf': 1}     # EHM_AUDIT_UNIFORM / _PER_LEAF
 EHM_COMPILE_SPINE_ROOTS = 1     # ehm_compiled_create_opts
 EHM_NARROW_FLUSH = 1            # ehm_compiled_narrow_opts
+EHM_CELL_MAX_DEPTH = 256        # ehm_compiled_cells: levels below a root a leaf's cell may lie
 
 
 # every symbol include/ehm_search.h declares (host bookkeeping of the prefix searches)
@@ -246,6 +249,28 @@ class AppliedSamples(ctypes.Structure):
                                                'relaxed')]
 
 
+class CertifyOpts(ctypes.Structure):
+    _fields_ = [('n', ctypes.c_int64), ('leaf_ids', ctypes.c_void_p),
+                ('root_vertices', ctypes.c_void_p), ('chunk', ctypes.c_int64),
+                ('relaxed', ctypes.c_void_p), ('cost_u', ctypes.c_void_p),
+                ('p', ctypes.c_int32), ('n_u', ctypes.c_int32), ('n_delta', ctypes.c_int32),
+                ('max_tries', ctypes.c_int32), ('device', ctypes.c_int32),
+                ('reserved', ctypes.c_int32)]
+
+
+class CertifyResult(ctypes.Structure):
+    _fields_ = [('counts', ctypes.c_int64 * 6), ('relaxed', ctypes.c_int64),
+                ('worst_leaf', ctypes.c_int64), ('worst_tbest', ctypes.c_double),
+                ('certified_volume', ctypes.c_double), ('cell_volume', ctypes.c_double),
+                ('seconds', ctypes.c_double * 6)]
+
+
+class CertifyLeaves(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ('status', 'delta_idx', 'tbest', 'tries', 'relaxed',
+                                               'n_candidates', 'volume', 'vertices', 'inputs',
+                                               'W')]
+
+
 _lib = None
 
 
@@ -299,6 +324,19 @@ def load(build_if_missing=True):
                                        ctypes.POINTER(AppliedResult),
                                        ctypes.POINTER(AppliedSamples)]
     lib.ehm_applied_last_error.restype = ctypes.c_char_p
+    mirrors = (CertifyOpts, CertifyResult, CertifyLeaves)  # ... and the certificate's
+    sizes = (i64 * len(mirrors))()
+    lib.ehm_certify_abi_sizes.argtypes = [vp, i32]
+    if lib.ehm_certify_abi_sizes(ctypes.addressof(sizes), len(mirrors)) != len(mirrors) or any(
+            int(sizes[k]) != ctypes.sizeof(m) for k, m in enumerate(mirrors)):
+        raise EhmError(EHM_E_INVALID, 'libehmpc.so and its ctypes binding disagree about the '
+                       "certificate's structs: %s against %s (rebuild the library)" % (
+                           [int(v) for v in sizes], [ctypes.sizeof(m) for m in mirrors]))
+    lib.ehm_compiled_certify.argtypes = [vp, vp, vp, ctypes.POINTER(CertifyOpts),
+                                         ctypes.POINTER(CertifyResult),
+                                         ctypes.POINTER(CertifyLeaves)]
+    lib.ehm_compiled_cells.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+    lib.ehm_certify_last_error.restype = ctypes.c_char_p
     lib.ehm_explicit_set_costs.argtypes = [vp, vp, vp]
     lib.ehm_explicit_sample.argtypes = [vp, ctypes.POINTER(AuditOpts), vp, vp]
     lib.ehm_explicit_audit.argtypes = [vp, vp, ctypes.POINTER(AuditOpts),
@@ -397,7 +435,8 @@ def load(build_if_missing=True):
         fn = getattr(lib, name)
         if name not in ('ehm_last_error', 'ehm_version', 'ehm_stream',
                         'ehm_explicit_last_error', 'ehm_implicit_last_error',
-                        'ehm_compiled_last_error', 'ehm_applied_last_error'):
+                        'ehm_compiled_last_error', 'ehm_applied_last_error',
+                        'ehm_certify_last_error'):
             fn.restype = i32
     lib.ehm_search_last_error.restype = ctypes.c_char_p
     lib.ehm_search_create.argtypes = [i32, i32, i32, ctypes.POINTER(vp)]

@@ -18,7 +18,8 @@ problem relaxed by ``input_tol`` -- so the relaxation admits an input that overs
 rounding (a single law) and never lowers the cost of an input that is admissible as it stands.  The
 audit judges  0 <= V_u(x) - V*(x) <= max(eps_a, eps_r V*(x))  per point.  By convexity of V_delta
 the interpolated input costs at most the interpolated vertex costs, V_u <= Vbar: this audit is the
-tighter one, and the only one for a law that keeps no costs.  A sampled check, not a certificate.
+tighter one, and the only one for a law that keeps no costs.  A sampled check;
+``CompiledLaw.certify`` (certify.py) is the statement for every state of a leaf.
 """
 
 import ctypes
@@ -158,7 +159,8 @@ def root_cells(law):
 class AppliedAuditResult:
     """
     What ``CompiledLaw.audit`` / ``ExplicitMPC.audit_applied`` found (a sampled
-    check, not a certificate): ``counts`` samples by status name (STATUS_NAMES), ``max_ratio`` the
+    check -- ``CompiledLaw.certify`` is the certificate): ``counts`` samples by status name
+    (STATUS_NAMES), ``max_ratio`` the
     largest (V_u - V*) / bound over statuses 0-2 (-inf if there is none), ``worst`` that sample
     (id, x, leaf, u, vu, vstar, bound; None if there is none), ``histogram`` int64 [33] of the
     ratio (32 bins over [0, 1], one above), ``seconds`` (sampling kernel, evaluation kernel, pack

@@ -49,6 +49,17 @@ those in ``flushed``.
 checks the law's contract at sampled states by what its input costs (applied.py): a
 compiled law keeps no costs, so the input it applies is priced by P_theta with the first input
 fixed to it, against P_theta itself.  For double and single laws, compiled here or only loaded.
+
+    cells = law.cells()                           # certify.LeafCells
+
+rebuilds the simplex of every leaf from the law's own arrays and gives the leaf's own map at its
+vertices (certify.py): a compiled law keeps no vertices, and a statement that holds
+on a whole leaf, where the audit speaks of samples, starts from them.
+
+    res = law.certify(oracle)                     # certify.CertificateResult
+
+is that statement: the contract of ``audit`` proved on every leaf the test can close, from the
+costs of the vertex inputs (convexity of the fixed-commutation cost along the leaf's affine map).
 """
 
 import ctypes
@@ -504,7 +515,8 @@ class CompiledLaw:
         pass; no result depends on it.  Works for double and single laws, compiled here or loaded.
         ``EhmError`` for a law with test nodes (``compile(spine='roots')`` has none) and for an
         oracle without a batched P_theta; ``ValueError`` for p + n_u > 8.  Returns an
-        ``applied.AppliedAuditResult``.  A sampled check, not a certificate.
+        ``applied.AppliedAuditResult``.  A sampled check; ``certify`` gives the statement that
+        holds at every state of a leaf.
         """
         from . import applied
         if not getattr(self, '_handle', None):
@@ -526,6 +538,49 @@ class CompiledLaw:
         return applied.run(oracle, self.p, self.n_u, self.device, input_tol, law=self._handle,
                            X=X, cells=self._root_cells, n=n, seed=seed, rtol=rtol,
                            return_samples=return_samples, first=first, chunk=chunk)
+
+    # -- the leaf cells (certify.py) ------------------------------------------------
+    def cells(self, leaves=None):
+        """
+        The simplex of every leaf (``leaves``: rows of the leaf records, None: all), rebuilt on the
+        device from the root records, the root entries and the planes alone, and the input this
+        leaf's own map gives at each of its vertices, in the law's own arithmetic.  Works for
+        double and single laws, compiled here or loaded; the same law loaded from its file gives
+        the same cells bit for bit.  A leaf more than 256 levels below its root, or one whose path
+        holds a node that does not bisect the cell that reaches it, has status ``no_cell`` and NaN
+        rows.  ``EhmError`` for a law with test nodes (``compile(spine='roots')`` has none).
+        Returns a ``certify.LeafCells``.
+        """
+        from . import certify
+        return certify.cells(self, leaves)
+
+    def certify(self, oracle, leaves=None, input_tol=None, max_tries=3, chunk=0,
+                return_leaves=False):
+        """
+        Certifies the law's contract leaf by leaf: a leaf is ``certified`` when
+        V_u(x) - V*(x) < max(eps_a, eps_r V*(x)) is PROVED at every state x of its cell, V_u and V*
+        as in ``audit``.  On a leaf the law is affine, so for a fixed commutation d the cost of its
+        input is convex in x and lies below the interpolation of its values W at the cell's
+        vertices; the decision form of the reference's bar_E_delta_R (``ehm_bar_e_batch``) with
+        Vbar = W then closes the cell or not.  The candidates d are the commutations of the
+        applied-input problem feasible at all p + 1 vertices (by convexity feasible on the cell),
+        tried in the order of sum W, at most ``max_tries`` of them (0: all); any one that closes
+        the cell proves the statement.  A leaf without a candidate is tried on the problem relaxed
+        by ``input_tol`` (None: as ``audit``) and marked ``relaxed``: its certificate is for an
+        input within input_tol of the law's.  ``leaves``: rows of the leaf records (None: all);
+        ``chunk``: leaves per pass, no result depends on it.
+
+        What it covers: the piecewise-affine function the arrays define on the cells their planes
+        define (``cells``).  Not: the rounding of a single law's evaluation (DESIGN.md 3.8c bounds
+        it), a state within rounding of a split face being handed to the sibling leaf's map, the
+        recovery error of the root vertices the cells carry, nor the tolerances of the LP solves.
+        ``uncertified`` is not a violation: the vertex interpolation of a convex function is an
+        upper bound, not the function.  Refusals as ``audit``.  Returns a
+        ``certify.CertificateResult``.
+        """
+        from . import certify
+        return certify.certify(self, oracle, leaves=leaves, input_tol=input_tol,
+                               max_tries=max_tries, chunk=chunk, return_leaves=return_leaves)
 
     def __call__(self, x):
         """(u, t): the input for state x and the evaluation time, as the reference's call."""

@@ -41,6 +41,7 @@
 
 #include "../../include/ehmpc.h"
 #include "ehm_compiled_dev.h"
+#include "ehm_compiled_view.h"
 #include "ehm_explicit_view.h"
 #include "ehm_host.h"
 
@@ -526,6 +527,23 @@ struct ehm_compiled {
                             d.leaf_stride, d.side_stride, d.p, d.n_u, d.n_roots};
     }
 };
+
+void ehm_compiled_get_view(const ehm_compiled* C, ehm_compiled_view* out) {
+    out->device = C->device;
+    out->single = C->single;
+    out->node = C->node.ptr;
+    out->leaf_rec = C->leaf_rec.ptr;
+    out->root_entry = C->root_entry.as<const int32_t>();
+    out->p = (int)C->h[H_P];
+    out->n_u = (int)C->h[H_NU];
+    out->node_stride = (int)C->h[H_NS];
+    out->leaf_stride = (int)C->h[H_LS];
+    out->n_roots = C->h[H_ROOTS];
+    out->n_int = C->h[H_INT];
+    out->n_leaf = C->h[H_LEAF];
+    out->n_test = C->h[H_TEST];
+    out->stream = C->stream;
+}
 
 namespace {
 

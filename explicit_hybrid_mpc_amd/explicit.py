@@ -487,6 +487,22 @@ class ExplicitMPC:
                           X=X, rtol=rtol, return_samples=return_samples, first=first, chunk=chunk)
         return res
 
+    def certify_applied(self, oracle=None, spine='roots', dtype=np.float64, flush=False, **kw):
+        """
+        ``CompiledLaw.certify`` (certify.py) for this law: compiles it
+        (``compile(spine=spine, dtype=dtype, flush=flush)``) and certifies the compiled law leaf
+        by leaf against ``oracle`` (default: the one the law was built with); ``kw`` as
+        ``CompiledLaw.certify``.  Returns its ``certify.CertificateResult``.
+        """
+        oracle = self._oracle if oracle is None else oracle
+        if oracle is None:
+            raise ValueError('certify_applied needs an oracle: the law was built without one')
+        law = self.compile(dtype=dtype, spine=spine, flush=flush)
+        try:
+            return law.certify(oracle, **kw)
+        finally:
+            law.close()
+
     def node_modes(self, plant):
         """int32 [n_nodes]: step-0 mode of every node's commutation (-1: none); all 0 for a
         single-mode plant."""

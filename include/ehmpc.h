@@ -847,6 +847,107 @@ const char* ehm_applied_last_error(void);
 /* ehm_abi_sizes for ehm_applied_opts, ehm_applied_result, ehm_applied_samples, in this order. */
 int ehm_applied_abi_sizes(int64_t* sizes, int32_t n);
 
+/* ---- leaf cells of a compiled law (csrc/ehm_certify.hip) --------------------------
+ *
+ * The simplex of every requested leaf, rebuilt from the law's own arrays (root_rec, root_entry,
+ * node), and the input the leaf's own affine map gives at each of its vertices: what a certificate
+ * of the law leaf by leaf starts from.  For double and single laws, compiled or imported.
+ * leaf_ids [n]: rows of leaf_rec (0 .. n_leaf - 1; EHM_E_INVALID outside), or NULL: leaves 0 .. n - 1
+ * (n <= n_leaf).  root_vertices [n_roots][p+1][p]: the roots' vertices, which the caller recovers
+ * from root_rec (applied.root_cells: v_i = v_0 + column i of inv(inv(E))).
+ * A leaf is walked up to its root through a parent table made on the device (the turns kept in a
+ * set of EHM_CELL_MAX_DEPTH bits) and then down from the root's vertices: at a plane node
+ * s_i = ((0 + a_0 v_i0) + .. + a_(p-1) v_i(p-1)) + b in double (float coefficients widened), exactly
+ * one s_i > 0.5 and exactly one s_i < -0.5 are required -- the two ends of the bisected edge --, their
+ * midpoint is (v + w) / 2 as ehm_split_batch computes it and replaces the negative-side vertex in
+ * the left child, the positive-side one in the right child.
+ * Outputs: vertices [n][p+1][p]; ubar [n][p+1][n_u] (may be NULL): the leaf map at every vertex in
+ * the law's own arithmetic -- a double law u_0 + K (v - v_0) as ehm_compiled_eval_batch sums it, a
+ * single law xs = (float) v and float sums, one rounding per product and per sum, widened;
+ * status [n]: 0 a cell, 1 no_cell (a leaf deeper than EHM_CELL_MAX_DEPTH, a node that is no
+ * bisection of the cell that reaches it, a leaf no root reaches), whose vertices and ubar are NaN.
+ * A law with test nodes is refused (EHM_E_INVALID).  Errors through ehm_certify_last_error. */
+#define EHM_CELL_MAX_DEPTH 256
+#define EHM_CELL_OK        0
+#define EHM_CELL_NO_CELL   1
+int ehm_compiled_cells(ehm_compiled* law, const double* root_vertices, int64_t n,
+                       const int32_t* leaf_ids, double* vertices, double* ubar, int32_t* status);
+const char* ehm_certify_last_error(void);
+
+/* ---- certificate of a compiled law leaf by leaf (csrc/ehm_certify.hip) ----------
+ *
+ * On a leaf the law is affine, and for a fixed commutation d the cost V_d(x, u(x)) of its input --
+ * the optimum of the applied-input problem of section 3.8e with the commutation fixed -- is convex in
+ * x.  With W_i its values at the p + 1 vertices of the leaf's cell,
+ *     V_u(x) <= V_d(x, u(x)) <= sum_i alpha_i(x) W_i      on the cell,
+ * so ehm_bar_e_batch(oracle, cell, Vbar = W) closing the cell proves
+ *     V_u(x) - V*(x) < max(eps_a, eps_r V*(x))            at every state x of the leaf.
+ * Per leaf: the cell and the vertex inputs (ehm_compiled_cells); theta' = (v_i, ubar_i) and the
+ * constant 0 + cost_u[0] ubar_0 + .. packed on the device, a component of ubar that is not finite
+ * replaced by 0 and the leaf flagged no_law; every (vertex, commutation) pair tested for feasibility
+ * on `applied` (ehm_point_idx_batch, feas = 1, feasible iff tau <= 1e-8 as in the batched oracles);
+ * a commutation feasible at all p + 1 vertices is a CANDIDATE (feasible on the cell by convexity of
+ * the feasible set in (theta, u_0)); the candidates' vertex problems solved (feas = 0),
+ * W_i = J_i + constant_i; a leaf without a candidate repeats both steps on opts->relaxed (may be
+ * NULL) and is marked relaxed if that gives one: its certificate is for an input within input_tol
+ * of the law's.  A candidate one of whose solves reports EHM_ST_STALLED is not tried.  The others
+ * are ordered by ((0 + W_0) + .. ) + W_p ascending, the lowest index on ties, and tried in that
+ * order, at most max_tries of them (0: all), until ehm_bar_e_batch closes the cell.  Any candidate
+ * that closes it proves the statement: the order affects cost only.
+ * Statuses, the first that applies: 4 no_cell, 3 no_law, 0 certified, 2 inadmissible (no
+ * candidate, not even relaxed, and none set aside), 5 stalled (not certified, and a candidate was
+ * set aside for a stalled solve), 1 uncertified (every try had t* >= 0: NOT a violation -- the
+ * interpolation of a convex function is an upper bound, not the function). */
+typedef struct ehm_certify_opts {
+    int64_t n;                      /* leaves of this call                                     */
+    const int32_t* leaf_ids;        /* [n] rows of leaf_rec, or NULL: leaves 0 .. n - 1        */
+    const double* root_vertices;    /* [n_roots][p+1][p], as for ehm_compiled_cells            */
+    int64_t chunk;                  /* leaves per pass (0: 8192); no result depends on it      */
+    ehm_problem* relaxed;           /* the applied problem widened by input_tol, or NULL       */
+    const double* cost_u;           /* [n_u] cost of u_0 that `applied` does not hold          */
+    int32_t p, n_u;                 /* of the law; applied has p + n_u parameters              */
+    int32_t n_delta;                /* commutations of oracle, applied and relaxed             */
+    int32_t max_tries;              /* candidates tried per leaf (0: all)                      */
+    int32_t device;
+    int32_t reserved;
+} ehm_certify_opts;
+typedef struct ehm_certify_result {
+    int64_t counts[6];              /* leaves by status                                        */
+    int64_t relaxed;                /* leaves whose candidates come from opts->relaxed         */
+    int64_t worst_leaf;             /* position in the call (0 .. n - 1) of the uncertified leaf
+                                       with the largest tbest, the first on ties; -1: none     */
+    double  worst_tbest;            /* NaN: none                                               */
+    double  certified_volume;       /* sum of the certified cells' volumes, in leaf order      */
+    double  cell_volume;            /* the same over every leaf that has a cell                */
+    double  seconds[6];             /* [0] cell, pack and judge kernels (device time), then host
+                                       wall time of [1] the feasibility batches, [2] the cost
+                                       batches, [3] the tests, [4] the volumes, [5] the rest    */
+} ehm_certify_result;
+/* Per-leaf outputs, each [n] or NULL: delta_idx the closing commutation (-1: none), tbest of the
+ * last try (NaN: none), tries made, relaxed 0 / 1, n_candidates (those set aside included),
+ * volume of the cell (NaN: none); vertices [n][p+1][p], inputs [n][p+1][n_u], and W [n][p+1] the
+ * vertex costs of the last candidate tried (NaN: none). */
+typedef struct ehm_certify_leaves {
+    int32_t* status;
+    int32_t* delta_idx;
+    double*  tbest;
+    int32_t* tries;
+    int32_t* relaxed;
+    int32_t* n_candidates;
+    double*  volume;
+    double*  vertices;
+    double*  inputs;
+    double*  W;
+} ehm_certify_leaves;
+/* `oracle` is the problem the law was built for, `applied` the exact substitution
+ * (applied.applied_input_problem).  Refusals as ehm_compiled_cells and ehm_compiled_audit (test
+ * nodes, p + n_u > EHM_MAX_P, a law of another (p, n_u)).  leaves may be NULL. */
+int ehm_compiled_certify(ehm_compiled* law, ehm_problem* oracle, ehm_problem* applied,
+                         const ehm_certify_opts* opts, ehm_certify_result* result,
+                         const ehm_certify_leaves* leaves);
+/* ehm_abi_sizes for ehm_certify_opts, ehm_certify_result, ehm_certify_leaves, in this order. */
+int ehm_certify_abi_sizes(int64_t* sizes, int32_t n);
+
 /* ---- closed-loop simulation under the COMPILED law (csrc/ehm_compiled.hip) -------
  *
  * The entry points of the explicit law's rollout, argument for argument, on a compiled law -- also
