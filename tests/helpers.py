@@ -158,6 +158,77 @@ def make_gp(row, can, eps_a, eps_r):
     return gp
 
 
+# ---- one quadratic-cost law per quadratic shared-block instance, and the edges of the row layout --
+# Members of examples.linear_mpc(seed=0, n_x, n_u, N, n_random, cost='quadratic'): n = n_u N
+# columns, m = N (2 n_x + n_random + 2 n_u) rows, p = n_x, nothing eliminated.  The instance named
+# is the one of the suboptimality-test programme, n + p + 1 columns and lp_slots(m, p + 3) row slots
+# (csrc/ehm_k2.h), among the -DEHM2_QUAD=1 instances of csrc/ehm_k2.hip (build.K2Q_NPS x K2_SLOTS);
+# each row is the smallest member reaching its instance over n_x 2..4, n_u <= min(n_x, 3), N <= 30.
+#   (capacity, slots, n_x, n_u, N, n_random, what the row is there for)
+QUADRATIC_WIDTH_ROWS = (
+    (8, 1, 2, 1, 1, 0, ''),
+    (8, 2, 2, 1, 2, 24, ''),
+    (8, 3, 4, 1, 3, 32, ''),
+    (8, 4, 3, 1, 4, 40, ''),
+    (16, 1, 4, 2, 2, 0, ''),
+    (16, 2, 4, 1, 4, 8, ''),
+    (16, 3, 4, 1, 4, 24, ''),
+    (16, 4, 4, 1, 4, 40, ''),
+    (24, 1, 4, 3, 4, 0, ''),
+    (24, 2, 4, 3, 4, 2, ''),
+    (24, 3, 3, 1, 13, 2, ''),
+    (24, 4, 4, 1, 12, 8, ''),
+    (32, 2, 3, 3, 7, 0, ''),
+    (32, 3, 4, 3, 7, 4, ''),
+    (32, 4, 4, 1, 20, 0, ''),
+    # (32, 4) again with a short horizon and p = 3: the law of the persistent-kernel tests, whose
+    # CPU partition solves the uncondensed programmes (N = 20 takes ten times as long)
+    (32, 4, 3, 3, 7, 16, 'short'),
+    # n + p + 1 = the capacity: the last factorised column, t, sits in lane NP - 1
+    (8, 1, 4, 3, 1, 0, 'full'),
+    (16, 1, 3, 3, 4, 0, 'full'),
+    (24, 2, 3, 2, 10, 0, 'full'),
+    (32, 3, 4, 3, 9, 0, 'full'),
+    # m + p + 3 = 256 (m = 250): the second quadratic row is lane 63 of slot 4, and the law is at
+    # the row limit of the generation-1 kernels
+    (16, 4, 3, 1, 5, 42, 'rows256'),
+    # m = 64: the extra rows open a slot of their own
+    (8, 2, 2, 1, 1, 58, 'm64'),
+    # (m mod 64) + (p + 3) = 64: the extras just fit behind the rows; = 65: lp_xbase moves them to
+    # the next slot and leaves a gap of invalid rows
+    (8, 1, 4, 1, 1, 47, 'fit64'),
+    (8, 2, 4, 1, 1, 48, 'gap65'),
+)
+# the rows whose whole partition the persistent frontier kernel grows, and their theta scales:
+# 0.999 x tools/calibrate_configs.max_feasible_scale (quadratic_width_scale recomputes them), so
+# that the corner regions of the box are constrained
+QUADRATIC_PERSISTENT_ROWS = {(24, 1, 4, 3, 4, 0, ''): 0.704, (24, 4, 4, 1, 12, 8, ''): 0.6369,
+                             (32, 2, 3, 3, 7, 0, ''): 0.7827, (32, 4, 3, 3, 7, 16, 'short'): 0.7197}
+
+
+def quadratic_width_name(row):
+    cap, sl, n_x, n_u, N, n_random, tag = row
+    return 'k2q_%d_%d-nx%d_nu%d_N%d_r%d%s' % (cap, sl, n_x, n_u, N, n_random,
+                                             '_' + tag if tag else '')
+
+
+def quadratic_width_instance(row, scale=None):
+    """The row's MPC; with ``scale`` its theta scale is registered under a name of the row's own."""
+    n_x, n_u, N, n_random = row[2:6]
+    mpc = examples.linear_mpc(seed=0, n_x=n_x, n_u=n_u, N=N, n_random=n_random, cost='quadratic')
+    mpc.name = 'quadratic_nx%d_nu%d_N%d_r%d_seed0' % (n_x, n_u, N, n_random)
+    if scale is not None:
+        examples.THETA_SCALE.setdefault(mpc.name, scale)
+    return mpc
+
+
+def quadratic_width_scale(row, tol=1e-4):
+    """0.999 x the largest centred box with feasible vertices, rounded down to four digits."""
+    import math
+    from tools.calibrate_configs import max_feasible_scale
+    return math.floor(1e4 * 0.999 * max_feasible_scale(quadratic_width_instance(row), tol=tol)) / 1e4
+
+
 # ---- laws the LDS-resident wide family refuses: the streaming wide kernels (ehm_k3.hip) ----------
 # Rows in the format above (family, np, np, slots, n_x, n_u, N, n_random, s0, theta scale); k3's two
 # instances hold 64 columns x 8 or 16 row slots.  What k4 refuses them for (K2Api::fits):
@@ -233,13 +304,15 @@ def node_depths(tree):
     return out
 
 
-def check_budgeted_rounds(gps, roots, locs):
+def check_budgeted_rounds(gps, roots, locs, first_budget=64):
     """
     ehm_partition_advance: rounds of the PERSISTENT frontier kernel with a pop budget; what is
     left of its device queue is the frontier the ranks rebalance.  gps: three handles with the
     same problem and tolerances -- gps[0] and gps[1] play two ranks, rank 0 owns the roots, rank 1
     starts empty (shard_min_frontier < 0) and is fed by the first rounds; gps[2] grows the
     reference tree in one run.  The merged shares are that tree node for node.
+    first_budget: pops of the first round, doubled every round (trees of under 2000 nodes need a
+    smaller one to last the three rounds asked for below).
     Returns (reference tree, finished shares).
     """
     from explicit_hybrid_mpc_amd import distributed
@@ -248,7 +321,7 @@ def check_budgeted_rounds(gps, roots, locs):
     runs = [gps[r].begin(roots, shard=(r, world, -1)) for r in range(world)]
     assert runs[1].advance(10) == 0                     # nothing to do yet
     logs = [[] for _ in range(world)]
-    rnd, moved, budget = 0, 0, 64
+    rnd, moved, budget = 0, 0, int(first_budget)
     while True:
         counts = [run.advance(budget) for run in runs]
         budget = min(2 * budget, 4096)
