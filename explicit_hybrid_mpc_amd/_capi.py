@@ -61,6 +61,7 @@ EXPORTED = [
     'ehm_compiled_audit', 'ehm_applied_last_error', 'ehm_applied_abi_sizes',
     'ehm_compiled_cells', 'ehm_certify_last_error', 'ehm_compiled_certify',
     'ehm_certify_abi_sizes',
+    'ehm_compiled_reduce', 'ehm_reduce_last_error',
 ]
 EHM_AUDIT_MODES = {'uniform': 0, 'per_leaf': 1}     # EHM_AUDIT_UNIFORM / _PER_LEAF
 EHM_COMPILE_SPINE_ROOTS = 1     # ehm_compiled_create_opts
@@ -337,6 +338,8 @@ def load(build_if_missing=True):
                                          ctypes.POINTER(CertifyLeaves)]
     lib.ehm_compiled_cells.argtypes = [vp, vp, i64, vp, vp, vp, vp]
     lib.ehm_certify_last_error.restype = ctypes.c_char_p
+    lib.ehm_compiled_reduce.argtypes = [vp, vp, vp, vp, ctypes.POINTER(vp), vp, vp, vp, vp]
+    lib.ehm_reduce_last_error.restype = ctypes.c_char_p
     lib.ehm_explicit_set_costs.argtypes = [vp, vp, vp]
     lib.ehm_explicit_sample.argtypes = [vp, ctypes.POINTER(AuditOpts), vp, vp]
     lib.ehm_explicit_audit.argtypes = [vp, vp, ctypes.POINTER(AuditOpts),
@@ -436,7 +439,7 @@ def load(build_if_missing=True):
         if name not in ('ehm_last_error', 'ehm_version', 'ehm_stream',
                         'ehm_explicit_last_error', 'ehm_implicit_last_error',
                         'ehm_compiled_last_error', 'ehm_applied_last_error',
-                        'ehm_certify_last_error'):
+                        'ehm_certify_last_error', 'ehm_reduce_last_error'):
             fn.restype = i32
     lib.ehm_search_last_error.restype = ctypes.c_char_p
     lib.ehm_search_create.argtypes = [i32, i32, i32, ctypes.POINTER(vp)]

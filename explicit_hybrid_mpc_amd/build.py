@@ -7,7 +7,8 @@ Objects: ``ehm_capi.hip`` (C-ABI, host orchestration, generation-1 kernels),
 ``ehm_explicit.hip`` and ``ehm_implicit.hip`` (the closed loops around the two laws),
 ``ehm_audit.hip`` (the sampled audit of the explicit law), ``ehm_applied.hip`` (the audit of a
 law by the cost of the input it applies), ``ehm_certify.hip`` (the leaf cells of a compiled law, the
-inputs at their vertices and the certificate leaf by leaf),
+inputs at their vertices and the certificate leaf by leaf), ``ehm_reduce.hip`` (merging the leaves
+of a compiled law that apply one affine map),
 ``ehm_compiled.hip`` (the explicit law compiled into a hyperplane tree) and
 ``ehm_compiled32.hip`` (the kernels of its single-precision form), one
 instance of ``ehm_k2.hip`` per (column capacity NP, row slots) pair -- the solver keeps a
@@ -147,6 +148,7 @@ def _objects():
              []),
             (os.path.join(OBJ_DIR, 'ehm_certify.o'), os.path.join(SRC_DIR, 'ehm_certify.hip'),
              []),
+            (os.path.join(OBJ_DIR, 'ehm_reduce.o'), os.path.join(SRC_DIR, 'ehm_reduce.hip'), []),
             (os.path.join(OBJ_DIR, 'ehm_compiled.o'), os.path.join(SRC_DIR, 'ehm_compiled.hip'),
              []),
             (os.path.join(OBJ_DIR, 'ehm_compiled32.o'),
@@ -192,7 +194,7 @@ def is_stale():
     srcs = [os.path.join(SRC_DIR, f)
             for f in ('ehm_capi.hip', 'ehm_k2.hip', 'ehm_k3.hip', 'ehm_k4.hip', 'ehm_kp.hip',
                       'ehm_explicit.hip', 'ehm_implicit.hip', 'ehm_audit.hip', 'ehm_applied.hip',
-                      'ehm_certify.hip', 'ehm_compiled.hip', 'ehm_compiled32.hip')]
+                      'ehm_certify.hip', 'ehm_reduce.hip', 'ehm_compiled.hip', 'ehm_compiled32.hip')]
     return max([_dep_mtime()] + [os.path.getmtime(s)
                                  for s in srcs + SEARCH_DEPS + FRONTIER_DEPS]) > t
 

@@ -60,6 +60,12 @@ on a whole leaf, where the audit speaks of samples, starts from them.
 
 is that statement: the contract of ``audit`` proved on every leaf the test can close, from the
 costs of the vertex inputs (convexity of the fixed-commutation cost along the leaf's affine map).
+
+    small = law.reduce()                          # or ExplicitMPC.compile(reduce=True)
+
+merges the leaves that apply one affine map (csrc/ehm_reduce.hip): a new law of the
+same precision and file format whose input is within ``tol`` of this law's at every state of
+every cell of this law; ``small.reduction`` holds what it saved.
 """
 
 import ctypes
@@ -215,6 +221,7 @@ class CompiledLaw:
     _rollout_plant = None       # the plant the device holds (set_plant)
     _leaf_node = None
     flushed = None              # to_single(flush=True): the counts of the values set to zero
+    reduction = None            # reduce(): what the reduction this law came from saved
     _root_cells = None          # audit: the roots as the sampler's cells (built on first use)
     _input_scale = None         # audit: the default input_tol
 
@@ -282,6 +289,82 @@ class CompiledLaw:
         if self.leaf_mode is not None:
             law.set_leaf_modes(self.leaf_mode)
         return law
+
+    def reduce(self, tol=None, return_map=False):
+        """
+        The law with every subtree whose leaves all apply one affine map within ``tol`` replaced
+        by one leaf: a new, independent ``CompiledLaw`` of the same precision and file format
+        (ehm_compiled_reduce).  The representative of an internal record is its
+        leftmost leaf; the record is mergeable iff every leaf below it has a cell (``cells``), the
+        representative's ``leaf_mode`` (where the law holds leaf modes) and, at each vertex of its
+        OWN cell and for each input c, an input within ``tol[c]`` of the representative's map
+        there, both maps in the law's own arithmetic; a NaN never passes.  The topmost mergeable
+        records become leaves.  Both maps are affine, so the new law's input is within ``tol`` of
+        this law's at every state of every cell of this law -- against the original leaves, not
+        against a merged neighbour, so the bound does not grow with the levels merged.  It is per
+        call: a second ``reduce`` of the result may merge further, and its bound adds to the first.
+        A merged leaf takes the record, the ``leaf_mode`` and the ``leaf_node`` of its
+        representative: ``leaf_node`` of a merged leaf is the representative's source id, not the
+        id of a source node that spans the merged cell.
+        ``tol``: a scalar or [n_u], finite and >= 0; None: ``applied.default_input_tol`` of the
+        leaf records' u_0, the relaxation ``audit`` and ``certify`` grant an input; 0 merges only
+        where the computed difference is exactly zero.  A law in which nothing merges comes back
+        as an equal, independent copy.  ``mpc``, the leaf modes and ``flushed`` carry over, as in
+        ``to_single``.  The new law's ``reduction`` is a dict of n_leaf_before, n_leaf_after,
+        n_int_before, n_int_after, bytes_before, bytes_after, tol, max_deviation (the largest
+        difference that passed the test: an upper bound of the deviation at the cells' vertices)
+        and seconds.  ``return_map=True``: returns (law, leaf_of), leaf_of int32 [n_leaf_before]
+        the new leaf record of every original one.  ``EhmError`` (EHM_E_INVALID) for a law with
+        test nodes (``compile(spine='roots')`` has none), a ``tol`` that is negative or not
+        finite, a ``leaf_mode`` of the wrong length, and a law whose own arrays would not pass
+        the import check (``validate_arrays``), which the new law goes through.  Certify before
+        reducing: a certificate belongs to the function, and ``certify`` on the reduced law tests
+        the larger cells.
+        """
+        from . import applied
+        if not getattr(self, '_handle', None):
+            raise ValueError('the law is closed')
+        if self._h['n_test'] > 0:
+            raise _capi.EhmError(_capi.EHM_E_INVALID, 'the law has %d test nodes: its cells do not '
+                                 "follow from its planes -- compile(spine='roots') has none" %
+                                 self._h['n_test'])
+        n_leaf = self._h['n_leaf']
+        if tol is None:
+            if self._input_scale is None:
+                u0 = self.array('leaf_rec')[:, self.p:self.p + self.n_u]
+                self._input_scale = applied.default_input_tol(u0)
+            tol = self._input_scale
+        tol = np.asarray(tol, dtype=np.float64)
+        if tol.ndim > 1 or (tol.ndim == 1 and tol.size != self.n_u):
+            raise ValueError('tol must be a scalar or [%d]' % self.n_u)
+        tol = np.ascontiguousarray(np.broadcast_to(tol, (self.n_u,)))
+        if not (np.isfinite(tol).all() and (tol >= 0.).all()):
+            raise _capi.EhmError(_capi.EHM_E_INVALID, 'reduce: tol must be finite and >= 0, not '
+                                 '%s' % tol)
+        modes = None if self.leaf_mode is None else check_leaf_mode(self.leaf_mode, n_leaf)
+        if self._root_cells is None:
+            self._root_cells = applied.root_cells(self)
+        roots = self._root_cells['vertices']
+        handle = ctypes.c_void_p()
+        modes_out = None if modes is None else np.empty(n_leaf, dtype=np.int32)
+        leaf_of = np.empty(n_leaf, dtype=np.int32) if return_map else None
+        counts = np.zeros(4, dtype=np.int64)
+        stats = np.zeros(2)
+        rc = self._lib.ehm_compiled_reduce(self._handle, ptr(roots), ptr(tol), ptr(modes),
+                                           ctypes.byref(handle), ptr(modes_out), ptr(leaf_of),
+                                           ptr(counts), ptr(stats))
+        if rc != _capi.EHM_OK:
+            raise _capi.EhmError(rc, self._lib.ehm_reduce_last_error().decode('utf-8', 'replace'))
+        law = type(self)(handle, self.device, self.compile_seconds, dtype=self.dtype)
+        law.flushed = self.flushed
+        law.mpc = self.mpc
+        if modes is not None:
+            law.set_leaf_modes(modes_out[:int(counts[1])])
+        law.reduction = dict(n_leaf_before=int(counts[0]), n_leaf_after=int(counts[1]),
+                             n_int_before=int(counts[2]), n_int_after=int(counts[3]),
+                             bytes_before=self._bytes, bytes_after=law._bytes, tol=tol.copy(),
+                             max_deviation=float(stats[0]), seconds=float(stats[1]))
+        return (law, leaf_of) if return_map else law
 
     @classmethod
     def load(cls, path, device=0):

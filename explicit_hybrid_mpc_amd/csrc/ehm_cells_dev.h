@@ -1,0 +1,187 @@
+// What ehm_certify.hip and ehm_reduce.hip share on the device: the parent
+// table of a compiled law, the cell of a leaf rebuilt from the law's own arrays with the cell in
+// registers, and the leaf's affine map at a vertex in the law's own arithmetic.  The rules
+// themselves are plain C++ in ehm_certify_host.h.  Every translation unit that includes this gets
+// its own copy (unnamed namespace), as of ehm_compiled_dev.h.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <type_traits>
+
+#include "ehm_certify_host.h"
+#include "ehm_compiled_dev.h"
+#include "ehm_compiled_view.h"
+#include "ehm_host.h"
+
+namespace {
+
+__global__ void k_certify_roots(long long n_roots, const int32_t* __restrict__ root_entry,
+                                ehm_cert::Parents P) {
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_roots) return;
+    ehm_cert::link_root(P, (int32_t)r, root_entry[r]);
+}
+
+template <class T>
+__global__ void k_certify_parents(long long n_int, int p, int node_stride,
+                                  const T* __restrict__ node, ehm_cert::Parents P) {
+    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_int) return;
+    int32_t left, right;
+    ehm_cert::children_of(node + (size_t)k * node_stride, p, left, right);
+    ehm_cert::link_children(P, (int32_t)k, left, right);
+}
+
+inline unsigned cells_blocks_of(long long n, int block) {
+    return (unsigned)((n + block - 1) / block);
+}
+
+// the parent table of a law on the device
+struct ParentTable {
+    DevBuf node, node_side, leaf, leaf_side;
+    ehm_cert::Parents view() const {
+        return ehm_cert::Parents{node.as<int32_t>(), node_side.as<uint8_t>(), leaf.as<int32_t>(),
+                                 leaf_side.as<uint8_t>()};
+    }
+};
+
+inline hipError_t make_parents(const ehm_compiled_view& v, hipStream_t stream, ParentTable& T) {
+#define EHM_CELLS_TRY(expr)                \
+    do {                                   \
+        const hipError_t e_ = (expr);      \
+        if (e_ != hipSuccess) return e_;   \
+    } while (0)
+    EHM_CELLS_TRY(T.node.alloc((size_t)v.n_int * sizeof(int32_t)));
+    EHM_CELLS_TRY(T.node_side.alloc((size_t)v.n_int));
+    EHM_CELLS_TRY(T.leaf.alloc((size_t)v.n_leaf * sizeof(int32_t)));
+    EHM_CELLS_TRY(T.leaf_side.alloc((size_t)v.n_leaf));
+    if (v.n_int) {
+        EHM_CELLS_TRY(hipMemsetD32Async((hipDeviceptr_t)T.node.ptr, EHM_CERT_UNREACHED,
+                                        (size_t)v.n_int, stream));
+        EHM_CELLS_TRY(hipMemsetAsync(T.node_side.ptr, 0, (size_t)v.n_int, stream));
+    }
+    EHM_CELLS_TRY(hipMemsetD32Async((hipDeviceptr_t)T.leaf.ptr, EHM_CERT_UNREACHED,
+                                    (size_t)v.n_leaf, stream));
+    EHM_CELLS_TRY(hipMemsetAsync(T.leaf_side.ptr, 0, (size_t)v.n_leaf, stream));
+    const ehm_cert::Parents P = T.view();
+    if (v.n_int) {
+        if (v.single)
+            hipLaunchKernelGGL(k_certify_parents<float>, dim3(cells_blocks_of(v.n_int, 256)),
+                               dim3(256), 0, stream, v.n_int, v.p, v.node_stride,
+                               static_cast<const float*>(v.node), P);
+        else
+            hipLaunchKernelGGL(k_certify_parents<double>, dim3(cells_blocks_of(v.n_int, 256)),
+                               dim3(256), 0, stream, v.n_int, v.p, v.node_stride,
+                               static_cast<const double*>(v.node), P);
+        EHM_CELLS_TRY(hipGetLastError());
+    }
+    // the roots last: an entry is a root whatever else names it
+    hipLaunchKernelGGL(k_certify_roots, dim3(cells_blocks_of(v.n_roots, 256)), dim3(256), 0,
+                       stream, v.n_roots, v.root_entry, P);
+    EHM_CELLS_TRY(hipGetLastError());
+#undef EHM_CELLS_TRY
+    return hipSuccess;
+}
+
+// The cell of leaf record l into V [(P+1) P], statically indexed throughout: up to the root through
+// the parent table, the turns in a set of 256 bits; down from the root's vertices, at every plane
+// node s_i = a . v_i + b in double, the one vertex above 0.5 and the one below -0.5 the ends of the
+// bisected edge, their midpoint (v + w) / 2 in place of the negative-side vertex in the left child
+// and of the positive-side one in the right child.  False (V is then not a cell) for a leaf no root
+// reaches, one deeper than the set holds and one whose path holds a node that is no bisection.
+template <class T, int P>
+__device__ __forceinline__ bool leaf_cell(const ehm_cert::Parents& par, const T* __restrict__ node,
+                                          const int32_t* __restrict__ root_entry,
+                                          const double* __restrict__ root_vertices, int32_t l,
+                                          double (&V)[(P + 1) * P]) {
+#pragma clang fp contract(off)
+    constexpr bool SINGLE = std::is_same<T, float>::value;
+    constexpr int NS = SINGLE ? (P <= 5 ? 8 : 16) : (P <= 6 ? 8 : 16);
+    ehm_cert::TurnSet turns;
+    int32_t root = 0;
+    bool ok = ehm_cert::walk_up(par, l, turns, root);
+#pragma unroll
+    for (int e = 0; e < (P + 1) * P; ++e) V[e] = NAN;
+    if (ok) {
+        const double* rv = root_vertices + (size_t)root * (P + 1) * P;
+#pragma unroll
+        for (int e = 0; e < (P + 1) * P; ++e) V[e] = rv[e];
+        int32_t k = root_entry[root];
+        while (turns.depth > 0) {
+            if (k < 0) {
+                ok = false;
+                break;
+            }
+            const T* rec = node + (size_t)k * NS;
+            double a[P + 1];
+#pragma unroll
+            for (int c = 0; c <= P; ++c) a[c] = (double)rec[c];
+            double s[P + 1];
+#pragma unroll
+            for (int i = 0; i <= P; ++i) {
+                double t = 0.0;
+#pragma unroll
+                for (int c = 0; c < P; ++c) t = t + a[c] * V[i * P + c];
+                s[i] = t + a[P];
+            }
+            int pos, neg;
+            if (!ehm_cert::bisected_edge<P + 1>(s, pos, neg)) {
+                ok = false;
+                break;
+            }
+            int32_t left, right;
+            ehm_cert::children_of(rec, P, left, right);
+            const int turn = turns.pop();
+            const int gone = turn ? pos : neg;
+#pragma unroll
+            for (int c = 0; c < P; ++c) {
+                double vp = 0.0, vn = 0.0;
+#pragma unroll
+                for (int i = 0; i <= P; ++i) {
+                    vp = i == pos ? V[i * P + c] : vp;
+                    vn = i == neg ? V[i * P + c] : vn;
+                }
+                const double mid = (vn + vp) / 2.0;
+#pragma unroll
+                for (int i = 0; i <= P; ++i) V[i * P + c] = i == gone ? mid : V[i * P + c];
+            }
+            k = turn ? right : left;
+        }
+        ok = ok && k == ~l;
+    }
+    return ok;
+}
+
+// Component c of the map of leaf record lr at the point v [P] in the law's own arithmetic: the
+// leaf-map part of law_input (ehm_compiled_dev.h).  A double law: d = v - v_0,
+// u_c = u_0c + ((0 + K_c0 d_0) + .. + K_c(P-1) d_(P-1)) in double; a single law: xs = (float) v and
+// leaf_offset32 / leaf_input32, widened.
+template <int P>
+__device__ __forceinline__ double leaf_map_at(const double* __restrict__ lr, int n_u, int c,
+                                              const double* v) {
+#pragma clang fp contract(off)
+    double d[P];
+#pragma unroll
+    for (int j = 0; j < P; ++j) d[j] = v[j] - lr[j];
+    const double* Kc = lr + P + n_u;
+    double w = 0.0;
+#pragma unroll
+    for (int j = 0; j < P; ++j) w = w + Kc[c * P + j] * d[j];
+    return lr[P + c] + w;
+}
+
+template <int P>
+__device__ __forceinline__ double leaf_map_at(const float* __restrict__ lr, int n_u, int c,
+                                              const double* v) {
+#pragma clang fp contract(off)
+    float xs[P], d[P];
+#pragma unroll
+    for (int j = 0; j < P; ++j) xs[j] = (float)v[j];
+    leaf_offset32<P>(lr, xs, d);
+    return leaf_input32<P>(lr, n_u, c, d);
+}
+
+}  // namespace

@@ -27,7 +27,9 @@
 // multi-commutation oracle of ehm_capi.hip; a chunk's rows make their round trips through the host,
 // which the LP batches dwarf.
 //
-// The cell lives in registers: (P + 1) P <= 72 doubles, indexed statically throughout.  Every
+// The parent table, the cell of a leaf and the leaf's map at a vertex are ehm_cells_dev.h's, which
+// ehm_reduce.hip shares.  The cell lives in registers: (P + 1) P <= 72 doubles, indexed statically
+// throughout.  Every
 // operation a result depends on runs under fp contract(off) in a fixed order
 // (tests/certify_cpu.py is the numpy mirror).
 #include <hip/hip_runtime.h>
@@ -44,10 +46,7 @@
 #include <vector>
 
 #include "../../include/ehmpc.h"
-#include "ehm_certify_host.h"
-#include "ehm_compiled_dev.h"
-#include "ehm_compiled_view.h"
-#include "ehm_host.h"
+#include "ehm_cells_dev.h"
 
 #define EHM_CERT_BLOCK 64
 #define EHM_CERT_CHUNK 65536        // leaves per pass of ehm_compiled_cells
@@ -61,23 +60,6 @@ namespace {
 
 using ehm_cert::Parents;
 using ehm_cert::TurnSet;
-
-__global__ void k_certify_roots(long long n_roots, const int32_t* __restrict__ root_entry,
-                                Parents P) {
-    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_roots) return;
-    ehm_cert::link_root(P, (int32_t)r, root_entry[r]);
-}
-
-template <class T>
-__global__ void k_certify_parents(long long n_int, int p, int node_stride,
-                                  const T* __restrict__ node, Parents P) {
-    const long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n_int) return;
-    int32_t left, right;
-    ehm_cert::children_of(node + (size_t)k * node_stride, p, left, right);
-    ehm_cert::link_children(P, (int32_t)k, left, right);
-}
 
 template <class T>
 struct CellArgs {
@@ -98,64 +80,11 @@ struct CellArgs {
 template <class T, int P>
 __global__ __launch_bounds__(EHM_CERT_BLOCK) void k_certify_cells(CellArgs<T> A) {
 #pragma clang fp contract(off)
-    constexpr bool SINGLE = std::is_same<T, float>::value;
-    constexpr int NS = SINGLE ? (P <= 5 ? 8 : 16) : (P <= 6 ? 8 : 16);
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= A.n) return;
     const int32_t l = A.leaf_ids ? A.leaf_ids[q] : (int32_t)(A.first + q);
-    TurnSet turns;
-    int32_t root = 0;
-    bool ok = ehm_cert::walk_up(A.par, l, turns, root);
     double V[(P + 1) * P];
-#pragma unroll
-    for (int e = 0; e < (P + 1) * P; ++e) V[e] = NAN;
-    if (ok) {
-        const double* rv = A.root_vertices + (size_t)root * (P + 1) * P;
-#pragma unroll
-        for (int e = 0; e < (P + 1) * P; ++e) V[e] = rv[e];
-        int32_t k = A.root_entry[root];
-        while (turns.depth > 0) {
-            if (k < 0) {
-                ok = false;
-                break;
-            }
-            const T* rec = A.node + (size_t)k * NS;
-            double a[P + 1];
-#pragma unroll
-            for (int c = 0; c <= P; ++c) a[c] = (double)rec[c];
-            double s[P + 1];
-#pragma unroll
-            for (int i = 0; i <= P; ++i) {
-                double t = 0.0;
-#pragma unroll
-                for (int c = 0; c < P; ++c) t = t + a[c] * V[i * P + c];
-                s[i] = t + a[P];
-            }
-            int pos, neg;
-            if (!ehm_cert::bisected_edge<P + 1>(s, pos, neg)) {
-                ok = false;
-                break;
-            }
-            int32_t left, right;
-            ehm_cert::children_of(rec, P, left, right);
-            const int turn = turns.pop();
-            const int gone = turn ? pos : neg;
-#pragma unroll
-            for (int c = 0; c < P; ++c) {
-                double vp = 0.0, vn = 0.0;
-#pragma unroll
-                for (int i = 0; i <= P; ++i) {
-                    vp = i == pos ? V[i * P + c] : vp;
-                    vn = i == neg ? V[i * P + c] : vn;
-                }
-                const double mid = (vn + vp) / 2.0;
-#pragma unroll
-                for (int i = 0; i <= P; ++i) V[i * P + c] = i == gone ? mid : V[i * P + c];
-            }
-            k = turn ? right : left;
-        }
-        ok = ok && k == ~l;
-    }
+    const bool ok = leaf_cell<T, P>(A.par, A.node, A.root_entry, A.root_vertices, l, V);
     double* out = A.vertices + (size_t)q * (P + 1) * P;
 #pragma unroll
     for (int e = 0; e < (P + 1) * P; ++e) out[e] = ok ? V[e] : NAN;
@@ -170,26 +99,8 @@ __global__ __launch_bounds__(EHM_CERT_BLOCK) void k_certify_cells(CellArgs<T> A)
     }
     const T* lr = A.leaf_rec + (size_t)l * A.leaf_stride;
 #pragma unroll
-    for (int i = 0; i <= P; ++i) {
-        if constexpr (SINGLE) {
-            float xs[P], d[P];
-#pragma unroll
-            for (int c = 0; c < P; ++c) xs[c] = (float)V[i * P + c];
-            leaf_offset32<P>(lr, xs, d);
-            for (int c = 0; c < n_u; ++c) ub[i * n_u + c] = leaf_input32<P>(lr, n_u, c, d);
-        } else {
-            double d[P];
-#pragma unroll
-            for (int c = 0; c < P; ++c) d[c] = V[i * P + c] - lr[c];
-            const double* Kc = lr + P + n_u;
-            for (int c = 0; c < n_u; ++c) {
-                double w = 0.0;
-#pragma unroll
-                for (int j = 0; j < P; ++j) w = w + Kc[c * P + j] * d[j];
-                ub[i * n_u + c] = lr[P + c] + w;
-            }
-        }
-    }
+    for (int i = 0; i <= P; ++i)
+        for (int c = 0; c < n_u; ++c) ub[i * n_u + c] = leaf_map_at<P>(lr, n_u, c, &V[i * P]);
 }
 
 // theta' = (v_i, ubar_i) and konst_i = 0 + cost_u[0] ubar_i0 + .. of every (leaf, vertex) pair with a
@@ -292,51 +203,10 @@ int zfail(int code, const char* fmt, ...) {
             return zfail(EHM_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
     } while (0)
 
-unsigned blocks_of(long long n, int block) { return (unsigned)((n + block - 1) / block); }
+unsigned blocks_of(long long n, int block) { return cells_blocks_of(n, block); }
 
 double wall_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-}
-
-// the parent table of a law on the device
-struct ParentTable {
-    DevBuf node, node_side, leaf, leaf_side;
-    Parents view() const {
-        return Parents{node.as<int32_t>(), node_side.as<uint8_t>(), leaf.as<int32_t>(),
-                       leaf_side.as<uint8_t>()};
-    }
-};
-
-int make_parents(const ehm_compiled_view& v, hipStream_t stream, ParentTable& T) {
-    Z_TRY(T.node.alloc((size_t)v.n_int * sizeof(int32_t)));
-    Z_TRY(T.node_side.alloc((size_t)v.n_int));
-    Z_TRY(T.leaf.alloc((size_t)v.n_leaf * sizeof(int32_t)));
-    Z_TRY(T.leaf_side.alloc((size_t)v.n_leaf));
-    if (v.n_int) {
-        Z_TRY(hipMemsetD32Async((hipDeviceptr_t)T.node.ptr, EHM_CERT_UNREACHED, (size_t)v.n_int,
-                                stream));
-        Z_TRY(hipMemsetAsync(T.node_side.ptr, 0, (size_t)v.n_int, stream));
-    }
-    Z_TRY(hipMemsetD32Async((hipDeviceptr_t)T.leaf.ptr, EHM_CERT_UNREACHED, (size_t)v.n_leaf,
-                            stream));
-    Z_TRY(hipMemsetAsync(T.leaf_side.ptr, 0, (size_t)v.n_leaf, stream));
-    const Parents P = T.view();
-    if (v.n_int) {
-        if (v.single)
-            hipLaunchKernelGGL(k_certify_parents<float>, dim3(blocks_of(v.n_int, 256)), dim3(256),
-                               0, stream, v.n_int, v.p, v.node_stride,
-                               static_cast<const float*>(v.node), P);
-        else
-            hipLaunchKernelGGL(k_certify_parents<double>, dim3(blocks_of(v.n_int, 256)), dim3(256),
-                               0, stream, v.n_int, v.p, v.node_stride,
-                               static_cast<const double*>(v.node), P);
-        Z_TRY(hipGetLastError());
-    }
-    // the roots last: an entry is a root whatever else names it
-    hipLaunchKernelGGL(k_certify_roots, dim3(blocks_of(v.n_roots, 256)), dim3(256), 0, stream,
-                       v.n_roots, v.root_entry, P);
-    Z_TRY(hipGetLastError());
-    return EHM_OK;
 }
 
 // what both entry points check of a law and of the caller's leaves
@@ -476,8 +346,7 @@ int ehm_compiled_cells(ehm_compiled* law, const double* root_vertices, int64_t n
     const int p = v.p, n_u = v.n_u;
     const size_t cell = (size_t)(p + 1) * p;
     ParentTable T;
-    rc = make_parents(v, stream, T);
-    if (rc) return rc;
+    Z_TRY(make_parents(v, stream, T));
     DevBuf droots, dids, dvert, dubar, dstatus;
     Z_TRY(droots.upload(root_vertices, (size_t)v.n_roots * cell * sizeof(double)));
     const size_t cap = (size_t)std::min<int64_t>(n, EHM_CERT_CHUNK);
@@ -540,8 +409,7 @@ int ehm_compiled_certify(ehm_compiled* law, ehm_problem* oracle, ehm_problem* ap
     const int p = v.p, n_u = v.n_u, nv = p + 1, pp = p + n_u, nd = o->n_delta;
     const size_t cell = (size_t)nv * p;
     ParentTable T;
-    rc = make_parents(v, stream, T);
-    if (rc) return rc;
+    Z_TRY(make_parents(v, stream, T));
     const long long chunk = o->chunk > 0 ? o->chunk : EHM_CERT_PASS;
     const size_t cap = (size_t)std::min<long long>(chunk, o->n);
     const unsigned max_blocks = blocks_of((long long)cap, EHM_CERT_JUDGE_BLOCK);

@@ -533,6 +533,7 @@ void ehm_compiled_get_view(const ehm_compiled* C, ehm_compiled_view* out) {
     out->single = C->single;
     out->node = C->node.ptr;
     out->leaf_rec = C->leaf_rec.ptr;
+    out->leaf_node = C->leaf_node.as<const int32_t>();
     out->root_entry = C->root_entry.as<const int32_t>();
     out->p = (int)C->h[H_P];
     out->n_u = (int)C->h[H_NU];
@@ -605,6 +606,54 @@ int export_law(ehm_compiled* C, bool single, void* node, void* leaf_rec, int32_t
 }
 
 }  // namespace
+
+int ehm_compiled_adopt(const ehm_compiled* like, int64_t n_int, int64_t n_leaf, DevBuf& node,
+                       DevBuf& leaf_rec, DevBuf& leaf_node, DevBuf& root_entry,
+                       ehm_compiled** out) {
+    if (!like || !out) return cfail(EHM_E_INVALID, "adopt: bad argument");
+    *out = nullptr;
+    LawPtr C(new ehm_compiled(), ehm_compiled_destroy);
+    C->device = like->device;
+    C->single = like->single;
+    std::memcpy(C->h, like->h, sizeof C->h);
+    C->h[H_INT] = n_int;
+    C->h[H_LEAF] = n_leaf;
+    C->source_bytes = like->source_bytes;
+    C_TRY(hipSetDevice(C->device));
+    C_TRY(C->stream.create());
+    C->node = std::move(node);
+    C->leaf_rec = std::move(leaf_rec);
+    C->leaf_node = std::move(leaf_node);
+    C->root_entry = std::move(root_entry);
+    C_TRY(C->test_rec.alloc(0));
+    C_TRY(C->root_rec.alloc(C->root_bytes()));
+    C_TRY(hipMemcpy(C->root_rec.ptr, like->root_rec.ptr, C->root_bytes(),
+                    hipMemcpyDeviceToDevice));
+    if (C->nbr_bytes()) {
+        C_TRY(C->nbr.alloc(C->nbr_bytes()));
+        C_TRY(hipMemcpy(C->nbr.ptr, like->nbr.ptr, C->nbr_bytes(), hipMemcpyDeviceToDevice));
+    }
+    // the check of an import, on a host copy of what the device now holds
+    std::vector<char> h_node(C->node_bytes()), h_leaf(C->leaf_bytes());
+    std::vector<int32_t> h_leaf_node((size_t)n_leaf), h_entry((size_t)C->h[H_ROOTS]),
+        h_nbr(C->nbr_bytes() / sizeof(int32_t));
+    std::vector<double> h_root(C->root_bytes() / sizeof(double));
+    const int rc0 = export_law(C.get(), C->single, h_node.data(), h_leaf.data(),
+                               h_leaf_node.data(), nullptr, h_root.data(), h_entry.data(),
+                               h_nbr.data());
+    if (rc0 != EHM_OK) return rc0;
+    const int rc = C->single
+        ? validate(C->h, reinterpret_cast<const float*>(h_node.data()),
+                   reinterpret_cast<const float*>(h_leaf.data()), h_leaf_node.data(),
+                   (const double*)nullptr, h_root.data(), h_entry.data(), h_nbr.data())
+        : validate(C->h, reinterpret_cast<const double*>(h_node.data()),
+                   reinterpret_cast<const double*>(h_leaf.data()), h_leaf_node.data(),
+                   (const double*)nullptr, h_root.data(), h_entry.data(), h_nbr.data());
+    if (rc != EHM_OK) return rc;
+    C->bind();
+    *out = C.release();
+    return EHM_OK;
+}
 
 extern "C" {
 

@@ -1,5 +1,5 @@
-// What ehm_certify.hip reads of an ehm_compiled handle (ehm_compiled.hip owns the struct): device
-// pointers that stay the handle's, valid while it lives.  Not exported.
+// What ehm_certify.hip and ehm_reduce.hip read of an ehm_compiled handle (ehm_compiled.hip owns the
+// struct): device pointers that stay the handle's, valid while it lives.  Not exported.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -7,12 +7,14 @@
 #include <cstdint>
 
 #include "../../include/ehmpc.h"
+#include "ehm_host.h"
 
 struct ehm_compiled_view {
     int device;
     bool single;                // node and leaf_rec hold floats
     const void* node;           // [n_int][node_stride] of the law's scalar
     const void* leaf_rec;       // [n_leaf][leaf_stride] of the law's scalar
+    const int32_t* leaf_node;   // [n_leaf]
     const int32_t* root_entry;  // [n_roots]
     int p, n_u, node_stride, leaf_stride;
     long long n_roots, n_int, n_leaf, n_test;
@@ -20,3 +22,11 @@ struct ehm_compiled_view {
 };
 
 void ehm_compiled_get_view(const ehm_compiled* C, ehm_compiled_view* out);
+
+// A new law on the device of `like` with n_int internal and n_leaf leaf records of like's scalar
+// and strides (ehm_reduce.hip): it takes over the four buffers, copies like's root records and
+// adjacency table, and is checked as ehm_compiled_import checks a file's arrays (on a host copy)
+// before it is returned.  Errors through ehm_compiled_last_error.
+int ehm_compiled_adopt(const ehm_compiled* like, int64_t n_int, int64_t n_leaf, DevBuf& node,
+                       DevBuf& leaf_rec, DevBuf& leaf_node, DevBuf& root_entry,
+                       ehm_compiled** out);

@@ -246,7 +246,7 @@ class ExplicitMPC:
                                              ptr(left), ptr(right), ptr(vertices), ptr(vinput),
                                              ctypes.byref(self._handle)))
 
-    def compile(self, dtype=np.float64, spine='tests', flush=False):
+    def compile(self, dtype=np.float64, spine='tests', flush=False, reduce=None):
         """The law as a ``compiled.CompiledLaw``: one hyperplane per internal node, one affine map
         per leaf, compiled on the device.  It holds its own arrays and outlives this object.  For
         its rollouts it remembers ``mpc`` (the default plant) and, where ``mpc`` tells the step-0
@@ -254,7 +254,9 @@ class ExplicitMPC:
         ``dtype=np.float32``: the law in single precision (``CompiledLaw.to_single``), with
         ``flush=True`` its values below the normal range of a float set to zero instead of
         refused.  ``spine='roots'``: the data-less spine of a nested tree becomes the law's root
-        table instead of test nodes (``CompiledLaw.compile``)."""
+        table instead of test nodes (``CompiledLaw.compile``).  ``reduce``: a tolerance (a scalar
+        or [n_u]), or True for the default one: the law with the leaves that apply one affine map
+        within it merged (``CompiledLaw.reduce``), in the precision asked for."""
         from .compiled import CompiledLaw
         dtype = np.dtype(dtype).type
         if dtype not in (np.float64, np.float32):
@@ -275,6 +277,12 @@ class ExplicitMPC:
                 law = double.to_single(flush=bool(flush))
             finally:
                 double.close()
+        if reduce is not None and reduce is not False:
+            full = law
+            try:
+                law = full.reduce(tol=None if reduce is True else reduce)
+            finally:
+                full.close()
         return law
 
     def close(self):

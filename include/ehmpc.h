@@ -948,6 +948,36 @@ int ehm_compiled_certify(ehm_compiled* law, ehm_problem* oracle, ehm_problem* ap
 /* ehm_abi_sizes for ehm_certify_opts, ehm_certify_result, ehm_certify_leaves, in this order. */
 int ehm_certify_abi_sizes(int64_t* sizes, int32_t n);
 
+/* ---- merging the leaves that apply one affine map (csrc/ehm_reduce.hip) ----------
+ *
+ * A new, independent law of the same precision and format in which every subtree whose leaves all
+ * apply one affine map within tol is one leaf.  The REPRESENTATIVE of an internal record is its
+ * leftmost leaf.  An internal record is MERGEABLE iff every leaf l below it has a cell
+ * (ehm_compiled_cells: EHM_CELL_OK), the leaf mode of the representative (when leaf_mode is given)
+ * and, at each of the p + 1 vertices v_i of l's OWN cell and for each input c,
+ * !(|u_rep(v_i)_c - u_l(v_i)_c| <= tol[c]) false -- both maps in the law's own arithmetic as ubar of
+ * ehm_compiled_cells, the difference in double; a difference that is NaN never passes.  Both maps are
+ * affine, so the reduced law is within tol of the original at every state of every original cell;
+ * the comparison is with the original leaves, so the bound does not grow with the levels merged.
+ * The new leaves are the topmost mergeable records on each root path (a root entry may become a
+ * leaf); a merged leaf takes the record, the leaf_node and the leaf_mode of its representative.
+ * Surviving records keep their order (children still come after their parents); records no root
+ * reaches are kept as they are; root_rec and nbr are copied.  The new law is checked as
+ * ehm_compiled_import checks a file's arrays before it is returned.
+ * root_vertices as for ehm_compiled_cells; tol [n_u], finite and >= 0 (0 merges only where the
+ * computed difference is exactly zero); leaf_mode [n_leaf] or NULL.  Outputs: *out; leaf_mode_out
+ * [n_leaf of the new law, at most n_leaf] (may be NULL; written only with leaf_mode); leaf_of [n_leaf]
+ * (may be NULL) the new leaf record of every original one; counts [4] = leaves before and after,
+ * internal records before and after; stats [2] = the largest difference that passed the test at any
+ * record (an upper bound of the reduced law's deviation at the cells' vertices, <= tol), seconds.
+ * EHM_E_INVALID for a law with test nodes, a tol that is negative or not finite, and a law whose
+ * records form no forest (a record named by two parents or roots).  Errors through
+ * ehm_reduce_last_error. */
+int ehm_compiled_reduce(ehm_compiled* law, const double* root_vertices, const double* tol,
+                        const int32_t* leaf_mode, ehm_compiled** out, int32_t* leaf_mode_out,
+                        int32_t* leaf_of, int64_t* counts, double* stats);
+const char* ehm_reduce_last_error(void);
+
 /* ---- closed-loop simulation under the COMPILED law (csrc/ehm_compiled.hip) -------
  *
  * The entry points of the explicit law's rollout, argument for argument, on a compiled law -- also
