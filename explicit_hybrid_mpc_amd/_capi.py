@@ -62,6 +62,7 @@ EXPORTED = [
     'ehm_compiled_cells', 'ehm_certify_last_error', 'ehm_compiled_certify',
     'ehm_certify_abi_sizes',
     'ehm_compiled_reduce', 'ehm_reduce_last_error',
+    'ehm_compiled_successors', 'ehm_invariance_last_error', 'ehm_invariance_abi_sizes',
 ]
 EHM_AUDIT_MODES = {'uniform': 0, 'per_leaf': 1}     # EHM_AUDIT_UNIFORM / _PER_LEAF
 EHM_COMPILE_SPINE_ROOTS = 1     # ehm_compiled_create_opts
@@ -272,6 +273,26 @@ class CertifyLeaves(ctypes.Structure):
                                                'W')]
 
 
+class InvarianceOpts(ctypes.Structure):
+    _fields_ = [('n', ctypes.c_int64), ('leaf_ids', ctypes.c_void_p),
+                ('root_vertices', ctypes.c_void_p), ('chunk', ctypes.c_int64)] + \
+        [(k, ctypes.c_void_p) for k in ('A', 'B', 'w', 'E', 'region_rows', 'H', 'h', 'Gx', 'gx',
+                                        'leaf_mode', 'd_lo', 'd_hi')] + \
+        [('tol_exit', ctypes.c_double), ('n_modes', ctypes.c_int32), ('n_d', ctypes.c_int32),
+         ('n_g', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
+class InvarianceResult(ctypes.Structure):
+    _fields_ = [('counts', ctypes.c_int64 * 5), ('worst_leaf', ctypes.c_int64),
+                ('worst_margin', ctypes.c_double), ('invariant_volume', ctypes.c_double),
+                ('cell_volume', ctypes.c_double), ('seconds', ctypes.c_double)]
+
+
+class InvarianceLeaves(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ('status', 'margin', 'worst', 'max_violation',
+                                               'x_next', 'succ_root', 'succ_leaf')]
+
+
 _lib = None
 
 
@@ -340,6 +361,18 @@ def load(build_if_missing=True):
     lib.ehm_certify_last_error.restype = ctypes.c_char_p
     lib.ehm_compiled_reduce.argtypes = [vp, vp, vp, vp, ctypes.POINTER(vp), vp, vp, vp, vp]
     lib.ehm_reduce_last_error.restype = ctypes.c_char_p
+    mirrors = (InvarianceOpts, InvarianceResult, InvarianceLeaves)  # ... and the successors'
+    sizes = (i64 * len(mirrors))()
+    lib.ehm_invariance_abi_sizes.argtypes = [vp, i32]
+    if lib.ehm_invariance_abi_sizes(ctypes.addressof(sizes), len(mirrors)) != len(mirrors) or any(
+            int(sizes[k]) != ctypes.sizeof(m) for k, m in enumerate(mirrors)):
+        raise EhmError(EHM_E_INVALID, 'libehmpc.so and its ctypes binding disagree about the '
+                       "successors' structs: %s against %s (rebuild the library)" % (
+                           [int(v) for v in sizes], [ctypes.sizeof(m) for m in mirrors]))
+    lib.ehm_compiled_successors.argtypes = [vp, ctypes.POINTER(InvarianceOpts),
+                                            ctypes.POINTER(InvarianceResult),
+                                            ctypes.POINTER(InvarianceLeaves)]
+    lib.ehm_invariance_last_error.restype = ctypes.c_char_p
     lib.ehm_explicit_set_costs.argtypes = [vp, vp, vp]
     lib.ehm_explicit_sample.argtypes = [vp, ctypes.POINTER(AuditOpts), vp, vp]
     lib.ehm_explicit_audit.argtypes = [vp, vp, ctypes.POINTER(AuditOpts),
@@ -439,7 +472,8 @@ def load(build_if_missing=True):
         if name not in ('ehm_last_error', 'ehm_version', 'ehm_stream',
                         'ehm_explicit_last_error', 'ehm_implicit_last_error',
                         'ehm_compiled_last_error', 'ehm_applied_last_error',
-                        'ehm_certify_last_error', 'ehm_reduce_last_error'):
+                        'ehm_certify_last_error', 'ehm_reduce_last_error',
+                        'ehm_invariance_last_error'):
             fn.restype = i32
     lib.ehm_search_last_error.restype = ctypes.c_char_p
     lib.ehm_search_create.argtypes = [i32, i32, i32, ctypes.POINTER(vp)]

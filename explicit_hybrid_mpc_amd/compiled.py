@@ -665,6 +665,41 @@ class CompiledLaw:
         return certify.certify(self, oracle, leaves=leaves, input_tol=input_tol,
                                max_tries=max_tries, chunk=chunk, return_leaves=return_leaves)
 
+    # -- one-step invariance leaf by leaf (invariance.py) ---------------------------
+    def successors(self, plant=None, d_box=None, leaves=None, tol_exit=1e-9,
+                   return_successors=False, chunk=0):
+        """
+        Where the law's input sends the state, leaf by leaf: on a leaf the law is affine and in the
+        leaf's step-0 mode the plant is affine, so the image of the leaf under every disturbance of
+        the box ``d_box`` = (lo, hi) (arrays [plant.n_d]; None: the nominal successor, no E term)
+        is the convex hull of its successors at the (p + 1) 2^n_d points (cell vertex, box corner).
+        Each is computed bit for bit as ``rollout`` would compute it for that state, input, mode
+        and disturbance, located as one rollout step locates its state, and judged by the
+        rollout's exit test (``tol_exit``).  Status per leaf, the first that applies: ``no_cell``,
+        ``no_mode`` (no step-0 mode: the rollout's status 3), ``mode_region`` (a vertex of the
+        cell is outside the region of the leaf's mode: status 2 can occur on the leaf), ``exits``
+        (a vertex successor leaves the partitioned set: status 1 can occur), ``invariant``.
+        ``plant`` defaults as in ``rollout``; a guarded plant is refused (``ValueError``): its
+        mode is chosen per substep by guards, so the successor is not affine on a leaf.
+        ``leaves``: rows of the leaf records (None: all); ``chunk``: leaves per pass, no result
+        depends on it.  ``return_successors``: also the successors, their roots and their leaves
+        (the transition relation of the vertices).
+
+        ``invariant`` for every leaf proves that no trajectory leaves the set only where the set
+        -- the union of the roots -- is convex (``set_convex``, ``holds_on_set``); without that it
+        is a statement about the vertex successors.  What it covers: the piecewise-affine function
+        the arrays define on the cells their planes define, the nominal plant of ``Plant`` with a
+        box disturbance.  Not: measurement error v or input error e, the rounding of a single
+        law's evaluation at interior points, the sibling hand-over within rounding of a split
+        face, the recovery error of the root vertices.  ``margin`` is in units of the chosen
+        root's weights: for a point outside it orders leaves, it is not a distance.  ``EhmError``
+        for a law with test nodes.  Returns an ``invariance.SuccessorResult``.
+        """
+        from . import invariance
+        return invariance.successors(self, plant=plant, d_box=d_box, leaves=leaves,
+                                     tol_exit=tol_exit, return_successors=return_successors,
+                                     chunk=chunk)
+
     def __call__(self, x):
         """(u, t): the input for state x and the evaluation time, as the reference's call."""
         tic = time.time()

@@ -544,6 +544,9 @@ void ehm_compiled_get_view(const ehm_compiled* C, ehm_compiled_view* out) {
     out->n_leaf = C->h[H_LEAF];
     out->n_test = C->h[H_TEST];
     out->stream = C->stream;
+    out->root_rec = C->root_rec.as<const double>();
+    out->nbr = C->h[H_NBR] ? C->nbr.as<const int32_t>() : nullptr;
+    out->side_stride = (int)C->h[H_SS];
 }
 
 namespace {

@@ -1,5 +1,6 @@
-// What ehm_certify.hip and ehm_reduce.hip read of an ehm_compiled handle (ehm_compiled.hip owns the
-// struct): device pointers that stay the handle's, valid while it lives.  Not exported.
+// What ehm_certify.hip, ehm_reduce.hip and ehm_invariance.hip read of an ehm_compiled handle
+// (ehm_compiled.hip owns the struct): device pointers that stay the handle's, valid while it lives.
+// Not exported.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -19,6 +20,9 @@ struct ehm_compiled_view {
     int p, n_u, node_stride, leaf_stride;
     long long n_roots, n_int, n_leaf, n_test;
     hipStream_t stream;
+    const double* root_rec;     // [n_roots][side_stride] doubles in either precision
+    const int32_t* nbr;         // [n_roots][p+1] the roots' face adjacency, or nullptr
+    int side_stride;
 };
 
 void ehm_compiled_get_view(const ehm_compiled* C, ehm_compiled_view* out);

@@ -511,6 +511,18 @@ class ExplicitMPC:
         finally:
             law.close()
 
+    def successors(self, spine='roots', dtype=np.float64, flush=False, **kw):
+        """
+        ``CompiledLaw.successors`` (invariance.py) for this law: compiles it
+        (``compile(spine=spine, dtype=dtype, flush=flush)``) and asks where its input sends every
+        leaf; ``kw`` as ``CompiledLaw.successors``.  Returns its ``invariance.SuccessorResult``.
+        """
+        law = self.compile(dtype=dtype, spine=spine, flush=flush)
+        try:
+            return law.successors(**kw)
+        finally:
+            law.close()
+
     def node_modes(self, plant):
         """int32 [n_nodes]: step-0 mode of every node's commutation (-1: none); all 0 for a
         single-mode plant."""

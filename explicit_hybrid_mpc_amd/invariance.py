@@ -1,0 +1,237 @@
+"""
+One-step invariance of a compiled law leaf by leaf (csrc/ehm_invariance.hip):
+
+    res = law.successors()                      # SuccessorResult of every leaf, nominal successor
+    res = law.successors(d_box=(lo, hi))        # under every disturbance of the box
+    res.counts                                  # leaves by status name (STATUS_NAMES)
+    res.status, res.margin, res.worst           # per leaf
+    res.invariant_volume_fraction, res.set_convex, res.holds_on_set
+
+The argument.  On a leaf the law is affine, u = u_0 + K (x - v_0).  In the leaf's step-0 mode m the
+plant of ``rollout`` is x+ = A_m x + B_m u + w_m + E d, affine in (x, u, d).  So the successor map
+(x, d) -> x+ is affine on cell x box, and the image of the leaf under every disturbance of the box is
+the convex hull of its successors at the (p + 1) 2^n_d points (cell vertex, box corner).  If all of
+them lie in a CONVEX set, so does every successor of every state of the leaf.  The set is the union
+of the law's roots, where the law exists; ``roots_convex`` decides whether it is convex.
+
+A leaf is ``invariant`` when every one of those successors, located as one step of ``rollout``
+locates its state, passes the rollout's exit test on its root's weights (``tol_exit``), and every
+vertex of the cell passes the region rows of the leaf's mode (the rollout's status 2; a region is
+convex, so the whole cell lies in it).  ``exits``: some successor fails the exit test.  Where every
+leaf is invariant and the set is convex (``holds_on_set``) no trajectory of the nominal plant under
+disturbances of the box ever stops with status 1 or 2, whatever its length.
+
+What the result covers: the piecewise-affine function the law's arrays define on the cells their
+planes define (``cells``), and the nominal plant of ``simulate.Plant`` with a box disturbance.  It
+does not cover: measurement error v or input error e; the rounding of a single law's evaluation at
+interior points (DESIGN.md 3.8c bounds it); a state within rounding of a split face being handed to
+the sibling leaf's map; the recovery error of the root vertices the cells carry.  Without a convex
+set ``invariant`` is a statement about the vertex successors only.  ``margin`` is in units of the
+chosen root's barycentric weights: for a point outside it orders leaves, it is not a distance.
+"""
+
+import ctypes
+
+import numpy as np
+
+from . import _capi
+from ._capi import ptr
+
+STATUS_NAMES = ('invariant', 'exits', 'mode_region', 'no_mode', 'no_cell')
+MAX_D = 8                       # EHM_R_MAX_D: 2^8 corners
+
+
+def _check(rc):
+    if rc != _capi.EHM_OK:
+        raise _capi.EhmError(rc, _capi.load().ehm_invariance_last_error().decode('utf-8',
+                                                                                 'replace'))
+
+
+def roots_convex(root_vertices, rtol=1e-9):
+    """
+    True iff the union of the simplices ``root_vertices`` [n_roots, p+1, p] is convex; host numpy.
+
+    The vertices are deduplicated first: per coordinate, values closer than rtol max|v| are one
+    value, so vertices that differ in their last bits between roots are one vertex.  The boundary
+    facets are the facets (p vertices of a root) owned by exactly one root; each one's plane is
+    oriented by the owning root's opposite vertex.  The union is reported convex iff every distinct
+    vertex lies on the inner side of every boundary plane within rtol max|v| (unit normals).
+
+    Why that decides it: a closed union of simplices that lies inside the intersection of its
+    boundary facets' half-spaces and has nonempty interior IS that intersection -- a point of the
+    intersection outside the union could be joined to an interior point of the union by a segment
+    that leaves the union through a boundary facet, at whose plane it would change sides -- and an
+    intersection of half-spaces is convex; the union lies inside iff its vertices do.  Conversely
+    a convex union lies on one side of the plane of each of its boundary facets.  Limits: the roots
+    must be a face-to-face triangulation (a facet that is a proper part of a neighbour's facet
+    counts as boundary, and the answer is then False where it should be True, never the other way);
+    roots of no volume have no side and are not supported; the test is within rtol, so a dent
+    shallower than rtol max|v| is not seen.  The facet-by-vertex products are made in chunks of at
+    most about 256 MB.
+    """
+    V = np.ascontiguousarray(root_vertices, dtype=np.float64)
+    if V.ndim != 3 or V.shape[1] != V.shape[2] + 1:
+        raise ValueError('root_vertices must be [n_roots, p+1, p]')
+    R, nv, p = V.shape
+    if R == 0:
+        return True
+    scale = float(np.abs(V).max())
+    tol = float(rtol) * (scale if scale > 0. else 1.)
+    flat = V.reshape(-1, p)
+    key = np.empty(flat.shape, dtype=np.int64)
+    for c in range(p):
+        order = np.argsort(flat[:, c], kind='stable')
+        step = np.concatenate([[0], (np.diff(flat[order, c]) > tol).astype(np.int64)])
+        key[order, c] = np.cumsum(step)
+    uniq, first, vid = np.unique(key, axis=0, return_index=True, return_inverse=True)
+    points = flat[first]                                        # [n_points, p]
+    vid = vid.reshape(R, nv)
+    if p == 1:
+        lo, hi = points.min(), points.max()
+        covered = np.sort(V[:, :, 0], axis=1)
+        order = np.argsort(covered[:, 0])
+        reach = np.maximum.accumulate(covered[order, 1])
+        return bool((covered[order, 0][1:] <= reach[:-1] + tol).all() and reach[-1] >= hi - tol
+                    and covered[order, 0][0] <= lo + tol)
+    # every facet: the root's vertices without the k-th, which is its opposite vertex
+    keep = np.array([[j for j in range(nv) if j != k] for k in range(nv)])      # [nv, p]
+    facets = np.sort(vid[:, keep], axis=2).reshape(-1, p)                       # [R nv, p]
+    opposite = vid.reshape(-1)                                                  # facet r nv + k: k
+    _, index, counts = np.unique(facets, axis=0, return_index=True, return_counts=True)
+    boundary = index[counts == 1]
+    if boundary.size == 0:
+        return True
+    F = points[facets[boundary]]                                                # [nb, p, p]
+    edges = F[:, 1:] - F[:, :1]                                                 # [nb, p-1, p]
+    normal = np.linalg.svd(edges, full_matrices=True)[2][:, -1, :]              # unit, [nb, p]
+    side = np.einsum('fc,fc->f', normal, points[opposite[boundary]] - F[:, 0])
+    normal = normal * np.where(side < 0., -1., 1.)[:, None]
+    offset = np.einsum('fc,fc->f', normal, F[:, 0])
+    rows = max(1, (1 << 25) // max(1, points.shape[0]))
+    for s in range(0, normal.shape[0], rows):
+        d = normal[s:s + rows] @ points.T - offset[s:s + rows, None]
+        if (d < -tol).any():
+            return False
+    return True
+
+
+class SuccessorResult:
+    """
+    What ``CompiledLaw.successors`` found: ``n`` leaves asked for, ``counts`` by
+    status name (STATUS_NAMES); per leaf ``leaves`` (rows of the leaf records), ``leaf_node``,
+    ``status`` int32, ``margin`` (the smallest weight of any vertex successor in the root that
+    holds it; NaN without a cell or mode), ``worst`` = i n_c + j, the (vertex, corner) pair that
+    gives it, ``max_violation`` (of the plant's state rows at the successors);
+    ``invariant_volume_fraction`` and ``cell_volume_fraction`` over the roots' volume (of the whole
+    law also when only some ``leaves`` were asked for); ``worst_leaf`` (dict of leaf, leaf_node,
+    margin; None) the leaf of status invariant or exits with the smallest margin, ``worst_margin``;
+    ``seconds`` of the kernel; ``n_corners``; ``set_convex`` (``roots_convex`` of the law's roots);
+    ``holds_on_set``: every requested leaf is invariant, every leaf was requested, and the set is
+    convex.  With ``return_successors``: ``x_next`` [n, p+1, n_c, p], ``succ_root`` and
+    ``succ_leaf`` [n, p+1, n_c] (-1 where the successor is outside).
+    """
+
+    x_next = succ_root = succ_leaf = None
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        return 'SuccessorResult(n=%d, counts=%r, invariant_volume_fraction=%.6g, ' \
+            'worst_margin=%.3g, set_convex=%s, holds_on_set=%s)' % (
+                self.n, self.counts, self.invariant_volume_fraction, self.worst_margin,
+                self.set_convex, self.holds_on_set)
+
+
+def _box(plant, d_box):
+    """(lo, hi) float64 [n_d] of ``d_box``, or (None, None) for the nominal successor."""
+    if d_box is None:
+        return None, None
+    try:
+        lo, hi = d_box
+    except (TypeError, ValueError):
+        raise ValueError('d_box must be (lo, hi)')
+    lo = np.ascontiguousarray(np.atleast_1d(lo), dtype=np.float64)
+    hi = np.ascontiguousarray(np.atleast_1d(hi), dtype=np.float64)
+    if lo.shape != (plant.n_d,) or hi.shape != (plant.n_d,):
+        raise ValueError('d_box must be two arrays [%d] (the plant\'s n_d)' % plant.n_d)
+    if plant.n_d > MAX_D:
+        raise ValueError('a box of %d disturbances has more than 2^%d corners' % (plant.n_d,
+                                                                                 MAX_D))
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (lo <= hi).all()):
+        raise ValueError('d_box must be finite with lo <= hi')
+    return lo, hi
+
+
+def successors(law, plant=None, d_box=None, leaves=None, tol_exit=1e-9, return_successors=False,
+               chunk=0):
+    """The one path to ``ehm_compiled_successors``; see ``CompiledLaw.successors``."""
+    from . import applied, certify, simulate
+    if not getattr(law, '_handle', None):
+        raise ValueError('the law is closed')
+    if plant is None:
+        plant = law._rollout_plant
+    if plant is None and law.mpc is not None:
+        plant = simulate.Plant.from_mpc(law.mpc)
+    if plant is None:
+        raise ValueError('successors needs a plant: the law has none and no mpc to make one from')
+    if plant.guarded:
+        raise ValueError('a guarded plant chooses its mode per substep by its guards: the '
+                         'successor is not affine on a leaf')
+    if plant.n_x != law.p or plant.n_u != law.n_u:
+        raise ValueError('plant (n_x %d, n_u %d) does not fit the law (p %d, n_u %d)' % (
+            plant.n_x, plant.n_u, law.p, law.n_u))
+    lo, hi = _box(plant, d_box)
+    tol_exit, chunk = float(tol_exit), int(chunk)
+    if not tol_exit >= 0. or chunk < 0:
+        raise ValueError('tol_exit and chunk must be >= 0')
+    if law._h['n_test'] > 0:
+        raise _capi.EhmError(_capi.EHM_E_INVALID, 'the law has %d test nodes: its cells do not '
+                             "follow from its planes -- compile(spine='roots') has none" %
+                             law._h['n_test'])
+    modes = np.ascontiguousarray(law._plant_modes(plant), dtype=np.int32)
+    ids = certify._leaf_ids(law, leaves)
+    if law._root_cells is None:
+        law._root_cells = applied.root_cells(law)
+    roots = law._root_cells
+    if getattr(law, '_set_convex', None) is None:
+        law._set_convex = roots_convex(roots['vertices'])
+    n, p = ids.size, law.p
+    n_d = 0 if lo is None else plant.n_d
+    n_c = 1 << n_d
+    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+    opt = lambda a: ptr(a) if a.size else None
+    rows, H, h = plant.region_arrays()
+    A, B, w, E, H, h, Gx, gx = (f64(a) for a in (plant.A, plant.B, plant.w, plant.E, H, h,
+                                                 plant.Gx, plant.gx))
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    opts = _capi.InvarianceOpts(
+        n=n, leaf_ids=None if leaves is None else ptr(ids), root_vertices=ptr(roots['vertices']),
+        chunk=chunk, A=ptr(A), B=ptr(B), w=ptr(w), E=opt(E) if n_d else None,
+        region_rows=ptr(rows), H=opt(H), h=opt(h), Gx=opt(Gx), gx=opt(gx), leaf_mode=ptr(modes),
+        d_lo=opt(lo) if n_d else None, d_hi=opt(hi) if n_d else None, tol_exit=tol_exit,
+        n_modes=int(plant.n_modes), n_d=n_d, n_g=int(plant.gx.size))
+    arrays = dict(status=np.empty(n, np.int32), margin=np.empty(n), worst=np.empty(n, np.int32),
+                  max_violation=np.empty(n))
+    if return_successors:
+        arrays.update(x_next=np.empty((n, p + 1, n_c, p)),
+                      succ_root=np.empty((n, p + 1, n_c), np.int32),
+                      succ_leaf=np.empty((n, p + 1, n_c), np.int32))
+    lv = _capi.InvarianceLeaves(**{k: ptr(a) for k, a in arrays.items()})
+    res = _capi.InvarianceResult()
+    _check(_capi.load().ehm_compiled_successors(law._handle, ctypes.byref(opts),
+                                                ctypes.byref(res), ctypes.byref(lv)))
+    total = float(roots['volume'].sum())
+    counts = {name: int(res.counts[k]) for k, name in enumerate(STATUS_NAMES)}
+    worst = None
+    if res.worst_leaf >= 0:
+        l = int(ids[res.worst_leaf])
+        worst = dict(leaf=l, leaf_node=int(law.leaf_node[l]), margin=float(res.worst_margin))
+    every = n >= law._h['n_leaf'] and np.unique(ids).size == law._h['n_leaf']
+    return SuccessorResult(
+        n=n, counts=counts, leaves=ids, leaf_node=law.leaf_node[ids], n_corners=n_c,
+        invariant_volume_fraction=float(res.invariant_volume) / total,
+        cell_volume_fraction=float(res.cell_volume) / total, worst_leaf=worst,
+        worst_margin=float(res.worst_margin), seconds=float(res.seconds),
+        set_convex=bool(law._set_convex), tol_exit=tol_exit,
+        holds_on_set=bool(counts['invariant'] == n and every and law._set_convex), **arrays)

@@ -978,6 +978,92 @@ int ehm_compiled_reduce(ehm_compiled* law, const double* root_vertices, const do
                         int32_t* leaf_of, int64_t* counts, double* stats);
 const char* ehm_reduce_last_error(void);
 
+/* ---- one-step invariance leaf by leaf (csrc/ehm_invariance.hip) -------------------
+ *
+ * On a leaf the law is affine and in the leaf's step-0 mode the plant x+ = A_m x + B_m u + w_m + E d
+ * is affine in (x, u, d), so (x, d) -> x+ is affine on cell x box: the image of the leaf under every
+ * disturbance of the box [d_lo, d_hi] is the convex hull of the successors at the (p + 1) n_c points
+ * (cell vertex i, box corner j), n_c = 2^n_d (n_d = 0: no box, no E term, n_c = 1).  The entry takes
+ * its own copies of the plant; it does not read the handle's rollout attachment.
+ * Per requested leaf l (leaf_ids and root_vertices as for ehm_compiled_cells), one device thread:
+ *  1. the cell V and u_i, the leaf's own map at v_i: vertices and ubar of ehm_compiled_cells;
+ *  2. m = leaf_mode[l];
+ *  3. for every vertex i and region row r of mode m (region_rows [n_modes], H and h stacked by mode):
+ *     s = ((0 + H_r0 v_0) + ..); the vertex is in the region iff s <= h_r + tol_exit;
+ *  4. y_i[k] = (((0 + A_k0 v_0 + ..) + B_k0 u_0 + ..) + w_k);
+ *  5. corner j takes d_b = d_hi[b] where bit b of j is set, else d_lo[b];
+ *     x+_ij[k] = y_i[k] + E_k0 d_0 + .. in that order -- bit for bit what ehm_compiled_rollout
+ *     writes for the state v_i, the input u_i, mode m and the disturbance d_j;
+ *  6. x+_ij is located as one rollout step locates its state: with an adjacency table the visibility
+ *     walk started at the leaf's own root, else (or when the walk does not accept a root) the first
+ *     root that contains it, else the last; its weights (a0, alpha) are taken in that root;
+ *  7. margin_ij = min(a0, alpha_*) (a weight that is NaN is taken); x+_ij is INSIDE iff every weight
+ *     is >= -tol_exit (a NaN fails);
+ *  8. viol_ij = max_r (Gx_r . x+_ij - gx_r) from -inf, rows summed as in step 3 (n_g = 0: -inf).
+ * Status, the first that applies: 4 no_cell; 3 no_mode (m < 0 or m >= n_modes); 2 mode_region (a
+ * cell vertex fails a region row of m); 1 exits (some x+_ij is not inside); 0 invariant.
+ * Per-leaf outputs (required): status; margin, the minimum of margin_ij in (i, j) order, the first on
+ * ties, a NaN before any number (NaN without a cell or mode); worst = i n_c + j of that pair (-1);
+ * max_violation, the maximum of viol_ij (NaN without a cell or mode).  Optional, each may be NULL:
+ * x_next [n][p+1][n_c][p]; succ_root [n][p+1][n_c], the root of step 6 (-1 where x+_ij is not
+ * inside); succ_leaf, the row of leaf_rec the law's walk from that root ends in for x+_ij (-1
+ * likewise): the transition relation of the vertices.  Rows of a leaf without a cell or mode are NaN
+ * and -1.  margin is in units of the chosen root's weights: for a point outside it orders leaves, it
+ * is no distance.
+ * Result: counts by status (integer atomics on the device); worst_leaf, the position in the call of
+ * the leaf of status 0 or 1 with the smallest margin, the first on ties (-1, NaN: none);
+ * invariant_volume and cell_volume, the volumes (ehm_volume_batch) of the invariant leaves and of
+ * every leaf with a cell summed in leaf order; seconds, the device time of the kernel.  The leaves
+ * are processed chunk at a time (0: as many as keep x_next of a pass within 128 MiB); no result
+ * depends on the chunk.
+ * EHM_E_INVALID for a law with test nodes, n_u > 4, n_d > 8, n_modes > 4, more than 256 region rows
+ * or constraint rows, d_lo > d_hi or a bound that is not finite, a box without E, a leaf_ids entry
+ * outside the law (named in the message), a required array that is NULL, tol_exit negative or NaN.
+ * Errors through ehm_invariance_last_error. */
+typedef struct ehm_invariance_opts {
+    int64_t n;                      /* leaves of this call                                     */
+    const int32_t* leaf_ids;        /* [n] rows of leaf_rec, or NULL: leaves 0 .. n - 1        */
+    const double* root_vertices;    /* [n_roots][p+1][p], as for ehm_compiled_cells            */
+    int64_t chunk;                  /* leaves per pass (0: see above)                          */
+    const double* A;                /* [n_modes][p][p]                                         */
+    const double* B;                /* [n_modes][p][n_u]                                       */
+    const double* w;                /* [n_modes][p]                                            */
+    const double* E;                /* [p][n_d], NULL with n_d = 0                             */
+    const int32_t* region_rows;     /* [n_modes] rows of every mode's region, NULL: none       */
+    const double* H;                /* [rows][p] stacked by mode                               */
+    const double* h;                /* [rows]                                                  */
+    const double* Gx;               /* [n_g][p]                                                */
+    const double* gx;               /* [n_g]                                                   */
+    const int32_t* leaf_mode;       /* [n_leaf] step-0 mode of every leaf, -1: none            */
+    const double* d_lo;             /* [n_d]                                                   */
+    const double* d_hi;             /* [n_d]                                                   */
+    double tol_exit;
+    int32_t n_modes, n_d, n_g, reserved;
+} ehm_invariance_opts;
+typedef struct ehm_invariance_result {
+    int64_t counts[5];
+    int64_t worst_leaf;
+    double  worst_margin;
+    double  invariant_volume;
+    double  cell_volume;
+    double  seconds;
+} ehm_invariance_result;
+typedef struct ehm_invariance_leaves {
+    int32_t* status;
+    double*  margin;
+    int32_t* worst;
+    double*  max_violation;
+    double*  x_next;
+    int32_t* succ_root;
+    int32_t* succ_leaf;
+} ehm_invariance_leaves;
+int ehm_compiled_successors(ehm_compiled* law, const ehm_invariance_opts* opts,
+                            ehm_invariance_result* result, const ehm_invariance_leaves* leaves);
+const char* ehm_invariance_last_error(void);
+/* ehm_abi_sizes for ehm_invariance_opts, ehm_invariance_result, ehm_invariance_leaves, in this
+ * order. */
+int ehm_invariance_abi_sizes(int64_t* sizes, int32_t n);
+
 /* ---- closed-loop simulation under the COMPILED law (csrc/ehm_compiled.hip) -------
  *
  * The entry points of the explicit law's rollout, argument for argument, on a compiled law -- also
