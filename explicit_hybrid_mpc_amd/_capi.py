@@ -318,42 +318,27 @@ def load(build_if_missing=True):
     i32 = ctypes.c_int32
     # the struct mirrors below must be the library's structs: a mirror that is too small would be
     # overrun by the library's writes (ehm_abi_sizes, include/ehmpc.h)
-    mirrors = (ProblemDesc, RunOpts, NodeInit, Progress, TreeInfo, Counters)
-    sizes = (i64 * len(mirrors))()
-    lib.ehm_abi_sizes.argtypes = [vp, i32]
-    if lib.ehm_abi_sizes(ctypes.addressof(sizes), len(mirrors)) != len(mirrors) or any(
-            int(sizes[k]) != ctypes.sizeof(m) for k, m in enumerate(mirrors)):
-        raise EhmError(EHM_E_INVALID, 'libehmpc.so and its ctypes binding disagree about the public '
-                       'structs: %s against %s (rebuild the library)' % (
-                           [int(v) for v in sizes], [ctypes.sizeof(m) for m in mirrors]))
-    mirrors = (AuditOpts, AuditResult, AuditSamples)        # the audit's structs: a list of its own
-    sizes = (i64 * len(mirrors))()
-    lib.ehm_audit_abi_sizes.argtypes = [vp, i32]
-    if lib.ehm_audit_abi_sizes(ctypes.addressof(sizes), len(mirrors)) != len(mirrors) or any(
-            int(sizes[k]) != ctypes.sizeof(m) for k, m in enumerate(mirrors)):
-        raise EhmError(EHM_E_INVALID, 'libehmpc.so and its ctypes binding disagree about the '
-                       "audit's structs: %s against %s (rebuild the library)" % (
-                           [int(v) for v in sizes], [ctypes.sizeof(m) for m in mirrors]))
-    mirrors = (AppliedOpts, AppliedResult, AppliedSamples)  # ... and the applied-input audit's
-    sizes = (i64 * len(mirrors))()
-    lib.ehm_applied_abi_sizes.argtypes = [vp, i32]
-    if lib.ehm_applied_abi_sizes(ctypes.addressof(sizes), len(mirrors)) != len(mirrors) or any(
-            int(sizes[k]) != ctypes.sizeof(m) for k, m in enumerate(mirrors)):
-        raise EhmError(EHM_E_INVALID, 'libehmpc.so and its ctypes binding disagree about the '
-                       "applied-input audit's structs: %s against %s (rebuild the library)" % (
-                           [int(v) for v in sizes], [ctypes.sizeof(m) for m in mirrors]))
+    for getter, mirrors, what in (
+            ('ehm_abi_sizes', (ProblemDesc, RunOpts, NodeInit, Progress, TreeInfo, Counters),
+             'public '),
+            ('ehm_audit_abi_sizes', (AuditOpts, AuditResult, AuditSamples), "audit's "),
+            ('ehm_applied_abi_sizes', (AppliedOpts, AppliedResult, AppliedSamples),
+             "applied-input audit's "),
+            ('ehm_certify_abi_sizes', (CertifyOpts, CertifyResult, CertifyLeaves), "certificate's "),
+            ('ehm_invariance_abi_sizes', (InvarianceOpts, InvarianceResult, InvarianceLeaves),
+             "successors' ")):
+        sizes = (i64 * len(mirrors))()
+        fn = getattr(lib, getter)
+        fn.argtypes = [vp, i32]
+        if fn(ctypes.addressof(sizes), len(mirrors)) != len(mirrors) or any(
+                int(sizes[k]) != ctypes.sizeof(m) for k, m in enumerate(mirrors)):
+            raise EhmError(EHM_E_INVALID, 'libehmpc.so and its ctypes binding disagree about the '
+                           '%sstructs: %s against %s (rebuild the library)' % (
+                               what, [int(v) for v in sizes], [ctypes.sizeof(m) for m in mirrors]))
     lib.ehm_compiled_audit.argtypes = [vp, vp, vp, ctypes.POINTER(AppliedOpts),
                                        ctypes.POINTER(AppliedResult),
                                        ctypes.POINTER(AppliedSamples)]
     lib.ehm_applied_last_error.restype = ctypes.c_char_p
-    mirrors = (CertifyOpts, CertifyResult, CertifyLeaves)  # ... and the certificate's
-    sizes = (i64 * len(mirrors))()
-    lib.ehm_certify_abi_sizes.argtypes = [vp, i32]
-    if lib.ehm_certify_abi_sizes(ctypes.addressof(sizes), len(mirrors)) != len(mirrors) or any(
-            int(sizes[k]) != ctypes.sizeof(m) for k, m in enumerate(mirrors)):
-        raise EhmError(EHM_E_INVALID, 'libehmpc.so and its ctypes binding disagree about the '
-                       "certificate's structs: %s against %s (rebuild the library)" % (
-                           [int(v) for v in sizes], [ctypes.sizeof(m) for m in mirrors]))
     lib.ehm_compiled_certify.argtypes = [vp, vp, vp, ctypes.POINTER(CertifyOpts),
                                          ctypes.POINTER(CertifyResult),
                                          ctypes.POINTER(CertifyLeaves)]
@@ -361,14 +346,6 @@ def load(build_if_missing=True):
     lib.ehm_certify_last_error.restype = ctypes.c_char_p
     lib.ehm_compiled_reduce.argtypes = [vp, vp, vp, vp, ctypes.POINTER(vp), vp, vp, vp, vp]
     lib.ehm_reduce_last_error.restype = ctypes.c_char_p
-    mirrors = (InvarianceOpts, InvarianceResult, InvarianceLeaves)  # ... and the successors'
-    sizes = (i64 * len(mirrors))()
-    lib.ehm_invariance_abi_sizes.argtypes = [vp, i32]
-    if lib.ehm_invariance_abi_sizes(ctypes.addressof(sizes), len(mirrors)) != len(mirrors) or any(
-            int(sizes[k]) != ctypes.sizeof(m) for k, m in enumerate(mirrors)):
-        raise EhmError(EHM_E_INVALID, 'libehmpc.so and its ctypes binding disagree about the '
-                       "successors' structs: %s against %s (rebuild the library)" % (
-                           [int(v) for v in sizes], [ctypes.sizeof(m) for m in mirrors]))
     lib.ehm_compiled_successors.argtypes = [vp, ctypes.POINTER(InvarianceOpts),
                                             ctypes.POINTER(InvarianceResult),
                                             ctypes.POINTER(InvarianceLeaves)]
@@ -534,19 +511,18 @@ def load(build_if_missing=True):
     return lib
 
 
-def check(rc):
-    if rc != EHM_OK:
-        raise EhmError(rc, load().ehm_last_error().decode('utf-8', 'replace'))
+def checker(name):
+    """The check of one error channel: ``check(rc)`` raises EhmError with the text of ``name`` (an
+    ``ehm_*_last_error`` of the library) unless rc is EHM_OK."""
+    def check(rc):
+        if rc != EHM_OK:
+            raise EhmError(rc, getattr(load(), name)().decode('utf-8', 'replace'))
+    return check
 
 
-def check_search(rc):
-    if rc != EHM_OK:
-        raise EhmError(rc, load().ehm_search_last_error().decode('utf-8', 'replace'))
-
-
-def check_frontier(rc):
-    if rc != EHM_OK:
-        raise EhmError(rc, load().ehm_frontier_last_error().decode('utf-8', 'replace'))
+check = checker('ehm_last_error')
+check_search = checker('ehm_search_last_error')
+check_frontier = checker('ehm_frontier_last_error')
 
 
 def f64(a):

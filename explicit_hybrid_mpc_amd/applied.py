@@ -34,9 +34,7 @@ STATUS_NAMES = ('within', 'violation', 'negative', 'inadmissible', 'no_law', 'in
 INPUT_TOL_FACTOR = 1e-7     # a hundred solver tolerances (lexicographic.TOL, audit's rtol)
 
 
-def _check(rc):
-    if rc != _capi.EHM_OK:
-        raise _capi.EhmError(rc, _capi.load().ehm_applied_last_error().decode('utf-8', 'replace'))
+_check = _capi.checker('ehm_applied_last_error')
 
 
 def applied_input_problem(can, input_tol=0.):

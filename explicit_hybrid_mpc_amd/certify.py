@@ -50,9 +50,7 @@ SECONDS = ('kernels', 'feasibility', 'costs', 'tests', 'volumes', 'rest')
 MAX_DEPTH = _capi.EHM_CELL_MAX_DEPTH
 
 
-def _check(rc):
-    if rc != _capi.EHM_OK:
-        raise _capi.EhmError(rc, _capi.load().ehm_certify_last_error().decode('utf-8', 'replace'))
+_check = _capi.checker('ehm_certify_last_error')
 
 
 class LeafCells:

@@ -94,9 +94,8 @@ def leaf_stride32(p, n_u):
     return 4 * ((p + n_u + n_u * p + 3) // 4)
 
 
-def _check(rc):
-    if rc != _capi.EHM_OK:
-        raise _capi.EhmError(rc, _capi.load().ehm_compiled_last_error().decode('utf-8', 'replace'))
+_check = _capi.checker('ehm_compiled_last_error')
+_check_reduce = _capi.checker('ehm_reduce_last_error')
 
 
 def _shapes(h):
@@ -353,8 +352,7 @@ class CompiledLaw:
         rc = self._lib.ehm_compiled_reduce(self._handle, ptr(roots), ptr(tol), ptr(modes),
                                            ctypes.byref(handle), ptr(modes_out), ptr(leaf_of),
                                            ptr(counts), ptr(stats))
-        if rc != _capi.EHM_OK:
-            raise _capi.EhmError(rc, self._lib.ehm_reduce_last_error().decode('utf-8', 'replace'))
+        _check_reduce(rc)
         law = type(self)(handle, self.device, self.compile_seconds, dtype=self.dtype)
         law.flushed = self.flushed
         law.mpc = self.mpc

@@ -4,10 +4,10 @@
 //
 //   k_audit_sample    (ehm_audit.hip, through ehm_audit_sample.h) the points, uniform in the roots
 //   k_applied_pack    one thread per sample: theta' = (x, ubar), the cost constant, the flag of an
-//                     input that is not finite
+//                     input that is not finite (pack_applied_row of ehm_verdict.h)
 //   k_applied_reduce  V_u = optimum + constant, statuses, counts and the histogram by integer
 //                     atomics, the worst sample per workgroup (the host merges, ties to the smaller
-//                     id)
+//                     id): the rules and the tree of ehm_verdict.h
 //
 // The input is the law's own: ehm_compiled_eval_batch (double and single laws) or
 // ehm_explicit_eval_batch, so (u, leaf) are `evaluate` bit for bit.  Both optima come from
@@ -31,9 +31,10 @@
 #include "ehm_audit_sample.h"
 #include "ehm_explicit_view.h"
 #include "ehm_host.h"
+#include "ehm_verdict.h"
 
 #define EHM_APPLIED_BLOCK 256
-#define EHM_APPLIED_BINS 33
+#define EHM_APPLIED_BINS EHM_VERDICT_BINS
 // counters of a run: [0..5] statuses, [6..38] histogram
 #define EHM_APPLIED_COUNTERS (6 + EHM_APPLIED_BINS)
 #define EHM_APPLIED_NO_ID 0xffffffffffffffffULL
@@ -47,27 +48,10 @@ __global__ void k_applied_pack(long long n, int p, int n_u, const double* __rest
 #pragma clang fp contract(off)
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n) return;
-    double* t = theta + (size_t)q * (p + n_u);
-    for (int c = 0; c < p; ++c) t[c] = X[q * p + c];
-    double k = 0.0;
-    int bad = 0;
-    for (int j = 0; j < n_u; ++j) {
-        double u = U[q * n_u + j];
-        if (!isfinite(u)) {
-            bad = 1;
-            u = 0.0;
-        }
-        t[p + j] = u;
-        k = k + cost_u[j] * u;
-    }
-    konst[q] = k;
+    const bool bad = ehm_verdict::pack_applied_row(
+        p, n_u, [&](int c) { return X[q * p + c]; }, [&](int j) { return U[q * n_u + j]; }, cost_u,
+        theta + (size_t)q * (p + n_u), &konst[q]);
     no_law[q] = bad;
-}
-
-// (ratio, id) a beats b: the larger ratio, the smaller id on ties (no ratio here is a NaN: a
-// sample whose ratio is one enters as (-inf, no id))
-__device__ __forceinline__ bool applied_beats(double ra, uint64_t ia, double rb, uint64_t ib) {
-    return ra > rb || (ra == rb && ia < ib);
 }
 
 __global__ __launch_bounds__(EHM_APPLIED_BLOCK) void k_applied_reduce(
@@ -79,124 +63,84 @@ __global__ __launch_bounds__(EHM_APPLIED_BLOCK) void k_applied_reduce(
     unsigned long long* __restrict__ blk_id) {
 #pragma clang fp contract(off)
     __shared__ unsigned int cnt[EHM_APPLIED_COUNTERS];
-    __shared__ double sr[EHM_APPLIED_BLOCK];
-    __shared__ unsigned long long si[EHM_APPLIED_BLOCK];
-    const int t = threadIdx.x;
-    for (int i = t; i < EHM_APPLIED_COUNTERS; i += EHM_APPLIED_BLOCK) cnt[i] = 0;
+    ehm_verdict::counters_zero<EHM_APPLIED_BLOCK>(cnt);
     __syncthreads();
-    const long long q = (long long)blockIdx.x * EHM_APPLIED_BLOCK + t;
+    const long long q = (long long)blockIdx.x * EHM_APPLIED_BLOCK + threadIdx.x;
     double ratio = -INFINITY;
     unsigned long long id = EHM_APPLIED_NO_ID;
     if (q < n) {
         const double vs = vstar[q];
         const double v = ju[q] + konst[q];
         const double gap = v - vs;
-        const double er = eps_r * vs;
-        const double bound = eps_a > er ? eps_a : er;
-        const double slack = rtol * (1.0 + fabs(vs));
-        int st = 0;
+        const double bound = ehm_verdict::bound_of(eps_a, eps_r, vs);
+        int st;
         if (didx[q] < 0) st = 5;
         else if (no_law[q]) st = 4;
         else if (didx_u[q] < 0) st = 3;
-        else if (!(gap >= -slack)) st = 2;
-        else if (gap > bound + slack) st = 1;
+        else st = ehm_verdict::gap_status(gap, bound, ehm_verdict::slack_of(rtol, vs));
         vu[q] = v;
         status[q] = st;
         atomicAdd(&cnt[st], 1u);
         if (st <= 2) {
-            const double r = gap / bound;
-            int bin = 0;                            // negative (and NaN) ratios: bin 0
-            if (r > 1.0) bin = EHM_APPLIED_BINS - 1;
-            else if (r >= 0.0) {
-                bin = (int)(r * 32.0);
-                bin = bin > 31 ? 31 : bin;
-            }
-            atomicAdd(&cnt[6 + bin], 1u);
-            if (r == r) {                           // a NaN ratio is binned and never the worst
+            const double r = ehm_verdict::ratio_of(gap, bound);
+            atomicAdd(&cnt[6 + ehm_verdict::ratio_bin(r)], 1u);
+            if (ehm_verdict::ratio_is_candidate(r)) {
                 ratio = r;
                 id = first + (unsigned long long)q;
             }
         }
     }
-    sr[t] = ratio;
-    si[t] = id;
-    __syncthreads();
-    for (int h = EHM_APPLIED_BLOCK / 2; h > 0; h >>= 1) {
-        if (t < h && applied_beats(sr[t + h], si[t + h], sr[t], si[t])) {
-            sr[t] = sr[t + h];
-            si[t] = si[t + h];
-        }
-        __syncthreads();
+    ehm_verdict::block_worst<EHM_APPLIED_BLOCK>(
+        ratio, id,
+        [](double ra, unsigned long long ia, double rb, unsigned long long ib) {
+            return ehm_verdict::ratio_beats(ra, ia, rb, ib);
+        },
+        [](unsigned long long i) { return i != EHM_APPLIED_NO_ID; });
+    if (threadIdx.x == 0) {
+        blk_ratio[blockIdx.x] = ratio;
+        blk_id[blockIdx.x] = id;
     }
-    if (t == 0) {
-        blk_ratio[blockIdx.x] = sr[0];
-        blk_id[blockIdx.x] = si[0];
-    }
-    for (int i = t; i < EHM_APPLIED_COUNTERS; i += EHM_APPLIED_BLOCK)
-        if (cnt[i]) atomicAdd(&counters[i], (unsigned long long)cnt[i]);
+    ehm_verdict::counters_flush<EHM_APPLIED_BLOCK>(cnt, counters);
 }
 
-thread_local std::string a_err;
-int afail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    a_err = buf;
-    return code;
-}
-
-#define P_TRY(expr)                                                                        \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return afail(EHM_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
-    } while (0)
-
-unsigned blocks_of(long long n) {
-    return (unsigned)((n + EHM_APPLIED_BLOCK - 1) / EHM_APPLIED_BLOCK);
-}
-
-double wall_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-}
+thread_local ehm_err_channel a_err;
 
 int check_opts(const ehm_compiled* law, const ehm_applied_opts* o) {
-    if (!o) return afail(EHM_E_INVALID, "applied audit: no options");
-    if (o->n < 0 || o->chunk < 0) return afail(EHM_E_INVALID, "applied audit: n, chunk < 0");
+    if (!o) return a_err.fail(EHM_E_INVALID, "applied audit: no options");
+    if (o->n < 0 || o->chunk < 0) return a_err.fail(EHM_E_INVALID, "applied audit: n, chunk < 0");
     if (o->p < 1 || o->n_u < 1 || o->p + o->n_u > EHM_MAX_P)
-        return afail(EHM_E_INVALID, "applied audit: p = %d, n_u = %d: p + n_u must be <= %d",
-                     (int)o->p, (int)o->n_u, EHM_MAX_P);
-    if (!o->cost_u) return afail(EHM_E_INVALID, "applied audit: no cost_u");
-    if (!(o->rtol >= 0.0)) return afail(EHM_E_INVALID, "applied audit: rtol < 0");
+        return a_err.fail(EHM_E_INVALID, "applied audit: p = %d, n_u = %d: p + n_u must be <= %d",
+                          (int)o->p, (int)o->n_u, EHM_MAX_P);
+    if (!o->cost_u) return a_err.fail(EHM_E_INVALID, "applied audit: no cost_u");
+    if (!(o->rtol >= 0.0)) return a_err.fail(EHM_E_INVALID, "applied audit: rtol < 0");
     if (law) {
         int64_t info[14];
         if (ehm_compiled_info(law, info) != EHM_OK)
-            return afail(EHM_E_INVALID, "applied audit: %s", ehm_compiled_last_error());
+            return a_err.fail(EHM_E_INVALID, "applied audit: %s", ehm_compiled_last_error());
         if (info[1] != o->p || info[2] != o->n_u)
-            return afail(EHM_E_INVALID, "applied audit: the law has p = %lld, n_u = %lld, the "
-                         "options %d, %d", (long long)info[1], (long long)info[2], (int)o->p,
-                         (int)o->n_u);
+            return a_err.fail(EHM_E_INVALID, "applied audit: the law has p = %lld, n_u = %lld, the "
+                              "options %d, %d", (long long)info[1], (long long)info[2], (int)o->p,
+                              (int)o->n_u);
         if (info[6] > 0)
-            return afail(EHM_E_INVALID, "applied audit: the law has %lld test nodes (children "
-                         "that are no bisection); its roots do not tile the set -- compile it "
-                         "with the spine as its root table", (long long)info[6]);
+            return a_err.fail(EHM_E_INVALID, "applied audit: the law has %lld test nodes (children "
+                              "that are no bisection); its roots do not tile the set -- compile it "
+                              "with the spine as its root table", (long long)info[6]);
     } else if (o->source) {
         ehm_explicit_view v;
         ehm_explicit_get_view(o->source, &v);
         if (v.p != o->p || v.n_u != o->n_u)
-            return afail(EHM_E_INVALID, "applied audit: the source law has p = %d, n_u = %d, the "
-                         "options %d, %d", v.p, v.n_u, (int)o->p, (int)o->n_u);
+            return a_err.fail(EHM_E_INVALID, "applied audit: the source law has p = %d, n_u = %d, "
+                              "the options %d, %d", v.p, v.n_u, (int)o->p, (int)o->n_u);
     } else if (!o->u && o->n > 0) {
-        return afail(EHM_E_INVALID, "applied audit: no law, no source and no inputs");
+        return a_err.fail(EHM_E_INVALID, "applied audit: no law, no source and no inputs");
     }
     if (!o->x && o->n > 0) {
         if (o->n_cells < 1 || o->n_cells > 0x7fffffffLL || !o->cell_vertices || !o->cdf)
-            return afail(EHM_E_INVALID, "applied audit: no points and no cells to draw them in");
+            return a_err.fail(EHM_E_INVALID, "applied audit: no points and no cells to draw them "
+                              "in");
         const double total = o->cdf[o->n_cells - 1];
         if (!(total > 0.0) || !std::isfinite(total))
-            return afail(EHM_E_INVALID, "applied audit: the cells have no volume");
+            return a_err.fail(EHM_E_INVALID, "applied audit: the cells have no volume");
     }
     return EHM_OK;
 }
@@ -210,15 +154,14 @@ const char* ehm_applied_last_error(void) { return a_err.c_str(); }
 int ehm_applied_abi_sizes(int64_t* sizes, int32_t n) {
     const int64_t all[] = {(int64_t)sizeof(ehm_applied_opts), (int64_t)sizeof(ehm_applied_result),
                            (int64_t)sizeof(ehm_applied_samples)};
-    const int32_t known = (int32_t)(sizeof all / sizeof all[0]);
-    for (int32_t k = 0; sizes && k < n && k < known; ++k) sizes[k] = all[k];
-    return known;
+    return ehm_copy_abi_sizes(all, (int32_t)(sizeof all / sizeof all[0]), sizes, n);
 }
 
 int ehm_compiled_audit(ehm_compiled* law, ehm_problem* oracle, ehm_problem* applied,
                        const ehm_applied_opts* o, ehm_applied_result* res,
                        const ehm_applied_samples* smp) {
-    if (!oracle || !applied || !res) return afail(EHM_E_INVALID, "applied audit: bad argument");
+    if (!oracle || !applied || !res) return a_err.fail(EHM_E_INVALID, "applied audit: bad "
+                                                       "argument");
     int rc = check_opts(law, o);
     if (rc) return rc;
     std::memset(res, 0, sizeof *res);
@@ -231,41 +174,42 @@ int ehm_compiled_audit(ehm_compiled* law, ehm_problem* oracle, ehm_problem* appl
     if (o->n == 0) return EHM_OK;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || o->device < 0 || o->device >= ndev)
-        return afail(EHM_E_NO_DEVICE, "no HIP device %d (libehmpc has no CPU fallback)",
-                     (int)o->device);
-    P_TRY(hipSetDevice(o->device));
+        return a_err.fail(EHM_E_NO_DEVICE, "no HIP device %d (libehmpc has no CPU fallback)",
+                          (int)o->device);
+    EHM_HIP_TRY(a_err, hipSetDevice(o->device));
     const int p = o->p, n_u = o->n_u, pp = p + n_u;
     const bool draw = o->x == nullptr;
     Stream stream;
-    P_TRY(stream.create());
+    EHM_HIP_TRY(a_err, stream.create());
     DevBuf cvert, ccdf, dcost;
     if (draw) {
-        P_TRY(cvert.upload(o->cell_vertices,
-                           (size_t)o->n_cells * (size_t)(p + 1) * p * sizeof(double)));
-        P_TRY(ccdf.upload(o->cdf, (size_t)o->n_cells * sizeof(double)));
+        EHM_HIP_TRY(a_err, cvert.upload(o->cell_vertices,
+                                        (size_t)o->n_cells * (size_t)(p + 1) * p * sizeof(double)));
+        EHM_HIP_TRY(a_err, ccdf.upload(o->cdf, (size_t)o->n_cells * sizeof(double)));
     }
-    P_TRY(dcost.upload(o->cost_u, (size_t)n_u * sizeof(double)));
+    EHM_HIP_TRY(a_err, dcost.upload(o->cost_u, (size_t)n_u * sizeof(double)));
     const long long chunk = o->chunk > 0 ? o->chunk : 65536;
     const size_t cap = (size_t)std::min<long long>(chunk, o->n);
-    const unsigned max_blocks = blocks_of((long long)cap);
+    const unsigned max_blocks = blocks_of((long long)cap, EHM_APPLIED_BLOCK);
     DevBuf dx, dcell, du, dtheta, dkonst, dflag, dju, dvstar, ddidx, ddidxu, dvu, dstatus, dcnt,
         dbr, dbi;
-    P_TRY(dx.alloc(cap * p * sizeof(double)));
-    P_TRY(dcell.alloc(cap * sizeof(int32_t)));
-    P_TRY(du.alloc(cap * n_u * sizeof(double)));
-    P_TRY(dtheta.alloc(cap * pp * sizeof(double)));
-    P_TRY(dkonst.alloc(cap * sizeof(double)));
-    P_TRY(dflag.alloc(cap * sizeof(int32_t)));
-    P_TRY(dju.alloc(cap * sizeof(double)));
-    P_TRY(dvstar.alloc(cap * sizeof(double)));
-    P_TRY(ddidx.alloc(cap * sizeof(int32_t)));
-    P_TRY(ddidxu.alloc(cap * sizeof(int32_t)));
-    P_TRY(dvu.alloc(cap * sizeof(double)));
-    P_TRY(dstatus.alloc(cap * sizeof(int32_t)));
-    P_TRY(dcnt.alloc(EHM_APPLIED_COUNTERS * sizeof(unsigned long long)));
-    P_TRY(dbr.alloc(max_blocks * sizeof(double)));
-    P_TRY(dbi.alloc(max_blocks * sizeof(unsigned long long)));
-    P_TRY(hipMemsetAsync(dcnt.ptr, 0, EHM_APPLIED_COUNTERS * sizeof(unsigned long long), stream));
+    EHM_HIP_TRY(a_err, dx.alloc(cap * p * sizeof(double)));
+    EHM_HIP_TRY(a_err, dcell.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(a_err, du.alloc(cap * n_u * sizeof(double)));
+    EHM_HIP_TRY(a_err, dtheta.alloc(cap * pp * sizeof(double)));
+    EHM_HIP_TRY(a_err, dkonst.alloc(cap * sizeof(double)));
+    EHM_HIP_TRY(a_err, dflag.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(a_err, dju.alloc(cap * sizeof(double)));
+    EHM_HIP_TRY(a_err, dvstar.alloc(cap * sizeof(double)));
+    EHM_HIP_TRY(a_err, ddidx.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(a_err, ddidxu.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(a_err, dvu.alloc(cap * sizeof(double)));
+    EHM_HIP_TRY(a_err, dstatus.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(a_err, dcnt.alloc(EHM_APPLIED_COUNTERS * sizeof(unsigned long long)));
+    EHM_HIP_TRY(a_err, dbr.alloc(max_blocks * sizeof(double)));
+    EHM_HIP_TRY(a_err, dbi.alloc(max_blocks * sizeof(unsigned long long)));
+    EHM_HIP_TRY(a_err, hipMemsetAsync(dcnt.ptr, 0,
+                                      EHM_APPLIED_COUNTERS * sizeof(unsigned long long), stream));
     std::vector<double> hx(draw ? cap * p : 0), hu(o->u && !law && !o->source ? 0 : cap * n_u),
         htheta(cap * pp), hJ(cap), hJu(cap), hvu(cap), hbr(max_blocks);
     std::vector<int32_t> hcell(cap, -1), hleaf(cap, -1), hdidx(cap), hdidxu(cap), hrelaxed(cap, 0);
@@ -274,12 +218,12 @@ int ehm_compiled_audit(ehm_compiled* law, ehm_problem* oracle, ehm_problem* appl
     std::vector<int32_t> dsub;
     std::vector<unsigned long long> hbi(max_blocks);
     EventPair ev_s, ev_p, ev_r;
-    uint64_t best_id = EHM_APPLIED_NO_ID;
+    unsigned long long best_id = EHM_APPLIED_NO_ID;
     double best_ratio = -INFINITY;
     for (long long off = 0; off < o->n; off += chunk) {
         const long long nc = std::min<long long>(chunk, o->n - off);
         const uint64_t first = o->first + (uint64_t)off;
-        const unsigned nb = blocks_of(nc);
+        const unsigned nb = blocks_of(nc, EHM_APPLIED_BLOCK);
         // the points
         const double* xs = draw ? hx.data() : o->x + (size_t)off * p;
         if (draw) {
@@ -289,59 +233,60 @@ int ehm_compiled_audit(ehm_compiled* law, ehm_problem* oracle, ehm_problem* appl
                                     cvert.as<const double>(), dx.as<double>(),
                                     dcell.as<int32_t>());
             (void)hipEventRecord(ev_s.e1, stream);
-            P_TRY(hipGetLastError());
-            P_TRY(hipMemcpyAsync(hx.data(), dx.ptr, (size_t)nc * p * sizeof(double),
-                                 hipMemcpyDeviceToHost, stream));
-            P_TRY(hipMemcpyAsync(hcell.data(), dcell.ptr, (size_t)nc * sizeof(int32_t),
-                                 hipMemcpyDeviceToHost, stream));
-            P_TRY(hipStreamSynchronize(stream));
+            EHM_HIP_TRY(a_err, hipGetLastError());
+            EHM_HIP_TRY(a_err, hipMemcpyAsync(hx.data(), dx.ptr, (size_t)nc * p * sizeof(double),
+                                              hipMemcpyDeviceToHost, stream));
+            EHM_HIP_TRY(a_err, hipMemcpyAsync(hcell.data(), dcell.ptr, (size_t)nc * sizeof(int32_t),
+                                              hipMemcpyDeviceToHost, stream));
+            EHM_HIP_TRY(a_err, hipStreamSynchronize(stream));
             double s = 0.0;
             ev_s.seconds(&s);
             res->seconds[0] += s;
         } else {
-            P_TRY(hipMemcpyAsync(dx.ptr, xs, (size_t)nc * p * sizeof(double),
-                                 hipMemcpyHostToDevice, stream));
+            EHM_HIP_TRY(a_err, hipMemcpyAsync(dx.ptr, xs, (size_t)nc * p * sizeof(double),
+                                              hipMemcpyHostToDevice, stream));
         }
         // the input the law applies there: the law's own entry point
         const double* us = hu.data();
         if (law) {
             double s = 0.0;
             rc = ehm_compiled_eval_batch(law, nc, xs, hu.data(), hleaf.data(), nullptr, &s);
-            if (rc) return afail(rc, "applied audit: ehm_compiled_eval_batch: %s",
-                                 ehm_compiled_last_error());
+            if (rc) return a_err.fail(rc, "applied audit: ehm_compiled_eval_batch: %s",
+                                      ehm_compiled_last_error());
             res->seconds[1] += s;
         } else if (o->source) {
             double s = 0.0;
             rc = ehm_explicit_eval_batch(o->source, nc, xs, hu.data(), hleaf.data(), nullptr, &s);
-            if (rc) return afail(rc, "applied audit: ehm_explicit_eval_batch: %s",
-                                 ehm_explicit_last_error());
+            if (rc) return a_err.fail(rc, "applied audit: ehm_explicit_eval_batch: %s",
+                                      ehm_explicit_last_error());
             res->seconds[1] += s;
         } else {
             us = o->u + (size_t)off * n_u;
         }
-        P_TRY(hipSetDevice(o->device));
-        P_TRY(hipMemcpyAsync(du.ptr, us, (size_t)nc * n_u * sizeof(double), hipMemcpyHostToDevice,
-                             stream));
+        EHM_HIP_TRY(a_err, hipSetDevice(o->device));
+        EHM_HIP_TRY(a_err, hipMemcpyAsync(du.ptr, us, (size_t)nc * n_u * sizeof(double),
+                                          hipMemcpyHostToDevice, stream));
         (void)hipEventRecord(ev_p.e0, stream);
         hipLaunchKernelGGL(k_applied_pack, dim3(nb), dim3(EHM_APPLIED_BLOCK), 0, stream, nc, p, n_u,
                            dx.as<const double>(), du.as<const double>(),
                            dcost.as<const double>(), dtheta.as<double>(), dkonst.as<double>(),
                            dflag.as<int32_t>());
         (void)hipEventRecord(ev_p.e1, stream);
-        P_TRY(hipGetLastError());
-        P_TRY(hipMemcpyAsync(htheta.data(), dtheta.ptr, (size_t)nc * pp * sizeof(double),
-                             hipMemcpyDeviceToHost, stream));
-        P_TRY(hipStreamSynchronize(stream));
+        EHM_HIP_TRY(a_err, hipGetLastError());
+        EHM_HIP_TRY(a_err, hipMemcpyAsync(htheta.data(), dtheta.ptr,
+                                          (size_t)nc * pp * sizeof(double), hipMemcpyDeviceToHost,
+                                          stream));
+        EHM_HIP_TRY(a_err, hipStreamSynchronize(stream));
         // V* and V_u: the entry point GpuProblem.solve_pt calls, each on its problem's own stream
         auto t0 = std::chrono::steady_clock::now();
         rc = ehm_solve_pt_batch(oracle, nc, xs, hJ.data(), nullptr, hdidx.data());
         res->seconds[3] += wall_since(t0);
-        if (rc) return afail(rc, "applied audit: ehm_solve_pt_batch (oracle): %s",
-                             ehm_last_error());
+        if (rc) return a_err.fail(rc, "applied audit: ehm_solve_pt_batch (oracle): %s",
+                                  ehm_last_error());
         t0 = std::chrono::steady_clock::now();
         rc = ehm_solve_pt_batch(applied, nc, htheta.data(), hJu.data(), nullptr, hdidxu.data());
-        if (rc) return afail(rc, "applied audit: ehm_solve_pt_batch (applied): %s",
-                             ehm_last_error());
+        if (rc) return a_err.fail(rc, "applied audit: ehm_solve_pt_batch (applied): %s",
+                                  ehm_last_error());
         // an input that is not admissible as it stands: once more on the widened problem
         std::fill(hrelaxed.begin(), hrelaxed.begin() + nc, 0);
         if (o->relaxed) {
@@ -358,8 +303,8 @@ int ehm_compiled_audit(ehm_compiled* law, ehm_problem* oracle, ehm_problem* appl
                                 pp * sizeof(double));
                 rc = ehm_solve_pt_batch(o->relaxed, (int64_t)na, tsub.data(), jsub.data(), nullptr,
                                         dsub.data());
-                if (rc) return afail(rc, "applied audit: ehm_solve_pt_batch (relaxed): %s",
-                                     ehm_last_error());
+                if (rc) return a_err.fail(rc, "applied audit: ehm_solve_pt_batch (relaxed): %s",
+                                          ehm_last_error());
                 for (size_t a = 0; a < na; ++a)
                     if (dsub[a] >= 0) {
                         hJu[again[a]] = jsub[a];
@@ -370,15 +315,15 @@ int ehm_compiled_audit(ehm_compiled* law, ehm_problem* oracle, ehm_problem* appl
             }
         }
         res->seconds[4] += wall_since(t0);
-        P_TRY(hipSetDevice(o->device));
-        P_TRY(hipMemcpyAsync(dvstar.ptr, hJ.data(), (size_t)nc * sizeof(double),
-                             hipMemcpyHostToDevice, stream));
-        P_TRY(hipMemcpyAsync(ddidx.ptr, hdidx.data(), (size_t)nc * sizeof(int32_t),
-                             hipMemcpyHostToDevice, stream));
-        P_TRY(hipMemcpyAsync(dju.ptr, hJu.data(), (size_t)nc * sizeof(double),
-                             hipMemcpyHostToDevice, stream));
-        P_TRY(hipMemcpyAsync(ddidxu.ptr, hdidxu.data(), (size_t)nc * sizeof(int32_t),
-                             hipMemcpyHostToDevice, stream));
+        EHM_HIP_TRY(a_err, hipSetDevice(o->device));
+        EHM_HIP_TRY(a_err, hipMemcpyAsync(dvstar.ptr, hJ.data(), (size_t)nc * sizeof(double),
+                                          hipMemcpyHostToDevice, stream));
+        EHM_HIP_TRY(a_err, hipMemcpyAsync(ddidx.ptr, hdidx.data(), (size_t)nc * sizeof(int32_t),
+                                          hipMemcpyHostToDevice, stream));
+        EHM_HIP_TRY(a_err, hipMemcpyAsync(dju.ptr, hJu.data(), (size_t)nc * sizeof(double),
+                                          hipMemcpyHostToDevice, stream));
+        EHM_HIP_TRY(a_err, hipMemcpyAsync(ddidxu.ptr, hdidxu.data(), (size_t)nc * sizeof(int32_t),
+                                          hipMemcpyHostToDevice, stream));
         (void)hipEventRecord(ev_r.e0, stream);
         hipLaunchKernelGGL(k_applied_reduce, dim3(nb), dim3(EHM_APPLIED_BLOCK), 0, stream, nc,
                            first,
@@ -389,17 +334,18 @@ int ehm_compiled_audit(ehm_compiled* law, ehm_problem* oracle, ehm_problem* appl
                            dcnt.as<unsigned long long>(), dbr.as<double>(),
                            dbi.as<unsigned long long>());
         (void)hipEventRecord(ev_r.e1, stream);
-        P_TRY(hipGetLastError());
-        P_TRY(hipMemcpyAsync(hbr.data(), dbr.ptr, nb * sizeof(double), hipMemcpyDeviceToHost,
-                             stream));
-        P_TRY(hipMemcpyAsync(hbi.data(), dbi.ptr, nb * sizeof(unsigned long long),
-                             hipMemcpyDeviceToHost, stream));
-        P_TRY(hipMemcpyAsync(hvu.data(), dvu.ptr, (size_t)nc * sizeof(double),
-                             hipMemcpyDeviceToHost, stream));
+        EHM_HIP_TRY(a_err, hipGetLastError());
+        EHM_HIP_TRY(a_err, hipMemcpyAsync(hbr.data(), dbr.ptr, nb * sizeof(double),
+                                          hipMemcpyDeviceToHost, stream));
+        EHM_HIP_TRY(a_err, hipMemcpyAsync(hbi.data(), dbi.ptr, nb * sizeof(unsigned long long),
+                                          hipMemcpyDeviceToHost, stream));
+        EHM_HIP_TRY(a_err, hipMemcpyAsync(hvu.data(), dvu.ptr, (size_t)nc * sizeof(double),
+                                          hipMemcpyDeviceToHost, stream));
         if (smp && smp->status)
-            P_TRY(hipMemcpyAsync(smp->status + off, dstatus.ptr, (size_t)nc * sizeof(int32_t),
-                                 hipMemcpyDeviceToHost, stream));
-        P_TRY(hipStreamSynchronize(stream));
+            EHM_HIP_TRY(a_err, hipMemcpyAsync(smp->status + off, dstatus.ptr,
+                                              (size_t)nc * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                              stream));
+        EHM_HIP_TRY(a_err, hipStreamSynchronize(stream));
         if (smp) {
             const size_t n8 = (size_t)nc * sizeof(double), n4 = (size_t)nc * sizeof(int32_t);
             if (smp->x) std::memcpy(smp->x + (size_t)off * p, xs, n8 * p);
@@ -419,15 +365,8 @@ int ehm_compiled_audit(ehm_compiled* law, ehm_problem* oracle, ehm_problem* appl
         ev_r.seconds(&s);
         res->seconds[2] += s;
         // merge the workgroups' worst samples
-        bool moved = false;
-        for (unsigned b = 0; b < nb; ++b)
-            if (hbi[b] != EHM_APPLIED_NO_ID &&
-                (hbr[b] > best_ratio || (hbr[b] == best_ratio && hbi[b] < best_id))) {
-                best_ratio = hbr[b];
-                best_id = hbi[b];
-                moved = true;
-            }
-        if (moved) {
+        if (ehm_verdict::merge_block_worst(hbr.data(), hbi.data(), nb, EHM_APPLIED_NO_ID,
+                                           ehm_verdict::ratio_beats, best_ratio, best_id)) {
             const size_t q = (size_t)(best_id - first);
             res->worst_id = (int64_t)best_id;
             res->worst_leaf = hleaf[q];
@@ -440,7 +379,7 @@ int ehm_compiled_audit(ehm_compiled* law, ehm_problem* oracle, ehm_problem* appl
         }
     }
     unsigned long long cnt[EHM_APPLIED_COUNTERS];
-    P_TRY(hipMemcpy(cnt, dcnt.ptr, sizeof cnt, hipMemcpyDeviceToHost));
+    EHM_HIP_TRY(a_err, hipMemcpy(cnt, dcnt.ptr, sizeof cnt, hipMemcpyDeviceToHost));
     for (int i = 0; i < 6; ++i) res->counts[i] = (int64_t)cnt[i];
     for (int i = 0; i < EHM_APPLIED_BINS; ++i) res->histogram[i] = (int64_t)cnt[6 + i];
     return EHM_OK;

@@ -6,7 +6,8 @@
 //                    functions of ehm_explicit_dev.h, root locator included), the weights in the
 //                    located leaf, Vbar interpolated from the leaf's vertex costs
 //   k_audit_reduce   statuses, counts and the histogram by integer atomics, the worst sample by a
-//                    per-workgroup reduction the host merges (ties to the smaller id)
+//                    per-workgroup reduction the host merges (ties to the smaller id; a NaN ratio
+//                    is binned and never the worst): the rules and the tree of ehm_verdict.h
 //
 // V* and delta_idx come from ehm_solve_pt_batch itself (its re-solve of stalled LPs included): the
 // points of a chunk make one round trip through the host, which the LPs dwarf.  All arithmetic
@@ -29,9 +30,10 @@
 #include "ehm_explicit_view.h"
 #include "ehm_host.h"
 #include "ehm_philox.h"
+#include "ehm_verdict.h"
 
 #define EHM_AUDIT_BLOCK 256
-#define EHM_AUDIT_BINS 33
+#define EHM_AUDIT_BINS EHM_VERDICT_BINS
 // counters of a run: [0..4] statuses, [5] relocated, [6..38] histogram
 #define EHM_AUDIT_COUNTERS (5 + 1 + EHM_AUDIT_BINS)
 #define EHM_AUDIT_NO_ID 0xffffffffffffffffULL
@@ -118,11 +120,6 @@ __global__ void k_audit_cost(DevExplicit E, long long n, const double* __restric
     closed[q] = nflags[k] & 1;
 }
 
-// (ratio, id) a beats b: the larger ratio, the smaller id on ties (a NaN ratio never wins)
-__device__ __forceinline__ bool audit_beats(double ra, uint64_t ia, double rb, uint64_t ib) {
-    return ra > rb || (ra == rb && ia < ib);
-}
-
 __global__ __launch_bounds__(EHM_AUDIT_BLOCK) void k_audit_reduce(
     long long n, uint64_t first, const double* __restrict__ vbar, const double* __restrict__ vstar,
     const int32_t* __restrict__ didx, const int32_t* __restrict__ closed,
@@ -132,68 +129,43 @@ __global__ __launch_bounds__(EHM_AUDIT_BLOCK) void k_audit_reduce(
     double* __restrict__ blk_ratio, unsigned long long* __restrict__ blk_id) {
 #pragma clang fp contract(off)
     __shared__ unsigned int cnt[EHM_AUDIT_COUNTERS];
-    __shared__ double sr[EHM_AUDIT_BLOCK];
-    __shared__ unsigned long long si[EHM_AUDIT_BLOCK];
-    const int t = threadIdx.x;
-    for (int i = t; i < EHM_AUDIT_COUNTERS; i += EHM_AUDIT_BLOCK) cnt[i] = 0;
+    ehm_verdict::counters_zero<EHM_AUDIT_BLOCK>(cnt);
     __syncthreads();
-    const long long q = (long long)blockIdx.x * EHM_AUDIT_BLOCK + t;
+    const long long q = (long long)blockIdx.x * EHM_AUDIT_BLOCK + threadIdx.x;
     double ratio = -INFINITY;
     unsigned long long id = EHM_AUDIT_NO_ID;
     if (q < n) {
         const double vs = vstar[q];
         const double gap = vbar[q] - vs;
-        const double er = eps_r * vs;
-        const double bound = eps_a > er ? eps_a : er;
-        const double slack = rtol * (1.0 + fabs(vs));
-        int st = 0;
+        const double bound = ehm_verdict::bound_of(eps_a, eps_r, vs);
+        int st;
         if (didx[q] < 0) st = 4;
         else if (!closed[q]) st = 3;
-        else if (!(gap >= -slack)) st = 2;
-        else if (gap > bound + slack) st = 1;
+        else st = ehm_verdict::gap_status(gap, bound, ehm_verdict::slack_of(rtol, vs));
         status[q] = st;
         atomicAdd(&cnt[st], 1u);
         if (leaf[q] != cell_node[cell[q]]) atomicAdd(&cnt[5], 1u);
         if (st <= 2) {
-            const double r = gap / bound;
-            int bin = 0;                            // negative (and NaN) ratios: bin 0
-            if (r > 1.0) bin = EHM_AUDIT_BINS - 1;
-            else if (r >= 0.0) {
-                bin = (int)(r * 32.0);
-                bin = bin > 31 ? 31 : bin;
+            const double r = ehm_verdict::ratio_of(gap, bound);
+            atomicAdd(&cnt[6 + ehm_verdict::ratio_bin(r)], 1u);
+            if (ehm_verdict::ratio_is_candidate(r)) {
+                ratio = r;
+                id = first + (unsigned long long)q;
             }
-            atomicAdd(&cnt[6 + bin], 1u);
-            ratio = r;
-            id = first + (unsigned long long)q;
         }
     }
-    sr[t] = ratio;
-    si[t] = id;
-    __syncthreads();
-    for (int h = EHM_AUDIT_BLOCK / 2; h > 0; h >>= 1) {
-        if (t < h && audit_beats(sr[t + h], si[t + h], sr[t], si[t])) {
-            sr[t] = sr[t + h];
-            si[t] = si[t + h];
-        }
-        __syncthreads();
+    ehm_verdict::block_worst<EHM_AUDIT_BLOCK>(
+        ratio, id,
+        [](double ra, unsigned long long ia, double rb, unsigned long long ib) {
+            return ehm_verdict::ratio_beats(ra, ia, rb, ib);
+        },
+        [](unsigned long long i) { return i != EHM_AUDIT_NO_ID; });
+    if (threadIdx.x == 0) {
+        blk_ratio[blockIdx.x] = ratio;
+        blk_id[blockIdx.x] = id;
     }
-    if (t == 0) {
-        blk_ratio[blockIdx.x] = sr[0];
-        blk_id[blockIdx.x] = si[0];
-    }
-    for (int i = t; i < EHM_AUDIT_COUNTERS; i += EHM_AUDIT_BLOCK)
-        if (cnt[i]) atomicAdd(&counters[i], (unsigned long long)cnt[i]);
+    ehm_verdict::counters_flush<EHM_AUDIT_BLOCK>(cnt, counters);
 }
-
-#define A_TRY(expr)                                                                        \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return ehm_explicit_fail(EHM_E_HIP, "%s failed: %s", #expr,                    \
-                                     hipGetErrorString(e_));                               \
-    } while (0)
-
-unsigned blocks_of(long long n) { return (unsigned)((n + EHM_AUDIT_BLOCK - 1) / EHM_AUDIT_BLOCK); }
 
 // what both entry points ask of opts; `audit`: also the fields the sampler alone does not read
 int check_opts(const ehm_explicit_view& v, const ehm_audit_opts* o, bool audit) {
@@ -234,10 +206,13 @@ int check_opts(const ehm_explicit_view& v, const ehm_audit_opts* o, bool audit) 
 struct Cells {
     DevBuf vert, cdf, node;
     int upload(const ehm_explicit_view& v, const ehm_audit_opts* o, bool audit) {
+        ehm_err_channel& x_err = ehm_explicit_channel();
         const size_t nc = (size_t)o->n_cells;
-        A_TRY(vert.upload(o->cell_vertices, nc * (size_t)(v.p + 1) * v.p * sizeof(double)));
-        if (o->mode == EHM_AUDIT_UNIFORM) A_TRY(cdf.upload(o->cdf, nc * sizeof(double)));
-        if (audit) A_TRY(node.upload(o->cell_node, nc * sizeof(int32_t)));
+        EHM_HIP_TRY(x_err, vert.upload(o->cell_vertices,
+                                       nc * (size_t)(v.p + 1) * v.p * sizeof(double)));
+        if (o->mode == EHM_AUDIT_UNIFORM)
+            EHM_HIP_TRY(x_err, cdf.upload(o->cdf, nc * sizeof(double)));
+        if (audit) EHM_HIP_TRY(x_err, node.upload(o->cell_node, nc * sizeof(int32_t)));
         return EHM_OK;
     }
 };
@@ -254,8 +229,8 @@ void launch_sample(const ehm_explicit_view& v, const ehm_audit_opts* o, const Ce
 void ehm_audit_launch_sample(hipStream_t stream, long long n, uint64_t first, int mode, int kper,
                              uint64_t seed, int p, long long n_cells, const double* cdf,
                              const double* V, double* X, int32_t* cell) {
-    hipLaunchKernelGGL(k_audit_sample, dim3(blocks_of(n)), dim3(EHM_AUDIT_BLOCK), 0, stream, n,
-                       first, mode, kper, seed, p, n_cells, cdf, V, X, cell);
+    hipLaunchKernelGGL(k_audit_sample, dim3(blocks_of(n, EHM_AUDIT_BLOCK)), dim3(EHM_AUDIT_BLOCK),
+                       0, stream, n, first, mode, kper, seed, p, n_cells, cdf, V, X, cell);
 }
 
 extern "C" {
@@ -263,38 +238,38 @@ extern "C" {
 int ehm_audit_abi_sizes(int64_t* sizes, int32_t n) {
     const int64_t all[] = {(int64_t)sizeof(ehm_audit_opts), (int64_t)sizeof(ehm_audit_result),
                            (int64_t)sizeof(ehm_audit_samples)};
-    const int32_t known = (int32_t)(sizeof all / sizeof all[0]);
-    for (int32_t k = 0; sizes && k < n && k < known; ++k) sizes[k] = all[k];
-    return known;
+    return ehm_copy_abi_sizes(all, (int32_t)(sizeof all / sizeof all[0]), sizes, n);
 }
 
 int ehm_explicit_sample(ehm_explicit* E, const ehm_audit_opts* o, double* x, int32_t* cell) {
     if (!E) return ehm_explicit_fail(EHM_E_INVALID, "sample: no handle");
+    ehm_err_channel& x_err = ehm_explicit_channel();
     ehm_explicit_view v;
     ehm_explicit_get_view(E, &v);
     int rc = check_opts(v, o, false);
     if (rc || o->n == 0) return rc;
-    A_TRY(hipSetDevice(v.device));
+    EHM_HIP_TRY(x_err, hipSetDevice(v.device));
     Cells C;
     rc = C.upload(v, o, false);
     if (rc) return rc;
     const long long chunk = o->chunk > 0 ? o->chunk : 65536;
     const long long cap = std::min<long long>(chunk, o->n);
     DevBuf dx, dcell;
-    A_TRY(dx.alloc((size_t)cap * v.p * sizeof(double)));
-    A_TRY(dcell.alloc((size_t)cap * sizeof(int32_t)));
+    EHM_HIP_TRY(x_err, dx.alloc((size_t)cap * v.p * sizeof(double)));
+    EHM_HIP_TRY(x_err, dcell.alloc((size_t)cap * sizeof(int32_t)));
     for (long long off = 0; off < o->n; off += chunk) {
         const long long nc = std::min<long long>(chunk, o->n - off);
         launch_sample(v, o, C, nc, o->first + (uint64_t)off, dx.as<double>(),
                       dcell.as<int32_t>());
-        A_TRY(hipGetLastError());
+        EHM_HIP_TRY(x_err, hipGetLastError());
         if (x)
-            A_TRY(hipMemcpyAsync(x + (size_t)off * v.p, dx.ptr, (size_t)nc * v.p * sizeof(double),
-                                 hipMemcpyDeviceToHost, v.stream));
+            EHM_HIP_TRY(x_err, hipMemcpyAsync(x + (size_t)off * v.p, dx.ptr,
+                                              (size_t)nc * v.p * sizeof(double),
+                                              hipMemcpyDeviceToHost, v.stream));
         if (cell)
-            A_TRY(hipMemcpyAsync(cell + off, dcell.ptr, (size_t)nc * sizeof(int32_t),
-                                 hipMemcpyDeviceToHost, v.stream));
-        A_TRY(hipStreamSynchronize(v.stream));
+            EHM_HIP_TRY(x_err, hipMemcpyAsync(cell + off, dcell.ptr, (size_t)nc * sizeof(int32_t),
+                                              hipMemcpyDeviceToHost, v.stream));
+        EHM_HIP_TRY(x_err, hipStreamSynchronize(v.stream));
     }
     return EHM_OK;
 }
@@ -302,6 +277,7 @@ int ehm_explicit_sample(ehm_explicit* E, const ehm_audit_opts* o, double* x, int
 int ehm_explicit_audit(ehm_explicit* E, ehm_problem* prob, const ehm_audit_opts* o,
                        ehm_audit_result* res, const ehm_audit_samples* smp) {
     if (!E || !prob || !res) return ehm_explicit_fail(EHM_E_INVALID, "audit: bad argument");
+    ehm_err_channel& x_err = ehm_explicit_channel();
     ehm_explicit_view v;
     ehm_explicit_get_view(E, &v);
     int rc = check_opts(v, o, true);
@@ -313,7 +289,7 @@ int ehm_explicit_audit(ehm_explicit* E, ehm_problem* prob, const ehm_audit_opts*
     res->worst_vbar = res->worst_vstar = res->worst_bound = NAN;
     for (double& c : res->worst_x) c = NAN;
     if (o->n == 0) return EHM_OK;
-    A_TRY(hipSetDevice(v.device));
+    EHM_HIP_TRY(x_err, hipSetDevice(v.device));
     const DevExplicit D{v.rec, v.child, v.vinput, v.rec_stride, v.p, v.n_u, v.n_roots, v.n_nodes};
     const int p = v.p;
     Cells C;
@@ -321,31 +297,32 @@ int ehm_explicit_audit(ehm_explicit* E, ehm_problem* prob, const ehm_audit_opts*
     if (rc) return rc;
     const long long chunk = o->chunk > 0 ? o->chunk : 65536;
     const size_t cap = (size_t)std::min<long long>(chunk, o->n);
-    const unsigned max_blocks = blocks_of((long long)cap);
+    const unsigned max_blocks = blocks_of((long long)cap, EHM_AUDIT_BLOCK);
     DevBuf dx, dcell, dleaf, dvbar, dwmin, dclosed, dvstar, ddidx, dstatus, dcnt, dbr, dbi;
-    A_TRY(dx.alloc(cap * p * sizeof(double)));
-    A_TRY(dcell.alloc(cap * sizeof(int32_t)));
-    A_TRY(dleaf.alloc(cap * sizeof(int32_t)));
-    A_TRY(dvbar.alloc(cap * sizeof(double)));
-    A_TRY(dwmin.alloc(cap * sizeof(double)));
-    A_TRY(dclosed.alloc(cap * sizeof(int32_t)));
-    A_TRY(dvstar.alloc(cap * sizeof(double)));
-    A_TRY(ddidx.alloc(cap * sizeof(int32_t)));
-    A_TRY(dstatus.alloc(cap * sizeof(int32_t)));
-    A_TRY(dcnt.alloc(EHM_AUDIT_COUNTERS * sizeof(unsigned long long)));
-    A_TRY(dbr.alloc(max_blocks * sizeof(double)));
-    A_TRY(dbi.alloc(max_blocks * sizeof(unsigned long long)));
-    A_TRY(hipMemsetAsync(dcnt.ptr, 0, EHM_AUDIT_COUNTERS * sizeof(unsigned long long), v.stream));
+    EHM_HIP_TRY(x_err, dx.alloc(cap * p * sizeof(double)));
+    EHM_HIP_TRY(x_err, dcell.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(x_err, dleaf.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(x_err, dvbar.alloc(cap * sizeof(double)));
+    EHM_HIP_TRY(x_err, dwmin.alloc(cap * sizeof(double)));
+    EHM_HIP_TRY(x_err, dclosed.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(x_err, dvstar.alloc(cap * sizeof(double)));
+    EHM_HIP_TRY(x_err, ddidx.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(x_err, dstatus.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(x_err, dcnt.alloc(EHM_AUDIT_COUNTERS * sizeof(unsigned long long)));
+    EHM_HIP_TRY(x_err, dbr.alloc(max_blocks * sizeof(double)));
+    EHM_HIP_TRY(x_err, dbi.alloc(max_blocks * sizeof(unsigned long long)));
+    EHM_HIP_TRY(x_err, hipMemsetAsync(dcnt.ptr, 0, EHM_AUDIT_COUNTERS * sizeof(unsigned long long),
+                                      v.stream));
     std::vector<double> hx(cap * p), hJ(cap), hbr(max_blocks);
     std::vector<int32_t> hdidx(cap);
     std::vector<unsigned long long> hbi(max_blocks);
     EventPair ev_s, ev_c, ev_r;
-    uint64_t best_id = EHM_AUDIT_NO_ID;
+    unsigned long long best_id = EHM_AUDIT_NO_ID;
     double best_ratio = -INFINITY;
     for (long long off = 0; off < o->n; off += chunk) {
         const long long nc = std::min<long long>(chunk, o->n - off);
         const uint64_t first = o->first + (uint64_t)off;
-        const unsigned nb = blocks_of(nc);
+        const unsigned nb = blocks_of(nc, EHM_AUDIT_BLOCK);
         (void)hipEventRecord(ev_s.e0, v.stream);
         launch_sample(v, o, C, nc, first, dx.as<double>(), dcell.as<int32_t>());
         (void)hipEventRecord(ev_s.e1, v.stream);
@@ -354,22 +331,21 @@ int ehm_explicit_audit(ehm_explicit* E, ehm_problem* prob, const ehm_audit_opts*
                            dx.as<const double>(), v.nbr, v.vcost, v.nflags, dleaf.as<int32_t>(),
                            dvbar.as<double>(), dwmin.as<double>(), dclosed.as<int32_t>());
         (void)hipEventRecord(ev_c.e1, v.stream);
-        A_TRY(hipGetLastError());
-        A_TRY(hipMemcpyAsync(hx.data(), dx.ptr, (size_t)nc * p * sizeof(double),
-                             hipMemcpyDeviceToHost, v.stream));
-        A_TRY(hipStreamSynchronize(v.stream));
+        EHM_HIP_TRY(x_err, hipGetLastError());
+        EHM_HIP_TRY(x_err, hipMemcpyAsync(hx.data(), dx.ptr, (size_t)nc * p * sizeof(double),
+                                          hipMemcpyDeviceToHost, v.stream));
+        EHM_HIP_TRY(x_err, hipStreamSynchronize(v.stream));
         // V* and delta_idx: the entry point GpuProblem.solve_pt calls, on the problem's own stream
         // (and device)
         const auto t0 = std::chrono::steady_clock::now();
         rc = ehm_solve_pt_batch(prob, nc, hx.data(), hJ.data(), nullptr, hdidx.data());
-        res->seconds[2] +=
-            std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        res->seconds[2] += wall_since(t0);
         if (rc) return ehm_explicit_fail(rc, "audit: ehm_solve_pt_batch: %s", ehm_last_error());
-        A_TRY(hipSetDevice(v.device));
-        A_TRY(hipMemcpyAsync(dvstar.ptr, hJ.data(), (size_t)nc * sizeof(double),
-                             hipMemcpyHostToDevice, v.stream));
-        A_TRY(hipMemcpyAsync(ddidx.ptr, hdidx.data(), (size_t)nc * sizeof(int32_t),
-                             hipMemcpyHostToDevice, v.stream));
+        EHM_HIP_TRY(x_err, hipSetDevice(v.device));
+        EHM_HIP_TRY(x_err, hipMemcpyAsync(dvstar.ptr, hJ.data(), (size_t)nc * sizeof(double),
+                                          hipMemcpyHostToDevice, v.stream));
+        EHM_HIP_TRY(x_err, hipMemcpyAsync(ddidx.ptr, hdidx.data(), (size_t)nc * sizeof(int32_t),
+                                          hipMemcpyHostToDevice, v.stream));
         (void)hipEventRecord(ev_r.e0, v.stream);
         hipLaunchKernelGGL(k_audit_reduce, dim3(nb), dim3(EHM_AUDIT_BLOCK), 0, v.stream, nc, first,
                            dvbar.as<const double>(), dvstar.as<const double>(),
@@ -379,11 +355,11 @@ int ehm_explicit_audit(ehm_explicit* E, ehm_problem* prob, const ehm_audit_opts*
                            dstatus.as<int32_t>(), dcnt.as<unsigned long long>(), dbr.as<double>(),
                            dbi.as<unsigned long long>());
         (void)hipEventRecord(ev_r.e1, v.stream);
-        A_TRY(hipGetLastError());
-        A_TRY(hipMemcpyAsync(hbr.data(), dbr.ptr, nb * sizeof(double), hipMemcpyDeviceToHost,
-                             v.stream));
-        A_TRY(hipMemcpyAsync(hbi.data(), dbi.ptr, nb * sizeof(unsigned long long),
-                             hipMemcpyDeviceToHost, v.stream));
+        EHM_HIP_TRY(x_err, hipGetLastError());
+        EHM_HIP_TRY(x_err, hipMemcpyAsync(hbr.data(), dbr.ptr, nb * sizeof(double),
+                                          hipMemcpyDeviceToHost, v.stream));
+        EHM_HIP_TRY(x_err, hipMemcpyAsync(hbi.data(), dbi.ptr, nb * sizeof(unsigned long long),
+                                          hipMemcpyDeviceToHost, v.stream));
         if (smp) {
             const size_t o8 = (size_t)off * sizeof(double), o4 = (size_t)off * sizeof(int32_t);
             const size_t n8 = (size_t)nc * sizeof(double), n4 = (size_t)nc * sizeof(int32_t);
@@ -396,10 +372,10 @@ int ehm_explicit_audit(ehm_explicit* E, ehm_problem* prob, const ehm_audit_opts*
                 {smp->status, &dstatus, o4, n4}};
             for (const auto& b : back)
                 if (b.dst)
-                    A_TRY(hipMemcpyAsync((char*)b.dst + b.at, b.src->ptr, b.bytes,
-                                         hipMemcpyDeviceToHost, v.stream));
+                    EHM_HIP_TRY(x_err, hipMemcpyAsync((char*)b.dst + b.at, b.src->ptr, b.bytes,
+                                                      hipMemcpyDeviceToHost, v.stream));
         }
-        A_TRY(hipStreamSynchronize(v.stream));
+        EHM_HIP_TRY(x_err, hipStreamSynchronize(v.stream));
         double s = 0.0;
         ev_s.seconds(&s);
         res->seconds[0] += s;
@@ -408,21 +384,17 @@ int ehm_explicit_audit(ehm_explicit* E, ehm_problem* prob, const ehm_audit_opts*
         ev_r.seconds(&s);
         res->seconds[1] += s;
         // merge the workgroups' worst samples; fetch the record of a new overall worst
-        bool moved = false;
-        for (unsigned b = 0; b < nb; ++b)
-            if (hbi[b] != EHM_AUDIT_NO_ID &&
-                (hbr[b] > best_ratio || (hbr[b] == best_ratio && hbi[b] < best_id))) {
-                best_ratio = hbr[b];
-                best_id = hbi[b];
-                moved = true;
-            }
-        if (moved) {
+        if (ehm_verdict::merge_block_worst(hbr.data(), hbi.data(), nb, EHM_AUDIT_NO_ID,
+                                           ehm_verdict::ratio_beats, best_ratio, best_id)) {
             const size_t q = (size_t)(best_id - first);
             int32_t lf = -1, cl = -1;
             double vb = NAN;
-            A_TRY(hipMemcpy(&lf, dleaf.as<int32_t>() + q, sizeof lf, hipMemcpyDeviceToHost));
-            A_TRY(hipMemcpy(&cl, dcell.as<int32_t>() + q, sizeof cl, hipMemcpyDeviceToHost));
-            A_TRY(hipMemcpy(&vb, dvbar.as<double>() + q, sizeof vb, hipMemcpyDeviceToHost));
+            EHM_HIP_TRY(x_err, hipMemcpy(&lf, dleaf.as<int32_t>() + q, sizeof lf,
+                                         hipMemcpyDeviceToHost));
+            EHM_HIP_TRY(x_err, hipMemcpy(&cl, dcell.as<int32_t>() + q, sizeof cl,
+                                         hipMemcpyDeviceToHost));
+            EHM_HIP_TRY(x_err, hipMemcpy(&vb, dvbar.as<double>() + q, sizeof vb,
+                                         hipMemcpyDeviceToHost));
             res->worst_id = (int64_t)best_id;
             res->worst_leaf = lf;
             res->worst_cell = cl;
@@ -434,7 +406,7 @@ int ehm_explicit_audit(ehm_explicit* E, ehm_problem* prob, const ehm_audit_opts*
         }
     }
     unsigned long long cnt[EHM_AUDIT_COUNTERS];
-    A_TRY(hipMemcpy(cnt, dcnt.ptr, sizeof cnt, hipMemcpyDeviceToHost));
+    EHM_HIP_TRY(x_err, hipMemcpy(cnt, dcnt.ptr, sizeof cnt, hipMemcpyDeviceToHost));
     for (int i = 0; i < 5; ++i) res->counts[i] = (int64_t)cnt[i];
     res->relocated = (int64_t)cnt[5];
     for (int i = 0; i < EHM_AUDIT_BINS; ++i) res->histogram[i] = (int64_t)cnt[6 + i];

@@ -438,24 +438,14 @@ __global__ __launch_bounds__(64) void k_vertex_solve(DevProblem P, DevTree T,
 // =========================================================================================
 // host side
 // =========================================================================================
-static thread_local std::string g_err;
-
-static int fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
+static thread_local ehm_err_channel g_err;
 
 #define HIP_TRY(expr, code)                                                              \
     do {                                                                                 \
         hipError_t e_ = (expr);                                                          \
         if (e_ != hipSuccess)                                                            \
-            return fail(code, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),     \
-                        __FILE__, __LINE__);                                             \
+            return g_err.fail(code, "%s failed: %s (%s:%d)", #expr,                      \
+                              hipGetErrorString(e_), __FILE__, __LINE__);                \
     } while (0)
 
 // The node records of a tree (ehm_tree) and the arrays that grow with them.  The problem handle
@@ -589,8 +579,8 @@ static int map_deltas(ehm_problem* P, int64_t n_inst, const uint8_t* delta,
             }
         }
         if (found < 0)
-            return fail(EHM_E_INVALID, "instance %lld: not an admissible commutation",
-                        (long long)k);
+            return g_err.fail(EHM_E_INVALID, "instance %lld: not an admissible commutation",
+                              (long long)k);
         out[(size_t)k] = found;
     }
     return EHM_OK;
@@ -670,8 +660,9 @@ static int k2_config(ehm_problem* P, int kind_a, int kind_b, long long n_items, 
     const K2Api* api = k2_pick(n_lp - (P->dp.n - P->dp.nd0), slots, P->quadratic,
                                no_fits ? nullptr : &P->dp);
     if (!api)
-        return fail(EHM_E_INVALID, "no kernel instance for an LP with %d columns, %d row slots",
-                    n_lp, slots);
+        return g_err.fail(EHM_E_INVALID,
+                          "no kernel instance for an LP with %d columns, %d row slots", n_lp,
+                          slots);
     const size_t wave = api->wave_doubles(P->dp, n_lp, ne, persist ? 1 : 0);
     const size_t budget = EHM_LDS_BUDGET / sizeof(double);
     // w and c of the commutation behind the constant block in LDS -- unless that costs the
@@ -685,14 +676,16 @@ static int k2_config(ehm_problem* P, int kind_a, int kind_b, long long n_items, 
     dp.wc_lds = 0;
     const size_t shared0 = api->shared_doubles(dp);
     if (shared0 + wave > budget)
-        return fail(EHM_E_INVALID, "LP does not fit in LDS (%zu + %zu doubles)", shared0, wave);
+        return g_err.fail(EHM_E_INVALID, "LP does not fit in LDS (%zu + %zu doubles)", shared0,
+                          wave);
     const long long nw1 = (shared1 + wave <= budget)
         ? std::min<long long>(max_w, (long long)((budget - shared1) / wave)) : 0;
     const long long nw0 = std::min<long long>(max_w, (long long)((budget - shared0) / wave));
     const int wc_lds = (nw1 >= nw0 && nw1 >= 1) ? 1 : 0;
     const size_t shared = wc_lds ? shared1 : shared0;
     if (api->threads_per_lp > 64 && !api->fits && !P->dp.Wr3)
-        return fail(EHM_E_INVALID, "wide kernels selected but their constant image is missing");
+        return g_err.fail(EHM_E_INVALID,
+                          "wide kernels selected but their constant image is missing");
     // LPs per workgroup: as many wavefronts as fit (wave-local kernels); exactly one (wide)
     long long nw = wc_lds ? nw1 : nw0;
     nw = std::max(1LL, std::min(nw, n_items));
@@ -878,21 +871,23 @@ const char* ehm_last_error(void) { return g_err.c_str(); }
 const char* ehm_version(void) { return "ehmpc 0.1 (gfx950)"; }
 
 int ehm_problem_create(const ehm_problem_desc* d, int device, ehm_problem** out) {
-    if (!d || !out) return fail(EHM_E_INVALID, "null argument");
+    if (!d || !out) return g_err.fail(EHM_E_INVALID, "null argument");
     *out = nullptr;
     if (d->n < 1 || d->m < 1 || d->p < 1 || d->n_u < 1 || d->n_delta < 1)
-        return fail(EHM_E_INVALID, "non-positive dimension");
+        return g_err.fail(EHM_E_INVALID, "non-positive dimension");
     if (d->p > EHM_MAX_P || d->n + d->p + 1 > EHM_MAX_N || d->m + d->p + 3 > EHM_MAX_M)
-        return fail(EHM_E_INVALID,
-                    "unsupported size: need n+p+1 <= %d, m+p+3 <= %d, p <= %d (got n=%d m=%d p=%d)",
-                    EHM_MAX_N, EHM_MAX_M, EHM_MAX_P, d->n, d->m, d->p);
+        return g_err.fail(EHM_E_INVALID,
+                          "unsupported size: need n+p+1 <= %d, m+p+3 <= %d, p <= %d "
+                          "(got n=%d m=%d p=%d)",
+                          EHM_MAX_N, EHM_MAX_M, EHM_MAX_P, d->n, d->m, d->p);
     if (d->n_u > d->n || rec_doubles(d->p, d->n_u) > NODE_LDS_DOUBLES - 8)
-        return fail(EHM_E_INVALID, "unsupported n_u=%d", d->n_u);
+        return g_err.fail(EHM_E_INVALID, "unsupported n_u=%d", d->n_u);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(EHM_E_NO_DEVICE, "no HIP device available (libehmpc has no CPU fallback)");
+        return g_err.fail(EHM_E_NO_DEVICE,
+                          "no HIP device available (libehmpc has no CPU fallback)");
     if (device < 0 || device >= ndev)
-        return fail(EHM_E_NO_DEVICE, "device %d out of range (%d devices)", device, ndev);
+        return g_err.fail(EHM_E_NO_DEVICE, "device %d out of range (%d devices)", device, ndev);
     HIP_TRY(hipSetDevice(device), EHM_E_NO_DEVICE);
     // destroyed on every error return below
     std::unique_ptr<ehm_problem, int (*)(ehm_problem*)> P(new ehm_problem(), ehm_problem_destroy);
@@ -979,8 +974,8 @@ int ehm_problem_create(const ehm_problem_desc* d, int device, ehm_problem** out)
     const size_t lds_max = std::max(P->lds_point, P->lds_simplex);
     if (lds_max > 160 * 1024 || n + p + 1 > EHM_V1_MAX_N || m + p + 3 > EHM_V1_MAX_M) {
         if (P->solver_gen == 1)
-            return fail(EHM_E_INVALID, "LP too large for the generation-1 kernels (%zu bytes)",
-                        lds_max);
+            return g_err.fail(EHM_E_INVALID,
+                              "LP too large for the generation-1 kernels (%zu bytes)", lds_max);
     } else {
         const void* kernels[] = {(const void*)k_point_batch, (const void*)k_simplex_batch,
                                  (const void*)k_lcss_decide, (const void*)k_lcss_expand,
@@ -1002,8 +997,8 @@ int ehm_problem_create(const ehm_problem_desc* d, int device, ehm_problem** out)
 int ehm_problem_update_blocks(ehm_problem* P, int32_t first, int32_t count, const double* G,
                               const double* w, const double* S) {
     if (!P || !G || !w || !S || first < 0 || count < 0 || first + count > P->dp.n_delta)
-        return fail(EHM_E_INVALID, "bad argument");
-    if (P->active_run) return fail(EHM_E_INVALID, "a partition run is active on this handle");
+        return g_err.fail(EHM_E_INVALID, "bad argument");
+    if (P->active_run) return g_err.fail(EHM_E_INVALID, "a partition run is active on this handle");
     if (count == 0) return EHM_OK;
     HIP_TRY(hipSetDevice(P->device), EHM_E_HIP);
     HIP_TRY(hipStreamSynchronize(P->stream), EHM_E_HIP);
@@ -1025,7 +1020,7 @@ int ehm_problem_destroy(ehm_problem* P) {
 }
 
 int ehm_problem_set_eps(ehm_problem* P, double eps_a, double eps_r) {
-    if (!P) return fail(EHM_E_INVALID, "null problem");
+    if (!P) return g_err.fail(EHM_E_INVALID, "null problem");
     P->dp.eps_a = eps_a;
     P->dp.eps_r = eps_r;
     return EHM_OK;
@@ -1033,11 +1028,13 @@ int ehm_problem_set_eps(ehm_problem* P, double eps_a, double eps_r) {
 
 int ehm_problem_set_quadratic(ehm_problem* P, const double* H, const double* F, const double* f0,
                               const double* C, const double* c1, const double* c0) {
-    if (!P || !H || !F || !f0 || !C || !c1 || !c0) return fail(EHM_E_INVALID, "null argument");
+    if (!P || !H || !F || !f0 || !C || !c1 || !c0)
+        return g_err.fail(EHM_E_INVALID, "null argument");
     if (!P->v1_ok)
-        return fail(EHM_E_INVALID,
-                    "quadratic costs need the one-wavefront kernels: n+p+1 <= %d, m+p+3 <= %d",
-                    EHM_V1_MAX_N, EHM_V1_MAX_M);
+        return g_err.fail(EHM_E_INVALID,
+                          "quadratic costs need the one-wavefront kernels: n+p+1 <= %d, "
+                          "m+p+3 <= %d",
+                          EHM_V1_MAX_N, EHM_V1_MAX_M);
     HIP_TRY(hipSetDevice(P->device), EHM_E_HIP);
     const int n = P->dp.n, p = P->dp.p, nd = P->dp.n_delta;
     const size_t nH = (size_t)nd * n * n, nF = (size_t)nd * p * n, nf = (size_t)nd * n;
@@ -1092,13 +1089,14 @@ int ehm_problem_set_quadratic(ehm_problem* P, const double* H, const double* F, 
 }
 
 int ehm_problem_set_solver(ehm_problem* P, int generation) {
-    if (!P) return fail(EHM_E_INVALID, "null problem");
-    if (generation != 1 && generation != 2) return fail(EHM_E_INVALID, "solver generation 1 or 2");
+    if (!P) return g_err.fail(EHM_E_INVALID, "null problem");
+    if (generation != 1 && generation != 2)
+        return g_err.fail(EHM_E_INVALID, "solver generation 1 or 2");
     if (generation == 2 && P->quadratic && !P->k2q_ok)
-        return fail(EHM_E_INVALID,
-                    "no shared-block instance with the quadratic block holds this problem");
+        return g_err.fail(EHM_E_INVALID,
+                          "no shared-block instance with the quadratic block holds this problem");
     if (generation == 1 && !P->v1_ok)
-        return fail(EHM_E_INVALID, "the generation-1 kernels do not fit this problem in LDS");
+        return g_err.fail(EHM_E_INVALID, "the generation-1 kernels do not fit this problem in LDS");
     P->solver_gen = generation;
     return EHM_OK;
 }
@@ -1108,16 +1106,15 @@ int ehm_abi_sizes(int64_t* sizes, int32_t n) {
     const int64_t all[] = {(int64_t)sizeof(ehm_problem_desc), (int64_t)sizeof(ehm_run_opts),
                            (int64_t)sizeof(ehm_node_init),    (int64_t)sizeof(ehm_progress),
                            (int64_t)sizeof(ehm_tree_info),    (int64_t)sizeof(ehm_counters)};
-    const int32_t known = (int32_t)(sizeof all / sizeof all[0]);
-    for (int32_t k = 0; sizes && k < n && k < known; ++k) sizes[k] = all[k];
-    return known;
+    return ehm_copy_abi_sizes(all, (int32_t)(sizeof all / sizeof all[0]), sizes, n);
 }
 
 int ehm_selftest(int device, double* out, int32_t max_instances, int32_t* n_instances) {
-    if (!out || !n_instances) return fail(EHM_E_INVALID, "null argument");
+    if (!out || !n_instances) return g_err.fail(EHM_E_INVALID, "null argument");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return fail(EHM_E_NO_DEVICE, "no HIP device %d (libehmpc has no CPU fallback)", device);
+        return g_err.fail(EHM_E_NO_DEVICE, "no HIP device %d (libehmpc has no CPU fallback)",
+                          device);
     HIP_TRY(hipSetDevice(device), EHM_E_NO_DEVICE);
     DevBuf d_out;
     HIP_TRY(d_out.alloc(5 * sizeof(double)), EHM_E_HIP);
@@ -1135,7 +1132,7 @@ int ehm_selftest(int device, double* out, int32_t max_instances, int32_t* n_inst
 }
 
 int ehm_problem_set_option(ehm_problem* P, const char* name, double value) {
-    if (!P || !name) return fail(EHM_E_INVALID, "null argument");
+    if (!P || !name) return g_err.fail(EHM_E_INVALID, "null argument");
     if (!strcmp(name, "solver")) return ehm_problem_set_solver(P, (int)value);
     if (!strcmp(name, "decide_full")) {
         P->decide_full = value != 0.0;
@@ -1178,18 +1175,19 @@ int ehm_problem_set_option(ehm_problem* P, const char* name, double value) {
         return EHM_OK;
     }
     if (!strcmp(name, "any_admissible")) {
-        if (value < 0.0 || value > 2e9) return fail(EHM_E_INVALID, "any_admissible: seed + 1, or 0");
+        if (value < 0.0 || value > 2e9)
+            return g_err.fail(EHM_E_INVALID, "any_admissible: seed + 1, or 0");
         // the path codes the hashed draws read are allocated when a run begins (hy_begin)
         if (P->active_run)
-            return fail(EHM_E_INVALID, "any_admissible: not while a partition run is active");
+            return g_err.fail(EHM_E_INVALID, "any_admissible: not while a partition run is active");
         P->any_admissible = (int)value;
         return EHM_OK;
     }
-    return fail(EHM_E_INVALID, "unknown option '%s'", name);
+    return g_err.fail(EHM_E_INVALID, "unknown option '%s'", name);
 }
 
 int ehm_sync(ehm_problem* P) {
-    if (!P) return fail(EHM_E_INVALID, "null problem");
+    if (!P) return g_err.fail(EHM_E_INVALID, "null problem");
     HIP_TRY(hipStreamSynchronize(P->stream), EHM_E_HIP);
     return EHM_OK;
 }
@@ -1197,7 +1195,7 @@ int ehm_sync(ehm_problem* P) {
 void* ehm_stream(ehm_problem* P) { return P ? (void*)P->stream : nullptr; }
 
 int ehm_stats(ehm_problem* P, ehm_counters* out) {
-    if (!P || !out) return fail(EHM_E_INVALID, "null argument");
+    if (!P || !out) return g_err.fail(EHM_E_INVALID, "null argument");
     HIP_TRY(hipSetDevice(P->device), EHM_E_HIP);
     DevCounters c;
     HIP_TRY(hipStreamSynchronize(P->stream), EHM_E_HIP);
@@ -1385,7 +1383,7 @@ static int point_batch(ehm_problem* P, int64_t n_inst, const double* theta,
 int ehm_solve_ptd_batch(ehm_problem* P, int64_t n_inst, const double* theta,
                         const uint8_t* delta, double* J, double* u0, int32_t* status,
                         int32_t* iters) {
-    if (!P || !theta || !J || n_inst < 0) return fail(EHM_E_INVALID, "bad argument");
+    if (!P || !theta || !J || n_inst < 0) return g_err.fail(EHM_E_INVALID, "bad argument");
     std::vector<int32_t> didx;
     int rc = map_deltas(P, n_inst, delta, didx);
     if (rc) return rc;
@@ -1398,7 +1396,7 @@ int ehm_solve_ptd_batch(ehm_problem* P, int64_t n_inst, const double* theta,
 
 int ehm_feas_ptd_batch(ehm_problem* P, int64_t n_inst, const double* theta,
                        const uint8_t* delta, uint8_t* feasible, double* tau) {
-    if (!P || !theta || !feasible || n_inst < 0) return fail(EHM_E_INVALID, "bad argument");
+    if (!P || !theta || !feasible || n_inst < 0) return g_err.fail(EHM_E_INVALID, "bad argument");
     std::vector<int32_t> didx;
     int rc = map_deltas(P, n_inst, delta, didx);
     if (rc) return rc;
@@ -1444,7 +1442,7 @@ static int simplex_batch(ehm_problem* P, int64_t n_inst, const double* R, const 
 
 int ehm_slack_batch(ehm_problem* P, int64_t n_inst, const double* R, const double* Vbar,
                     const uint8_t* delta, double* tstar, double* alpha, int32_t* status) {
-    if (!P || !R || !Vbar || !tstar || n_inst < 0) return fail(EHM_E_INVALID, "bad argument");
+    if (!P || !R || !Vbar || !tstar || n_inst < 0) return g_err.fail(EHM_E_INVALID, "bad argument");
     std::vector<int32_t> didx;
     int rc = map_deltas(P, n_inst, delta, didx);
     if (rc) return rc;
@@ -1459,25 +1457,27 @@ int ehm_simplex_idx_batch(ehm_problem* P, int64_t n_inst, const double* R, const
                           int32_t* status) {
     if (!P || !R || !slot || !obj || n_inst < 0 || mode < 0 || mode > 2 ||
         (mode == SX_SLACK && !Vbar))
-        return fail(EHM_E_INVALID, "bad argument");
+        return g_err.fail(EHM_E_INVALID, "bad argument");
     for (int64_t k = 0; k < n_inst; ++k)
         if (slot[k] < 0 || slot[k] >= P->dp.n_delta)
-            return fail(EHM_E_INVALID, "instance %lld: slot %d out of range", (long long)k, slot[k]);
+            return g_err.fail(EHM_E_INVALID, "instance %lld: slot %d out of range", (long long)k,
+                              slot[k]);
     return simplex_batch(P, n_inst, R, Vbar, slot, mode, obj, alpha, status);
 }
 // feas = 1: phase-one form (tau out in J).
 int ehm_point_idx_batch(ehm_problem* P, int64_t n_inst, const double* theta, const int32_t* slot,
                         int32_t feas, double* J, double* u0, int32_t* status) {
-    if (!P || !theta || !slot || !J || n_inst < 0) return fail(EHM_E_INVALID, "bad argument");
+    if (!P || !theta || !slot || !J || n_inst < 0) return g_err.fail(EHM_E_INVALID, "bad argument");
     for (int64_t k = 0; k < n_inst; ++k)
         if (slot[k] < 0 || slot[k] >= P->dp.n_delta)
-            return fail(EHM_E_INVALID, "instance %lld: slot %d out of range", (long long)k, slot[k]);
+            return g_err.fail(EHM_E_INVALID, "instance %lld: slot %d out of range", (long long)k,
+                              slot[k]);
     return point_batch(P, n_inst, theta, slot, feas ? 1 : 0, J, u0, status, nullptr);
 }
 
 int ehm_min_simplex_batch(ehm_problem* P, int64_t n_inst, const double* R,
                           const uint8_t* delta, double* Jmin, int32_t* status) {
-    if (!P || !R || !Jmin || n_inst < 0) return fail(EHM_E_INVALID, "bad argument");
+    if (!P || !R || !Jmin || n_inst < 0) return g_err.fail(EHM_E_INVALID, "bad argument");
     std::vector<int32_t> didx;
     int rc = map_deltas(P, n_inst, delta, didx);
     if (rc) return rc;
@@ -1520,7 +1520,7 @@ static int feas_all_pairs(ehm_problem* P, int64_t n_inst, const double* theta,
 
 int ehm_solve_pt_batch(ehm_problem* P, int64_t n_inst, const double* theta, double* J,
                        double* u0, int32_t* delta_idx) {
-    if (!P || !theta || !J || n_inst < 0) return fail(EHM_E_INVALID, "bad argument");
+    if (!P || !theta || !J || n_inst < 0) return g_err.fail(EHM_E_INVALID, "bad argument");
     const int nd = P->dp.n_delta;
     const size_t p = P->dp.p, n_u = P->dp.n_u;
     std::vector<double> th;
@@ -1568,10 +1568,11 @@ int ehm_solve_pt_batch(ehm_problem* P, int64_t n_inst, const double* theta, doub
 
 // ---- the closed loop around the implicit law (ehm_implicit.hip; interface: ehm_implicit.h) -----
 int ehm_imp_describe(ehm_problem* P, ImpProblem* out) {
-    if (!P || !out) return fail(EHM_E_INVALID, "null argument");
+    if (!P || !out) return g_err.fail(EHM_E_INVALID, "null argument");
     if (P->solver_gen != 2)
-        return fail(EHM_E_INVALID, "the device loop of the implicit law runs on the generation-2 "
-                                   "kernels (ehm_problem_set_solver)");
+        return g_err.fail(EHM_E_INVALID,
+                          "the device loop of the implicit law runs on the generation-2 "
+                          "kernels (ehm_problem_set_solver)");
     *out = ImpProblem{P->device, P->dp.p, P->dp.n_u, P->dp.n_delta, P->stream};
     return EHM_OK;
 }
@@ -1580,7 +1581,7 @@ int ehm_imp_point(ehm_problem* P, int feas, long long max_items, const double* b
                   const int32_t* seg, double* J, double* u0, int32_t* status,
                   const long long* src, const int32_t* dst, const int32_t* n_dev) {
     if (!P || !base || !seg || !J || !src || max_items < 1)
-        return fail(EHM_E_INVALID, "bad argument");
+        return g_err.fail(EHM_E_INVALID, "bad argument");
     K2Cfg cfg;
     int rc = k2_config(P, feas ? LP_FEAS : LP_POINT, feas ? LP_FEAS : LP_POINT, max_items, cfg);
     if (rc) return rc;
@@ -1643,7 +1644,7 @@ static int vertex_solves(ehm_problem* P, int64_t n_inst, const double* R, const 
 
 int ehm_vr_batch(ehm_problem* P, int64_t n_inst, const double* R, int32_t* delta_idx,
                  double* vJ, double* vu0) {
-    if (!P || !R || !delta_idx || n_inst < 0) return fail(EHM_E_INVALID, "bad argument");
+    if (!P || !R || !delta_idx || n_inst < 0) return g_err.fail(EHM_E_INVALID, "bad argument");
     const int nd = P->dp.n_delta;
     std::vector<uint8_t> mask;
     int rc = vertex_feasible_mask(P, n_inst, R, mask);
@@ -1659,7 +1660,7 @@ int ehm_vr_batch(ehm_problem* P, int64_t n_inst, const double* R, int32_t* delta
     bool all_ok = true;
     rc = vertex_solves(P, n_inst, R, delta_idx, vJ, vu0, all_ok);
     if (rc) return rc;
-    if (!all_ok) return fail(EHM_E_NUMERIC, "a vertex solve of V_R did not converge");
+    if (!all_ok) return g_err.fail(EHM_E_NUMERIC, "a vertex solve of V_R did not converge");
     return EHM_OK;
 }
 
@@ -1756,8 +1757,9 @@ static int slack_all(ehm_problem* P, int64_t n_inst, const double* R, const doub
                     fclose(fp);
                 }
             }
-            return fail(EHM_E_NUMERIC, "slack LP (instance %lld, commutation %d) did not converge",
-                        (long long)(sel[f] / nd), (int)(sel[f] % nd));
+            return g_err.fail(EHM_E_NUMERIC,
+                              "slack LP (instance %lld, commutation %d) did not converge",
+                              (long long)(sel[f] / nd), (int)(sel[f] % nd));
         }
         tall[(size_t)sel[f]] = obj[f];
         if (feas_out) (*feas_out)[(size_t)sel[f]] = 1;
@@ -1769,7 +1771,8 @@ static int slack_all(ehm_problem* P, int64_t n_inst, const double* R, const doub
 
 int ehm_bar_e_batch(ehm_problem* P, int64_t n_inst, const double* R, const double* Vbar,
                     uint8_t* closed, double* tbest) {
-    if (!P || !R || !Vbar || !closed || n_inst < 0) return fail(EHM_E_INVALID, "bad argument");
+    if (!P || !R || !Vbar || !closed || n_inst < 0)
+        return g_err.fail(EHM_E_INVALID, "bad argument");
     const int nd = P->dp.n_delta;
     std::vector<double> tall;
     int rc = slack_all(P, n_inst, R, Vbar, nullptr, tall, nullptr);
@@ -1821,7 +1824,7 @@ static int bar_d_finish(ehm_problem* P, int64_t n_inst, const double* R, const d
     bool all_ok = true;
     int rc = vertex_solves(P, n_inst, R, delta_idx, vJ, vu0, all_ok);
     if (rc) return rc;
-    if (!all_ok) return fail(EHM_E_NUMERIC, "a vertex solve of bar_D did not converge");
+    if (!all_ok) return g_err.fail(EHM_E_NUMERIC, "a vertex solve of bar_D did not converge");
     // in_variability_ball (lib/oracle.py:220-283) for the instances with a better commutation
     const std::vector<int64_t> sel = where(n_inst, [&](int64_t k) { return delta_idx[k] >= 0; });
     const size_t F = sel.size();
@@ -1840,7 +1843,7 @@ static int bar_d_finish(ehm_problem* P, int64_t n_inst, const double* R, const d
         if (rc) return rc;
         for (size_t f = 0; f < F; ++f) {
             if (st[f] != 0 || st2[f] != 0)
-                return fail(EHM_E_NUMERIC, "in_variability_ball solve did not converge");
+                return g_err.fail(EHM_E_NUMERIC, "in_variability_ball solve did not converge");
             const int64_t k = sel[f];
             double vmax = -INFINITY;
             for (int v = 0; v < nv; ++v) vmax = std::max(vmax, Vbar[(size_t)k * nv + v]);
@@ -1854,7 +1857,8 @@ static int bar_d_finish(ehm_problem* P, int64_t n_inst, const double* R, const d
 int ehm_bar_d_batch(ehm_problem* P, int64_t n_inst, const double* R, const double* Vbar,
                     const uint8_t* delta_ref, int32_t* delta_idx, double* theta_star,
                     double* vJ, double* vu0, uint8_t* var_small) {
-    if (!P || !R || !Vbar || !delta_idx || n_inst < 0) return fail(EHM_E_INVALID, "bad argument");
+    if (!P || !R || !Vbar || !delta_idx || n_inst < 0)
+        return g_err.fail(EHM_E_INVALID, "bad argument");
     std::vector<int32_t> dref;
     int rc = map_deltas(P, n_inst, delta_ref, dref);
     if (rc) return rc;
@@ -1870,7 +1874,7 @@ int ehm_bar_d_batch(ehm_problem* P, int64_t n_inst, const double* R, const doubl
 
 // P_theta_delta(theta, d, check_feasibility=True) for EVERY commutation d: feasible[k*nd + d].
 int ehm_feas_all_batch(ehm_problem* P, int64_t n_inst, const double* theta, uint8_t* feasible) {
-    if (!P || !theta || !feasible || n_inst < 0) return fail(EHM_E_INVALID, "bad argument");
+    if (!P || !theta || !feasible || n_inst < 0) return g_err.fail(EHM_E_INVALID, "bad argument");
     std::vector<double> th;
     std::vector<int32_t> di;
     std::vector<uint8_t> ok;
@@ -1896,7 +1900,7 @@ int ehm_lcss_batch(ehm_problem* P, int64_t n_inst, const double* R, const double
                    uint8_t* closed, double* tbest, uint8_t* cand_out, int32_t* delta_idx,
                    double* theta_star, double* vJ, double* vu0, uint8_t* var_small) {
     if (!P || !R || !Vbar || !delta_ref || !vfeas || !closed || !delta_idx || n_inst < 0)
-        return fail(EHM_E_INVALID, "bad argument");
+        return g_err.fail(EHM_E_INVALID, "bad argument");
     const int nd = P->dp.n_delta, p = P->dp.p, nv = p + 1;
     std::vector<int32_t> dref;
     int rc = map_deltas(P, n_inst, delta_ref, dref);
@@ -1957,11 +1961,12 @@ int ehm_lcss_batch(ehm_problem* P, int64_t n_inst, const double* R, const double
 int ehm_split_batch(int device, int64_t n, int32_t p, const double* R, double* S1, double* S2,
                     int32_t* ij) {
     if (!R || !S1 || !S2 || !ij || n < 0 || p < 1 || p > EHM_MAX_P)
-        return fail(EHM_E_INVALID, "bad argument");
+        return g_err.fail(EHM_E_INVALID, "bad argument");
     if (n == 0) return EHM_OK;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev || device < 0)
-        return fail(EHM_E_NO_DEVICE, "no HIP device %d (libehmpc has no CPU fallback)", device);
+        return g_err.fail(EHM_E_NO_DEVICE, "no HIP device %d (libehmpc has no CPU fallback)",
+                          device);
     HIP_TRY(hipSetDevice(device), EHM_E_NO_DEVICE);
     const size_t bytes = (size_t)n * (p + 1) * p * sizeof(double);
     DevBuf dR, d1, d2, dij;
@@ -1981,11 +1986,13 @@ int ehm_split_batch(int device, int64_t n, int32_t p, const double* R, double* S
 }
 
 int ehm_volume_batch(int device, int64_t n, int32_t p, const double* R, double* vol) {
-    if (!R || !vol || n < 0 || p < 1 || p > EHM_MAX_P) return fail(EHM_E_INVALID, "bad argument");
+    if (!R || !vol || n < 0 || p < 1 || p > EHM_MAX_P)
+        return g_err.fail(EHM_E_INVALID, "bad argument");
     if (n == 0) return EHM_OK;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev || device < 0)
-        return fail(EHM_E_NO_DEVICE, "no HIP device %d (libehmpc has no CPU fallback)", device);
+        return g_err.fail(EHM_E_NO_DEVICE, "no HIP device %d (libehmpc has no CPU fallback)",
+                          device);
     HIP_TRY(hipSetDevice(device), EHM_E_NO_DEVICE);
     const size_t bytes = (size_t)n * (p + 1) * p * sizeof(double);
     DevBuf dR, dv;
@@ -2081,7 +2088,7 @@ static int read_counters(ehm_problem* P, DevCounters& c) {
 }
 
 int ehm_problem_layout(ehm_problem* P, int32_t out[4]) {
-    if (!P || !out) return fail(EHM_E_INVALID, "null argument");
+    if (!P || !out) return g_err.fail(EHM_E_INVALID, "null argument");
     out[0] = P->dp.nd0;
     out[1] = P->dp.n - P->dp.nd0;
     out[2] = P->dp.LE4;
@@ -2090,14 +2097,14 @@ int ehm_problem_layout(ehm_problem* P, int32_t out[4]) {
 }
 
 int ehm_tree_persist_kernel(const ehm_tree* T, int32_t out[4]) {
-    if (!T || !out) return fail(EHM_E_INVALID, "null argument");
+    if (!T || !out) return g_err.fail(EHM_E_INVALID, "null argument");
     for (int k = 0; k < 4; ++k) out[k] = T->persist_kernel[k];
     return EHM_OK;
 }
 
 int ehm_problem_batch_kernel(ehm_problem* P, int32_t kind, int32_t out[4]) {
-    if (!P || !out) return fail(EHM_E_INVALID, "null argument");
-    if (kind < LP_POINT || kind > LP_FEAS_SIMPLEX) return fail(EHM_E_INVALID, "LP kind 0..4");
+    if (!P || !out) return g_err.fail(EHM_E_INVALID, "null argument");
+    if (kind < LP_POINT || kind > LP_FEAS_SIMPLEX) return g_err.fail(EHM_E_INVALID, "LP kind 0..4");
     if (P->solver_gen == 1) {       // one wavefront per LP, sized at run time
         int n_lp, ne;
         kind_dims(P->dp, kind, n_lp, ne);
@@ -2119,7 +2126,7 @@ int ehm_problem_batch_kernel(ehm_problem* P, int32_t kind, int32_t out[4]) {
 }
 
 int ehm_solver_phase_ticks(ehm_problem* P, int64_t out[24]) {
-    if (!P || !out) return fail(EHM_E_INVALID, "null argument");
+    if (!P || !out) return g_err.fail(EHM_E_INVALID, "null argument");
     HIP_TRY(hipSetDevice(P->device), EHM_E_HIP);
     DevCounters c;
     int rc = read_counters(P, c);
@@ -2295,12 +2302,13 @@ __global__ void k_give_nodes(DevTree T, int first, int n, int nrec,
 
 int ehm_partition_begin(ehm_problem* P, int64_t n_roots, const double* root_vertices,
                         const ehm_node_init* init, const ehm_run_opts* opts, ehm_tree** out) {
-    if (!P || !root_vertices || !out || n_roots < 1) return fail(EHM_E_INVALID, "bad argument");
+    if (!P || !root_vertices || !out || n_roots < 1)
+        return g_err.fail(EHM_E_INVALID, "bad argument");
     *out = nullptr;
     // frontier buffers, queue and counters of a run live in the problem handle: one run at a time
     if (P->active_run)
-        return fail(EHM_E_INVALID, "another partition run is active on this problem handle "
-                                   "(finish or destroy it first)");
+        return g_err.fail(EHM_E_INVALID, "another partition run is active on this problem handle "
+                                         "(finish or destroy it first)");
     HIP_TRY(hipSetDevice(P->device), EHM_E_HIP);
     const int p = P->dp.p, n_u = P->dp.n_u;
     long long cap = (opts && opts->max_nodes > 0) ? opts->max_nodes : (1LL << 21);
@@ -2319,8 +2327,8 @@ int ehm_partition_begin(ehm_problem* P, int64_t n_roots, const double* root_vert
     R.shard_min = opts ? opts->shard_min_frontier : 0;
     R.deal_depth = (opts && opts->shard_world > 1 && opts->deal_depth > 0) ? opts->deal_depth : 0;
     if (R.shard_world > 1 && (R.shard_rank < 0 || R.shard_rank >= R.shard_world))
-        return fail(EHM_E_INVALID, "shard_rank %d out of range for world %d", R.shard_rank,
-                    R.shard_world);
+        return g_err.fail(EHM_E_INVALID, "shard_rank %d out of range for world %d", R.shard_rank,
+                          R.shard_world);
     R.sharded = (R.shard_world == 1);
     T->skip_volume = opts ? opts->skip_volume : 0;
     int rc = tree_alloc(T.get(), P, cap);
@@ -2370,7 +2378,7 @@ int ehm_partition_begin(ehm_problem* P, int64_t n_roots, const double* root_vert
         for (int64_t k = 0; k < n_roots; ++k) ids[(size_t)k] = (int32_t)k;
         hipError_t e = hipMemcpyAsync(P->fr_a.ptr, ids.data(), ids.size() * 4,
                                       hipMemcpyHostToDevice, P->stream);
-        if (e != hipSuccess) return fail(EHM_E_HIP, "frontier upload failed");
+        if (e != hipSuccess) return g_err.fail(EHM_E_HIP, "frontier upload failed");
         (void)hipStreamSynchronize(P->stream);
     }
     if ((rc = read_counters(P, R.c0))) return rc;
@@ -2378,15 +2386,15 @@ int ehm_partition_begin(ehm_problem* P, int64_t n_roots, const double* root_vert
         // root gradients start unknown (all-ones = NaN); the vertex solves of 'ecc' fill them
         hipError_t e = hipMemsetAsync(T->dt.grad, 0xFF, (size_t)n_roots * (p + 1) * p * 8,
                                       P->stream);
-        if (e != hipSuccess) return fail(EHM_E_HIP, "gradient buffer init failed");
+        if (e != hipSuccess) return g_err.fail(EHM_E_HIP, "gradient buffer init failed");
     }
     if (T->dt.wit) {        // roots carry no witness
         hipError_t e = hipMemsetAsync(T->dt.wit, 0, (size_t)n_roots * (p + 2) * 8, P->stream);
-        if (e != hipSuccess) return fail(EHM_E_HIP, "witness buffer init failed");
+        if (e != hipSuccess) return g_err.fail(EHM_E_HIP, "witness buffer init failed");
     }
     if (T->dt.mt.state) {   // an empty table (the payload needs no clearing)
         hipError_t e = hipMemsetAsync(T->dt.mt.state, 0, ((size_t)T->dt.mt.mask + 1) * 8, P->stream);
-        if (e != hipSuccess) return fail(EHM_E_HIP, "midpoint table init failed");
+        if (e != hipSuccess) return g_err.fail(EHM_E_HIP, "midpoint table init failed");
     }
     {
         unsigned long long inf_bits = 0x7FF0000000000000ULL;
@@ -2442,10 +2450,10 @@ int ehm_partition_begin(ehm_problem* P, int64_t n_roots, const double* root_vert
         DevCounters cv;
         if ((rc = read_counters(P, cv))) return rc;
         if (cv.errors != 0)
-            return fail(EHM_E_INFEASIBLE,
-                        "STOP, Theta contains infeasible regions (%llu of %lld root-vertex "
-                        "solves found no feasible point)",
-                        (unsigned long long)cv.errors, (long long)(n_roots * (p + 1)));
+            return g_err.fail(EHM_E_INFEASIBLE,
+                              "STOP, Theta contains infeasible regions (%llu of %lld root-vertex "
+                              "solves found no feasible point)",
+                              (unsigned long long)cv.errors, (long long)(n_roots * (p + 1)));
     }
     P->active_run = *out = T.release();
     return EHM_OK;
@@ -2465,7 +2473,8 @@ static int persistent_run(ehm_tree* T, long long max_pops = 0) {
     const bool no_k4 = dealt || max_pops > 0 || P->check_witness;
     int rc = k2_config(P, LP_SLACK, LP_POINT, 1LL << 40, cfg, true, no_k4);   // the full grid
     if (rc) return rc;
-    if (!cfg.api->persist) return fail(EHM_E_INVALID, "no persistent kernel for this LP size");
+    if (!cfg.api->persist)
+        return g_err.fail(EHM_E_INVALID, "no persistent kernel for this LP size");
     // two solver widths where a pair is compiled: the midpoint LPs have p + 1 columns less
     const KpApi* kp = nullptr;
     bool kp_mid = false;
@@ -2532,7 +2541,7 @@ static int persistent_run(ehm_tree* T, long long max_pops = 0) {
     // solved elsewhere; node ids stay below the put-back mark EHM_REQUEUED)
     const long long n_slots = 2 * T->limit + waves + 64;
     if (n_slots > 0x7fffffffLL || T->limit >= (long long)EHM_REQUEUED)
-        return fail(EHM_E_INVALID, "node pool too large for the persistent engine");
+        return g_err.fail(EHM_E_INVALID, "node pool too large for the persistent engine");
     HIP_TRY(P->pq_slots.ensure((size_t)n_slots * 4), EHM_E_HIP);
     HIP_TRY(P->pq_ctl.ensure(sizeof(PersistCtl)), EHM_E_HIP);
     int32_t* slots = P->pq_slots.as<int32_t>();
@@ -2595,14 +2604,15 @@ static int persistent_run(ehm_tree* T, long long max_pops = 0) {
             EHM_E_HIP);
     HIP_TRY(hipStreamSynchronize(P->stream), EHM_E_HIP);
     if (h.abort == 1)
-        return fail(EHM_E_CAPACITY, "node pool exhausted at %d nodes (max_nodes=%lld)",
-                    h.n_nodes, T->limit);
+        return g_err.fail(EHM_E_CAPACITY, "node pool exhausted at %d nodes (max_nodes=%lld)",
+                          h.n_nodes, T->limit);
     // what a budgeted launch leaves: the contiguous queue slice [pop_limit, tail)
     const long long left_over =
         (deal.pop_limit > 0 && h.tail > deal.pop_limit) ? (long long)h.tail - deal.pop_limit : 0;
     if (h.abort != 0 || h.pending != left_over)
-        return fail(EHM_E_HIP, "persistent frontier kernel stopped early (abort=%d, pending=%d, "
-                               "expected %lld)", h.abort, h.pending, left_over);
+        return g_err.fail(EHM_E_HIP,
+                          "persistent frontier kernel stopped early (abort=%d, pending=%d, "
+                          "expected %lld)", h.abort, h.pending, left_over);
     if (left_over > 0) {
         DevBuf& fb = P->fr_a;
         HIP_TRY(fb.ensure((size_t)left_over * 4 * 2), EHM_E_HIP);
@@ -2636,12 +2646,13 @@ static int persistent_run(ehm_tree* T, long long max_pops = 0) {
 // ehm_partition_give move between ranks.  The rebalancing rounds of the multi-GPU driver
 // (explicit_hybrid_mpc_amd/distributed.py, engine='persistent') are this call + one all-gather.
 int ehm_partition_advance(ehm_tree* T, int64_t max_pops, int64_t* frontier_size) {
-    if (!T || !T->run.active) return fail(EHM_E_INVALID, "no partition run in progress");
+    if (!T || !T->run.active) return g_err.fail(EHM_E_INVALID, "no partition run in progress");
     ehm_problem* P = T->prob;
     auto& R = T->run;
     if (T->hy || P->solver_gen != 2 || P->dp.Wr3)
-        return fail(EHM_E_INVALID, "ehm_partition_advance: needs a single-commutation problem on "
-                                   "the shared-block kernels (use ehm_partition_step)");
+        return g_err.fail(EHM_E_INVALID,
+                          "ehm_partition_advance: needs a single-commutation problem on "
+                          "the shared-block kernels (use ehm_partition_step)");
     HIP_TRY(hipSetDevice(P->device), EHM_E_HIP);
     int rc = EHM_OK;
     T->keep_ids = true;
@@ -2652,7 +2663,7 @@ int ehm_partition_advance(ehm_tree* T, int64_t max_pops, int64_t* frontier_size)
 
 // Runs up to max_sweeps frontier sweeps (<= 0: until the frontier is empty).
 int ehm_partition_step(ehm_tree* T, int32_t max_sweeps, int64_t* frontier_size) {
-    if (!T || !T->run.active) return fail(EHM_E_INVALID, "no partition run in progress");
+    if (!T || !T->run.active) return g_err.fail(EHM_E_INVALID, "no partition run in progress");
     ehm_problem* P = T->prob;
     auto& R = T->run;
     HIP_TRY(hipSetDevice(P->device), EHM_E_HIP);
@@ -2754,7 +2765,7 @@ int ehm_partition_step(ehm_tree* T, int32_t max_sweeps, int64_t* frontier_size) 
                                           P->stream);
             if (e == hipSuccess) e = hipStreamSynchronize(P->stream);
             if (e != hipSuccess)
-                return fail(EHM_E_HIP, "sweep %d failed: %s", R.sweeps, hipGetErrorString(e));
+                return g_err.fail(EHM_E_HIP, "sweep %d failed: %s", R.sweeps, hipGetErrorString(e));
         }
         ++R.sweeps;
         ++done;
@@ -2769,8 +2780,8 @@ int ehm_partition_step(ehm_tree* T, int32_t max_sweeps, int64_t* frontier_size) 
             break;
         }
         if (R.n_nodes + 2LL * n_open > T->limit)
-            return fail(EHM_E_CAPACITY, "node pool exhausted at %lld nodes (max_nodes=%lld)",
-                        R.n_nodes, T->limit);
+            return g_err.fail(EHM_E_CAPACITY, "node pool exhausted at %lld nodes (max_nodes=%lld)",
+                              R.n_nodes, T->limit);
         // next frontier buffer must hold 2*n_open ids
         DevBuf& nb = R.cur_is_a ? fr_b : fr_a;
         if ((long long)nb.cap < 2LL * n_open * 4) {
@@ -2811,7 +2822,7 @@ int ehm_partition_step(ehm_tree* T, int32_t max_sweeps, int64_t* frontier_size) 
 int ehm_partition_take(ehm_tree* T, int64_t count, int32_t* node_ids, double* records,
                        int32_t* meta) {
     if (!T || !T->run.active || !node_ids || !records || !meta || count < 0)
-        return fail(EHM_E_INVALID, "bad argument");
+        return g_err.fail(EHM_E_INVALID, "bad argument");
     ehm_problem* P = T->prob;
     auto& R = T->run;
     if (T->hy) {
@@ -2819,13 +2830,14 @@ int ehm_partition_take(ehm_tree* T, int64_t count, int32_t* node_ids, double* re
         // hand-over does not carry it: a moved subtree would draw as if it started at code 0 and
         // the run would no longer repeat the single-GPU one (nor the CPU oracle's rule 'hash')
         if (P->any_admissible && count > 0)
-            return fail(EHM_E_INVALID, "nodes cannot be handed over under option any_admissible "
-                                       "(its draws are reproducible only without rebalancing)");
+            return g_err.fail(EHM_E_INVALID,
+                              "nodes cannot be handed over under option any_admissible "
+                              "(its draws are reproducible only without rebalancing)");
         HIP_TRY(hipSetDevice(P->device), EHM_E_HIP);
         return hy_take(T, count, node_ids, records, meta);
     }
-    if (count > R.nf) return fail(EHM_E_INVALID, "cannot take %lld of %lld frontier nodes",
-                                  (long long)count, (long long)R.nf);
+    if (count > R.nf) return g_err.fail(EHM_E_INVALID, "cannot take %lld of %lld frontier nodes",
+                                        (long long)count, (long long)R.nf);
     if (count == 0) return EHM_OK;
     HIP_TRY(hipSetDevice(P->device), EHM_E_HIP);
     const int nrec = rec_doubles(P->dp.p, P->dp.n_u);
@@ -2872,21 +2884,22 @@ int ehm_partition_take(ehm_tree* T, int64_t count, int32_t* node_ids, double* re
 int ehm_partition_give(ehm_tree* T, int64_t count, const double* records, const int32_t* meta,
                        int32_t* first_id) {
     if (!T || !T->run.active || !records || !meta || count < 0)
-        return fail(EHM_E_INVALID, "bad argument");
+        return g_err.fail(EHM_E_INVALID, "bad argument");
     ehm_problem* P = T->prob;
     auto& R = T->run;
     if (T->hy) {
         if (P->any_admissible && count > 0)
-            return fail(EHM_E_INVALID, "nodes cannot be handed over under option any_admissible "
-                                       "(its draws are reproducible only without rebalancing)");
+            return g_err.fail(EHM_E_INVALID,
+                              "nodes cannot be handed over under option any_admissible "
+                              "(its draws are reproducible only without rebalancing)");
         HIP_TRY(hipSetDevice(P->device), EHM_E_HIP);
         return hy_give(T, count, records, meta, first_id);
     }
     if (first_id) *first_id = (int32_t)R.n_nodes;
     if (count == 0) return EHM_OK;
     if (R.n_nodes + count > T->limit)
-        return fail(EHM_E_CAPACITY, "node pool exhausted at %lld nodes (max_nodes=%lld)",
-                    R.n_nodes, T->limit);
+        return g_err.fail(EHM_E_CAPACITY, "node pool exhausted at %lld nodes (max_nodes=%lld)",
+                          R.n_nodes, T->limit);
     HIP_TRY(hipSetDevice(P->device), EHM_E_HIP);
     const int nrec = rec_doubles(P->dp.p, P->dp.n_u);
     HIP_TRY(P->in0.ensure((size_t)count * nrec * sizeof(double)), EHM_E_HIP);
@@ -2917,7 +2930,7 @@ int ehm_partition_give(ehm_tree* T, int64_t count, const double* records, const 
 
 // Pool occupancy of a run in progress (no device work): nodes allocated, nodes the caller allowed.
 int ehm_partition_counts(const ehm_tree* T, int64_t* n_nodes, int64_t* max_nodes) {
-    if (!T || !T->run.active) return fail(EHM_E_INVALID, "no partition run in progress");
+    if (!T || !T->run.active) return g_err.fail(EHM_E_INVALID, "no partition run in progress");
     if (n_nodes) *n_nodes = T->run.n_nodes;
     if (max_nodes) *max_nodes = T->limit;
     return EHM_OK;
@@ -2927,7 +2940,7 @@ int ehm_partition_counts(const ehm_tree* T, int64_t* n_nodes, int64_t* max_nodes
 // runs move any frontier node as rec_doubles doubles; multi-commutation runs move lcss nodes only
 // (ecc nodes carry no data yet), each with its bit rows appended (ehm_hybrid.h).
 int ehm_partition_movable(const ehm_tree* T, int64_t* movable, int32_t* record_doubles) {
-    if (!T || !T->run.active) return fail(EHM_E_INVALID, "no partition run in progress");
+    if (!T || !T->run.active) return g_err.fail(EHM_E_INVALID, "no partition run in progress");
     const DevProblem& dp = T->prob->dp;
     if (movable) *movable = T->hy ? T->hy->n_lcss : T->run.nf;
     if (record_doubles)
@@ -2937,8 +2950,8 @@ int ehm_partition_movable(const ehm_tree* T, int64_t* movable, int32_t* record_d
 }
 
 int ehm_partition_progress(ehm_tree* T, ehm_progress* out) {
-    if (!T || !out) return fail(EHM_E_INVALID, "null argument");
-    if (!T->run.active) return fail(EHM_E_INVALID, "no partition run in progress");
+    if (!T || !out) return g_err.fail(EHM_E_INVALID, "null argument");
+    if (!T->run.active) return g_err.fail(EHM_E_INVALID, "no partition run in progress");
     ehm_problem* P = T->prob;
     auto& R = T->run;
     HIP_TRY(hipSetDevice(P->device), EHM_E_HIP);
@@ -2983,7 +2996,7 @@ int ehm_partition_progress(ehm_tree* T, ehm_progress* out) {
 }
 
 int ehm_partition_finish(ehm_tree* T) {
-    if (!T || !T->run.active) return fail(EHM_E_INVALID, "no partition run in progress");
+    if (!T || !T->run.active) return g_err.fail(EHM_E_INVALID, "no partition run in progress");
     ehm_problem* P = T->prob;
     auto& R = T->run;
     HIP_TRY(hipSetDevice(P->device), EHM_E_HIP);
@@ -3008,8 +3021,8 @@ int ehm_partition_finish(ehm_tree* T) {
     R.active = false;
     if (P->active_run == T) P->active_run = nullptr;
     if (c1.errors != 0 && !getenv("EHM_KEEP_GOING"))
-        return fail(EHM_E_NUMERIC, "%llu oracle solves did not converge",
-                    (unsigned long long)c1.errors);
+        return g_err.fail(EHM_E_NUMERIC, "%llu oracle solves did not converge",
+                          (unsigned long long)c1.errors);
     const long long received = R.received;
     T->info.n_nodes = R.n_nodes;
     T->info.n_roots = R.n_roots;
@@ -3075,7 +3088,7 @@ int ehm_partition_finish(ehm_tree* T) {
 
 int ehm_partition_run(ehm_problem* P, int64_t n_roots, const double* root_vertices,
                       const ehm_node_init* init, const ehm_run_opts* opts, ehm_tree** out) {
-    if (!out) return fail(EHM_E_INVALID, "bad argument");
+    if (!out) return g_err.fail(EHM_E_INVALID, "bad argument");
     ehm_tree* T = nullptr;
     int rc = ehm_partition_begin(P, n_roots, root_vertices, init, opts, &T);
     if (rc) return rc;
@@ -3089,8 +3102,9 @@ int ehm_partition_run(ehm_problem* P, int64_t n_roots, const double* root_vertic
 }
 
 int ehm_tree_info_get(const ehm_tree* Tc, ehm_tree_info* out) {
-    if (!Tc || !out) return fail(EHM_E_INVALID, "null argument");
-    if (!Tc->prob) return fail(EHM_E_INVALID, "the problem handle of this tree was destroyed");
+    if (!Tc || !out) return g_err.fail(EHM_E_INVALID, "null argument");
+    if (!Tc->prob)
+        return g_err.fail(EHM_E_INVALID, "the problem handle of this tree was destroyed");
     ehm_tree* T = const_cast<ehm_tree*>(Tc);
     if (T->info.volume_closed < 0.0 && !T->skip_volume) {
         // sum of closed-leaf volumes (lib/worker.py:374-375): a reduction kernel over the pool
@@ -3118,8 +3132,9 @@ int ehm_tree_info_get(const ehm_tree* Tc, ehm_tree_info* out) {
 int ehm_tree_export(const ehm_tree* Tc, double* vertices, int32_t* left, int32_t* right,
                     int32_t* delta_idx, double* vcost, double* vinput, uint8_t* flags,
                     double* tstar) {
-    if (!Tc) return fail(EHM_E_INVALID, "null tree");
-    if (!Tc->prob) return fail(EHM_E_INVALID, "the problem handle of this tree was destroyed");
+    if (!Tc) return g_err.fail(EHM_E_INVALID, "null tree");
+    if (!Tc->prob)
+        return g_err.fail(EHM_E_INVALID, "the problem handle of this tree was destroyed");
     ehm_tree* T = const_cast<ehm_tree*>(Tc);
     ehm_problem* P = T->prob;
     HIP_TRY(hipSetDevice(P->device), EHM_E_HIP);
@@ -3154,8 +3169,10 @@ int ehm_tree_export(const ehm_tree* Tc, double* vertices, int32_t* left, int32_t
         HIP_TRY(hipStreamSynchronize(P->stream), EHM_E_HIP);
         const int reached = hb[2 * (levels & 1) + 1];
         if (reached != n || hb[2 * (levels & 1)] != reached)
-            return fail(EHM_E_HIP, "tree structure inconsistent (%d of %lld nodes numbered in %d levels)",
-                        reached, n, levels);
+            return g_err.fail(EHM_E_HIP,
+                              "tree structure inconsistent (%d of %lld nodes numbered in %d "
+                              "levels)",
+                              reached, n, levels);
         hipLaunchKernelGGL(k_bfs_invert, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, P->stream,
                            perm, T->d_inv.as<int32_t>(), n);
         T->have_perm = true;
@@ -3200,7 +3217,8 @@ int ehm_tree_export(const ehm_tree* Tc, double* vertices, int32_t* left, int32_t
         EXP_COPY(flags ? flags + k0 : nullptr, s_f, (size_t)nk);
 #undef EXP_COPY
         if (e == hipSuccess) e = hipStreamSynchronize(P->stream);
-        if (e != hipSuccess) return fail(EHM_E_HIP, "tree export failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess)
+            return g_err.fail(EHM_E_HIP, "tree export failed: %s", hipGetErrorString(e));
     }
     return EHM_OK;
 }
@@ -3208,16 +3226,17 @@ int ehm_tree_export(const ehm_tree* Tc, double* vertices, int32_t* left, int32_t
 // Page-locked host memory for the arrays ehm_tree_export fills: copies into it run at the speed
 // of the host link (into pageable memory they are staged by the runtime, several times slower).
 int ehm_host_alloc(size_t bytes, void** out) {
-    if (!out) return fail(EHM_E_INVALID, "ehm_host_alloc: out is NULL");
+    if (!out) return g_err.fail(EHM_E_INVALID, "ehm_host_alloc: out is NULL");
     *out = nullptr;
     void* q = nullptr;
     if (hipHostMalloc(&q, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess)
-        return fail(EHM_E_CAPACITY, "ehm_host_alloc: %zu bytes of page-locked memory refused", bytes);
+        return g_err.fail(EHM_E_CAPACITY, "ehm_host_alloc: %zu bytes of page-locked memory refused",
+                          bytes);
     *out = q;
     return EHM_OK;
 }
 int ehm_host_free(void* q) {
-    if (q && hipHostFree(q) != hipSuccess) return fail(EHM_E_HIP, "ehm_host_free failed");
+    if (q && hipHostFree(q) != hipSuccess) return g_err.fail(EHM_E_HIP, "ehm_host_free failed");
     return EHM_OK;
 }
 

@@ -35,10 +35,6 @@ __global__ void k_certify_parents(long long n_int, int p, int node_stride,
     ehm_cert::link_children(P, (int32_t)k, left, right);
 }
 
-inline unsigned cells_blocks_of(long long n, int block) {
-    return (unsigned)((n + block - 1) / block);
-}
-
 // the parent table of a law on the device
 struct ParentTable {
     DevBuf node, node_side, leaf, leaf_side;
@@ -69,21 +65,48 @@ inline hipError_t make_parents(const ehm_compiled_view& v, hipStream_t stream, P
     const ehm_cert::Parents P = T.view();
     if (v.n_int) {
         if (v.single)
-            hipLaunchKernelGGL(k_certify_parents<float>, dim3(cells_blocks_of(v.n_int, 256)),
+            hipLaunchKernelGGL(k_certify_parents<float>, dim3(blocks_of(v.n_int, 256)),
                                dim3(256), 0, stream, v.n_int, v.p, v.node_stride,
                                static_cast<const float*>(v.node), P);
         else
-            hipLaunchKernelGGL(k_certify_parents<double>, dim3(cells_blocks_of(v.n_int, 256)),
+            hipLaunchKernelGGL(k_certify_parents<double>, dim3(blocks_of(v.n_int, 256)),
                                dim3(256), 0, stream, v.n_int, v.p, v.node_stride,
                                static_cast<const double*>(v.node), P);
         EHM_CELLS_TRY(hipGetLastError());
     }
     // the roots last: an entry is a root whatever else names it
-    hipLaunchKernelGGL(k_certify_roots, dim3(cells_blocks_of(v.n_roots, 256)), dim3(256), 0,
+    hipLaunchKernelGGL(k_certify_roots, dim3(blocks_of(v.n_roots, 256)), dim3(256), 0,
                        stream, v.n_roots, v.root_entry, P);
     EHM_CELLS_TRY(hipGetLastError());
 #undef EHM_CELLS_TRY
     return hipSuccess;
+}
+
+// What every entry point that rebuilds cells refuses of a law (`who` names the entry point) ...
+inline int check_law_shape(ehm_err_channel& err, const ehm_compiled_view& v, const char* who) {
+    if (v.n_test > 0)
+        return err.fail(EHM_E_INVALID,
+                        "%s: the law has %lld test nodes (children that are no bisection); its "
+                        "cells do not follow from its planes -- compile it with the spine as its "
+                        "root table",
+                        who, v.n_test);
+    if (v.p < 1 || v.p > EHM_CP) return err.fail(EHM_E_INVALID, "%s: p = %d", who, v.p);
+    if (v.n_roots >= 0x7fffffffLL) return err.fail(EHM_E_INVALID, "%s: too many roots", who);
+    return EHM_OK;
+}
+
+// ... and of the caller's n leaves (leaf_ids nullptr: the first n)
+inline int check_law_leaves(ehm_err_channel& err, const ehm_compiled_view& v, int64_t n,
+                            const int32_t* leaf_ids, const char* who) {
+    if (!leaf_ids && n > v.n_leaf)
+        return err.fail(EHM_E_INVALID, "%s: n = %lld of %lld leaves", who, (long long)n, v.n_leaf);
+    if (leaf_ids) {
+        const int64_t bad = ehm_cert::first_bad_leaf(leaf_ids, n, v.n_leaf);
+        if (bad >= 0)
+            return err.fail(EHM_E_INVALID, "%s: leaf_ids[%lld] = %d of %lld leaves", who,
+                            (long long)bad, (int)leaf_ids[bad], v.n_leaf);
+    }
+    return EHM_OK;
 }
 
 // The cell of leaf record l into V [(P+1) P], statically indexed throughout: up to the root through

@@ -19,8 +19,10 @@
 //                      at the p + 1 vertices in the law's own arithmetic
 //   k_certify_pack     one thread per (leaf, vertex): theta' = (v, ubar) of the applied-input problem,
 //                      the cost constant, the flag of an input that is not finite
+//                      (pack_applied_row of ehm_verdict.h)
 //   k_certify_judge    one thread per leaf: its status from what the host's batches found, the
-//                      counts by integer atomics, the worst uncertified leaf per workgroup
+//                      counts by integer atomics, the worst uncertified leaf per workgroup (the
+//                      counters and the tree of ehm_verdict.h)
 //
 // ehm_compiled_certify runs the batched oracles between them (ehm_point_idx_batch on the applied
 // problem, ehm_bar_e_batch on the oracle's): host-orchestrated over the batched kernels like every
@@ -47,6 +49,7 @@
 
 #include "../../include/ehmpc.h"
 #include "ehm_cells_dev.h"
+#include "ehm_verdict.h"
 
 #define EHM_CERT_BLOCK 64
 #define EHM_CERT_CHUNK 65536        // leaves per pass of ehm_compiled_cells
@@ -103,8 +106,8 @@ __global__ __launch_bounds__(EHM_CERT_BLOCK) void k_certify_cells(CellArgs<T> A)
         for (int c = 0; c < n_u; ++c) ub[i * n_u + c] = leaf_map_at<P>(lr, n_u, c, &V[i * P]);
 }
 
-// theta' = (v_i, ubar_i) and konst_i = 0 + cost_u[0] ubar_i0 + .. of every (leaf, vertex) pair with a
-// cell; a component that is not finite enters as 0 and flags the leaf (k_applied_pack's rule)
+// theta' = (v_i, ubar_i) and konst_i of every (leaf, vertex) pair; a pair without a cell enters as
+// zeros, a component that is not finite flags the leaf
 __global__ void k_certify_pack(long long n_pairs, int p, int n_u, const double* __restrict__ V,
                                const double* __restrict__ U, const int32_t* __restrict__ cell,
                                const double* __restrict__ cost_u, double* __restrict__ theta,
@@ -113,21 +116,11 @@ __global__ void k_certify_pack(long long n_pairs, int p, int n_u, const double* 
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n_pairs) return;
     const long long leaf = q / (p + 1);
-    double* t = theta + (size_t)q * (p + n_u);
     const bool has = cell[leaf] == EHM_CELL_OK;
-    for (int c = 0; c < p; ++c) t[c] = has ? V[q * p + c] : 0.0;
-    double k = 0.0;
-    bool bad = false;
-    for (int j = 0; j < n_u; ++j) {
-        double u = has ? U[q * n_u + j] : 0.0;
-        if (!isfinite(u)) {
-            bad = true;
-            u = 0.0;
-        }
-        t[p + j] = u;
-        k = k + cost_u[j] * u;
-    }
-    konst[q] = k;
+    const bool bad = ehm_verdict::pack_applied_row(
+        p, n_u, [&](int c) { return has ? V[q * p + c] : 0.0; },
+        [&](int j) { return has ? U[q * n_u + j] : 0.0; }, cost_u, theta + (size_t)q * (p + n_u),
+        &konst[q]);
     if (bad) atomicOr(&no_law[leaf], 1);
 }
 
@@ -139,12 +132,9 @@ __global__ __launch_bounds__(EHM_CERT_JUDGE_BLOCK) void k_certify_judge(
     unsigned long long* __restrict__ counters, double* __restrict__ blk_t,
     long long* __restrict__ blk_i) {
     __shared__ unsigned int cnt[ehm_cert::CERT_STATUSES];
-    __shared__ double st[EHM_CERT_JUDGE_BLOCK];
-    __shared__ long long si[EHM_CERT_JUDGE_BLOCK];
-    const int t = threadIdx.x;
-    if (t < ehm_cert::CERT_STATUSES) cnt[t] = 0;
+    ehm_verdict::counters_zero<EHM_CERT_JUDGE_BLOCK>(cnt);
     __syncthreads();
-    const long long q = (long long)blockIdx.x * EHM_CERT_JUDGE_BLOCK + t;
+    const long long q = (long long)blockIdx.x * EHM_CERT_JUDGE_BLOCK + threadIdx.x;
     double tb = -INFINITY;
     long long id = -1;
     if (q < n) {
@@ -157,23 +147,17 @@ __global__ __launch_bounds__(EHM_CERT_JUDGE_BLOCK) void k_certify_judge(
             id = first + q;
         }
     }
-    st[t] = tb;
-    si[t] = id;
-    __syncthreads();
-    for (int h = EHM_CERT_JUDGE_BLOCK / 2; h > 0; h >>= 1) {
-        if (t < h && si[t + h] >= 0 &&
-            (si[t] < 0 || ehm_cert::worst_beats(st[t + h], si[t + h], st[t], si[t]))) {
-            st[t] = st[t + h];
-            si[t] = si[t + h];
-        }
-        __syncthreads();
+    ehm_verdict::block_worst<EHM_CERT_JUDGE_BLOCK>(
+        tb, id,
+        [](double ta, long long ia, double tb_, long long ib) {
+            return ehm_cert::worst_beats(ta, ia, tb_, ib);
+        },
+        [](long long i) { return i >= 0; });
+    if (threadIdx.x == 0) {
+        blk_t[blockIdx.x] = tb;
+        blk_i[blockIdx.x] = id;
     }
-    if (t == 0) {
-        blk_t[blockIdx.x] = st[0];
-        blk_i[blockIdx.x] = si[0];
-    }
-    if (t < ehm_cert::CERT_STATUSES && cnt[t])
-        atomicAdd(&counters[t], (unsigned long long)cnt[t]);
+    ehm_verdict::counters_flush<EHM_CERT_JUDGE_BLOCK>(cnt, counters);
 }
 
 typedef void (*cells64_fn)(CellArgs<double>);
@@ -185,47 +169,12 @@ const cells64_fn k_cells64[EHM_CP] = EHM_CERT_ALL(double);
 const cells32_fn k_cells32[EHM_CP] = EHM_CERT_ALL(float);
 #undef EHM_CERT_ALL
 
-thread_local std::string z_err;
-int zfail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    z_err = buf;
-    return code;
-}
-
-#define Z_TRY(expr)                                                                        \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return zfail(EHM_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
-    } while (0)
-
-unsigned blocks_of(long long n, int block) { return cells_blocks_of(n, block); }
-
-double wall_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-}
+thread_local ehm_err_channel z_err;
 
 // what both entry points check of a law and of the caller's leaves
 int check_law(const ehm_compiled_view& v, int64_t n, const int32_t* leaf_ids, const char* who) {
-    if (v.n_test > 0)
-        return zfail(EHM_E_INVALID, "%s: the law has %lld test nodes (children that are no "
-                     "bisection); its cells do not follow from its planes -- compile it with the "
-                     "spine as its root table", who, v.n_test);
-    if (v.p < 1 || v.p > EHM_CP) return zfail(EHM_E_INVALID, "%s: p = %d", who, v.p);
-    if (v.n_roots >= 0x7fffffffLL) return zfail(EHM_E_INVALID, "%s: too many roots", who);
-    if (!leaf_ids && n > v.n_leaf)
-        return zfail(EHM_E_INVALID, "%s: n = %lld of %lld leaves", who, (long long)n, v.n_leaf);
-    if (leaf_ids) {
-        const int64_t bad = ehm_cert::first_bad_leaf(leaf_ids, n, v.n_leaf);
-        if (bad >= 0)
-            return zfail(EHM_E_INVALID, "%s: leaf_ids[%lld] = %d of %lld leaves", who,
-                         (long long)bad, (int)leaf_ids[bad], v.n_leaf);
-    }
-    return EHM_OK;
+    const int rc = check_law_shape(z_err, v, who);
+    return rc ? rc : check_law_leaves(z_err, v, n, leaf_ids, who);
 }
 
 // k_certify_cells for the leaves ids[0 .. nc - 1] (device; nullptr: first .. first + nc - 1)
@@ -273,7 +222,8 @@ int find_candidates(ehm_problem* P, const std::vector<long long>& todo, int nv, 
             }
     int rc = ehm_point_idx_batch(P, (int64_t)pairs, th.data(), slot.data(), 1, tau.data(), nullptr,
                                  nullptr);
-    if (rc) return zfail(rc, "certify: ehm_point_idx_batch (feasibility): %s", ehm_last_error());
+    if (rc) return z_err.fail(rc, "certify: ehm_point_idx_batch (feasibility): %s",
+                              ehm_last_error());
     *t_feas += wall_since(t0);
     t0 = std::chrono::steady_clock::now();
     std::vector<long long> who;         // (leaf position, commutation) of every candidate
@@ -302,7 +252,7 @@ int find_candidates(ehm_problem* P, const std::vector<long long>& todo, int nv, 
         }
     rc = ehm_point_idx_batch(P, (int64_t)rows, th.data(), slot.data(), 0, J.data(), nullptr,
                              st.data());
-    if (rc) return zfail(rc, "certify: ehm_point_idx_batch (costs): %s", ehm_last_error());
+    if (rc) return z_err.fail(rc, "certify: ehm_point_idx_batch (costs): %s", ehm_last_error());
     for (size_t a = 0; a < who.size(); ++a) {
         Candidate c{};
         c.d = which[a];
@@ -326,52 +276,52 @@ const char* ehm_certify_last_error(void) { return z_err.c_str(); }
 int ehm_certify_abi_sizes(int64_t* sizes, int32_t n) {
     const int64_t all[] = {(int64_t)sizeof(ehm_certify_opts), (int64_t)sizeof(ehm_certify_result),
                            (int64_t)sizeof(ehm_certify_leaves)};
-    const int32_t known = (int32_t)(sizeof all / sizeof all[0]);
-    for (int32_t k = 0; sizes && k < n && k < known; ++k) sizes[k] = all[k];
-    return known;
+    return ehm_copy_abi_sizes(all, (int32_t)(sizeof all / sizeof all[0]), sizes, n);
 }
 
 int ehm_compiled_cells(ehm_compiled* law, const double* root_vertices, int64_t n,
                        const int32_t* leaf_ids, double* vertices, double* ubar, int32_t* status) {
     if (!law || !root_vertices || n < 0 || (n > 0 && (!vertices || !status)))
-        return zfail(EHM_E_INVALID, "cells: bad argument");
+        return z_err.fail(EHM_E_INVALID, "cells: bad argument");
     ehm_compiled_view v;
     ehm_compiled_get_view(law, &v);
     int rc = check_law(v, n, leaf_ids, "cells");
     if (rc) return rc;
     if (n == 0) return EHM_OK;
-    Z_TRY(hipSetDevice(v.device));
+    EHM_HIP_TRY(z_err, hipSetDevice(v.device));
     Stream stream;
-    Z_TRY(stream.create());
+    EHM_HIP_TRY(z_err, stream.create());
     const int p = v.p, n_u = v.n_u;
     const size_t cell = (size_t)(p + 1) * p;
     ParentTable T;
-    Z_TRY(make_parents(v, stream, T));
+    EHM_HIP_TRY(z_err, make_parents(v, stream, T));
     DevBuf droots, dids, dvert, dubar, dstatus;
-    Z_TRY(droots.upload(root_vertices, (size_t)v.n_roots * cell * sizeof(double)));
+    EHM_HIP_TRY(z_err, droots.upload(root_vertices, (size_t)v.n_roots * cell * sizeof(double)));
     const size_t cap = (size_t)std::min<int64_t>(n, EHM_CERT_CHUNK);
-    if (leaf_ids) Z_TRY(dids.alloc(cap * sizeof(int32_t)));
-    Z_TRY(dvert.alloc(cap * cell * sizeof(double)));
-    if (ubar) Z_TRY(dubar.alloc(cap * (size_t)(p + 1) * n_u * sizeof(double)));
-    Z_TRY(dstatus.alloc(cap * sizeof(int32_t)));
+    if (leaf_ids) EHM_HIP_TRY(z_err, dids.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(z_err, dvert.alloc(cap * cell * sizeof(double)));
+    if (ubar) EHM_HIP_TRY(z_err, dubar.alloc(cap * (size_t)(p + 1) * n_u * sizeof(double)));
+    EHM_HIP_TRY(z_err, dstatus.alloc(cap * sizeof(int32_t)));
     for (int64_t off = 0; off < n; off += EHM_CERT_CHUNK) {
         const int64_t nc = std::min<int64_t>(EHM_CERT_CHUNK, n - off);
         if (leaf_ids)
-            Z_TRY(hipMemcpyAsync(dids.ptr, leaf_ids + off, (size_t)nc * sizeof(int32_t),
-                                 hipMemcpyHostToDevice, stream));
+            EHM_HIP_TRY(z_err, hipMemcpyAsync(dids.ptr, leaf_ids + off,
+                                              (size_t)nc * sizeof(int32_t), hipMemcpyHostToDevice,
+                                              stream));
         launch_cells(v, stream, T, droots.as<const double>(),
                      leaf_ids ? dids.as<const int32_t>() : nullptr, off, nc, dvert.as<double>(),
                      ubar ? dubar.as<double>() : nullptr, dstatus.as<int32_t>());
-        Z_TRY(hipGetLastError());
-        Z_TRY(hipMemcpyAsync(vertices + (size_t)off * cell, dvert.ptr,
-                             (size_t)nc * cell * sizeof(double), hipMemcpyDeviceToHost, stream));
+        EHM_HIP_TRY(z_err, hipGetLastError());
+        EHM_HIP_TRY(z_err, hipMemcpyAsync(vertices + (size_t)off * cell, dvert.ptr,
+                                          (size_t)nc * cell * sizeof(double), hipMemcpyDeviceToHost,
+                                          stream));
         if (ubar)
-            Z_TRY(hipMemcpyAsync(ubar + (size_t)off * (p + 1) * n_u, dubar.ptr,
-                                 (size_t)nc * (p + 1) * n_u * sizeof(double),
-                                 hipMemcpyDeviceToHost, stream));
-        Z_TRY(hipMemcpyAsync(status + off, dstatus.ptr, (size_t)nc * sizeof(int32_t),
-                             hipMemcpyDeviceToHost, stream));
-        Z_TRY(hipStreamSynchronize(stream));
+            EHM_HIP_TRY(z_err, hipMemcpyAsync(ubar + (size_t)off * (p + 1) * n_u, dubar.ptr,
+                                              (size_t)nc * (p + 1) * n_u * sizeof(double),
+                                              hipMemcpyDeviceToHost, stream));
+        EHM_HIP_TRY(z_err, hipMemcpyAsync(status + off, dstatus.ptr, (size_t)nc * sizeof(int32_t),
+                                          hipMemcpyDeviceToHost, stream));
+        EHM_HIP_TRY(z_err, hipStreamSynchronize(stream));
     }
     return EHM_OK;
 }
@@ -380,19 +330,19 @@ int ehm_compiled_certify(ehm_compiled* law, ehm_problem* oracle, ehm_problem* ap
                          const ehm_certify_opts* o, ehm_certify_result* res,
                          const ehm_certify_leaves* lv) {
     if (!law || !oracle || !applied || !o || !res)
-        return zfail(EHM_E_INVALID, "certify: bad argument");
+        return z_err.fail(EHM_E_INVALID, "certify: bad argument");
     if (o->n < 0 || o->chunk < 0 || o->max_tries < 0 || o->n_delta < 1)
-        return zfail(EHM_E_INVALID, "certify: n, chunk, max_tries < 0 or n_delta < 1");
+        return z_err.fail(EHM_E_INVALID, "certify: n, chunk, max_tries < 0 or n_delta < 1");
     if (o->p < 1 || o->n_u < 1 || o->p + o->n_u > EHM_MAX_P)
-        return zfail(EHM_E_INVALID, "certify: p = %d, n_u = %d: p + n_u must be <= %d", (int)o->p,
-                     (int)o->n_u, EHM_MAX_P);
+        return z_err.fail(EHM_E_INVALID, "certify: p = %d, n_u = %d: p + n_u must be <= %d",
+                          (int)o->p, (int)o->n_u, EHM_MAX_P);
     if (!o->cost_u || !o->root_vertices)
-        return zfail(EHM_E_INVALID, "certify: no cost_u or no root vertices");
+        return z_err.fail(EHM_E_INVALID, "certify: no cost_u or no root vertices");
     ehm_compiled_view v;
     ehm_compiled_get_view(law, &v);
     if (v.p != o->p || v.n_u != o->n_u)
-        return zfail(EHM_E_INVALID, "certify: the law has p = %d, n_u = %d, the options %d, %d",
-                     v.p, v.n_u, (int)o->p, (int)o->n_u);
+        return z_err.fail(EHM_E_INVALID, "certify: the law has p = %d, n_u = %d, the options %d, "
+                          "%d", v.p, v.n_u, (int)o->p, (int)o->n_u);
     int rc = check_law(v, o->n, o->leaf_ids, "certify");
     if (rc) return rc;
     std::memset(res, 0, sizeof *res);
@@ -401,39 +351,40 @@ int ehm_compiled_certify(ehm_compiled* law, ehm_problem* oracle, ehm_problem* ap
     if (o->n == 0) return EHM_OK;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || o->device < 0 || o->device >= ndev)
-        return zfail(EHM_E_NO_DEVICE, "no HIP device %d (libehmpc has no CPU fallback)",
-                     (int)o->device);
-    Z_TRY(hipSetDevice(v.device));
+        return z_err.fail(EHM_E_NO_DEVICE, "no HIP device %d (libehmpc has no CPU fallback)",
+                          (int)o->device);
+    EHM_HIP_TRY(z_err, hipSetDevice(v.device));
     Stream stream;
-    Z_TRY(stream.create());
+    EHM_HIP_TRY(z_err, stream.create());
     const int p = v.p, n_u = v.n_u, nv = p + 1, pp = p + n_u, nd = o->n_delta;
     const size_t cell = (size_t)nv * p;
     ParentTable T;
-    Z_TRY(make_parents(v, stream, T));
+    EHM_HIP_TRY(z_err, make_parents(v, stream, T));
     const long long chunk = o->chunk > 0 ? o->chunk : EHM_CERT_PASS;
     const size_t cap = (size_t)std::min<long long>(chunk, o->n);
     const unsigned max_blocks = blocks_of((long long)cap, EHM_CERT_JUDGE_BLOCK);
     DevBuf droots, dcost, dids, dvert, dubar, dcell, dtheta, dkonst, dnolaw, dncand, dnaside,
         dclosed, dtbest, dstatus, dcnt, dbt, dbi;
-    Z_TRY(droots.upload(o->root_vertices, (size_t)v.n_roots * cell * sizeof(double)));
-    Z_TRY(dcost.upload(o->cost_u, (size_t)n_u * sizeof(double)));
-    if (o->leaf_ids) Z_TRY(dids.alloc(cap * sizeof(int32_t)));
-    Z_TRY(dvert.alloc(cap * cell * sizeof(double)));
-    Z_TRY(dubar.alloc(cap * nv * n_u * sizeof(double)));
-    Z_TRY(dcell.alloc(cap * sizeof(int32_t)));
-    Z_TRY(dtheta.alloc(cap * nv * pp * sizeof(double)));
-    Z_TRY(dkonst.alloc(cap * nv * sizeof(double)));
-    Z_TRY(dnolaw.alloc(cap * sizeof(int32_t)));
-    Z_TRY(dncand.alloc(cap * sizeof(int32_t)));
-    Z_TRY(dnaside.alloc(cap * sizeof(int32_t)));
-    Z_TRY(dclosed.alloc(cap * sizeof(int32_t)));
-    Z_TRY(dtbest.alloc(cap * sizeof(double)));
-    Z_TRY(dstatus.alloc(cap * sizeof(int32_t)));
-    Z_TRY(dcnt.alloc(ehm_cert::CERT_STATUSES * sizeof(unsigned long long)));
-    Z_TRY(dbt.alloc(max_blocks * sizeof(double)));
-    Z_TRY(dbi.alloc(max_blocks * sizeof(long long)));
-    Z_TRY(hipMemsetAsync(dcnt.ptr, 0, ehm_cert::CERT_STATUSES * sizeof(unsigned long long),
-                         stream));
+    EHM_HIP_TRY(z_err, droots.upload(o->root_vertices, (size_t)v.n_roots * cell * sizeof(double)));
+    EHM_HIP_TRY(z_err, dcost.upload(o->cost_u, (size_t)n_u * sizeof(double)));
+    if (o->leaf_ids) EHM_HIP_TRY(z_err, dids.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(z_err, dvert.alloc(cap * cell * sizeof(double)));
+    EHM_HIP_TRY(z_err, dubar.alloc(cap * nv * n_u * sizeof(double)));
+    EHM_HIP_TRY(z_err, dcell.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(z_err, dtheta.alloc(cap * nv * pp * sizeof(double)));
+    EHM_HIP_TRY(z_err, dkonst.alloc(cap * nv * sizeof(double)));
+    EHM_HIP_TRY(z_err, dnolaw.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(z_err, dncand.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(z_err, dnaside.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(z_err, dclosed.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(z_err, dtbest.alloc(cap * sizeof(double)));
+    EHM_HIP_TRY(z_err, dstatus.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(z_err, dcnt.alloc(ehm_cert::CERT_STATUSES * sizeof(unsigned long long)));
+    EHM_HIP_TRY(z_err, dbt.alloc(max_blocks * sizeof(double)));
+    EHM_HIP_TRY(z_err, dbi.alloc(max_blocks * sizeof(long long)));
+    EHM_HIP_TRY(z_err, hipMemsetAsync(dcnt.ptr, 0,
+                                      ehm_cert::CERT_STATUSES * sizeof(unsigned long long),
+                                      stream));
     std::vector<double> hvert(cap * cell), hubar(cap * nv * n_u), htheta(cap * nv * pp),
         hkonst(cap * nv), htbest(cap), hvol(cap), hW(cap * nv), hbt(max_blocks), R, Vb, tb, vsub;
     std::vector<int32_t> hcell(cap), hnolaw(cap), hncand(cap), hnaside(cap), hclosed(cap),
@@ -444,16 +395,18 @@ int ehm_compiled_certify(ehm_compiled* law, ehm_problem* oracle, ehm_problem* ap
     std::vector<std::vector<int32_t>> order(cap);
     std::vector<double> keys;
     EventPair ev_c, ev_j;
-    bool have_worst = false;
+    long long worst_leaf = -1;
+    double worst_tbest = NAN;
     for (long long off = 0; off < o->n; off += chunk) {
         const long long nc = std::min<long long>(chunk, o->n - off);
         auto t_pass = std::chrono::steady_clock::now();
         const double before = res->seconds[1] + res->seconds[2] + res->seconds[3] + res->seconds[4];
         // the cells, the vertex inputs and the rows of the applied problem
         if (o->leaf_ids)
-            Z_TRY(hipMemcpyAsync(dids.ptr, o->leaf_ids + off, (size_t)nc * sizeof(int32_t),
-                                 hipMemcpyHostToDevice, stream));
-        Z_TRY(hipMemsetAsync(dnolaw.ptr, 0, (size_t)nc * sizeof(int32_t), stream));
+            EHM_HIP_TRY(z_err, hipMemcpyAsync(dids.ptr, o->leaf_ids + off,
+                                              (size_t)nc * sizeof(int32_t), hipMemcpyHostToDevice,
+                                              stream));
+        EHM_HIP_TRY(z_err, hipMemsetAsync(dnolaw.ptr, 0, (size_t)nc * sizeof(int32_t), stream));
         (void)hipEventRecord(ev_c.e0, stream);
         launch_cells(v, stream, T, droots.as<const double>(),
                      o->leaf_ids ? dids.as<const int32_t>() : nullptr, off, nc, dvert.as<double>(),
@@ -463,20 +416,24 @@ int ehm_compiled_certify(ehm_compiled* law, ehm_problem* oracle, ehm_problem* ap
                            dcell.as<const int32_t>(), dcost.as<const double>(),
                            dtheta.as<double>(), dkonst.as<double>(), dnolaw.as<int32_t>());
         (void)hipEventRecord(ev_c.e1, stream);
-        Z_TRY(hipGetLastError());
-        Z_TRY(hipMemcpyAsync(hvert.data(), dvert.ptr, (size_t)nc * cell * sizeof(double),
-                             hipMemcpyDeviceToHost, stream));
-        Z_TRY(hipMemcpyAsync(hubar.data(), dubar.ptr, (size_t)nc * nv * n_u * sizeof(double),
-                             hipMemcpyDeviceToHost, stream));
-        Z_TRY(hipMemcpyAsync(hcell.data(), dcell.ptr, (size_t)nc * sizeof(int32_t),
-                             hipMemcpyDeviceToHost, stream));
-        Z_TRY(hipMemcpyAsync(htheta.data(), dtheta.ptr, (size_t)nc * nv * pp * sizeof(double),
-                             hipMemcpyDeviceToHost, stream));
-        Z_TRY(hipMemcpyAsync(hkonst.data(), dkonst.ptr, (size_t)nc * nv * sizeof(double),
-                             hipMemcpyDeviceToHost, stream));
-        Z_TRY(hipMemcpyAsync(hnolaw.data(), dnolaw.ptr, (size_t)nc * sizeof(int32_t),
-                             hipMemcpyDeviceToHost, stream));
-        Z_TRY(hipStreamSynchronize(stream));
+        EHM_HIP_TRY(z_err, hipGetLastError());
+        EHM_HIP_TRY(z_err, hipMemcpyAsync(hvert.data(), dvert.ptr,
+                                          (size_t)nc * cell * sizeof(double), hipMemcpyDeviceToHost,
+                                          stream));
+        EHM_HIP_TRY(z_err, hipMemcpyAsync(hubar.data(), dubar.ptr,
+                                          (size_t)nc * nv * n_u * sizeof(double),
+                                          hipMemcpyDeviceToHost, stream));
+        EHM_HIP_TRY(z_err, hipMemcpyAsync(hcell.data(), dcell.ptr, (size_t)nc * sizeof(int32_t),
+                                          hipMemcpyDeviceToHost, stream));
+        EHM_HIP_TRY(z_err, hipMemcpyAsync(htheta.data(), dtheta.ptr,
+                                          (size_t)nc * nv * pp * sizeof(double),
+                                          hipMemcpyDeviceToHost, stream));
+        EHM_HIP_TRY(z_err, hipMemcpyAsync(hkonst.data(), dkonst.ptr,
+                                          (size_t)nc * nv * sizeof(double), hipMemcpyDeviceToHost,
+                                          stream));
+        EHM_HIP_TRY(z_err, hipMemcpyAsync(hnolaw.data(), dnolaw.ptr, (size_t)nc * sizeof(int32_t),
+                                          hipMemcpyDeviceToHost, stream));
+        EHM_HIP_TRY(z_err, hipStreamSynchronize(stream));
         // candidates: on the exact substitution, and where it gives none on the relaxed problem
         todo.clear();
         for (long long q = 0; q < nc; ++q) {
@@ -541,7 +498,7 @@ int ehm_compiled_certify(ehm_compiled* law, ehm_problem* oracle, ehm_problem* ap
             }
             rc = ehm_bar_e_batch(oracle, (int64_t)nb, R.data(), Vb.data(), closed.data(),
                                  tb.data());
-            if (rc) return zfail(rc, "certify: ehm_bar_e_batch: %s", ehm_last_error());
+            if (rc) return z_err.fail(rc, "certify: ehm_bar_e_batch: %s", ehm_last_error());
             next.clear();
             for (size_t a = 0; a < nb; ++a) {
                 const long long q = open[a];
@@ -566,21 +523,21 @@ int ehm_compiled_certify(ehm_compiled* law, ehm_problem* oracle, ehm_problem* ap
             for (size_t a = 0; a < todo.size(); ++a)
                 std::memcpy(&R[a * cell], &hvert[(size_t)todo[a] * cell], cell * sizeof(double));
             rc = ehm_volume_batch(v.device, (int64_t)todo.size(), p, R.data(), vsub.data());
-            if (rc) return zfail(rc, "certify: ehm_volume_batch: %s", ehm_last_error());
+            if (rc) return z_err.fail(rc, "certify: ehm_volume_batch: %s", ehm_last_error());
             for (size_t a = 0; a < todo.size(); ++a) hvol[(size_t)todo[a]] = vsub[a];
         }
         res->seconds[4] += wall_since(t0);
         // the judgement
-        Z_TRY(hipSetDevice(v.device));
+        EHM_HIP_TRY(z_err, hipSetDevice(v.device));
         const unsigned nblk = blocks_of(nc, EHM_CERT_JUDGE_BLOCK);
-        Z_TRY(hipMemcpyAsync(dncand.ptr, hncand.data(), (size_t)nc * sizeof(int32_t),
-                             hipMemcpyHostToDevice, stream));
-        Z_TRY(hipMemcpyAsync(dnaside.ptr, hnaside.data(), (size_t)nc * sizeof(int32_t),
-                             hipMemcpyHostToDevice, stream));
-        Z_TRY(hipMemcpyAsync(dclosed.ptr, hclosed.data(), (size_t)nc * sizeof(int32_t),
-                             hipMemcpyHostToDevice, stream));
-        Z_TRY(hipMemcpyAsync(dtbest.ptr, htbest.data(), (size_t)nc * sizeof(double),
-                             hipMemcpyHostToDevice, stream));
+        EHM_HIP_TRY(z_err, hipMemcpyAsync(dncand.ptr, hncand.data(), (size_t)nc * sizeof(int32_t),
+                                          hipMemcpyHostToDevice, stream));
+        EHM_HIP_TRY(z_err, hipMemcpyAsync(dnaside.ptr, hnaside.data(), (size_t)nc * sizeof(int32_t),
+                                          hipMemcpyHostToDevice, stream));
+        EHM_HIP_TRY(z_err, hipMemcpyAsync(dclosed.ptr, hclosed.data(), (size_t)nc * sizeof(int32_t),
+                                          hipMemcpyHostToDevice, stream));
+        EHM_HIP_TRY(z_err, hipMemcpyAsync(dtbest.ptr, htbest.data(), (size_t)nc * sizeof(double),
+                                          hipMemcpyHostToDevice, stream));
         (void)hipEventRecord(ev_j.e0, stream);
         hipLaunchKernelGGL(k_certify_judge, dim3(nblk), dim3(EHM_CERT_JUDGE_BLOCK), 0, stream, nc,
                            off, dcell.as<const int32_t>(), dnolaw.as<const int32_t>(),
@@ -589,27 +546,24 @@ int ehm_compiled_certify(ehm_compiled* law, ehm_problem* oracle, ehm_problem* ap
                            dstatus.as<int32_t>(), dcnt.as<unsigned long long>(), dbt.as<double>(),
                            dbi.as<long long>());
         (void)hipEventRecord(ev_j.e1, stream);
-        Z_TRY(hipGetLastError());
-        Z_TRY(hipMemcpyAsync(hstatus.data(), dstatus.ptr, (size_t)nc * sizeof(int32_t),
-                             hipMemcpyDeviceToHost, stream));
-        Z_TRY(hipMemcpyAsync(hbt.data(), dbt.ptr, nblk * sizeof(double), hipMemcpyDeviceToHost,
-                             stream));
-        Z_TRY(hipMemcpyAsync(hbi.data(), dbi.ptr, nblk * sizeof(long long), hipMemcpyDeviceToHost,
-                             stream));
-        Z_TRY(hipStreamSynchronize(stream));
+        EHM_HIP_TRY(z_err, hipGetLastError());
+        EHM_HIP_TRY(z_err, hipMemcpyAsync(hstatus.data(), dstatus.ptr, (size_t)nc * sizeof(int32_t),
+                                          hipMemcpyDeviceToHost, stream));
+        EHM_HIP_TRY(z_err, hipMemcpyAsync(hbt.data(), dbt.ptr, nblk * sizeof(double),
+                                          hipMemcpyDeviceToHost, stream));
+        EHM_HIP_TRY(z_err, hipMemcpyAsync(hbi.data(), dbi.ptr, nblk * sizeof(long long),
+                                          hipMemcpyDeviceToHost, stream));
+        EHM_HIP_TRY(z_err, hipStreamSynchronize(stream));
         double s = 0.0;
         ev_c.seconds(&s);
         res->seconds[0] += s;
         ev_j.seconds(&s);
         res->seconds[0] += s;
-        for (unsigned b = 0; b < nblk; ++b)
-            if (hbi[b] >= 0 && (!have_worst || ehm_cert::worst_beats(hbt[b], hbi[b],
-                                                                     res->worst_tbest,
-                                                                     res->worst_leaf))) {
-                have_worst = true;
-                res->worst_tbest = hbt[b];
-                res->worst_leaf = hbi[b];
-            }
+        if (ehm_verdict::merge_block_worst(hbt.data(), hbi.data(), nblk, -1LL,
+                                           ehm_cert::worst_beats, worst_tbest, worst_leaf)) {
+            res->worst_tbest = worst_tbest;
+            res->worst_leaf = worst_leaf;
+        }
         for (long long q = 0; q < nc; ++q) {
             if (hcell[q] == EHM_CELL_OK) res->cell_volume += hvol[q];
             if (hstatus[q] == ehm_cert::CERT_CERTIFIED) res->certified_volume += hvol[q];
@@ -633,7 +587,7 @@ int ehm_compiled_certify(ehm_compiled* law, ehm_problem* oracle, ehm_problem* ap
         res->seconds[5] += wall_since(t_pass) - batches;
     }
     unsigned long long cnt[ehm_cert::CERT_STATUSES];
-    Z_TRY(hipMemcpy(cnt, dcnt.ptr, sizeof cnt, hipMemcpyDeviceToHost));
+    EHM_HIP_TRY(z_err, hipMemcpy(cnt, dcnt.ptr, sizeof cnt, hipMemcpyDeviceToHost));
     for (int i = 0; i < ehm_cert::CERT_STATUSES; ++i) res->counts[i] = (int64_t)cnt[i];
     return EHM_OK;
 }

@@ -353,23 +353,7 @@ bool locate_off() {
     return off;
 }
 
-thread_local std::string c_err;
-int cfail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    c_err = buf;
-    return code;
-}
-
-#define C_TRY(expr)                                                                        \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return cfail(EHM_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
-    } while (0)
+thread_local ehm_err_channel c_err;
 
 // header of the arrays: [version, p, n_u, n_roots, n_int, n_leaf, n_test, node_stride,
 // leaf_stride, side_stride, has_nbr, n_source_nodes]
@@ -402,81 +386,81 @@ int validate(const int64_t* h, const T* node, const T* leaf_rec,
              const int32_t* leaf_node, const double* test_rec, const double* root_rec,
              const int32_t* root_entry, const int32_t* nbr) {
     constexpr bool SINGLE = sizeof(T) == sizeof(float);
-    if (!h) return cfail(EHM_E_INVALID, "compiled law: no header");
+    if (!h) return c_err.fail(EHM_E_INVALID, "compiled law: no header");
     if (h[H_VERSION] != EHM_C_VERSION)
-        return cfail(EHM_E_INVALID, "compiled law: format version %lld (this library reads %d)",
-                     (long long)h[H_VERSION], EHM_C_VERSION);
+        return c_err.fail(EHM_E_INVALID, "compiled law: format version %lld (this library reads "
+                          "%d)", (long long)h[H_VERSION], EHM_C_VERSION);
     const int64_t p = h[H_P], n_u = h[H_NU], n_roots = h[H_ROOTS], n_int = h[H_INT],
                   n_leaf = h[H_LEAF], n_test = h[H_TEST];
     if (p < 1 || p > EHM_CP || n_u < 1 || n_u > (1 << 20))
-        return cfail(EHM_E_INVALID, "compiled law: p = %lld (1..%d), n_u = %lld", (long long)p,
-                     EHM_CP, (long long)n_u);
+        return c_err.fail(EHM_E_INVALID, "compiled law: p = %lld (1..%d), n_u = %lld", (long long)p,
+                          EHM_CP, (long long)n_u);
     const int64_t lim = (int64_t)1 << 31;
     if (n_roots < 1 || n_int < 0 || n_leaf < 1 || n_test < 0 || n_test > n_int ||
         n_int >= lim || n_leaf >= lim || n_roots > n_int + n_leaf || h[H_SRC] < n_leaf ||
         h[H_SRC] >= lim)
-        return cfail(EHM_E_INVALID, "compiled law: bad counts");
+        return c_err.fail(EHM_E_INVALID, "compiled law: bad counts");
     if (SINGLE && n_test > 0)
-        return cfail(EHM_E_INVALID, "compiled law: a single-precision law has no test nodes (%lld)",
-                     (long long)n_test);
+        return c_err.fail(EHM_E_INVALID, "compiled law: a single-precision law has no test nodes "
+                          "(%lld)", (long long)n_test);
     const int ns = SINGLE ? node_stride32_of((int)p) : node_stride_of((int)p),
               ls = SINGLE ? leaf_stride32_of((int)p, (int)n_u) : leaf_stride_of((int)p, (int)n_u),
               ss = side_stride_of((int)p);
     if (h[H_NS] != ns || h[H_LS] != ls || h[H_SS] != ss)
-        return cfail(EHM_E_INVALID, "compiled law: record strides %lld / %lld / %lld, not "
-                     "%d / %d / %d", (long long)h[H_NS], (long long)h[H_LS], (long long)h[H_SS],
-                     ns, ls, ss);
+        return c_err.fail(EHM_E_INVALID, "compiled law: record strides %lld / %lld / %lld, not %d "
+                          "/ %d / %d", (long long)h[H_NS], (long long)h[H_LS], (long long)h[H_SS],
+                          ns, ls, ss);
     if (h[H_NBR] != 0 && h[H_NBR] != 1)
-        return cfail(EHM_E_INVALID, "compiled law: bad adjacency flag");
+        return c_err.fail(EHM_E_INVALID, "compiled law: bad adjacency flag");
     if (h[H_NBR] && (n_roots < EHM_C_LOCATE_MIN || n_roots >= (1 << 20)))
-        return cfail(EHM_E_INVALID, "compiled law: an adjacency table with %lld roots",
-                     (long long)n_roots);
+        return c_err.fail(EHM_E_INVALID, "compiled law: an adjacency table with %lld roots",
+                          (long long)n_roots);
     if ((n_int && !node) || !leaf_rec || !leaf_node || (n_test && !test_rec) || !root_rec ||
         !root_entry || (h[H_NBR] && !nbr))
-        return cfail(EHM_E_INVALID, "compiled law: an array is missing");
+        return c_err.fail(EHM_E_INVALID, "compiled law: an array is missing");
     for (int64_t k = 0; k < n_int; ++k) {
         const T* r = node + (size_t)k * ns;
         if (!all_finite(r, (size_t)p + 1))
-            return cfail(EHM_E_INVALID, "compiled law: node %lld is not finite", (long long)k);
+            return c_err.fail(EHM_E_INVALID, "compiled law: node %lld is not finite", (long long)k);
         int32_t ch[2];
         std::memcpy(ch, r + p + 1, sizeof ch);
         for (int s = 0; s < 2; ++s)
             if (!entry_ok(ch[s], n_int, n_leaf) || (ch[s] >= 0 && ch[s] <= k))
-                return cfail(EHM_E_INVALID, "compiled law: node %lld has child %d (children "
-                             "come after their parents)", (long long)k, (int)ch[s]);
+                return c_err.fail(EHM_E_INVALID, "compiled law: node %lld has child %d (children "
+                                  "come after their parents)", (long long)k, (int)ch[s]);
         bool zero = true, bits = true;
         for (int c = 0; c < p; ++c) {
             zero = zero && r[c] == 0.0;
             bits = bits && !std::signbit(r[c]);
         }
         if (zero && !(bits && r[p] >= 0.0 && r[p] < (double)n_test && r[p] == std::floor(r[p])))
-            return cfail(EHM_E_INVALID, "compiled law: node %lld has a zero normal and names no "
-                         "test record", (long long)k);
+            return c_err.fail(EHM_E_INVALID, "compiled law: node %lld has a zero normal and names "
+                              "no test record", (long long)k);
     }
     if constexpr (SINGLE) {
         bool normal = all_normal(leaf_rec, (size_t)n_leaf * ls);
         for (int64_t k = 0; k < n_int && normal; ++k)
             normal = all_normal(node + (size_t)k * ns, (size_t)p + 1);
         if (!normal)
-            return cfail(EHM_E_INVALID, "compiled law: a single-precision record holds a "
-                         "subnormal or non-finite value");
+            return c_err.fail(EHM_E_INVALID, "compiled law: a single-precision record holds a "
+                              "subnormal or non-finite value");
     }
     if (!all_finite(leaf_rec, (size_t)n_leaf * ls) || (n_test && !all_finite(test_rec, (size_t)n_test * ss)) ||
         !all_finite(root_rec, (size_t)n_roots * ss))
-        return cfail(EHM_E_INVALID, "compiled law: a record is not finite");
+        return c_err.fail(EHM_E_INVALID, "compiled law: a record is not finite");
     for (int64_t l = 0; l < n_leaf; ++l)
         if (leaf_node[l] < 0 || leaf_node[l] >= h[H_SRC])
-            return cfail(EHM_E_INVALID, "compiled law: leaf %lld names node %d of %lld",
-                         (long long)l, (int)leaf_node[l], (long long)h[H_SRC]);
+            return c_err.fail(EHM_E_INVALID, "compiled law: leaf %lld names node %d of %lld",
+                              (long long)l, (int)leaf_node[l], (long long)h[H_SRC]);
     for (int64_t r = 0; r < n_roots; ++r)
         if (!entry_ok(root_entry[r], n_int, n_leaf))
-            return cfail(EHM_E_INVALID, "compiled law: root %lld enters at %d", (long long)r,
-                         (int)root_entry[r]);
+            return c_err.fail(EHM_E_INVALID, "compiled law: root %lld enters at %d", (long long)r,
+                              (int)root_entry[r]);
     if (h[H_NBR])
         for (int64_t i = 0; i < n_roots * (p + 1); ++i)
             if (nbr[i] < -1 || nbr[i] >= n_roots)
-                return cfail(EHM_E_INVALID, "compiled law: adjacency entry %lld is %d",
-                             (long long)i, (int)nbr[i]);
+                return c_err.fail(EHM_E_INVALID, "compiled law: adjacency entry %lld is %d",
+                                  (long long)i, (int)nbr[i]);
     return EHM_OK;
 }
 
@@ -558,26 +542,27 @@ template <class T>
 int import_law(int device, const int64_t* header, const T* node, const T* leaf_rec,
                const int32_t* leaf_node, const double* test_rec, const double* root_rec,
                const int32_t* root_entry, const int32_t* nbr, ehm_compiled** out) {
-    if (!out) return cfail(EHM_E_INVALID, "import: bad argument");
+    if (!out) return c_err.fail(EHM_E_INVALID, "import: bad argument");
     *out = nullptr;
     const int rc = validate(header, node, leaf_rec, leaf_node, test_rec, root_rec, root_entry, nbr);
     if (rc != EHM_OK) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return cfail(EHM_E_NO_DEVICE, "no HIP device %d (libehmpc has no CPU fallback)", device);
+        return c_err.fail(EHM_E_NO_DEVICE, "no HIP device %d (libehmpc has no CPU fallback)",
+                          device);
     LawPtr C(new ehm_compiled(), ehm_compiled_destroy);
     C->device = device;
     C->single = sizeof(T) == sizeof(float);
     std::memcpy(C->h, header, sizeof C->h);
-    C_TRY(hipSetDevice(device));
-    C_TRY(C->stream.create());
-    C_TRY(C->node.upload(node, C->node_bytes()));
-    C_TRY(C->leaf_rec.upload(leaf_rec, C->leaf_bytes()));
-    C_TRY(C->leaf_node.upload(leaf_node, C->leaf_node_bytes()));
-    C_TRY(C->test_rec.upload(test_rec, C->test_bytes()));
-    C_TRY(C->root_rec.upload(root_rec, C->root_bytes()));
-    C_TRY(C->root_entry.upload(root_entry, C->entry_bytes()));
-    if (header[H_NBR]) C_TRY(C->nbr.upload(nbr, C->nbr_bytes()));
+    EHM_HIP_TRY(c_err, hipSetDevice(device));
+    EHM_HIP_TRY(c_err, C->stream.create());
+    EHM_HIP_TRY(c_err, C->node.upload(node, C->node_bytes()));
+    EHM_HIP_TRY(c_err, C->leaf_rec.upload(leaf_rec, C->leaf_bytes()));
+    EHM_HIP_TRY(c_err, C->leaf_node.upload(leaf_node, C->leaf_node_bytes()));
+    EHM_HIP_TRY(c_err, C->test_rec.upload(test_rec, C->test_bytes()));
+    EHM_HIP_TRY(c_err, C->root_rec.upload(root_rec, C->root_bytes()));
+    EHM_HIP_TRY(c_err, C->root_entry.upload(root_entry, C->entry_bytes()));
+    if (header[H_NBR]) EHM_HIP_TRY(c_err, C->nbr.upload(nbr, C->nbr_bytes()));
     C->bind();
     *out = C.release();
     return EHM_OK;
@@ -586,11 +571,12 @@ int import_law(int device, const int64_t* header, const T* node, const T* leaf_r
 // ehm_compiled_export / _export_single
 int export_law(ehm_compiled* C, bool single, void* node, void* leaf_rec, int32_t* leaf_node,
                double* test_rec, double* root_rec, int32_t* root_entry, int32_t* nbr) {
-    if (!C) return cfail(EHM_E_INVALID, "export: bad argument");
+    if (!C) return c_err.fail(EHM_E_INVALID, "export: bad argument");
     if (C->single != single)
-        return cfail(EHM_E_INVALID, "export: the law is in %s precision (ehm_compiled_export%s)",
-                     C->single ? "single" : "double", C->single ? "_single" : "");
-    C_TRY(hipSetDevice(C->device));
+        return c_err.fail(EHM_E_INVALID, "export: the law is in %s precision "
+                          "(ehm_compiled_export%s)", C->single ? "single" : "double",
+                          C->single ? "_single" : "");
+    EHM_HIP_TRY(c_err, hipSetDevice(C->device));
     struct {
         void* host;
         const DevBuf* buf;
@@ -604,7 +590,8 @@ int export_law(ehm_compiled* C, bool single, void* node, void* leaf_rec, int32_t
                  {nbr, &C->nbr, C->nbr_bytes()}};
     for (const auto& part : parts)
         if (part.host && part.bytes)
-            C_TRY(hipMemcpy(part.host, part.buf->ptr, part.bytes, hipMemcpyDeviceToHost));
+            EHM_HIP_TRY(c_err, hipMemcpy(part.host, part.buf->ptr, part.bytes,
+                                         hipMemcpyDeviceToHost));
     return EHM_OK;
 }
 
@@ -613,7 +600,7 @@ int export_law(ehm_compiled* C, bool single, void* node, void* leaf_rec, int32_t
 int ehm_compiled_adopt(const ehm_compiled* like, int64_t n_int, int64_t n_leaf, DevBuf& node,
                        DevBuf& leaf_rec, DevBuf& leaf_node, DevBuf& root_entry,
                        ehm_compiled** out) {
-    if (!like || !out) return cfail(EHM_E_INVALID, "adopt: bad argument");
+    if (!like || !out) return c_err.fail(EHM_E_INVALID, "adopt: bad argument");
     *out = nullptr;
     LawPtr C(new ehm_compiled(), ehm_compiled_destroy);
     C->device = like->device;
@@ -622,19 +609,20 @@ int ehm_compiled_adopt(const ehm_compiled* like, int64_t n_int, int64_t n_leaf, 
     C->h[H_INT] = n_int;
     C->h[H_LEAF] = n_leaf;
     C->source_bytes = like->source_bytes;
-    C_TRY(hipSetDevice(C->device));
-    C_TRY(C->stream.create());
+    EHM_HIP_TRY(c_err, hipSetDevice(C->device));
+    EHM_HIP_TRY(c_err, C->stream.create());
     C->node = std::move(node);
     C->leaf_rec = std::move(leaf_rec);
     C->leaf_node = std::move(leaf_node);
     C->root_entry = std::move(root_entry);
-    C_TRY(C->test_rec.alloc(0));
-    C_TRY(C->root_rec.alloc(C->root_bytes()));
-    C_TRY(hipMemcpy(C->root_rec.ptr, like->root_rec.ptr, C->root_bytes(),
-                    hipMemcpyDeviceToDevice));
+    EHM_HIP_TRY(c_err, C->test_rec.alloc(0));
+    EHM_HIP_TRY(c_err, C->root_rec.alloc(C->root_bytes()));
+    EHM_HIP_TRY(c_err, hipMemcpy(C->root_rec.ptr, like->root_rec.ptr, C->root_bytes(),
+                                 hipMemcpyDeviceToDevice));
     if (C->nbr_bytes()) {
-        C_TRY(C->nbr.alloc(C->nbr_bytes()));
-        C_TRY(hipMemcpy(C->nbr.ptr, like->nbr.ptr, C->nbr_bytes(), hipMemcpyDeviceToDevice));
+        EHM_HIP_TRY(c_err, C->nbr.alloc(C->nbr_bytes()));
+        EHM_HIP_TRY(c_err, hipMemcpy(C->nbr.ptr, like->nbr.ptr, C->nbr_bytes(),
+                                     hipMemcpyDeviceToDevice));
     }
     // the check of an import, on a host copy of what the device now holds
     std::vector<char> h_node(C->node_bytes()), h_leaf(C->leaf_bytes());
@@ -676,24 +664,26 @@ int ehm_compiled_create(ehm_explicit* src, const double* vertices, ehm_compiled*
 
 int ehm_compiled_create_opts(ehm_explicit* src, const double* vertices, int32_t flags,
                              ehm_compiled** out, double* compile_seconds) {
-    if (!src || !vertices || !out) return cfail(EHM_E_INVALID, "compile: bad argument");
+    if (!src || !vertices || !out) return c_err.fail(EHM_E_INVALID, "compile: bad argument");
     *out = nullptr;
     if (flags & ~EHM_COMPILE_SPINE_ROOTS)
-        return cfail(EHM_E_INVALID, "compile: unknown flags %d", (int)flags);
+        return c_err.fail(EHM_E_INVALID, "compile: unknown flags %d", (int)flags);
     ehm_explicit_view v{};
     ehm_explicit_get_view(src, &v);
     const int p = v.p, n_u = v.n_u;
     const int64_t n = v.n_nodes;
-    if (n >= ((int64_t)1 << 31)) return cfail(EHM_E_INVALID, "compile: %lld nodes", (long long)n);
+    if (n >= ((int64_t)1 << 31)) return c_err.fail(EHM_E_INVALID, "compile: %lld nodes",
+                                                   (long long)n);
     LawPtr C(new ehm_compiled(), ehm_compiled_destroy);
     C->device = v.device;
-    C_TRY(hipSetDevice(v.device));
-    C_TRY(C->stream.create());
+    EHM_HIP_TRY(c_err, hipSetDevice(v.device));
+    EHM_HIP_TRY(c_err, C->stream.create());
     const auto t0 = std::chrono::steady_clock::now();
     // the numbering (host: a prefix count over the child pairs): internal nodes and leaves in
     // source order
     std::vector<int2> ch((size_t)n);
-    C_TRY(hipMemcpy(ch.data(), v.child, ch.size() * sizeof(int2), hipMemcpyDeviceToHost));
+    EHM_HIP_TRY(c_err, hipMemcpy(ch.data(), v.child, ch.size() * sizeof(int2),
+                                 hipMemcpyDeviceToHost));
     std::vector<int32_t> newid((size_t)n);
     int64_t n_int = 0, n_leaf = 0;
     for (int64_t k = 0; k < n; ++k) {
@@ -703,22 +693,22 @@ int ehm_compiled_create_opts(ehm_explicit* src, const double* vertices, int32_t 
             continue;
         }
         if (c.x <= k || c.y <= k || c.x >= n || c.y >= n)
-            return cfail(EHM_E_INVALID, "compile: node %lld has children %d, %d (a compiled law "
-                         "needs children after their parents)", (long long)k, c.x, c.y);
+            return c_err.fail(EHM_E_INVALID, "compile: node %lld has children %d, %d (a compiled "
+                              "law needs children after their parents)", (long long)k, c.x, c.y);
         newid[(size_t)k] = (int32_t)n_int++;
     }
     const int ns = node_stride_of(p), ls = leaf_stride_of(p, n_u), ss = side_stride_of(p);
     DevBuf d_vert, d_cls, d_newid, d_tidx;
-    C_TRY(d_vert.upload(vertices, (size_t)n * (p + 1) * p * sizeof(double)));
-    C_TRY(d_cls.alloc((size_t)n * sizeof(int32_t)));
+    EHM_HIP_TRY(c_err, d_vert.upload(vertices, (size_t)n * (p + 1) * p * sizeof(double)));
+    EHM_HIP_TRY(c_err, d_cls.alloc((size_t)n * sizeof(int32_t)));
     const dim3 grid((unsigned)((n + 127) / 128)), block(128);
     hipLaunchKernelGGL(k_compiled_classify, grid, block, 0, C->stream, (long long)n, p, v.child,
                        d_vert.as<const double>(), d_cls.as<int32_t>());
-    C_TRY(hipGetLastError());
+    EHM_HIP_TRY(c_err, hipGetLastError());
     std::vector<int32_t> cls((size_t)n), tidx((size_t)n, -1);
-    C_TRY(hipMemcpyAsync(cls.data(), d_cls.ptr, cls.size() * sizeof(int32_t),
-                         hipMemcpyDeviceToHost, C->stream));
-    C_TRY(hipStreamSynchronize(C->stream));
+    EHM_HIP_TRY(c_err, hipMemcpyAsync(cls.data(), d_cls.ptr, cls.size() * sizeof(int32_t),
+                                      hipMemcpyDeviceToHost, C->stream));
+    EHM_HIP_TRY(c_err, hipStreamSynchronize(C->stream));
     d_vert.reset();             // the vertices were needed for the classification only
     // EHM_COMPILE_SPINE_ROOTS: the chain of test nodes from node 0 along the right children gets
     // no records, and what hangs off it becomes the roots (source ids in root_ids; empty: the
@@ -733,8 +723,8 @@ int ehm_compiled_create_opts(ehm_explicit* src, const double* vertices, int32_t 
         }
         if (!root_ids.empty()) {
             root_ids.push_back((int32_t)k);
-            C_TRY(hipMemcpyAsync(d_cls.ptr, cls.data(), cls.size() * sizeof(int32_t),
-                                 hipMemcpyHostToDevice, C->stream));
+            EHM_HIP_TRY(c_err, hipMemcpyAsync(d_cls.ptr, cls.data(), cls.size() * sizeof(int32_t),
+                                              hipMemcpyHostToDevice, C->stream));
             n_int = 0;
             for (int64_t i = 0; i < n; ++i)
                 if (ch[(size_t)i].x >= 0)
@@ -742,11 +732,11 @@ int ehm_compiled_create_opts(ehm_explicit* src, const double* vertices, int32_t 
         }
     }
     const int64_t n_roots = root_ids.empty() ? (int64_t)v.n_roots : (int64_t)root_ids.size();
-    C_TRY(d_newid.upload(newid.data(), newid.size() * sizeof(int32_t)));
+    EHM_HIP_TRY(c_err, d_newid.upload(newid.data(), newid.size() * sizeof(int32_t)));
     int64_t n_test = 0;
     for (int64_t k = 0; k < n; ++k)
         if (cls[(size_t)k] == 0) tidx[(size_t)k] = (int32_t)n_test++;
-    C_TRY(d_tidx.upload(tidx.data(), tidx.size() * sizeof(int32_t)));
+    EHM_HIP_TRY(c_err, d_tidx.upload(tidx.data(), tidx.size() * sizeof(int32_t)));
     int64_t* h = C->h;
     h[H_VERSION] = EHM_C_VERSION;
     h[H_P] = p;
@@ -761,28 +751,28 @@ int ehm_compiled_create_opts(ehm_explicit* src, const double* vertices, int32_t 
     const bool own_nbr = !root_ids.empty() && n_roots >= EHM_C_LOCATE_MIN && n_roots < (1 << 20);
     h[H_NBR] = (root_ids.empty() ? v.nbr != nullptr : own_nbr) ? 1 : 0;
     h[H_SRC] = n;
-    C_TRY(C->node.alloc(C->node_bytes()));
-    C_TRY(C->leaf_rec.alloc(C->leaf_bytes()));
-    C_TRY(C->leaf_node.alloc(C->leaf_node_bytes()));
-    C_TRY(C->test_rec.alloc(C->test_bytes()));
-    C_TRY(C->root_rec.alloc(C->root_bytes()));
+    EHM_HIP_TRY(c_err, C->node.alloc(C->node_bytes()));
+    EHM_HIP_TRY(c_err, C->leaf_rec.alloc(C->leaf_bytes()));
+    EHM_HIP_TRY(c_err, C->leaf_node.alloc(C->leaf_node_bytes()));
+    EHM_HIP_TRY(c_err, C->test_rec.alloc(C->test_bytes()));
+    EHM_HIP_TRY(c_err, C->root_rec.alloc(C->root_bytes()));
     DevBuf d_root_ids;
     if (root_ids.empty()) {
-        C_TRY(C->root_entry.upload(newid.data(), C->entry_bytes()));
+        EHM_HIP_TRY(c_err, C->root_entry.upload(newid.data(), C->entry_bytes()));
         if (v.nbr) {
-            C_TRY(C->nbr.alloc(C->nbr_bytes()));
-            C_TRY(hipMemcpyAsync(C->nbr.ptr, v.nbr, C->nbr_bytes(), hipMemcpyDeviceToDevice,
-                                 C->stream));
+            EHM_HIP_TRY(c_err, C->nbr.alloc(C->nbr_bytes()));
+            EHM_HIP_TRY(c_err, hipMemcpyAsync(C->nbr.ptr, v.nbr, C->nbr_bytes(),
+                                              hipMemcpyDeviceToDevice, C->stream));
         }
     } else {
         std::vector<int32_t> entry(root_ids.size());
         for (size_t i = 0; i < root_ids.size(); ++i) entry[i] = newid[(size_t)root_ids[i]];
-        C_TRY(C->root_entry.upload(entry.data(), C->entry_bytes()));
-        C_TRY(d_root_ids.upload(root_ids.data(), root_ids.size() * sizeof(int32_t)));
+        EHM_HIP_TRY(c_err, C->root_entry.upload(entry.data(), C->entry_bytes()));
+        EHM_HIP_TRY(c_err, d_root_ids.upload(root_ids.data(), root_ids.size() * sizeof(int32_t)));
         if (own_nbr) {
             std::vector<int32_t> nbr;
             ehm_root_adjacency(n_roots, p, vertices, root_ids.data(), nbr);
-            C_TRY(C->nbr.upload(nbr.data(), C->nbr_bytes()));
+            EHM_HIP_TRY(c_err, C->nbr.upload(nbr.data(), C->nbr_bytes()));
         }
     }
     CompileArgs A{};
@@ -807,8 +797,8 @@ int ehm_compiled_create_opts(ehm_explicit* src, const double* vertices, int32_t 
     hipLaunchKernelGGL(k_compiled_roots, dim3((unsigned)((n_roots + 127) / 128)), block, 0,
                        C->stream, (int)n_roots, p, v.rec_stride, ss,
                        d_root_ids.as<const int32_t>(), v.rec, C->root_rec.as<double>());
-    C_TRY(hipGetLastError());
-    C_TRY(hipStreamSynchronize(C->stream));
+    EHM_HIP_TRY(c_err, hipGetLastError());
+    EHM_HIP_TRY(c_err, hipStreamSynchronize(C->stream));
     if (compile_seconds)
         *compile_seconds =
             std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -855,16 +845,17 @@ int ehm_compiled_narrow(ehm_compiled* src, ehm_compiled** out) {
 
 int ehm_compiled_narrow_opts(ehm_compiled* src, int32_t opts, int64_t* flushed,
                              ehm_compiled** out) {
-    if (!src || !out) return cfail(EHM_E_INVALID, "narrow: bad argument");
+    if (!src || !out) return c_err.fail(EHM_E_INVALID, "narrow: bad argument");
     *out = nullptr;
     if (flushed) flushed[0] = flushed[1] = flushed[2] = 0;
     if (opts & ~EHM_NARROW_FLUSH)
-        return cfail(EHM_E_INVALID, "narrow: unknown flags %d", (int)opts);
-    if (src->single) return cfail(EHM_E_INVALID, "narrow: the law is in single precision already");
+        return c_err.fail(EHM_E_INVALID, "narrow: unknown flags %d", (int)opts);
+    if (src->single) return c_err.fail(EHM_E_INVALID, "narrow: the law is in single precision "
+                                       "already");
     if (src->h[H_TEST] > 0)
-        return cfail(EHM_E_INVALID, "narrow: the law has %lld test nodes (children that are no "
-                     "bisection); only a walk by planes alone has a single-precision form",
-                     (long long)src->h[H_TEST]);
+        return c_err.fail(EHM_E_INVALID, "narrow: the law has %lld test nodes (children that are "
+                          "no bisection); only a walk by planes alone has a single-precision form",
+                          (long long)src->h[H_TEST]);
     const int p = src->d.p, n_u = src->d.n_u;
     LawPtr C(new ehm_compiled(), ehm_compiled_destroy);
     C->device = src->device;
@@ -873,11 +864,11 @@ int ehm_compiled_narrow_opts(ehm_compiled* src, int32_t opts, int64_t* flushed,
     C->h[H_NS] = node_stride32_of(p);
     C->h[H_LS] = leaf_stride32_of(p, n_u);
     C->source_bytes = src->source_bytes;
-    C_TRY(hipSetDevice(C->device));
-    C_TRY(C->stream.create());
-    C_TRY(C->node.alloc(C->node_bytes()));
-    C_TRY(C->leaf_rec.alloc(C->leaf_bytes()));
-    C_TRY(C->test_rec.alloc(0));
+    EHM_HIP_TRY(c_err, hipSetDevice(C->device));
+    EHM_HIP_TRY(c_err, C->stream.create());
+    EHM_HIP_TRY(c_err, C->node.alloc(C->node_bytes()));
+    EHM_HIP_TRY(c_err, C->leaf_rec.alloc(C->leaf_bytes()));
+    EHM_HIP_TRY(c_err, C->test_rec.alloc(0));
     struct {
         DevBuf* dst;
         const DevBuf* from;
@@ -888,17 +879,17 @@ int ehm_compiled_narrow_opts(ehm_compiled* src, int32_t opts, int64_t* flushed,
                 {&C->nbr, &src->nbr, C->nbr_bytes()}};
     for (const auto& part : same) {
         if (!part.bytes) continue;
-        C_TRY(part.dst->alloc(part.bytes));
-        C_TRY(hipMemcpyAsync(part.dst->ptr, part.from->ptr, part.bytes, hipMemcpyDeviceToDevice,
-                             C->stream));
+        EHM_HIP_TRY(c_err, part.dst->alloc(part.bytes));
+        EHM_HIP_TRY(c_err, hipMemcpyAsync(part.dst->ptr, part.from->ptr, part.bytes,
+                                          hipMemcpyDeviceToDevice, C->stream));
     }
     DevBuf d_flags, d_flushed;
-    C_TRY(d_flags.alloc(sizeof(int)));
-    C_TRY(hipMemsetAsync(d_flags.ptr, 0, sizeof(int), C->stream));
+    EHM_HIP_TRY(c_err, d_flags.alloc(sizeof(int)));
+    EHM_HIP_TRY(c_err, hipMemsetAsync(d_flags.ptr, 0, sizeof(int), C->stream));
     unsigned long long gone[3] = {0, 0, 0};
     if (opts & EHM_NARROW_FLUSH) {
-        C_TRY(d_flushed.alloc(sizeof gone));
-        C_TRY(hipMemsetAsync(d_flushed.ptr, 0, sizeof gone, C->stream));
+        EHM_HIP_TRY(c_err, d_flushed.alloc(sizeof gone));
+        EHM_HIP_TRY(c_err, hipMemsetAsync(d_flushed.ptr, 0, sizeof gone, C->stream));
     }
     NarrowArgs A{};
     A.n_int = src->h[H_INT];
@@ -917,20 +908,23 @@ int ehm_compiled_narrow_opts(ehm_compiled* src, int32_t opts, int64_t* flushed,
     A.flushed = d_flushed.as<unsigned long long>();
     void* args[] = {&A};
     // the source's arrays were written on its own stream (create) or by blocking copies (import)
-    C_TRY(hipStreamSynchronize(src->stream));
-    C_TRY(hipLaunchKernel(ehm_compiled32_api()->narrow,
-                          dim3((unsigned)((A.n_int + A.n_leaf + 255) / 256)), dim3(256), args, 0,
-                          C->stream));
+    EHM_HIP_TRY(c_err, hipStreamSynchronize(src->stream));
+    EHM_HIP_TRY(c_err, hipLaunchKernel(ehm_compiled32_api()->narrow,
+                                       dim3((unsigned)((A.n_int + A.n_leaf + 255) / 256)),
+                                       dim3(256), args, 0, C->stream));
     int flags = 0;
-    C_TRY(hipMemcpyAsync(&flags, d_flags.ptr, sizeof flags, hipMemcpyDeviceToHost, C->stream));
+    EHM_HIP_TRY(c_err, hipMemcpyAsync(&flags, d_flags.ptr, sizeof flags, hipMemcpyDeviceToHost,
+                                      C->stream));
     if (d_flushed)
-        C_TRY(hipMemcpyAsync(gone, d_flushed.ptr, sizeof gone, hipMemcpyDeviceToHost, C->stream));
-    C_TRY(hipStreamSynchronize(C->stream));
+        EHM_HIP_TRY(c_err, hipMemcpyAsync(gone, d_flushed.ptr, sizeof gone, hipMemcpyDeviceToHost,
+                                          C->stream));
+    EHM_HIP_TRY(c_err, hipStreamSynchronize(C->stream));
     if (flags)
-        return cfail(EHM_E_INVALID, "narrow: the law has no single-precision form:%s%s%s",
-                     flags & NARROW_OVERFLOW ? " a value overflows or is not finite;" : "",
-                     flags & NARROW_UNDERFLOW ? " a nonzero value becomes zero or subnormal;" : "",
-                     flags & NARROW_ZERO_NORMAL ? " a plane's normal becomes zero;" : "");
+        return c_err.fail(
+            EHM_E_INVALID, "narrow: the law has no single-precision form:%s%s%s",
+            flags & NARROW_OVERFLOW ? " a value overflows or is not finite;" : "",
+            flags & NARROW_UNDERFLOW ? " a nonzero value becomes zero or subnormal;" : "",
+            flags & NARROW_ZERO_NORMAL ? " a plane's normal becomes zero;" : "");
     if (flushed)
         for (int i = 0; i < 3; ++i) flushed[i] = (int64_t)gone[i];
     C->bind();
@@ -939,7 +933,7 @@ int ehm_compiled_narrow_opts(ehm_compiled* src, int32_t opts, int64_t* flushed,
 }
 
 int ehm_compiled_info(const ehm_compiled* C, int64_t* info) {
-    if (!C || !info) return cfail(EHM_E_INVALID, "info: bad argument");
+    if (!C || !info) return c_err.fail(EHM_E_INVALID, "info: bad argument");
     for (int i = 0; i < EHM_C_HEADER; ++i) info[i] = C->h[i];
     info[EHM_C_HEADER] = (int64_t)C->bytes();
     info[EHM_C_HEADER + 1] = C->source_bytes;
@@ -958,10 +952,11 @@ int ehm_compiled_export_single(ehm_compiled* C, float* node, float* leaf_rec, in
 
 int ehm_compiled_eval_batch(ehm_compiled* C, int64_t n, const double* x, double* u,
                             int32_t* leaf, int32_t* depth, double* kernel_seconds) {
-    if (!C || n < 0 || (n > 0 && (!x || !u))) return cfail(EHM_E_INVALID, "eval: bad argument");
+    if (!C || n < 0 || (n > 0 && (!x || !u))) return c_err.fail(EHM_E_INVALID, "eval: bad "
+                                                                "argument");
     if (kernel_seconds) *kernel_seconds = 0.0;
     if (n == 0) return EHM_OK;
-    C_TRY(hipSetDevice(C->device));
+    EHM_HIP_TRY(c_err, hipSetDevice(C->device));
     const int p = C->d.p, n_u = C->d.n_u;
     if ((size_t)n > C->cap) {
         for (DevBuf* b : {&C->x, &C->u, &C->leaf, &C->depth, &C->root}) b->reset();
@@ -971,12 +966,12 @@ int ehm_compiled_eval_batch(ehm_compiled* C, int64_t n, const double* x, double*
             C->leaf.alloc((size_t)n * sizeof(int32_t)) != hipSuccess ||
             C->depth.alloc((size_t)n * sizeof(int32_t)) != hipSuccess ||
             C->root.alloc((size_t)n * sizeof(int32_t)) != hipSuccess)
-            return cfail(EHM_E_HIP, "out of device memory for %lld queries", (long long)n);
+            return c_err.fail(EHM_E_HIP, "out of device memory for %lld queries", (long long)n);
         C->cap = (size_t)n;
     }
     EventPair ev;
-    C_TRY(hipMemcpyAsync(C->x.ptr, x, (size_t)n * p * sizeof(double), hipMemcpyHostToDevice,
-                         C->stream));
+    EHM_HIP_TRY(c_err, hipMemcpyAsync(C->x.ptr, x, (size_t)n * p * sizeof(double),
+                                      hipMemcpyHostToDevice, C->stream));
     (void)hipEventRecord(ev.e0, C->stream);
     const bool locate = C->nbr && !locate_off();
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
@@ -991,23 +986,24 @@ int ehm_compiled_eval_batch(ehm_compiled* C, int64_t n, const double* x, double*
         double* up = C->u.as<double>();
         int32_t *lp = C->leaf.as<int32_t>(), *dp = C->depth.as<int32_t>();
         void* args[] = {&C->d32, &nn, &xp, &up, &lp, &dp, &root};
-        C_TRY(hipLaunchKernel(ehm_compiled32_api()->eval[p - 1], grid, block, args, 0, C->stream));
+        EHM_HIP_TRY(c_err, hipLaunchKernel(ehm_compiled32_api()->eval[p - 1], grid, block, args, 0,
+                                           C->stream));
     } else {
         hipLaunchKernelGGL(k_eval_table[p - 1], grid, block, 0, C->stream, C->d, (long long)n,
                            C->x.as<const double>(), C->u.as<double>(), C->leaf.as<int32_t>(),
                            C->depth.as<int32_t>(), root);
     }
     (void)hipEventRecord(ev.e1, C->stream);
-    C_TRY(hipGetLastError());
-    C_TRY(hipMemcpyAsync(u, C->u.ptr, (size_t)n * n_u * sizeof(double), hipMemcpyDeviceToHost,
-                         C->stream));
+    EHM_HIP_TRY(c_err, hipGetLastError());
+    EHM_HIP_TRY(c_err, hipMemcpyAsync(u, C->u.ptr, (size_t)n * n_u * sizeof(double),
+                                      hipMemcpyDeviceToHost, C->stream));
     if (leaf)
-        C_TRY(hipMemcpyAsync(leaf, C->leaf.ptr, (size_t)n * sizeof(int32_t),
-                             hipMemcpyDeviceToHost, C->stream));
+        EHM_HIP_TRY(c_err, hipMemcpyAsync(leaf, C->leaf.ptr, (size_t)n * sizeof(int32_t),
+                                          hipMemcpyDeviceToHost, C->stream));
     if (depth)
-        C_TRY(hipMemcpyAsync(depth, C->depth.ptr, (size_t)n * sizeof(int32_t),
-                             hipMemcpyDeviceToHost, C->stream));
-    C_TRY(hipStreamSynchronize(C->stream));
+        EHM_HIP_TRY(c_err, hipMemcpyAsync(depth, C->depth.ptr, (size_t)n * sizeof(int32_t),
+                                          hipMemcpyDeviceToHost, C->stream));
+    EHM_HIP_TRY(c_err, hipStreamSynchronize(C->stream));
     ev.seconds(kernel_seconds);
     return EHM_OK;
 }
@@ -1020,12 +1016,12 @@ namespace {
 
 // what the plant setters refuse about the law itself
 int rollout_law_ok(const ehm_compiled* C, const char* who) {
-    if (!C) return cfail(EHM_E_INVALID, "%s: a required array is NULL", who);
+    if (!C) return c_err.fail(EHM_E_INVALID, "%s: a required array is NULL", who);
     if (C->h[H_TEST] > 0)
-        return cfail(EHM_E_INVALID, "%s: the law has %lld test nodes (children that are no "
-                     "bisection); the rollout's exit test is made on the root and needs a walk "
-                     "by planes alone -- roll such a tree out on the source evaluator", who,
-                     (long long)C->h[H_TEST]);
+        return c_err.fail(EHM_E_INVALID, "%s: the law has %lld test nodes (children that are no "
+                          "bisection); the rollout's exit test is made on the root and needs a "
+                          "walk by planes alone -- roll such a tree out on the source evaluator",
+                          who, (long long)C->h[H_TEST]);
     return EHM_OK;
 }
 
@@ -1050,10 +1046,10 @@ int ehm_compiled_set_plant(ehm_compiled* C, int32_t n_modes, const double* A, co
                            const double* R) {
     const int rc = rollout_law_ok(C, "set_plant");
     if (rc != EHM_OK) return rc;
-    return install_plant(C->ro, cfail, C->device, C->d.p, C->d.n_u, C->h[H_LEAF], "leaf",
+    return install_plant(C->ro, c_err, C->device, C->d.p, C->d.n_u, C->h[H_LEAF], "leaf",
                          "set_plant", n_modes, EHM_R_MAX_MODES, A, B, w, n_g, Gx, gx, leaf_mode,
                          cost_kind, Q, R, nullptr, [&](Pack& pk, DevPlant& pl, int p, int) {
-                             return pack_nominal(cfail, pk, pl, p, n_modes, n_d, Emat, region_rows,
+                             return pack_nominal(c_err, pk, pl, p, n_modes, n_d, Emat, region_rows,
                                                  H, h);
                          });
 }
@@ -1069,10 +1065,10 @@ int ehm_compiled_set_plant_guarded(ehm_compiled* C, int32_t n_modes, const doubl
     const int rc = rollout_law_ok(C, "set_plant_guarded");
     if (rc != EHM_OK) return rc;
     DevGuard gd{};
-    return install_plant(C->ro, cfail, C->device, C->d.p, C->d.n_u, C->h[H_LEAF], "leaf",
+    return install_plant(C->ro, c_err, C->device, C->d.p, C->d.n_u, C->h[H_LEAF], "leaf",
                          "set_plant_guarded", n_modes, EHM_G_MAX_MODES, A, B, w, n_g, Gx, gx,
                          leaf_mode, cost_kind, Q, R, &gd, [&](Pack& pk, DevPlant&, int p, int n_u) {
-                             return pack_guarded(cfail, pk, gd, p, n_u, n_modes, substeps, n_guards,
+                             return pack_guarded(c_err, pk, gd, p, n_u, n_modes, substeps, n_guards,
                                                  guard_mode, guard_row0, ga, gb, gc, gt, strict,
                                                  default_mode);
                          });
@@ -1080,8 +1076,8 @@ int ehm_compiled_set_plant_guarded(ehm_compiled* C, int32_t n_modes, const doubl
 
 int ehm_compiled_set_noise(ehm_compiled* C, int32_t n_terms, const int32_t* desc,
                            const double* data, int32_t n_data, int32_t n_d) {
-    if (!C) return cfail(EHM_E_INVALID, "set_noise: no handle");
-    return install_noise(C->ro, cfail, C->device, C->d.p, C->d.n_u, n_terms, desc, data, n_data,
+    if (!C) return c_err.fail(EHM_E_INVALID, "set_noise: no handle");
+    return install_noise(C->ro, c_err, C->device, C->d.p, C->d.n_u, n_terms, desc, data, n_data,
                          n_d);
 }
 
@@ -1090,13 +1086,13 @@ int ehm_compiled_rollout(ehm_compiled* C, int64_t n, int32_t T, const double* x0
                          double* u_traj, int32_t* leaf_traj, double* x_final, int32_t* steps,
                          int32_t* status, double* cost, double* u_norm_sum,
                          double* max_violation, double* kernel_seconds) {
-    if (!C) return cfail(EHM_E_INVALID, "rollout: bad argument");
+    if (!C) return c_err.fail(EHM_E_INVALID, "rollout: bad argument");
     if (C->single)
-        return rollout_run(C->ro, cfail, C->device, C->stream, C->d32, C->d.p, C->d.n_u,
+        return rollout_run(C->ro, c_err, C->device, C->stream, C->d32, C->d.p, C->d.n_u,
                            rollout_nbr(C), rollout32_table().fn, n, T, x0, d, v, tol_exit, x_traj,
                            u_traj, leaf_traj, x_final, steps, status, cost, u_norm_sum,
                            max_violation, kernel_seconds, nullptr);
-    return rollout_run(C->ro, cfail, C->device, C->stream, C->d, C->d.p, C->d.n_u, rollout_nbr(C),
+    return rollout_run(C->ro, c_err, C->device, C->stream, C->d, C->d.p, C->d.n_u, rollout_nbr(C),
                        k_rollout_table, n, T, x0, d, v, tol_exit, x_traj, u_traj, leaf_traj,
                        x_final, steps, status, cost, u_norm_sum, max_violation, kernel_seconds,
                        nullptr);
@@ -1108,16 +1104,16 @@ int ehm_compiled_rollout_noisy(ehm_compiled* C, int64_t n, int32_t T, const doub
                                double* e_traj, double* w_traj, double* x_final, int32_t* steps,
                                int32_t* status, double* cost, double* u_norm_sum,
                                double* max_violation, double* kernel_seconds) {
-    if (!C) return cfail(EHM_E_INVALID, "rollout_noisy: no handle");
-    const int rc = noisy_ready(C->ro, cfail);
+    if (!C) return c_err.fail(EHM_E_INVALID, "rollout_noisy: no handle");
+    const int rc = noisy_ready(C->ro, c_err);
     if (rc != EHM_OK) return rc;
     const NoisyCall nz{seed, traj0, v_traj, e_traj, w_traj};
     if (C->single)
-        return rollout_run(C->ro, cfail, C->device, C->stream, C->d32, C->d.p, C->d.n_u,
+        return rollout_run(C->ro, c_err, C->device, C->stream, C->d32, C->d.p, C->d.n_u,
                            rollout_nbr(C), rollout32_table().fn, n, T, x0, nullptr, nullptr,
                            tol_exit, x_traj, u_traj, leaf_traj, x_final, steps, status, cost,
                            u_norm_sum, max_violation, kernel_seconds, &nz);
-    return rollout_run(C->ro, cfail, C->device, C->stream, C->d, C->d.p, C->d.n_u, rollout_nbr(C),
+    return rollout_run(C->ro, c_err, C->device, C->stream, C->d, C->d.p, C->d.n_u, rollout_nbr(C),
                        k_rollout_table, n, T, x0, nullptr, nullptr, tol_exit, x_traj, u_traj,
                        leaf_traj, x_final, steps, status, cost, u_norm_sum, max_violation,
                        kernel_seconds, &nz);

@@ -289,23 +289,7 @@ bool locate_off() {
     return off;
 }
 
-thread_local std::string x_err;
-int xfail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    x_err = buf;
-    return code;
-}
-
-#define Y_TRY(expr)                                                                        \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return xfail(EHM_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
-    } while (0)
+thread_local ehm_err_channel x_err;
 
 
 }  // namespace
@@ -331,13 +315,13 @@ void ehm_explicit_get_view(const ehm_explicit* E, ehm_explicit_view* out) {
                              E->stream};
 }
 
+ehm_err_channel& ehm_explicit_channel() { return x_err; }
+
 int ehm_explicit_fail(int code, const char* fmt, ...) {
-    char buf[512];
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
+    x_err.vfail(code, fmt, ap);
     va_end(ap);
-    x_err = buf;
     return code;
 }
 
@@ -396,39 +380,42 @@ int ehm_explicit_create(int device, int64_t n_nodes, int32_t n_roots, int32_t p,
                         const double* vinput, ehm_explicit** out) {
     if (!out || !left || !right || !vertices || !vinput || n_nodes < 1 || n_roots < 1 ||
         n_roots > n_nodes || p < 1 || p > EHM_XP || n_u < 1)
-        return xfail(EHM_E_INVALID, "bad argument");
+        return x_err.fail(EHM_E_INVALID, "bad argument");
     *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return xfail(EHM_E_NO_DEVICE, "no HIP device %d (libehmpc has no CPU fallback)", device);
+        return x_err.fail(EHM_E_NO_DEVICE, "no HIP device %d (libehmpc has no CPU fallback)",
+                          device);
     // destroyed on every error return below
     std::unique_ptr<ehm_explicit, int (*)(ehm_explicit*)> E(new ehm_explicit(),
                                                             ehm_explicit_destroy);
     E->device = device;
-    Y_TRY(hipSetDevice(device));
-    Y_TRY(E->stream.create());
+    EHM_HIP_TRY(x_err, hipSetDevice(device));
+    EHM_HIP_TRY(x_err, E->stream.create());
     const int stride = ((p + p * p + 7) / 8) * 8;
     const size_t nV = (size_t)n_nodes * (p + 1) * p, nU = (size_t)n_nodes * (p + 1) * n_u;
     std::vector<int2> ch((size_t)n_nodes);
     for (int64_t k = 0; k < n_nodes; ++k) ch[(size_t)k] = make_int2(left[k], right[k]);
     DevBuf d_vert, d_sing;
-    Y_TRY(E->rec.alloc((size_t)n_nodes * stride * sizeof(double)));
-    Y_TRY(E->child.upload(ch.data(), ch.size() * sizeof(int2)));
-    Y_TRY(E->vinput.upload(vinput, nU * sizeof(double)));
-    Y_TRY(d_vert.upload(vertices, nV * sizeof(double)));
-    Y_TRY(d_sing.alloc(sizeof(int32_t)));
-    Y_TRY(hipMemset(d_sing.ptr, 0, sizeof(int32_t)));
+    EHM_HIP_TRY(x_err, E->rec.alloc((size_t)n_nodes * stride * sizeof(double)));
+    EHM_HIP_TRY(x_err, E->child.upload(ch.data(), ch.size() * sizeof(int2)));
+    EHM_HIP_TRY(x_err, E->vinput.upload(vinput, nU * sizeof(double)));
+    EHM_HIP_TRY(x_err, d_vert.upload(vertices, nV * sizeof(double)));
+    EHM_HIP_TRY(x_err, d_sing.alloc(sizeof(int32_t)));
+    EHM_HIP_TRY(x_err, hipMemset(d_sing.ptr, 0, sizeof(int32_t)));
     hipLaunchKernelGGL(k_explicit_setup, dim3((unsigned)((n_nodes + 127) / 128)), dim3(128), 0,
                        E->stream, (long long)n_nodes, (int)p, stride, d_vert.as<const double>(),
                        E->rec.as<double>(), d_sing.as<int32_t>());
     int32_t sing = 0;
-    Y_TRY(hipMemcpyAsync(&sing, d_sing.ptr, sizeof sing, hipMemcpyDeviceToHost, E->stream));
-    Y_TRY(hipStreamSynchronize(E->stream));
-    if (sing) return xfail(EHM_E_NUMERIC, "%d degenerate simplices in the partition", (int)sing);
+    EHM_HIP_TRY(x_err, hipMemcpyAsync(&sing, d_sing.ptr, sizeof sing, hipMemcpyDeviceToHost,
+                                      E->stream));
+    EHM_HIP_TRY(x_err, hipStreamSynchronize(E->stream));
+    if (sing) return x_err.fail(EHM_E_NUMERIC, "%d degenerate simplices in the partition",
+                                (int)sing);
     if (n_roots >= EHM_X_LOCATE_MIN && n_roots < (1 << 20)) {
         std::vector<int32_t> nbr;
         ehm_root_adjacency(n_roots, p, vertices, nullptr, nbr);
-        Y_TRY(E->nbr.upload(nbr.data(), nbr.size() * sizeof(int32_t)));
+        EHM_HIP_TRY(x_err, E->nbr.upload(nbr.data(), nbr.size() * sizeof(int32_t)));
     }
     E->d.rec = E->rec.as<const double>();
     E->d.child = E->child.as<const int2>();
@@ -444,10 +431,10 @@ int ehm_explicit_create(int device, int64_t n_nodes, int32_t n_roots, int32_t p,
 
 int ehm_explicit_eval_batch(ehm_explicit* E, int64_t n, const double* x, double* u,
                             int32_t* leaf, int32_t* visited, double* kernel_seconds) {
-    if (!E || !x || !u || n < 0) return xfail(EHM_E_INVALID, "bad argument");
+    if (!E || !x || !u || n < 0) return x_err.fail(EHM_E_INVALID, "bad argument");
     if (n == 0) return EHM_OK;
     hipError_t e = hipSetDevice(E->device);
-    if (e != hipSuccess) return xfail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return x_err.fail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
     const int p = E->d.p, n_u = E->d.n_u;
     if ((size_t)n > E->cap) {
         for (DevBuf* b : {&E->x, &E->u, &E->leaf, &E->depth, &E->root}) b->reset();
@@ -457,12 +444,12 @@ int ehm_explicit_eval_batch(ehm_explicit* E, int64_t n, const double* x, double*
             E->leaf.alloc((size_t)n * sizeof(int32_t)) != hipSuccess ||
             E->depth.alloc((size_t)n * sizeof(int32_t)) != hipSuccess ||
             E->root.alloc((size_t)n * sizeof(int32_t)) != hipSuccess)
-            return xfail(EHM_E_HIP, "out of device memory for %lld queries", (long long)n);
+            return x_err.fail(EHM_E_HIP, "out of device memory for %lld queries", (long long)n);
         E->cap = (size_t)n;
     }
     EventPair ev;
-    Y_TRY(hipMemcpyAsync(E->x.ptr, x, (size_t)n * p * sizeof(double), hipMemcpyHostToDevice,
-                         E->stream));
+    EHM_HIP_TRY(x_err, hipMemcpyAsync(E->x.ptr, x, (size_t)n * p * sizeof(double),
+                                      hipMemcpyHostToDevice, E->stream));
     (void)hipEventRecord(ev.e0, E->stream);
     // long spines: the visibility walk over the roots finds the root first (locate_off: the
     // reference's serial walk for every state)
@@ -476,38 +463,39 @@ int ehm_explicit_eval_batch(ehm_explicit* E, int64_t n, const double* x, double*
                        E->leaf.as<int32_t>(), E->depth.as<int32_t>(),
                        locate ? E->root.as<const int32_t>() : (const int32_t*)nullptr);
     (void)hipEventRecord(ev.e1, E->stream);
-    Y_TRY(hipGetLastError());
-    Y_TRY(hipMemcpyAsync(u, E->u.ptr, (size_t)n * n_u * sizeof(double), hipMemcpyDeviceToHost,
-                         E->stream));
+    EHM_HIP_TRY(x_err, hipGetLastError());
+    EHM_HIP_TRY(x_err, hipMemcpyAsync(u, E->u.ptr, (size_t)n * n_u * sizeof(double),
+                                      hipMemcpyDeviceToHost, E->stream));
     if (leaf)
-        Y_TRY(hipMemcpyAsync(leaf, E->leaf.ptr, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost,
-                             E->stream));
+        EHM_HIP_TRY(x_err, hipMemcpyAsync(leaf, E->leaf.ptr, (size_t)n * sizeof(int32_t),
+                                          hipMemcpyDeviceToHost, E->stream));
     if (visited)
-        Y_TRY(hipMemcpyAsync(visited, E->depth.ptr, (size_t)n * sizeof(int32_t),
-                             hipMemcpyDeviceToHost, E->stream));
-    Y_TRY(hipStreamSynchronize(E->stream));
+        EHM_HIP_TRY(x_err, hipMemcpyAsync(visited, E->depth.ptr, (size_t)n * sizeof(int32_t),
+                                          hipMemcpyDeviceToHost, E->stream));
+    EHM_HIP_TRY(x_err, hipStreamSynchronize(E->stream));
     ev.seconds(kernel_seconds);
     return EHM_OK;
 }
 
 int ehm_explicit_set_costs(ehm_explicit* E, const double* vcost, const uint8_t* flags) {
-    if (!E || !vcost || !flags) return xfail(EHM_E_INVALID, "set_costs: a required array is NULL");
-    Y_TRY(hipSetDevice(E->device));
+    if (!E || !vcost || !flags) return x_err.fail(EHM_E_INVALID, "set_costs: a required array is "
+                                                  "NULL");
+    EHM_HIP_TRY(x_err, hipSetDevice(E->device));
     const size_t n = (size_t)E->d.n_nodes;
     DevBuf c, f;        // the handle keeps its earlier pair if an upload fails
-    Y_TRY(c.upload(vcost, n * (size_t)(E->d.p + 1) * sizeof(double)));
-    Y_TRY(f.upload(flags, n * sizeof(uint8_t)));
+    EHM_HIP_TRY(x_err, c.upload(vcost, n * (size_t)(E->d.p + 1) * sizeof(double)));
+    EHM_HIP_TRY(x_err, f.upload(flags, n * sizeof(uint8_t)));
     E->vcost = std::move(c);
     E->nflags = std::move(f);
     return EHM_OK;
 }
 
 int ehm_explicit_records(ehm_explicit* E, double* rec) {
-    if (!E || !rec) return xfail(EHM_E_INVALID, "records: bad argument");
-    Y_TRY(hipSetDevice(E->device));
+    if (!E || !rec) return x_err.fail(EHM_E_INVALID, "records: bad argument");
+    EHM_HIP_TRY(x_err, hipSetDevice(E->device));
     const size_t w = (size_t)(E->d.p + E->d.p * E->d.p) * sizeof(double);
-    Y_TRY(hipMemcpy2D(rec, w, E->rec.ptr, (size_t)E->d.rec_stride * sizeof(double), w,
-                      (size_t)E->d.n_nodes, hipMemcpyDeviceToHost));
+    EHM_HIP_TRY(x_err, hipMemcpy2D(rec, w, E->rec.ptr, (size_t)E->d.rec_stride * sizeof(double), w,
+                                   (size_t)E->d.n_nodes, hipMemcpyDeviceToHost));
     return EHM_OK;
 }
 
@@ -517,11 +505,11 @@ int ehm_explicit_set_plant(ehm_explicit* E, int32_t n_modes, const double* A, co
                            int32_t n_g, const double* Gx, const double* gx,
                            const int32_t* node_mode, int32_t cost_kind, const double* Q,
                            const double* R) {
-    if (!E) return xfail(EHM_E_INVALID, "set_plant: a required array is NULL");
-    return install_plant(E->ro, xfail, E->device, E->d.p, E->d.n_u, E->d.n_nodes, "node",
+    if (!E) return x_err.fail(EHM_E_INVALID, "set_plant: a required array is NULL");
+    return install_plant(E->ro, x_err, E->device, E->d.p, E->d.n_u, E->d.n_nodes, "node",
                          "set_plant", n_modes, EHM_R_MAX_MODES, A, B, w, n_g, Gx, gx, node_mode,
                          cost_kind, Q, R, nullptr, [&](Pack& pk, DevPlant& pl, int p, int) {
-                             return pack_nominal(xfail, pk, pl, p, n_modes, n_d, Emat, region_rows,
+                             return pack_nominal(x_err, pk, pl, p, n_modes, n_d, Emat, region_rows,
                                                  H, h);
                          });
 }
@@ -534,12 +522,12 @@ int ehm_explicit_set_plant_guarded(ehm_explicit* E, int32_t n_modes, const doubl
                                    int32_t default_mode, int32_t n_g, const double* Gx,
                                    const double* gx, const int32_t* node_mode, int32_t cost_kind,
                                    const double* Q, const double* R) {
-    if (!E) return xfail(EHM_E_INVALID, "set_plant_guarded: a required array is NULL");
+    if (!E) return x_err.fail(EHM_E_INVALID, "set_plant_guarded: a required array is NULL");
     DevGuard gd{};
-    return install_plant(E->ro, xfail, E->device, E->d.p, E->d.n_u, E->d.n_nodes, "node",
+    return install_plant(E->ro, x_err, E->device, E->d.p, E->d.n_u, E->d.n_nodes, "node",
                          "set_plant_guarded", n_modes, EHM_G_MAX_MODES, A, B, w, n_g, Gx, gx,
                          node_mode, cost_kind, Q, R, &gd, [&](Pack& pk, DevPlant&, int p, int n_u) {
-                             return pack_guarded(xfail, pk, gd, p, n_u, n_modes, substeps, n_guards,
+                             return pack_guarded(x_err, pk, gd, p, n_u, n_modes, substeps, n_guards,
                                                  guard_mode, guard_row0, ga, gb, gc, gt, strict,
                                                  default_mode);
                          });
@@ -550,8 +538,8 @@ int ehm_explicit_rollout(ehm_explicit* E, int64_t n, int32_t T, const double* x0
                          double* u_traj, int32_t* leaf_traj, double* x_final, int32_t* steps,
                          int32_t* status, double* cost, double* u_norm_sum,
                          double* max_violation, double* kernel_seconds) {
-    if (!E) return xfail(EHM_E_INVALID, "rollout: bad argument");
-    return rollout_run(E->ro, xfail, E->device, E->stream, E->d, E->d.p, E->d.n_u,
+    if (!E) return x_err.fail(EHM_E_INVALID, "rollout: bad argument");
+    return rollout_run(E->ro, x_err, E->device, E->stream, E->d, E->d.p, E->d.n_u,
                        (E->nbr && !locate_off()) ? E->nbr.as<const int32_t>() : nullptr,
                        k_rollout_table, n, T, x0, d, v, tol_exit, x_traj, u_traj, leaf_traj,
                        x_final, steps, status, cost, u_norm_sum, max_violation, kernel_seconds,
@@ -560,8 +548,8 @@ int ehm_explicit_rollout(ehm_explicit* E, int64_t n, int32_t T, const double* x0
 
 int ehm_explicit_set_noise(ehm_explicit* E, int32_t n_terms, const int32_t* desc,
                            const double* data, int32_t n_data, int32_t n_d) {
-    if (!E) return xfail(EHM_E_INVALID, "set_noise: no handle");
-    return install_noise(E->ro, xfail, E->device, E->d.p, E->d.n_u, n_terms, desc, data, n_data,
+    if (!E) return x_err.fail(EHM_E_INVALID, "set_noise: no handle");
+    return install_noise(E->ro, x_err, E->device, E->d.p, E->d.n_u, n_terms, desc, data, n_data,
                          n_d);
 }
 
@@ -571,11 +559,11 @@ int ehm_explicit_rollout_noisy(ehm_explicit* E, int64_t n, int32_t T, const doub
                                double* e_traj, double* w_traj, double* x_final, int32_t* steps,
                                int32_t* status, double* cost, double* u_norm_sum,
                                double* max_violation, double* kernel_seconds) {
-    if (!E) return xfail(EHM_E_INVALID, "rollout_noisy: no handle");
-    const int rc = noisy_ready(E->ro, xfail);
+    if (!E) return x_err.fail(EHM_E_INVALID, "rollout_noisy: no handle");
+    const int rc = noisy_ready(E->ro, x_err);
     if (rc != EHM_OK) return rc;
     const NoisyCall nz{seed, traj0, v_traj, e_traj, w_traj};
-    return rollout_run(E->ro, xfail, E->device, E->stream, E->d, E->d.p, E->d.n_u,
+    return rollout_run(E->ro, x_err, E->device, E->stream, E->d, E->d.p, E->d.n_u,
                        (E->nbr && !locate_off()) ? E->nbr.as<const int32_t>() : nullptr,
                        k_rollout_table, n, T, x0, nullptr, nullptr, tol_exit, x_traj, u_traj,
                        leaf_traj, x_final, steps, status, cost, u_norm_sum, max_violation,
@@ -584,20 +572,21 @@ int ehm_explicit_rollout_noisy(ehm_explicit* E, int64_t n, int32_t T, const doub
 
 int ehm_philox_batch(int64_t n, const uint64_t* counters, const uint64_t* key, uint64_t* out) {
     if (n < 0 || (n > 0 && (!counters || !key || !out)))
-        return xfail(EHM_E_INVALID, "philox_batch: bad argument");
+        return x_err.fail(EHM_E_INVALID, "philox_batch: bad argument");
     if (n == 0) return EHM_OK;
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return xfail(EHM_E_NO_DEVICE, "philox_batch: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return x_err.fail(EHM_E_NO_DEVICE, "philox_batch: %s",
+                                           hipGetErrorString(e));
     const size_t bytes = (size_t)n * 4 * sizeof(uint64_t);
     DevBuf dc, dout;
-    Y_TRY(dc.upload(counters, bytes));
-    Y_TRY(dout.alloc(bytes));
+    EHM_HIP_TRY(x_err, dc.upload(counters, bytes));
+    EHM_HIP_TRY(x_err, dout.alloc(bytes));
     hipLaunchKernelGGL(k_philox_batch, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0,
                        (long long)n, dc.as<const uint64_t>(), key[0], key[1],
                        dout.as<uint64_t>());
-    Y_TRY(hipGetLastError());
-    Y_TRY(hipMemcpy(out, dout.ptr, bytes, hipMemcpyDeviceToHost));
+    EHM_HIP_TRY(x_err, hipGetLastError());
+    EHM_HIP_TRY(x_err, hipMemcpy(out, dout.ptr, bytes, hipMemcpyDeviceToHost));
     return EHM_OK;
 }
 

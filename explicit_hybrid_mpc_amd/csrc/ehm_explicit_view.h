@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/ehmpc.h"
+#include "ehm_err.h"
 
 struct ehm_explicit_view {
     int device;
@@ -28,7 +29,9 @@ struct ehm_explicit_view {
 void ehm_explicit_get_view(const ehm_explicit* E, ehm_explicit_view* out);
 // sets the message of ehm_explicit_last_error and returns `code` (the error channel of every entry
 // point that takes an ehm_explicit handle)
-int ehm_explicit_fail(int code, const char* fmt, ...);
+int ehm_explicit_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+// the channel itself, for EHM_HIP_TRY
+ehm_err_channel& ehm_explicit_channel();
 
 // Face adjacency of n_roots simplices (host): nbr [n_roots][p+1], the root across the face opposite
 // vertex i, -1 on the hull.  Root r has the vertices [p+1][p] of node ids[r] (ids nullptr: node r).

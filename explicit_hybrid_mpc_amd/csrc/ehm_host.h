@@ -1,14 +1,42 @@
 // Owners of the library's HIP resources on the host side: device buffers, events and streams.
 // Each frees what it holds when its owner goes; they are moved, never copied.  Their methods
 // return hipError_t, so every translation unit reports a failure through its own error channel
-// (ehm_last_error, ehm_explicit_last_error).
+// (ehm_err.h) with EHM_HIP_TRY.  After them the small helpers every host path repeats: the grid of
+// a launch, a wall clock and the sizes behind the ehm_*_abi_sizes getters.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cstddef>
+#include <cstdint>
 #include <utility>
+
+#include "ehm_err.h"
+
+// `expr` (a hipError_t) or return EHM_E_HIP with its text in `channel` (an ehm_err_channel)
+#define EHM_HIP_TRY(channel, expr)                                                         \
+    do {                                                                                   \
+        const hipError_t e_ = (expr);                                                      \
+        if (e_ != hipSuccess)                                                              \
+            return (channel).fail(EHM_E_HIP, "%s failed: %s", #expr,                       \
+                                  hipGetErrorString(e_));                                  \
+    } while (0)
+
+// workgroups of `block` threads that cover n items
+inline unsigned blocks_of(long long n, int block) { return (unsigned)((n + block - 1) / block); }
+
+inline double wall_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// what every ehm_*_abi_sizes returns: the first min(n, known) of `all` into `sizes` (nullptr:
+// none), and `known`
+inline int ehm_copy_abi_sizes(const int64_t* all, int32_t known, int64_t* sizes, int32_t n) {
+    for (int32_t k = 0; sizes && k < n && k < known; ++k) sizes[k] = all[k];
+    return known;
+}
 
 // One device allocation of `cap` bytes (nullptr / 0: none).
 struct DevBuf {

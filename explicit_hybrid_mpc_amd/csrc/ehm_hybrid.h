@@ -805,7 +805,7 @@ static int hy_alloc(ehm_tree* T) {
     const int nd = P->dp.n_delta, p = P->dp.p, nv = p + 1, n_u = P->dp.n_u;
     H.nw = (nd + 63) / 64;
     if (H.nw > 4)
-        return fail(EHM_E_INVALID, "hybrid engine: at most 256 commutations (got %d)", nd);
+        return g_err.fail(EHM_E_INVALID, "hybrid engine: at most 256 commutations (got %d)", nd);
     const int nw = H.nw;
     H.ch = std::max<long long>(1024, std::min<long long>(1LL << 17, (1LL << 22) / nd));
     if (const char* e = getenv("EHM_HY_CHUNK")) H.ch = std::max(64, atoi(e));
@@ -1170,11 +1170,11 @@ static int hy_read_ctr(ehm_tree* T) {
             EHM_E_HIP);
     HIP_TRY(hipStreamSynchronize(P->stream), EHM_E_HIP);
     if (H.h.error == 1)
-        return fail(EHM_E_CAPACITY, "node pool exhausted at %d nodes (max_nodes=%lld)",
-                    H.h.n_nodes, T->limit);
+        return g_err.fail(EHM_E_CAPACITY, "node pool exhausted at %d nodes (max_nodes=%lld)",
+                          H.h.n_nodes, T->limit);
     if (H.h.error == 3)
-        return fail(EHM_E_INFEASIBLE, "STOP, Theta contains infeasible regions (node %d)",
-                    H.h.err_node);
+        return g_err.fail(EHM_E_INFEASIBLE, "STOP, Theta contains infeasible regions (node %d)",
+                          H.h.err_node);
     if (H.h.error != 0) {
         static const char* what[] = {"?", "suboptimality-test problem", "min over the simplex",
                                      "midpoint solve"};
@@ -1192,8 +1192,8 @@ static int hy_read_ctr(ehm_tree* T) {
                 fclose(fp);
             }
         }
-        return fail(EHM_E_NUMERIC, "node %d: %s with commutation %d did not converge",
-                    H.h.err_node, what[H.h.err_kind & 3], H.h.err_kind >> 4);
+        return g_err.fail(EHM_E_NUMERIC, "node %d: %s with commutation %d did not converge",
+                          H.h.err_node, what[H.h.err_kind & 3], H.h.err_kind >> 4);
     }
     return EHM_OK;
 }
@@ -1251,7 +1251,7 @@ static int hy_begin(ehm_tree* T, int64_t n_roots, const ehm_node_init* init) {
     ehm_problem* P = T->prob;
     auto& R = T->run;
     if (P->solver_gen != 2 && !P->v1_ok)
-        return fail(EHM_E_INVALID, "this problem does not fit the generation-1 kernels");
+        return g_err.fail(EHM_E_INVALID, "this problem does not fit the generation-1 kernels");
     T->hy = std::make_unique<HyState>();
     HyState& H = *T->hy;
     H.on = true;
@@ -1264,7 +1264,8 @@ static int hy_begin(ehm_tree* T, int64_t n_roots, const ehm_node_init* init) {
     std::vector<uint8_t> flags((size_t)n_roots, 0);
     if (R.action == 1) {
         if (!init || !init->delta || !init->vcost || !init->vinput)
-            return fail(EHM_E_INVALID, "action 'lcss' needs delta / vertex costs / vertex inputs");
+            return g_err.fail(EHM_E_INVALID,
+                              "action 'lcss' needs delta / vertex costs / vertex inputs");
         if ((rc = map_deltas(P, n_roots, init->delta, didx))) return rc;
         std::fill(flags.begin(), flags.end(), (uint8_t)2);
     }
@@ -1282,7 +1283,8 @@ static int hy_begin(ehm_tree* T, int64_t n_roots, const ehm_node_init* init) {
     if (sharded || P->any_admissible) {
         // path codes: the deal of a sharded run and the draws of option any_admissible hash them
         if (sharded && R.deal_depth <= 0)
-            return fail(EHM_E_INVALID, "sharded multi-commutation runs need ehm_run_opts.deal_depth");
+            return g_err.fail(EHM_E_INVALID,
+                              "sharded multi-commutation runs need ehm_run_opts.deal_depth");
         if (sharded) H.deal = PersistDeal{0, R.deal_depth, R.shard_rank, R.shard_world, 1};
         HIP_TRY(T->code.ensure((size_t)T->pool.cap * 4), EHM_E_HIP);
         T->dt.code = T->code.as<uint32_t>();
@@ -1431,8 +1433,8 @@ static int hy_take(ehm_tree* T, int64_t count, int32_t* node_ids, double* record
     HyState& H = *T->hy;
     auto& R = T->run;
     if (count > H.n_lcss)
-        return fail(EHM_E_INVALID, "cannot take %lld of %lld movable frontier nodes",
-                    (long long)count, H.n_lcss);
+        return g_err.fail(EHM_E_INVALID, "cannot take %lld of %lld movable frontier nodes",
+                          (long long)count, H.n_lcss);
     if (count == 0) return EHM_OK;
     const int W = hy_record_doubles(P->dp.p, P->dp.n_u, H.nw);
     HIP_TRY(P->out0.ensure((size_t)count * W * sizeof(double)), EHM_E_HIP);
@@ -1464,8 +1466,8 @@ static int hy_give(ehm_tree* T, int64_t count, const double* records, const int3
     if (first_id) *first_id = (int32_t)R.n_nodes;
     if (count == 0) return EHM_OK;
     if (R.n_nodes + count > T->limit)
-        return fail(EHM_E_CAPACITY, "node pool exhausted at %lld nodes (max_nodes=%lld)",
-                    R.n_nodes, T->limit);
+        return g_err.fail(EHM_E_CAPACITY, "node pool exhausted at %lld nodes (max_nodes=%lld)",
+                          R.n_nodes, T->limit);
     const int W = hy_record_doubles(P->dp.p, P->dp.n_u, H.nw);
     HIP_TRY(P->in0.ensure((size_t)count * W * sizeof(double)), EHM_E_HIP);
     HIP_TRY(P->in1.ensure((size_t)count * 2 * sizeof(int32_t)), EHM_E_HIP);

@@ -447,28 +447,12 @@ const step_fn k_step_table[IK_KINDS][EHM_I_MAX_P][EHM_R_MAX_NU] = {
 #undef EHM_I_S_NU
 #undef EHM_I_M_NU
 
-thread_local std::string i_err;
-int ifail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    i_err = buf;
-    return code;
-}
-
-#define I_TRY(expr)                                                                        \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return ifail(EHM_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
-    } while (0)
+thread_local ehm_err_channel i_err;
 // a call into the solver handle: its message travels with the code
 #define I_SOLVER(expr)                                                                     \
     do {                                                                                   \
         const int rc_ = (expr);                                                            \
-        if (rc_ != EHM_OK) return ifail(rc_, "%s", ehm_last_error());                      \
+        if (rc_ != EHM_OK) return i_err.fail(rc_, "%s", ehm_last_error());                      \
     } while (0)
 
 }  // namespace
@@ -495,14 +479,14 @@ int imp_install_plant(ehm_implicit* I, const char* who, int32_t n_modes, int max
                       int32_t cost_kind, const double* Q, const double* R, const DevGuard* gd,
                       Own own) {
     if (!I || !A || !B || !w || !mode_of || !Q || !R)
-        return ifail(EHM_E_INVALID, "%s: a required array is NULL", who);
+        return i_err.fail(EHM_E_INVALID, "%s: a required array is NULL", who);
     if (n_modes < 1 || n_modes > max_modes)
-        return ifail(EHM_E_INVALID, "%s: %d modes (1..%d)", who, (int)n_modes, max_modes);
+        return i_err.fail(EHM_E_INVALID, "%s: %d modes (1..%d)", who, (int)n_modes, max_modes);
     if (n_g < 0 || n_g > EHM_R_MAX_ROWS || (n_g > 0 && (!Gx || !gx)))
-        return ifail(EHM_E_INVALID, "%s: n_g = %d (0..%d)", who, (int)n_g, EHM_R_MAX_ROWS);
+        return i_err.fail(EHM_E_INVALID, "%s: n_g = %d (0..%d)", who, (int)n_g, EHM_R_MAX_ROWS);
     if (cost_kind != 0 && cost_kind != 1)
-        return ifail(EHM_E_INVALID, "%s: cost_kind %d (0 inf-norm, 1 quadratic)", who,
-                     (int)cost_kind);
+        return i_err.fail(EHM_E_INVALID, "%s: cost_kind %d (0 inf-norm, 1 quadratic)", who,
+                          (int)cost_kind);
     const int p = I->ip.p, n_u = I->ip.n_u, nd = I->ip.n_delta;
     DevPlant pl{};
     pl.n_modes = n_modes;
@@ -520,17 +504,17 @@ int imp_install_plant(ehm_implicit* I, const char* who, int32_t n_modes, int max
     if (rc != EHM_OK) return rc;
     pl.total = (int)pk.buf.size();
     if (pl.total > EHM_N_MAX_LDS)
-        return ifail(EHM_E_INVALID, "%s: the plant takes %d doubles of LDS (%d)", who, pl.total,
-                     EHM_N_MAX_LDS);
+        return i_err.fail(EHM_E_INVALID, "%s: the plant takes %d doubles of LDS (%d)", who,
+                          pl.total, EHM_N_MAX_LDS);
     for (int d = 0; d < nd; ++d)
         if (mode_of[d] < 0 || (!gd && mode_of[d] >= n_modes))
-            return ifail(EHM_E_INVALID, "%s: commutation %d has mode %d of %d", who, d,
-                         (int)mode_of[d], (int)n_modes);
-    I_TRY(hipSetDevice(I->ip.device));
+            return i_err.fail(EHM_E_INVALID, "%s: commutation %d has mode %d of %d", who, d,
+                              (int)mode_of[d], (int)n_modes);
+    EHM_HIP_TRY(i_err, hipSetDevice(I->ip.device));
     DevBuf d_plant, d_mode;
     if (d_plant.upload(pk.buf.data(), pk.buf.size() * sizeof(double)) != hipSuccess ||
         d_mode.upload(mode_of, (size_t)nd * sizeof(int32_t)) != hipSuccess)
-        return ifail(EHM_E_HIP, "%s: device allocation / copy failed", who);
+        return i_err.fail(EHM_E_HIP, "%s: device allocation / copy failed", who);
     I->plant = std::move(d_plant);
     I->mode_of = std::move(d_mode);
     pl.data = I->plant.as<const double>();
@@ -554,13 +538,13 @@ int ehm_implicit_destroy(ehm_implicit* I) {
 }
 
 int ehm_implicit_create(ehm_problem* prob, ehm_implicit** out) {
-    if (!prob || !out) return ifail(EHM_E_INVALID, "bad argument");
+    if (!prob || !out) return i_err.fail(EHM_E_INVALID, "bad argument");
     *out = nullptr;
     ImpProblem ip{};
     I_SOLVER(ehm_imp_describe(prob, &ip));
     if (ip.p < 1 || ip.p > EHM_I_MAX_P || ip.n_u < 1 || ip.n_u > EHM_R_MAX_NU)
-        return ifail(EHM_E_INVALID, "the device loop takes p <= %d and n_u <= %d (p %d, n_u %d)",
-                     EHM_I_MAX_P, EHM_R_MAX_NU, ip.p, ip.n_u);
+        return i_err.fail(EHM_E_INVALID, "the device loop takes p <= %d and n_u <= %d (p %d, n_u "
+                          "%d)", EHM_I_MAX_P, EHM_R_MAX_NU, ip.p, ip.n_u);
     ehm_implicit* I = new ehm_implicit();
     I->prob = prob;
     I->ip = ip;
@@ -578,20 +562,20 @@ int ehm_implicit_set_plant(ehm_implicit* I, int32_t n_modes, const double* A, co
         I, "implicit_set_plant", n_modes, EHM_R_MAX_MODES, A, B, w, n_g, Gx, gx, mode_of,
         cost_kind, Q, R, nullptr, [&](Pack& pk, DevPlant& pl, int p, int) {
             if (n_d < 0 || n_d > EHM_R_MAX_D || (n_d > 0 && !Emat))
-                return ifail(EHM_E_INVALID, "implicit_set_plant: n_d = %d (0..%d, E needed if > 0)",
-                             (int)n_d, EHM_R_MAX_D);
+                return i_err.fail(EHM_E_INVALID, "implicit_set_plant: n_d = %d (0..%d, E needed if "
+                                  "> 0)", (int)n_d, EHM_R_MAX_D);
             int rows = 0;
             for (int m = 0; m < n_modes; ++m) {
                 const int r = region_rows ? region_rows[m] : 0;
                 if (r < 0)
-                    return ifail(EHM_E_INVALID, "implicit_set_plant: mode %d has %d region rows", m,
-                                 r);
+                    return i_err.fail(EHM_E_INVALID, "implicit_set_plant: mode %d has %d region "
+                                      "rows", m, r);
                 pl.row0[m] = rows;
                 rows += r;
             }
             if (rows > EHM_R_MAX_ROWS || (rows > 0 && (!H || !h)))
-                return ifail(EHM_E_INVALID, "implicit_set_plant: %d mode-region rows (0..%d)", rows,
-                             EHM_R_MAX_ROWS);
+                return i_err.fail(EHM_E_INVALID, "implicit_set_plant: %d mode-region rows (0..%d)",
+                                  rows, EHM_R_MAX_ROWS);
             for (int m = n_modes; m <= EHM_R_MAX_MODES; ++m) pl.row0[m] = rows;
             pl.n_d = n_d;
             pl.oE = pk.put(Emat, (size_t)p * n_d);
@@ -615,37 +599,37 @@ int ehm_implicit_set_plant_guarded(ehm_implicit* I, int32_t n_modes, const doubl
         cost_kind, Q, R, &gd, [&](Pack& pk, DevPlant&, int p, int n_u) {
             const char* who = "implicit_set_plant_guarded";
             if ((n_guards > 0 && !guard_mode) || !guard_row0)
-                return ifail(EHM_E_INVALID, "%s: a required array is NULL", who);
+                return i_err.fail(EHM_E_INVALID, "%s: a required array is NULL", who);
             if (substeps < 1 || substeps > EHM_G_MAX_SUB)
-                return ifail(EHM_E_INVALID, "%s: %d substeps (1..%d)", who, (int)substeps,
-                             EHM_G_MAX_SUB);
+                return i_err.fail(EHM_E_INVALID, "%s: %d substeps (1..%d)", who, (int)substeps,
+                                  EHM_G_MAX_SUB);
             if (n_guards < 0 || n_guards > EHM_G_MAX_ROWS)
-                return ifail(EHM_E_INVALID, "%s: %d guards (0..%d)", who, (int)n_guards,
-                             EHM_G_MAX_ROWS);
+                return i_err.fail(EHM_E_INVALID, "%s: %d guards (0..%d)", who, (int)n_guards,
+                                  EHM_G_MAX_ROWS);
             if (default_mode < 0 || default_mode >= n_modes)
-                return ifail(EHM_E_INVALID, "%s: default mode %d of %d", who, (int)default_mode,
-                             (int)n_modes);
+                return i_err.fail(EHM_E_INVALID, "%s: default mode %d of %d", who,
+                                  (int)default_mode, (int)n_modes);
             if (guard_row0[0] != 0)
-                return ifail(EHM_E_INVALID, "%s: the rows of guard 0 start at %d", who,
-                             (int)guard_row0[0]);
+                return i_err.fail(EHM_E_INVALID, "%s: the rows of guard 0 start at %d", who,
+                                  (int)guard_row0[0]);
             gd.substeps = substeps;
             gd.n_guards = n_guards;
             gd.default_mode = default_mode;
             for (int g = 0; g <= n_guards; ++g) {
                 if (g < n_guards) {
                     if (guard_mode[g] < 0 || guard_mode[g] >= n_modes)
-                        return ifail(EHM_E_INVALID, "%s: guard %d selects mode %d of %d", who, g,
-                                     (int)guard_mode[g], (int)n_modes);
+                        return i_err.fail(EHM_E_INVALID, "%s: guard %d selects mode %d of %d", who,
+                                          g, (int)guard_mode[g], (int)n_modes);
                     if (guard_row0[g + 1] <= guard_row0[g])
-                        return ifail(EHM_E_INVALID, "%s: guard %d has no rows", who, g);
+                        return i_err.fail(EHM_E_INVALID, "%s: guard %d has no rows", who, g);
                     gd.mode[g] = guard_mode[g];
                 }
                 gd.row0[g] = guard_row0[g];
             }
             const int rows = guard_row0[n_guards];
             if (rows > EHM_G_MAX_ROWS || (rows > 0 && (!ga || !gb || !gc || !gt || !strict)))
-                return ifail(EHM_E_INVALID, "%s: %d guard rows (0..%d)", who, rows,
-                             EHM_G_MAX_ROWS);
+                return i_err.fail(EHM_E_INVALID, "%s: %d guard rows (0..%d)", who, rows,
+                                  EHM_G_MAX_ROWS);
             for (int r = 0; r < rows; ++r) gd.strict[r] = strict[r] != 0;
             gd.oGa = pk.put(ga, (size_t)rows * p);
             gd.oGb = pk.put(gb, (size_t)rows * n_u);
@@ -659,19 +643,19 @@ int ehm_implicit_set_noise(ehm_implicit* I, int32_t n_terms, const int32_t* desc
                            const double* data, int32_t n_data, int32_t n_d) {
     if (!I || n_terms < 0 || n_terms > EHM_N_MAX_TERMS || (n_terms > 0 && !desc) || n_data < 0 ||
         (n_data > 0 && !data) || n_d < 0 || n_d > EHM_R_MAX_D)
-        return ifail(EHM_E_INVALID, "implicit_set_noise: bad argument (at most %d terms, n_d <= %d)",
-                     EHM_N_MAX_TERMS, EHM_R_MAX_D);
+        return i_err.fail(EHM_E_INVALID, "implicit_set_noise: bad argument (at most %d terms, n_d "
+                          "<= %d)", EHM_N_MAX_TERMS, EHM_R_MAX_D);
     DevNoise nz{};
     const int bad = noise_fill(nz, n_terms, desc, n_data, I->ip.p, I->ip.n_u, n_d);
     if (bad >= 0)
-        return ifail(EHM_E_INVALID, "implicit_set_noise: term %d has a bad descriptor", bad);
+        return i_err.fail(EHM_E_INVALID, "implicit_set_noise: term %d has a bad descriptor", bad);
     if (I->pl.total + n_data > EHM_N_MAX_LDS)
-        return ifail(EHM_E_INVALID, "implicit_set_noise: plant and model take %d doubles of LDS "
-                                    "(%d)", I->pl.total + n_data, EHM_N_MAX_LDS);
-    I_TRY(hipSetDevice(I->ip.device));
+        return i_err.fail(EHM_E_INVALID, "implicit_set_noise: plant and model take %d doubles of "
+                          "LDS (%d)", I->pl.total + n_data, EHM_N_MAX_LDS);
+    EHM_HIP_TRY(i_err, hipSetDevice(I->ip.device));
     DevBuf d_noise;
     if (d_noise.upload(data, (size_t)n_data * sizeof(double)) != hipSuccess)
-        return ifail(EHM_E_HIP, "implicit_set_noise: device allocation / copy failed");
+        return i_err.fail(EHM_E_HIP, "implicit_set_noise: device allocation / copy failed");
     I->noise = std::move(d_noise);
     nz.data = I->noise.as<const double>();
     I->nz = nz;
@@ -689,36 +673,37 @@ int ehm_implicit_rollout(ehm_implicit* I, int64_t n, int32_t T, const double* x0
                          double* device_seconds) {
     if (!I || !x0 || !x_final || !steps || !status || !cost || !u_norm_sum || !max_violation ||
         !stalled || !counts || n < 0 || T < 0 || !(tol_exit >= 0.0))
-        return ifail(EHM_E_INVALID, "implicit_rollout: bad argument");
-    if (!I->plant) return ifail(EHM_E_INVALID, "implicit_rollout: no plant (ehm_implicit_set_plant)");
+        return i_err.fail(EHM_E_INVALID, "implicit_rollout: bad argument");
+    if (!I->plant) return i_err.fail(EHM_E_INVALID, "implicit_rollout: no plant "
+                                     "(ehm_implicit_set_plant)");
     const int p = I->ip.p, n_u = I->ip.n_u, nd = I->ip.n_delta, n_d = I->pl.n_d;
     if (noisy) {
         if (d || v)
-            return ifail(EHM_E_INVALID, "implicit_rollout: the model draws d and v itself");
+            return i_err.fail(EHM_E_INVALID, "implicit_rollout: the model draws d and v itself");
         if (!I->noise)
-            return ifail(EHM_E_INVALID, "implicit_rollout: no model (ehm_implicit_set_noise)");
+            return i_err.fail(EHM_E_INVALID, "implicit_rollout: no model (ehm_implicit_set_noise)");
         if (I->guarded)
-            return ifail(EHM_E_INVALID, "implicit_rollout: the plant is guarded (noisy guarded "
-                                        "plants are not supported)");
+            return i_err.fail(EHM_E_INVALID, "implicit_rollout: the plant is guarded (noisy "
+                              "guarded plants are not supported)");
         if (I->noise_n_d != n_d)
-            return ifail(EHM_E_INVALID, "implicit_rollout: the model has n_d = %d, the plant %d",
-                         I->noise_n_d, n_d);
+            return i_err.fail(EHM_E_INVALID, "implicit_rollout: the model has n_d = %d, the plant "
+                              "%d", I->noise_n_d, n_d);
         if (I->pl.total + I->nz.total > EHM_N_MAX_LDS)
-            return ifail(EHM_E_INVALID, "implicit_rollout: plant and model take %d doubles of LDS "
-                                        "(%d)", I->pl.total + I->nz.total, EHM_N_MAX_LDS);
+            return i_err.fail(EHM_E_INVALID, "implicit_rollout: plant and model take %d doubles of "
+                              "LDS (%d)", I->pl.total + I->nz.total, EHM_N_MAX_LDS);
     }
     if (d && (n_d == 0 || I->guarded))
-        return ifail(EHM_E_INVALID, "implicit_rollout: a disturbance was given but the plant "
-                                    "takes none");
+        return i_err.fail(EHM_E_INVALID, "implicit_rollout: a disturbance was given but the plant "
+                                         "takes none");
     for (int k = 0; k < 5; ++k) counts[k] = 0;
     if (n == 0) return EHM_OK;
     if (nd > 65535)
-        return ifail(EHM_E_INVALID, "implicit_rollout: %d commutations (the compaction grid takes "
-                                    "65535)", nd);
+        return i_err.fail(EHM_E_INVALID, "implicit_rollout: %d commutations (the compaction grid "
+                          "takes 65535)", nd);
     if (n * nd >= (int64_t)1 << 31)
-        return ifail(EHM_E_INVALID, "implicit_rollout: %lld trajectories x %d commutations (split "
-                                    "the batch)", (long long)n, nd);
-    I_TRY(hipSetDevice(I->ip.device));
+        return i_err.fail(EHM_E_INVALID, "implicit_rollout: %lld trajectories x %d commutations "
+                          "(split the batch)", (long long)n, nd);
+    EHM_HIP_TRY(i_err, hipSetDevice(I->ip.device));
     hipStream_t st = I->ip.stream;
     const size_t N = (size_t)n, nT = (size_t)T, K = N * nd, D = sizeof(double),
                  I4 = sizeof(int32_t);
@@ -778,18 +763,19 @@ int ehm_implicit_rollout(ehm_implicit* I, int64_t n, int32_t T, const double* x0
             std::memcpy(b.field, &b.buf.ptr, sizeof b.buf.ptr);
         }
     if (!ok)
-        return ifail(EHM_E_HIP, "implicit_rollout: out of device memory for %lld x %d steps x %d "
-                                "commutations", (long long)n, (int)T, nd);
+        return i_err.fail(EHM_E_HIP, "implicit_rollout: out of device memory for %lld x %d steps x "
+                          "%d commutations", (long long)n, (int)T, nd);
     A.d = dd.as<const double>();
     A.v = dv.as<const double>();
     A.counts = dcounts.as<unsigned long long>();
-    I_TRY(hipMemcpyAsync(dx0.ptr, x0, N * p * D, hipMemcpyHostToDevice, st));
-    if (d) I_TRY(hipMemcpyAsync(dd.ptr, d, nT * N * n_d * D, hipMemcpyHostToDevice, st));
-    if (v) I_TRY(hipMemcpyAsync(dv.ptr, v, nT * N * p * D, hipMemcpyHostToDevice, st));
-    I_TRY(hipMemsetAsync(dcounts.ptr, 0, 3 * sizeof(unsigned long long), st));
+    EHM_HIP_TRY(i_err, hipMemcpyAsync(dx0.ptr, x0, N * p * D, hipMemcpyHostToDevice, st));
+    if (d) EHM_HIP_TRY(i_err, hipMemcpyAsync(dd.ptr, d, nT * N * n_d * D, hipMemcpyHostToDevice,
+                                             st));
+    if (v) EHM_HIP_TRY(i_err, hipMemcpyAsync(dv.ptr, v, nT * N * p * D, hipMemcpyHostToDevice, st));
+    EHM_HIP_TRY(i_err, hipMemsetAsync(dcounts.ptr, 0, 3 * sizeof(unsigned long long), st));
     // records of steps a trajectory does not reach: all-ones bytes, i.e. NaN and -1
     for (Buf& b : bufs)
-        if (b.record && b.buf) I_TRY(hipMemsetAsync(b.buf.ptr, 0xff, b.bytes, st));
+        if (b.record && b.buf) EHM_HIP_TRY(i_err, hipMemsetAsync(b.buf.ptr, 0xff, b.bytes, st));
     DevNoise NZ{};
     size_t lds_step = (size_t)I->pl.total * D, lds_meas = 0;
     if (noisy) {
@@ -825,12 +811,13 @@ int ehm_implicit_rollout(ehm_implicit* I, int64_t n, int32_t T, const double* x0
         hipLaunchKernelGGL(f_step, g_traj, dim3(256), lds_step, st, A, I->pl, NZ, I->gd);
     }
     (void)hipEventRecord(ev.e1, st);
-    I_TRY(hipGetLastError());
+    EHM_HIP_TRY(i_err, hipGetLastError());
     for (const Buf& b : bufs)
-        if (b.host) I_TRY(hipMemcpyAsync(b.host, b.buf.ptr, b.bytes, hipMemcpyDeviceToHost, st));
+        if (b.host) EHM_HIP_TRY(i_err, hipMemcpyAsync(b.host, b.buf.ptr, b.bytes,
+                                                      hipMemcpyDeviceToHost, st));
     unsigned long long c2[3] = {0, 0, 0};
-    I_TRY(hipMemcpyAsync(c2, dcounts.ptr, sizeof c2, hipMemcpyDeviceToHost, st));
-    I_TRY(hipStreamSynchronize(st));
+    EHM_HIP_TRY(i_err, hipMemcpyAsync(c2, dcounts.ptr, sizeof c2, hipMemcpyDeviceToHost, st));
+    EHM_HIP_TRY(i_err, hipStreamSynchronize(st));
     ev.seconds(device_seconds);
     counts[0] = (int64_t)c2[0];              // stalled pairs, both solves
     counts[1] = (int64_t)K * T;              // phase-one LPs

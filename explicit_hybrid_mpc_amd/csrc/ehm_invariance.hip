@@ -281,23 +281,26 @@ const succ64_fn k_succ64[EHM_CP] = EHM_INV_ALL(double);
 const succ32_fn k_succ32[EHM_CP] = EHM_INV_ALL(float);
 #undef EHM_INV_ALL
 
-thread_local std::string v_err;
-int vfail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    v_err = buf;
-    return code;
+// the device buffers of a run
+struct SuccBufs {
+    DevBuf plant, mode, roots, ids, vert, status, margin, worst, viol, x, sr, sl, cnt;
+};
+
+// the arguments of a pass over leaves off .. off + nc - 1 on the law's scalar T
+template <class T>
+SuccArgs<T> succ_args(const ehm_compiled_view& v, const ehm_invariance_opts* o, const SuccBufs& D,
+                      const ehm_cert::Parents& par, long long nc, long long off, int o_lo,
+                      int o_hi) {
+    return {nc, o->leaf_ids ? D.ids.as<const int32_t>() : nullptr, off,
+            static_cast<const T*>(v.node), static_cast<const T*>(v.leaf_rec), v.root_entry,
+            v.root_rec, v.nbr, D.roots.as<const double>(), par, D.mode.as<const int32_t>(),
+            v.n_u, v.leaf_stride, v.side_stride, (int)v.n_roots, o->n_d, o_lo, o_hi, o->tol_exit,
+            D.vert.as<double>(), D.status.as<int32_t>(), D.margin.as<double>(),
+            D.worst.as<int32_t>(), D.viol.as<double>(), D.x.as<double>(), D.sr.as<int32_t>(),
+            D.sl.as<int32_t>(), D.cnt.as<unsigned long long>()};
 }
 
-#define V_TRY(expr)                                                                        \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return vfail(EHM_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
-    } while (0)
+thread_local ehm_err_channel v_err;
 
 // a smaller margin, the earlier leaf on ties; a NaN never wins
 bool worst_leaf_beats(double ma, long long ia, double mb, long long ib) {
@@ -314,68 +317,58 @@ int ehm_invariance_abi_sizes(int64_t* sizes, int32_t n) {
     const int64_t all[] = {(int64_t)sizeof(ehm_invariance_opts),
                            (int64_t)sizeof(ehm_invariance_result),
                            (int64_t)sizeof(ehm_invariance_leaves)};
-    const int32_t known = (int32_t)(sizeof all / sizeof all[0]);
-    for (int32_t k = 0; sizes && k < n && k < known; ++k) sizes[k] = all[k];
-    return known;
+    return ehm_copy_abi_sizes(all, (int32_t)(sizeof all / sizeof all[0]), sizes, n);
 }
 
 int ehm_compiled_successors(ehm_compiled* law, const ehm_invariance_opts* o,
                             ehm_invariance_result* res, const ehm_invariance_leaves* lv) {
-    if (!law || !o || !res || !lv) return vfail(EHM_E_INVALID, "successors: bad argument");
-    if (o->n < 0 || o->chunk < 0) return vfail(EHM_E_INVALID, "successors: n or chunk < 0");
+    if (!law || !o || !res || !lv) return v_err.fail(EHM_E_INVALID, "successors: bad argument");
+    if (o->n < 0 || o->chunk < 0) return v_err.fail(EHM_E_INVALID, "successors: n or chunk < 0");
     if (!o->root_vertices || !o->A || !o->B || !o->w || !o->leaf_mode)
-        return vfail(EHM_E_INVALID, "successors: a required array is NULL");
+        return v_err.fail(EHM_E_INVALID, "successors: a required array is NULL");
     if (o->n > 0 && (!lv->status || !lv->margin || !lv->worst || !lv->max_violation))
-        return vfail(EHM_E_INVALID, "successors: a required output is NULL");
+        return v_err.fail(EHM_E_INVALID, "successors: a required output is NULL");
     if (!(o->tol_exit >= 0.0))
-        return vfail(EHM_E_INVALID, "successors: tol_exit must be >= 0");
+        return v_err.fail(EHM_E_INVALID, "successors: tol_exit must be >= 0");
     ehm_compiled_view v;
     ehm_compiled_get_view(law, &v);
-    if (v.n_test > 0)
-        return vfail(EHM_E_INVALID, "successors: the law has %lld test nodes (children that are "
-                     "no bisection); its cells do not follow from its planes -- compile it with "
-                     "the spine as its root table", v.n_test);
+    int rc = check_law_shape(v_err, v, "successors");
+    if (rc) return rc;
     const int p = v.p, n_u = v.n_u;
-    if (p < 1 || p > EHM_CP) return vfail(EHM_E_INVALID, "successors: p = %d", p);
-    if (v.n_roots >= 0x7fffffffLL) return vfail(EHM_E_INVALID, "successors: too many roots");
     if (n_u > EHM_R_MAX_NU)
-        return vfail(EHM_E_INVALID, "successors: n_u = %d, at most %d inputs", n_u, EHM_R_MAX_NU);
+        return v_err.fail(EHM_E_INVALID, "successors: n_u = %d, at most %d inputs", n_u,
+                          EHM_R_MAX_NU);
     if (o->n_modes < 1 || o->n_modes > EHM_R_MAX_MODES)
-        return vfail(EHM_E_INVALID, "successors: %d modes (1..%d)", (int)o->n_modes,
-                     EHM_R_MAX_MODES);
+        return v_err.fail(EHM_E_INVALID, "successors: %d modes (1..%d)", (int)o->n_modes,
+                          EHM_R_MAX_MODES);
     if (o->n_d < 0 || o->n_d > EHM_R_MAX_D)
-        return vfail(EHM_E_INVALID, "successors: n_d = %d (0..%d)", (int)o->n_d, EHM_R_MAX_D);
+        return v_err.fail(EHM_E_INVALID, "successors: n_d = %d (0..%d)", (int)o->n_d, EHM_R_MAX_D);
     if (o->n_d > 0 && !o->E)
-        return vfail(EHM_E_INVALID, "successors: a box of %d disturbances but no E", (int)o->n_d);
+        return v_err.fail(EHM_E_INVALID, "successors: a box of %d disturbances but no E",
+                          (int)o->n_d);
     if (o->n_d > 0 && (!o->d_lo || !o->d_hi))
-        return vfail(EHM_E_INVALID, "successors: a required array is NULL");
+        return v_err.fail(EHM_E_INVALID, "successors: a required array is NULL");
     for (int b = 0; b < o->n_d; ++b)
         if (!std::isfinite(o->d_lo[b]) || !std::isfinite(o->d_hi[b]) || o->d_lo[b] > o->d_hi[b])
-            return vfail(EHM_E_INVALID, "successors: the box is [%g, %g] on axis %d", o->d_lo[b],
-                         o->d_hi[b], b);
+            return v_err.fail(EHM_E_INVALID, "successors: the box is [%g, %g] on axis %d",
+                              o->d_lo[b], o->d_hi[b], b);
     if (o->n_g < 0 || o->n_g > EHM_R_MAX_ROWS || (o->n_g > 0 && (!o->Gx || !o->gx)))
-        return vfail(EHM_E_INVALID, "successors: n_g = %d (0..%d)", (int)o->n_g, EHM_R_MAX_ROWS);
+        return v_err.fail(EHM_E_INVALID, "successors: n_g = %d (0..%d)", (int)o->n_g,
+                          EHM_R_MAX_ROWS);
     DevPlant pl{};
     int rows = 0;
     for (int m = 0; m < o->n_modes; ++m) {
         const int r = o->region_rows ? o->region_rows[m] : 0;
-        if (r < 0) return vfail(EHM_E_INVALID, "successors: mode %d has %d region rows", m, r);
+        if (r < 0) return v_err.fail(EHM_E_INVALID, "successors: mode %d has %d region rows", m, r);
         pl.row0[m] = rows;
         rows += r;
     }
     if (rows > EHM_R_MAX_ROWS || (rows > 0 && (!o->H || !o->h)))
-        return vfail(EHM_E_INVALID, "successors: %d mode-region rows (0..%d)", rows,
-                     EHM_R_MAX_ROWS);
+        return v_err.fail(EHM_E_INVALID, "successors: %d mode-region rows (0..%d)", rows,
+                          EHM_R_MAX_ROWS);
     for (int m = o->n_modes; m <= EHM_R_MAX_MODES; ++m) pl.row0[m] = rows;
-    if (!o->leaf_ids && o->n > v.n_leaf)
-        return vfail(EHM_E_INVALID, "successors: n = %lld of %lld leaves", (long long)o->n,
-                     v.n_leaf);
-    if (o->leaf_ids) {
-        const int64_t bad = ehm_cert::first_bad_leaf(o->leaf_ids, o->n, v.n_leaf);
-        if (bad >= 0)
-            return vfail(EHM_E_INVALID, "successors: leaf_ids[%lld] = %d of %lld leaves",
-                         (long long)bad, (int)o->leaf_ids[bad], v.n_leaf);
-    }
+    rc = check_law_leaves(v_err, v, o->n, o->leaf_ids, "successors");
+    if (rc) return rc;
     std::memset(res, 0, sizeof *res);
     res->worst_leaf = -1;
     res->worst_margin = NAN;
@@ -399,33 +392,34 @@ int ehm_compiled_successors(ehm_compiled* law, const ehm_invariance_opts* o,
     pl.total = (int)pk.buf.size();
     const size_t plant_bytes = (size_t)pl.total * sizeof(double);
     const size_t lds = plant_bytes + EHM_INV_STATUSES * sizeof(unsigned int);
-    V_TRY(hipSetDevice(v.device));
+    EHM_HIP_TRY(v_err, hipSetDevice(v.device));
     Stream stream;
-    V_TRY(stream.create());
+    EHM_HIP_TRY(v_err, stream.create());
     const size_t cell = (size_t)(p + 1) * p, pts = (size_t)(p + 1) * n_c;
     ParentTable T;
-    V_TRY(make_parents(v, stream, T));
+    EHM_HIP_TRY(v_err, make_parents(v, stream, T));
     const long long chunk =
         o->chunk > 0 ? o->chunk
                      : std::max<long long>(EHM_INV_BLOCK, std::min<long long>(
                                                65536, EHM_INV_BUDGET / (long long)(pts * p)));
     const size_t cap = (size_t)std::min<long long>(chunk, o->n);
-    DevBuf dplant, dmode, droots, dids, dvert, dstatus, dmargin, dworst, dviol, dx, dsr, dsl, dcnt;
-    V_TRY(dplant.upload(pk.buf.data(), plant_bytes));
-    pl.data = dplant.as<const double>();
-    V_TRY(dmode.upload(o->leaf_mode, (size_t)v.n_leaf * sizeof(int32_t)));
-    V_TRY(droots.upload(o->root_vertices, (size_t)v.n_roots * cell * sizeof(double)));
-    if (o->leaf_ids) V_TRY(dids.alloc(cap * sizeof(int32_t)));
-    V_TRY(dvert.alloc(cap * cell * sizeof(double)));
-    V_TRY(dstatus.alloc(cap * sizeof(int32_t)));
-    V_TRY(dmargin.alloc(cap * sizeof(double)));
-    V_TRY(dworst.alloc(cap * sizeof(int32_t)));
-    V_TRY(dviol.alloc(cap * sizeof(double)));
-    if (lv->x_next) V_TRY(dx.alloc(cap * pts * p * sizeof(double)));
-    if (lv->succ_root) V_TRY(dsr.alloc(cap * pts * sizeof(int32_t)));
-    if (lv->succ_leaf) V_TRY(dsl.alloc(cap * pts * sizeof(int32_t)));
-    V_TRY(dcnt.alloc(EHM_INV_STATUSES * sizeof(unsigned long long)));
-    V_TRY(hipMemsetAsync(dcnt.ptr, 0, EHM_INV_STATUSES * sizeof(unsigned long long), stream));
+    SuccBufs D;
+    EHM_HIP_TRY(v_err, D.plant.upload(pk.buf.data(), plant_bytes));
+    pl.data = D.plant.as<const double>();
+    EHM_HIP_TRY(v_err, D.mode.upload(o->leaf_mode, (size_t)v.n_leaf * sizeof(int32_t)));
+    EHM_HIP_TRY(v_err, D.roots.upload(o->root_vertices, (size_t)v.n_roots * cell * sizeof(double)));
+    if (o->leaf_ids) EHM_HIP_TRY(v_err, D.ids.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(v_err, D.vert.alloc(cap * cell * sizeof(double)));
+    EHM_HIP_TRY(v_err, D.status.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(v_err, D.margin.alloc(cap * sizeof(double)));
+    EHM_HIP_TRY(v_err, D.worst.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(v_err, D.viol.alloc(cap * sizeof(double)));
+    if (lv->x_next) EHM_HIP_TRY(v_err, D.x.alloc(cap * pts * p * sizeof(double)));
+    if (lv->succ_root) EHM_HIP_TRY(v_err, D.sr.alloc(cap * pts * sizeof(int32_t)));
+    if (lv->succ_leaf) EHM_HIP_TRY(v_err, D.sl.alloc(cap * pts * sizeof(int32_t)));
+    EHM_HIP_TRY(v_err, D.cnt.alloc(EHM_INV_STATUSES * sizeof(unsigned long long)));
+    EHM_HIP_TRY(v_err, hipMemsetAsync(D.cnt.ptr, 0, EHM_INV_STATUSES * sizeof(unsigned long long),
+                                      stream));
     std::vector<double> hvert(cap * cell), R, vsub;
     std::vector<long long> has;
     EventPair ev;
@@ -433,56 +427,43 @@ int ehm_compiled_successors(ehm_compiled* law, const ehm_invariance_opts* o,
     for (long long off = 0; off < o->n; off += chunk) {
         const long long nc = std::min<long long>(chunk, o->n - off);
         if (o->leaf_ids)
-            V_TRY(hipMemcpyAsync(dids.ptr, o->leaf_ids + off, (size_t)nc * sizeof(int32_t),
-                                 hipMemcpyHostToDevice, stream));
-        const dim3 grid(cells_blocks_of(nc, EHM_INV_BLOCK)), block(EHM_INV_BLOCK);
+            EHM_HIP_TRY(v_err, hipMemcpyAsync(D.ids.ptr, o->leaf_ids + off,
+                                              (size_t)nc * sizeof(int32_t), hipMemcpyHostToDevice,
+                                              stream));
+        const dim3 grid(blocks_of(nc, EHM_INV_BLOCK)), block(EHM_INV_BLOCK);
         (void)hipEventRecord(ev.e0, stream);
-        if (v.single) {
-            SuccArgs<float> A{nc, o->leaf_ids ? dids.as<const int32_t>() : nullptr, off,
-                              static_cast<const float*>(v.node),
-                              static_cast<const float*>(v.leaf_rec), v.root_entry, v.root_rec,
-                              v.nbr, droots.as<const double>(), T.view(),
-                              dmode.as<const int32_t>(), n_u, v.leaf_stride, v.side_stride,
-                              (int)v.n_roots, n_d, o_lo, o_hi, o->tol_exit, dvert.as<double>(),
-                              dstatus.as<int32_t>(), dmargin.as<double>(), dworst.as<int32_t>(),
-                              dviol.as<double>(), dx.as<double>(), dsr.as<int32_t>(),
-                              dsl.as<int32_t>(), dcnt.as<unsigned long long>()};
-            hipLaunchKernelGGL(k_succ32[p - 1], grid, block, lds, stream, A, pl);
-        } else {
-            SuccArgs<double> A{nc, o->leaf_ids ? dids.as<const int32_t>() : nullptr, off,
-                               static_cast<const double*>(v.node),
-                               static_cast<const double*>(v.leaf_rec), v.root_entry, v.root_rec,
-                               v.nbr, droots.as<const double>(), T.view(),
-                               dmode.as<const int32_t>(), n_u, v.leaf_stride, v.side_stride,
-                               (int)v.n_roots, n_d, o_lo, o_hi, o->tol_exit, dvert.as<double>(),
-                               dstatus.as<int32_t>(), dmargin.as<double>(), dworst.as<int32_t>(),
-                               dviol.as<double>(), dx.as<double>(), dsr.as<int32_t>(),
-                               dsl.as<int32_t>(), dcnt.as<unsigned long long>()};
-            hipLaunchKernelGGL(k_succ64[p - 1], grid, block, lds, stream, A, pl);
-        }
+        if (v.single)
+            hipLaunchKernelGGL(k_succ32[p - 1], grid, block, lds, stream,
+                               succ_args<float>(v, o, D, T.view(), nc, off, o_lo, o_hi), pl);
+        else
+            hipLaunchKernelGGL(k_succ64[p - 1], grid, block, lds, stream,
+                               succ_args<double>(v, o, D, T.view(), nc, off, o_lo, o_hi), pl);
         (void)hipEventRecord(ev.e1, stream);
-        V_TRY(hipGetLastError());
+        EHM_HIP_TRY(v_err, hipGetLastError());
         const size_t N = (size_t)nc;
-        V_TRY(hipMemcpyAsync(hvert.data(), dvert.ptr, N * cell * sizeof(double),
-                             hipMemcpyDeviceToHost, stream));
-        V_TRY(hipMemcpyAsync(lv->status + off, dstatus.ptr, N * sizeof(int32_t),
-                             hipMemcpyDeviceToHost, stream));
-        V_TRY(hipMemcpyAsync(lv->margin + off, dmargin.ptr, N * sizeof(double),
-                             hipMemcpyDeviceToHost, stream));
-        V_TRY(hipMemcpyAsync(lv->worst + off, dworst.ptr, N * sizeof(int32_t),
-                             hipMemcpyDeviceToHost, stream));
-        V_TRY(hipMemcpyAsync(lv->max_violation + off, dviol.ptr, N * sizeof(double),
-                             hipMemcpyDeviceToHost, stream));
+        EHM_HIP_TRY(v_err, hipMemcpyAsync(hvert.data(), D.vert.ptr, N * cell * sizeof(double),
+                                          hipMemcpyDeviceToHost, stream));
+        EHM_HIP_TRY(v_err, hipMemcpyAsync(lv->status + off, D.status.ptr, N * sizeof(int32_t),
+                                          hipMemcpyDeviceToHost, stream));
+        EHM_HIP_TRY(v_err, hipMemcpyAsync(lv->margin + off, D.margin.ptr, N * sizeof(double),
+                                          hipMemcpyDeviceToHost, stream));
+        EHM_HIP_TRY(v_err, hipMemcpyAsync(lv->worst + off, D.worst.ptr, N * sizeof(int32_t),
+                                          hipMemcpyDeviceToHost, stream));
+        EHM_HIP_TRY(v_err, hipMemcpyAsync(lv->max_violation + off, D.viol.ptr, N * sizeof(double),
+                                          hipMemcpyDeviceToHost, stream));
         if (lv->x_next)
-            V_TRY(hipMemcpyAsync(lv->x_next + (size_t)off * pts * p, dx.ptr,
-                                 N * pts * p * sizeof(double), hipMemcpyDeviceToHost, stream));
+            EHM_HIP_TRY(v_err, hipMemcpyAsync(lv->x_next + (size_t)off * pts * p, D.x.ptr,
+                                              N * pts * p * sizeof(double), hipMemcpyDeviceToHost,
+                                              stream));
         if (lv->succ_root)
-            V_TRY(hipMemcpyAsync(lv->succ_root + (size_t)off * pts, dsr.ptr,
-                                 N * pts * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+            EHM_HIP_TRY(v_err, hipMemcpyAsync(lv->succ_root + (size_t)off * pts, D.sr.ptr,
+                                              N * pts * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                              stream));
         if (lv->succ_leaf)
-            V_TRY(hipMemcpyAsync(lv->succ_leaf + (size_t)off * pts, dsl.ptr,
-                                 N * pts * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-        V_TRY(hipStreamSynchronize(stream));
+            EHM_HIP_TRY(v_err, hipMemcpyAsync(lv->succ_leaf + (size_t)off * pts, D.sl.ptr,
+                                              N * pts * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                              stream));
+        EHM_HIP_TRY(v_err, hipStreamSynchronize(stream));
         double s = 0.0;
         ev.seconds(&s);
         res->seconds += s;
@@ -505,10 +486,9 @@ int ehm_compiled_successors(ehm_compiled* law, const ehm_invariance_opts* o,
             vsub.resize(has.size());
             for (size_t a = 0; a < has.size(); ++a)
                 std::memcpy(&R[a * cell], &hvert[(size_t)has[a] * cell], cell * sizeof(double));
-            const int rc = ehm_volume_batch(v.device, (int64_t)has.size(), p, R.data(),
-                                            vsub.data());
-            if (rc) return vfail(rc, "successors: ehm_volume_batch: %s", ehm_last_error());
-            V_TRY(hipSetDevice(v.device));
+            rc = ehm_volume_batch(v.device, (int64_t)has.size(), p, R.data(), vsub.data());
+            if (rc) return v_err.fail(rc, "successors: ehm_volume_batch: %s", ehm_last_error());
+            EHM_HIP_TRY(v_err, hipSetDevice(v.device));
             for (size_t a = 0; a < has.size(); ++a) {
                 res->cell_volume += vsub[a];
                 if (lv->status[off + has[a]] == INV_INVARIANT) res->invariant_volume += vsub[a];
@@ -516,7 +496,7 @@ int ehm_compiled_successors(ehm_compiled* law, const ehm_invariance_opts* o,
         }
     }
     unsigned long long cnt[EHM_INV_STATUSES];
-    V_TRY(hipMemcpy(cnt, dcnt.ptr, sizeof cnt, hipMemcpyDeviceToHost));
+    EHM_HIP_TRY(v_err, hipMemcpy(cnt, D.cnt.ptr, sizeof cnt, hipMemcpyDeviceToHost));
     for (int i = 0; i < EHM_INV_STATUSES; ++i) res->counts[i] = (int64_t)cnt[i];
     return EHM_OK;
 }

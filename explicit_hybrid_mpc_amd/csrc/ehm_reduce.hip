@@ -275,42 +275,26 @@ const flags64_fn k_flags64[EHM_CP] = EHM_RED_ALL(double);
 const flags32_fn k_flags32[EHM_CP] = EHM_RED_ALL(float);
 #undef EHM_RED_ALL
 
-thread_local std::string r_err;
-int rfail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    r_err = buf;
-    return code;
-}
-
-#define R_TRY(expr)                                                                        \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return rfail(EHM_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));        \
-    } while (0)
+thread_local ehm_err_channel r_err;
 
 // out [n] = the exclusive sums of in [n] on the device
 int exclusive_scan(hipStream_t stream, const int32_t* in, int32_t* out, long long n) {
     const long long tiles = (n + EHM_RED_SCAN_TILE - 1) / EHM_RED_SCAN_TILE;
     DevBuf sums, offs;
-    R_TRY(sums.alloc((size_t)tiles * sizeof(int32_t)));
+    EHM_HIP_TRY(r_err, sums.alloc((size_t)tiles * sizeof(int32_t)));
     hipLaunchKernelGGL(k_reduce_scan, dim3((unsigned)tiles), dim3(EHM_RED_SCAN_BLOCK), 0, stream,
                        n, in, out, sums.as<int32_t>());
-    R_TRY(hipGetLastError());
+    EHM_HIP_TRY(r_err, hipGetLastError());
     if (tiles > 1) {
-        R_TRY(offs.alloc((size_t)tiles * sizeof(int32_t)));
+        EHM_HIP_TRY(r_err, offs.alloc((size_t)tiles * sizeof(int32_t)));
         const int rc = exclusive_scan(stream, sums.as<const int32_t>(), offs.as<int32_t>(), tiles);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_reduce_scan_add, dim3(cells_blocks_of(n, 256)), dim3(256), 0, stream,
+        hipLaunchKernelGGL(k_reduce_scan_add, dim3(blocks_of(n, 256)), dim3(256), 0, stream,
                            n, out, offs.as<const int32_t>());
-        R_TRY(hipGetLastError());
+        EHM_HIP_TRY(r_err, hipGetLastError());
     }
     // the buffers are freed on return: hipFree waits for the work that uses them
-    R_TRY(hipStreamSynchronize(stream));
+    EHM_HIP_TRY(r_err, hipStreamSynchronize(stream));
     return EHM_OK;
 }
 
@@ -325,38 +309,38 @@ int reduce_law(ehm_compiled* law, const ehm_compiled_view& v, hipStream_t stream
     const T* leaf_rec = static_cast<const T*>(v.leaf_rec);
     const int32_t* leaf_node = v.leaf_node;
     ParentTable tab;
-    R_TRY(make_parents(v, stream, tab));
+    EHM_HIP_TRY(r_err, make_parents(v, stream, tab));
     const Parents par = tab.view();
     DevBuf d_bad, d_rep, d_open, d_roots, d_tol, d_mode, d_blk, d_dev;
-    R_TRY(d_bad.alloc(sizeof(int32_t)));
-    R_TRY(hipMemsetAsync(d_bad.ptr, 0, sizeof(int32_t), stream));
-    hipLaunchKernelGGL(k_reduce_forest<T>, dim3(cells_blocks_of(n_int + n_roots, 256)), dim3(256),
+    EHM_HIP_TRY(r_err, d_bad.alloc(sizeof(int32_t)));
+    EHM_HIP_TRY(r_err, hipMemsetAsync(d_bad.ptr, 0, sizeof(int32_t), stream));
+    hipLaunchKernelGGL(k_reduce_forest<T>, dim3(blocks_of(n_int + n_roots, 256)), dim3(256),
                        0, stream, n_int, n_roots, p, v.node_stride, node, v.root_entry, par,
                        d_bad.as<int32_t>());
-    R_TRY(hipGetLastError());
+    EHM_HIP_TRY(r_err, hipGetLastError());
     int32_t bad = 0;
-    R_TRY(hipMemcpyAsync(&bad, d_bad.ptr, sizeof bad, hipMemcpyDeviceToHost, stream));
-    R_TRY(hipStreamSynchronize(stream));
+    EHM_HIP_TRY(r_err, hipMemcpyAsync(&bad, d_bad.ptr, sizeof bad, hipMemcpyDeviceToHost, stream));
+    EHM_HIP_TRY(r_err, hipStreamSynchronize(stream));
     if (bad)
-        return rfail(EHM_E_INVALID, "reduce: the law's records form no forest (a record is named "
-                     "by two parents or roots)");
-    R_TRY(d_rep.alloc((size_t)n_int * sizeof(int32_t)));
-    R_TRY(d_open.alloc((size_t)n_int));
+        return r_err.fail(EHM_E_INVALID, "reduce: the law's records form no forest (a record is "
+                          "named by two parents or roots)");
+    EHM_HIP_TRY(r_err, d_rep.alloc((size_t)n_int * sizeof(int32_t)));
+    EHM_HIP_TRY(r_err, d_open.alloc((size_t)n_int));
     if (n_int) {
-        R_TRY(hipMemsetD32Async((hipDeviceptr_t)d_rep.ptr, -1, (size_t)n_int, stream));
-        R_TRY(hipMemsetAsync(d_open.ptr, 0, (size_t)n_int, stream));
+        EHM_HIP_TRY(r_err, hipMemsetD32Async((hipDeviceptr_t)d_rep.ptr, -1, (size_t)n_int, stream));
+        EHM_HIP_TRY(r_err, hipMemsetAsync(d_open.ptr, 0, (size_t)n_int, stream));
     }
-    hipLaunchKernelGGL(k_reduce_rep, dim3(cells_blocks_of(n_leaf, 256)), dim3(256), 0, stream,
+    hipLaunchKernelGGL(k_reduce_rep, dim3(blocks_of(n_leaf, 256)), dim3(256), 0, stream,
                        n_leaf, par, d_rep.as<int32_t>());
-    R_TRY(hipGetLastError());
+    EHM_HIP_TRY(r_err, hipGetLastError());
     // the flags
     const size_t cell = (size_t)(p + 1) * p;
-    R_TRY(d_roots.upload(root_vertices, (size_t)n_roots * cell * sizeof(double)));
-    R_TRY(d_tol.upload(tol, (size_t)n_u * sizeof(double)));
-    if (leaf_mode) R_TRY(d_mode.upload(leaf_mode, (size_t)n_leaf * sizeof(int32_t)));
-    const unsigned nblk = cells_blocks_of(n_leaf, EHM_RED_BLOCK);
-    R_TRY(d_blk.alloc((size_t)nblk * sizeof(double)));
-    R_TRY(d_dev.alloc(sizeof(double)));
+    EHM_HIP_TRY(r_err, d_roots.upload(root_vertices, (size_t)n_roots * cell * sizeof(double)));
+    EHM_HIP_TRY(r_err, d_tol.upload(tol, (size_t)n_u * sizeof(double)));
+    if (leaf_mode) EHM_HIP_TRY(r_err, d_mode.upload(leaf_mode, (size_t)n_leaf * sizeof(int32_t)));
+    const unsigned nblk = blocks_of(n_leaf, EHM_RED_BLOCK);
+    EHM_HIP_TRY(r_err, d_blk.alloc((size_t)nblk * sizeof(double)));
+    EHM_HIP_TRY(r_err, d_dev.alloc(sizeof(double)));
     FlagArgs<T> F{n_leaf, node, leaf_rec, v.root_entry, d_roots.as<const double>(), par,
                   d_rep.as<const int32_t>(), leaf_mode ? d_mode.as<const int32_t>() : nullptr,
                   d_tol.as<const double>(), n_u, v.leaf_stride, d_open.as<uint8_t>(),
@@ -365,24 +349,26 @@ int reduce_law(ehm_compiled* law, const ehm_compiled_view& v, hipStream_t stream
         hipLaunchKernelGGL(k_flags32[p - 1], dim3(nblk), dim3(EHM_RED_BLOCK), 0, stream, F);
     else
         hipLaunchKernelGGL(k_flags64[p - 1], dim3(nblk), dim3(EHM_RED_BLOCK), 0, stream, F);
-    R_TRY(hipGetLastError());
+    EHM_HIP_TRY(r_err, hipGetLastError());
     hipLaunchKernelGGL(k_reduce_max, dim3(1), dim3(256), 0, stream, (long long)nblk,
                        d_blk.as<const double>(), d_dev.as<double>());
-    R_TRY(hipGetLastError());
+    EHM_HIP_TRY(r_err, hipGetLastError());
     // survivors and their new places; element n of each scan is the number of survivors
     DevBuf d_keep_int, d_keep_leaf, d_new_int, d_new_leaf, d_target;
-    R_TRY(d_keep_int.alloc((size_t)(n_int + 1) * sizeof(int32_t)));
-    R_TRY(d_keep_leaf.alloc((size_t)(n_leaf + 1) * sizeof(int32_t)));
-    R_TRY(d_new_int.alloc((size_t)(n_int + 1) * sizeof(int32_t)));
-    R_TRY(d_new_leaf.alloc((size_t)(n_leaf + 1) * sizeof(int32_t)));
-    R_TRY(d_target.alloc((size_t)n_leaf * sizeof(int32_t)));
-    R_TRY(hipMemsetAsync(d_keep_int.ptr, 0, (size_t)(n_int + 1) * sizeof(int32_t), stream));
-    R_TRY(hipMemsetAsync(d_keep_leaf.ptr, 0, (size_t)(n_leaf + 1) * sizeof(int32_t), stream));
-    hipLaunchKernelGGL(k_reduce_survive, dim3(cells_blocks_of(n_int + n_leaf, 256)), dim3(256), 0,
+    EHM_HIP_TRY(r_err, d_keep_int.alloc((size_t)(n_int + 1) * sizeof(int32_t)));
+    EHM_HIP_TRY(r_err, d_keep_leaf.alloc((size_t)(n_leaf + 1) * sizeof(int32_t)));
+    EHM_HIP_TRY(r_err, d_new_int.alloc((size_t)(n_int + 1) * sizeof(int32_t)));
+    EHM_HIP_TRY(r_err, d_new_leaf.alloc((size_t)(n_leaf + 1) * sizeof(int32_t)));
+    EHM_HIP_TRY(r_err, d_target.alloc((size_t)n_leaf * sizeof(int32_t)));
+    EHM_HIP_TRY(r_err, hipMemsetAsync(d_keep_int.ptr, 0, (size_t)(n_int + 1) * sizeof(int32_t),
+                                      stream));
+    EHM_HIP_TRY(r_err, hipMemsetAsync(d_keep_leaf.ptr, 0, (size_t)(n_leaf + 1) * sizeof(int32_t),
+                                      stream));
+    hipLaunchKernelGGL(k_reduce_survive, dim3(blocks_of(n_int + n_leaf, 256)), dim3(256), 0,
                        stream, n_int, n_leaf, par, d_open.as<const uint8_t>(),
                        d_rep.as<const int32_t>(), d_keep_int.as<int32_t>(),
                        d_keep_leaf.as<int32_t>(), d_target.as<int32_t>());
-    R_TRY(hipGetLastError());
+    EHM_HIP_TRY(r_err, hipGetLastError());
     int rc = exclusive_scan(stream, d_keep_int.as<const int32_t>(), d_new_int.as<int32_t>(),
                             n_int + 1);
     if (rc) return rc;
@@ -390,23 +376,24 @@ int reduce_law(ehm_compiled* law, const ehm_compiled_view& v, hipStream_t stream
                         n_leaf + 1);
     if (rc) return rc;
     int32_t m_int = 0, m_leaf = 0;
-    R_TRY(hipMemcpyAsync(&m_int, d_new_int.as<int32_t>() + n_int, sizeof m_int,
-                         hipMemcpyDeviceToHost, stream));
-    R_TRY(hipMemcpyAsync(&m_leaf, d_new_leaf.as<int32_t>() + n_leaf, sizeof m_leaf,
-                         hipMemcpyDeviceToHost, stream));
-    R_TRY(hipMemcpyAsync(max_deviation, d_dev.ptr, sizeof(double), hipMemcpyDeviceToHost, stream));
-    R_TRY(hipStreamSynchronize(stream));
+    EHM_HIP_TRY(r_err, hipMemcpyAsync(&m_int, d_new_int.as<int32_t>() + n_int, sizeof m_int,
+                                      hipMemcpyDeviceToHost, stream));
+    EHM_HIP_TRY(r_err, hipMemcpyAsync(&m_leaf, d_new_leaf.as<int32_t>() + n_leaf, sizeof m_leaf,
+                                      hipMemcpyDeviceToHost, stream));
+    EHM_HIP_TRY(r_err, hipMemcpyAsync(max_deviation, d_dev.ptr, sizeof(double),
+                                      hipMemcpyDeviceToHost, stream));
+    EHM_HIP_TRY(r_err, hipStreamSynchronize(stream));
     if (m_int < 0 || m_int > n_int || m_leaf < 1 || m_leaf > n_leaf)
-        return rfail(EHM_E_NUMERIC, "reduce: %d of %lld internal records and %d of %lld leaves "
-                     "survive", (int)m_int, n_int, (int)m_leaf, n_leaf);
+        return r_err.fail(EHM_E_NUMERIC, "reduce: %d of %lld internal records and %d of %lld "
+                          "leaves survive", (int)m_int, n_int, (int)m_leaf, n_leaf);
     // the new arrays
     DevBuf node_out, leaf_out, leaf_node_out, mode_out, entry_out, d_leaf_of;
-    R_TRY(node_out.alloc((size_t)m_int * v.node_stride * sizeof(T)));
-    R_TRY(leaf_out.alloc((size_t)m_leaf * v.leaf_stride * sizeof(T)));
-    R_TRY(leaf_node_out.alloc((size_t)m_leaf * sizeof(int32_t)));
-    if (leaf_mode) R_TRY(mode_out.alloc((size_t)m_leaf * sizeof(int32_t)));
-    R_TRY(entry_out.alloc((size_t)n_roots * sizeof(int32_t)));
-    R_TRY(d_leaf_of.alloc((size_t)n_leaf * sizeof(int32_t)));
+    EHM_HIP_TRY(r_err, node_out.alloc((size_t)m_int * v.node_stride * sizeof(T)));
+    EHM_HIP_TRY(r_err, leaf_out.alloc((size_t)m_leaf * v.leaf_stride * sizeof(T)));
+    EHM_HIP_TRY(r_err, leaf_node_out.alloc((size_t)m_leaf * sizeof(int32_t)));
+    if (leaf_mode) EHM_HIP_TRY(r_err, mode_out.alloc((size_t)m_leaf * sizeof(int32_t)));
+    EHM_HIP_TRY(r_err, entry_out.alloc((size_t)n_roots * sizeof(int32_t)));
+    EHM_HIP_TRY(r_err, d_leaf_of.alloc((size_t)n_leaf * sizeof(int32_t)));
     RewriteArgs<T> W{n_int, n_leaf, n_roots, p, v.node_stride, v.leaf_stride, node, leaf_rec,
                      leaf_node, leaf_mode ? d_mode.as<const int32_t>() : nullptr, v.root_entry,
                      d_open.as<const uint8_t>(), d_rep.as<const int32_t>(),
@@ -415,22 +402,24 @@ int reduce_law(ehm_compiled* law, const ehm_compiled_view& v, hipStream_t stream
                      d_target.as<const int32_t>(), node_out.as<T>(), leaf_out.as<T>(),
                      leaf_node_out.as<int32_t>(), leaf_mode ? mode_out.as<int32_t>() : nullptr,
                      entry_out.as<int32_t>(), d_leaf_of.as<int32_t>()};
-    hipLaunchKernelGGL(k_reduce_rewrite<T>, dim3(cells_blocks_of(n_int + n_leaf + n_roots, 256)),
+    hipLaunchKernelGGL(k_reduce_rewrite<T>, dim3(blocks_of(n_int + n_leaf + n_roots, 256)),
                        dim3(256), 0, stream, W);
-    R_TRY(hipGetLastError());
+    EHM_HIP_TRY(r_err, hipGetLastError());
     if (leaf_of)
-        R_TRY(hipMemcpyAsync(leaf_of, d_leaf_of.ptr, (size_t)n_leaf * sizeof(int32_t),
-                             hipMemcpyDeviceToHost, stream));
+        EHM_HIP_TRY(r_err, hipMemcpyAsync(leaf_of, d_leaf_of.ptr, (size_t)n_leaf * sizeof(int32_t),
+                                          hipMemcpyDeviceToHost, stream));
     if (leaf_mode && leaf_mode_out)
-        R_TRY(hipMemcpyAsync(leaf_mode_out, mode_out.ptr, (size_t)m_leaf * sizeof(int32_t),
-                             hipMemcpyDeviceToHost, stream));
-    R_TRY(hipStreamSynchronize(stream));
+        EHM_HIP_TRY(r_err, hipMemcpyAsync(leaf_mode_out, mode_out.ptr,
+                                          (size_t)m_leaf * sizeof(int32_t), hipMemcpyDeviceToHost,
+                                          stream));
+    EHM_HIP_TRY(r_err, hipStreamSynchronize(stream));
     counts[0] = n_leaf;
     counts[1] = m_leaf;
     counts[2] = n_int;
     counts[3] = m_int;
     rc = ehm_compiled_adopt(law, m_int, m_leaf, node_out, leaf_out, leaf_node_out, entry_out, out);
-    if (rc) return rfail(rc, "reduce: the reduced law is refused: %s", ehm_compiled_last_error());
+    if (rc) return r_err.fail(rc, "reduce: the reduced law is refused: %s",
+                              ehm_compiled_last_error());
     return EHM_OK;
 }
 
@@ -445,31 +434,27 @@ int ehm_compiled_reduce(ehm_compiled* law, const double* root_vertices, const do
                         int32_t* leaf_of, int64_t* counts, double* stats) {
     if (out) *out = nullptr;
     if (!law || !root_vertices || !tol || !out || !counts || !stats)
-        return rfail(EHM_E_INVALID, "reduce: bad argument");
+        return r_err.fail(EHM_E_INVALID, "reduce: bad argument");
     const auto t0 = std::chrono::steady_clock::now();
     ehm_compiled_view v;
     ehm_compiled_get_view(law, &v);
-    if (v.n_test > 0)
-        return rfail(EHM_E_INVALID, "reduce: the law has %lld test nodes (children that are no "
-                     "bisection); its cells do not follow from its planes -- compile it with the "
-                     "spine as its root table", v.n_test);
-    if (v.p < 1 || v.p > EHM_CP) return rfail(EHM_E_INVALID, "reduce: p = %d", v.p);
-    if (v.n_roots >= 0x7fffffffLL) return rfail(EHM_E_INVALID, "reduce: too many roots");
+    if (const int rc = check_law_shape(r_err, v, "reduce")) return rc;
     for (int c = 0; c < v.n_u; ++c)
         if (!(tol[c] >= 0.0) || !std::isfinite(tol[c]))
-            return rfail(EHM_E_INVALID, "reduce: tol[%d] = %g (a finite number >= 0)", c, tol[c]);
-    R_TRY(hipSetDevice(v.device));
+            return r_err.fail(EHM_E_INVALID, "reduce: tol[%d] = %g (a finite number >= 0)", c,
+                              tol[c]);
+    EHM_HIP_TRY(r_err, hipSetDevice(v.device));
     Stream stream;
-    R_TRY(stream.create());
+    EHM_HIP_TRY(r_err, stream.create());
     // the law's arrays were written on its own stream (create) or by blocking copies (import)
-    R_TRY(hipStreamSynchronize(v.stream));
+    EHM_HIP_TRY(r_err, hipStreamSynchronize(v.stream));
     stats[0] = 0.0;
     const int rc = v.single
         ? reduce_law<float>(law, v, stream, root_vertices, tol, leaf_mode, out, leaf_mode_out,
                             leaf_of, counts, &stats[0])
         : reduce_law<double>(law, v, stream, root_vertices, tol, leaf_mode, out, leaf_mode_out,
                              leaf_of, counts, &stats[0]);
-    stats[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    stats[1] = wall_since(t0);
     return rc;
 }
 

@@ -508,32 +508,29 @@ struct RolloutAttach {
     int noise_n_d = 0;
 };
 
-// a translation unit's error channel (xfail, cfail): stores the message, returns the code
-typedef int (*fail_fn)(int, const char*, ...);
-
 // What the two plant setters share: the checks of the common arguments; A, B, w, Gx, gx, Q and R
 // packed, then the setter's own arrays (`own` checks and packs them); the mode table (n_mode
 // entries, one per `what`) checked (< n_modes for the nominal plant; >= -1 for a guarded one, whose
 // guards choose the modes); the new device buffers swapped in.  gd: the guards of a guarded plant
 // (filled by `own`), nullptr for the nominal.
 template <class Own>
-int install_plant(RolloutAttach& ro, fail_fn fail, int device, int p, int n_u, int64_t n_mode,
-                  const char* what, const char* who, int32_t n_modes, int max_modes,
+int install_plant(RolloutAttach& ro, ehm_err_channel& err, int device, int p, int n_u,
+                  int64_t n_mode, const char* what, const char* who, int32_t n_modes, int max_modes,
                   const double* A, const double* B, const double* w, int32_t n_g, const double* Gx,
                   const double* gx, const int32_t* mode, int32_t cost_kind, const double* Q,
                   const double* R, const DevGuard* gd, Own own) {
     if (!A || !B || !w || !mode || !Q || !R)
-        return fail(EHM_E_INVALID, "%s: a required array is NULL", who);
+        return err.fail(EHM_E_INVALID, "%s: a required array is NULL", who);
     if (n_modes < 1 || n_modes > max_modes)
-        return fail(EHM_E_INVALID, "%s: %d modes (1..%d)", who, (int)n_modes, max_modes);
+        return err.fail(EHM_E_INVALID, "%s: %d modes (1..%d)", who, (int)n_modes, max_modes);
     if (n_g < 0 || n_g > EHM_R_MAX_ROWS || (n_g > 0 && (!Gx || !gx)))
-        return fail(EHM_E_INVALID, "%s: n_g = %d (0..%d)", who, (int)n_g, EHM_R_MAX_ROWS);
+        return err.fail(EHM_E_INVALID, "%s: n_g = %d (0..%d)", who, (int)n_g, EHM_R_MAX_ROWS);
     if (cost_kind != 0 && cost_kind != 1)
-        return fail(EHM_E_INVALID, "%s: cost_kind %d (0 inf-norm, 1 quadratic)", who,
-                    (int)cost_kind);
+        return err.fail(EHM_E_INVALID, "%s: cost_kind %d (0 inf-norm, 1 quadratic)", who,
+                        (int)cost_kind);
     if (n_u > EHM_R_MAX_NU)
-        return fail(EHM_E_INVALID, "%s: n_u = %d, the rollout takes at most %d inputs", who, n_u,
-                    EHM_R_MAX_NU);
+        return err.fail(EHM_E_INVALID, "%s: n_u = %d, the rollout takes at most %d inputs", who,
+                        n_u, EHM_R_MAX_NU);
     DevPlant pl{};
     pl.n_modes = n_modes;
     pl.n_g = n_g;
@@ -551,14 +548,14 @@ int install_plant(RolloutAttach& ro, fail_fn fail, int device, int p, int n_u, i
     pl.total = (int)pk.buf.size();
     for (int64_t k = 0; k < n_mode; ++k)
         if (gd ? mode[k] < -1 : mode[k] >= n_modes)
-            return fail(EHM_E_INVALID, "%s: %s %lld has mode %d of %d", who, what, (long long)k,
-                        (int)mode[k], (int)n_modes);
+            return err.fail(EHM_E_INVALID, "%s: %s %lld has mode %d of %d", who, what, (long long)k,
+                            (int)mode[k], (int)n_modes);
     hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return err.fail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
     DevBuf d_plant, d_mode;
     if (d_plant.upload(pk.buf.data(), pk.buf.size() * sizeof(double)) != hipSuccess ||
         d_mode.upload(mode, (size_t)n_mode * sizeof(int32_t)) != hipSuccess)
-        return fail(EHM_E_HIP, "%s: device allocation / copy failed", who);
+        return err.fail(EHM_E_HIP, "%s: device allocation / copy failed", who);
     ro.plant = std::move(d_plant);
     ro.mode = std::move(d_mode);
     pl.data = ro.plant.as<const double>();
@@ -569,22 +566,22 @@ int install_plant(RolloutAttach& ro, fail_fn fail, int device, int p, int n_u, i
 }
 
 // `own` of the nominal setter: E, and the mode regions stacked by mode
-inline int pack_nominal(fail_fn fail, Pack& pk, DevPlant& pl, int p, int32_t n_modes, int32_t n_d,
-                        const double* Emat, const int32_t* region_rows, const double* H,
-                        const double* h) {
+inline int pack_nominal(ehm_err_channel& err, Pack& pk, DevPlant& pl, int p, int32_t n_modes,
+                        int32_t n_d, const double* Emat, const int32_t* region_rows,
+                        const double* H, const double* h) {
     if (n_d < 0 || n_d > EHM_R_MAX_D || (n_d > 0 && !Emat))
-        return fail(EHM_E_INVALID, "set_plant: n_d = %d (0..%d, E needed if > 0)", (int)n_d,
-                    EHM_R_MAX_D);
+        return err.fail(EHM_E_INVALID, "set_plant: n_d = %d (0..%d, E needed if > 0)", (int)n_d,
+                        EHM_R_MAX_D);
     int rows = 0;
     for (int m = 0; m < n_modes; ++m) {
         const int r = region_rows ? region_rows[m] : 0;
-        if (r < 0) return fail(EHM_E_INVALID, "set_plant: mode %d has %d region rows", m, r);
+        if (r < 0) return err.fail(EHM_E_INVALID, "set_plant: mode %d has %d region rows", m, r);
         pl.row0[m] = rows;
         rows += r;
     }
     if (rows > EHM_R_MAX_ROWS || (rows > 0 && (!H || !h)))
-        return fail(EHM_E_INVALID, "set_plant: %d mode-region rows (0..%d)", rows,
-                    EHM_R_MAX_ROWS);
+        return err.fail(EHM_E_INVALID, "set_plant: %d mode-region rows (0..%d)", rows,
+                        EHM_R_MAX_ROWS);
     for (int m = n_modes; m <= EHM_R_MAX_MODES; ++m) pl.row0[m] = rows;
     pl.n_d = n_d;
     pl.oE = pk.put(Emat, (size_t)p * n_d);
@@ -594,43 +591,43 @@ inline int pack_nominal(fail_fn fail, Pack& pk, DevPlant& pl, int p, int32_t n_m
 }
 
 // `own` of the guarded setter: the guards into gd, their rows after the modes
-inline int pack_guarded(fail_fn fail, Pack& pk, DevGuard& gd, int p, int n_u, int32_t n_modes,
-                        int32_t substeps, int32_t n_guards, const int32_t* guard_mode,
-                        const int32_t* guard_row0, const double* ga, const double* gb,
-                        const double* gc, const double* gt, const int32_t* strict,
-                        int32_t default_mode) {
+inline int pack_guarded(ehm_err_channel& err, Pack& pk, DevGuard& gd, int p, int n_u,
+                        int32_t n_modes, int32_t substeps, int32_t n_guards,
+                        const int32_t* guard_mode, const int32_t* guard_row0, const double* ga,
+                        const double* gb, const double* gc, const double* gt,
+                        const int32_t* strict, int32_t default_mode) {
     if ((n_guards > 0 && !guard_mode) || !guard_row0)
-        return fail(EHM_E_INVALID, "set_plant_guarded: a required array is NULL");
+        return err.fail(EHM_E_INVALID, "set_plant_guarded: a required array is NULL");
     if (substeps < 1 || substeps > EHM_G_MAX_SUB)
-        return fail(EHM_E_INVALID, "set_plant_guarded: %d substeps (1..%d)", (int)substeps,
-                    EHM_G_MAX_SUB);
+        return err.fail(EHM_E_INVALID, "set_plant_guarded: %d substeps (1..%d)", (int)substeps,
+                        EHM_G_MAX_SUB);
     if (n_guards < 0 || n_guards > EHM_G_MAX_ROWS)
-        return fail(EHM_E_INVALID, "set_plant_guarded: %d guards (0..%d)", (int)n_guards,
-                    EHM_G_MAX_ROWS);
+        return err.fail(EHM_E_INVALID, "set_plant_guarded: %d guards (0..%d)", (int)n_guards,
+                        EHM_G_MAX_ROWS);
     if (default_mode < 0 || default_mode >= n_modes)
-        return fail(EHM_E_INVALID, "set_plant_guarded: default mode %d of %d", (int)default_mode,
-                    (int)n_modes);
+        return err.fail(EHM_E_INVALID, "set_plant_guarded: default mode %d of %d",
+                        (int)default_mode, (int)n_modes);
     if (guard_row0[0] != 0)
-        return fail(EHM_E_INVALID, "set_plant_guarded: the rows of guard 0 start at %d",
-                    (int)guard_row0[0]);
+        return err.fail(EHM_E_INVALID, "set_plant_guarded: the rows of guard 0 start at %d",
+                        (int)guard_row0[0]);
     gd.substeps = substeps;
     gd.n_guards = n_guards;
     gd.default_mode = default_mode;
     for (int g = 0; g <= n_guards; ++g) {
         if (g < n_guards) {
             if (guard_mode[g] < 0 || guard_mode[g] >= n_modes)
-                return fail(EHM_E_INVALID, "set_plant_guarded: guard %d selects mode %d of %d", g,
-                            (int)guard_mode[g], (int)n_modes);
+                return err.fail(EHM_E_INVALID, "set_plant_guarded: guard %d selects mode %d of %d",
+                                g, (int)guard_mode[g], (int)n_modes);
             if (guard_row0[g + 1] <= guard_row0[g])
-                return fail(EHM_E_INVALID, "set_plant_guarded: guard %d has no rows", g);
+                return err.fail(EHM_E_INVALID, "set_plant_guarded: guard %d has no rows", g);
             gd.mode[g] = guard_mode[g];
         }
         gd.row0[g] = guard_row0[g];
     }
     const int rows = guard_row0[n_guards];
     if (rows > EHM_G_MAX_ROWS || (rows > 0 && (!ga || !gb || !gc || !gt || !strict)))
-        return fail(EHM_E_INVALID, "set_plant_guarded: %d guard rows (0..%d)", rows,
-                    EHM_G_MAX_ROWS);
+        return err.fail(EHM_E_INVALID, "set_plant_guarded: %d guard rows (0..%d)", rows,
+                        EHM_G_MAX_ROWS);
     for (int r = 0; r < rows; ++r) gd.strict[r] = strict[r] != 0;
     gd.oGa = pk.put(ga, (size_t)rows * p);
     gd.oGb = pk.put(gb, (size_t)rows * n_u);
@@ -640,24 +637,24 @@ inline int pack_guarded(fail_fn fail, Pack& pk, DevGuard& gd, int p, int n_u, in
 }
 
 // set_noise of a fused rollout's handle
-inline int install_noise(RolloutAttach& ro, fail_fn fail, int device, int p, int n_u,
+inline int install_noise(RolloutAttach& ro, ehm_err_channel& err, int device, int p, int n_u,
                          int32_t n_terms, const int32_t* desc, const double* data, int32_t n_data,
                          int32_t n_d) {
     if (n_terms < 0 || n_terms > EHM_N_MAX_TERMS || (n_terms > 0 && !desc) || n_data < 0 ||
         (n_data > 0 && !data) || n_d < 0 || n_d > EHM_R_MAX_D)
-        return fail(EHM_E_INVALID, "set_noise: bad argument (at most %d terms, n_d <= %d)",
-                    EHM_N_MAX_TERMS, EHM_R_MAX_D);
+        return err.fail(EHM_E_INVALID, "set_noise: bad argument (at most %d terms, n_d <= %d)",
+                        EHM_N_MAX_TERMS, EHM_R_MAX_D);
     DevNoise nz{};
     const int bad = noise_fill(nz, n_terms, desc, n_data, p, n_u, n_d);
-    if (bad >= 0) return fail(EHM_E_INVALID, "set_noise: term %d has a bad descriptor", bad);
+    if (bad >= 0) return err.fail(EHM_E_INVALID, "set_noise: term %d has a bad descriptor", bad);
     if (ro.pl.total + n_data > EHM_N_MAX_LDS)
-        return fail(EHM_E_INVALID, "set_noise: plant and model take %d doubles of LDS (%d)",
-                    ro.pl.total + n_data, EHM_N_MAX_LDS);
+        return err.fail(EHM_E_INVALID, "set_noise: plant and model take %d doubles of LDS (%d)",
+                        ro.pl.total + n_data, EHM_N_MAX_LDS);
     hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return err.fail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
     DevBuf d_noise;
     if (d_noise.upload(data, (size_t)n_data * sizeof(double)) != hipSuccess)
-        return fail(EHM_E_HIP, "set_noise: device allocation / copy failed");
+        return err.fail(EHM_E_HIP, "set_noise: device allocation / copy failed");
     ro.noise = std::move(d_noise);
     nz.data = ro.noise.as<const double>();
     ro.nz = nz;
@@ -672,11 +669,11 @@ struct NoisyCall {
 };
 
 // What the noisy entry point checks before rollout_run
-inline int noisy_ready(const RolloutAttach& ro, fail_fn fail) {
-    if (!ro.noise) return fail(EHM_E_INVALID, "rollout_noisy: no model (set_noise)");
+inline int noisy_ready(const RolloutAttach& ro, ehm_err_channel& err) {
+    if (!ro.noise) return err.fail(EHM_E_INVALID, "rollout_noisy: no model (set_noise)");
     if (ro.plant && ro.noise_n_d != ro.pl.n_d)
-        return fail(EHM_E_INVALID, "rollout_noisy: the model has n_d = %d, the plant %d",
-                    ro.noise_n_d, ro.pl.n_d);
+        return err.fail(EHM_E_INVALID, "rollout_noisy: the model has n_d = %d, the plant %d",
+                        ro.noise_n_d, ro.pl.n_d);
     return EHM_OK;
 }
 
@@ -684,8 +681,8 @@ inline int noisy_ready(const RolloutAttach& ro, fail_fn fail) {
 // first argument) in one launch on `stream`; table [kind][p - 1][n_u - 1] are the law's kernels,
 // nbr its root adjacency (or nullptr: the serial walk).
 template <class Law>
-int rollout_run(RolloutAttach& ro, fail_fn fail, int device, hipStream_t stream, const Law& law,
-                int p, int n_u, const int32_t* nbr,
+int rollout_run(RolloutAttach& ro, ehm_err_channel& err, int device, hipStream_t stream,
+                const Law& law, int p, int n_u, const int32_t* nbr,
                 void (*const (&table)[PK_KINDS][8][EHM_R_MAX_NU])(Law, DevPlant, RollArgs, DevNoise,
                                                                   DevGuard),
                 int64_t n, int32_t T, const double* x0, const double* d, const double* v,
@@ -695,22 +692,23 @@ int rollout_run(RolloutAttach& ro, fail_fn fail, int device, hipStream_t stream,
                 const NoisyCall* nz) {
     if (!x0 || !x_final || !steps || !status || !cost || !u_norm_sum || !max_violation || n < 0 ||
         T < 0 || !(tol_exit >= 0.0))
-        return fail(EHM_E_INVALID, "rollout: bad argument");
-    if (!ro.plant) return fail(EHM_E_INVALID, "rollout: no plant (set_plant)");
+        return err.fail(EHM_E_INVALID, "rollout: bad argument");
+    if (!ro.plant) return err.fail(EHM_E_INVALID, "rollout: no plant (set_plant)");
     if (d && ro.pl.n_d == 0)
-        return fail(EHM_E_INVALID, "rollout: a disturbance was given but the plant has no E");
+        return err.fail(EHM_E_INVALID, "rollout: a disturbance was given but the plant has no E");
     // a plant set after the model may have grown past what set_noise checked
     if (nz && ro.kind == PK_GUARDED)
-        return fail(EHM_E_INVALID, "rollout_noisy: the plant is guarded (noisy guarded plants "
-                                   "are not supported)");
+        return err.fail(EHM_E_INVALID, "rollout_noisy: the plant is guarded (noisy guarded plants "
+                                       "are not supported)");
     if (nz && ro.pl.total + ro.nz.total > EHM_N_MAX_LDS)
-        return fail(EHM_E_INVALID, "rollout_noisy: plant and model take %d doubles of LDS (%d)",
-                    ro.pl.total + ro.nz.total, EHM_N_MAX_LDS);
+        return err.fail(EHM_E_INVALID, "rollout_noisy: plant and model take %d doubles of LDS (%d)",
+                        ro.pl.total + ro.nz.total, EHM_N_MAX_LDS);
     const int n_d = ro.pl.n_d;
     if (n == 0) return EHM_OK;
-    if (n > (int64_t)1 << 31) return fail(EHM_E_INVALID, "rollout: %lld trajectories", (long long)n);
+    if (n > (int64_t)1 << 31)
+        return err.fail(EHM_E_INVALID, "rollout: %lld trajectories", (long long)n);
     hipError_t e = hipSetDevice(device);
-    if (e != hipSuccess) return fail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return err.fail(EHM_E_HIP, "hipSetDevice: %s", hipGetErrorString(e));
     const size_t N = (size_t)n, nT = (size_t)T, D = sizeof(double), I = sizeof(int32_t);
     RollArgs R{};
     R.n = n;
@@ -747,22 +745,18 @@ int rollout_run(RolloutAttach& ro, fail_fn fail, int device, hipStream_t stream,
             std::memcpy(o.field, &o.buf.ptr, sizeof o.buf.ptr);
         }
     if (!ok)
-        return fail(EHM_E_HIP, "rollout: out of device memory for %lld x %d steps", (long long)n,
-                    (int)T);
-#define EHM_RUN_TRY(expr)                                                                  \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return fail(EHM_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));         \
-    } while (0)
+        return err.fail(EHM_E_HIP, "rollout: out of device memory for %lld x %d steps",
+                        (long long)n, (int)T);
     R.x0 = dx0.as<const double>();
     R.d = dd.as<const double>();
     R.v = dv.as<const double>();
     R.mode = ro.mode.as<const int32_t>();
     R.nbr = nbr;
-    EHM_RUN_TRY(hipMemcpyAsync(dx0.ptr, x0, N * p * D, hipMemcpyHostToDevice, stream));
-    if (d) EHM_RUN_TRY(hipMemcpyAsync(dd.ptr, d, nT * N * n_d * D, hipMemcpyHostToDevice, stream));
-    if (v) EHM_RUN_TRY(hipMemcpyAsync(dv.ptr, v, nT * N * p * D, hipMemcpyHostToDevice, stream));
+    EHM_HIP_TRY(err, hipMemcpyAsync(dx0.ptr, x0, N * p * D, hipMemcpyHostToDevice, stream));
+    if (d) EHM_HIP_TRY(err, hipMemcpyAsync(dd.ptr, d, nT * N * n_d * D, hipMemcpyHostToDevice,
+                                           stream));
+    if (v) EHM_HIP_TRY(err, hipMemcpyAsync(dv.ptr, v, nT * N * p * D, hipMemcpyHostToDevice,
+                                           stream));
     EventPair ev;
     (void)hipEventRecord(ev.e0, stream);
     DevNoise NZ{};
@@ -777,12 +771,12 @@ int rollout_run(RolloutAttach& ro, fail_fn fail, int device, hipStream_t stream,
                        dim3((unsigned)((n + 255) / 256)), dim3(256), lds, stream, law, ro.pl, R,
                        NZ, ro.gd);
     (void)hipEventRecord(ev.e1, stream);
-    EHM_RUN_TRY(hipGetLastError());
+    EHM_HIP_TRY(err, hipGetLastError());
     for (const Out& o : out)
         if (o.host)
-            EHM_RUN_TRY(hipMemcpyAsync(o.host, o.buf.ptr, o.bytes, hipMemcpyDeviceToHost, stream));
-    EHM_RUN_TRY(hipStreamSynchronize(stream));
-#undef EHM_RUN_TRY
+            EHM_HIP_TRY(err, hipMemcpyAsync(o.host, o.buf.ptr, o.bytes, hipMemcpyDeviceToHost,
+                                            stream));
+    EHM_HIP_TRY(err, hipStreamSynchronize(stream));
     ev.seconds(kernel_seconds);
     return EHM_OK;
 }

@@ -23,9 +23,7 @@ from ._capi import f64, ptr
 from .engine import FlatTree
 
 
-def _check(rc):
-    if rc != _capi.EHM_OK:
-        raise _capi.EhmError(rc, _capi.load().ehm_explicit_last_error().decode('utf-8', 'replace'))
+_check = _capi.checker('ehm_explicit_last_error')
 
 
 def node_commutation(nd):

@@ -30,9 +30,7 @@ MAX_P, MAX_NU = 8, 4
 CHUNK_BYTES = 768 << 20
 
 
-def _check(rc):
-    if rc != _capi.EHM_OK:
-        raise _capi.EhmError(rc, _capi.load().ehm_implicit_last_error().decode('utf-8', 'replace'))
+_check = _capi.checker('ehm_implicit_last_error')
 
 
 def check_args(oracle, plant):

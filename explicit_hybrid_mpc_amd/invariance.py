@@ -41,10 +41,7 @@ STATUS_NAMES = ('invariant', 'exits', 'mode_region', 'no_mode', 'no_cell')
 MAX_D = 8                       # EHM_R_MAX_D: 2^8 corners
 
 
-def _check(rc):
-    if rc != _capi.EHM_OK:
-        raise _capi.EhmError(rc, _capi.load().ehm_invariance_last_error().decode('utf-8',
-                                                                                 'replace'))
+_check = _capi.checker('ehm_invariance_last_error')
 
 
 def roots_convex(root_vertices, rtol=1e-9):

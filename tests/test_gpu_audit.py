@@ -224,6 +224,47 @@ def test_a_broken_leaf_is_found(cases, kind):
             assert res.worst['leaf'] != L and res.histogram[0] >= hit.sum()
 
 
+def test_a_nan_ratio_is_binned_and_never_the_worst(cases):
+    """Leaf L_nan (cell 0) has NaN vertex costs, leaf L_bad (cell 30) is raised by 3 B as in
+    test_a_broken_leaf_is_found.  With 4 samples per leaf, sample 0 -- slot 0 of the first
+    256-sample workgroup, which also holds L_bad's samples 120 .. 123 -- has a NaN ratio: it is
+    status 2 and counted in bin 0, and the worst sample is the mirror's (np.nanmax, the smallest
+    id), a sample of L_bad, whatever the chunk."""
+    c = cases('lin')
+    flat = c.flat
+    node = c.law.cells()['node']
+    assert node.size >= 64 and (flat.flags[node[[0, 30]]] & 1).all()
+    L_nan, L_bad = int(node[0]), int(node[30])
+    B = max(c.orc.eps_a, c.orc.eps_r * float(np.max(flat.vertex_costs[L_bad])))
+    costs = np.array(flat.vertex_costs)
+    costs[L_nan] = np.nan
+    costs[L_bad] += 3. * B
+    law = _with_costs(c, costs)
+    runs = [law.audit(per_leaf=4, seed=3, return_samples=True, chunk=chunk)
+            for chunk in (0, 256, 100)]
+    law.close()
+    res = runs[0]
+    print('samples', res.n, 'worst', res.worst['id'], res.worst['leaf'], res.max_ratio)
+    nan = res.leaf == L_nan
+    assert res.cell[0] == 0 and nan[0] and np.isnan(res.vbar[nan]).all()
+    assert (res.status[nan] == 2).all() and res.counts['negative'] == nan.sum()
+    closed = (flat.flags[res.leaf] & 1).astype(bool)
+    st, ratio = ac.statuses(res.vbar, res.vstar, closed, res.delta_idx, c.orc.eps_a, c.orc.eps_r,
+                            1e-7)
+    assert np.array_equal(res.status, st) and np.isnan(ratio[nan]).all()
+    counts, hist, best, worst = ac.summary(np.arange(res.n), st, ratio)
+    assert np.array_equal(res.histogram, hist)
+    # bin 0 holds the NaN ratios
+    assert res.histogram[0] >= nan.sum()
+    assert res.worst['id'] == worst and res.max_ratio == best and best >= 3.
+    assert res.worst['leaf'] == res.leaf[worst] == L_bad
+    for other in runs[1:]:
+        assert other.counts == res.counts and np.array_equal(other.histogram, res.histogram)
+        assert other.worst['id'] == res.worst['id'] and other.max_ratio == res.max_ratio
+        assert other.worst['leaf'] == res.worst['leaf']
+        assert np.array_equal(other.status, res.status)
+
+
 def test_open_leaves_are_counted_not_passed(cases):
     from explicit_hybrid_mpc_amd import engine, explicit, partition
     c = cases('lin')

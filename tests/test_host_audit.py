@@ -4,10 +4,17 @@ construction, on a hand-made two-leaf tree, and the status logic on hand-made ro
 what tests/test_gpu_audit.py holds the device to.
 """
 
+import os
+import shutil
+import subprocess
+
 import numpy as np
 import pytest
 
+from tests import applied_cpu as apc
 from tests import audit_cpu as ac
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # the unit square cut along its diagonal: two leaves of volume 1/2
 CELLS = np.array([[[0., 0.], [1., 0.], [1., 1.]],
@@ -142,3 +149,57 @@ def test_forest_order_numbers_the_roots_first_then_breadth_first():
     spine = np.zeros(11, dtype=bool)
     spine[[0, 2]] = True
     assert explicit.forest_order(left, right, spine).tolist() == [1, 3, 4, 5, 6, 7, 8, 9, 10]
+
+
+def test_verdict_rules_under_the_sanitizers_match_the_mirrors(tmp_path):
+    """csrc/ehm_verdict.h and csrc/ehm_err.h driven by a stand-alone program built with the address
+    and undefined-behaviour sanitizers: its own checks (the ladder at its thresholds, the bins, the
+    host merge, a message longer than the channel's buffer), and its ladder and bins on rows that
+    the two numpy mirrors judge too -- the C++ rules pinned to tests/audit_cpu.py and
+    tests/applied_cpu.py."""
+    cxx = shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
+    if cxx is None:
+        pytest.skip('no host C++ compiler')
+    exe = str(tmp_path / 'verdict_host_main')
+    src = os.path.join(ROOT, 'tests', 'native', 'verdict_host_main.cpp')
+    subprocess.run([cxx, '-std=c++17', '-O1', '-g', '-ffp-contract=off',
+                    '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-Wall', '-Wextra',
+                    '-Werror', src, '-o', exe], check=True, capture_output=True, text=True)
+    # the ladder: V* = 0 makes bound = eps_a and slack = rtol, so the gaps are the thresholds
+    # themselves and their neighbours; then rows whose gap rounds
+    eps_a, eps_r, rtol = 0.25, 0.5, 1e-7
+    inf = np.inf
+    gaps = [-rtol, np.nextafter(-rtol, 0.), np.nextafter(-rtol, -inf), eps_a + rtol,
+            np.nextafter(eps_a + rtol, 0.), np.nextafter(eps_a + rtol, inf), 0., -0., np.nan, inf,
+            -inf, eps_a]
+    rows = [(g, 0., eps_a, eps_r, rtol) for g in gaps]
+    rng = np.random.default_rng(7)
+    vs = rng.uniform(0.1, 4., 64)
+    rows += [(v + g, v, eps_a, eps_r, rtol) for v, g in zip(vs, rng.uniform(-0.5, 3., 64))]
+    rows += [(1., 1., 0., 0., rtol), (2., 1., 0., 0., rtol)]      # 0 / 0 and 1 / 0 at eps = 0
+    ratios = [-0., 0., 1. / 32., 31. / 32., np.nextafter(1., 0.), 1., np.nextafter(1., 2.), inf,
+              -inf, np.nan, 0.5, np.nextafter(0.5, 0.)]
+    text = ''.join('j ' + ' '.join(float(x).hex() for x in r) + '\n' for r in rows)
+    text += ''.join('b %s\n' % float(r).hex() for r in ratios)
+    out = subprocess.run([exe], input=text, capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    lines = out.stdout.split('\n')
+    assert lines[len(rows) + len(ratios)] == 'verdict host rules: ok'
+    vbar, vstar = np.array([r[0] for r in rows]), np.array([r[1] for r in rows])
+    n = len(rows)
+    for k in range(n):
+        e_a, e_r = rows[k][2], rows[k][3]
+        st, ratio = ac.statuses(vbar[k:k + 1], vstar[k:k + 1], [True], [0], e_a, e_r, rtol)
+        _, st_u, ratio_u = apc.statuses(vbar[k:k + 1], np.zeros(1), vstar[k:k + 1], [0], [0], [0],
+                                        e_a, e_r, rtol)
+        got_st, got_bin, got_r = lines[k].split()
+        assert int(got_st) == st[0] == st_u[0], (rows[k], lines[k])
+        assert np.array_equal(np.array([float.fromhex(got_r)]), ratio, equal_nan=True)
+        assert np.array_equal(ratio, ratio_u, equal_nan=True)
+        hist = ac.summary([0], np.zeros(1, dtype=np.int32), ratio)[1]
+        hist_u = apc.summary([0], np.zeros(1, dtype=np.int32), ratio_u)[1]
+        assert hist[int(got_bin)] == 1 == hist_u[int(got_bin)], (rows[k], lines[k])
+    for k, r in enumerate(ratios):
+        hist = ac.summary([0], np.zeros(1, dtype=np.int32), np.array([r]))[1]
+        assert hist[int(lines[n + k])] == 1, (r, lines[n + k])
+    assert [int(v) for v in lines[n:n + 10]] == [0, 0, 1, 31, 31, 31, 32, 32, 0, 0]
