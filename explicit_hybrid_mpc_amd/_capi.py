@@ -63,6 +63,7 @@ EXPORTED = [
     'ehm_certify_abi_sizes',
     'ehm_compiled_reduce', 'ehm_reduce_last_error',
     'ehm_compiled_successors', 'ehm_invariance_last_error', 'ehm_invariance_abi_sizes',
+    'ehm_compiled_core', 'ehm_core_last_error', 'ehm_core_abi_sizes',
 ]
 EHM_AUDIT_MODES = {'uniform': 0, 'per_leaf': 1}     # EHM_AUDIT_UNIFORM / _PER_LEAF
 EHM_COMPILE_SPINE_ROOTS = 1     # ehm_compiled_create_opts
@@ -293,6 +294,24 @@ class InvarianceLeaves(ctypes.Structure):
                                                'x_next', 'succ_root', 'succ_leaf')]
 
 
+class CoreOpts(ctypes.Structure):
+    _fields_ = [('status', ctypes.c_void_p), ('n_status', ctypes.c_int64),
+                ('max_edges', ctypes.c_int64), ('tol_side', ctypes.c_double),
+                ('max_fan', ctypes.c_int32), ('rows', ctypes.c_int32),
+                ('want_edges', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
+class CoreResult(ctypes.Structure):
+    _fields_ = [('counts', ctypes.c_int64 * 7), ('n_edges', ctypes.c_int64),
+                ('n_sweeps', ctypes.c_int64), ('core_volume', ctypes.c_double),
+                ('cell_volume', ctypes.c_double), ('seconds_reach', ctypes.c_double),
+                ('seconds_sweeps', ctypes.c_double)]
+
+
+class CoreLeaves(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ('level', 'status', 'indptr', 'indices_out')]
+
+
 _lib = None
 
 
@@ -326,7 +345,8 @@ def load(build_if_missing=True):
              "applied-input audit's "),
             ('ehm_certify_abi_sizes', (CertifyOpts, CertifyResult, CertifyLeaves), "certificate's "),
             ('ehm_invariance_abi_sizes', (InvarianceOpts, InvarianceResult, InvarianceLeaves),
-             "successors' ")):
+             "successors' "),
+            ('ehm_core_abi_sizes', (CoreOpts, CoreResult, CoreLeaves), "invariant core's ")):
         sizes = (i64 * len(mirrors))()
         fn = getattr(lib, getter)
         fn.argtypes = [vp, i32]
@@ -350,6 +370,10 @@ def load(build_if_missing=True):
                                             ctypes.POINTER(InvarianceResult),
                                             ctypes.POINTER(InvarianceLeaves)]
     lib.ehm_invariance_last_error.restype = ctypes.c_char_p
+    lib.ehm_compiled_core.argtypes = [vp, ctypes.POINTER(InvarianceOpts),
+                                      ctypes.POINTER(CoreOpts), ctypes.POINTER(CoreResult),
+                                      ctypes.POINTER(CoreLeaves)]
+    lib.ehm_core_last_error.restype = ctypes.c_char_p
     lib.ehm_explicit_set_costs.argtypes = [vp, vp, vp]
     lib.ehm_explicit_sample.argtypes = [vp, ctypes.POINTER(AuditOpts), vp, vp]
     lib.ehm_explicit_audit.argtypes = [vp, vp, ctypes.POINTER(AuditOpts),
@@ -450,7 +474,7 @@ def load(build_if_missing=True):
                         'ehm_explicit_last_error', 'ehm_implicit_last_error',
                         'ehm_compiled_last_error', 'ehm_applied_last_error',
                         'ehm_certify_last_error', 'ehm_reduce_last_error',
-                        'ehm_invariance_last_error'):
+                        'ehm_invariance_last_error', 'ehm_core_last_error'):
             fn.restype = i32
     lib.ehm_search_last_error.restype = ctypes.c_char_p
     lib.ehm_search_create.argtypes = [i32, i32, i32, ctypes.POINTER(vp)]

@@ -698,6 +698,40 @@ class CompiledLaw:
                                      tol_exit=tol_exit, return_successors=return_successors,
                                      chunk=chunk)
 
+    # -- the leaves the closed loop never leaves (invariance.py) -----------------
+    def invariant_core(self, plant=None, d_box=None, tol_exit=1e-9, tol_side=None,
+                       rows='invariant', return_edges=False, max_fan=None, max_edges=None):
+        """
+        From which leaves is it safe to start?  ``successors`` judges one step; this follows the
+        steps after it.  The MAY-REACH relation lists, for every leaf, the leaves the image of
+        that leaf -- under the law, the plant and every disturbance of ``d_box`` -- can land in;
+        it is a superset of what the evaluator can return for any state of the leaf.  The CORE is
+        the largest set of leaves that is closed under it and holds no leaf that fails the
+        one-step test (``tol_exit``): where the set is convex (``set_convex``), every state of a
+        core leaf stays in the set, in its mode's region and in a core leaf for ever.  A leaf
+        outside the core has a ``level``: 0 for a leaf that fails the one-step test, k for one
+        that can reach level k - 1, so its states have k safe steps.  The relation is a superset,
+        so the core is an inner approximation: leaves next to a leaking leaf are lost
+        conservatively.
+
+        ``tol_side`` (default ``tol_exit``; keep it >= ``tol_exit``) is the slack of every side
+        decision, in the units of the planes (half the bisected edge) and of the roots' weights;
+        it has to cover the rounding of the sums the decisions are made on.  ``rows``:
+        ``'invariant'`` builds the rows the fixed point needs, ``'all'`` those of every leaf with
+        a cell and a mode (the transition graph of the whole law).  ``return_edges``: also the
+        relation as CSR.  ``max_fan`` (default ``invariance.MAX_FAN``): a longer row is cut off
+        and its leaf is a seed with status ``unresolved``; ``max_edges`` (``invariance.MAX_EDGES``):
+        a relation with more edges is an ``EhmError`` that names the total.  Always the whole law:
+        a fixed point over some of the leaves means nothing.  Covered and not covered: as
+        ``successors``.  Refusals as ``successors``.  Returns an ``invariance.CoreResult``.
+        """
+        from . import invariance
+        return invariance.invariant_core(
+            self, plant=plant, d_box=d_box, tol_exit=tol_exit, tol_side=tol_side, rows=rows,
+            return_edges=return_edges,
+            max_fan=invariance.MAX_FAN if max_fan is None else max_fan,
+            max_edges=invariance.MAX_EDGES if max_edges is None else max_edges)
+
     def __call__(self, x):
         """(u, t): the input for state x and the evaluation time, as the reference's call."""
         tic = time.time()

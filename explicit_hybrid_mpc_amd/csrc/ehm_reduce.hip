@@ -21,6 +21,7 @@
 //                      leaf that stands for every leaf
 //   k_reduce_scan      order-preserving compaction: exclusive sums of the survivors (blocks of 1024,
 //   k_reduce_scan_add  the block sums scanned the same way), so children still follow their parents
+//                      (ehm_scan_dev.h)
 //   k_reduce_rewrite   renumbers children and root entries, gathers the leaf records, leaf_node and
 //                      leaf_mode, and writes the new leaf of every original leaf
 //
@@ -41,11 +42,9 @@
 #include "../../include/ehmpc.h"
 #include "ehm_cells_dev.h"
 #include "ehm_reduce_host.h"
+#include "ehm_scan_dev.h"
 
 #define EHM_RED_BLOCK 64            // k_reduce_flags: the cell of P = 8 takes 144 registers
-#define EHM_RED_SCAN_BLOCK 256
-#define EHM_RED_SCAN_ITEMS 4
-#define EHM_RED_SCAN_TILE (EHM_RED_SCAN_BLOCK * EHM_RED_SCAN_ITEMS)
 
 namespace {
 
@@ -175,43 +174,6 @@ __global__ void k_reduce_survive(long long n_int, long long n_leaf, Parents P,
     }
 }
 
-// out [n]: the exclusive sums of in [n] within tiles of 1024; sums [tiles]: the tiles' totals
-__global__ __launch_bounds__(EHM_RED_SCAN_BLOCK) void k_reduce_scan(
-    long long n, const int32_t* __restrict__ in, int32_t* __restrict__ out,
-    int32_t* __restrict__ sums) {
-    __shared__ int32_t sh[EHM_RED_SCAN_BLOCK];
-    const int t = threadIdx.x;
-    const long long base = (long long)blockIdx.x * EHM_RED_SCAN_TILE + (long long)t * EHM_RED_SCAN_ITEMS;
-    int32_t v[EHM_RED_SCAN_ITEMS];
-    int32_t local = 0;
-#pragma unroll
-    for (int j = 0; j < EHM_RED_SCAN_ITEMS; ++j) {
-        v[j] = base + j < n ? in[base + j] : 0;
-        local += v[j];
-    }
-    sh[t] = local;
-    __syncthreads();
-    for (int off = 1; off < EHM_RED_SCAN_BLOCK; off <<= 1) {
-        const int32_t x = t >= off ? sh[t - off] : 0;
-        __syncthreads();
-        sh[t] += x;
-        __syncthreads();
-    }
-    int32_t run = sh[t] - local;
-#pragma unroll
-    for (int j = 0; j < EHM_RED_SCAN_ITEMS; ++j) {
-        if (base + j < n) out[base + j] = run;
-        run += v[j];
-    }
-    if (t == EHM_RED_SCAN_BLOCK - 1) sums[blockIdx.x] = sh[t];
-}
-
-__global__ void k_reduce_scan_add(long long n, int32_t* __restrict__ out,
-                                  const int32_t* __restrict__ offs) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] += offs[i / EHM_RED_SCAN_TILE];
-}
-
 template <class T>
 struct RewriteArgs {
     long long n_int, n_leaf, n_roots;
@@ -276,27 +238,6 @@ const flags32_fn k_flags32[EHM_CP] = EHM_RED_ALL(float);
 #undef EHM_RED_ALL
 
 thread_local ehm_err_channel r_err;
-
-// out [n] = the exclusive sums of in [n] on the device
-int exclusive_scan(hipStream_t stream, const int32_t* in, int32_t* out, long long n) {
-    const long long tiles = (n + EHM_RED_SCAN_TILE - 1) / EHM_RED_SCAN_TILE;
-    DevBuf sums, offs;
-    EHM_HIP_TRY(r_err, sums.alloc((size_t)tiles * sizeof(int32_t)));
-    hipLaunchKernelGGL(k_reduce_scan, dim3((unsigned)tiles), dim3(EHM_RED_SCAN_BLOCK), 0, stream,
-                       n, in, out, sums.as<int32_t>());
-    EHM_HIP_TRY(r_err, hipGetLastError());
-    if (tiles > 1) {
-        EHM_HIP_TRY(r_err, offs.alloc((size_t)tiles * sizeof(int32_t)));
-        const int rc = exclusive_scan(stream, sums.as<const int32_t>(), offs.as<int32_t>(), tiles);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_reduce_scan_add, dim3(blocks_of(n, 256)), dim3(256), 0, stream,
-                           n, out, offs.as<const int32_t>());
-        EHM_HIP_TRY(r_err, hipGetLastError());
-    }
-    // the buffers are freed on return: hipFree waits for the work that uses them
-    EHM_HIP_TRY(r_err, hipStreamSynchronize(stream));
-    return EHM_OK;
-}
 
 template <class T>
 int reduce_law(ehm_compiled* law, const ehm_compiled_view& v, hipStream_t stream,
@@ -369,10 +310,10 @@ int reduce_law(ehm_compiled* law, const ehm_compiled_view& v, hipStream_t stream
                        d_rep.as<const int32_t>(), d_keep_int.as<int32_t>(),
                        d_keep_leaf.as<int32_t>(), d_target.as<int32_t>());
     EHM_HIP_TRY(r_err, hipGetLastError());
-    int rc = exclusive_scan(stream, d_keep_int.as<const int32_t>(), d_new_int.as<int32_t>(),
+    int rc = exclusive_scan(r_err, stream, d_keep_int.as<const int32_t>(), d_new_int.as<int32_t>(),
                             n_int + 1);
     if (rc) return rc;
-    rc = exclusive_scan(stream, d_keep_leaf.as<const int32_t>(), d_new_leaf.as<int32_t>(),
+    rc = exclusive_scan(r_err, stream, d_keep_leaf.as<const int32_t>(), d_new_leaf.as<int32_t>(),
                         n_leaf + 1);
     if (rc) return rc;
     int32_t m_int = 0, m_leaf = 0;

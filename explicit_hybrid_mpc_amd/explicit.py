@@ -521,6 +521,22 @@ class ExplicitMPC:
         finally:
             law.close()
 
+    def invariant_core(self, spine='roots', dtype=np.float64, flush=False, **kw):
+        """
+        ``CompiledLaw.invariant_core`` (invariance.py) for this law: compiles it
+        (``compile(spine=spine, dtype=dtype, flush=flush)``) and finds the leaves the closed loop
+        never leaves; ``kw`` as ``CompiledLaw.invariant_core``.  Returns its
+        ``invariance.CoreResult``, whose ``contains`` needs the compiled law and is not available
+        here.
+        """
+        law = self.compile(dtype=dtype, spine=spine, flush=flush)
+        try:
+            res = law.invariant_core(**kw)
+            res._law = None
+            return res
+        finally:
+            law.close()
+
     def node_modes(self, plant):
         """int32 [n_nodes]: step-0 mode of every node's commutation (-1: none); all 0 for a
         single-mode plant."""

@@ -1,5 +1,6 @@
 """
-One-step invariance of a compiled law leaf by leaf (csrc/ehm_invariance.hip):
+One-step invariance of a compiled law leaf by leaf (csrc/ehm_invariance.hip), and the
+leaves the closed loop never leaves (csrc/ehm_core.hip; ``invariant_core`` below):
 
     res = law.successors()                      # SuccessorResult of every leaf, nominal successor
     res = law.successors(d_box=(lo, hi))        # under every disturbance of the box
@@ -39,9 +40,19 @@ from ._capi import ptr
 
 STATUS_NAMES = ('invariant', 'exits', 'mode_region', 'no_mode', 'no_cell')
 MAX_D = 8                       # EHM_R_MAX_D: 2^8 corners
+# ``CoreResult.status``: the one-step status, and ``unresolved`` for a leaf whose row was cut off
+CORE_STATUS_NAMES = STATUS_NAMES + ('unresolved',)
+CORE_COUNT_NAMES = ('core', 'transient') + CORE_STATUS_NAMES[1:]
+CORE_ROWS = {'invariant': 0, 'all': 1}          # EHM_CORE_ROWS_*
+# Resource caps of ``invariant_core``.  A row longer than MAX_FAN is cut off (its leaf is a seed);
+# the relation takes 4 bytes per edge on the device, and as much on the host with return_edges:
+# 512 MiB at MAX_EDGES.
+MAX_FAN = 4096
+MAX_EDGES = 1 << 27
 
 
 _check = _capi.checker('ehm_invariance_last_error')
+_check_core = _capi.checker('ehm_core_last_error')
 
 
 def roots_convex(root_vertices, rtol=1e-9):
@@ -232,3 +243,109 @@ def successors(law, plant=None, d_box=None, leaves=None, tol_exit=1e-9, return_s
         worst_margin=float(res.worst_margin), seconds=float(res.seconds),
         set_convex=bool(law._set_convex), tol_exit=tol_exit,
         holds_on_set=bool(counts['invariant'] == n and every and law._set_convex), **arrays)
+
+
+class CoreResult:
+    """
+    What ``CompiledLaw.invariant_core`` found.  Per leaf: ``level`` int32 (-1 for
+    a core leaf, 0 for a seed, k >= 1 for a leaf whose every state has its first k successors in
+    the set and in its mode's region), ``core`` bool, ``status`` int32 (the one-step status of
+    ``successors``, CORE_STATUS_NAMES: ``unresolved`` where the leaf's row was longer than
+    ``max_fan``).  ``counts`` by CORE_COUNT_NAMES (core, transient = level >= 1, then the seeds by
+    status); ``core_volume_fraction`` and ``cell_volume_fraction`` over the roots' volume;
+    ``n_sweeps`` = the largest level + 1; ``n_edges``; ``set_convex``; ``holds``: the set is convex
+    and the core is not empty -- every state of a core leaf then stays in the set, in its mode's
+    region and in the core for ever, under the assumptions of ``successors``.  ``seeds`` is the
+    ``SuccessorResult`` the seeds came from.  With ``return_edges``: ``indptr`` int64 [n_leaf + 1]
+    and ``indices`` int32, the may-reach relation as CSR (row order: roots ascending, left before
+    right).  ``seconds_reach`` (device time of the relation), ``seconds_sweeps`` (wall time of the
+    fixed point).
+    """
+
+    indptr = indices = None
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        return 'CoreResult(counts=%r, core_volume_fraction=%.6g, n_sweeps=%d, n_edges=%d, ' \
+            'set_convex=%s, holds=%s)' % (self.counts, self.core_volume_fraction, self.n_sweeps,
+                                          self.n_edges, self.set_convex, self.holds)
+
+    def contains(self, X):
+        """bool [n]: the leaf the law evaluates X [n, p] in is a core leaf; False where the law has
+        no input for the state.  ``evaluate`` answers for every state, so for one outside the set
+        this is the answer for the leaf the walk from the last root ends in: ask ``rollout`` or
+        the roots whether the state is in the set."""
+        if getattr(self, '_law', None) is None or not getattr(self._law, '_handle', None):
+            raise ValueError('contains needs the compiled law the result was made for, open')
+        u, leaf, _, _ = self._law.evaluate(X, return_info=True)
+        row = np.searchsorted(self._law.leaf_node, leaf)
+        return self.core[row] & np.isfinite(u).all(axis=1)
+
+
+def invariant_core(law, plant=None, d_box=None, tol_exit=1e-9, tol_side=None, rows='invariant',
+                   return_edges=False, max_fan=MAX_FAN, max_edges=MAX_EDGES):
+    """The one path to ``ehm_compiled_core``; see ``CompiledLaw.invariant_core``."""
+    from . import simulate
+    if rows not in CORE_ROWS:
+        raise ValueError("rows must be 'invariant' or 'all'")
+    if not float(tol_exit) >= 0.:
+        raise ValueError('tol_exit must be >= 0')
+    tol_side = float(tol_exit) if tol_side is None else float(tol_side)
+    max_fan, max_edges = int(max_fan), int(max_edges)
+    if not tol_side >= 0.:
+        raise ValueError('tol_side must be >= 0')
+    if max_fan < 1 or not 1 <= max_edges < 2 ** 31:
+        raise ValueError('max_fan must be >= 1 and max_edges in 1 .. 2^31 - 1')
+    seeds = successors(law, plant=plant, d_box=d_box, tol_exit=tol_exit)
+    if plant is None:
+        plant = law._rollout_plant
+    if plant is None:
+        plant = simulate.Plant.from_mpc(law.mpc)
+    lo, hi = _box(plant, d_box)
+    n_leaf = law._h['n_leaf']
+    n_d = 0 if lo is None else plant.n_d
+    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+    A, B, w, E = (f64(a) for a in (plant.A, plant.B, plant.w, plant.E))
+    modes = np.ascontiguousarray(law._plant_modes(plant), dtype=np.int32)
+    roots = law._root_cells
+    po = _capi.InvarianceOpts(
+        n=0, root_vertices=ptr(roots['vertices']), A=ptr(A), B=ptr(B), w=ptr(w),
+        E=ptr(E) if n_d and E.size else None, leaf_mode=ptr(modes),
+        d_lo=ptr(lo) if n_d else None, d_hi=ptr(hi) if n_d else None, tol_exit=float(tol_exit),
+        n_modes=int(plant.n_modes), n_d=n_d, n_g=0)
+    status_in = np.ascontiguousarray(seeds.status, dtype=np.int32)
+    co = _capi.CoreOpts(status=ptr(status_in), n_status=status_in.size, max_edges=max_edges,
+                        tol_side=tol_side, max_fan=max_fan, rows=CORE_ROWS[rows],
+                        want_edges=int(bool(return_edges)))
+    level, status = np.empty(n_leaf, np.int32), np.empty(n_leaf, np.int32)
+    indptr = np.empty(n_leaf + 1, np.int64) if return_edges else None
+    edges = ctypes.c_void_p(None)
+    lv = _capi.CoreLeaves(level=ptr(level), status=ptr(status), indptr=ptr(indptr),
+                          indices_out=ctypes.addressof(edges) if return_edges else None)
+    res = _capi.CoreResult()
+    lib = _capi.load()
+    indices = None
+    try:
+        _check_core(lib.ehm_compiled_core(law._handle, ctypes.byref(po), ctypes.byref(co),
+                                          ctypes.byref(res), ctypes.byref(lv)))
+        if return_edges:
+            n_e = int(res.n_edges)
+            indices = np.empty(n_e, np.int32)
+            if n_e:
+                ctypes.memmove(indices.ctypes.data, edges.value, n_e * 4)
+    finally:
+        if edges.value:
+            lib.ehm_host_free(edges)
+    total = float(roots['volume'].sum())
+    counts = {name: int(res.counts[k]) for k, name in enumerate(CORE_COUNT_NAMES)}
+    core = level < 0
+    return CoreResult(
+        level=level, core=core, status=status, counts=counts, seeds=seeds,
+        core_volume_fraction=float(res.core_volume) / total,
+        cell_volume_fraction=float(res.cell_volume) / total, n_sweeps=int(res.n_sweeps),
+        n_edges=int(res.n_edges), set_convex=bool(law._set_convex),
+        holds=bool(law._set_convex and core.any()), indptr=indptr, indices=indices,
+        seconds_reach=float(res.seconds_reach), seconds_sweeps=float(res.seconds_sweeps),
+        tol_exit=float(tol_exit), tol_side=tol_side, rows=rows, _law=law)

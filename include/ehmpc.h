@@ -1064,6 +1064,71 @@ const char* ehm_invariance_last_error(void);
  * order. */
 int ehm_invariance_abi_sizes(int64_t* sizes, int32_t n);
 
+/* ---- the invariant core of a compiled law (csrc/ehm_core.hip) ---------------------
+ * (no counterpart in the reference)
+ *
+ * The may-reach relation between the leaves and its fixed point.  On a leaf L with mode m the image
+ * under every disturbance of the box is I(L) = hull{y_i} + E [d_lo, d_hi], y_i the p + 1 vertex
+ * successors of ehm_compiled_successors before the disturbance (its step 4, bit for bit).  An affine
+ * f = g . x + h has over I(L) the maximum max_i f(y_i) + sum_k max(gE_k d_lo_k, gE_k d_hi_k),
+ * gE_k = ((0 + g_0 E_0k) + ..), and the minimum with min in both places.
+ * `plant` is an ehm_invariance_opts of which root_vertices, A, B, w, E, leaf_mode, d_lo, d_hi,
+ * n_modes and n_d are read (n_d up to 64 here: no corner is enumerated); the rest is ignored.
+ * The row of leaf l -- built when l has a cell and a mode and (rows = EHM_CORE_ROWS_ALL or
+ * status[l] = 0) -- lists, roots ascending and below a root left before right, every leaf reached by:
+ *  1. root r is a candidate iff its bounding box, widened per coordinate by (p + 1) tol_side times
+ *     its extent, meets the image's, and no barycentric weight of r (the sums of the [v0 | inv(E)]
+ *     record at the y_i, the rows of inv(E) as g) has its maximum over I(L) below -tol_side;
+ *  2. from the entry of a candidate: at a plane node with s = a . x + b visit the left child iff
+ *     smax >= -eps_T - tol_side - w, the right child iff smin < -eps_T + tol_side + w; eps_T is 2^-52
+ *     for a double law and 2^-23 for a single law, w = 0 for a double law and
+ *     (p + 3) 2^-24 ((0 + |a_0| X_0 + ..) + |b|) + 2^-126 for a single law, X_c the largest |x_c| of
+ *     the image's bounding box.
+ * A row longer than max_fan is cut off: it is empty and the leaf's status is 5 (unresolved).  If the
+ * rows together hold more than max_edges (at most 2^31 - 1) the call fails with EHM_E_CAPACITY and
+ * the message names the total.
+ * level [n_leaf]: 0 for a seed (status other than 0 after the above), k >= 1 for a leaf not of a
+ * lower level whose row names a leaf of level k - 1, -1 for the core, the leaves never reached.
+ * status [n_leaf]: the caller's with 5 where a row was cut off.  counts: core, level >= 1, then the
+ * seeds by status 1 .. 5.  n_sweeps = the largest level + 1.  core_volume and cell_volume through
+ * ehm_volume_batch, summed in leaf order.  seconds_reach: device time of the two passes of the
+ * relation; seconds_sweeps: wall time of the fixed point.  With want_edges: indptr [n_leaf + 1]
+ * (caller's) and *indices_out, the rows' leaves in page-locked memory the caller releases with
+ * ehm_host_free.
+ * EHM_E_INVALID as ehm_compiled_successors for the law, the plant and the box; for n_status other
+ * than the law's leaves, a status outside 0 .. 4, tol_side negative or NaN, max_fan < 1.  Errors
+ * through ehm_core_last_error. */
+#define EHM_CORE_ROWS_INVARIANT 0
+#define EHM_CORE_ROWS_ALL 1
+typedef struct ehm_core_opts {
+    const int32_t* status;          /* [n_status] the one-step status of every leaf            */
+    int64_t n_status;               /* must be the law's n_leaf                                */
+    int64_t max_edges;
+    double  tol_side;
+    int32_t max_fan, rows, want_edges, reserved;
+} ehm_core_opts;
+typedef struct ehm_core_result {
+    int64_t counts[7];
+    int64_t n_edges;
+    int64_t n_sweeps;
+    double  core_volume;
+    double  cell_volume;
+    double  seconds_reach;
+    double  seconds_sweeps;
+} ehm_core_result;
+typedef struct ehm_core_leaves {
+    int32_t*  level;                /* [n_leaf]                                                */
+    int32_t*  status;               /* [n_leaf]                                                */
+    int64_t*  indptr;               /* [n_leaf + 1], with want_edges                           */
+    int32_t** indices_out;          /* with want_edges                                         */
+} ehm_core_leaves;
+int ehm_compiled_core(ehm_compiled* law, const ehm_invariance_opts* plant,
+                      const ehm_core_opts* opts, ehm_core_result* result,
+                      const ehm_core_leaves* leaves);
+const char* ehm_core_last_error(void);
+/* ehm_abi_sizes for ehm_core_opts, ehm_core_result, ehm_core_leaves, in this order. */
+int ehm_core_abi_sizes(int64_t* sizes, int32_t n);
+
 /* ---- closed-loop simulation under the COMPILED law (csrc/ehm_compiled.hip) -------
  *
  * The entry points of the explicit law's rollout, argument for argument, on a compiled law -- also
