@@ -63,7 +63,7 @@ __global__ __launch_bounds__(EHM_APPLIED_BLOCK) void k_applied_reduce(
     unsigned long long* __restrict__ blk_id) {
 #pragma clang fp contract(off)
     __shared__ unsigned int cnt[EHM_APPLIED_COUNTERS];
-    ehm_verdict::counters_zero<EHM_APPLIED_BLOCK>(cnt);
+    ehm_verdict::counters_zero<EHM_APPLIED_BLOCK, EHM_APPLIED_COUNTERS>(cnt);
     __syncthreads();
     const long long q = (long long)blockIdx.x * EHM_APPLIED_BLOCK + threadIdx.x;
     double ratio = -INFINITY;
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(EHM_APPLIED_BLOCK) void k_applied_reduce(
         blk_ratio[blockIdx.x] = ratio;
         blk_id[blockIdx.x] = id;
     }
-    ehm_verdict::counters_flush<EHM_APPLIED_BLOCK>(cnt, counters);
+    ehm_verdict::counters_flush<EHM_APPLIED_BLOCK, EHM_APPLIED_COUNTERS>(cnt, counters);
 }
 
 thread_local ehm_err_channel a_err;

@@ -129,7 +129,7 @@ __global__ __launch_bounds__(EHM_AUDIT_BLOCK) void k_audit_reduce(
     double* __restrict__ blk_ratio, unsigned long long* __restrict__ blk_id) {
 #pragma clang fp contract(off)
     __shared__ unsigned int cnt[EHM_AUDIT_COUNTERS];
-    ehm_verdict::counters_zero<EHM_AUDIT_BLOCK>(cnt);
+    ehm_verdict::counters_zero<EHM_AUDIT_BLOCK, EHM_AUDIT_COUNTERS>(cnt);
     __syncthreads();
     const long long q = (long long)blockIdx.x * EHM_AUDIT_BLOCK + threadIdx.x;
     double ratio = -INFINITY;
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(EHM_AUDIT_BLOCK) void k_audit_reduce(
         blk_ratio[blockIdx.x] = ratio;
         blk_id[blockIdx.x] = id;
     }
-    ehm_verdict::counters_flush<EHM_AUDIT_BLOCK>(cnt, counters);
+    ehm_verdict::counters_flush<EHM_AUDIT_BLOCK, EHM_AUDIT_COUNTERS>(cnt, counters);
 }
 
 // what both entry points ask of opts; `audit`: also the fields the sampler alone does not read

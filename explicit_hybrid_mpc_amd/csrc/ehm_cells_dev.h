@@ -1,15 +1,19 @@
-// What ehm_certify.hip and ehm_reduce.hip share on the device: the parent
-// table of a compiled law, the cell of a leaf rebuilt from the law's own arrays with the cell in
-// registers, and the leaf's affine map at a vertex in the law's own arithmetic.  The rules
-// themselves are plain C++ in ehm_certify_host.h.  Every translation unit that includes this gets
-// its own copy (unnamed namespace), as of ehm_compiled_dev.h.
+// What ehm_certify.hip, ehm_reduce.hip, ehm_invariance.hip and ehm_core.hip share (DESIGN.md 3.8f
+// to 3.8i): the parent table of a compiled law, the cell of a leaf rebuilt from the law's own
+// arrays with the cell in registers, the leaf's affine map at a vertex in the law's own arithmetic
+// and the volumes of a chunk's cells; for the last two what they refuse of the plant they step a
+// leaf's vertices through and how they pack it.  The rules of the cells are plain C++ in
+// ehm_certify_host.h.  Every translation unit that includes this gets its own copy (unnamed
+// namespace), as of ehm_compiled_dev.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <type_traits>
+#include <vector>
 
 #include "ehm_certify_host.h"
 #include "ehm_compiled_dev.h"
@@ -205,6 +209,60 @@ __device__ __forceinline__ double leaf_map_at(const float* __restrict__ lr, int 
     for (int j = 0; j < P; ++j) xs[j] = (float)v[j];
     leaf_offset32<P>(lr, xs, d);
     return leaf_input32<P>(lr, n_u, c, d);
+}
+
+// What both entry points refuse of the plant of the step, the plant part of an
+// ehm_invariance_opts: the inputs, the modes, the box of at most max_d disturbances and its E.
+inline int check_step_plant(ehm_err_channel& err, const ehm_invariance_opts* o, int n_u, int max_d,
+                            const char* who) {
+    if (n_u > EHM_R_MAX_NU)
+        return err.fail(EHM_E_INVALID, "%s: n_u = %d, at most %d inputs", who, n_u,
+                        EHM_R_MAX_NU);
+    if (o->n_modes < 1 || o->n_modes > EHM_R_MAX_MODES)
+        return err.fail(EHM_E_INVALID, "%s: %d modes (1..%d)", who, (int)o->n_modes,
+                        EHM_R_MAX_MODES);
+    if (o->n_d < 0 || o->n_d > max_d)
+        return err.fail(EHM_E_INVALID, "%s: n_d = %d (0..%d)", who, (int)o->n_d, max_d);
+    if (o->n_d > 0 && !o->E)
+        return err.fail(EHM_E_INVALID, "%s: a box of %d disturbances but no E", who, (int)o->n_d);
+    if (o->n_d > 0 && (!o->d_lo || !o->d_hi))
+        return err.fail(EHM_E_INVALID, "%s: a required array is NULL", who);
+    for (int b = 0; b < o->n_d; ++b)
+        if (!std::isfinite(o->d_lo[b]) || !std::isfinite(o->d_hi[b]) || o->d_lo[b] > o->d_hi[b])
+            return err.fail(EHM_E_INVALID, "%s: the box is [%g, %g] on axis %d", who, o->d_lo[b],
+                            o->d_hi[b], b);
+    return EHM_OK;
+}
+
+// That plant's doubles into pk: A, B, w and E at pl's offsets, the box after them at o_lo, o_hi.
+inline void pack_step_plant(Pack& pk, DevPlant& pl, const ehm_invariance_opts* o, int p, int n_u,
+                            int& o_lo, int& o_hi) {
+    pl.n_modes = o->n_modes;
+    pl.n_d = o->n_d;
+    pl.oA = pk.put(o->A, (size_t)o->n_modes * p * p);
+    pl.oB = pk.put(o->B, (size_t)o->n_modes * p * n_u);
+    pl.ow = pk.put(o->w, (size_t)o->n_modes * p);
+    pl.oE = pk.put(o->E, (size_t)p * o->n_d);
+    o_lo = pk.put(o->d_lo, (size_t)o->n_d);
+    o_hi = pk.put(o->d_hi, (size_t)o->n_d);
+}
+
+// The volumes of the cells a chunk's positions `has` hold (cells [..][(p+1) p] by position):
+// vol[a] is that of position has[a].  ehm_volume_batch may leave another device current, so the
+// caller's is set again.
+inline int cell_volumes(ehm_err_channel& err, const char* who, int device, int p,
+                        const double* cells, const std::vector<long long>& has,
+                        std::vector<double>& vol) {
+    const size_t cell = (size_t)(p + 1) * p;
+    vol.resize(has.size());
+    if (has.empty()) return EHM_OK;
+    std::vector<double> packed(has.size() * cell);
+    for (size_t a = 0; a < has.size(); ++a)
+        std::memcpy(&packed[a * cell], cells + (size_t)has[a] * cell, cell * sizeof(double));
+    const int rc = ehm_volume_batch(device, (int64_t)has.size(), p, packed.data(), vol.data());
+    if (rc) return err.fail(rc, "%s: ehm_volume_batch: %s", who, ehm_last_error());
+    EHM_HIP_TRY(err, hipSetDevice(device));
+    return EHM_OK;
 }
 
 }  // namespace

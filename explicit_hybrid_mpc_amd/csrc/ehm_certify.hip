@@ -132,7 +132,7 @@ __global__ __launch_bounds__(EHM_CERT_JUDGE_BLOCK) void k_certify_judge(
     unsigned long long* __restrict__ counters, double* __restrict__ blk_t,
     long long* __restrict__ blk_i) {
     __shared__ unsigned int cnt[ehm_cert::CERT_STATUSES];
-    ehm_verdict::counters_zero<EHM_CERT_JUDGE_BLOCK>(cnt);
+    ehm_verdict::counters_zero<EHM_CERT_JUDGE_BLOCK, ehm_cert::CERT_STATUSES>(cnt);
     __syncthreads();
     const long long q = (long long)blockIdx.x * EHM_CERT_JUDGE_BLOCK + threadIdx.x;
     double tb = -INFINITY;
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(EHM_CERT_JUDGE_BLOCK) void k_certify_judge(
         blk_t[blockIdx.x] = tb;
         blk_i[blockIdx.x] = id;
     }
-    ehm_verdict::counters_flush<EHM_CERT_JUDGE_BLOCK>(cnt, counters);
+    ehm_verdict::counters_flush<EHM_CERT_JUDGE_BLOCK, ehm_cert::CERT_STATUSES>(cnt, counters);
 }
 
 typedef void (*cells64_fn)(CellArgs<double>);
@@ -517,17 +517,11 @@ int ehm_compiled_certify(ehm_compiled* law, ehm_problem* oracle, ehm_problem* ap
         todo.clear();
         for (long long q = 0; q < nc; ++q)
             if (hcell[q] == EHM_CELL_OK) todo.push_back(q);
-        if (!todo.empty()) {
-            R.resize(todo.size() * cell);
-            vsub.resize(todo.size());
-            for (size_t a = 0; a < todo.size(); ++a)
-                std::memcpy(&R[a * cell], &hvert[(size_t)todo[a] * cell], cell * sizeof(double));
-            rc = ehm_volume_batch(v.device, (int64_t)todo.size(), p, R.data(), vsub.data());
-            if (rc) return z_err.fail(rc, "certify: ehm_volume_batch: %s", ehm_last_error());
-            for (size_t a = 0; a < todo.size(); ++a) hvol[(size_t)todo[a]] = vsub[a];
-        }
+        rc = cell_volumes(z_err, "certify", v.device, p, hvert.data(), todo, vsub);
+        if (rc) return rc;
+        for (size_t a = 0; a < todo.size(); ++a) hvol[(size_t)todo[a]] = vsub[a];
         res->seconds[4] += wall_since(t0);
-        // the judgement
+        // the judgement (the oracles above may have left another device current)
         EHM_HIP_TRY(z_err, hipSetDevice(v.device));
         const unsigned nblk = blocks_of(nc, EHM_CERT_JUDGE_BLOCK);
         EHM_HIP_TRY(z_err, hipMemcpyAsync(dncand.ptr, hncand.data(), (size_t)nc * sizeof(int32_t),

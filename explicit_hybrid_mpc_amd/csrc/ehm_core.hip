@@ -9,7 +9,8 @@
 //   k_root_boxes   one thread per root: the bounding box of its vertices
 //   k_reach        one thread per leaf, templated on the law's scalar and on P, run twice (count, then
 //                  fill): the cell (leaf_cell), the inputs (leaf_map_at) and the y_i in the order of
-//                  k_successors, kept where the cell was; the image's box; the roots scanned serially
+//                  k_successors (a copy of its step: DESIGN.md 3.8i, Kernels, says why), kept where
+//                  the cell was; the image's box; the roots scanned serially
 //                  in ascending order, a root a candidate iff its box meets the image's and none of
 //                  its p + 1 weights has its maximum over I(L) below -tol_side; below a candidate a
 //                  stackless depth-first traversal, left where the plane's maximum allows the walk to
@@ -17,12 +18,13 @@
 //                  table, the decision of a node recomputed on the way back from its left child
 //   k_core_seed    level 0 for the leaves that fail the one-step test or have no row they asked for
 //   k_core_sweep   one thread per leaf without a level: level s if its row names a level < s
-//   k_core_counts  the leaves by outcome, integer atomics in LDS, then global
+//   k_core_counts  the leaves by outcome, through the LDS counters of ehm_verdict.h
 //
-// The plant and the box sit in LDS.  Every operation a decision depends on runs under
+// The plant and the box sit in LDS (plant_load).  Every operation a decision depends on runs under
 // fp contract(off) in a fixed order (tests/core_cpu.py is the numpy mirror); decisions are
 // comparisons, so the relation and the levels are the mirror's bit for bit.  The volumes are summed
-// on the host in leaf order.
+// on the host in leaf order; the chunk of the count pass, which sends the cells there, changes no
+// result.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,11 +37,12 @@
 #include "../../include/ehmpc.h"
 #include "ehm_cells_dev.h"
 #include "ehm_scan_dev.h"
+#include "ehm_verdict.h"
 
 #define EHM_CORE_BLOCK 64
 #define EHM_CORE_OUTCOMES 7
 #define EHM_CORE_MAX_D 64           // columns of E the box may have
-#define EHM_CORE_CHUNK 65536        // leaves per count pass (their cells go to the host)
+#define EHM_CORE_CHUNK 65536        // leaves per count pass (plant->chunk = 0)
 #define EHM_CORE_POLL 8             // sweeps between two reads of the change flag
 #define EHM_CORE_U32 5.9604644775390625e-08      // 2^-24: the single law's widening is (P + 3) of it
 #define EHM_CORE_TINY 1.1754943508222875e-38    // 2^-126: what underflow can add to it
@@ -358,7 +361,7 @@ __global__ __launch_bounds__(EHM_CORE_BLOCK) void k_reach(ReachArgs A, DevPlant 
     extern __shared__ __attribute__((aligned(16))) double sh[];
     unsigned long long* sum = reinterpret_cast<unsigned long long*>(sh + PL.total);
     const int t = threadIdx.x;
-    for (int i = t; i < PL.total; i += blockDim.x) sh[i] = PL.data[i];
+    plant_load(PL, sh);
     if (t == 0) *sum = 0ull;
     __syncthreads();
     const long long q = (long long)blockIdx.x * blockDim.x + t;
@@ -423,16 +426,15 @@ __global__ __launch_bounds__(256) void k_core_counts(long long n_leaf,
                                                      const int32_t* __restrict__ status,
                                                      unsigned long long* __restrict__ counters) {
     __shared__ unsigned int cnt[EHM_CORE_OUTCOMES];
-    const int t = threadIdx.x;
-    if (t < EHM_CORE_OUTCOMES) cnt[t] = 0;
+    ehm_verdict::counters_zero<256, EHM_CORE_OUTCOMES>(cnt);
     __syncthreads();
-    const long long l = (long long)blockIdx.x * blockDim.x + t;
+    const long long l = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (l < n_leaf) {
         const int lv = level[l];
         atomicAdd(&cnt[lv < 0 ? 0 : lv > 0 ? 1 : 1 + status[l]], 1u);
     }
     __syncthreads();
-    if (t < EHM_CORE_OUTCOMES && cnt[t]) atomicAdd(&counters[t], (unsigned long long)cnt[t]);
+    ehm_verdict::counters_flush<256, EHM_CORE_OUTCOMES>(cnt, counters);
 }
 
 typedef void (*reach_fn)(ReachArgs, DevPlant);
@@ -459,6 +461,7 @@ int ehm_core_abi_sizes(int64_t* sizes, int32_t n) {
 int ehm_compiled_core(ehm_compiled* law, const ehm_invariance_opts* o, const ehm_core_opts* co,
                       ehm_core_result* res, const ehm_core_leaves* lv) {
     if (!law || !o || !co || !res || !lv) return c_err.fail(EHM_E_INVALID, "core: bad argument");
+    if (o->chunk < 0) return c_err.fail(EHM_E_INVALID, "core: chunk < 0");
     if (!o->root_vertices || !o->A || !o->B || !o->w || !o->leaf_mode || !co->status)
         return c_err.fail(EHM_E_INVALID, "core: a required array is NULL");
     if (!lv->level || !lv->status)
@@ -476,21 +479,8 @@ int ehm_compiled_core(ehm_compiled* law, const ehm_invariance_opts* o, const ehm
     int rc = check_law_shape(c_err, v, "core");
     if (rc) return rc;
     const int p = v.p, n_u = v.n_u;
-    if (n_u > EHM_R_MAX_NU)
-        return c_err.fail(EHM_E_INVALID, "core: n_u = %d, at most %d inputs", n_u, EHM_R_MAX_NU);
-    if (o->n_modes < 1 || o->n_modes > EHM_R_MAX_MODES)
-        return c_err.fail(EHM_E_INVALID, "core: %d modes (1..%d)", (int)o->n_modes,
-                          EHM_R_MAX_MODES);
-    if (o->n_d < 0 || o->n_d > EHM_CORE_MAX_D)
-        return c_err.fail(EHM_E_INVALID, "core: n_d = %d (0..%d)", (int)o->n_d, EHM_CORE_MAX_D);
-    if (o->n_d > 0 && !o->E)
-        return c_err.fail(EHM_E_INVALID, "core: a box of %d disturbances but no E", (int)o->n_d);
-    if (o->n_d > 0 && (!o->d_lo || !o->d_hi))
-        return c_err.fail(EHM_E_INVALID, "core: a required array is NULL");
-    for (int b = 0; b < o->n_d; ++b)
-        if (!std::isfinite(o->d_lo[b]) || !std::isfinite(o->d_hi[b]) || o->d_lo[b] > o->d_hi[b])
-            return c_err.fail(EHM_E_INVALID, "core: the box is [%g, %g] on axis %d", o->d_lo[b],
-                              o->d_hi[b], b);
+    rc = check_step_plant(c_err, o, n_u, EHM_CORE_MAX_D, "core");
+    if (rc) return rc;
     const long long n_leaf = v.n_leaf;
     if (co->n_status != n_leaf)
         return c_err.fail(EHM_E_INVALID, "core: a status array of %lld for %lld leaves",
@@ -503,17 +493,10 @@ int ehm_compiled_core(ehm_compiled* law, const ehm_invariance_opts* o, const ehm
     if (lv->indices_out) *lv->indices_out = nullptr;
     if (n_leaf == 0) return EHM_OK;
     // the plant's doubles, the box after them
-    const int n_d = o->n_d;
     DevPlant pl{};
+    ReachArgs A{};
     Pack pk;
-    pl.n_modes = o->n_modes;
-    pl.n_d = n_d;
-    pl.oA = pk.put(o->A, (size_t)o->n_modes * p * p);
-    pl.oB = pk.put(o->B, (size_t)o->n_modes * p * n_u);
-    pl.ow = pk.put(o->w, (size_t)o->n_modes * p);
-    pl.oE = pk.put(o->E, (size_t)p * n_d);
-    const int o_lo = pk.put(o->d_lo, (size_t)n_d);
-    const int o_hi = pk.put(o->d_hi, (size_t)n_d);
+    pack_step_plant(pk, pl, o, p, n_u, A.o_lo, A.o_hi);
     pl.total = (int)pk.buf.size();
     const size_t plant_bytes = (size_t)pl.total * sizeof(double);
     const size_t lds = plant_bytes + sizeof(unsigned long long);
@@ -531,7 +514,8 @@ int ehm_compiled_core(ehm_compiled* law, const ehm_invariance_opts* o, const ehm
     EHM_HIP_TRY(c_err, d_status.upload(co->status, (size_t)n_leaf * sizeof(int32_t)));
     EHM_HIP_TRY(c_err, d_roots.upload(o->root_vertices, (size_t)v.n_roots * cell * sizeof(double)));
     EHM_HIP_TRY(c_err, d_box.alloc((size_t)v.n_roots * 2 * p * sizeof(double)));
-    const size_t cap = (size_t)std::min<long long>(EHM_CORE_CHUNK, n_leaf);
+    const long long chunk = o->chunk > 0 ? o->chunk : EHM_CORE_CHUNK;
+    const size_t cap = (size_t)std::min<long long>(chunk, n_leaf);
     EHM_HIP_TRY(c_err, d_vert.alloc(cap * cell * sizeof(double)));
     EHM_HIP_TRY(c_err, d_count.alloc((size_t)(n_leaf + 1) * sizeof(int32_t)));
     EHM_HIP_TRY(c_err, d_over.alloc((size_t)n_leaf * sizeof(int32_t)));
@@ -543,7 +527,6 @@ int ehm_compiled_core(ehm_compiled* law, const ehm_invariance_opts* o, const ehm
     hipLaunchKernelGGL(k_root_boxes, dim3(blocks_of(v.n_roots, 256)), dim3(256), 0, stream,
                        v.n_roots, p, d_roots.as<const double>(), d_box.as<double>());
     EHM_HIP_TRY(c_err, hipGetLastError());
-    ReachArgs A{};
     A.budget = 3 * v.n_int + 3;
     A.node = v.node;
     A.leaf_rec = v.leaf_rec;
@@ -558,9 +541,7 @@ int ehm_compiled_core(ehm_compiled* law, const ehm_invariance_opts* o, const ehm
     A.leaf_stride = v.leaf_stride;
     A.side_stride = v.side_stride;
     A.n_roots = (int)v.n_roots;
-    A.n_d = n_d;
-    A.o_lo = o_lo;
-    A.o_hi = o_hi;
+    A.n_d = o->n_d;
     A.rows_all = co->rows == EHM_CORE_ROWS_ALL;
     A.max_fan = co->max_fan;
     A.tol_side = co->tol_side;
@@ -575,11 +556,11 @@ int ehm_compiled_core(ehm_compiled* law, const ehm_invariance_opts* o, const ehm
                            A, pl);
     };
     // the count pass, chunk by chunk: the cells go to the host for their volumes
-    std::vector<double> hvert(cap * cell), R, vsub, volume((size_t)n_leaf, 0.0);
+    std::vector<double> hvert(cap * cell), vsub, volume((size_t)n_leaf, 0.0);
     std::vector<long long> has;
     EventPair ev;
-    for (long long off = 0; off < n_leaf; off += EHM_CORE_CHUNK) {
-        const long long nc = std::min<long long>(EHM_CORE_CHUNK, n_leaf - off);
+    for (long long off = 0; off < n_leaf; off += chunk) {
+        const long long nc = std::min<long long>(chunk, n_leaf - off);
         A.vertices = d_vert.as<double>();
         (void)hipEventRecord(ev.e0, stream);
         launch(off, nc);
@@ -595,16 +576,9 @@ int ehm_compiled_core(ehm_compiled* law, const ehm_invariance_opts* o, const ehm
         has.clear();
         for (long long q = 0; q < nc; ++q)
             if (hvert[(size_t)q * cell] == hvert[(size_t)q * cell]) has.push_back(q);
-        if (!has.empty()) {
-            R.resize(has.size() * cell);
-            vsub.resize(has.size());
-            for (size_t a = 0; a < has.size(); ++a)
-                std::memcpy(&R[a * cell], &hvert[(size_t)has[a] * cell], cell * sizeof(double));
-            rc = ehm_volume_batch(v.device, (int64_t)has.size(), p, R.data(), vsub.data());
-            if (rc) return c_err.fail(rc, "core: ehm_volume_batch: %s", ehm_last_error());
-            EHM_HIP_TRY(c_err, hipSetDevice(v.device));
-            for (size_t a = 0; a < has.size(); ++a) volume[(size_t)(off + has[a])] = vsub[a];
-        }
+        rc = cell_volumes(c_err, "core", v.device, p, hvert.data(), has, vsub);
+        if (rc) return rc;
+        for (size_t a = 0; a < has.size(); ++a) volume[(size_t)(off + has[a])] = vsub[a];
     }
     unsigned long long total = 0;
     EHM_HIP_TRY(c_err, hipMemcpy(&total, d_total.ptr, sizeof total, hipMemcpyDeviceToHost));

@@ -8,13 +8,16 @@
 //   k_successors   one thread per requested leaf, templated on the law's scalar and on P: the cell
 //                  and the leaf's map at its vertices (ehm_cells_dev.h), the region rows of the
 //                  leaf's mode at every vertex, the plant step in the order of rollout_apply
-//                  (ehm_rollout_dev.h), every successor located as one step of k_compiled_rollout
-//                  locates its state (the visibility walk from the leaf's own root, else the serial
-//                  rule; ehm_compiled_dev.h) and judged by its weights in that root; the counts by
-//                  integer atomics
+//                  (ehm_rollout_dev.h; k_reach of ehm_core.hip holds a copy of the step before the
+//                  disturbance: DESIGN.md 3.8i, Kernels, says why it is no shared function), every
+//                  successor located as one step of k_compiled_rollout locates its state (the
+//                  visibility walk from the leaf's own root, else the serial rule;
+//                  ehm_compiled_dev.h) and judged by its weights in that root; the counts by the
+//                  LDS counters of ehm_verdict.h
 //
-// The plant sits in LDS with the box after it.  The cell lives in registers as in k_certify_cells;
-// the vertex of a pass is picked out of it by selects, so the body is compiled once per (T, P).
+// The plant sits in LDS (plant_load) with the box after it.  The cell lives in registers as in
+// k_certify_cells; the vertex of a pass is picked out of it by selects, so the body is compiled
+// once per (T, P).
 // Every operation a result depends on runs under fp contract(off) in a fixed order
 // (tests/invariance_cpu.py is the numpy mirror).  The worst leaf and the volumes are taken on the
 // host in leaf order, so no result depends on the chunk.
@@ -31,6 +34,7 @@
 
 #include "../../include/ehmpc.h"
 #include "ehm_cells_dev.h"
+#include "ehm_verdict.h"
 
 #define EHM_INV_BLOCK 64
 #define EHM_INV_STATUSES 5
@@ -40,13 +44,12 @@ namespace {
 
 enum { INV_INVARIANT = 0, INV_EXITS = 1, INV_MODE_REGION = 2, INV_NO_MODE = 3, INV_NO_CELL = 4 };
 
-template <class T>
 struct SuccArgs {
     long long n;
     const int32_t* leaf_ids;        // or nullptr: leaves first .. first + n - 1
     long long first;
-    const T* node;
-    const T* leaf_rec;
+    const void* node;               // of the law's scalar, as leaf_rec
+    const void* leaf_rec;
     const int32_t* root_entry;
     const double* root_rec;         // [n_roots][side_stride]
     const int32_t* nbr;             // [n_roots][P+1] or nullptr
@@ -101,13 +104,14 @@ __device__ __forceinline__ bool margin_beats(double a, double b) {
 
 // Everything of one leaf; returns its status.
 template <class T, int P>
-__device__ __forceinline__ int leaf_successors(const SuccArgs<T>& A, const DevPlant& PL,
+__device__ __forceinline__ int leaf_successors(const SuccArgs& A, const DevPlant& PL,
                                                const double* sh, long long q) {
 #pragma clang fp contract(off)
     const int32_t l = A.leaf_ids ? A.leaf_ids[q] : (int32_t)(A.first + q);
     const int n_u = A.n_u, n_d = A.n_d, n_c = 1 << n_d;
+    const T* node = static_cast<const T*>(A.node);
     double V[(P + 1) * P];
-    const bool ok = leaf_cell<T, P>(A.par, A.node, A.root_entry, A.root_vertices, l, V);
+    const bool ok = leaf_cell<T, P>(A.par, node, A.root_entry, A.root_vertices, l, V);
     double* vout = A.vertices + (size_t)q * (P + 1) * P;
 #pragma unroll
     for (int e = 0; e < (P + 1) * P; ++e) vout[e] = ok ? V[e] : NAN;
@@ -130,7 +134,7 @@ __device__ __forceinline__ int leaf_successors(const SuccArgs<T>& A, const DevPl
     ehm_cert::TurnSet turns;
     int32_t root = 0;
     (void)ehm_cert::walk_up(A.par, l, turns, root);
-    const T* lr = A.leaf_rec + (size_t)l * A.leaf_stride;
+    const T* lr = static_cast<const T*>(A.leaf_rec) + (size_t)l * A.leaf_stride;
     const double* sA = sh + PL.oA + m * P * P;
     const double* sB = sh + PL.oB + m * P * n_u;
     const double* sw = sh + PL.ow + m * P;
@@ -243,7 +247,7 @@ __device__ __forceinline__ int leaf_successors(const SuccArgs<T>& A, const DevPl
                 for (int c = 0; c < P; ++c) A.x_next[(pts + at) * P + c] = z[c];
             if (A.succ_root) A.succ_root[pts + at] = inside ? kr : -1;
             if (A.succ_leaf)
-                A.succ_leaf[pts + at] = inside ? succ_walk<P>(A.node, A.root_entry[kr], z) : -1;
+                A.succ_leaf[pts + at] = inside ? succ_walk<P>(node, A.root_entry[kr], z) : -1;
         }
     }
     A.margin[q] = best;
@@ -253,52 +257,31 @@ __device__ __forceinline__ int leaf_successors(const SuccArgs<T>& A, const DevPl
 }
 
 template <class T, int P>
-__global__ __launch_bounds__(EHM_INV_BLOCK) void k_successors(SuccArgs<T> A, DevPlant PL) {
+__global__ __launch_bounds__(EHM_INV_BLOCK) void k_successors(SuccArgs A, DevPlant PL) {
     // all of the block's LDS is dynamic, so its base stays 16-byte aligned: the plant and the box
     // (PL.total doubles), the status counters after them
     extern __shared__ __attribute__((aligned(16))) double sh[];
     unsigned int* cnt = reinterpret_cast<unsigned int*>(sh + PL.total);
-    const int t = threadIdx.x;
-    for (int i = t; i < PL.total; i += blockDim.x) sh[i] = PL.data[i];
-    if (t < EHM_INV_STATUSES) cnt[t] = 0;
+    plant_load(PL, sh);
+    ehm_verdict::counters_zero<EHM_INV_BLOCK, EHM_INV_STATUSES>(cnt);
     __syncthreads();
-    const long long q = (long long)blockIdx.x * blockDim.x + t;
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q < A.n) {
         const int s = leaf_successors<T, P>(A, PL, sh, q);
         A.status[q] = s;
         atomicAdd(&cnt[s], 1u);
     }
     __syncthreads();
-    if (t < EHM_INV_STATUSES && cnt[t]) atomicAdd(&A.counters[t], (unsigned long long)cnt[t]);
+    ehm_verdict::counters_flush<EHM_INV_BLOCK, EHM_INV_STATUSES>(cnt, A.counters);
 }
 
-typedef void (*succ64_fn)(SuccArgs<double>, DevPlant);
-typedef void (*succ32_fn)(SuccArgs<float>, DevPlant);
+typedef void (*succ_fn)(SuccArgs, DevPlant);
 #define EHM_INV_ALL(T) {&k_successors<T, 1>, &k_successors<T, 2>, &k_successors<T, 3>, \
                         &k_successors<T, 4>, &k_successors<T, 5>, &k_successors<T, 6>, \
                         &k_successors<T, 7>, &k_successors<T, 8>}
-const succ64_fn k_succ64[EHM_CP] = EHM_INV_ALL(double);
-const succ32_fn k_succ32[EHM_CP] = EHM_INV_ALL(float);
+const succ_fn k_succ64[EHM_CP] = EHM_INV_ALL(double);
+const succ_fn k_succ32[EHM_CP] = EHM_INV_ALL(float);
 #undef EHM_INV_ALL
-
-// the device buffers of a run
-struct SuccBufs {
-    DevBuf plant, mode, roots, ids, vert, status, margin, worst, viol, x, sr, sl, cnt;
-};
-
-// the arguments of a pass over leaves off .. off + nc - 1 on the law's scalar T
-template <class T>
-SuccArgs<T> succ_args(const ehm_compiled_view& v, const ehm_invariance_opts* o, const SuccBufs& D,
-                      const ehm_cert::Parents& par, long long nc, long long off, int o_lo,
-                      int o_hi) {
-    return {nc, o->leaf_ids ? D.ids.as<const int32_t>() : nullptr, off,
-            static_cast<const T*>(v.node), static_cast<const T*>(v.leaf_rec), v.root_entry,
-            v.root_rec, v.nbr, D.roots.as<const double>(), par, D.mode.as<const int32_t>(),
-            v.n_u, v.leaf_stride, v.side_stride, (int)v.n_roots, o->n_d, o_lo, o_hi, o->tol_exit,
-            D.vert.as<double>(), D.status.as<int32_t>(), D.margin.as<double>(),
-            D.worst.as<int32_t>(), D.viol.as<double>(), D.x.as<double>(), D.sr.as<int32_t>(),
-            D.sl.as<int32_t>(), D.cnt.as<unsigned long long>()};
-}
 
 thread_local ehm_err_channel v_err;
 
@@ -335,23 +318,8 @@ int ehm_compiled_successors(ehm_compiled* law, const ehm_invariance_opts* o,
     int rc = check_law_shape(v_err, v, "successors");
     if (rc) return rc;
     const int p = v.p, n_u = v.n_u;
-    if (n_u > EHM_R_MAX_NU)
-        return v_err.fail(EHM_E_INVALID, "successors: n_u = %d, at most %d inputs", n_u,
-                          EHM_R_MAX_NU);
-    if (o->n_modes < 1 || o->n_modes > EHM_R_MAX_MODES)
-        return v_err.fail(EHM_E_INVALID, "successors: %d modes (1..%d)", (int)o->n_modes,
-                          EHM_R_MAX_MODES);
-    if (o->n_d < 0 || o->n_d > EHM_R_MAX_D)
-        return v_err.fail(EHM_E_INVALID, "successors: n_d = %d (0..%d)", (int)o->n_d, EHM_R_MAX_D);
-    if (o->n_d > 0 && !o->E)
-        return v_err.fail(EHM_E_INVALID, "successors: a box of %d disturbances but no E",
-                          (int)o->n_d);
-    if (o->n_d > 0 && (!o->d_lo || !o->d_hi))
-        return v_err.fail(EHM_E_INVALID, "successors: a required array is NULL");
-    for (int b = 0; b < o->n_d; ++b)
-        if (!std::isfinite(o->d_lo[b]) || !std::isfinite(o->d_hi[b]) || o->d_lo[b] > o->d_hi[b])
-            return v_err.fail(EHM_E_INVALID, "successors: the box is [%g, %g] on axis %d",
-                              o->d_lo[b], o->d_hi[b], b);
+    rc = check_step_plant(v_err, o, n_u, EHM_R_MAX_D, "successors");
+    if (rc) return rc;
     if (o->n_g < 0 || o->n_g > EHM_R_MAX_ROWS || (o->n_g > 0 && (!o->Gx || !o->gx)))
         return v_err.fail(EHM_E_INVALID, "successors: n_g = %d (0..%d)", (int)o->n_g,
                           EHM_R_MAX_ROWS);
@@ -373,22 +341,16 @@ int ehm_compiled_successors(ehm_compiled* law, const ehm_invariance_opts* o,
     res->worst_leaf = -1;
     res->worst_margin = NAN;
     if (o->n == 0) return EHM_OK;
-    // the plant's doubles, the box after them
-    const int n_d = o->n_d, n_c = 1 << n_d;
+    // the plant's doubles and the box, the region rows and the state rows after them
+    const int n_c = 1 << o->n_d;
     Pack pk;
-    pl.n_modes = o->n_modes;
-    pl.n_d = n_d;
+    int o_lo, o_hi;
+    pack_step_plant(pk, pl, o, p, n_u, o_lo, o_hi);
     pl.n_g = o->n_g;
-    pl.oA = pk.put(o->A, (size_t)o->n_modes * p * p);
-    pl.oB = pk.put(o->B, (size_t)o->n_modes * p * n_u);
-    pl.ow = pk.put(o->w, (size_t)o->n_modes * p);
-    pl.oE = pk.put(o->E, (size_t)p * n_d);
     pl.oH = pk.put(o->H, (size_t)rows * p);
     pl.oh = pk.put(o->h, (size_t)rows);
     pl.oG = pk.put(o->Gx, (size_t)o->n_g * p);
     pl.og = pk.put(o->gx, (size_t)o->n_g);
-    const int o_lo = pk.put(o->d_lo, (size_t)n_d);
-    const int o_hi = pk.put(o->d_hi, (size_t)n_d);
     pl.total = (int)pk.buf.size();
     const size_t plant_bytes = (size_t)pl.total * sizeof(double);
     const size_t lds = plant_bytes + EHM_INV_STATUSES * sizeof(unsigned int);
@@ -403,66 +365,68 @@ int ehm_compiled_successors(ehm_compiled* law, const ehm_invariance_opts* o,
                      : std::max<long long>(EHM_INV_BLOCK, std::min<long long>(
                                                65536, EHM_INV_BUDGET / (long long)(pts * p)));
     const size_t cap = (size_t)std::min<long long>(chunk, o->n);
-    SuccBufs D;
-    EHM_HIP_TRY(v_err, D.plant.upload(pk.buf.data(), plant_bytes));
-    pl.data = D.plant.as<const double>();
-    EHM_HIP_TRY(v_err, D.mode.upload(o->leaf_mode, (size_t)v.n_leaf * sizeof(int32_t)));
-    EHM_HIP_TRY(v_err, D.roots.upload(o->root_vertices, (size_t)v.n_roots * cell * sizeof(double)));
-    if (o->leaf_ids) EHM_HIP_TRY(v_err, D.ids.alloc(cap * sizeof(int32_t)));
-    EHM_HIP_TRY(v_err, D.vert.alloc(cap * cell * sizeof(double)));
-    EHM_HIP_TRY(v_err, D.status.alloc(cap * sizeof(int32_t)));
-    EHM_HIP_TRY(v_err, D.margin.alloc(cap * sizeof(double)));
-    EHM_HIP_TRY(v_err, D.worst.alloc(cap * sizeof(int32_t)));
-    EHM_HIP_TRY(v_err, D.viol.alloc(cap * sizeof(double)));
-    if (lv->x_next) EHM_HIP_TRY(v_err, D.x.alloc(cap * pts * p * sizeof(double)));
-    if (lv->succ_root) EHM_HIP_TRY(v_err, D.sr.alloc(cap * pts * sizeof(int32_t)));
-    if (lv->succ_leaf) EHM_HIP_TRY(v_err, D.sl.alloc(cap * pts * sizeof(int32_t)));
-    EHM_HIP_TRY(v_err, D.cnt.alloc(EHM_INV_STATUSES * sizeof(unsigned long long)));
-    EHM_HIP_TRY(v_err, hipMemsetAsync(D.cnt.ptr, 0, EHM_INV_STATUSES * sizeof(unsigned long long),
+    DevBuf d_plant, d_mode, d_roots, d_ids, d_cnt;
+    EHM_HIP_TRY(v_err, d_plant.upload(pk.buf.data(), plant_bytes));
+    pl.data = d_plant.as<const double>();
+    EHM_HIP_TRY(v_err, d_mode.upload(o->leaf_mode, (size_t)v.n_leaf * sizeof(int32_t)));
+    EHM_HIP_TRY(v_err, d_roots.upload(o->root_vertices, (size_t)v.n_roots * cell * sizeof(double)));
+    if (o->leaf_ids) EHM_HIP_TRY(v_err, d_ids.alloc(cap * sizeof(int32_t)));
+    EHM_HIP_TRY(v_err, d_cnt.alloc(EHM_INV_STATUSES * sizeof(unsigned long long)));
+    EHM_HIP_TRY(v_err, hipMemsetAsync(d_cnt.ptr, 0, EHM_INV_STATUSES * sizeof(unsigned long long),
                                       stream));
-    std::vector<double> hvert(cap * cell), R, vsub;
+    // a pass sets n and first; the outputs follow
+    SuccArgs A{0, d_ids.as<const int32_t>(), 0, v.node, v.leaf_rec, v.root_entry, v.root_rec, v.nbr,
+               d_roots.as<const double>(), T.view(), d_mode.as<const int32_t>(), n_u,
+               v.leaf_stride, v.side_stride, (int)v.n_roots, o->n_d, o_lo, o_hi, o->tol_exit};
+    A.counters = d_cnt.as<unsigned long long>();
+    std::vector<double> hvert(cap * cell), vsub;
+    // the per-leaf outputs: host array (nullptr: not asked for), the SuccArgs pointer its device
+    // buffer goes to, bytes per leaf; the cells alone come a chunk at a time, for the volumes
+    const size_t D = sizeof(double), I = sizeof(int32_t);
+    struct Out {
+        void* host;
+        void* field;
+        size_t bytes;
+        bool per_chunk;
+        DevBuf buf;
+    } out[] = {
+        {hvert.data(), &A.vertices, cell * D, true},
+        {lv->status, &A.status, I},
+        {lv->margin, &A.margin, D},
+        {lv->worst, &A.worst, I},
+        {lv->max_violation, &A.max_violation, D},
+        {lv->x_next, &A.x_next, pts * p * D},
+        {lv->succ_root, &A.succ_root, pts * I},
+        {lv->succ_leaf, &A.succ_leaf, pts * I},
+    };
+    for (Out& t : out)
+        if (t.host) {
+            EHM_HIP_TRY(v_err, t.buf.alloc(cap * t.bytes));
+            std::memcpy(t.field, &t.buf.ptr, sizeof t.buf.ptr);
+        }
     std::vector<long long> has;
     EventPair ev;
     bool have_worst = false;
     for (long long off = 0; off < o->n; off += chunk) {
         const long long nc = std::min<long long>(chunk, o->n - off);
         if (o->leaf_ids)
-            EHM_HIP_TRY(v_err, hipMemcpyAsync(D.ids.ptr, o->leaf_ids + off,
+            EHM_HIP_TRY(v_err, hipMemcpyAsync(d_ids.ptr, o->leaf_ids + off,
                                               (size_t)nc * sizeof(int32_t), hipMemcpyHostToDevice,
                                               stream));
+        A.n = nc;
+        A.first = off;
         const dim3 grid(blocks_of(nc, EHM_INV_BLOCK)), block(EHM_INV_BLOCK);
         (void)hipEventRecord(ev.e0, stream);
-        if (v.single)
-            hipLaunchKernelGGL(k_succ32[p - 1], grid, block, lds, stream,
-                               succ_args<float>(v, o, D, T.view(), nc, off, o_lo, o_hi), pl);
-        else
-            hipLaunchKernelGGL(k_succ64[p - 1], grid, block, lds, stream,
-                               succ_args<double>(v, o, D, T.view(), nc, off, o_lo, o_hi), pl);
+        hipLaunchKernelGGL((v.single ? k_succ32 : k_succ64)[p - 1], grid, block, lds, stream, A,
+                           pl);
         (void)hipEventRecord(ev.e1, stream);
         EHM_HIP_TRY(v_err, hipGetLastError());
-        const size_t N = (size_t)nc;
-        EHM_HIP_TRY(v_err, hipMemcpyAsync(hvert.data(), D.vert.ptr, N * cell * sizeof(double),
-                                          hipMemcpyDeviceToHost, stream));
-        EHM_HIP_TRY(v_err, hipMemcpyAsync(lv->status + off, D.status.ptr, N * sizeof(int32_t),
-                                          hipMemcpyDeviceToHost, stream));
-        EHM_HIP_TRY(v_err, hipMemcpyAsync(lv->margin + off, D.margin.ptr, N * sizeof(double),
-                                          hipMemcpyDeviceToHost, stream));
-        EHM_HIP_TRY(v_err, hipMemcpyAsync(lv->worst + off, D.worst.ptr, N * sizeof(int32_t),
-                                          hipMemcpyDeviceToHost, stream));
-        EHM_HIP_TRY(v_err, hipMemcpyAsync(lv->max_violation + off, D.viol.ptr, N * sizeof(double),
-                                          hipMemcpyDeviceToHost, stream));
-        if (lv->x_next)
-            EHM_HIP_TRY(v_err, hipMemcpyAsync(lv->x_next + (size_t)off * pts * p, D.x.ptr,
-                                              N * pts * p * sizeof(double), hipMemcpyDeviceToHost,
-                                              stream));
-        if (lv->succ_root)
-            EHM_HIP_TRY(v_err, hipMemcpyAsync(lv->succ_root + (size_t)off * pts, D.sr.ptr,
-                                              N * pts * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                              stream));
-        if (lv->succ_leaf)
-            EHM_HIP_TRY(v_err, hipMemcpyAsync(lv->succ_leaf + (size_t)off * pts, D.sl.ptr,
-                                              N * pts * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                              stream));
+        for (const Out& t : out)
+            if (t.host)
+                EHM_HIP_TRY(v_err, hipMemcpyAsync(static_cast<char*>(t.host) +
+                                                      (t.per_chunk ? 0 : (size_t)off * t.bytes),
+                                                  t.buf.ptr, (size_t)nc * t.bytes,
+                                                  hipMemcpyDeviceToHost, stream));
         EHM_HIP_TRY(v_err, hipStreamSynchronize(stream));
         double s = 0.0;
         ev.seconds(&s);
@@ -481,22 +445,15 @@ int ehm_compiled_successors(ehm_compiled* law, const ehm_invariance_opts* o,
             }
             if (st != INV_NO_CELL) has.push_back(q);
         }
-        if (!has.empty()) {
-            R.resize(has.size() * cell);
-            vsub.resize(has.size());
-            for (size_t a = 0; a < has.size(); ++a)
-                std::memcpy(&R[a * cell], &hvert[(size_t)has[a] * cell], cell * sizeof(double));
-            rc = ehm_volume_batch(v.device, (int64_t)has.size(), p, R.data(), vsub.data());
-            if (rc) return v_err.fail(rc, "successors: ehm_volume_batch: %s", ehm_last_error());
-            EHM_HIP_TRY(v_err, hipSetDevice(v.device));
-            for (size_t a = 0; a < has.size(); ++a) {
-                res->cell_volume += vsub[a];
-                if (lv->status[off + has[a]] == INV_INVARIANT) res->invariant_volume += vsub[a];
-            }
+        rc = cell_volumes(v_err, "successors", v.device, p, hvert.data(), has, vsub);
+        if (rc) return rc;
+        for (size_t a = 0; a < has.size(); ++a) {
+            res->cell_volume += vsub[a];
+            if (lv->status[off + has[a]] == INV_INVARIANT) res->invariant_volume += vsub[a];
         }
     }
     unsigned long long cnt[EHM_INV_STATUSES];
-    EHM_HIP_TRY(v_err, hipMemcpy(cnt, D.cnt.ptr, sizeof cnt, hipMemcpyDeviceToHost));
+    EHM_HIP_TRY(v_err, hipMemcpy(cnt, d_cnt.ptr, sizeof cnt, hipMemcpyDeviceToHost));
     for (int i = 0; i < EHM_INV_STATUSES; ++i) res->counts[i] = (int64_t)cnt[i];
     return EHM_OK;
 }

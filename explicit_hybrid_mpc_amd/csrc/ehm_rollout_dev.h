@@ -240,10 +240,15 @@ struct RollState {
     double cost, unorm, maxv;
 };
 
-// plant and model into LDS (all threads of the block; the caller synchronises)
+// the plant's doubles into LDS (all threads of the block; the caller synchronises)
+__device__ __forceinline__ void plant_load(const DevPlant& PL, double* sh) {
+    for (int i = threadIdx.x; i < PL.total; i += blockDim.x) sh[i] = PL.data[i];
+}
+
+// plant and model into LDS (likewise)
 template <PlantKind KIND>
 __device__ __forceinline__ void rollout_load(const DevPlant& PL, const DevNoise& NZ, double* sh) {
-    for (int i = threadIdx.x; i < PL.total; i += blockDim.x) sh[i] = PL.data[i];
+    plant_load(PL, sh);
     if constexpr (KIND == PK_NOISY)
         for (int i = threadIdx.x; i < NZ.total; i += blockDim.x) sh[PL.total + i] = NZ.data[i];
 }

@@ -1,4 +1,4 @@
-// What the law checks share when they judge and reduce (DESIGN.md 3.8d to 3.8f): the contract
+// What the law checks share when they judge and reduce (DESIGN.md 3.8d to 3.8i): the contract
 // V - V* <= max(eps_a, eps_r V*) with its slack, the ratio's histogram bin, who is the worst, and
 // on the device the LDS counters, the workgroup's worst (key, id) and the row of the applied-input
 // problem.  The rules are plain C++ that the kernels inline and a host program can drive
@@ -91,15 +91,16 @@ inline bool merge_block_worst(const double* key, const Id* id, size_t n, Id no_i
 
 #if defined(__HIPCC__)
 
-// an N-entry block of LDS counters: zeroed (a barrier follows in the kernel), and its counts
-// added to the run's once the workgroup's atomics are behind a barrier
+// an N-entry block of LDS counters (static, or a kernel's place in its dynamic LDS): zeroed (a
+// barrier follows in the kernel), and its counts added to the run's once the workgroup's atomics
+// are behind a barrier
 template <int BLOCK, int N>
-__device__ __forceinline__ void counters_zero(unsigned int (&cnt)[N]) {
+__device__ __forceinline__ void counters_zero(unsigned int* cnt) {
     for (int i = threadIdx.x; i < N; i += BLOCK) cnt[i] = 0;
 }
 
 template <int BLOCK, int N>
-__device__ __forceinline__ void counters_flush(const unsigned int (&cnt)[N],
+__device__ __forceinline__ void counters_flush(const unsigned int* cnt,
                                                unsigned long long* __restrict__ counters) {
     for (int i = threadIdx.x; i < N; i += BLOCK)
         if (cnt[i]) atomicAdd(&counters[i], (unsigned long long)cnt[i]);

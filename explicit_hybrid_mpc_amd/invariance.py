@@ -171,54 +171,78 @@ def _box(plant, d_box):
     return lo, hi
 
 
+class _Step:
+    """What both entry points need of (law, plant, d_box, tol_exit), resolved once: ``plant``, the
+    box ``lo`` / ``hi`` (None without one) and ``n_d`` (0 without one), ``tol_exit`` and ``chunk``,
+    the plant's arrays as contiguous float64 (``A B w E H h Gx gx``; ``rows`` int32), the leaf
+    ``modes`` int32, the law's root cells ``roots`` and ``set_convex``."""
+
+    def __init__(self, law, plant, d_box, tol_exit, chunk=0):
+        from . import applied, simulate
+        if not getattr(law, '_handle', None):
+            raise ValueError('the law is closed')
+        if plant is None:
+            plant = law._rollout_plant
+        if plant is None and law.mpc is not None:
+            plant = simulate.Plant.from_mpc(law.mpc)
+        if plant is None:
+            raise ValueError('successors needs a plant: the law has none and no mpc to make one '
+                             'from')
+        if plant.guarded:
+            raise ValueError('a guarded plant chooses its mode per substep by its guards: the '
+                             'successor is not affine on a leaf')
+        if plant.n_x != law.p or plant.n_u != law.n_u:
+            raise ValueError('plant (n_x %d, n_u %d) does not fit the law (p %d, n_u %d)' % (
+                plant.n_x, plant.n_u, law.p, law.n_u))
+        self.plant = plant
+        self.lo, self.hi = _box(plant, d_box)
+        self.n_d = 0 if self.lo is None else plant.n_d
+        self.tol_exit, self.chunk = float(tol_exit), int(chunk)
+        if not self.tol_exit >= 0. or self.chunk < 0:
+            raise ValueError('tol_exit and chunk must be >= 0')
+        if law._h['n_test'] > 0:
+            raise _capi.EhmError(_capi.EHM_E_INVALID, 'the law has %d test nodes: its cells do '
+                                 "not follow from its planes -- compile(spine='roots') has none" %
+                                 law._h['n_test'])
+        self.modes = np.ascontiguousarray(law._plant_modes(plant), dtype=np.int32)
+        if law._root_cells is None:
+            law._root_cells = applied.root_cells(law)
+        self.roots = law._root_cells
+        if getattr(law, '_set_convex', None) is None:
+            law._set_convex = roots_convex(self.roots['vertices'])
+        self.set_convex = bool(law._set_convex)
+        rows, H, h = plant.region_arrays()
+        self.rows = np.ascontiguousarray(rows, dtype=np.int32)
+        for k, a in dict(A=plant.A, B=plant.B, w=plant.w, E=plant.E, H=H, h=h, Gx=plant.Gx,
+                         gx=plant.gx).items():
+            setattr(self, k, np.ascontiguousarray(a, dtype=np.float64))
+
+    def opts(self, **kw):
+        """The plant part of an ``InvarianceOpts`` (an empty array, or E without a box: NULL)."""
+        opt = lambda a: ptr(a) if a.size else None
+        box = lambda a: opt(a) if self.n_d else None
+        return _capi.InvarianceOpts(
+            root_vertices=ptr(self.roots['vertices']), A=ptr(self.A), B=ptr(self.B), w=ptr(self.w),
+            E=box(self.E), leaf_mode=ptr(self.modes), d_lo=box(self.lo), d_hi=box(self.hi),
+            tol_exit=self.tol_exit, n_modes=int(self.plant.n_modes), n_d=self.n_d, **kw)
+
+
 def successors(law, plant=None, d_box=None, leaves=None, tol_exit=1e-9, return_successors=False,
                chunk=0):
     """The one path to ``ehm_compiled_successors``; see ``CompiledLaw.successors``."""
-    from . import applied, certify, simulate
-    if not getattr(law, '_handle', None):
-        raise ValueError('the law is closed')
-    if plant is None:
-        plant = law._rollout_plant
-    if plant is None and law.mpc is not None:
-        plant = simulate.Plant.from_mpc(law.mpc)
-    if plant is None:
-        raise ValueError('successors needs a plant: the law has none and no mpc to make one from')
-    if plant.guarded:
-        raise ValueError('a guarded plant chooses its mode per substep by its guards: the '
-                         'successor is not affine on a leaf')
-    if plant.n_x != law.p or plant.n_u != law.n_u:
-        raise ValueError('plant (n_x %d, n_u %d) does not fit the law (p %d, n_u %d)' % (
-            plant.n_x, plant.n_u, law.p, law.n_u))
-    lo, hi = _box(plant, d_box)
-    tol_exit, chunk = float(tol_exit), int(chunk)
-    if not tol_exit >= 0. or chunk < 0:
-        raise ValueError('tol_exit and chunk must be >= 0')
-    if law._h['n_test'] > 0:
-        raise _capi.EhmError(_capi.EHM_E_INVALID, 'the law has %d test nodes: its cells do not '
-                             "follow from its planes -- compile(spine='roots') has none" %
-                             law._h['n_test'])
-    modes = np.ascontiguousarray(law._plant_modes(plant), dtype=np.int32)
+    return _successors(law, _Step(law, plant, d_box, tol_exit, chunk), leaves, return_successors)
+
+
+def _successors(law, st, leaves, return_successors):
+    from . import certify
     ids = certify._leaf_ids(law, leaves)
-    if law._root_cells is None:
-        law._root_cells = applied.root_cells(law)
-    roots = law._root_cells
-    if getattr(law, '_set_convex', None) is None:
-        law._set_convex = roots_convex(roots['vertices'])
     n, p = ids.size, law.p
-    n_d = 0 if lo is None else plant.n_d
-    n_c = 1 << n_d
-    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+    n_c = 1 << st.n_d
     opt = lambda a: ptr(a) if a.size else None
-    rows, H, h = plant.region_arrays()
-    A, B, w, E, H, h, Gx, gx = (f64(a) for a in (plant.A, plant.B, plant.w, plant.E, H, h,
-                                                 plant.Gx, plant.gx))
-    rows = np.ascontiguousarray(rows, dtype=np.int32)
-    opts = _capi.InvarianceOpts(
-        n=n, leaf_ids=None if leaves is None else ptr(ids), root_vertices=ptr(roots['vertices']),
-        chunk=chunk, A=ptr(A), B=ptr(B), w=ptr(w), E=opt(E) if n_d else None,
-        region_rows=ptr(rows), H=opt(H), h=opt(h), Gx=opt(Gx), gx=opt(gx), leaf_mode=ptr(modes),
-        d_lo=opt(lo) if n_d else None, d_hi=opt(hi) if n_d else None, tol_exit=tol_exit,
-        n_modes=int(plant.n_modes), n_d=n_d, n_g=int(plant.gx.size))
+    opts = st.opts(
+        n=n, leaf_ids=None if leaves is None else ptr(ids), chunk=st.chunk,
+        region_rows=ptr(st.rows), H=opt(st.H), h=opt(st.h), Gx=opt(st.Gx), gx=opt(st.gx),
+        n_g=int(st.gx.size))
     arrays = dict(status=np.empty(n, np.int32), margin=np.empty(n), worst=np.empty(n, np.int32),
                   max_violation=np.empty(n))
     if return_successors:
@@ -229,7 +253,7 @@ def successors(law, plant=None, d_box=None, leaves=None, tol_exit=1e-9, return_s
     res = _capi.InvarianceResult()
     _check(_capi.load().ehm_compiled_successors(law._handle, ctypes.byref(opts),
                                                 ctypes.byref(res), ctypes.byref(lv)))
-    total = float(roots['volume'].sum())
+    total = float(st.roots['volume'].sum())
     counts = {name: int(res.counts[k]) for k, name in enumerate(STATUS_NAMES)}
     worst = None
     if res.worst_leaf >= 0:
@@ -241,8 +265,8 @@ def successors(law, plant=None, d_box=None, leaves=None, tol_exit=1e-9, return_s
         invariant_volume_fraction=float(res.invariant_volume) / total,
         cell_volume_fraction=float(res.cell_volume) / total, worst_leaf=worst,
         worst_margin=float(res.worst_margin), seconds=float(res.seconds),
-        set_convex=bool(law._set_convex), tol_exit=tol_exit,
-        holds_on_set=bool(counts['invariant'] == n and every and law._set_convex), **arrays)
+        set_convex=st.set_convex, tol_exit=st.tol_exit,
+        holds_on_set=bool(counts['invariant'] == n and every and st.set_convex), **arrays)
 
 
 class CoreResult:
@@ -287,7 +311,6 @@ class CoreResult:
 def invariant_core(law, plant=None, d_box=None, tol_exit=1e-9, tol_side=None, rows='invariant',
                    return_edges=False, max_fan=MAX_FAN, max_edges=MAX_EDGES):
     """The one path to ``ehm_compiled_core``; see ``CompiledLaw.invariant_core``."""
-    from . import simulate
     if rows not in CORE_ROWS:
         raise ValueError("rows must be 'invariant' or 'all'")
     if not float(tol_exit) >= 0.:
@@ -298,23 +321,10 @@ def invariant_core(law, plant=None, d_box=None, tol_exit=1e-9, tol_side=None, ro
         raise ValueError('tol_side must be >= 0')
     if max_fan < 1 or not 1 <= max_edges < 2 ** 31:
         raise ValueError('max_fan must be >= 1 and max_edges in 1 .. 2^31 - 1')
-    seeds = successors(law, plant=plant, d_box=d_box, tol_exit=tol_exit)
-    if plant is None:
-        plant = law._rollout_plant
-    if plant is None:
-        plant = simulate.Plant.from_mpc(law.mpc)
-    lo, hi = _box(plant, d_box)
+    st = _Step(law, plant, d_box, tol_exit)
+    seeds = _successors(law, st, None, False)
     n_leaf = law._h['n_leaf']
-    n_d = 0 if lo is None else plant.n_d
-    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
-    A, B, w, E = (f64(a) for a in (plant.A, plant.B, plant.w, plant.E))
-    modes = np.ascontiguousarray(law._plant_modes(plant), dtype=np.int32)
-    roots = law._root_cells
-    po = _capi.InvarianceOpts(
-        n=0, root_vertices=ptr(roots['vertices']), A=ptr(A), B=ptr(B), w=ptr(w),
-        E=ptr(E) if n_d and E.size else None, leaf_mode=ptr(modes),
-        d_lo=ptr(lo) if n_d else None, d_hi=ptr(hi) if n_d else None, tol_exit=float(tol_exit),
-        n_modes=int(plant.n_modes), n_d=n_d, n_g=0)
+    po = st.opts(n=0, n_g=0)
     status_in = np.ascontiguousarray(seeds.status, dtype=np.int32)
     co = _capi.CoreOpts(status=ptr(status_in), n_status=status_in.size, max_edges=max_edges,
                         tol_side=tol_side, max_fan=max_fan, rows=CORE_ROWS[rows],
@@ -338,14 +348,14 @@ def invariant_core(law, plant=None, d_box=None, tol_exit=1e-9, tol_side=None, ro
     finally:
         if edges.value:
             lib.ehm_host_free(edges)
-    total = float(roots['volume'].sum())
+    total = float(st.roots['volume'].sum())
     counts = {name: int(res.counts[k]) for k, name in enumerate(CORE_COUNT_NAMES)}
     core = level < 0
     return CoreResult(
         level=level, core=core, status=status, counts=counts, seeds=seeds,
         core_volume_fraction=float(res.core_volume) / total,
         cell_volume_fraction=float(res.cell_volume) / total, n_sweeps=int(res.n_sweeps),
-        n_edges=int(res.n_edges), set_convex=bool(law._set_convex),
-        holds=bool(law._set_convex and core.any()), indptr=indptr, indices=indices,
+        n_edges=int(res.n_edges), set_convex=st.set_convex,
+        holds=bool(st.set_convex and core.any()), indptr=indptr, indices=indices,
         seconds_reach=float(res.seconds_reach), seconds_sweeps=float(res.seconds_sweeps),
         tol_exit=float(tol_exit), tol_side=tol_side, rows=rows, _law=law)

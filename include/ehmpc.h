@@ -1073,7 +1073,9 @@ int ehm_invariance_abi_sizes(int64_t* sizes, int32_t n);
  * f = g . x + h has over I(L) the maximum max_i f(y_i) + sum_k max(gE_k d_lo_k, gE_k d_hi_k),
  * gE_k = ((0 + g_0 E_0k) + ..), and the minimum with min in both places.
  * `plant` is an ehm_invariance_opts of which root_vertices, A, B, w, E, leaf_mode, d_lo, d_hi,
- * n_modes and n_d are read (n_d up to 64 here: no corner is enumerated); the rest is ignored.
+ * n_modes, n_d and chunk are read (n_d up to 64 here: no corner is enumerated; chunk: the leaves
+ * whose cells go to the host at a time for their volumes, 0: 65536, and no result depends on it);
+ * the rest is ignored.
  * The row of leaf l -- built when l has a cell and a mode and (rows = EHM_CORE_ROWS_ALL or
  * status[l] = 0) -- lists, roots ascending and below a root left before right, every leaf reached by:
  *  1. root r is a candidate iff its bounding box, widened per coordinate by (p + 1) tol_side times
@@ -1096,8 +1098,8 @@ int ehm_invariance_abi_sizes(int64_t* sizes, int32_t n);
  * (caller's) and *indices_out, the rows' leaves in page-locked memory the caller releases with
  * ehm_host_free.
  * EHM_E_INVALID as ehm_compiled_successors for the law, the plant and the box; for n_status other
- * than the law's leaves, a status outside 0 .. 4, tol_side negative or NaN, max_fan < 1.  Errors
- * through ehm_core_last_error. */
+ * than the law's leaves, a status outside 0 .. 4, tol_side negative or NaN, max_fan < 1, a negative
+ * chunk.  Errors through ehm_core_last_error. */
 #define EHM_CORE_ROWS_INVARIANT 0
 #define EHM_CORE_ROWS_ALL 1
 typedef struct ehm_core_opts {

@@ -292,7 +292,7 @@ def test_the_entry_point_refuses():
     n_leaf = law.stats['n_leaf']
     lib = _capi.load()
 
-    def call(law_, plant_, handle=0, core=None, **kw):
+    def call(law_, plant_, handle=0, core=None, outputs=None, **kw):
         n = law_.stats['n_leaf']
         if law_.stats['n_test'] > 0:            # refused before anything is read
             roots = np.zeros((law_.stats['n_roots'], law_.p + 1, law_.p))
@@ -310,11 +310,24 @@ def test_the_entry_point_refuses():
         c.update(core or {})
         level, out = np.empty(n, np.int32), np.empty(n, np.int32)
         lv = _capi.CoreLeaves(level=level.ctypes.data, status=out.ctypes.data)
+        indptr, got = np.empty(n + 1, np.int64), ctypes.c_void_p(None)
+        edges = outputs is not None and c['want_edges']
+        if edges:                               # the outputs of want_edges; `outputs` takes them
+            lv.indptr, lv.indices_out = indptr.ctypes.data, ctypes.addressof(got)
         res = _capi.CoreResult()
         rc_ = lib.ehm_compiled_core(law_._handle if handle == 0 else handle,
                                     ctypes.byref(_capi.InvarianceOpts(**o)),
                                     ctypes.byref(_capi.CoreOpts(**c)), ctypes.byref(res),
                                     ctypes.byref(lv))
+        if outputs is not None:
+            outputs.update(status=out)
+        if edges:
+            indices = np.empty(res.n_edges if got.value else 0, np.int32)
+            if indices.size:
+                ctypes.memmove(indices.ctypes.data, got.value, indices.nbytes)
+            if got.value:
+                lib.ehm_host_free(got)
+            outputs.update(indptr=indptr, indices=indices)
         return rc_, lib.ehm_core_last_error(), level, res
 
     code, _, level, res = call(law, plant)
@@ -338,6 +351,35 @@ def test_the_entry_point_refuses():
     assert call(law, plant, A=None)[0] == _capi.EHM_E_INVALID
     assert call(law, plant, leaf_mode=None)[0] == _capi.EHM_E_INVALID
     assert call(law, plant, n_modes=5)[0] == _capi.EHM_E_INVALID
+    # the chunk of the count pass: several chunks (every one after the first starts at a leaf
+    # other than 0 and writes its volumes behind the earlier ones') give what one chunk gives, bit
+    # for bit; on the whole square, which the plant's contraction maps into itself
+    ex = es.SynthLaw(es.kuhn_forest(p), n_u, 1, rng, n_sub=3).explicit()
+    whole = ex.compile()
+    ex.close()
+    n_whole = whole.stats['n_leaf']
+    assert n_whole > 2 * 16
+    mixed = (np.arange(n_whole) % 3 == 0).astype(np.int32)      # some seeds, so levels differ
+    for want in (0, 1):
+        runs = []
+        for chunk in (16, 0):
+            e = {}
+            code, _, level, res = call(whole, plant, chunk=chunk, outputs=e,
+                                       core=dict(status=mixed.ctypes.data, want_edges=want))
+            assert code == _capi.EHM_OK
+            runs.append(dict(e, level=level, counts=np.array(res.counts[:]),
+                             volumes=np.array([res.core_volume, res.cell_volume]),
+                             n_edges=np.array([res.n_edges])))
+        assert sorted(runs[0]) == sorted(runs[1]) and ('indices' in runs[0]) == bool(want)
+        assert 'status' in runs[0]
+        for k in runs[0]:
+            _same(runs[0][k], runs[1][k], 'chunk 16 against 0: ' + k)
+        print('chunks:', n_whole, 'leaves,', runs[0]['n_edges'][0], 'edges, levels up to',
+              runs[0]['level'].max(), 'volumes', runs[0]['volumes'])
+        assert runs[0]['n_edges'][0] > 0 and runs[0]['volumes'][0] < runs[0]['volumes'][1]
+    code, msg, _, _ = call(whole, plant, chunk=-1)
+    assert code == _capi.EHM_E_INVALID and b'chunk' in msg
+    whole.close()
     lo, hi = np.array([0., 1.]), np.array([1., 0.5])
     E = np.ascontiguousarray(plant.E)
     code, msg, _, _ = call(law, plant, n_d=2, E=E.ctypes.data, d_lo=lo.ctypes.data,

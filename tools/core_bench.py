@@ -5,7 +5,8 @@ DESIGN.md 3.8i; needs a GPU, except --registers).
 
     python tools/core_bench.py [--trees headline,config3,cwh_z_job1] [--trajectories 100000]
                                [--steps 200] [--out PATH]
-    python tools/core_bench.py --registers [--registers-out PATH]
+    python tools/core_bench.py --registers [--registers-source ehm_invariance.hip]
+                               [--registers-out PATH]
 
 Trees: the headline partition, the depth-18 config-3 tree and cwh_z job 1, as tools/audit_bench.py
 builds them, each as a double law and as ``to_single(flush=True)``.  The plant is ``Plant.from_mpc``
@@ -24,7 +25,9 @@ numbers in advance.  One JSON line per measurement to stdout and, as they come, 
 profiles/core/core_bench.txt.
 
 --registers compiles csrc/ehm_core.hip for gfx950 with -Rpass-analysis=kernel-resource-usage and
-writes the figures of every kernel to profiles/core/registers.txt (no GPU needed).
+writes the figures of every kernel to profiles/core/registers.txt (no GPU needed);
+--registers-source ehm_invariance.hip does the same for the kernels of ``successors``, which step a
+leaf's vertices with the same device code, into profiles/invariance/registers.txt.
 """
 import argparse
 import json
@@ -41,12 +44,22 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def registers(path):
+# per source of --registers: where the figures go, and what its kernels keep in dynamic LDS
+REGISTERS = {
+    'ehm_core.hip': ('core', 'the static part; the plant, the box and the edge count of k_reach '
+                     'are dynamic, a few KiB'),
+    'ehm_invariance.hip': ('invariance', 'the static part, none; the plant, the box and the '
+                           'counters are dynamic, at most 40 852 bytes'),
+}
+
+
+def registers(source, path):
     from explicit_hybrid_mpc_amd import build
-    src = os.path.join(build.SRC_DIR, 'ehm_core.hip')
+    src = os.path.join(build.SRC_DIR, source)
+    path = path or os.path.join(ROOT, 'profiles', REGISTERS[source][0], 'registers.txt')
     with tempfile.TemporaryDirectory() as tmp:
         cmd = [build._hipcc()] + build.FLAGS + ['-Rpass-analysis=kernel-resource-usage', '-c', src,
-                                                '-o', os.path.join(tmp, 'ehm_core.o')]
+                                                '-o', os.path.join(tmp, 'registers.o')]
         text = subprocess.run(cmd, check=True, stderr=subprocess.PIPE, text=True).stderr
     demangle = subprocess.run(['c++filt'], input=text, stdout=subprocess.PIPE, text=True).stdout
     rows, cur = [], None
@@ -65,8 +78,7 @@ def registers(path):
     os.makedirs(os.path.dirname(path), exist_ok=True)
     with open(path, 'w') as out:
         out.write('# hipcc --offload-arch=gfx950 -O3 -Rpass-analysis=kernel-resource-usage on '
-                  'csrc/ehm_core.hip\n# (LDS: the static part; the plant, the box and the edge '
-                  'count of k_reach are dynamic, a few KiB)\n')
+                  'csrc/%s\n# (LDS: %s)\n' % (source, REGISTERS[source][1]))
         for r in rows:
             out.write('%-26s SGPRs %3s  VGPRs %3s  AGPRs %3s  scratch %s bytes/lane  waves/SIMD %s'
                       '  LDS %s bytes/block\n' % (
@@ -96,11 +108,11 @@ def main():
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'core', 'core_bench.txt'))
     ap.add_argument('--append', action='store_true', help='add to --out instead of replacing it')
     ap.add_argument('--registers', action='store_true')
-    ap.add_argument('--registers-out', default=os.path.join(ROOT, 'profiles', 'core',
-                                                            'registers.txt'))
+    ap.add_argument('--registers-source', default='ehm_core.hip', choices=sorted(REGISTERS))
+    ap.add_argument('--registers-out', default=None)
     args = ap.parse_args()
     if args.registers:
-        return registers(args.registers_out)
+        return registers(args.registers_source, args.registers_out)
     from explicit_hybrid_mpc_amd import _capi, explicit, invariance, simulate
     from tools.audit_bench import config3, cwh_job1, headline
     from tools.invariance_bench import process_box
