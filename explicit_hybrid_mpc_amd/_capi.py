@@ -64,6 +64,8 @@ EXPORTED = [
     'ehm_compiled_reduce', 'ehm_reduce_last_error',
     'ehm_compiled_successors', 'ehm_invariance_last_error', 'ehm_invariance_abi_sizes',
     'ehm_compiled_core', 'ehm_core_last_error', 'ehm_core_abi_sizes',
+    'ehm_compiled_robust_successors', 'ehm_compiled_robust_core', 'ehm_robust_last_error',
+    'ehm_robust_abi_sizes',
 ]
 EHM_AUDIT_MODES = {'uniform': 0, 'per_leaf': 1}     # EHM_AUDIT_UNIFORM / _PER_LEAF
 EHM_COMPILE_SPINE_ROOTS = 1     # ehm_compiled_create_opts
@@ -312,6 +314,24 @@ class CoreLeaves(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ('level', 'status', 'indptr', 'indices_out')]
 
 
+class RobustOpts(ctypes.Structure):
+    _fields_ = [('facets', ctypes.c_void_p), ('n_facets', ctypes.c_int64)] + \
+        [(k, ctypes.c_void_p) for k in ('v_lo', 'v_hi', 'e_lo', 'e_hi')] + \
+        [('tol_set', ctypes.c_double)]
+
+
+class RobustResult(ctypes.Structure):
+    _fields_ = [('counts', ctypes.c_int64 * 5), ('worst_leaf', ctypes.c_int64),
+                ('worst_margin', ctypes.c_double), ('invariant_volume', ctypes.c_double),
+                ('cell_volume', ctypes.c_double), ('seconds', ctypes.c_double),
+                ('seconds_slack', ctypes.c_double), ('n_generators', ctypes.c_int32),
+                ('reserved', ctypes.c_int32)]
+
+
+class RobustLeaves(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ('status', 'margin', 'worst')]
+
+
 _lib = None
 
 
@@ -346,7 +366,9 @@ def load(build_if_missing=True):
             ('ehm_certify_abi_sizes', (CertifyOpts, CertifyResult, CertifyLeaves), "certificate's "),
             ('ehm_invariance_abi_sizes', (InvarianceOpts, InvarianceResult, InvarianceLeaves),
              "successors' "),
-            ('ehm_core_abi_sizes', (CoreOpts, CoreResult, CoreLeaves), "invariant core's ")):
+            ('ehm_core_abi_sizes', (CoreOpts, CoreResult, CoreLeaves), "invariant core's "),
+            ('ehm_robust_abi_sizes', (RobustOpts, RobustResult, RobustLeaves),
+             "robust step's ")):
         sizes = (i64 * len(mirrors))()
         fn = getattr(lib, getter)
         fn.argtypes = [vp, i32]
@@ -374,6 +396,15 @@ def load(build_if_missing=True):
                                       ctypes.POINTER(CoreOpts), ctypes.POINTER(CoreResult),
                                       ctypes.POINTER(CoreLeaves)]
     lib.ehm_core_last_error.restype = ctypes.c_char_p
+    lib.ehm_compiled_robust_successors.argtypes = [vp, ctypes.POINTER(InvarianceOpts),
+                                                   ctypes.POINTER(RobustOpts),
+                                                   ctypes.POINTER(RobustResult),
+                                                   ctypes.POINTER(RobustLeaves)]
+    lib.ehm_compiled_robust_core.argtypes = [vp, ctypes.POINTER(InvarianceOpts),
+                                             ctypes.POINTER(RobustOpts), ctypes.POINTER(CoreOpts),
+                                             ctypes.POINTER(CoreResult),
+                                             ctypes.POINTER(CoreLeaves)]
+    lib.ehm_robust_last_error.restype = ctypes.c_char_p
     lib.ehm_explicit_set_costs.argtypes = [vp, vp, vp]
     lib.ehm_explicit_sample.argtypes = [vp, ctypes.POINTER(AuditOpts), vp, vp]
     lib.ehm_explicit_audit.argtypes = [vp, vp, ctypes.POINTER(AuditOpts),
@@ -474,7 +505,8 @@ def load(build_if_missing=True):
                         'ehm_explicit_last_error', 'ehm_implicit_last_error',
                         'ehm_compiled_last_error', 'ehm_applied_last_error',
                         'ehm_certify_last_error', 'ehm_reduce_last_error',
-                        'ehm_invariance_last_error', 'ehm_core_last_error'):
+                        'ehm_invariance_last_error', 'ehm_core_last_error',
+                        'ehm_robust_last_error'):
             fn.restype = i32
     lib.ehm_search_last_error.restype = ctypes.c_char_p
     lib.ehm_search_create.argtypes = [i32, i32, i32, ctypes.POINTER(vp)]

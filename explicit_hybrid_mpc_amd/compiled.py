@@ -732,6 +732,64 @@ class CompiledLaw:
             max_fan=invariance.MAX_FAN if max_fan is None else max_fan,
             max_edges=invariance.MAX_EDGES if max_edges is None else max_edges)
 
+    # -- the same two questions under measurement and input error (robust.py) -------
+    def robust_successors(self, plant=None, d_box=None, v_box=None, e_box=None, noise=None,
+                          leaves=None, tol_exit=1e-9, tol_set=1e-9, chunk=0):
+        """
+        ``successors`` for the closed loop ``rollout(..., noise=)`` runs: the law is evaluated at
+        the measured state z = x + v, the region of the leaf's mode is tested on the true state,
+        the plant steps with u + e and a disturbance d.  With d, v and e in the boxes ``d_box``,
+        ``v_box``, ``e_box`` (each (lo, hi) or None for none; v and e must hold 0) the image of a
+        leaf's measured states is the hull of its p + 1 nominal vertex successors plus
+        G_m [box], G_m = [E | -A_m | B_m | I], box = [d; v; e; v] -- up to 64 generators, no corner
+        enumerated.  A leaf is ``invariant`` when the minimum over that image of every boundary
+        facet's form n_f . z - c_f (``invariance.boundary_facets``, unit normals) is
+        >= -tol_set max|root vertex| and every region row of its mode holds on cell - v box
+        (``tol_exit``); else ``exits`` / ``mode_region``; ``no_mode``, ``no_cell`` as
+        ``successors``.  ``margin`` is the smallest facet minimum, a distance in state units with
+        no threshold applied.  ``tol_set`` defaults to the tolerance within which the set is known
+        to be convex at all.
+
+        ``noise=`` (a ``NoiseModel``; not together with a box) fills the three boxes from the model:
+        ``noise.bounding_boxes`` at ``u_abs``, the largest vertex input modulus of any leaf, and at
+        ``x_abs``, a verified bound on every true state (``noise.state_bound`` from the set's
+        largest vertex moduli); both are in the result with the boxes.  The boxes are global:
+        per-leaf radii would be tighter.  With neither noise nor v / e boxes this is the
+        closed-form test under ``d_box`` alone, for any n_d up to 64.
+
+        As with ``successors``, the result proves something only where the set is convex
+        (``set_convex``, ``holds_on_set``); without that the facets bound nothing.  Not covered:
+        the rounding of a single law's evaluation at interior points, the hand-over within
+        rounding of a split face, the recovery error of the root vertices, guarded plants
+        (``ValueError``).  ``EhmError`` for a law with test nodes.  Returns a
+        ``robust.RobustSuccessorResult``.
+        """
+        from . import robust
+        return robust.robust_successors(self, plant=plant, d_box=d_box, v_box=v_box, e_box=e_box,
+                                        noise=noise, leaves=leaves, tol_exit=tol_exit,
+                                        tol_set=tol_set, chunk=chunk)
+
+    def robust_core(self, plant=None, d_box=None, v_box=None, e_box=None, noise=None,
+                    tol_exit=1e-9, tol_set=1e-9, tol_side=None, rows='invariant',
+                    return_edges=False, max_fan=None, max_edges=None):
+        """
+        ``invariant_core`` for the noisy closed loop: the may-reach relation of the images of
+        ``robust_successors`` (boxes and ``noise=`` as there), seeded with the leaves its one-step
+        test does not call invariant.  Where the set is convex, every trajectory of the noisy
+        closed loop from a state of a core leaf has, for any errors in the boxes and at every
+        length, every measured state in the set and in a core leaf, every true state in its mode's
+        region and within the v box of the set; a leaf of level k has k safe steps.  ``tol_side``,
+        ``rows``, ``return_edges``, ``max_fan``, ``max_edges`` as ``invariant_core``.  Returns an
+        ``invariance.CoreResult`` whose ``seeds`` is the ``robust.RobustSuccessorResult``.
+        """
+        from . import invariance, robust
+        return robust.robust_core(
+            self, plant=plant, d_box=d_box, v_box=v_box, e_box=e_box, noise=noise,
+            tol_exit=tol_exit, tol_set=tol_set, tol_side=tol_side, rows=rows,
+            return_edges=return_edges,
+            max_fan=invariance.MAX_FAN if max_fan is None else max_fan,
+            max_edges=invariance.MAX_EDGES if max_edges is None else max_edges)
+
     def __call__(self, x):
         """(u, t): the input for state x and the evaluation time, as the reference's call."""
         tic = time.time()

@@ -234,15 +234,73 @@ inline int check_step_plant(ehm_err_channel& err, const ehm_invariance_opts* o, 
     return EHM_OK;
 }
 
+// The generators of the robust step: per mode G_m = [E | -A_m | B_m | I] [p][n_g]
+// and the box [d; v; e; v] stacked in that order; the v columns (both blocks) and the e columns are
+// there only where the caller gives the box.  Every entry is a copy or a negation, so G is exact.
+// `o` has passed check_step_plant.  Refused: a v or e box of which one bound is NULL, one without 0
+// (v_0 = 0, and e = 0 where u = 0, are draws too), n_g > max_g.
+struct RobustGen {
+    std::vector<double> G, lo, hi;
+    int n_g = 0;
+};
+
+inline int robust_generators(ehm_err_channel& err, const ehm_invariance_opts* o,
+                             const ehm_robust_opts* ro, int p, int n_u, int max_g, const char* who,
+                             RobustGen& g) {
+    if ((!ro->v_lo) != (!ro->v_hi) || (!ro->e_lo) != (!ro->e_hi))
+        return err.fail(EHM_E_INVALID, "%s: a box with one bound NULL", who);
+    const int n_d = o->n_d, n_v = ro->v_lo ? p : 0, n_e = ro->e_lo ? n_u : 0;
+    g.n_g = n_d + 2 * n_v + n_e;
+    if (g.n_g > max_g)
+        return err.fail(EHM_E_INVALID, "%s: n_g = %d generators (n_d + 2 p + n_u), at most %d", who,
+                        g.n_g, max_g);
+    for (int c = 0; c < n_v; ++c)
+        if (!(ro->v_lo[c] <= 0.0 && ro->v_hi[c] >= 0.0))
+            return err.fail(EHM_E_INVALID, "%s: the v box [%g, %g] on axis %d does not hold 0", who,
+                            ro->v_lo[c], ro->v_hi[c], c);
+    for (int c = 0; c < n_e; ++c)
+        if (!(ro->e_lo[c] <= 0.0 && ro->e_hi[c] >= 0.0))
+            return err.fail(EHM_E_INVALID, "%s: the e box [%g, %g] on axis %d does not hold 0", who,
+                            ro->e_lo[c], ro->e_hi[c], c);
+    const int n_g = g.n_g;
+    g.G.assign((size_t)o->n_modes * p * n_g, 0.0);
+    for (int m = 0; m < o->n_modes; ++m)
+        for (int k = 0; k < p; ++k) {
+            double* row = &g.G[((size_t)m * p + k) * n_g];
+            for (int b = 0; b < n_d; ++b) row[b] = o->E[k * n_d + b];
+            for (int c = 0; c < n_v; ++c) row[n_d + c] = -o->A[((size_t)m * p + k) * p + c];
+            for (int c = 0; c < n_e; ++c) row[n_d + n_v + c] = o->B[((size_t)m * p + k) * n_u + c];
+            if (n_v) row[n_d + n_v + n_e + k] = 1.0;
+        }
+    g.lo.clear();
+    g.hi.clear();
+    g.lo.insert(g.lo.end(), o->d_lo, o->d_lo + n_d);
+    g.hi.insert(g.hi.end(), o->d_hi, o->d_hi + n_d);
+    for (int rep = 0; rep < 2; ++rep) {
+        g.lo.insert(g.lo.end(), ro->v_lo, ro->v_lo + n_v);
+        g.hi.insert(g.hi.end(), ro->v_hi, ro->v_hi + n_v);
+        if (rep == 0) {
+            g.lo.insert(g.lo.end(), ro->e_lo, ro->e_lo + n_e);
+            g.hi.insert(g.hi.end(), ro->e_hi, ro->e_hi + n_e);
+        }
+    }
+    for (int k = 0; k < n_g; ++k)
+        if (!std::isfinite(g.lo[k]) || !std::isfinite(g.hi[k]) || g.lo[k] > g.hi[k])
+            return err.fail(EHM_E_INVALID, "%s: the box is [%g, %g] on generator %d", who, g.lo[k],
+                            g.hi[k], k);
+    return EHM_OK;
+}
+
 // That plant's doubles into pk: A, B, w and E at pl's offsets, the box after them at o_lo, o_hi.
+// e_modes: the blocks [p][n_d] that E holds (1: the shared E; n_modes: the generators of every mode).
 inline void pack_step_plant(Pack& pk, DevPlant& pl, const ehm_invariance_opts* o, int p, int n_u,
-                            int& o_lo, int& o_hi) {
+                            int& o_lo, int& o_hi, int e_modes = 1) {
     pl.n_modes = o->n_modes;
     pl.n_d = o->n_d;
     pl.oA = pk.put(o->A, (size_t)o->n_modes * p * p);
     pl.oB = pk.put(o->B, (size_t)o->n_modes * p * n_u);
     pl.ow = pk.put(o->w, (size_t)o->n_modes * p);
-    pl.oE = pk.put(o->E, (size_t)p * o->n_d);
+    pl.oE = pk.put(o->E, (size_t)e_modes * p * o->n_d);
     o_lo = pk.put(o->d_lo, (size_t)o->n_d);
     o_hi = pk.put(o->d_hi, (size_t)o->n_d);
 }

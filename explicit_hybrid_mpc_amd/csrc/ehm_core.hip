@@ -4,7 +4,11 @@
 // every disturbance of the box is I(L) = hull{y_i} + E [d_lo, d_hi] with y_i the p + 1 vertex
 // successors before the disturbance, and an affine f = g . x + h has over I(L) the extrema
 // max_i f(y_i) + sum_k max(gE_k d_lo_k, gE_k d_hi_k) (min likewise), gE_k = g . E[:, k]: no corner of
-// the box is enumerated.
+// the box is enumerated.  A second set of k_reach instances (PER_MODE) reads the generator block of
+// the leaf's mode, the blocks p n_g doubles apart: the robust step's G_m = [E | -A_m | B_m | I]
+// (ehm_compiled_robust_core), whose box is [d; v; e; v]; the instances of this
+// section's entry point read the shared E and compile to the code they had before there was a
+// second set.
 //
 //   k_root_boxes   one thread per root: the bounding box of its vertices
 //   k_reach        one thread per leaf, templated on the law's scalar and on P, run twice (count, then
@@ -148,8 +152,9 @@ __device__ __forceinline__ void node_decision(const T* __restrict__ node, int k,
     go_right = smin < -eps + slack;
 }
 
-// Everything of one leaf in one pass.
-template <class T, int P>
+// Everything of one leaf in one pass.  PER_MODE: the generator block is G_m of the leaf's mode, the
+// blocks P n_d doubles apart; else the shared E, and the code is that of 3.8i.
+template <class T, int P, bool PER_MODE>
 __device__ __forceinline__ void leaf_reach(const ReachArgs& A, const DevPlant& PL,
                                            const double* sh, long long q) {
 #pragma clang fp contract(off)
@@ -179,7 +184,7 @@ __device__ __forceinline__ void leaf_reach(const ReachArgs& A, const DevPlant& P
     const double* sA = sh + PL.oA + m * P * P;
     const double* sB = sh + PL.oB + m * P * n_u;
     const double* sw = sh + PL.ow + m * P;
-    const double* sE = sh + PL.oE;
+    const double* sE = sh + PL.oE + (PER_MODE ? m * (P * n_d) : 0);
     const double* lo_d = sh + A.o_lo;
     const double* hi_d = sh + A.o_hi;
     // the vertex successors before the disturbance, in place of the cell
@@ -354,7 +359,7 @@ __device__ __forceinline__ void leaf_reach(const ReachArgs& A, const DevPlant& P
     }
 }
 
-template <class T, int P>
+template <class T, int P, bool PER_MODE>
 __global__ __launch_bounds__(EHM_CORE_BLOCK) void k_reach(ReachArgs A, DevPlant PL) {
     // all of the block's LDS is dynamic: the plant and the box (PL.total doubles), the block's edge
     // count after them
@@ -366,7 +371,7 @@ __global__ __launch_bounds__(EHM_CORE_BLOCK) void k_reach(ReachArgs A, DevPlant 
     __syncthreads();
     const long long q = (long long)blockIdx.x * blockDim.x + t;
     if (q < A.n) {
-        leaf_reach<T, P>(A, PL, sh, q);
+        leaf_reach<T, P, PER_MODE>(A, PL, sh, q);
         if (!A.indptr) {
             const int c = A.count[A.first + q];
             if (c) atomicAdd(sum, (unsigned long long)c);
@@ -438,10 +443,12 @@ __global__ __launch_bounds__(256) void k_core_counts(long long n_leaf,
 }
 
 typedef void (*reach_fn)(ReachArgs, DevPlant);
-#define EHM_CORE_ALL(T) {&k_reach<T, 1>, &k_reach<T, 2>, &k_reach<T, 3>, &k_reach<T, 4>, \
-                         &k_reach<T, 5>, &k_reach<T, 6>, &k_reach<T, 7>, &k_reach<T, 8>}
-const reach_fn k_reach64[EHM_CP] = EHM_CORE_ALL(double);
-const reach_fn k_reach32[EHM_CP] = EHM_CORE_ALL(float);
+#define EHM_CORE_ALL(T, M) {&k_reach<T, 1, M>, &k_reach<T, 2, M>, &k_reach<T, 3, M>, \
+                            &k_reach<T, 4, M>, &k_reach<T, 5, M>, &k_reach<T, 6, M>, \
+                            &k_reach<T, 7, M>, &k_reach<T, 8, M>}
+// [0]: the shared E (ehm_compiled_core); [1]: a generator block per mode (ehm_compiled_robust_core)
+const reach_fn k_reach64[2][EHM_CP] = {EHM_CORE_ALL(double, false), EHM_CORE_ALL(double, true)};
+const reach_fn k_reach32[2][EHM_CP] = {EHM_CORE_ALL(float, false), EHM_CORE_ALL(float, true)};
 #undef EHM_CORE_ALL
 
 thread_local ehm_err_channel c_err;
@@ -458,8 +465,14 @@ int ehm_core_abi_sizes(int64_t* sizes, int32_t n) {
     return ehm_copy_abi_sizes(all, (int32_t)(sizeof all / sizeof all[0]), sizes, n);
 }
 
-int ehm_compiled_core(ehm_compiled* law, const ehm_invariance_opts* o, const ehm_core_opts* co,
-                      ehm_core_result* res, const ehm_core_leaves* lv) {
+}  // extern "C"
+
+namespace {
+
+// Both entry points.  ro: the robust step's boxes (the generator block of a leaf is then G_m of its
+// mode), nullptr: the shared E and the box of `o`.
+int core_run(ehm_compiled* law, const ehm_invariance_opts* o, const ehm_robust_opts* ro,
+             const ehm_core_opts* co, ehm_core_result* res, const ehm_core_leaves* lv) {
     if (!law || !o || !co || !res || !lv) return c_err.fail(EHM_E_INVALID, "core: bad argument");
     if (o->chunk < 0) return c_err.fail(EHM_E_INVALID, "core: chunk < 0");
     if (!o->root_vertices || !o->A || !o->B || !o->w || !o->leaf_mode || !co->status)
@@ -481,6 +494,17 @@ int ehm_compiled_core(ehm_compiled* law, const ehm_invariance_opts* o, const ehm
     const int p = v.p, n_u = v.n_u;
     rc = check_step_plant(c_err, o, n_u, EHM_CORE_MAX_D, "core");
     if (rc) return rc;
+    RobustGen gen;
+    ehm_invariance_opts og = *o;
+    if (ro) {
+        rc = robust_generators(c_err, o, ro, p, n_u, EHM_CORE_MAX_D, "robust_core", gen);
+        if (rc) return rc;
+        og.E = gen.G.data();
+        og.d_lo = gen.lo.data();
+        og.d_hi = gen.hi.data();
+        og.n_d = gen.n_g;
+        o = &og;
+    }
     const long long n_leaf = v.n_leaf;
     if (co->n_status != n_leaf)
         return c_err.fail(EHM_E_INVALID, "core: a status array of %lld for %lld leaves",
@@ -496,7 +520,7 @@ int ehm_compiled_core(ehm_compiled* law, const ehm_invariance_opts* o, const ehm
     DevPlant pl{};
     ReachArgs A{};
     Pack pk;
-    pack_step_plant(pk, pl, o, p, n_u, A.o_lo, A.o_hi);
+    pack_step_plant(pk, pl, o, p, n_u, A.o_lo, A.o_hi, ro ? o->n_modes : 1);
     pl.total = (int)pk.buf.size();
     const size_t plant_bytes = (size_t)pl.total * sizeof(double);
     const size_t lds = plant_bytes + sizeof(unsigned long long);
@@ -552,8 +576,8 @@ int ehm_compiled_core(ehm_compiled* law, const ehm_invariance_opts* o, const ehm
         A.first = first;
         A.n = n;
         const dim3 grid(blocks_of(n, EHM_CORE_BLOCK)), block(EHM_CORE_BLOCK);
-        hipLaunchKernelGGL((v.single ? k_reach32 : k_reach64)[p - 1], grid, block, lds, stream,
-                           A, pl);
+        hipLaunchKernelGGL((v.single ? k_reach32 : k_reach64)[ro ? 1 : 0][p - 1], grid, block, lds,
+                           stream, A, pl);
     };
     // the count pass, chunk by chunk: the cells go to the host for their volumes
     std::vector<double> hvert(cap * cell), vsub, volume((size_t)n_leaf, 0.0);
@@ -671,6 +695,22 @@ int ehm_compiled_core(ehm_compiled* law, const ehm_invariance_opts* o, const ehm
         }
     }
     return EHM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ehm_compiled_core(ehm_compiled* law, const ehm_invariance_opts* o, const ehm_core_opts* co,
+                      ehm_core_result* res, const ehm_core_leaves* lv) {
+    return core_run(law, o, nullptr, co, res, lv);
+}
+
+int ehm_compiled_robust_core(ehm_compiled* law, const ehm_invariance_opts* o,
+                             const ehm_robust_opts* ro, const ehm_core_opts* co,
+                             ehm_core_result* res, const ehm_core_leaves* lv) {
+    if (!ro) return c_err.fail(EHM_E_INVALID, "robust_core: bad argument");
+    return core_run(law, o, ro, co, res, lv);
 }
 
 }  // extern "C"

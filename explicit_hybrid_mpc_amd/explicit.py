@@ -537,6 +537,35 @@ class ExplicitMPC:
         finally:
             law.close()
 
+    def robust_successors(self, spine='roots', dtype=np.float64, flush=False, **kw):
+        """
+        ``CompiledLaw.robust_successors`` (robust.py) for this law: compiles it
+        (``compile(spine=spine, dtype=dtype, flush=flush)``) and asks where its input sends every
+        leaf under measurement and input error; ``kw`` as ``CompiledLaw.robust_successors``.
+        Returns its ``robust.RobustSuccessorResult``.
+        """
+        law = self.compile(dtype=dtype, spine=spine, flush=flush)
+        try:
+            return law.robust_successors(**kw)
+        finally:
+            law.close()
+
+    def robust_core(self, spine='roots', dtype=np.float64, flush=False, **kw):
+        """
+        ``CompiledLaw.robust_core`` (robust.py) for this law: compiles it
+        (``compile(spine=spine, dtype=dtype, flush=flush)``) and finds the leaves the noisy closed
+        loop never leaves; ``kw`` as ``CompiledLaw.robust_core``.  Returns its
+        ``invariance.CoreResult``, whose ``contains`` needs the compiled law and is not available
+        here.
+        """
+        law = self.compile(dtype=dtype, spine=spine, flush=flush)
+        try:
+            res = law.robust_core(**kw)
+            res._law = None
+            return res
+        finally:
+            law.close()
+
     def node_modes(self, plant):
         """int32 [n_nodes]: step-0 mode of every node's commutation (-1: none); all 0 for a
         single-mode plant."""

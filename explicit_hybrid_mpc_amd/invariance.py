@@ -24,11 +24,13 @@ disturbances of the box ever stops with status 1 or 2, whatever its length.
 
 What the result covers: the piecewise-affine function the law's arrays define on the cells their
 planes define (``cells``), and the nominal plant of ``simulate.Plant`` with a box disturbance.  It
-does not cover: measurement error v or input error e; the rounding of a single law's evaluation at
-interior points (DESIGN.md 3.8c bounds it); a state within rounding of a split face being handed to
-the sibling leaf's map; the recovery error of the root vertices the cells carry.  Without a convex
-set ``invariant`` is a statement about the vertex successors only.  ``margin`` is in units of the
-chosen root's barycentric weights: for a point outside it orders leaves, it is not a distance.
+does not cover: measurement error v or input error e (``robust.py``, DESIGN.md 3.8j, does: the
+closed-form facet test and the core with a generator block per mode); the rounding of a single
+law's evaluation at interior points (DESIGN.md 3.8c bounds it); a state within rounding of a split
+face being handed to the sibling leaf's map; the recovery error of the root vertices the cells
+carry.  Without a convex set ``invariant`` is a statement about the vertex successors only.
+``margin`` is in units of the chosen root's barycentric weights: for a point outside it orders
+leaves, it is not a distance.
 """
 
 import ctypes
@@ -56,8 +58,16 @@ _check_core = _capi.checker('ehm_core_last_error')
 
 
 def roots_convex(root_vertices, rtol=1e-9):
+    """True iff the union of the simplices ``root_vertices`` [n_roots, p+1, p] is convex: the third
+    return of ``boundary_facets``, which says how it is decided."""
+    return boundary_facets(root_vertices, rtol)[2]
+
+
+def boundary_facets(root_vertices, rtol=1e-9):
     """
-    True iff the union of the simplices ``root_vertices`` [n_roots, p+1, p] is convex; host numpy.
+    (normals [n_b, p], offsets [n_b], convex): the boundary facets of the union of the simplices
+    ``root_vertices`` [n_roots, p+1, p] as half-spaces normal . x >= offset with unit normals, and
+    whether the union is convex -- it is then the intersection of those half-spaces; host numpy.
 
     The vertices are deduplicated first: per coordinate, values closer than rtol max|v| are one
     value, so vertices that differ in their last bits between roots are one vertex.  The boundary
@@ -81,8 +91,9 @@ def roots_convex(root_vertices, rtol=1e-9):
     if V.ndim != 3 or V.shape[1] != V.shape[2] + 1:
         raise ValueError('root_vertices must be [n_roots, p+1, p]')
     R, nv, p = V.shape
+    none = np.zeros((0, p)), np.zeros(0)
     if R == 0:
-        return True
+        return none + (True,)
     scale = float(np.abs(V).max())
     tol = float(rtol) * (scale if scale > 0. else 1.)
     flat = V.reshape(-1, p)
@@ -99,8 +110,9 @@ def roots_convex(root_vertices, rtol=1e-9):
         covered = np.sort(V[:, :, 0], axis=1)
         order = np.argsort(covered[:, 0])
         reach = np.maximum.accumulate(covered[order, 1])
-        return bool((covered[order, 0][1:] <= reach[:-1] + tol).all() and reach[-1] >= hi - tol
-                    and covered[order, 0][0] <= lo + tol)
+        return (np.array([[1.], [-1.]]), np.array([lo, -hi]),
+                bool((covered[order, 0][1:] <= reach[:-1] + tol).all() and reach[-1] >= hi - tol
+                     and covered[order, 0][0] <= lo + tol))
     # every facet: the root's vertices without the k-th, which is its opposite vertex
     keep = np.array([[j for j in range(nv) if j != k] for k in range(nv)])      # [nv, p]
     facets = np.sort(vid[:, keep], axis=2).reshape(-1, p)                       # [R nv, p]
@@ -108,7 +120,7 @@ def roots_convex(root_vertices, rtol=1e-9):
     _, index, counts = np.unique(facets, axis=0, return_index=True, return_counts=True)
     boundary = index[counts == 1]
     if boundary.size == 0:
-        return True
+        return none + (True,)
     F = points[facets[boundary]]                                                # [nb, p, p]
     edges = F[:, 1:] - F[:, :1]                                                 # [nb, p-1, p]
     normal = np.linalg.svd(edges, full_matrices=True)[2][:, -1, :]              # unit, [nb, p]
@@ -119,8 +131,8 @@ def roots_convex(root_vertices, rtol=1e-9):
     for s in range(0, normal.shape[0], rows):
         d = normal[s:s + rows] @ points.T - offset[s:s + rows, None]
         if (d < -tol).any():
-            return False
-    return True
+            return normal, offset, False
+    return normal, offset, True
 
 
 class SuccessorResult:
@@ -195,8 +207,7 @@ class _Step:
             raise ValueError('plant (n_x %d, n_u %d) does not fit the law (p %d, n_u %d)' % (
                 plant.n_x, plant.n_u, law.p, law.n_u))
         self.plant = plant
-        self.lo, self.hi = _box(plant, d_box)
-        self.n_d = 0 if self.lo is None else plant.n_d
+        self._set_box(d_box)
         self.tol_exit, self.chunk = float(tol_exit), int(chunk)
         if not self.tol_exit >= 0. or self.chunk < 0:
             raise ValueError('tol_exit and chunk must be >= 0')
@@ -208,14 +219,21 @@ class _Step:
         if law._root_cells is None:
             law._root_cells = applied.root_cells(law)
         self.roots = law._root_cells
-        if getattr(law, '_set_convex', None) is None:
-            law._set_convex = roots_convex(self.roots['vertices'])
+        if getattr(law, '_set_facets', None) is None:
+            law._set_facets = boundary_facets(self.roots['vertices'])
+            law._set_convex = law._set_facets[2]
+        self.facets = law._set_facets
         self.set_convex = bool(law._set_convex)
         rows, H, h = plant.region_arrays()
         self.rows = np.ascontiguousarray(rows, dtype=np.int32)
         for k, a in dict(A=plant.A, B=plant.B, w=plant.w, E=plant.E, H=H, h=h, Gx=plant.Gx,
                          gx=plant.gx).items():
             setattr(self, k, np.ascontiguousarray(a, dtype=np.float64))
+
+    def _set_box(self, d_box):
+        """``lo`` / ``hi`` / ``n_d`` of the caller's box (``robust._RobustStep`` has three)."""
+        self.lo, self.hi = _box(self.plant, d_box)
+        self.n_d = 0 if self.lo is None else self.plant.n_d
 
     def opts(self, **kw):
         """The plant part of an ``InvarianceOpts`` (an empty array, or E without a box: NULL)."""
@@ -311,6 +329,15 @@ class CoreResult:
 def invariant_core(law, plant=None, d_box=None, tol_exit=1e-9, tol_side=None, rows='invariant',
                    return_edges=False, max_fan=MAX_FAN, max_edges=MAX_EDGES):
     """The one path to ``ehm_compiled_core``; see ``CompiledLaw.invariant_core``."""
+    tol_side, max_fan, max_edges = _core_args(tol_exit, tol_side, rows, max_fan, max_edges)
+    st = _Step(law, plant, d_box, tol_exit)
+    seeds = _successors(law, st, None, False)
+    return _core(law, st, seeds, tol_side, rows, return_edges, max_fan, max_edges,
+                 lambda lib, po, co, res, lv: lib.ehm_compiled_core(law._handle, po, co, res, lv))
+
+
+def _core_args(tol_exit, tol_side, rows, max_fan, max_edges):
+    """(tol_side, max_fan, max_edges) checked, as both core calls take them."""
     if rows not in CORE_ROWS:
         raise ValueError("rows must be 'invariant' or 'all'")
     if not float(tol_exit) >= 0.:
@@ -321,8 +348,13 @@ def invariant_core(law, plant=None, d_box=None, tol_exit=1e-9, tol_side=None, ro
         raise ValueError('tol_side must be >= 0')
     if max_fan < 1 or not 1 <= max_edges < 2 ** 31:
         raise ValueError('max_fan must be >= 1 and max_edges in 1 .. 2^31 - 1')
-    st = _Step(law, plant, d_box, tol_exit)
-    seeds = _successors(law, st, None, False)
+    return tol_side, max_fan, max_edges
+
+
+def _core(law, st, seeds, tol_side, rows, return_edges, max_fan, max_edges, call):
+    """The relation and its fixed point from the one-step result ``seeds``; ``call(lib, plant opts,
+    core opts, result, leaves)`` is the entry point (``ehm_compiled_core`` or its robust form)."""
+    tol_exit = st.tol_exit
     n_leaf = law._h['n_leaf']
     po = st.opts(n=0, n_g=0)
     status_in = np.ascontiguousarray(seeds.status, dtype=np.int32)
@@ -338,8 +370,8 @@ def invariant_core(law, plant=None, d_box=None, tol_exit=1e-9, tol_side=None, ro
     lib = _capi.load()
     indices = None
     try:
-        _check_core(lib.ehm_compiled_core(law._handle, ctypes.byref(po), ctypes.byref(co),
-                                          ctypes.byref(res), ctypes.byref(lv)))
+        _check_core(call(lib, ctypes.byref(po), ctypes.byref(co), ctypes.byref(res),
+                         ctypes.byref(lv)))
         if return_edges:
             n_e = int(res.n_edges)
             indices = np.empty(n_e, np.int32)

@@ -291,6 +291,66 @@ class NoiseModel:
                 np.ascontiguousarray(np.array(data, dtype=np.float64)))
 
 
+def bounding_boxes(model, x_abs, u_abs):
+    """
+    {'process': (lo, hi), 'state': (lo, hi), 'input': (lo, hi)}: per kind an interval hull of every
+    draw ``model.sample`` can make at true states with |x| <= x_abs and inputs with |u| <= u_abs
+    (coordinate-wise), summed over the kind's terms; host numpy.  A box term M (c + h s), |s| <= 1,
+    lies in M c -+ |M| h.  A ball term L q with ||q||_norm <= r has coordinate i within
+    -+ r ||L_i||_*, the dual norm of the ball's (2 <-> 2, inf <-> 1, 1 <-> inf), and r is at most
+    sigma, sigma || |F| x_abs ||_px or sigma || |F| u_abs ||_pu: the norms are monotone in the
+    moduli and |F x| <= |F| |x|.  The bounds are in floating point: a draw may pass one by rounding.
+    """
+    x_abs = np.asarray(x_abs, dtype=np.float64).reshape(model.n_x)
+    u_abs = np.asarray(u_abs, dtype=np.float64).reshape(model.n_u)
+    out = {k: (np.zeros(model.out_dim(k)), np.zeros(model.out_dim(k))) for k in KINDS}
+    for term in model.terms:
+        lo, hi = out[term.kind]
+        if term.shape == 'box':
+            mid, rad = term.map @ term.c, np.abs(term.map) @ term.h
+            out[term.kind] = (lo + (mid - rad), hi + (mid + rad))
+            continue
+        r = term.sigma
+        if term.dep != 'const':
+            y = np.abs(term.F) @ (x_abs if term.dep == 'state' else u_abs)
+            r = r * _norm_rows([y[i:i + 1] for i in range(y.size)], term.p_dep)[0]
+        L = np.abs(term.map)
+        dual = np.sqrt((L * L).sum(axis=1)) if term.norm == 2 else \
+            L.sum(axis=1) if term.norm == 0 else L.max(axis=1)
+        out[term.kind] = (lo - r * dual, hi + r * dual)
+    return out
+
+
+def state_bound(model, set_abs, u_abs, grow=1e-6, iterations=100):
+    """
+    x_abs [n_x] with |x| <= x_abs for every true state x = z - v of a closed loop whose measured
+    states z obey |z| <= set_abs, v drawn by ``model`` at x.  With v_half(a) the coordinate-wise
+    largest modulus of the 'state' box of ``bounding_boxes(model, a, u_abs)``, every true state has
+    |x| <= set_abs + v_half(|x|), and v_half is a constant plus a monotone, positively homogeneous
+    function; so any a with set_abs + v_half(a) <= a bounds |x|.  a is found by
+    iterating a <- set_abs + v_half(a) from set_abs, inflated by 1 + grow, and VERIFIED.
+    ``ValueError`` where no iterate passes within ``iterations``: the relative error is 100 % or more.
+    """
+    set_abs = np.asarray(set_abs, dtype=np.float64).reshape(model.n_x)
+
+    def v_half(a):
+        with np.errstate(over='ignore', invalid='ignore'):      # a diverging iterate ends below
+            lo, hi = bounding_boxes(model, a, u_abs)['state']
+        return np.maximum(np.abs(lo), np.abs(hi))
+
+    a = set_abs.copy()
+    for _ in range(int(iterations)):
+        a = set_abs + v_half(a)
+        cand = a * (1. + grow)
+        if not np.isfinite(cand).all():
+            break
+        if (set_abs + v_half(cand) <= cand).all():
+            return cand
+    raise ValueError('no bound on the true state within %d iterations: the state-dependent '
+                     'measurement error does not contract (a relative error of 100 %% or more)'
+                     % iterations)
+
+
 def state_input_model(half, n_u):
     """
     A hand-built state / input model for a law without one of its own (``from_mpc`` gives None),

@@ -1131,6 +1131,86 @@ const char* ehm_core_last_error(void);
 /* ehm_abi_sizes for ehm_core_opts, ehm_core_result, ehm_core_leaves, in this order. */
 int ehm_core_abi_sizes(int64_t* sizes, int32_t n);
 
+/* ---- one-step invariance and the core under measurement and input error (csrc/ehm_robust.hip,
+ * csrc/ehm_core.hip) -------------------------------------------------------------
+ * (no counterpart in the reference)
+ *
+ * The closed loop of ehm_compiled_rollout_noisy evaluates the law at the measured state z = x + v,
+ * tests the mode's region rows on the true state x = z - v and steps the plant with u + e.  With d, v
+ * and e in boxes the measured state's successor on leaf L of mode m is
+ *     z+ = [A_m z + B_m u(z) + w_m] + E d - A_m v + B_m e + v'          (v' in the box of v),
+ * so its image is I(L) = hull{y_i} + G_m [g_lo, g_hi]: y_i the p + 1 vertex successors of
+ * ehm_compiled_successors before the disturbance (its step 4, bit for bit), G_m = [E | -A_m | B_m | I]
+ * [p][n_g], n_g = n_d + 2 p + n_u, the box [d; v; e; v].  The columns of v (both blocks) and of e are
+ * there only where the box is given (v_lo / v_hi, e_lo / e_hi: both NULL for none), so n_g shrinks
+ * accordingly; n_g <= 64.  The v and e boxes must hold 0.
+ * `plant` is an ehm_invariance_opts of which n, leaf_ids, root_vertices, chunk, A, B, w, E,
+ * region_rows, H, h, leaf_mode, d_lo, d_hi, tol_exit, n_modes and n_d (up to 64) are read.
+ *
+ * ehm_compiled_robust_successors: facets [n_facets][p+1] are the boundary facets of the roots' union,
+ * row f = [n_f | c_f], n_f a unit normal, the inner side n_f . x >= c_f.  A small kernel first fills
+ * slack[f][m] = sum_k min(nG_k g_lo_k, nG_k g_hi_k) from 0, nG_k = ((0 + n_f0 G_m[0][k]) + ..).  Per
+ * requested leaf, one device thread:
+ *  1. the cell and m as ehm_compiled_successors;
+ *  2. region row r of mode m holds iff  max_i ((0 + H_r0 v_i0) + ..) + rs_r <= h_r + tol_exit,
+ *     rs_r = sum_c max((-H_rc) v_lo_c, (-H_rc) v_hi_c) from 0 (0 without a v box), the maximum taken
+ *     in vertex order;
+ *  3. y_i as step 4 of ehm_compiled_successors;
+ *  4. for every facet f in order: mn_f = min_i ((0 + n_f0 y_i0) + ..), the first on ties, a NaN before
+ *     any number; val_f = (mn_f - c_f) + slack[f][m]; the facet holds iff
+ *     val_f >= -(tol_set * max|root_vertices|) (a NaN fails).
+ * Status, the first that applies: 4 no_cell; 3 no_mode; 2 mode_region (a region row fails); 1 exits (a
+ * facet fails); 0 invariant.  margin: the minimum of val_f in facet order, the first on ties, a NaN
+ * before any number (NaN without a cell or mode) -- a distance in state units, no threshold applied;
+ * worst = f (p + 1) + i of the facet and the vertex that give it (-1).  Result: counts, worst_leaf,
+ * worst_margin, the volumes and seconds as ehm_compiled_successors; seconds_slack, the device time
+ * of the slack kernel; n_generators.  No result depends on the chunk (0: 65536 leaves per pass).
+ * Where the union is not convex the facets bound nothing: the caller says so, the call is the same.
+ *
+ * ehm_compiled_robust_core: ehm_compiled_core with G_m of the leaf's mode in the place of E and the
+ * stacked box in the place of [d_lo, d_hi]; everything else -- the candidate roots, the traversal,
+ * tol_side, the single law's widening, max_fan, max_edges, the fixed point, the outputs -- is
+ * ehm_compiled_core's.  `opts->status` is the one-step status of ehm_compiled_robust_successors.
+ *
+ * EHM_E_INVALID, before the device is touched: as ehm_compiled_successors for the law and the plant;
+ * n_g > 64; a box with lo > hi or a bound that is not finite; a v or e box without 0 or with one
+ * bound NULL; n_facets < 1 or n_facets (p + 1) >= 2^31 (robust_successors); tol_set negative or NaN;
+ * a required array that is NULL.  Errors through ehm_robust_last_error (robust_successors) and
+ * ehm_core_last_error (robust_core). */
+typedef struct ehm_robust_opts {
+    const double* facets;           /* [n_facets][p+1]; not read by ehm_compiled_robust_core   */
+    int64_t n_facets;
+    const double* v_lo;             /* [p] or NULL                                             */
+    const double* v_hi;
+    const double* e_lo;             /* [n_u] or NULL                                           */
+    const double* e_hi;
+    double tol_set;
+} ehm_robust_opts;
+typedef struct ehm_robust_result {
+    int64_t counts[5];
+    int64_t worst_leaf;
+    double  worst_margin;
+    double  invariant_volume;
+    double  cell_volume;
+    double  seconds;
+    double  seconds_slack;
+    int32_t n_generators, reserved;
+} ehm_robust_result;
+typedef struct ehm_robust_leaves {
+    int32_t* status;
+    double*  margin;
+    int32_t* worst;
+} ehm_robust_leaves;
+int ehm_compiled_robust_successors(ehm_compiled* law, const ehm_invariance_opts* plant,
+                                   const ehm_robust_opts* opts, ehm_robust_result* result,
+                                   const ehm_robust_leaves* leaves);
+int ehm_compiled_robust_core(ehm_compiled* law, const ehm_invariance_opts* plant,
+                             const ehm_robust_opts* robust, const ehm_core_opts* opts,
+                             ehm_core_result* result, const ehm_core_leaves* leaves);
+const char* ehm_robust_last_error(void);
+/* ehm_abi_sizes for ehm_robust_opts, ehm_robust_result, ehm_robust_leaves, in this order. */
+int ehm_robust_abi_sizes(int64_t* sizes, int32_t n);
+
 /* ---- closed-loop simulation under the COMPILED law (csrc/ehm_compiled.hip) -------
  *
  * The entry points of the explicit law's rollout, argument for argument, on a compiled law -- also

@@ -50,6 +50,9 @@ REGISTERS = {
                      'are dynamic, a few KiB'),
     'ehm_invariance.hip': ('invariance', 'the static part, none; the plant, the box and the '
                            'counters are dynamic, at most 40 852 bytes'),
+    'ehm_robust.hip': ('robust', 'the static part, none; the plant, the generators of every mode, '
+                       'the boxes, the region rows and the counters are dynamic, at most 39 316 '
+                       'bytes'),
 }
 
 
