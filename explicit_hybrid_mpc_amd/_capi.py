@@ -66,6 +66,8 @@ EXPORTED = [
     'ehm_compiled_core', 'ehm_core_last_error', 'ehm_core_abi_sizes',
     'ehm_compiled_robust_successors', 'ehm_compiled_robust_core', 'ehm_robust_last_error',
     'ehm_robust_abi_sizes',
+    'ehm_compiled_robust_successors_leaf', 'ehm_compiled_robust_core_leaf',
+    'ehm_robust_radii_abi_sizes',
 ]
 EHM_AUDIT_MODES = {'uniform': 0, 'per_leaf': 1}     # EHM_AUDIT_UNIFORM / _PER_LEAF
 EHM_COMPILE_SPINE_ROOTS = 1     # ehm_compiled_create_opts
@@ -332,6 +334,17 @@ class RobustLeaves(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ('status', 'margin', 'worst')]
 
 
+class RobustRadii(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ('desc', 'data', 'x_abs', 'u_abs')] + \
+        [(k, ctypes.c_int32) for k in ('n_terms', 'n_data', 'n_x', 'n_u', 'n_d', 'radius_iters')]
+
+
+class RobustLeafBoxes(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ('d', 'v', 'e', 'v_next', 'x_abs_leaf',
+                                               'x_next_abs', 'u_abs_leaf')] + \
+        [('seconds_radii', ctypes.c_double)]
+
+
 _lib = None
 
 
@@ -368,7 +381,9 @@ def load(build_if_missing=True):
              "successors' "),
             ('ehm_core_abi_sizes', (CoreOpts, CoreResult, CoreLeaves), "invariant core's "),
             ('ehm_robust_abi_sizes', (RobustOpts, RobustResult, RobustLeaves),
-             "robust step's ")):
+             "robust step's "),
+            ('ehm_robust_radii_abi_sizes', (RobustRadii, RobustLeafBoxes),
+             "per-leaf radii's ")):
         sizes = (i64 * len(mirrors))()
         fn = getattr(lib, getter)
         fn.argtypes = [vp, i32]
@@ -404,6 +419,18 @@ def load(build_if_missing=True):
                                              ctypes.POINTER(RobustOpts), ctypes.POINTER(CoreOpts),
                                              ctypes.POINTER(CoreResult),
                                              ctypes.POINTER(CoreLeaves)]
+    lib.ehm_compiled_robust_successors_leaf.argtypes = [vp, ctypes.POINTER(InvarianceOpts),
+                                                        ctypes.POINTER(RobustOpts),
+                                                        ctypes.POINTER(RobustRadii),
+                                                        ctypes.POINTER(RobustResult),
+                                                        ctypes.POINTER(RobustLeaves),
+                                                        ctypes.POINTER(RobustLeafBoxes)]
+    lib.ehm_compiled_robust_core_leaf.argtypes = [vp, ctypes.POINTER(InvarianceOpts),
+                                                  ctypes.POINTER(RobustOpts),
+                                                  ctypes.POINTER(RobustRadii),
+                                                  ctypes.POINTER(CoreOpts),
+                                                  ctypes.POINTER(CoreResult),
+                                                  ctypes.POINTER(CoreLeaves)]
     lib.ehm_robust_last_error.restype = ctypes.c_char_p
     lib.ehm_explicit_set_costs.argtypes = [vp, vp, vp]
     lib.ehm_explicit_sample.argtypes = [vp, ctypes.POINTER(AuditOpts), vp, vp]

@@ -734,7 +734,8 @@ class CompiledLaw:
 
     # -- the same two questions under measurement and input error (robust.py) -------
     def robust_successors(self, plant=None, d_box=None, v_box=None, e_box=None, noise=None,
-                          leaves=None, tol_exit=1e-9, tol_set=1e-9, chunk=0):
+                          leaves=None, tol_exit=1e-9, tol_set=1e-9, chunk=0, radii='global',
+                          radius_iters=3):
         """
         ``successors`` for the closed loop ``rollout(..., noise=)`` runs: the law is evaluated at
         the measured state z = x + v, the region of the leaf's mode is tested on the true state,
@@ -753,9 +754,19 @@ class CompiledLaw:
         ``noise=`` (a ``NoiseModel``; not together with a box) fills the three boxes from the model:
         ``noise.bounding_boxes`` at ``u_abs``, the largest vertex input modulus of any leaf, and at
         ``x_abs``, a verified bound on every true state (``noise.state_bound`` from the set's
-        largest vertex moduli); both are in the result with the boxes.  The boxes are global:
-        per-leaf radii would be tighter.  With neither noise nor v / e boxes this is the
+        largest vertex moduli); both are in the result with the boxes.  These boxes are global
+        (``radii='global'``, the default).  With neither noise nor v / e boxes this is the
         closed-form test under ``d_box`` alone, for any n_d up to 64.
+
+        ``radii='leaf'`` (needs ``noise=``, takes no boxes) bounds every error on
+        leaf L at the states and inputs L itself can see: the true state by ``radius_iters`` (1..16)
+        steps of a <- min(a, c_L + vhalf(a, u_abs)) from the global ``x_abs``, the input by the
+        leaf's largest vertex input modulus, the next true state by the leaf's image.  The device
+        makes one box per leaf from the packed model the rollout uses; the result then also holds
+        ``leaf_boxes``, ``x_abs_leaf``, ``x_next_abs`` and ``u_abs_leaf``, and ``boxes``, ``x_abs``,
+        ``u_abs`` stay the global ones.  ``ValueError`` without ``noise=``, with a box, for an
+        unknown ``radii``, a ``radius_iters`` outside 1..16 and a model whose constant part of the
+        v or e box does not hold 0.
 
         As with ``successors``, the result proves something only where the set is convex
         (``set_convex``, ``holds_on_set``); without that the facets bound nothing.  Not covered:
@@ -767,11 +778,13 @@ class CompiledLaw:
         from . import robust
         return robust.robust_successors(self, plant=plant, d_box=d_box, v_box=v_box, e_box=e_box,
                                         noise=noise, leaves=leaves, tol_exit=tol_exit,
-                                        tol_set=tol_set, chunk=chunk)
+                                        tol_set=tol_set, chunk=chunk, radii=radii,
+                                        radius_iters=radius_iters)
 
     def robust_core(self, plant=None, d_box=None, v_box=None, e_box=None, noise=None,
                     tol_exit=1e-9, tol_set=1e-9, tol_side=None, rows='invariant',
-                    return_edges=False, max_fan=None, max_edges=None):
+                    return_edges=False, max_fan=None, max_edges=None, radii='global',
+                    radius_iters=3):
         """
         ``invariant_core`` for the noisy closed loop: the may-reach relation of the images of
         ``robust_successors`` (boxes and ``noise=`` as there), seeded with the leaves its one-step
@@ -779,7 +792,9 @@ class CompiledLaw:
         closed loop from a state of a core leaf has, for any errors in the boxes and at every
         length, every measured state in the set and in a core leaf, every true state in its mode's
         region and within the v box of the set; a leaf of level k has k safe steps.  ``tol_side``,
-        ``rows``, ``return_edges``, ``max_fan``, ``max_edges`` as ``invariant_core``.  Returns an
+        ``rows``, ``return_edges``, ``max_fan``, ``max_edges`` as ``invariant_core``; ``radii`` and
+        ``radius_iters`` as ``robust_successors`` (``'leaf'``: the image of a leaf is spanned by the
+        leaf's own boxes, which the device makes for all leaves itself).  Returns an
         ``invariance.CoreResult`` whose ``seeds`` is the ``robust.RobustSuccessorResult``.
         """
         from . import invariance, robust
@@ -788,7 +803,8 @@ class CompiledLaw:
             tol_exit=tol_exit, tol_set=tol_set, tol_side=tol_side, rows=rows,
             return_edges=return_edges,
             max_fan=invariance.MAX_FAN if max_fan is None else max_fan,
-            max_edges=invariance.MAX_EDGES if max_edges is None else max_edges)
+            max_edges=invariance.MAX_EDGES if max_edges is None else max_edges, radii=radii,
+            radius_iters=radius_iters)
 
     def __call__(self, x):
         """(u, t): the input for state x and the evaluation time, as the reference's call."""

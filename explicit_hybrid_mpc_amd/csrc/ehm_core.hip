@@ -8,7 +8,10 @@
 // the leaf's mode, the blocks p n_g doubles apart: the robust step's G_m = [E | -A_m | B_m | I]
 // (ehm_compiled_robust_core), whose box is [d; v; e; v]; the instances of this
 // section's entry point read the shared E and compile to the code they had before there was a
-// second set.
+// second set.  A third set (k_reach_leaf, ehm_compiled_robust_core_leaf) reads a box
+// per leaf: k_leaf_radii (ehm_radii_dev.h) makes the boxes of all leaves, leaf-fastest, and every lane
+// copies its leaf's into a slice of LDS of its own, so the traversal reads it through the same
+// pointers and the other two sets keep their code.
 //
 //   k_root_boxes   one thread per root: the bounding box of its vertices
 //   k_reach        one thread per leaf, templated on the law's scalar and on P, run twice (count, then
@@ -40,6 +43,7 @@
 
 #include "../../include/ehmpc.h"
 #include "ehm_cells_dev.h"
+#include "ehm_radii_dev.h"
 #include "ehm_scan_dev.h"
 #include "ehm_verdict.h"
 
@@ -77,6 +81,15 @@ struct ReachArgs {
     const int32_t* indptr;          // [n_leaf + 1], nullptr in the count pass
     int32_t* indices;
     unsigned long long* total;      // the count pass: the sum of the counts
+};
+
+// The per-leaf boxes of DESIGN.md 3.8k, for the PER_LEAF instances alone: their own kernel argument,
+// so that the other instances keep theirs.  Every lane copies its leaf's box, read leaf-fastest from
+// `box`, into a slice of LDS of its own, 2 n_d + 1 doubles apart (an odd stride), at o_box.
+struct LeafBoxes {
+    const double* box;              // [2][n_d][box_n] (k_leaf_radii)
+    long long box_n;
+    int o_box;
 };
 
 // row i of Y [(P+1) P] into v [P] by selects, so Y stays in registers
@@ -154,9 +167,12 @@ __device__ __forceinline__ void node_decision(const T* __restrict__ node, int k,
 
 // Everything of one leaf in one pass.  PER_MODE: the generator block is G_m of the leaf's mode, the
 // blocks P n_d doubles apart; else the shared E, and the code is that of 3.8i.
-template <class T, int P, bool PER_MODE>
+// PER_LEAF (with PER_MODE): the box is the leaf's own, copied from LB into the lane's slice of LDS
+// (3.8k); the traversal reads it through the same pointers.
+template <class T, int P, bool PER_MODE, bool PER_LEAF>
 __device__ __forceinline__ void leaf_reach(const ReachArgs& A, const DevPlant& PL,
-                                           const double* sh, long long q) {
+                                           const double* sh, long long q,
+                                           const LeafBoxes* LB = nullptr) {
 #pragma clang fp contract(off)
     const int32_t l = (int32_t)(A.first + q);
     const bool fill = A.indptr != nullptr;
@@ -187,6 +203,12 @@ __device__ __forceinline__ void leaf_reach(const ReachArgs& A, const DevPlant& P
     const double* sE = sh + PL.oE + (PER_MODE ? m * (P * n_d) : 0);
     const double* lo_d = sh + A.o_lo;
     const double* hi_d = sh + A.o_hi;
+    if constexpr (PER_LEAF) {
+        double* mine = const_cast<double*>(sh) + LB->o_box + (int)threadIdx.x * (2 * n_d + 1);
+        for (int k = 0; k < 2 * n_d; ++k) mine[k] = LB->box[(size_t)k * LB->box_n + l];
+        lo_d = mine;
+        hi_d = mine + n_d;
+    }
     // the vertex successors before the disturbance, in place of the cell
     for (int i = 0; i <= P; ++i) {
         double v[P];
@@ -371,7 +393,29 @@ __global__ __launch_bounds__(EHM_CORE_BLOCK) void k_reach(ReachArgs A, DevPlant 
     __syncthreads();
     const long long q = (long long)blockIdx.x * blockDim.x + t;
     if (q < A.n) {
-        leaf_reach<T, P, PER_MODE>(A, PL, sh, q);
+        leaf_reach<T, P, PER_MODE, false>(A, PL, sh, q);
+        if (!A.indptr) {
+            const int c = A.count[A.first + q];
+            if (c) atomicAdd(sum, (unsigned long long)c);
+        }
+    }
+    __syncthreads();
+    if (t == 0 && !A.indptr && *sum) atomicAdd(A.total, *sum);
+}
+
+// k_reach with the leaf's own box: the same block, the lanes' slices after the edge count
+template <class T, int P>
+__global__ __launch_bounds__(EHM_CORE_BLOCK) void k_reach_leaf(ReachArgs A, DevPlant PL,
+                                                               LeafBoxes LB) {
+    extern __shared__ __attribute__((aligned(16))) double sh[];
+    unsigned long long* sum = reinterpret_cast<unsigned long long*>(sh + PL.total);
+    const int t = threadIdx.x;
+    plant_load(PL, sh);
+    if (t == 0) *sum = 0ull;
+    __syncthreads();
+    const long long q = (long long)blockIdx.x * blockDim.x + t;
+    if (q < A.n) {
+        leaf_reach<T, P, true, true>(A, PL, sh, q, &LB);
         if (!A.indptr) {
             const int c = A.count[A.first + q];
             if (c) atomicAdd(sum, (unsigned long long)c);
@@ -450,6 +494,14 @@ typedef void (*reach_fn)(ReachArgs, DevPlant);
 const reach_fn k_reach64[2][EHM_CP] = {EHM_CORE_ALL(double, false), EHM_CORE_ALL(double, true)};
 const reach_fn k_reach32[2][EHM_CP] = {EHM_CORE_ALL(float, false), EHM_CORE_ALL(float, true)};
 #undef EHM_CORE_ALL
+// the leaf's own box (ehm_compiled_robust_core_leaf)
+typedef void (*reach_leaf_fn)(ReachArgs, DevPlant, LeafBoxes);
+#define EHM_CORE_ALL(T) {&k_reach_leaf<T, 1>, &k_reach_leaf<T, 2>, &k_reach_leaf<T, 3>, \
+                         &k_reach_leaf<T, 4>, &k_reach_leaf<T, 5>, &k_reach_leaf<T, 6>, \
+                         &k_reach_leaf<T, 7>, &k_reach_leaf<T, 8>}
+const reach_leaf_fn k_reachl64[EHM_CP] = EHM_CORE_ALL(double);
+const reach_leaf_fn k_reachl32[EHM_CP] = EHM_CORE_ALL(float);
+#undef EHM_CORE_ALL
 
 thread_local ehm_err_channel c_err;
 
@@ -471,8 +523,10 @@ namespace {
 
 // Both entry points.  ro: the robust step's boxes (the generator block of a leaf is then G_m of its
 // mode), nullptr: the shared E and the box of `o`.
+// rr (with ro): the box is the leaf's own, made here from the model for all leaves (3.8k).
 int core_run(ehm_compiled* law, const ehm_invariance_opts* o, const ehm_robust_opts* ro,
-             const ehm_core_opts* co, ehm_core_result* res, const ehm_core_leaves* lv) {
+             const ehm_robust_radii* rr, const ehm_core_opts* co, ehm_core_result* res,
+             const ehm_core_leaves* lv) {
     if (!law || !o || !co || !res || !lv) return c_err.fail(EHM_E_INVALID, "core: bad argument");
     if (o->chunk < 0) return c_err.fail(EHM_E_INVALID, "core: chunk < 0");
     if (!o->root_vertices || !o->A || !o->B || !o->w || !o->leaf_mode || !co->status)
@@ -492,6 +546,13 @@ int core_run(ehm_compiled* law, const ehm_invariance_opts* o, const ehm_robust_o
     int rc = check_law_shape(c_err, v, "core");
     if (rc) return rc;
     const int p = v.p, n_u = v.n_u;
+    RadiiPlan rp;
+    if (rr) {
+        rc = radii_plan(c_err, o, ro, rr, p, n_u, EHM_CORE_MAX_D, "robust_core_leaf", rp);
+        if (rc) return rc;
+        o = &rp.og;
+        ro = &rp.rg;
+    }
     rc = check_step_plant(c_err, o, n_u, EHM_CORE_MAX_D, "core");
     if (rc) return rc;
     RobustGen gen;
@@ -521,9 +582,22 @@ int core_run(ehm_compiled* law, const ehm_invariance_opts* o, const ehm_robust_o
     ReachArgs A{};
     Pack pk;
     pack_step_plant(pk, pl, o, p, n_u, A.o_lo, A.o_hi, ro ? o->n_modes : 1);
+    const int o_xabs = rr ? pk.put(rr->x_abs, (size_t)p) : 0;
+    const int o_uabs = rr ? pk.put(rr->u_abs, (size_t)n_u) : 0;
     pl.total = (int)pk.buf.size();
     const size_t plant_bytes = (size_t)pl.total * sizeof(double);
-    const size_t lds = plant_bytes + sizeof(unsigned long long);
+    // the per-leaf instances: a slice of 2 n_g + 1 doubles per lane after the plant and the count
+    const int n_g = o->n_d;
+    const size_t slices = rr ? (size_t)EHM_CORE_BLOCK * (2 * n_g + 1) : 0;
+    const size_t lds = plant_bytes + slices * sizeof(double) + sizeof(unsigned long long);
+    if (rr && pl.total + rr->n_data > EHM_N_MAX_LDS)
+        return c_err.fail(EHM_E_INVALID,
+                          "robust_core_leaf: plant and model need %d doubles of LDS (%d)",
+                          pl.total + (int)rr->n_data, EHM_N_MAX_LDS);
+    if (rr && lds > (size_t)EHM_N_MAX_LDS * sizeof(double))
+        return c_err.fail(EHM_E_INVALID,
+                          "robust_core_leaf: plant and the lanes' boxes need %zu bytes of LDS (%zu)",
+                          lds, (size_t)EHM_N_MAX_LDS * sizeof(double));
     EHM_HIP_TRY(c_err, hipSetDevice(v.device));
     Stream stream;
     EHM_HIP_TRY(c_err, stream.create());
@@ -551,6 +625,53 @@ int core_run(ehm_compiled* law, const ehm_invariance_opts* o, const ehm_robust_o
     hipLaunchKernelGGL(k_root_boxes, dim3(blocks_of(v.n_roots, 256)), dim3(256), 0, stream,
                        v.n_roots, p, d_roots.as<const double>(), d_box.as<double>());
     EHM_HIP_TRY(c_err, hipGetLastError());
+    // the boxes of all leaves, leaf-fastest, by the kernel of the one-step test
+    DevBuf d_model, d_lbox, d_xl, d_xn, d_ul;
+    LeafBoxes LB{};
+    double seconds_radii = 0.0;
+    if (rr) {
+        EHM_HIP_TRY(c_err, d_model.upload(rr->data, (size_t)rr->n_data * sizeof(double)));
+        EHM_HIP_TRY(c_err, d_lbox.alloc(2 * (size_t)n_g * n_leaf * sizeof(double)));
+        EHM_HIP_TRY(c_err, d_xl.alloc((size_t)n_leaf * p * sizeof(double)));
+        EHM_HIP_TRY(c_err, d_xn.alloc((size_t)n_leaf * p * sizeof(double)));
+        EHM_HIP_TRY(c_err, d_ul.alloc((size_t)n_leaf * n_u * sizeof(double)));
+        rp.nz.data = d_model.as<const double>();
+        RadiiArgs RA{};
+        RA.n = n_leaf;
+        RA.node = v.node;
+        RA.leaf_rec = v.leaf_rec;
+        RA.root_entry = v.root_entry;
+        RA.root_vertices = d_roots.as<const double>();
+        RA.par = T.view();
+        RA.leaf_mode = d_mode.as<const int32_t>();
+        RA.n_u = n_u;
+        RA.leaf_stride = v.leaf_stride;
+        RA.n_dd = rp.n_dd;
+        RA.n_v = rp.n_v;
+        RA.n_e = rp.n_e;
+        RA.n_g = n_g;
+        RA.iters = rr->radius_iters;
+        RA.o_xabs = o_xabs;
+        RA.o_uabs = o_uabs;
+        RA.box_n = n_leaf;
+        RA.box = d_lbox.as<double>();
+        RA.x_abs_leaf = d_xl.as<double>();
+        RA.x_next_abs = d_xn.as<double>();
+        RA.u_abs_leaf = d_ul.as<double>();
+        EventPair evr;
+        (void)hipEventRecord(evr.e0, stream);
+        hipLaunchKernelGGL((v.single ? k_rad32 : k_rad64)[p - 1],
+                           dim3(blocks_of(n_leaf, EHM_RAD_BLOCK)), dim3(EHM_RAD_BLOCK),
+                           plant_bytes + (size_t)rr->n_data * sizeof(double), stream, RA, pl,
+                           rp.nz);
+        (void)hipEventRecord(evr.e1, stream);
+        EHM_HIP_TRY(c_err, hipGetLastError());
+        EHM_HIP_TRY(c_err, hipStreamSynchronize(stream));
+        evr.seconds(&seconds_radii);
+        LB.box = d_lbox.as<const double>();
+        LB.box_n = n_leaf;
+        LB.o_box = pl.total + 1;         // after the block's edge count
+    }
     A.budget = 3 * v.n_int + 3;
     A.node = v.node;
     A.leaf_rec = v.leaf_rec;
@@ -576,8 +697,12 @@ int core_run(ehm_compiled* law, const ehm_invariance_opts* o, const ehm_robust_o
         A.first = first;
         A.n = n;
         const dim3 grid(blocks_of(n, EHM_CORE_BLOCK)), block(EHM_CORE_BLOCK);
-        hipLaunchKernelGGL((v.single ? k_reach32 : k_reach64)[ro ? 1 : 0][p - 1], grid, block, lds,
-                           stream, A, pl);
+        if (rr)
+            hipLaunchKernelGGL((v.single ? k_reachl32 : k_reachl64)[p - 1], grid, block, lds, stream,
+                               A, pl, LB);
+        else
+            hipLaunchKernelGGL((v.single ? k_reach32 : k_reach64)[ro ? 1 : 0][p - 1], grid, block,
+                               lds, stream, A, pl);
     };
     // the count pass, chunk by chunk: the cells go to the host for their volumes
     std::vector<double> hvert(cap * cell), vsub, volume((size_t)n_leaf, 0.0);
@@ -604,6 +729,7 @@ int core_run(ehm_compiled* law, const ehm_invariance_opts* o, const ehm_robust_o
         if (rc) return rc;
         for (size_t a = 0; a < has.size(); ++a) volume[(size_t)(off + has[a])] = vsub[a];
     }
+    res->seconds_reach += seconds_radii;
     unsigned long long total = 0;
     EHM_HIP_TRY(c_err, hipMemcpy(&total, d_total.ptr, sizeof total, hipMemcpyDeviceToHost));
     if (total > (unsigned long long)co->max_edges)
@@ -703,14 +829,22 @@ extern "C" {
 
 int ehm_compiled_core(ehm_compiled* law, const ehm_invariance_opts* o, const ehm_core_opts* co,
                       ehm_core_result* res, const ehm_core_leaves* lv) {
-    return core_run(law, o, nullptr, co, res, lv);
+    return core_run(law, o, nullptr, nullptr, co, res, lv);
 }
 
 int ehm_compiled_robust_core(ehm_compiled* law, const ehm_invariance_opts* o,
                              const ehm_robust_opts* ro, const ehm_core_opts* co,
                              ehm_core_result* res, const ehm_core_leaves* lv) {
     if (!ro) return c_err.fail(EHM_E_INVALID, "robust_core: bad argument");
-    return core_run(law, o, ro, co, res, lv);
+    return core_run(law, o, ro, nullptr, co, res, lv);
+}
+
+int ehm_compiled_robust_core_leaf(ehm_compiled* law, const ehm_invariance_opts* o,
+                                  const ehm_robust_opts* ro, const ehm_robust_radii* rr,
+                                  const ehm_core_opts* co, ehm_core_result* res,
+                                  const ehm_core_leaves* lv) {
+    if (!ro || !rr || !o) return c_err.fail(EHM_E_INVALID, "robust_core_leaf: bad argument");
+    return core_run(law, o, ro, rr, co, res, lv);
 }
 
 }  // extern "C"

@@ -18,6 +18,16 @@
 //                    order: the row [n_f | c_f] is the same for all lanes (a wave-uniform load), the
 //                    slack is read at [f][m]; the counts by the LDS counters of ehm_verdict.h
 //
+// With per-leaf error boxes (ehm_compiled_robust_successors_leaf) the box differs from
+// leaf to leaf, so no table holds the sum over the generators:
+//   k_leaf_radii        (ehm_radii_dev.h) one thread per requested leaf: the leaf's box, leaf-fastest
+//   k_robust_ng         one thread per (facet, mode): nG[f][m][k] = n_f . G_m[:, k], k_robust_slack's sum
+//   k_robust_step_leaf  k_robust_step over the same body (LEAF): the v box of the region rows is the
+//                       leaf's, the facet value (mn_f - c_f) + sum_k min(nG_k lo_k(L), nG_k hi_k(L))
+//                       from 0 in k order -- with constant boxes k_robust_slack's value bit for bit
+// The new arguments travel in a struct of their own (LeafBox), so k_robust_step compiles to the code it
+// had.
+//
 // The plant, G, the boxes and the region rows sit in LDS (plant_load).  Every operation a result
 // depends on runs under fp contract(off) in a fixed order (tests/robust_cpu.py is the numpy mirror).
 // The worst leaf and the volumes are taken on the host in leaf order, so no result depends on the
@@ -32,6 +42,7 @@
 
 #include "../../include/ehmpc.h"
 #include "ehm_cells_dev.h"
+#include "ehm_radii_dev.h"
 #include "ehm_verdict.h"
 
 #define EHM_ROB_BLOCK 64
@@ -66,6 +77,15 @@ struct RobustArgs {
     unsigned long long* counters;   // [EHM_ROB_STATUSES]
 };
 
+// The per-leaf boxes of DESIGN.md 3.8k, for the LEAF instances alone: their own kernel argument, so
+// that the other instances keep theirs.
+struct LeafBox {
+    const double* box;              // [2][n_g][box_n], leaf-fastest (k_leaf_radii)
+    long long box_n;
+    const double* nG;               // [n_facets][n_modes][n_g]
+    int n_g, n_dd, n_v;
+};
+
 // a beats b as the smaller value: the smaller number, a NaN before any number; the earlier stays on
 // ties
 __device__ __forceinline__ bool value_beats(double a, double b) {
@@ -94,10 +114,31 @@ __global__ void k_robust_slack(long long n_facets, int n_modes, int p, int n_g,
     slack[t] = s;
 }
 
-// Everything of one leaf; returns its status.
-template <class T, int P>
+// nG[f][m][k] = ((0 + n_f0 G_m[0][k]) + ..): the sum of k_robust_slack, kept per generator for the
+// boxes that differ from leaf to leaf
+__global__ void k_robust_ng(long long n_facets, int n_modes, int p, int n_g,
+                            const double* __restrict__ facets, const double* __restrict__ G,
+                            double* __restrict__ nG) {
+#pragma clang fp contract(off)
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_facets * n_modes) return;
+    const long long f = t / n_modes;
+    const int m = (int)(t - f * n_modes);
+    const double* nf = facets + (size_t)f * (p + 1);
+    const double* Gm = G + (size_t)m * p * n_g;
+    for (int k = 0; k < n_g; ++k) {
+        double ng = 0.0;
+        for (int c = 0; c < p; ++c) ng = ng + nf[c] * Gm[c * n_g + k];
+        nG[(size_t)t * n_g + k] = ng;
+    }
+}
+
+// Everything of one leaf; returns its status.  LEAF: the v box of the region rows and the box of the
+// facet sums are the leaf's own (LB); else LB is not read and the code is that of
+// 3.8j.
+template <class T, int P, bool LEAF>
 __device__ __forceinline__ int leaf_robust(const RobustArgs& A, const DevPlant& PL,
-                                           const double* sh, long long q) {
+                                           const double* sh, long long q, const LeafBox* LB) {
 #pragma clang fp contract(off)
     const int32_t l = A.leaf_ids ? A.leaf_ids[q] : (int32_t)(A.first + q);
     const int n_u = A.n_u;
@@ -118,6 +159,14 @@ __device__ __forceinline__ int leaf_robust(const RobustArgs& A, const DevPlant& 
     const double* v_lo = sh + A.o_vlo;
     const double* v_hi = sh + A.o_vhi;
     bool in_region = true;
+    double vl[P], vh[P];
+    if constexpr (LEAF) {
+#pragma unroll
+        for (int c = 0; c < P; ++c) {
+            vl[c] = LB->n_v ? LB->box[(size_t)(LB->n_dd + c) * LB->box_n + q] : 0.0;
+            vh[c] = LB->n_v ? LB->box[(size_t)(LB->n_g + LB->n_dd + c) * LB->box_n + q] : 0.0;
+        }
+    }
     for (int r = PL.row0[m]; r < PL.row0[m + 1]; ++r) {
         double H[P];
 #pragma unroll
@@ -134,7 +183,15 @@ __device__ __forceinline__ int leaf_robust(const RobustArgs& A, const DevPlant& 
 #pragma unroll
         for (int c = 0; c < P; ++c) {
             const double g = 0.0 - H[c];
-            const double a = g * v_lo[c], b = g * v_hi[c];
+            double lo_c, hi_c;
+            if constexpr (LEAF) {
+                lo_c = vl[c];
+                hi_c = vh[c];
+            } else {
+                lo_c = v_lo[c];
+                hi_c = v_hi[c];
+            }
+            const double a = g * lo_c, b = g * hi_c;
             rs = rs + (a > b ? a : b);
         }
         in_region = in_region && (smax + rs <= sh[PL.oh + r] + A.tol_exit);
@@ -191,7 +248,21 @@ __device__ __forceinline__ int leaf_robust(const RobustArgs& A, const DevPlant& 
             mn = b ? s : mn;
             at = b ? i : at;
         }
-        const double val = (mn - nf[P]) + slack[(size_t)f * PL.n_modes];
+        double sl;
+        if constexpr (LEAF) {
+            const double* __restrict__ ng = LB->nG + ((size_t)f * PL.n_modes + m) * LB->n_g;
+            const double* __restrict__ bl = LB->box + q;
+            const double* __restrict__ bh = LB->box + (size_t)LB->n_g * LB->box_n + q;
+            sl = 0.0;
+            for (int k = 0; k < LB->n_g; ++k) {
+                const double a = ng[k] * bl[(size_t)k * LB->box_n];
+                const double b = ng[k] * bh[(size_t)k * LB->box_n];
+                sl = sl + (a < b ? a : b);
+            }
+        } else {
+            sl = slack[(size_t)f * PL.n_modes];
+        }
+        const double val = (mn - nf[P]) + sl;
         all_hold = all_hold && (val >= -A.thr);
         if (best_at < 0 || value_beats(val, best)) {
             best = val;
@@ -203,8 +274,9 @@ __device__ __forceinline__ int leaf_robust(const RobustArgs& A, const DevPlant& 
     return !in_region ? ROB_MODE_REGION : all_hold ? ROB_INVARIANT : ROB_EXITS;
 }
 
-template <class T, int P>
-__global__ __launch_bounds__(EHM_ROB_BLOCK) void k_robust_step(RobustArgs A, DevPlant PL) {
+template <class T, int P, bool LEAF>
+__device__ __forceinline__ void robust_block(const RobustArgs& A, const DevPlant& PL,
+                                             const LeafBox* LB) {
     // all of the block's LDS is dynamic: the plant, G, the boxes and the region rows (PL.total
     // doubles), the status counters after them
     extern __shared__ __attribute__((aligned(16))) double sh[];
@@ -214,7 +286,7 @@ __global__ __launch_bounds__(EHM_ROB_BLOCK) void k_robust_step(RobustArgs A, Dev
     __syncthreads();
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q < A.n) {
-        const int s = leaf_robust<T, P>(A, PL, sh, q);
+        const int s = leaf_robust<T, P, LEAF>(A, PL, sh, q, LB);
         A.status[q] = s;
         atomicAdd(&cnt[s], 1u);
     }
@@ -222,12 +294,31 @@ __global__ __launch_bounds__(EHM_ROB_BLOCK) void k_robust_step(RobustArgs A, Dev
     ehm_verdict::counters_flush<EHM_ROB_BLOCK, EHM_ROB_STATUSES>(cnt, A.counters);
 }
 
+template <class T, int P>
+__global__ __launch_bounds__(EHM_ROB_BLOCK) void k_robust_step(RobustArgs A, DevPlant PL) {
+    robust_block<T, P, false>(A, PL, nullptr);
+}
+
+template <class T, int P>
+__global__ __launch_bounds__(EHM_ROB_BLOCK) void k_robust_step_leaf(RobustArgs A, DevPlant PL,
+                                                                    LeafBox LB) {
+    robust_block<T, P, true>(A, PL, &LB);
+}
+
 typedef void (*robust_fn)(RobustArgs, DevPlant);
+typedef void (*robust_leaf_fn)(RobustArgs, DevPlant, LeafBox);
 #define EHM_ROB_ALL(T) {&k_robust_step<T, 1>, &k_robust_step<T, 2>, &k_robust_step<T, 3>, \
                         &k_robust_step<T, 4>, &k_robust_step<T, 5>, &k_robust_step<T, 6>, \
                         &k_robust_step<T, 7>, &k_robust_step<T, 8>}
 const robust_fn k_rob64[EHM_CP] = EHM_ROB_ALL(double);
 const robust_fn k_rob32[EHM_CP] = EHM_ROB_ALL(float);
+#undef EHM_ROB_ALL
+#define EHM_ROB_ALL(T) {&k_robust_step_leaf<T, 1>, &k_robust_step_leaf<T, 2>, \
+                        &k_robust_step_leaf<T, 3>, &k_robust_step_leaf<T, 4>, \
+                        &k_robust_step_leaf<T, 5>, &k_robust_step_leaf<T, 6>, \
+                        &k_robust_step_leaf<T, 7>, &k_robust_step_leaf<T, 8>}
+const robust_leaf_fn k_robl64[EHM_CP] = EHM_ROB_ALL(double);
+const robust_leaf_fn k_robl32[EHM_CP] = EHM_ROB_ALL(float);
 #undef EHM_ROB_ALL
 
 thread_local ehm_err_channel b_err;
@@ -244,10 +335,21 @@ int ehm_robust_abi_sizes(int64_t* sizes, int32_t n) {
     return ehm_copy_abi_sizes(all, (int32_t)(sizeof all / sizeof all[0]), sizes, n);
 }
 
-int ehm_compiled_robust_successors(ehm_compiled* law, const ehm_invariance_opts* o,
-                                   const ehm_robust_opts* ro, ehm_robust_result* res,
-                                   const ehm_robust_leaves* lv) {
-    const char* who = "robust_successors";
+int ehm_robust_radii_abi_sizes(int64_t* sizes, int32_t n) {
+    const int64_t all[] = {(int64_t)sizeof(ehm_robust_radii),
+                           (int64_t)sizeof(ehm_robust_leaf_boxes)};
+    return ehm_copy_abi_sizes(all, (int32_t)(sizeof all / sizeof all[0]), sizes, n);
+}
+
+}  // extern "C"
+
+namespace {
+
+// Both entry points.  rr: the boxes are the leaf's own, made from the model (lb takes
+// them, or is nullptr); nullptr: the boxes of `o` and `ro` (3.8j).
+int robust_run(ehm_compiled* law, const ehm_invariance_opts* o, const ehm_robust_opts* ro,
+               const ehm_robust_radii* rr, ehm_robust_result* res, const ehm_robust_leaves* lv,
+               ehm_robust_leaf_boxes* lb, const char* who) {
     if (!law || !o || !ro || !res || !lv) return b_err.fail(EHM_E_INVALID, "%s: bad argument", who);
     if (o->n < 0 || o->chunk < 0) return b_err.fail(EHM_E_INVALID, "%s: n or chunk < 0", who);
     if (!o->root_vertices || !o->A || !o->B || !o->w || !o->leaf_mode || !ro->facets)
@@ -264,11 +366,20 @@ int ehm_compiled_robust_successors(ehm_compiled* law, const ehm_invariance_opts*
     if (ro->n_facets < 1 || ro->n_facets * (p + 1) >= 0x7fffffffLL)
         return b_err.fail(EHM_E_INVALID, "%s: %lld facets (1 .. (2^31 - 1) / (p + 1))", who,
                           (long long)ro->n_facets);
-    rc = check_step_plant(b_err, o, n_u, EHM_ROB_MAX_G, who);
-    if (rc) return rc;
-    RobustGen gen;
-    rc = robust_generators(b_err, o, ro, p, n_u, EHM_ROB_MAX_G, who, gen);
-    if (rc) return rc;
+    RadiiPlan rp;
+    RobustGen gen0;
+    if (rr) {
+        rc = radii_plan(b_err, o, ro, rr, p, n_u, EHM_ROB_MAX_G, who, rp);
+        if (rc) return rc;
+        o = &rp.og;
+        ro = &rp.rg;
+    } else {
+        rc = check_step_plant(b_err, o, n_u, EHM_ROB_MAX_G, who);
+        if (rc) return rc;
+        rc = robust_generators(b_err, o, ro, p, n_u, EHM_ROB_MAX_G, who, gen0);
+        if (rc) return rc;
+    }
+    const RobustGen& gen = rr ? rp.gen : gen0;
     DevPlant pl{};
     int rows = 0;
     for (int m = 0; m < o->n_modes; ++m) {
@@ -287,6 +398,7 @@ int ehm_compiled_robust_successors(ehm_compiled* law, const ehm_invariance_opts*
     res->worst_leaf = -1;
     res->worst_margin = NAN;
     res->n_generators = gen.n_g;
+    if (lb) lb->seconds_radii = 0.0;
     if (o->n == 0) return EHM_OK;
     const size_t cell = (size_t)(p + 1) * p;
     double scale = 0.0;
@@ -305,9 +417,14 @@ int ehm_compiled_robust_successors(ehm_compiled* law, const ehm_invariance_opts*
     pl.oH = pk.put(o->H, (size_t)rows * p);
     pl.oh = pk.put(o->h, (size_t)rows);
     const int o_vlo = pk.put(ro->v_lo, (size_t)p), o_vhi = pk.put(ro->v_hi, (size_t)p);
+    const int o_xabs = rr ? pk.put(rr->x_abs, (size_t)p) : 0;
+    const int o_uabs = rr ? pk.put(rr->u_abs, (size_t)n_u) : 0;
     pl.total = (int)pk.buf.size();
     const size_t plant_bytes = (size_t)pl.total * sizeof(double);
     const size_t lds = plant_bytes + EHM_ROB_STATUSES * sizeof(unsigned int);
+    if (rr && pl.total + rr->n_data > EHM_N_MAX_LDS)
+        return b_err.fail(EHM_E_INVALID, "%s: plant and model need %d doubles of LDS (%d)", who,
+                          pl.total + (int)rr->n_data, EHM_N_MAX_LDS);
     EHM_HIP_TRY(b_err, hipSetDevice(v.device));
     Stream stream;
     EHM_HIP_TRY(b_err, stream.create());
@@ -327,12 +444,31 @@ int ehm_compiled_robust_successors(ehm_compiled* law, const ehm_invariance_opts*
     EHM_HIP_TRY(b_err, d_cnt.alloc(EHM_ROB_STATUSES * sizeof(unsigned long long)));
     EHM_HIP_TRY(b_err, hipMemsetAsync(d_cnt.ptr, 0, EHM_ROB_STATUSES * sizeof(unsigned long long),
                                       stream));
-    EventPair ev;
+    // the per-leaf boxes: the model, the box of a chunk, the bounds, the table nG
+    const int n_g = gen.n_g;
+    DevBuf d_model, d_box, d_xl, d_xn, d_ul, d_ng;
+    RadiiArgs RA{};
+    LeafBox LB{};
+    if (rr) {
+        EHM_HIP_TRY(b_err, d_model.upload(rr->data, (size_t)rr->n_data * sizeof(double)));
+        EHM_HIP_TRY(b_err, d_box.alloc(2 * (size_t)n_g * cap * sizeof(double)));
+        EHM_HIP_TRY(b_err, d_xl.alloc(cap * p * sizeof(double)));
+        EHM_HIP_TRY(b_err, d_xn.alloc(cap * p * sizeof(double)));
+        EHM_HIP_TRY(b_err, d_ul.alloc(cap * n_u * sizeof(double)));
+        EHM_HIP_TRY(b_err, d_ng.alloc((size_t)ro->n_facets * o->n_modes * n_g * sizeof(double)));
+        rp.nz.data = d_model.as<const double>();
+    }
+    EventPair ev, ev_radii;
     (void)hipEventRecord(ev.e0, stream);
-    hipLaunchKernelGGL(k_robust_slack, dim3(blocks_of(ro->n_facets * o->n_modes, 256)), dim3(256),
-                       0, stream, (long long)ro->n_facets, (int)o->n_modes, p, gen.n_g,
-                       d_facets.as<const double>(), pl.data + pl.oE, pl.data + o_lo,
-                       pl.data + o_hi, d_slack.as<double>());
+    if (rr)
+        hipLaunchKernelGGL(k_robust_ng, dim3(blocks_of(ro->n_facets * o->n_modes, 256)), dim3(256),
+                           0, stream, (long long)ro->n_facets, (int)o->n_modes, p, n_g,
+                           d_facets.as<const double>(), pl.data + pl.oE, d_ng.as<double>());
+    else
+        hipLaunchKernelGGL(k_robust_slack, dim3(blocks_of(ro->n_facets * o->n_modes, 256)),
+                           dim3(256), 0, stream, (long long)ro->n_facets, (int)o->n_modes, p,
+                           gen.n_g, d_facets.as<const double>(), pl.data + pl.oE, pl.data + o_lo,
+                           pl.data + o_hi, d_slack.as<double>());
     (void)hipEventRecord(ev.e1, stream);
     EHM_HIP_TRY(b_err, hipGetLastError());
     EHM_HIP_TRY(b_err, hipStreamSynchronize(stream));
@@ -364,6 +500,37 @@ int ehm_compiled_robust_successors(ehm_compiled* law, const ehm_invariance_opts*
     A.status = d_status.as<int32_t>();
     A.margin = d_margin.as<double>();
     A.worst = d_worst.as<int32_t>();
+    if (rr) {
+        RA.leaf_ids = A.leaf_ids;
+        RA.node = A.node;
+        RA.leaf_rec = A.leaf_rec;
+        RA.root_entry = A.root_entry;
+        RA.root_vertices = A.root_vertices;
+        RA.par = A.par;
+        RA.leaf_mode = A.leaf_mode;
+        RA.n_u = n_u;
+        RA.leaf_stride = v.leaf_stride;
+        RA.n_dd = rp.n_dd;
+        RA.n_v = rp.n_v;
+        RA.n_e = rp.n_e;
+        RA.n_g = n_g;
+        RA.iters = rr->radius_iters;
+        RA.o_xabs = o_xabs;
+        RA.o_uabs = o_uabs;
+        RA.box_n = (long long)cap;
+        RA.box = d_box.as<double>();
+        RA.x_abs_leaf = d_xl.as<double>();
+        RA.x_next_abs = d_xn.as<double>();
+        RA.u_abs_leaf = d_ul.as<double>();
+        LB.box = d_box.as<const double>();
+        LB.box_n = (long long)cap;
+        LB.nG = d_ng.as<const double>();
+        LB.n_g = n_g;
+        LB.n_dd = rp.n_dd;
+        LB.n_v = rp.n_v;
+    }
+    const size_t lds_radii = rr ? plant_bytes + (size_t)rr->n_data * sizeof(double) : 0;
+    std::vector<double> hbox(lb ? 2 * (size_t)n_g * cap : 0);
     std::vector<double> hvert(cap * cell), vsub;
     std::vector<long long> has;
     bool have_worst = false;
@@ -376,10 +543,42 @@ int ehm_compiled_robust_successors(ehm_compiled* law, const ehm_invariance_opts*
         A.n = nc;
         A.first = off;
         const dim3 grid(blocks_of(nc, EHM_ROB_BLOCK)), block(EHM_ROB_BLOCK);
+        if (rr) {
+            RA.n = nc;
+            RA.first = off;
+            (void)hipEventRecord(ev_radii.e0, stream);
+            hipLaunchKernelGGL((v.single ? k_rad32 : k_rad64)[p - 1], grid, dim3(EHM_RAD_BLOCK),
+                               lds_radii, stream, RA, pl, rp.nz);
+            (void)hipEventRecord(ev_radii.e1, stream);
+            EHM_HIP_TRY(b_err, hipGetLastError());
+        }
         (void)hipEventRecord(ev.e0, stream);
-        hipLaunchKernelGGL((v.single ? k_rob32 : k_rob64)[p - 1], grid, block, lds, stream, A, pl);
+        if (rr)
+            hipLaunchKernelGGL((v.single ? k_robl32 : k_robl64)[p - 1], grid, block, lds, stream, A,
+                               pl, LB);
+        else
+            hipLaunchKernelGGL((v.single ? k_rob32 : k_rob64)[p - 1], grid, block, lds, stream, A,
+                               pl);
         (void)hipEventRecord(ev.e1, stream);
         EHM_HIP_TRY(b_err, hipGetLastError());
+        if (lb) {
+            if (!hbox.empty())
+                EHM_HIP_TRY(b_err, hipMemcpyAsync(hbox.data(), d_box.ptr,
+                                                  hbox.size() * sizeof(double),
+                                                  hipMemcpyDeviceToHost, stream));
+            if (lb->x_abs_leaf)
+                EHM_HIP_TRY(b_err, hipMemcpyAsync(lb->x_abs_leaf + off * p, d_xl.ptr,
+                                                  (size_t)nc * p * sizeof(double),
+                                                  hipMemcpyDeviceToHost, stream));
+            if (lb->x_next_abs)
+                EHM_HIP_TRY(b_err, hipMemcpyAsync(lb->x_next_abs + off * p, d_xn.ptr,
+                                                  (size_t)nc * p * sizeof(double),
+                                                  hipMemcpyDeviceToHost, stream));
+            if (lb->u_abs_leaf)
+                EHM_HIP_TRY(b_err, hipMemcpyAsync(lb->u_abs_leaf + off * n_u, d_ul.ptr,
+                                                  (size_t)nc * n_u * sizeof(double),
+                                                  hipMemcpyDeviceToHost, stream));
+        }
         EHM_HIP_TRY(b_err, hipMemcpyAsync(hvert.data(), d_vert.ptr,
                                           (size_t)nc * cell * sizeof(double),
                                           hipMemcpyDeviceToHost, stream));
@@ -396,6 +595,22 @@ int ehm_compiled_robust_successors(ehm_compiled* law, const ehm_invariance_opts*
         double s = 0.0;
         ev.seconds(&s);
         res->seconds += s;
+        if (rr && lb) {
+            ev_radii.seconds(&s);
+            lb->seconds_radii += s;
+            // the chunk's box, leaf-fastest, into the caller's arrays by kind: [n][2][dim]
+            struct { double* out; int col0, dim; } kinds[4] = {
+                {lb->d, 0, rp.n_dd}, {lb->v, rp.n_dd, rp.n_v},
+                {lb->e, rp.n_dd + rp.n_v, rp.n_e}, {lb->v_next, rp.n_dd + rp.n_v + rp.n_e, rp.n_v}};
+            for (const auto& kd : kinds) {
+                if (!kd.out) continue;
+                for (long long q = 0; q < nc; ++q)
+                    for (int side = 0; side < 2; ++side)
+                        for (int k = 0; k < kd.dim; ++k)
+                            kd.out[((size_t)(off + q) * 2 + side) * kd.dim + k] =
+                                hbox[((size_t)side * n_g + kd.col0 + k) * cap + (size_t)q];
+            }
+        }
         // the worst leaf and the volumes, in leaf order
         has.clear();
         for (long long q = 0; q < nc; ++q) {
@@ -420,6 +635,24 @@ int ehm_compiled_robust_successors(ehm_compiled* law, const ehm_invariance_opts*
     EHM_HIP_TRY(b_err, hipMemcpy(cnt, d_cnt.ptr, sizeof cnt, hipMemcpyDeviceToHost));
     for (int i = 0; i < EHM_ROB_STATUSES; ++i) res->counts[i] = (int64_t)cnt[i];
     return EHM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ehm_compiled_robust_successors(ehm_compiled* law, const ehm_invariance_opts* o,
+                                   const ehm_robust_opts* ro, ehm_robust_result* res,
+                                   const ehm_robust_leaves* lv) {
+    return robust_run(law, o, ro, nullptr, res, lv, nullptr, "robust_successors");
+}
+
+int ehm_compiled_robust_successors_leaf(ehm_compiled* law, const ehm_invariance_opts* o,
+                                        const ehm_robust_opts* ro, const ehm_robust_radii* rr,
+                                        ehm_robust_result* res, const ehm_robust_leaves* lv,
+                                        ehm_robust_leaf_boxes* lb) {
+    if (!rr) return b_err.fail(EHM_E_INVALID, "robust_successors_leaf: bad argument");
+    return robust_run(law, o, ro, rr, res, lv, lb, "robust_successors_leaf");
 }
 
 }  // extern "C"

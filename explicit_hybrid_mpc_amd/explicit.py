@@ -541,7 +541,8 @@ class ExplicitMPC:
         """
         ``CompiledLaw.robust_successors`` (robust.py) for this law: compiles it
         (``compile(spine=spine, dtype=dtype, flush=flush)``) and asks where its input sends every
-        leaf under measurement and input error; ``kw`` as ``CompiledLaw.robust_successors``.
+        leaf under measurement and input error; ``kw`` as ``CompiledLaw.robust_successors``
+        (``radii='leaf'``, ``radius_iters``: the per-leaf boxes of DESIGN.md 3.8k).
         Returns its ``robust.RobustSuccessorResult``.
         """
         law = self.compile(dtype=dtype, spine=spine, flush=flush)
@@ -554,7 +555,8 @@ class ExplicitMPC:
         """
         ``CompiledLaw.robust_core`` (robust.py) for this law: compiles it
         (``compile(spine=spine, dtype=dtype, flush=flush)``) and finds the leaves the noisy closed
-        loop never leaves; ``kw`` as ``CompiledLaw.robust_core``.  Returns its
+        loop never leaves; ``kw`` as ``CompiledLaw.robust_core`` (``radii``, ``radius_iters``
+        included).  Returns its
         ``invariance.CoreResult``, whose ``contains`` needs the compiled law and is not available
         here.
         """

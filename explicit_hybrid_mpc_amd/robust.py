@@ -6,6 +6,8 @@ csrc/ehm_robust.hip; the relation by csrc/ehm_core.hip):
     res = law.robust_successors(noise=NoiseModel.from_mpc(mpc))     # boxes from the model
     res.status, res.margin, res.worst, res.counts, res.boxes, res.holds_on_set
     core = law.robust_core(noise=model)                             # an invariance.CoreResult
+    res = law.robust_successors(noise=model, radii='leaf')          # a box per leaf (3.8k)
+    res.leaf_boxes, res.x_abs_leaf, res.x_next_abs, res.u_abs_leaf
 
 The argument.  The noisy closed loop (``rollout(..., noise=)``) evaluates the law at the measured
 state z = x + v, tests the region of the leaf's mode m on the true state x = z - v and steps the plant
@@ -27,6 +29,18 @@ state of it has, for any errors of the boxes and at every length, every measured
 and in a core leaf, every true state in its mode's region and within the v box of the set.  Not
 covered: the rounding of a single law's evaluation at interior points, the hand-over within rounding
 of a split face, the recovery error of the root vertices, guarded plants (refused).
+
+Per-leaf radii (``radii='leaf'``).  With ``noise=`` the boxes above are
+``noise.bounding_boxes`` at one global bound, so a state-dependent radius is taken at the set's corner
+for every leaf.  The rollout draws v_t at the true state x_t and the last input u_(t-1), e_t and d_t at
+x_t and u_t = u(z_t), v_(t+1) at x_(t+1) and u_t.  For z_t in the cell of leaf L: |x_t| <= a_L, found
+by ``radius_iters`` steps of a <- min(a, c_L + vhalf(a, u_abs)) from the global x_abs (every iterate
+is a valid bound by monotonicity alone); |u_t| <= ubar_L, the largest vertex input modulus of L;
+|x_(t+1)| <= a'_L = min(x_abs, max_i |y_i| + |E| dmax_L + |A_m| vmax_L + |B_m| emax_L).  So
+v_L = box_state(a_L, u_abs), e_L = box_input(a_L, ubar_L), d_L = box_process(a_L, ubar_L),
+v'_L = box_state(a'_L, ubar_L), and the image of L is hull{y_i} + G_m [d_L; v_L; e_L; v'_L].  The device
+makes the boxes from the packed model the rollout uses; statuses, margins and the core's promises are
+the ones above, read leaf by leaf.
 """
 
 import ctypes
@@ -38,6 +52,8 @@ from . import noise as noise_mod
 from ._capi import ptr
 
 MAX_G = 64                      # EHM_ROB_MAX_G: generators n_d + 2 p + n_u
+RADII = ('global', 'leaf')
+MAX_RADIUS_ITERS = 16           # EHM_RAD_MAX_ITERS
 
 _check = _capi.checker('ehm_robust_last_error')
 
@@ -53,19 +69,27 @@ class RobustSuccessorResult:
     ``worst_margin``; ``seconds`` of the kernel, ``seconds_slack`` of the facet-by-mode table;
     ``n_facets``, ``n_generators``; ``boxes``: the dict of (lo, hi) by kind that was certified
     ('process', 'state', 'input'; None for a kind without a box), and with ``noise=`` the global
-    bounds they were made from, ``x_abs`` and ``u_abs`` (else None); ``set_convex``;
+    bounds they were made from, ``x_abs`` and ``u_abs`` (else None); ``radii`` ('global' or 'leaf');
+    with ``radii='leaf'`` ``leaf_boxes``, a dict with 'process', 'state', 'input'
+    and 'state_next', each [n, 2, dim] (lo, hi per requested leaf; None for a kind without terms; NaN
+    for a leaf without a cell or mode), ``x_abs_leaf`` [n, p] (a_L), ``x_next_abs`` [n, p] (a'_L),
+    ``u_abs_leaf`` [n, n_u] (ubar_L), ``radius_iters``, ``seconds_radii`` -- ``boxes``, ``x_abs`` and
+    ``u_abs`` stay the global ones the iteration starts from -- else all None; ``set_convex``;
     ``holds_on_set``: every requested leaf is invariant, every leaf was requested, and the set is
     convex.  Without a convex set the facets bound nothing and ``invariant`` proves nothing.
     """
+
+    radii = 'global'
+    leaf_boxes = x_abs_leaf = x_next_abs = u_abs_leaf = radius_iters = seconds_radii = None
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
 
     def __repr__(self):
-        return 'RobustSuccessorResult(n=%d, counts=%r, invariant_volume_fraction=%.6g, ' \
+        return 'RobustSuccessorResult(n=%d, radii=%r, counts=%r, invariant_volume_fraction=%.6g, ' \
             'worst_margin=%.3g, n_generators=%d, set_convex=%s, holds_on_set=%s)' % (
-                self.n, self.counts, self.invariant_volume_fraction, self.worst_margin,
-                self.n_generators, self.set_convex, self.holds_on_set)
+                self.n, self.radii, self.counts, self.invariant_volume_fraction,
+                self.worst_margin, self.n_generators, self.set_convex, self.holds_on_set)
 
 
 def _pair(box, size, name, holds_zero):
@@ -86,11 +110,42 @@ def _pair(box, size, name, holds_zero):
     return lo, hi
 
 
+def _radii_args(radii, radius_iters, noise, d_box, v_box, e_box):
+    """(radii, radius_iters) checked; what ``radii='leaf'`` refuses needs no law."""
+    if radii not in RADII:
+        raise ValueError("radii must be 'global' or 'leaf', not %r" % (radii,))
+    try:
+        iters = int(radius_iters)
+        whole = iters == radius_iters
+    except (TypeError, ValueError):
+        whole = False
+    if not whole or not 1 <= iters <= MAX_RADIUS_ITERS:
+        raise ValueError('radius_iters must be an integer in 1..%d, not %r' % (MAX_RADIUS_ITERS,
+                                                                               radius_iters))
+    if radii == 'leaf':
+        if noise is None:
+            raise ValueError("radii='leaf' makes the boxes of every leaf from a model: give noise=")
+        if not (d_box is None and v_box is None and e_box is None):
+            raise ValueError("radii='leaf' makes the boxes of every leaf from the model: give no "
+                             'boxes')
+        const = noise_mod.bounding_boxes(noise, np.zeros(noise.n_x), np.zeros(noise.n_u))
+        for kind, name in (('state', 'v'), ('input', 'e')):
+            lo, hi = const[kind]
+            if not ((lo <= 0.).all() and (hi >= 0.).all()):
+                raise ValueError("radii='leaf': the constant part of the %s box must hold 0 (a "
+                                 "leaf's box is a subset of the global one): [%s, %s]" % (name, lo,
+                                                                                          hi))
+    return radii, iters
+
+
 class _RobustStep(invariance._Step):
     """``invariance._Step`` with the three boxes resolved: ``boxes`` (dict by kind of (lo, hi) or
     None), ``x_abs`` / ``u_abs`` (with ``noise=``), ``tol_set``, and ``robust_opts()``."""
 
-    def __init__(self, law, plant, d_box, v_box, e_box, noise, tol_exit, tol_set, chunk=0):
+    def __init__(self, law, plant, d_box, v_box, e_box, noise, tol_exit, tol_set, chunk=0,
+                 radii='global', radius_iters=3):
+        self.radii, self.radius_iters = _radii_args(radii, radius_iters, noise, d_box, v_box, e_box)
+        self.noise = noise
         if noise is not None and not (d_box is None and v_box is None and e_box is None):
             raise ValueError('noise= fills all three boxes: give it or boxes, not both')
         self.tol_set = float(tol_set)
@@ -132,6 +187,21 @@ class _RobustStep(invariance._Step):
         if self.n_g > MAX_G:
             raise ValueError('%d generators (n_d + 2 p + n_u), at most %d' % (self.n_g, MAX_G))
 
+    def radii_opts(self):
+        """The ``RobustRadii`` of ``radii='leaf'``: the packed model, the global bounds, the
+        iterations.  The arrays live as long as this object."""
+        desc, data = self.noise.pack()
+        self._packed = (np.ascontiguousarray(desc, dtype=np.int32),
+                        np.ascontiguousarray(data, dtype=np.float64),
+                        np.ascontiguousarray(self.x_abs, dtype=np.float64),
+                        np.ascontiguousarray(self.u_abs, dtype=np.float64))
+        desc, data, x_abs, u_abs = self._packed
+        return _capi.RobustRadii(
+            desc=ptr(desc) if desc.size else None, data=ptr(data) if data.size else None,
+            x_abs=ptr(x_abs), u_abs=ptr(u_abs), n_terms=int(desc.shape[0]), n_data=int(data.size),
+            n_x=self.noise.n_x, n_u=self.noise.n_u, n_d=self.noise.n_d,
+            radius_iters=self.radius_iters)
+
     def robust_opts(self):
         v, e = self.boxes['state'], self.boxes['input']
         return _capi.RobustOpts(
@@ -143,11 +213,12 @@ class _RobustStep(invariance._Step):
 
 
 def robust_successors(law, plant=None, d_box=None, v_box=None, e_box=None, noise=None, leaves=None,
-                      tol_exit=1e-9, tol_set=1e-9, chunk=0):
-    """The one path to ``ehm_compiled_robust_successors``; see
+                      tol_exit=1e-9, tol_set=1e-9, chunk=0, radii='global', radius_iters=3):
+    """The one path to ``ehm_compiled_robust_successors`` and its per-leaf form; see
     ``CompiledLaw.robust_successors``."""
+    _radii_args(radii, radius_iters, noise, d_box, v_box, e_box)
     return _robust_successors(law, _RobustStep(law, plant, d_box, v_box, e_box, noise, tol_exit,
-                                               tol_set, chunk), leaves)
+                                               tol_set, chunk, radii, radius_iters), leaves)
 
 
 def _robust_successors(law, st, leaves):
@@ -161,8 +232,30 @@ def _robust_successors(law, st, leaves):
     arrays = dict(status=np.empty(n, np.int32), margin=np.empty(n), worst=np.empty(n, np.int32))
     lv = _capi.RobustLeaves(**{k: ptr(a) for k, a in arrays.items()})
     res = _capi.RobustResult()
-    _check(_capi.load().ehm_compiled_robust_successors(
-        law._handle, ctypes.byref(opts), ctypes.byref(ro), ctypes.byref(res), ctypes.byref(lv)))
+    leaf = {}
+    if st.radii == 'leaf':
+        p, n_u, model = law.p, law.n_u, st.noise
+        has = {k: any(t.kind == k for t in model.terms) for k in noise_mod.KINDS}
+        has['process'] = has['process'] and st.plant.n_d > 0
+        boxes = dict(process=np.empty((n, 2, st.plant.n_d)) if has['process'] else None,
+                     state=np.empty((n, 2, p)) if has['state'] else None,
+                     input=np.empty((n, 2, n_u)) if has['input'] else None,
+                     state_next=np.empty((n, 2, p)) if has['state'] else None)
+        leaf = dict(leaf_boxes=boxes, x_abs_leaf=np.empty((n, p)), x_next_abs=np.empty((n, p)),
+                    u_abs_leaf=np.empty((n, n_u)))
+        lb = _capi.RobustLeafBoxes(
+            d=ptr(boxes['process']), v=ptr(boxes['state']), e=ptr(boxes['input']),
+            v_next=ptr(boxes['state_next']), x_abs_leaf=ptr(leaf['x_abs_leaf']),
+            x_next_abs=ptr(leaf['x_next_abs']), u_abs_leaf=ptr(leaf['u_abs_leaf']))
+        rr = st.radii_opts()
+        _check(_capi.load().ehm_compiled_robust_successors_leaf(
+            law._handle, ctypes.byref(opts), ctypes.byref(ro), ctypes.byref(rr), ctypes.byref(res),
+            ctypes.byref(lv), ctypes.byref(lb)))
+        leaf.update(radius_iters=st.radius_iters, seconds_radii=float(lb.seconds_radii))
+    else:
+        _check(_capi.load().ehm_compiled_robust_successors(
+            law._handle, ctypes.byref(opts), ctypes.byref(ro), ctypes.byref(res),
+            ctypes.byref(lv)))
     total = float(st.roots['volume'].sum())
     counts = {name: int(res.counts[k]) for k, name in enumerate(invariance.STATUS_NAMES)}
     worst = None
@@ -177,19 +270,29 @@ def _robust_successors(law, st, leaves):
         worst_margin=float(res.worst_margin), seconds=float(res.seconds),
         seconds_slack=float(res.seconds_slack), n_facets=int(st.facet_rows.shape[0]),
         n_generators=int(res.n_generators), boxes=st.boxes, x_abs=st.x_abs, u_abs=st.u_abs,
-        set_convex=st.set_convex, tol_exit=st.tol_exit, tol_set=st.tol_set,
-        holds_on_set=bool(counts['invariant'] == n and every and st.set_convex), **arrays)
+        set_convex=st.set_convex, tol_exit=st.tol_exit, tol_set=st.tol_set, radii=st.radii,
+        holds_on_set=bool(counts['invariant'] == n and every and st.set_convex), **arrays, **leaf)
 
 
 def robust_core(law, plant=None, d_box=None, v_box=None, e_box=None, noise=None, tol_exit=1e-9,
                 tol_set=1e-9, tol_side=None, rows='invariant', return_edges=False,
-                max_fan=invariance.MAX_FAN, max_edges=invariance.MAX_EDGES):
-    """The one path to ``ehm_compiled_robust_core``; see ``CompiledLaw.robust_core``."""
+                max_fan=invariance.MAX_FAN, max_edges=invariance.MAX_EDGES, radii='global',
+                radius_iters=3):
+    """The one path to ``ehm_compiled_robust_core`` and its per-leaf form; see
+    ``CompiledLaw.robust_core``."""
+    _radii_args(radii, radius_iters, noise, d_box, v_box, e_box)
     tol_side, max_fan, max_edges = invariance._core_args(tol_exit, tol_side, rows, max_fan,
                                                          max_edges)
-    st = _RobustStep(law, plant, d_box, v_box, e_box, noise, tol_exit, tol_set)
+    st = _RobustStep(law, plant, d_box, v_box, e_box, noise, tol_exit, tol_set, 0, radii,
+                     radius_iters)
     seeds = _robust_successors(law, st, None)
     ro = st.robust_opts()
+    if st.radii == 'leaf':
+        rr = st.radii_opts()
+        return invariance._core(
+            law, st, seeds, tol_side, rows, return_edges, max_fan, max_edges,
+            lambda lib, po, co, res, lv: lib.ehm_compiled_robust_core_leaf(
+                law._handle, po, ctypes.byref(ro), ctypes.byref(rr), co, res, lv))
     return invariance._core(
         law, st, seeds, tol_side, rows, return_edges, max_fan, max_edges,
         lambda lib, po, co, res, lv: lib.ehm_compiled_robust_core(

@@ -1211,6 +1211,75 @@ const char* ehm_robust_last_error(void);
 /* ehm_abi_sizes for ehm_robust_opts, ehm_robust_result, ehm_robust_leaves, in this order. */
 int ehm_robust_abi_sizes(int64_t* sizes, int32_t n);
 
+/* ---- the same two checks with per-leaf error boxes (csrc/ehm_radii_dev.h, csrc/ehm_robust.hip,
+ * csrc/ehm_core.hip) ---------------------------------------------------------------
+ * (no counterpart in the reference)
+ *
+ * The boxes of d, v, e and v' are no longer one per call but one per leaf, made on the device from
+ * the packed uncertainty model that ehm_compiled_set_noise takes (desc [n_terms][8], data [n_data]):
+ * on leaf L every error is bounded at the states and inputs L itself can see.  box_K(a, b) is the
+ * interval hull of kind K over every draw at |x| <= a, |u| <= b: terms in model order, sums from 0.0,
+ * a box term adds mid -+ rad (mid = sum_k M_ik c_k, rad = sum_k |M_ik| h_k), a ball term -+ r dual_i
+ * with r the sampler's radius at |F| and a or b, dual_i the dual norm of row i of L.  Per leaf, one
+ * device thread (k_leaf_radii):
+ *  1. c_L[c] = max_i |V_ic| over the cell's vertices, ubar_L[k] = max_i |u_k(V_i)| (the leaf's map in
+ *     the law's arithmetic), the y_i as ehm_compiled_successors' step 4;
+ *  2. a = x_abs; radius_iters times a <- min(a, c_L + vhalf(a, u_abs)), vhalf the larger modulus of
+ *     the two bounds of box_state: a_L;
+ *  3. v_L = box_state(a_L, u_abs), e_L = box_input(a_L, ubar_L), d_L = box_process(a_L, ubar_L);
+ *  4. xplus_L = max_i |y_i| + |E| dmax_L + |A_m| vmax_L + |B_m| emax_L (in that order, column by
+ *     column), a'_L = min(x_abs, xplus_L), v'_L = box_state(a'_L, ubar_L).
+ * x_abs and u_abs are the caller's global bounds on every true state and every commanded input; they
+ * must be valid (the Python layer verifies x_abs), the iteration only ever lowers them.  The image is
+ * I(L) = hull{y_i} + G_m [d_L; v_L; e_L; v'_L]; a kind without terms has no columns in G_m.  A facet's
+ * value is (mn_f - c_f) + sum_k min(nG[f][m][k] lo_k(L), nG[f][m][k] hi_k(L)) from 0 in k order,
+ * nG[f][m][k] = ((0 + n_f0 G_m[0][k]) + ..) from a small kernel; the region rows are tested on
+ * cell - v_L.  Statuses, margin, worst, counts, volumes and the core are those of the entry points
+ * above, read leaf by leaf.  d_lo / d_hi of `plant` and the v / e bounds of `robust` are not read.
+ *
+ * ehm_compiled_robust_successors_leaf: `leaf_boxes` (may be NULL) takes, per requested leaf, the boxes
+ * and bounds; an array that is NULL, or whose kind has no terms, is not written; seconds_radii is the
+ * device time of k_leaf_radii, result->seconds_slack that of the nG table.
+ * ehm_compiled_robust_core_leaf: makes the boxes of all leaves on the device itself (their time is part
+ * of seconds_reach) and reads them in a third set of the relation's kernels.
+ *
+ * EHM_E_INVALID, before the device is touched: everything the entry points above refuse; more than 16
+ * terms or a bad descriptor (the message names the term); model dimensions that are not the plant's;
+ * n_d > 8; radius_iters outside 1..16; x_abs or u_abs NULL, negative or not finite; a model whose
+ * constant part of the v or e box (box_K(0, 0)) does not hold 0; n_g > 64; plant, generators, bounds
+ * and model together above 8192 doubles of LDS.  Errors through ehm_robust_last_error
+ * (robust_successors_leaf) and ehm_core_last_error (robust_core_leaf). */
+typedef struct ehm_robust_radii {
+    const int32_t* desc;            /* [n_terms][8]                                            */
+    const double*  data;            /* [n_data]                                                */
+    const double*  x_abs;           /* [p]                                                     */
+    const double*  u_abs;           /* [n_u]                                                   */
+    int32_t n_terms, n_data;
+    int32_t n_x, n_u, n_d;          /* the model's dimensions                                  */
+    int32_t radius_iters;
+} ehm_robust_radii;
+typedef struct ehm_robust_leaf_boxes {
+    double* d;                      /* [n][2][n_d]: lo, hi                                     */
+    double* v;                      /* [n][2][p]                                               */
+    double* e;                      /* [n][2][n_u]                                             */
+    double* v_next;                 /* [n][2][p]                                               */
+    double* x_abs_leaf;             /* [n][p]    a_L                                           */
+    double* x_next_abs;             /* [n][p]    a'_L                                          */
+    double* u_abs_leaf;             /* [n][n_u]  ubar_L                                        */
+    double  seconds_radii;          /* written by the call                                     */
+} ehm_robust_leaf_boxes;
+int ehm_compiled_robust_successors_leaf(ehm_compiled* law, const ehm_invariance_opts* plant,
+                                        const ehm_robust_opts* robust,
+                                        const ehm_robust_radii* radii, ehm_robust_result* result,
+                                        const ehm_robust_leaves* leaves,
+                                        ehm_robust_leaf_boxes* leaf_boxes);
+int ehm_compiled_robust_core_leaf(ehm_compiled* law, const ehm_invariance_opts* plant,
+                                  const ehm_robust_opts* robust, const ehm_robust_radii* radii,
+                                  const ehm_core_opts* opts, ehm_core_result* result,
+                                  const ehm_core_leaves* leaves);
+/* ehm_abi_sizes for ehm_robust_radii, ehm_robust_leaf_boxes, in this order. */
+int ehm_robust_radii_abi_sizes(int64_t* sizes, int32_t n);
+
 /* ---- closed-loop simulation under the COMPILED law (csrc/ehm_compiled.hip) -------
  *
  * The entry points of the explicit law's rollout, argument for argument, on a compiled law -- also
