@@ -68,10 +68,12 @@ EXPORTED = [
     'ehm_robust_abi_sizes',
     'ehm_compiled_robust_successors_leaf', 'ehm_compiled_robust_core_leaf',
     'ehm_robust_radii_abi_sizes',
+    'ehm_compiled_reach', 'ehm_reach_last_error', 'ehm_reach_abi_sizes',
 ]
 EHM_AUDIT_MODES = {'uniform': 0, 'per_leaf': 1}     # EHM_AUDIT_UNIFORM / _PER_LEAF
 EHM_COMPILE_SPINE_ROOTS = 1     # ehm_compiled_create_opts
 EHM_NARROW_FLUSH = 1            # ehm_compiled_narrow_opts
+EHM_REACH_MAPS = {'thread': 0, 'wave': 1}           # EHM_REACH_MAP_*
 EHM_CELL_MAX_DEPTH = 256        # ehm_compiled_cells: levels below a root a leaf's cell may lie
 
 
@@ -345,6 +347,27 @@ class RobustLeafBoxes(ctypes.Structure):
         [('seconds_radii', ctypes.c_double)]
 
 
+class ReachOpts(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ('root_vertices', 'indptr', 'indices', 'level',
+                                               'start')] + \
+        [(k, ctypes.c_int64) for k in ('n_leaf', 'n_edges', 'n_level', 'n_start', 'max_sweeps')] + \
+        [(k, ctypes.c_int32) for k in ('horizon', 'want_steps', 'row_map', 'reserved')]
+
+
+class ReachResult(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int64) for k in ('n_arrival', 'leak_step', 'settle', 'n_steps',
+                                              'sweeps_arrival', 'sweeps_settle')] + \
+        [('arrival_done', ctypes.c_int32), ('settle_done', ctypes.c_int32)] + \
+        [(k, ctypes.c_double) for k in ('seconds_boxes', 'seconds_arrival', 'seconds_settle',
+                                        'seconds_steps', 'seconds_upload')]
+
+
+class ReachLeaves(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ('arrival', 'depart', 'limit', 'steps', 'leaf_box',
+                                               'tube_box', 'tube_count', 'settle_box',
+                                               'settle_count', 'step_box', 'step_count')]
+
+
 _lib = None
 
 
@@ -383,7 +406,8 @@ def load(build_if_missing=True):
             ('ehm_robust_abi_sizes', (RobustOpts, RobustResult, RobustLeaves),
              "robust step's "),
             ('ehm_robust_radii_abi_sizes', (RobustRadii, RobustLeafBoxes),
-             "per-leaf radii's ")):
+             "per-leaf radii's "),
+            ('ehm_reach_abi_sizes', (ReachOpts, ReachResult, ReachLeaves), "reach tube's ")):
         sizes = (i64 * len(mirrors))()
         fn = getattr(lib, getter)
         fn.argtypes = [vp, i32]
@@ -432,6 +456,9 @@ def load(build_if_missing=True):
                                                   ctypes.POINTER(CoreResult),
                                                   ctypes.POINTER(CoreLeaves)]
     lib.ehm_robust_last_error.restype = ctypes.c_char_p
+    lib.ehm_compiled_reach.argtypes = [vp, ctypes.POINTER(ReachOpts), ctypes.POINTER(ReachResult),
+                                       ctypes.POINTER(ReachLeaves)]
+    lib.ehm_reach_last_error.restype = ctypes.c_char_p
     lib.ehm_explicit_set_costs.argtypes = [vp, vp, vp]
     lib.ehm_explicit_sample.argtypes = [vp, ctypes.POINTER(AuditOpts), vp, vp]
     lib.ehm_explicit_audit.argtypes = [vp, vp, ctypes.POINTER(AuditOpts),
@@ -533,7 +560,7 @@ def load(build_if_missing=True):
                         'ehm_compiled_last_error', 'ehm_applied_last_error',
                         'ehm_certify_last_error', 'ehm_reduce_last_error',
                         'ehm_invariance_last_error', 'ehm_core_last_error',
-                        'ehm_robust_last_error'):
+                        'ehm_robust_last_error', 'ehm_reach_last_error'):
             fn.restype = i32
     lib.ehm_search_last_error.restype = ctypes.c_char_p
     lib.ehm_search_create.argtypes = [i32, i32, i32, ctypes.POINTER(vp)]

@@ -10,7 +10,8 @@ law by the cost of the input it applies), ``ehm_certify.hip`` (the leaf cells of
 inputs at their vertices and the certificate leaf by leaf), ``ehm_reduce.hip`` (merging the leaves
 of a compiled law that apply one affine map), ``ehm_invariance.hip`` (the one-step successors of a
 compiled law's leaves), ``ehm_core.hip`` (the may-reach relation between the leaves and the
-invariant core), ``ehm_robust.hip`` (the one-step test under measurement and input error),
+invariant core), ``ehm_reach.hip`` (the reach tube and the limit set of that relation),
+``ehm_robust.hip`` (the one-step test under measurement and input error),
 ``ehm_compiled.hip`` (the explicit law compiled into a hyperplane tree) and
 ``ehm_compiled32.hip`` (the kernels of its single-precision form), one
 instance of ``ehm_k2.hip`` per (column capacity NP, row slots) pair -- the solver keeps a
@@ -154,6 +155,7 @@ def _objects():
             (os.path.join(OBJ_DIR, 'ehm_invariance.o'),
              os.path.join(SRC_DIR, 'ehm_invariance.hip'), []),
             (os.path.join(OBJ_DIR, 'ehm_core.o'), os.path.join(SRC_DIR, 'ehm_core.hip'), []),
+            (os.path.join(OBJ_DIR, 'ehm_reach.o'), os.path.join(SRC_DIR, 'ehm_reach.hip'), []),
             (os.path.join(OBJ_DIR, 'ehm_robust.o'), os.path.join(SRC_DIR, 'ehm_robust.hip'), []),
             (os.path.join(OBJ_DIR, 'ehm_compiled.o'), os.path.join(SRC_DIR, 'ehm_compiled.hip'),
              []),
@@ -201,7 +203,7 @@ def is_stale():
             for f in ('ehm_capi.hip', 'ehm_k2.hip', 'ehm_k3.hip', 'ehm_k4.hip', 'ehm_kp.hip',
                       'ehm_explicit.hip', 'ehm_implicit.hip', 'ehm_audit.hip', 'ehm_applied.hip',
                       'ehm_certify.hip', 'ehm_reduce.hip', 'ehm_invariance.hip', 'ehm_compiled.hip',
-                      'ehm_compiled32.hip', 'ehm_core.hip', 'ehm_robust.hip')]
+                      'ehm_compiled32.hip', 'ehm_core.hip', 'ehm_robust.hip', 'ehm_reach.hip')]
     return max([_dep_mtime()] + [os.path.getmtime(s)
                                  for s in srcs + SEARCH_DEPS + FRONTIER_DEPS]) > t
 

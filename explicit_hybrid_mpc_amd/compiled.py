@@ -806,6 +806,21 @@ class CompiledLaw:
             max_edges=invariance.MAX_EDGES if max_edges is None else max_edges, radii=radii,
             radius_iters=radius_iters)
 
+    # -- where the closed loop goes (invariance.py) -------------------------------
+    def reach(self, core, start=None, X0=None, horizon=0, max_sweeps=None, return_steps=False,
+              row_map=None):
+        """
+        The reach tube, the limit set and the step sets of the closed loop from ``start`` (or the
+        leaves of the states ``X0``; neither: all core leaves), over the relation of ``core``, an
+        ``invariance.CoreResult`` of this law made with ``return_edges=True`` by ``invariant_core``
+        or ``robust_core``: ``core.reach(...)``, which documents the arguments.  Returns an
+        ``invariance.ReachResult``.
+        """
+        if getattr(core, '_law', None) is not self:
+            raise ValueError('the core was made for another law')
+        return core.reach(start=start, X0=X0, horizon=horizon, max_sweeps=max_sweeps,
+                          return_steps=return_steps, row_map=row_map)
+
     def __call__(self, x):
         """(u, t): the input for state x and the evaluation time, as the reference's call."""
         tic = time.time()

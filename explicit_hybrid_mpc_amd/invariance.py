@@ -1,6 +1,8 @@
 """
 One-step invariance of a compiled law leaf by leaf (csrc/ehm_invariance.hip), and the
-leaves the closed loop never leaves (csrc/ehm_core.hip; ``invariant_core`` below):
+leaves the closed loop never leaves (csrc/ehm_core.hip; ``invariant_core`` below), and
+where the loop goes from a set of leaves (csrc/ehm_reach.hip; ``CoreResult.reach``,
+``reach_relation`` and ``ReachResult`` at the end):
 
     res = law.successors()                      # SuccessorResult of every leaf, nominal successor
     res = law.successors(d_box=(lo, hi))        # under every disturbance of the box
@@ -391,3 +393,234 @@ def _core(law, st, seeds, tol_side, rows, return_edges, max_fan, max_edges, call
         holds=bool(st.set_convex and core.any()), indptr=indptr, indices=indices,
         seconds_reach=float(res.seconds_reach), seconds_sweeps=float(res.seconds_sweeps),
         tol_exit=float(tol_exit), tol_side=tol_side, rows=rows, _law=law)
+
+
+# -- the reach tube and the limit set of the closed loop (csrc/ehm_reach.hip) ---------
+
+_check_reach = _capi.checker('ehm_reach_last_error')
+MAX_STEP_BYTES = 1 << 28        # (horizon + 1) n_leaf of ``return_steps``
+ROW_MAP = 'wave'                # the default row mapping: 4x to 10x faster
+
+
+class ReachResult:
+    """
+    What ``CoreResult.reach`` / ``reach_relation`` found, all sets as masks or
+    arrays over the leaf records.  Seeds (``level == 0``) are absorbing: nothing is claimed of a
+    trajectory after it reaches one.
+
+    Arrival: ``arrival`` int32 (the first step a leaf can be reached at from the start set, -1:
+    never), ``closure`` bool, ``n_arrival``, ``leak_step`` (the first step a seed can be reached at,
+    -1: never) and ``safe`` (``leak_step == -1``); ``tube_box`` [n_arrival + 1, 2, p] and
+    ``tube_count``: the box (lo, hi) and size of the leaves reached within k steps.
+
+    Limit set (only when ``safe``): ``limit`` bool, the fixed point of D_0 = closure,
+    D_(j+1) = post(D_j) (None when a phase did not finish; ``limit_outer`` is then the last D_j,
+    or None); ``depart`` int32, the first j >= 1 with the leaf not in D_j (-1 for limit leaves and
+    outside the closure); ``settle``; ``settle_box`` [settle + 1, 2, p], ``settle_count``;
+    ``limit_box`` = ``settle_box[-1]``.
+
+    Step sets: ``step_box`` [H' + 1, 2, p] and ``step_count`` of R_k = post^k(start), H' the horizon
+    cut at ``leak_step``; ``steps`` uint8 [H' + 1, n_leaf] with ``return_steps``.
+
+    The box of an empty set, or of leaves without a cell, is NaN.  ``closure_volume_fraction`` and
+    ``limit_volume_fraction`` over the roots' volume (None without a law's cells).  ``converged``:
+    every phase that ran finished within ``max_sweeps``.  ``holds``: the core's set is convex, the
+    run is ``safe`` and converged -- then a trajectory whose step-0 state is evaluated in a start
+    leaf is, at every step k, evaluated in a leaf of the closure, of R_k and of D_min(k, settle).
+    ``n_outside``: states of ``X0`` the law has no input for.  ``seconds_boxes``, ``seconds_arrival``,
+    ``seconds_settle``, ``seconds_steps``: device time; ``seconds_upload``: wall time of checking and
+    uploading the relation.
+    """
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        return 'ReachResult(closure=%d, n_arrival=%d, leak_step=%d, limit=%s, settle=%s, ' \
+            'converged=%s, holds=%s)' % (
+                int(self.closure.sum()), self.n_arrival, self.leak_step,
+                None if self.limit is None else int(self.limit.sum()), self.settle, self.converged,
+                self.holds)
+
+    def contains(self, X, k=None):
+        """bool [n]: the leaf the law evaluates X [n, p] in lies in the limit set (``k`` None) or in
+        D_min(k, settle); False where the law has no input for the state.  As ``CoreResult.contains``
+        it answers for the leaf ``evaluate`` returns, also for a state outside the set."""
+        if self.limit is None:
+            raise ValueError('contains needs a limit set: the run leaks or did not converge')
+        if getattr(self, '_law', None) is None or not getattr(self._law, '_handle', None):
+            raise ValueError('contains needs the compiled law the result was made for, open')
+        u, leaf, _, _ = self._law.evaluate(X, return_info=True)
+        row = np.searchsorted(self._law.leaf_node, leaf)
+        ok = np.isfinite(u).all(axis=1) & (row < self.limit.size)
+        row = np.minimum(row, self.limit.size - 1)
+        if k is None or int(k) >= self.settle:
+            return self.limit[row] & ok
+        if int(k) < 0:
+            raise ValueError('k must be >= 0')
+        # D_j holds the closure's leaves that have not departed by j
+        return self.closure[row] & ((self.depart[row] < 0) | (self.depart[row] > int(k))) & ok
+
+
+def _start_rows(n_leaf, start):
+    """int32 rows of a start set given as a bool mask [n_leaf] or as int rows; nonempty."""
+    s = np.asarray(start)
+    if s.dtype == np.bool_:
+        if s.shape != (n_leaf,):
+            raise ValueError('a start mask must be [%d] (one entry per leaf)' % n_leaf)
+        rows = np.nonzero(s)[0]
+    else:
+        if s.ndim != 1 or (s.size and s.dtype.kind not in 'iu'):
+            raise ValueError('start must be a bool mask or a 1-d array of leaf rows')
+        rows = s
+        if rows.size and (int(rows.min()) < 0 or int(rows.max()) >= n_leaf):
+            raise ValueError('start rows must lie in 0 .. %d' % (n_leaf - 1))
+    if rows.size == 0:
+        raise ValueError('the start set is empty')
+    return np.ascontiguousarray(rows, dtype=np.int32)
+
+
+def reach_relation(law, indptr, indices, level, start, horizon=0, max_sweeps=None,
+                   return_steps=False, row_map=None):
+    """
+    The one path to ``ehm_compiled_reach``: the reach tube, limit set and step sets (DESIGN.md
+    3.8l) of any relation over the first ``n = len(indptr) - 1`` leaf records of ``law``, as CSR
+    (``indptr`` [n + 1], ``indices``), with ``level`` [n] (0: a seed, absorbing) and ``start`` (a
+    bool mask [n] or int rows).  ``horizon``: the step sets R_0 .. R_horizon (cut at the leak);
+    ``max_sweeps`` (None: n) bounds each phase; ``return_steps``: the step sets as masks, needs
+    (horizon + 1) n <= 2^28; ``row_map``: ``'thread'`` or ``'wave'`` (None: ``ROW_MAP``), how the
+    device walks a row -- no result depends on it.  Returns a ``ReachResult`` whose ``holds`` is
+    False and whose volume fractions are those of the law's cells: ``CoreResult.reach`` fills in
+    what the core knows.
+    """
+    from . import applied
+    if not getattr(law, '_handle', None):
+        raise ValueError('the law is closed')
+    indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+    indices = np.ascontiguousarray(indices, dtype=np.int32)
+    level = np.ascontiguousarray(level, dtype=np.int32)
+    if indptr.ndim != 1 or indptr.size < 2 or indices.ndim != 1 or level.ndim != 1:
+        raise ValueError('indptr [n + 1] with n >= 1, indices and level must be 1-d')
+    n = indptr.size - 1
+    if n > law._h['n_leaf']:
+        raise ValueError('a relation over %d leaves, the law has %d' % (n, law._h['n_leaf']))
+    if level.size != n:
+        raise ValueError('level must be [%d] (one entry per leaf)' % n)
+    rows = _start_rows(n, start)
+    horizon = int(horizon)
+    max_sweeps = n if max_sweeps is None else int(max_sweeps)
+    if horizon < 0:
+        raise ValueError('horizon must be >= 0')
+    if max_sweeps < 1:
+        raise ValueError('max_sweeps must be >= 1')
+    if return_steps and (horizon + 1) * n > MAX_STEP_BYTES:
+        raise ValueError('return_steps needs (horizon + 1) * n_leaf <= 2^28')
+    row_map = ROW_MAP if row_map is None else row_map
+    if row_map not in _capi.EHM_REACH_MAPS:
+        raise ValueError("row_map must be 'thread' or 'wave'")
+    if law._h['n_test'] > 0:
+        raise _capi.EhmError(_capi.EHM_E_INVALID, 'the law has %d test nodes: its cells do '
+                             "not follow from its planes -- compile(spine='roots') has none" %
+                             law._h['n_test'])
+    if law._root_cells is None:
+        law._root_cells = applied.root_cells(law)
+    roots = law._root_cells
+    p = law.p
+    cap = min(max_sweeps, n) + 1
+    out = dict(arrival=np.empty(n, np.int32), depart=np.empty(n, np.int32),
+               limit=np.empty(n, np.uint8),
+               steps=np.empty((horizon + 1, n), np.uint8) if return_steps else None,
+               leaf_box=np.empty((2, p, n)), tube_box=np.empty((cap, 2, p)),
+               tube_count=np.empty(cap, np.int64), settle_box=np.empty((cap, 2, p)),
+               settle_count=np.empty(cap, np.int64), step_box=np.empty((horizon + 1, 2, p)),
+               step_count=np.empty(horizon + 1, np.int64))
+    opts = _capi.ReachOpts(root_vertices=ptr(roots['vertices']), indptr=ptr(indptr),
+                           indices=ptr(indices), level=ptr(level), start=ptr(rows), n_leaf=n,
+                           n_edges=indices.size, n_level=level.size, n_start=rows.size,
+                           max_sweeps=max_sweeps, horizon=horizon,
+                           want_steps=int(bool(return_steps)),
+                           row_map=_capi.EHM_REACH_MAPS[row_map])
+    lv = _capi.ReachLeaves(**{k: ptr(a) for k, a in out.items()})
+    res = _capi.ReachResult()
+    _check_reach(_capi.load().ehm_compiled_reach(law._handle, ctypes.byref(opts),
+                                                 ctypes.byref(res), ctypes.byref(lv)))
+    n_arrival, settle, n_steps = int(res.n_arrival), int(res.settle), int(res.n_steps)
+    leak = int(res.leak_step)
+    ran_b = bool(res.arrival_done) and leak < 0
+    done_b = ran_b and bool(res.settle_done)
+    arrival = out['arrival']
+    closure = arrival >= 0
+    last = out['limit'].astype(bool)
+    settle_box = out['settle_box'][:settle + 1].copy() if ran_b else None
+    # the volumes: |det| of the cells' edge matrices over p!, against the roots'
+    lo, hi = out['leaf_box']
+    has = np.isfinite(lo).all(axis=0)
+    frac = lambda mask: None
+    total = float(roots['volume'].sum())
+    if n == law._h['n_leaf']:
+        V = law.cells().vertices
+        det = np.zeros(n)
+        det[has] = np.abs(np.linalg.det(V[has][:, 1:] - V[has][:, :1]))
+        fact = float(np.prod(np.arange(1, p + 1)))
+        frac = lambda mask: float(det[mask].sum()) / fact / total
+    return ReachResult(
+        arrival=arrival, closure=closure, n_arrival=n_arrival, leak_step=leak, safe=leak < 0,
+        limit=last if done_b else None, limit_outer=last if ran_b and not done_b else None,
+        depart=out['depart'], settle=settle if ran_b else None,
+        tube_box=out['tube_box'][:n_arrival + 1].copy(),
+        tube_count=out['tube_count'][:n_arrival + 1].copy(), settle_box=settle_box,
+        settle_count=out['settle_count'][:settle + 1].copy() if ran_b else None,
+        limit_box=settle_box[-1] if ran_b else None,
+        step_box=out['step_box'][:n_steps].copy(), step_count=out['step_count'][:n_steps].copy(),
+        steps=out['steps'][:n_steps].copy() if return_steps else None,
+        leaf_box=np.ascontiguousarray(np.transpose(out['leaf_box'], (2, 0, 1))),
+        closure_volume_fraction=frac(closure),
+        limit_volume_fraction=frac(last) if done_b else None,
+        converged=bool(res.arrival_done) and (done_b or not ran_b), holds=False,
+        horizon=horizon, max_sweeps=max_sweeps, row_map=row_map, n_outside=0,
+        sweeps_arrival=int(res.sweeps_arrival), sweeps_settle=int(res.sweeps_settle),
+        seconds_boxes=float(res.seconds_boxes), seconds_arrival=float(res.seconds_arrival),
+        seconds_settle=float(res.seconds_settle), seconds_steps=float(res.seconds_steps),
+        seconds_upload=float(res.seconds_upload), _law=law)
+
+
+def _core_reach(self, start=None, X0=None, horizon=0, max_sweeps=None, return_steps=False,
+                row_map=None):
+    """
+    Where does the closed loop go from ``start``?  The forward analysis of the
+    relation this result holds (it must have been made with ``return_edges=True``): the leaves
+    reachable step by step with their bounding boxes, the first step a seed can be reached
+    (``leak_step``), and, when none can, the limit set the loop settles into and its box.
+
+    ``start``: a bool mask or int rows of the leaf records; or ``X0`` [n, p]: the leaves ``evaluate``
+    returns for those states, located as ``contains`` locates them (states without an input are
+    counted in ``n_outside`` and left out); neither: all core leaves.  ``horizon``, ``max_sweeps``,
+    ``return_steps``, ``row_map`` as ``reach_relation``.  ``ValueError`` for both ``start`` and ``X0``,
+    an empty start, a result without edges and a closed law.  Returns a ``ReachResult``; every
+    statement holds under the assumptions and exclusions of the core that made the relation.
+    """
+    law = getattr(self, '_law', None)
+    if self.indptr is None or self.indices is None:
+        raise ValueError('reach needs the relation: make the core with return_edges=True')
+    if start is not None and X0 is not None:
+        raise ValueError('give start or X0, not both')
+    if law is None or not getattr(law, '_handle', None):
+        raise ValueError('reach needs the compiled law the result was made for: the law is closed')
+    n_outside = 0
+    if X0 is not None:
+        X0 = np.ascontiguousarray(X0, dtype=np.float64)
+        u, leaf, _, _ = law.evaluate(X0, return_info=True)
+        ok = np.isfinite(u).all(axis=1)
+        n_outside = int((~ok).sum())
+        start = np.unique(np.searchsorted(law.leaf_node, leaf[ok])).astype(np.int32)
+    elif start is None:
+        start = self.core
+    out = reach_relation(law, self.indptr, self.indices, self.level, start, horizon=horizon,
+                         max_sweeps=max_sweeps, return_steps=return_steps, row_map=row_map)
+    out.n_outside = n_outside
+    out.set_convex = bool(self.set_convex)
+    out.holds = bool(self.set_convex and out.safe and out.converged)
+    return out
+
+
+CoreResult.reach = _core_reach

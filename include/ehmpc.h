@@ -1280,6 +1280,79 @@ int ehm_compiled_robust_core_leaf(ehm_compiled* law, const ehm_invariance_opts* 
 /* ehm_abi_sizes for ehm_robust_radii, ehm_robust_leaf_boxes, in this order. */
 int ehm_robust_radii_abi_sizes(int64_t* sizes, int32_t n);
 
+/* ---- reach tube and limit set of the closed loop (csrc/ehm_reach.hip) -------------
+ * (no counterpart in the reference)
+ *
+ * The forward analysis of a may-reach relation between the first n_leaf leaf records of a law
+ * (n_leaf at most the law's), given as host CSR (indptr, indices: what ehm_compiled_core returns with
+ * want_edges, or any other relation), with `level` [n_leaf] (0: a seed) and the start rows.  A seed is
+ * absorbing: F(l) is the row of l for a non-seed and empty for a seed, whether or not the relation
+ * has a row for it; post(X) is the union of F over X.
+ *  A. arrival [n_leaf]: the smallest k >= 0 with l in post^k(S), -1 if there is none, by sweeps
+ *     k = 1, 2, .. (a row with arrival k - 1 writes k into every target without an arrival) until a
+ *     sweep reaches nothing new or max_sweeps sweeps were made (arrival_done = 0).  n_arrival: the
+ *     largest arrival.  leak_step: the smallest arrival of a seed, -1 without one.
+ *  B. only with arrival_done and leak_step = -1: D_0 = {arrival >= 0}, D_(j+1) = post(D_j), until
+ *     D_(j+1) = D_j or D_(j+1) is empty (settle_done = 1; settle = j resp. j + 1) or max_sweeps sweeps
+ *     were made (settle_done = 0, settle = the sweeps made).  depart [n_leaf]: the first j >= 1 with l
+ *     not in D_j, -1 for the leaves of the last set and those outside D_0.  limit [n_leaf]: the last
+ *     D_j (all 0 when phase B did not run).
+ *  C. R_0 = S, R_(k+1) = post(R_k) for k = 0 .. n_steps - 1, n_steps - 1 = horizon, cut at leak_step
+ *     where there is one and at max_sweeps where phase A did not finish.  steps [n_steps][n_leaf]
+ *     with want_steps.
+ * Boxes: leaf_box [2][p][n_leaf] (lo then hi, leaf-fastest; may be NULL) holds per coordinate the
+ * smallest and largest vertex coordinate of the leaf's cell (ehm_compiled_cells), NaN without a cell;
+ * the box of a set takes the minimum and maximum over its leaves that have a cell, NaN for none, and
+ * adds 0.0 to each bound (a zero is +0).  tube_box [n_arrival + 1][2][p]: of {0 <= arrival <= k};
+ * settle_box [settle + 1][2][p]: of D_j; step_box [n_steps][2][p]: of R_k; the counts beside them are
+ * the sets' sizes.  The caller's tube and settle arrays hold min(max_sweeps, n_leaf) + 1 rows, the
+ * step arrays horizon + 1.
+ * row_map: how the rows are walked, one thread per row (EHM_REACH_MAP_THREAD) or one wavefront per
+ * row, the lanes striding it (EHM_REACH_MAP_WAVE); no result depends on it.
+ * seconds_boxes / _arrival / _settle / _steps: device time of the phases; seconds_upload: wall time of
+ * checking, narrowing and uploading the relation.
+ * EHM_E_INVALID, before the device is touched: a NULL argument or required array; a law with test
+ * nodes; n_leaf < 1 or above the law's; indptr[0] != 0, a decreasing indptr, indptr[n_leaf] other
+ * than n_edges, n_edges >= 2^31; an index outside 0 .. n_leaf - 1; n_level other than n_leaf; an
+ * empty start or a start row out of range; horizon < 0; max_sweeps < 1; a row_map that is neither;
+ * want_steps with (horizon + 1) n_leaf > 2^28.  Errors through ehm_reach_last_error. */
+#define EHM_REACH_MAP_THREAD 0
+#define EHM_REACH_MAP_WAVE 1
+typedef struct ehm_reach_opts {
+    const double*  root_vertices;   /* [n_roots][p+1][p], as for ehm_compiled_cells            */
+    const int64_t* indptr;          /* [n_leaf + 1]                                            */
+    const int32_t* indices;         /* [n_edges]                                               */
+    const int32_t* level;           /* [n_level]                                               */
+    const int32_t* start;           /* [n_start] rows of the leaf records                      */
+    int64_t n_leaf, n_edges, n_level, n_start;
+    int64_t max_sweeps;
+    int32_t horizon, want_steps, row_map, reserved;
+} ehm_reach_opts;
+typedef struct ehm_reach_result {
+    int64_t n_arrival, leak_step, settle, n_steps;
+    int64_t sweeps_arrival, sweeps_settle;
+    int32_t arrival_done, settle_done;
+    double  seconds_boxes, seconds_arrival, seconds_settle, seconds_steps, seconds_upload;
+} ehm_reach_result;
+typedef struct ehm_reach_leaves {
+    int32_t* arrival;               /* [n_leaf]                                                */
+    int32_t* depart;                /* [n_leaf]                                                */
+    uint8_t* limit;                 /* [n_leaf]                                                */
+    uint8_t* steps;                 /* [horizon + 1][n_leaf], with want_steps                  */
+    double*  leaf_box;              /* [2][p][n_leaf] or NULL                                  */
+    double*  tube_box;
+    int64_t* tube_count;
+    double*  settle_box;
+    int64_t* settle_count;
+    double*  step_box;
+    int64_t* step_count;
+} ehm_reach_leaves;
+int ehm_compiled_reach(ehm_compiled* law, const ehm_reach_opts* opts, ehm_reach_result* result,
+                       const ehm_reach_leaves* leaves);
+const char* ehm_reach_last_error(void);
+/* ehm_abi_sizes for ehm_reach_opts, ehm_reach_result, ehm_reach_leaves, in this order. */
+int ehm_reach_abi_sizes(int64_t* sizes, int32_t n);
+
 /* ---- closed-loop simulation under the COMPILED law (csrc/ehm_compiled.hip) -------
  *
  * The entry points of the explicit law's rollout, argument for argument, on a compiled law -- also
