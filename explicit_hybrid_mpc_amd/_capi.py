@@ -69,6 +69,7 @@ EXPORTED = [
     'ehm_compiled_robust_successors_leaf', 'ehm_compiled_robust_core_leaf',
     'ehm_robust_radii_abi_sizes',
     'ehm_compiled_reach', 'ehm_reach_last_error', 'ehm_reach_abi_sizes',
+    'ehm_compiled_cost', 'ehm_cost_last_error', 'ehm_cost_abi_sizes',
 ]
 EHM_AUDIT_MODES = {'uniform': 0, 'per_leaf': 1}     # EHM_AUDIT_UNIFORM / _PER_LEAF
 EHM_COMPILE_SPINE_ROOTS = 1     # ehm_compiled_create_opts
@@ -368,6 +369,24 @@ class ReachLeaves(ctypes.Structure):
                                                'settle_count', 'step_box', 'step_count')]
 
 
+class CostOpts(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ('root_vertices', 'indptr', 'indices', 'level',
+                                               'domain', 'start', 'w_hi', 'w_lo')] + \
+        [(k, ctypes.c_int64) for k in ('n_leaf', 'n_edges', 'n_level', 'n_domain', 'n_start')] + \
+        [(k, ctypes.c_int32) for k in ('horizon', 'want_paths')]
+
+
+class CostResult(ctypes.Structure):
+    _fields_ = [('n_domain', ctypes.c_int64), ('n_start', ctypes.c_int64)] + \
+        [(k, ctypes.c_double) for k in ('seconds_weights', 'seconds_sweeps', 'seconds_upload')]
+
+
+class CostLeaves(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ('w_hi', 'w_lo', 'pad', 'hi', 'lo', 'max_hi',
+                                               'min_lo', 'start_hi', 'start_lo', 'path_hi',
+                                               'path_lo')]
+
+
 _lib = None
 
 
@@ -407,7 +426,8 @@ def load(build_if_missing=True):
              "robust step's "),
             ('ehm_robust_radii_abi_sizes', (RobustRadii, RobustLeafBoxes),
              "per-leaf radii's "),
-            ('ehm_reach_abi_sizes', (ReachOpts, ReachResult, ReachLeaves), "reach tube's ")):
+            ('ehm_reach_abi_sizes', (ReachOpts, ReachResult, ReachLeaves), "reach tube's "),
+            ('ehm_cost_abi_sizes', (CostOpts, CostResult, CostLeaves), "fuel bounds' ")):
         sizes = (i64 * len(mirrors))()
         fn = getattr(lib, getter)
         fn.argtypes = [vp, i32]
@@ -459,6 +479,9 @@ def load(build_if_missing=True):
     lib.ehm_compiled_reach.argtypes = [vp, ctypes.POINTER(ReachOpts), ctypes.POINTER(ReachResult),
                                        ctypes.POINTER(ReachLeaves)]
     lib.ehm_reach_last_error.restype = ctypes.c_char_p
+    lib.ehm_compiled_cost.argtypes = [vp, ctypes.POINTER(CostOpts), ctypes.POINTER(CostResult),
+                                      ctypes.POINTER(CostLeaves)]
+    lib.ehm_cost_last_error.restype = ctypes.c_char_p
     lib.ehm_explicit_set_costs.argtypes = [vp, vp, vp]
     lib.ehm_explicit_sample.argtypes = [vp, ctypes.POINTER(AuditOpts), vp, vp]
     lib.ehm_explicit_audit.argtypes = [vp, vp, ctypes.POINTER(AuditOpts),
@@ -560,7 +583,8 @@ def load(build_if_missing=True):
                         'ehm_compiled_last_error', 'ehm_applied_last_error',
                         'ehm_certify_last_error', 'ehm_reduce_last_error',
                         'ehm_invariance_last_error', 'ehm_core_last_error',
-                        'ehm_robust_last_error', 'ehm_reach_last_error'):
+                        'ehm_robust_last_error', 'ehm_reach_last_error',
+                        'ehm_cost_last_error'):
             fn.restype = i32
     lib.ehm_search_last_error.restype = ctypes.c_char_p
     lib.ehm_search_create.argtypes = [i32, i32, i32, ctypes.POINTER(vp)]

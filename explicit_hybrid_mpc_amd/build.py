@@ -11,6 +11,7 @@ inputs at their vertices and the certificate leaf by leaf), ``ehm_reduce.hip`` (
 of a compiled law that apply one affine map), ``ehm_invariance.hip`` (the one-step successors of a
 compiled law's leaves), ``ehm_core.hip`` (the may-reach relation between the leaves and the
 invariant core), ``ehm_reach.hip`` (the reach tube and the limit set of that relation),
+``ehm_cost.hip`` (certified fuel bounds of the closed loop over that relation),
 ``ehm_robust.hip`` (the one-step test under measurement and input error),
 ``ehm_compiled.hip`` (the explicit law compiled into a hyperplane tree) and
 ``ehm_compiled32.hip`` (the kernels of its single-precision form), one
@@ -156,6 +157,7 @@ def _objects():
              os.path.join(SRC_DIR, 'ehm_invariance.hip'), []),
             (os.path.join(OBJ_DIR, 'ehm_core.o'), os.path.join(SRC_DIR, 'ehm_core.hip'), []),
             (os.path.join(OBJ_DIR, 'ehm_reach.o'), os.path.join(SRC_DIR, 'ehm_reach.hip'), []),
+            (os.path.join(OBJ_DIR, 'ehm_cost.o'), os.path.join(SRC_DIR, 'ehm_cost.hip'), []),
             (os.path.join(OBJ_DIR, 'ehm_robust.o'), os.path.join(SRC_DIR, 'ehm_robust.hip'), []),
             (os.path.join(OBJ_DIR, 'ehm_compiled.o'), os.path.join(SRC_DIR, 'ehm_compiled.hip'),
              []),
@@ -203,7 +205,8 @@ def is_stale():
             for f in ('ehm_capi.hip', 'ehm_k2.hip', 'ehm_k3.hip', 'ehm_k4.hip', 'ehm_kp.hip',
                       'ehm_explicit.hip', 'ehm_implicit.hip', 'ehm_audit.hip', 'ehm_applied.hip',
                       'ehm_certify.hip', 'ehm_reduce.hip', 'ehm_invariance.hip', 'ehm_compiled.hip',
-                      'ehm_compiled32.hip', 'ehm_core.hip', 'ehm_robust.hip', 'ehm_reach.hip')]
+                      'ehm_compiled32.hip', 'ehm_core.hip', 'ehm_robust.hip', 'ehm_reach.hip',
+                      'ehm_cost.hip')]
     return max([_dep_mtime()] + [os.path.getmtime(s)
                                  for s in srcs + SEARCH_DEPS + FRONTIER_DEPS]) > t
 

@@ -821,6 +821,20 @@ class CompiledLaw:
         return core.reach(start=start, X0=X0, horizon=horizon, max_sweeps=max_sweeps,
                           return_steps=return_steps, row_map=row_map)
 
+    # -- what the closed loop spends (invariance.py) ------------------------------
+    def cost(self, core, domain=None, start=None, X0=None, horizon=64, w_hi=None, w_lo=None,
+             return_paths=False):
+        """
+        Certified bounds of the summed input 2-norm of every trajectory that stays in ``domain``
+        (None: the core) over the relation of ``core``, an ``invariance.CoreResult`` of this law
+        made with ``return_edges=True``: ``core.cost(...)``, which documents the arguments.
+        Returns an ``invariance.CostResult``.
+        """
+        if getattr(core, '_law', None) is not self:
+            raise ValueError('the core was made for another law')
+        return core.cost(domain=domain, start=start, X0=X0, horizon=horizon, w_hi=w_hi,
+                         w_lo=w_lo, return_paths=return_paths)
+
     def __call__(self, x):
         """(u, t): the input for state x and the evaluation time, as the reference's call."""
         tic = time.time()

@@ -36,6 +36,7 @@
 #include "../../include/ehmpc.h"
 #include "ehm_cells_dev.h"
 #include "ehm_reach_host.h"
+#include "ehm_relation_dev.h"
 
 #define EHM_REACH_CELL_BLOCK 64
 #define EHM_REACH_BLOCK 256
@@ -276,12 +277,11 @@ int ehm_compiled_reach(ehm_compiled* law, const ehm_reach_opts* o, ehm_reach_res
     EHM_HIP_TRY(r_err, stream.create());
     ParentTable T;
     EHM_HIP_TRY(r_err, make_parents(v, stream, T));
-    DevBuf d_roots, d_lbox, d_ptr, d_idx, d_level, d_arrival, d_part, d_size, d_gone, d_box;
+    DevBuf d_roots, d_lbox, d_arrival, d_part, d_size, d_gone, d_box;
+    DevRelation rel;
     const size_t cell = (size_t)(p + 1) * p;
     EHM_HIP_TRY(r_err, d_roots.upload(o->root_vertices, (size_t)v.n_roots * cell * sizeof(double)));
-    EHM_HIP_TRY(r_err, d_ptr.upload(ptr32.data(), ptr32.size() * sizeof(int32_t)));
-    EHM_HIP_TRY(r_err, d_idx.upload(o->indices, (size_t)o->n_edges * sizeof(int32_t)));
-    EHM_HIP_TRY(r_err, d_level.upload(o->level, (size_t)n * sizeof(int32_t)));
+    EHM_HIP_TRY(r_err, rel.upload(ptr32, o->indices, o->n_edges, o->level, n));
     res->seconds_upload = wall_since(t_up);
     EHM_HIP_TRY(r_err, d_lbox.alloc((size_t)p2 * n * sizeof(double)));
     const long long blocks = blocks_of(n, EHM_REACH_BLOCK);
@@ -314,9 +314,9 @@ int ehm_compiled_reach(ehm_compiled* law, const ehm_reach_opts* o, ehm_reach_res
 
     const dim3 block(EHM_REACH_BLOCK), lgrid((unsigned)blocks);
     const dim3 rgrid(wave ? blocks_of(n * EHM_REACH_WAVE, EHM_REACH_BLOCK) : (unsigned)blocks);
-    const int32_t* ptr = d_ptr.as<const int32_t>();
-    const int32_t* idx = d_idx.as<const int32_t>();
-    const int32_t* level = d_level.as<const int32_t>();
+    const int32_t* ptr = rel.ptr.as<const int32_t>();
+    const int32_t* idx = rel.idx.as<const int32_t>();
+    const int32_t* level = rel.level.as<const int32_t>();
     BookArgs B{};
     B.n = n;
     B.p = p;

@@ -35,33 +35,40 @@ inline int check_options(ehm_err_channel& err, const ehm_reach_opts* o, int64_t 
     return EHM_OK;
 }
 
-// The relation: indptr[0] = 0, nondecreasing, indptr[n_leaf] = n_edges < 2^31, every index in
-// 0 .. n_leaf - 1, a level per leaf.  On success ptr32 [n_leaf + 1] is indptr in 32 bits.
+// A relation as CSR over n leaves: indptr[0] = 0, nondecreasing, indptr[n] = n_edges < 2^31, every
+// index in 0 .. n - 1, a level per leaf.  On success ptr32 [n + 1] is indptr in the 32 bits the
+// kernels read.  `who` names the entry point (ehm_cost.hip checks its relation here too).
+inline int check_csr(ehm_err_channel& err, const char* who, int64_t n, int64_t n_edges,
+                     int64_t n_level, const int64_t* indptr, const int32_t* indices,
+                     std::vector<int32_t>& ptr32) {
+    if (n_edges < 0 || n_edges > 0x7fffffffLL)
+        return err.fail(EHM_E_INVALID, "%s: n_edges = %lld (0 .. 2^31 - 1)", who,
+                        (long long)n_edges);
+    if (n_level != n)
+        return err.fail(EHM_E_INVALID, "%s: a level array of %lld for %lld leaves", who,
+                        (long long)n_level, (long long)n);
+    if (indptr[0] != 0)
+        return err.fail(EHM_E_INVALID, "%s: indptr[0] = %lld, not 0", who, (long long)indptr[0]);
+    for (int64_t l = 0; l < n; ++l)
+        if (indptr[l + 1] < indptr[l])
+            return err.fail(EHM_E_INVALID, "%s: indptr decreases at row %lld (%lld after %lld)", who,
+                            (long long)l, (long long)indptr[l + 1], (long long)indptr[l]);
+    if (indptr[n] != n_edges)
+        return err.fail(EHM_E_INVALID, "%s: indptr ends at %lld, n_edges is %lld", who,
+                        (long long)indptr[n], (long long)n_edges);
+    for (int64_t e = 0; e < n_edges; ++e)
+        if (indices[e] < 0 || indices[e] >= n)
+            return err.fail(EHM_E_INVALID, "%s: indices[%lld] = %d of %lld leaves", who,
+                            (long long)e, (int)indices[e], (long long)n);
+    ptr32.resize((size_t)n + 1);
+    for (int64_t l = 0; l <= n; ++l) ptr32[(size_t)l] = (int32_t)indptr[l];
+    return EHM_OK;
+}
+
+// The relation of a reach call.
 inline int check_relation(ehm_err_channel& err, const ehm_reach_opts* o,
                           std::vector<int32_t>& ptr32) {
-    const int64_t n = o->n_leaf;
-    if (o->n_edges < 0 || o->n_edges > 0x7fffffffLL)
-        return err.fail(EHM_E_INVALID, "reach: n_edges = %lld (0 .. 2^31 - 1)",
-                        (long long)o->n_edges);
-    if (o->n_level != n)
-        return err.fail(EHM_E_INVALID, "reach: a level array of %lld for %lld leaves",
-                        (long long)o->n_level, (long long)n);
-    if (o->indptr[0] != 0)
-        return err.fail(EHM_E_INVALID, "reach: indptr[0] = %lld, not 0", (long long)o->indptr[0]);
-    for (int64_t l = 0; l < n; ++l)
-        if (o->indptr[l + 1] < o->indptr[l])
-            return err.fail(EHM_E_INVALID, "reach: indptr decreases at row %lld (%lld after %lld)",
-                            (long long)l, (long long)o->indptr[l + 1], (long long)o->indptr[l]);
-    if (o->indptr[n] != o->n_edges)
-        return err.fail(EHM_E_INVALID, "reach: indptr ends at %lld, n_edges is %lld",
-                        (long long)o->indptr[n], (long long)o->n_edges);
-    for (int64_t e = 0; e < o->n_edges; ++e)
-        if (o->indices[e] < 0 || o->indices[e] >= n)
-            return err.fail(EHM_E_INVALID, "reach: indices[%lld] = %d of %lld leaves", (long long)e,
-                            (int)o->indices[e], (long long)n);
-    ptr32.resize((size_t)n + 1);
-    for (int64_t l = 0; l <= n; ++l) ptr32[(size_t)l] = (int32_t)o->indptr[l];
-    return EHM_OK;
+    return check_csr(err, "reach", o->n_leaf, o->n_edges, o->n_level, o->indptr, o->indices, ptr32);
 }
 
 // The start rows as a mask [n_leaf]: nonempty, every row in range; a row named twice is one row.

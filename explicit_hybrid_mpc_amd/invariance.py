@@ -624,3 +624,188 @@ def _core_reach(self, start=None, X0=None, horizon=0, max_sweeps=None, return_st
 
 
 CoreResult.reach = _core_reach
+
+
+# -- certified fuel bounds of the closed loop (csrc/ehm_cost.hip) ---------------------
+
+_check_cost = _capi.checker('ehm_cost_last_error')
+MAX_PATH_BYTES = 1 << 28        # horizon n_leaf 4 of ``return_paths``, per direction
+COST_MAX_NU = 4                 # the inputs a rollout steps
+
+
+class CostResult:
+    """
+    What ``CoreResult.cost`` / ``cost_relation`` found: bounds of the summed input
+    2-norm (``u_norm_sum`` of a rollout) of every trajectory that stays in the domain D.
+
+    Per leaf, NaN outside D: ``w_hi``, ``w_lo`` (the largest and smallest 2-norm of the commanded
+    input on the leaf's cell, widened by ``pad``, the rounding of the law's evaluation), ``hi`` = U_H
+    and ``lo`` = L_H, the bounds over ``horizon`` steps from the leaf.  Per step k = 0 .. H:
+    ``max_hi``, ``min_lo`` over D, ``start_hi``, ``start_lo`` over the start set, ``rate_hi`` =
+    ``max_hi[k] / k`` and ``rate_lo`` = ``min_lo[k] / k`` (NaN at k = 0).  ``best_rate_hi`` = min_k
+    rate_hi at ``best_k_hi``, ``best_rate_lo`` = max_k rate_lo at ``best_k_lo``: every window of K
+    steps spends at most K rate_hi[K], so the long-run spend per step lies in [best_rate_lo,
+    best_rate_hi].  With ``return_paths``: ``path_hi``, ``path_lo`` int32 [H + 1], the leaves a
+    worst and a best path visits (-1 after a leaf with an empty row).  ``holds``: the core's set
+    is convex.  ``n_domain``, ``n_start``; ``seconds_weights``, ``seconds_sweeps`` (device time)
+    and ``seconds_upload`` (wall time of checking and uploading the relation).
+    """
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        return 'CostResult(n_domain=%d, n_start=%d, horizon=%d, start=[%.6g, %.6g], ' \
+            'rate=[%.6g (k=%d), %.6g (k=%d)], holds=%s)' % (
+                self.n_domain, self.n_start, self.horizon, self.start_lo[-1], self.start_hi[-1],
+                self.best_rate_lo, self.best_k_lo, self.best_rate_hi, self.best_k_hi, self.holds)
+
+
+def _set_rows(n_leaf, rows, what):
+    """``_start_rows`` for the set called ``what``."""
+    try:
+        return _start_rows(n_leaf, rows)
+    except ValueError as e:
+        raise ValueError(str(e).replace('start', what)) from None
+
+
+def cost_relation(law, indptr, indices, level, domain, start=None, horizon=64, w_hi=None,
+                  w_lo=None, return_paths=False):
+    """
+    The one path to ``ehm_compiled_cost``: certified bounds of the summed input 2-norm over k = 0 ..
+    ``horizon`` steps on the relation over the first ``n = len(indptr) - 1`` leaf
+    records of ``law``, as ``reach_relation`` takes it.  ``domain`` (a bool mask [n] or int rows)
+    must hold no seed (``level == 0``) and be closed under the relation -- the device checks both and
+    ``EhmError`` names the first row that fails --; ``start`` (None: the domain) lies in it.  The
+    weights come from the law's cells and maps (a domain leaf without a cell is refused) unless
+    ``w_hi`` and ``w_lo`` [n] are both given: any per-leaf cost, finite with ``w_lo <= w_hi`` on the
+    domain.  ``return_paths`` needs horizon * n * 4 <= 2^28.  Returns a ``CostResult`` whose
+    ``holds`` is False: ``CoreResult.cost`` fills in what the core knows.
+    """
+    from . import applied
+    if not getattr(law, '_handle', None):
+        raise ValueError('the law is closed')
+    indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+    indices = np.ascontiguousarray(indices, dtype=np.int32)
+    level = np.ascontiguousarray(level, dtype=np.int32)
+    if indptr.ndim != 1 or indptr.size < 2 or indices.ndim != 1 or level.ndim != 1:
+        raise ValueError('indptr [n + 1] with n >= 1, indices and level must be 1-d')
+    n = indptr.size - 1
+    if n > law._h['n_leaf']:
+        raise ValueError('a relation over %d leaves, the law has %d' % (n, law._h['n_leaf']))
+    if level.size != n:
+        raise ValueError('level must be [%d] (one entry per leaf)' % n)
+    dom = _set_rows(n, domain, 'domain')
+    rows = dom if start is None else _set_rows(n, start, 'start')
+    if not np.isin(rows, dom).all():
+        raise ValueError('the start set must lie in the domain: row %d does not'
+                         % int(rows[~np.isin(rows, dom)][0]))
+    horizon = int(horizon)
+    if horizon < 1:
+        raise ValueError('horizon must be >= 1')
+    if (w_hi is None) != (w_lo is None):
+        raise ValueError('give both w_hi and w_lo, or neither')
+    if return_paths and horizon * n * 4 > MAX_PATH_BYTES:
+        raise ValueError('return_paths needs horizon * n_leaf * 4 <= 2^28')
+    if w_hi is not None:
+        w_hi = np.ascontiguousarray(w_hi, dtype=np.float64)
+        w_lo = np.ascontiguousarray(w_lo, dtype=np.float64)
+        if w_hi.shape != (n,) or w_lo.shape != (n,):
+            raise ValueError('w_hi and w_lo must be [%d] (one entry per leaf)' % n)
+        if not (np.isfinite(w_hi[dom]).all() and np.isfinite(w_lo[dom]).all()):
+            raise ValueError('w_hi and w_lo must be finite on the domain')
+        if (w_lo[dom] > w_hi[dom]).any():
+            raise ValueError('w_lo <= w_hi must hold on the domain')
+    if law._h['n_test'] > 0:
+        raise _capi.EhmError(_capi.EHM_E_INVALID, 'the law has %d test nodes: its cells do '
+                             "not follow from its planes -- compile(spine='roots') has none" %
+                             law._h['n_test'])
+    if law.n_u > COST_MAX_NU:
+        raise ValueError('cost bounds at most %d inputs, the law has %d' % (COST_MAX_NU, law.n_u))
+    if law._root_cells is None:
+        law._root_cells = applied.root_cells(law)
+    roots = law._root_cells
+    out = dict(w_hi=np.empty(n), w_lo=np.empty(n), pad=np.empty(n), hi=np.empty(n),
+               lo=np.empty(n), max_hi=np.empty(horizon + 1), min_lo=np.empty(horizon + 1),
+               start_hi=np.empty(horizon + 1), start_lo=np.empty(horizon + 1),
+               path_hi=np.empty(horizon + 1, np.int32) if return_paths else None,
+               path_lo=np.empty(horizon + 1, np.int32) if return_paths else None)
+    opts = _capi.CostOpts(root_vertices=ptr(roots['vertices']), indptr=ptr(indptr),
+                          indices=ptr(indices), level=ptr(level), domain=ptr(dom),
+                          start=ptr(rows), w_hi=ptr(w_hi), w_lo=ptr(w_lo), n_leaf=n,
+                          n_edges=indices.size, n_level=level.size, n_domain=dom.size,
+                          n_start=rows.size, horizon=horizon, want_paths=int(bool(return_paths)))
+    lv = _capi.CostLeaves(**{k: ptr(a) for k, a in out.items()})
+    res = _capi.CostResult()
+    _check_cost(_capi.load().ehm_compiled_cost(law._handle, ctypes.byref(opts),
+                                               ctypes.byref(res), ctypes.byref(lv)))
+    k = np.arange(horizon + 1, dtype=np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        rate_hi, rate_lo = out['max_hi'] / k, out['min_lo'] / k
+    rate_hi[0] = rate_lo[0] = np.nan
+    best_k_hi = 1 + int(np.argmin(rate_hi[1:]))
+    best_k_lo = 1 + int(np.argmax(rate_lo[1:]))
+    return CostResult(
+        rate_hi=rate_hi, rate_lo=rate_lo, best_rate_hi=float(rate_hi[best_k_hi]),
+        best_k_hi=best_k_hi, best_rate_lo=float(rate_lo[best_k_lo]), best_k_lo=best_k_lo,
+        holds=False, horizon=horizon, n_domain=int(res.n_domain), n_start=int(res.n_start),
+        domain=dom, start=rows, seconds_weights=float(res.seconds_weights),
+        seconds_sweeps=float(res.seconds_sweeps), seconds_upload=float(res.seconds_upload),
+        _law=law, **out)
+
+
+def _core_cost(self, domain=None, start=None, X0=None, horizon=64, w_hi=None, w_lo=None,
+               return_paths=False):
+    """
+    What can the closed loop spend while it stays in ``domain``?  Certified bounds
+    of the summed input 2-norm over the relation this result holds (it must have been made with
+    ``return_edges=True``).  ``domain``: a bool mask or int rows, a set without a seed that the
+    relation does not leave (the core, a safe closure, every D_j and the limit set of ``reach``);
+    None: the core.  ``start``: a subset of it, or ``X0`` [n, p], located as ``reach`` locates it;
+    neither: the domain.  ``horizon``, ``w_hi``, ``w_lo``, ``return_paths`` as ``cost_relation``.
+    ``ValueError`` for both ``start`` and ``X0``, an empty set, a start outside the domain, a result
+    without edges and a closed law.  Returns a ``CostResult``; every statement holds under the
+    assumptions and exclusions of the core that made the relation.
+    """
+    law = getattr(self, '_law', None)
+    if self.indptr is None or self.indices is None:
+        raise ValueError('cost needs the relation: make the core with return_edges=True')
+    if start is not None and X0 is not None:
+        raise ValueError('give start or X0, not both')
+    if law is None or not getattr(law, '_handle', None):
+        raise ValueError('cost needs the compiled law the result was made for: the law is closed')
+    n_outside = 0
+    if X0 is not None:
+        X0 = np.ascontiguousarray(X0, dtype=np.float64)
+        u, leaf, _, _ = law.evaluate(X0, return_info=True)
+        ok = np.isfinite(u).all(axis=1)
+        n_outside = int((~ok).sum())
+        start = np.unique(np.searchsorted(law.leaf_node, leaf[ok])).astype(np.int32)
+    out = cost_relation(law, self.indptr, self.indices, self.level,
+                        self.core if domain is None else domain, start=start, horizon=horizon,
+                        w_hi=w_hi, w_lo=w_lo, return_paths=return_paths)
+    out.n_outside = n_outside
+    out.set_convex = bool(self.set_convex)
+    out.holds = bool(self.set_convex)
+    return out
+
+
+CoreResult.cost = _core_cost
+
+
+def _reach_cost(self, core, which='limit', **kw):
+    """``core.cost`` on a set this result found: ``which`` = ``'limit'`` (the limit set) or
+    ``'closure'``; the run must be safe (and, for the limit set, converged).  ``core``: the
+    ``CoreResult`` whose relation the reach was made over; the other arguments as
+    ``CoreResult.cost``."""
+    if which not in ('limit', 'closure'):
+        raise ValueError("which must be 'limit' or 'closure'")
+    if not self.safe:
+        raise ValueError('the run leaks: the closure holds a seed')
+    domain = self.limit if which == 'limit' else self.closure
+    if domain is None:
+        raise ValueError('no limit set: the run did not converge')
+    return core.cost(domain=domain, **kw)
+
+
+ReachResult.cost = _reach_cost

@@ -1353,6 +1353,73 @@ const char* ehm_reach_last_error(void);
 /* ehm_abi_sizes for ehm_reach_opts, ehm_reach_result, ehm_reach_leaves, in this order. */
 int ehm_reach_abi_sizes(int64_t* sizes, int32_t n);
 
+/* ---- certified fuel bounds of the closed loop (csrc/ehm_cost.hip) ----------------
+ * (no counterpart in the reference)
+ *
+ * Upper and lower bounds of the summed input 2-norm of every trajectory over k = 0 .. horizon steps,
+ * by a max-plus and a min-plus dynamic program over a relation between the first n_leaf leaf records
+ * of a law, given as for ehm_compiled_reach.  domain [n_domain] and start [n_start] are rows of the
+ * leaf records (a row named twice is one row); the start set lies in the domain.  The domain D holds
+ * no seed (level 0) and is closed under the relation; the device checks both and the call is
+ * refused with "row r is a seed" or "row r of the domain reaches leaf t outside it", r the smallest
+ * such row and t its smallest such target.
+ * Weights, per leaf of D, by the device unless w_hi and w_lo [n_leaf] are both given (then they are
+ * read on D, must be finite with w_lo <= w_hi there, and pad is 0): with u(v) the leaf's own map at
+ * the p + 1 vertices of its cell in the law's arithmetic (ehm_compiled_cells' ubar) and |.| the
+ * 2-norm as the rollout takes it (squares summed in ascending component order, sqrt, in double),
+ *   w_hi = max_v |u(v)| + pad,  w_lo = max(0, |g| - pad),  g_c = max(0, min_v u_c(v), -max_v u_c(v)),
+ *   pad = (2 p + n_u + 8) eps_T |R|,  R_c = |u0_c| + sum_j |K_cj| (max_v |v_j - v0_j| + x_j),
+ * eps_T = 2^-53 and x_j = 0 for a double law, eps_T = 2^-24 and x_j = max_v |v_j| for a single one
+ * (whose state is narrowed before the offset is taken).  A leaf of D without a cell is refused by
+ * name.
+ * Recurrence on D: U_0 = L_0 = 0; U_(k+1)(l) = w_hi[l] + max over t in row(l) of U_k(t);
+ * L_(k+1)(l) = w_lo[l] + min over the row of L_k(t); an empty row contributes 0.  The leaves'
+ * arrays are NaN outside D: w_hi, w_lo, pad, hi = U_horizon, lo = L_horizon.  max_hi, min_lo
+ * [horizon + 1]: over D for every k; start_hi, start_lo: over the start set.  With want_paths
+ * (horizon n_leaf 4 <= 2^28 bytes per direction): path_hi / path_lo int32 [horizon + 1] start at
+ * the smallest leaf of the start set that attains start_hi[horizon] / start_lo[horizon] and follow
+ * the smallest leaf that attains the max / min of each row, -1 after an empty row.
+ * seconds_weights, seconds_sweeps: device time; seconds_upload: wall time of checking, narrowing
+ * and uploading the relation.
+ * EHM_E_INVALID, before the device is touched: what ehm_compiled_reach refuses of a law and of a
+ * relation; n_u > 4; horizon < 1; an empty domain or start set, a row of either out of range, a
+ * start row outside the domain; only one of w_hi, w_lo; a weight on D that is not finite or
+ * w_lo > w_hi; the bytes of the paths.  Errors through ehm_cost_last_error. */
+typedef struct ehm_cost_opts {
+    const double*  root_vertices;   /* [n_roots][p+1][p], as for ehm_compiled_cells            */
+    const int64_t* indptr;          /* [n_leaf + 1]                                            */
+    const int32_t* indices;         /* [n_edges]                                               */
+    const int32_t* level;           /* [n_level]                                               */
+    const int32_t* domain;          /* [n_domain] rows of the leaf records                     */
+    const int32_t* start;           /* [n_start] rows of the leaf records                      */
+    const double*  w_hi;            /* [n_leaf] or NULL: both or neither                       */
+    const double*  w_lo;
+    int64_t n_leaf, n_edges, n_level, n_domain, n_start;
+    int32_t horizon, want_paths;
+} ehm_cost_opts;
+typedef struct ehm_cost_result {
+    int64_t n_domain, n_start;      /* distinct rows                                           */
+    double  seconds_weights, seconds_sweeps, seconds_upload;
+} ehm_cost_result;
+typedef struct ehm_cost_leaves {
+    double*  w_hi;                  /* [n_leaf]                                                */
+    double*  w_lo;
+    double*  pad;
+    double*  hi;
+    double*  lo;
+    double*  max_hi;                /* [horizon + 1]                                           */
+    double*  min_lo;
+    double*  start_hi;
+    double*  start_lo;
+    int32_t* path_hi;               /* [horizon + 1], with want_paths                          */
+    int32_t* path_lo;
+} ehm_cost_leaves;
+int ehm_compiled_cost(ehm_compiled* law, const ehm_cost_opts* opts, ehm_cost_result* result,
+                      const ehm_cost_leaves* leaves);
+const char* ehm_cost_last_error(void);
+/* ehm_abi_sizes for ehm_cost_opts, ehm_cost_result, ehm_cost_leaves, in this order. */
+int ehm_cost_abi_sizes(int64_t* sizes, int32_t n);
+
 /* ---- closed-loop simulation under the COMPILED law (csrc/ehm_compiled.hip) -------
  *
  * The entry points of the explicit law's rollout, argument for argument, on a compiled law -- also
