@@ -62,6 +62,7 @@ EXPORTED = [
     'ehm_compiled_cells', 'ehm_certify_last_error', 'ehm_compiled_certify',
     'ehm_certify_abi_sizes',
     'ehm_compiled_reduce', 'ehm_reduce_last_error',
+    'ehm_compiled_refine', 'ehm_refine_last_error',
     'ehm_compiled_successors', 'ehm_invariance_last_error', 'ehm_invariance_abi_sizes',
     'ehm_compiled_core', 'ehm_core_last_error', 'ehm_core_abi_sizes',
     'ehm_compiled_robust_successors', 'ehm_compiled_robust_core', 'ehm_robust_last_error',
@@ -76,6 +77,9 @@ EHM_COMPILE_SPINE_ROOTS = 1     # ehm_compiled_create_opts
 EHM_NARROW_FLUSH = 1            # ehm_compiled_narrow_opts
 EHM_REACH_MAPS = {'thread': 0, 'wave': 1}           # EHM_REACH_MAP_*
 EHM_CELL_MAX_DEPTH = 256        # ehm_compiled_cells: levels below a root a leaf's cell may lie
+EHM_REFINE_MAX_LEVELS = 16      # ehm_compiled_refine: levels of one call
+# EHM_REFINE_*: why a leaf of a refined law was not split further, by code
+EHM_REFINE_STOPS = ('unselected', 'satisfied', 'levels', 'no_cell', 'unseparated', 'too_deep')
 
 
 # every symbol include/ehm_search.h declares (host bookkeeping of the prefix searches)
@@ -447,6 +451,9 @@ def load(build_if_missing=True):
     lib.ehm_certify_last_error.restype = ctypes.c_char_p
     lib.ehm_compiled_reduce.argtypes = [vp, vp, vp, vp, ctypes.POINTER(vp), vp, vp, vp, vp]
     lib.ehm_reduce_last_error.restype = ctypes.c_char_p
+    lib.ehm_compiled_refine.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i64, ctypes.POINTER(vp),
+                                        vp, vp, vp, vp, vp]
+    lib.ehm_refine_last_error.restype = ctypes.c_char_p
     lib.ehm_compiled_successors.argtypes = [vp, ctypes.POINTER(InvarianceOpts),
                                             ctypes.POINTER(InvarianceResult),
                                             ctypes.POINTER(InvarianceLeaves)]
@@ -582,6 +589,7 @@ def load(build_if_missing=True):
                         'ehm_explicit_last_error', 'ehm_implicit_last_error',
                         'ehm_compiled_last_error', 'ehm_applied_last_error',
                         'ehm_certify_last_error', 'ehm_reduce_last_error',
+                        'ehm_refine_last_error',
                         'ehm_invariance_last_error', 'ehm_core_last_error',
                         'ehm_robust_last_error', 'ehm_reach_last_error',
                         'ehm_cost_last_error'):

@@ -8,7 +8,8 @@ Objects: ``ehm_capi.hip`` (C-ABI, host orchestration, generation-1 kernels),
 ``ehm_audit.hip`` (the sampled audit of the explicit law), ``ehm_applied.hip`` (the audit of a
 law by the cost of the input it applies), ``ehm_certify.hip`` (the leaf cells of a compiled law, the
 inputs at their vertices and the certificate leaf by leaf), ``ehm_reduce.hip`` (merging the leaves
-of a compiled law that apply one affine map), ``ehm_invariance.hip`` (the one-step successors of a
+of a compiled law that apply one affine map), ``ehm_refine.hip`` (splitting the leaves of a compiled
+law, its inverse), ``ehm_invariance.hip`` (the one-step successors of a
 compiled law's leaves), ``ehm_core.hip`` (the may-reach relation between the leaves and the
 invariant core), ``ehm_reach.hip`` (the reach tube and the limit set of that relation),
 ``ehm_cost.hip`` (certified fuel bounds of the closed loop over that relation),
@@ -153,6 +154,7 @@ def _objects():
             (os.path.join(OBJ_DIR, 'ehm_certify.o'), os.path.join(SRC_DIR, 'ehm_certify.hip'),
              []),
             (os.path.join(OBJ_DIR, 'ehm_reduce.o'), os.path.join(SRC_DIR, 'ehm_reduce.hip'), []),
+            (os.path.join(OBJ_DIR, 'ehm_refine.o'), os.path.join(SRC_DIR, 'ehm_refine.hip'), []),
             (os.path.join(OBJ_DIR, 'ehm_invariance.o'),
              os.path.join(SRC_DIR, 'ehm_invariance.hip'), []),
             (os.path.join(OBJ_DIR, 'ehm_core.o'), os.path.join(SRC_DIR, 'ehm_core.hip'), []),
@@ -206,7 +208,7 @@ def is_stale():
                       'ehm_explicit.hip', 'ehm_implicit.hip', 'ehm_audit.hip', 'ehm_applied.hip',
                       'ehm_certify.hip', 'ehm_reduce.hip', 'ehm_invariance.hip', 'ehm_compiled.hip',
                       'ehm_compiled32.hip', 'ehm_core.hip', 'ehm_robust.hip', 'ehm_reach.hip',
-                      'ehm_cost.hip')]
+                      'ehm_cost.hip', 'ehm_refine.hip')]
     return max([_dep_mtime()] + [os.path.getmtime(s)
                                  for s in srcs + SEARCH_DEPS + FRONTIER_DEPS]) > t
 

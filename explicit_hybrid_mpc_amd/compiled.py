@@ -66,6 +66,14 @@ costs of the vertex inputs (convexity of the fixed-commutation cost along the le
 merges the leaves that apply one affine map (csrc/ehm_reduce.hip): a new law of the
 same precision and file format whose input is within ``tol`` of this law's at every state of
 every cell of this law; ``small.reduction`` holds what it saved.
+
+    fine = law.refine(levels=2, leaves=mask)      # or max_diameter=, max_spread=
+
+goes the other way (csrc/ehm_refine.hip): the selected leaves are bisected as the
+partitioner would have bisected their cells and both children keep the parent's record verbatim, so
+the new law applies the same input bit for bit at every state while every leaf-by-leaf statement
+(``certify``, ``successors``, ``invariant_core``, ``reach``, ``cost``) is made on smaller cells;
+``fine.refinement`` holds what it did.
 """
 
 import ctypes
@@ -96,6 +104,7 @@ def leaf_stride32(p, n_u):
 
 _check = _capi.checker('ehm_compiled_last_error')
 _check_reduce = _capi.checker('ehm_reduce_last_error')
+_check_refine = _capi.checker('ehm_refine_last_error')
 
 
 def _shapes(h):
@@ -152,6 +161,57 @@ def check_leaf_mode(leaf_mode, n_leaf):
         raise _capi.EhmError(_capi.EHM_E_INVALID, 'compiled law: leaf_mode holds %d (a mode, or '
                              '-1 for none)' % int(a.min() if a.min() < -1 else a.max()))
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def refine_selection(n_leaf, levels, leaves):
+    """(levels int32 [n_leaf], selected uint8 [n_leaf]) of ``CompiledLaw.refine``'s ``levels`` (an
+    int or int [n_leaf], 0 .. 16) and ``leaves`` (None: all, a bool mask [n_leaf], or leaf ids);
+    ``EhmError`` (EHM_E_INVALID) for anything else.  Host only."""
+    lv = np.asarray(levels)
+    if lv.dtype.kind not in 'iu' or lv.ndim > 1 or (lv.ndim == 1 and lv.size != n_leaf):
+        raise _capi.EhmError(_capi.EHM_E_INVALID, 'refine: levels must be an integer or %d '
+                             'integers, not %s %s' % (n_leaf, lv.dtype, lv.shape))
+    if lv.size and (int(lv.min()) < 0 or int(lv.max()) > _capi.EHM_REFINE_MAX_LEVELS):
+        raise _capi.EhmError(_capi.EHM_E_INVALID, 'refine: levels must be 0 .. %d, not %d' % (
+            _capi.EHM_REFINE_MAX_LEVELS, int(lv.min() if lv.min() < 0 else lv.max())))
+    lv = np.ascontiguousarray(np.broadcast_to(lv, (n_leaf,)), dtype=np.int32)
+    if leaves is None:
+        return lv, np.ones(n_leaf, dtype=np.uint8)
+    sel = np.asarray(leaves)
+    if sel.dtype == np.bool_:
+        if sel.shape != (n_leaf,):
+            raise _capi.EhmError(_capi.EHM_E_INVALID, 'refine: a mask of %s for %d leaves' % (
+                sel.shape, n_leaf))
+        return lv, np.ascontiguousarray(sel, dtype=np.uint8)
+    if sel.ndim != 1 or (sel.size and sel.dtype.kind not in 'iu'):
+        raise _capi.EhmError(_capi.EHM_E_INVALID, 'refine: leaves must be a bool mask or leaf ids, '
+                             'not %s %s' % (sel.dtype, sel.shape))
+    if sel.size and (int(sel.min()) < 0 or int(sel.max()) >= n_leaf):
+        raise _capi.EhmError(_capi.EHM_E_INVALID, 'refine: leaf %d of %d leaves' % (
+            int(sel.min() if sel.min() < 0 else sel.max()), n_leaf))
+    mask = np.zeros(n_leaf, dtype=np.uint8)
+    mask[sel.astype(np.int64)] = 1
+    return lv, mask
+
+
+def refine_criteria(n_u, max_diameter, max_spread):
+    """(max_diameter float64 [1] or None, max_spread float64 [n_u] or None) of ``CompiledLaw.refine``;
+    ``EhmError`` (EHM_E_INVALID) for one that is negative or not finite.  Host only."""
+    out = []
+    for name, value, size in (('max_diameter', max_diameter, 1), ('max_spread', max_spread, n_u)):
+        if value is None:
+            out.append(None)
+            continue
+        a = np.asarray(value, dtype=np.float64)
+        if a.ndim > 1 or (a.ndim == 1 and (name == 'max_diameter' or a.size != size)):
+            raise ValueError('%s must be a scalar%s' % (
+                name, '' if name == 'max_diameter' else ' or [%d]' % size))
+        a = np.ascontiguousarray(np.broadcast_to(a, (size,)))
+        if not (np.isfinite(a).all() and (a >= 0.).all()):
+            raise _capi.EhmError(_capi.EHM_E_INVALID, 'refine: %s must be finite and >= 0, not '
+                                 '%s' % (name, a))
+        out.append(a)
+    return tuple(out)
 
 
 def read_file(path):
@@ -221,6 +281,7 @@ class CompiledLaw:
     _leaf_node = None
     flushed = None              # to_single(flush=True): the counts of the values set to zero
     reduction = None            # reduce(): what the reduction this law came from saved
+    refinement = None           # refine(): what the refinement this law came from did
     _root_cells = None          # audit: the roots as the sampler's cells (built on first use)
     _input_scale = None         # audit: the default input_tol
 
@@ -364,6 +425,93 @@ class CompiledLaw:
                              max_deviation=float(stats[0]), seconds=float(stats[1]))
         return (law, leaf_of) if return_map else law
 
+    def refine(self, levels=1, leaves=None, max_diameter=None, max_spread=None, max_leaves=None,
+               return_map=False):
+        """
+        The law with the cells of its leaves bisected, the inverse of ``reduce``: a new, independent
+        ``CompiledLaw`` of the same precision and file format (ehm_compiled_refine)
+        that applies the same input, bit for bit, at every state.  A leaf is split as the
+        partitioner would have split its cell (``cells``): along the first longest edge (i, j) in
+        ``tools.split_along_longest_edge``'s arithmetic and order, by the plane that is +1 at v_j,
+        -1 at v_i and 0 at the other vertices; the left child is the partitioner's S_1.  Both
+        children carry the parent's leaf record, ``leaf_node`` and ``leaf_mode`` byte for byte, and
+        a leaf record is anchored, so the audits and the certificate -- statements about the
+        function -- carry over; what changes is the cells every leaf-by-leaf statement is made on.
+        ``certify`` now tests smaller cells, and ``successors``, ``invariant_core``, the robust
+        forms, ``reach`` and ``cost`` have to be computed again on the refined law.  The left child
+        keeps the leaf's index, the right children and the new planes are appended in leaf order.
+
+        ``leaves``: None for all, a bool mask [n_leaf], or leaf ids.  ``levels``: an int or int
+        [n_leaf], 0 .. 16 passes over the leaves; both children of a split leaf inherit what is
+        left.  With no criterion every selected leaf is split ``levels`` times.  With
+        ``max_diameter`` (compared with the longest edge) or ``max_spread`` (a scalar or [n_u],
+        compared per input c with max_i u_c(v_i) - min_i u_c(v_i) of the leaf's own map at its
+        vertices, in the law's arithmetic) a leaf with levels left is split iff one of them is
+        exceeded on its own cell; a NaN never splits.  ``max_leaves`` (default 2^24): a call that
+        could make more leaves -- 2^levels per selected leaf -- is refused before anything is
+        allocated.  A plane that, as stored, fails the test ``cells`` applies (a sliver in a single
+        law) is not written: the leaf is kept whole and reported.
+
+        ``mpc``, the leaf modes and ``flushed`` carry over, ``reduction`` is None, ``refinement`` is
+        a dict of n_leaf_before, n_leaf_after, n_int_before, n_int_after, bytes_before,
+        bytes_after, passes, n_split, max_plane_residual (the largest distance of an accepted
+        plane's value at a vertex from +1, -1 or 0; measured, not gated), stops (final leaves by
+        stop code: ``_capi.EHM_REFINE_STOPS``), seconds and plan_seconds.  ``return_map=True``:
+        returns (law, origin, stop): origin int32 [n_leaf_after] the source leaf of every leaf, stop
+        int8 the code of every leaf -- unselected, satisfied (levels done without a criterion, or
+        every criterion met), levels (exhausted with a criterion exceeded), no_cell, unseparated,
+        too_deep (at depth 256: its children would have no cell).  ``levels`` = 0 returns an equal,
+        independent copy.  ``EhmError`` (EHM_E_INVALID) for a law with test nodes, ``levels``
+        outside 0 .. 16, ``leaves`` of the wrong length or out of range, a criterion that is
+        negative or not finite, a ``leaf_mode`` of the wrong length, ``max_leaves`` exceeded and
+        a closed law.
+        """
+        from . import applied
+        if not getattr(self, '_handle', None):
+            raise _capi.EhmError(_capi.EHM_E_INVALID, 'refine: the law is closed')
+        if self._h['n_test'] > 0:
+            raise _capi.EhmError(_capi.EHM_E_INVALID, 'the law has %d test nodes: its cells do not '
+                                 "follow from its planes -- compile(spine='roots') has none" %
+                                 self._h['n_test'])
+        n_leaf = self._h['n_leaf']
+        levels, selected = refine_selection(n_leaf, levels, leaves)
+        crit = refine_criteria(self.n_u, max_diameter, max_spread)
+        max_leaves = 1 << 24 if max_leaves is None else int(max_leaves)
+        worst = int((1 << levels.astype(np.int64))[selected != 0].sum() + (selected == 0).sum())
+        if max_leaves < 1 or worst > max_leaves:
+            raise _capi.EhmError(_capi.EHM_E_INVALID, 'refine: the call could make %d leaves, '
+                                 'max_leaves is %d' % (worst, max_leaves))
+        modes = None if self.leaf_mode is None else check_leaf_mode(self.leaf_mode, n_leaf)
+        if self._root_cells is None:
+            self._root_cells = applied.root_cells(self)
+        roots = self._root_cells['vertices']
+        handle = ctypes.c_void_p()
+        modes_out = None if modes is None else np.empty(worst, dtype=np.int32)
+        origin = np.empty(worst, dtype=np.int32)
+        stop = np.empty(worst, dtype=np.int8)
+        counts = np.zeros(12, dtype=np.int64)
+        stats = np.zeros(3)
+        rc = self._lib.ehm_compiled_refine(
+            self._handle, ptr(roots), ptr(levels), ptr(selected), ptr(crit[0]), ptr(crit[1]),
+            ptr(modes), max_leaves, worst, ctypes.byref(handle), ptr(modes_out), ptr(origin),
+            ptr(stop), ptr(counts), ptr(stats))
+        _check_refine(rc)
+        law = type(self)(handle, self.device, self.compile_seconds, dtype=self.dtype)
+        law.flushed = self.flushed
+        law.mpc = self.mpc
+        n_after = int(counts[1])
+        if modes is not None:
+            law.set_leaf_modes(modes_out[:n_after])
+        law.refinement = dict(
+            n_leaf_before=int(counts[0]), n_leaf_after=n_after, n_int_before=int(counts[2]),
+            n_int_after=int(counts[3]), bytes_before=self._bytes, bytes_after=law._bytes,
+            passes=int(counts[4]), n_split=int(counts[5]), max_plane_residual=float(stats[0]),
+            stops=dict(zip(_capi.EHM_REFINE_STOPS, (int(v) for v in counts[6:12]))),
+            seconds=float(stats[1]), plan_seconds=float(stats[2]))
+        if return_map:
+            return law, origin[:n_after].copy(), stop[:n_after].copy()
+        return law
+
     @classmethod
     def load(cls, path, device=0):
         """The law ``save`` wrote (one .npz of plain arrays): a single law where the file says
@@ -456,7 +604,8 @@ class CompiledLaw:
     # -- closed loop ---------------------------------------------------------------------------
     @property
     def leaf_node(self):
-        """int32 [n_leaf]: the source node id of every leaf (ascending)."""
+        """int32 [n_leaf]: the source node id of every leaf (ascending; in a refined law the
+        children of a split leaf share their parent's, so it is neither ascending nor unique)."""
         if self._leaf_node is None:
             out = np.zeros(self._h['n_leaf'], dtype=np.int32)
             self._export(None, None, ptr(out), None, None, None, None)

@@ -608,6 +608,9 @@ int ehm_compiled_adopt(const ehm_compiled* like, int64_t n_int, int64_t n_leaf, 
     std::memcpy(C->h, like->h, sizeof C->h);
     C->h[H_INT] = n_int;
     C->h[H_LEAF] = n_leaf;
+    // a refined law (ehm_refine.hip) has leaves that share a source node: the header's node count
+    // stays an upper bound of leaf_node and is never below the leaves (what an import asks)
+    C->h[H_SRC] = std::max(C->h[H_SRC], n_leaf);
     C->source_bytes = like->source_bytes;
     EHM_HIP_TRY(c_err, hipSetDevice(C->device));
     EHM_HIP_TRY(c_err, C->stream.create());

@@ -28,9 +28,10 @@ struct ehm_compiled_view {
 void ehm_compiled_get_view(const ehm_compiled* C, ehm_compiled_view* out);
 
 // A new law on the device of `like` with n_int internal and n_leaf leaf records of like's scalar
-// and strides (ehm_reduce.hip): it takes over the four buffers, copies like's root records and
+// and strides (ehm_reduce.hip, ehm_refine.hip): it takes over the four buffers, copies like's root records and
 // adjacency table, and is checked as ehm_compiled_import checks a file's arrays (on a host copy)
-// before it is returned.  Errors through ehm_compiled_last_error.
+// before it is returned; the header's source node count is raised to n_leaf where it was below
+// (the leaves of a refined law share source nodes).  Errors through ehm_compiled_last_error.
 int ehm_compiled_adopt(const ehm_compiled* like, int64_t n_int, int64_t n_leaf, DevBuf& node,
                        DevBuf& leaf_rec, DevBuf& leaf_node, DevBuf& root_entry,
                        ehm_compiled** out);

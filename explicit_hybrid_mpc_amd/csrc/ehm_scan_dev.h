@@ -1,6 +1,6 @@
 // The order-preserving exclusive scan of int32 on the device that ehm_reduce.hip (the compaction of
-// the survivors) and ehm_core.hip (the row offsets of the may-reach relation, 3.8i)
-// share: tiles of 1024, the tiles' totals scanned the same way.  Every translation unit that includes
+// the survivors), ehm_core.hip (the row offsets of the may-reach relation, 3.8i) and
+// ehm_refine.hip (the places of the appended records, 3.8n) share: tiles of 1024, the tiles' totals scanned the same way.  Every translation unit that includes
 // this gets its own copy (unnamed namespace), as of ehm_cells_dev.h.
 #pragma once
 

@@ -289,6 +289,19 @@ def _successors(law, st, leaves, return_successors):
         holds_on_set=bool(counts['invariant'] == n and every and st.set_convex), **arrays)
 
 
+def _leaf_rows(law, leaf):
+    """The rows of the leaf records with the source node ids ``leaf`` (what ``evaluate`` returns).
+    In a refined law (``CompiledLaw.refine``, also one loaded from its file) the children of a split
+    leaf share their source node, so a state does not name its leaf record this way: ``ValueError``."""
+    unique = getattr(law, '_leaf_node_ascending', None)
+    if unique is None:
+        unique = law._leaf_node_ascending = bool((np.diff(law.leaf_node) > 0).all())
+    if not unique:
+        raise ValueError('the leaves of a refined law share source nodes: a state does not name its '
+                         'leaf record; give leaf rows (start=, masks) instead of states')
+    return np.searchsorted(law.leaf_node, leaf)
+
+
 class CoreResult:
     """
     What ``CompiledLaw.invariant_core`` found.  Per leaf: ``level`` int32 (-1 for
@@ -324,7 +337,7 @@ class CoreResult:
         if getattr(self, '_law', None) is None or not getattr(self._law, '_handle', None):
             raise ValueError('contains needs the compiled law the result was made for, open')
         u, leaf, _, _ = self._law.evaluate(X, return_info=True)
-        row = np.searchsorted(self._law.leaf_node, leaf)
+        row = _leaf_rows(self._law, leaf)
         return self.core[row] & np.isfinite(u).all(axis=1)
 
 
@@ -451,7 +464,7 @@ class ReachResult:
         if getattr(self, '_law', None) is None or not getattr(self._law, '_handle', None):
             raise ValueError('contains needs the compiled law the result was made for, open')
         u, leaf, _, _ = self._law.evaluate(X, return_info=True)
-        row = np.searchsorted(self._law.leaf_node, leaf)
+        row = _leaf_rows(self._law, leaf)
         ok = np.isfinite(u).all(axis=1) & (row < self.limit.size)
         row = np.minimum(row, self.limit.size - 1)
         if k is None or int(k) >= self.settle:
@@ -612,7 +625,7 @@ def _core_reach(self, start=None, X0=None, horizon=0, max_sweeps=None, return_st
         u, leaf, _, _ = law.evaluate(X0, return_info=True)
         ok = np.isfinite(u).all(axis=1)
         n_outside = int((~ok).sum())
-        start = np.unique(np.searchsorted(law.leaf_node, leaf[ok])).astype(np.int32)
+        start = np.unique(_leaf_rows(law, leaf[ok])).astype(np.int32)
     elif start is None:
         start = self.core
     out = reach_relation(law, self.indptr, self.indices, self.level, start, horizon=horizon,
@@ -780,7 +793,7 @@ def _core_cost(self, domain=None, start=None, X0=None, horizon=64, w_hi=None, w_
         u, leaf, _, _ = law.evaluate(X0, return_info=True)
         ok = np.isfinite(u).all(axis=1)
         n_outside = int((~ok).sum())
-        start = np.unique(np.searchsorted(law.leaf_node, leaf[ok])).astype(np.int32)
+        start = np.unique(_leaf_rows(law, leaf[ok])).astype(np.int32)
     out = cost_relation(law, self.indptr, self.indices, self.level,
                         self.core if domain is None else domain, start=start, horizon=horizon,
                         w_hi=w_hi, w_lo=w_lo, return_paths=return_paths)

@@ -978,6 +978,56 @@ int ehm_compiled_reduce(ehm_compiled* law, const double* root_vertices, const do
                         int32_t* leaf_of, int64_t* counts, double* stats);
 const char* ehm_reduce_last_error(void);
 
+/* ---- splitting the leaves of a compiled law (csrc/ehm_refine.hip) -----------------
+ *
+ * The inverse of ehm_compiled_reduce: a new, independent law of the same precision and format whose
+ * selected leaves are bisected as the partitioner would have bisected their cells.  Both children of
+ * a split leaf keep its leaf record, leaf_node and leaf_mode byte for byte, and a leaf record is
+ * anchored (u = u_0 + K (x - v_0)), so the new law applies the same input, bit for bit, at every
+ * state; only the cells get smaller.
+ * One split: the cell as ehm_compiled_cells rebuilds it; its first longest edge (i, j), i < j, in
+ * ehm_split_batch's arithmetic and order; the plane s = a . x + b with s(v_j) = +1, s(v_i) = -1 and
+ * s = 0 at the other vertices from a p x p solve in double (rows v_k - v_i, k != i ascending; right-
+ * hand side 2 for k = j, else 1; partial pivoting, the first largest modulus on ties; b = -1 - a . v_i;
+ * one rounding per product and per sum), rounded to the law's scalar.  Left iff s >= -eps: the left
+ * child is the partitioner's S_1 (the midpoint replaces v_i), the right child S_2.  The stored plane,
+ * widened, must be finite (a single law: normal or zero) and at the cell's vertices pass the test of
+ * ehm_compiled_cells with its positive end at j and its negative end at i; else the leaf is kept
+ * whole (EHM_REFINE_UNSEPARATED).
+ * The left child keeps the leaf's index l; with offset[l] the number of split leaves before l, the
+ * right child is leaf n_leaf + offset[l] and the plane internal record n_int + offset[l]; the one
+ * reference that named ~l (a child slot or a root entry) names the new record.  root_rec and nbr are
+ * copied.  A level is one pass over the current leaves; a leaf's remaining levels go to both
+ * children, minus one; passes are made until one splits nothing.
+ * levels [n_leaf], each 0 .. EHM_REFINE_MAX_LEVELS; selected [n_leaf] (0 / 1) or NULL: all;
+ * max_diameter (one number) and max_spread [n_u], each NULL or finite and >= 0: with neither, a
+ * selected leaf is split while it has levels left; else only while one of them is exceeded on its own
+ * cell -- the longest edge > *max_diameter, or for an input c max_i u_c(v_i) - min_i u_c(v_i) >
+ * max_spread[c], the leaf map as ubar of ehm_compiled_cells; a NaN never splits.  root_vertices and
+ * leaf_mode as for ehm_compiled_reduce.  The call could make at most worst = sum over the leaves of
+ * 2^levels (selected) or 1 leaves: worst > max_leaves is refused before anything is allocated, and
+ * the per-leaf outputs, each of `capacity` >= worst elements or NULL, are leaf_mode_out (written only
+ * with leaf_mode), origin (the source leaf of every new leaf) and stop (EHM_REFINE_*, one per new
+ * leaf).  counts [12] = leaves before and after, internal records before and after, passes that
+ * split, leaves split, then the new leaves by stop code; stats [3] = the largest |s(v_k) - target_k|
+ * of an accepted plane (measured, not gated), seconds, seconds of the plan kernels on the device.
+ * EHM_E_INVALID for a law with test nodes, levels outside their range, a criterion that is negative
+ * or not finite, and max_leaves exceeded.  Errors through ehm_refine_last_error. */
+#define EHM_REFINE_MAX_LEVELS  16
+#define EHM_REFINE_UNSELECTED  0   /* the leaf was not selected                                    */
+#define EHM_REFINE_SATISFIED   1   /* levels done with no criterion, or every criterion met        */
+#define EHM_REFINE_LEVELS      2   /* levels exhausted with a criterion still exceeded             */
+#define EHM_REFINE_NO_CELL     3   /* the leaf has no cell                                         */
+#define EHM_REFINE_UNSEPARATED 4   /* the stored plane failed the acceptance test                  */
+#define EHM_REFINE_TOO_DEEP    5   /* at depth EHM_CELL_MAX_DEPTH: its children would have no cell */
+#define EHM_REFINE_STOPS       6
+int ehm_compiled_refine(ehm_compiled* law, const double* root_vertices, const int32_t* levels,
+                        const uint8_t* selected, const double* max_diameter,
+                        const double* max_spread, const int32_t* leaf_mode, int64_t max_leaves,
+                        int64_t capacity, ehm_compiled** out, int32_t* leaf_mode_out,
+                        int32_t* origin, int8_t* stop, int64_t* counts, double* stats);
+const char* ehm_refine_last_error(void);
+
 /* ---- one-step invariance leaf by leaf (csrc/ehm_invariance.hip) -------------------
  *
  * On a leaf the law is affine and in the leaf's step-0 mode the plant x+ = A_m x + B_m u + w_m + E d
